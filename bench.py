@@ -17,6 +17,7 @@ BASELINE.json metric: "basis subsets solved/sec (enum) + tableau-update GB/s vs 
               bounded sample, rank 0, N=1 only.
 
 Usage: python bench.py --gpus N --steps K --warmup W      (N>1: under torch.distributed.run)
+       [--dump-outputs DIR]   what the last timed step returned, one float64 DIR/<name>.npy per array
 """
 import argparse
 import json
@@ -30,7 +31,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0        # MI355X HBM3E 8.0 TB/s (spec)
 FP64_VECTOR_PEAK_TF = 78.6   # MI355X fp64 vector peak (spec)
 
 
@@ -53,7 +54,24 @@ def parse_args():
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes for `traffic` (the committed profile is used if its hash matches)")
     ap.add_argument("--batch", type=int, default=4096)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (objective, rank, counts, vertex x, "
+                         "basis) as float64 DIR/<name>.npy; the inputs are seeded, so runs compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the arrays a caller of the timed step receives, float64 (rank and counts are below 2**53,
+    so exact).  The torch.distributed form of the step returns no vertex: x and basis are then absent."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"obj": res["zstar"], "rank": res["rank"], "counts": res["counts"],
+              "x": res.get("x"), "basis": res.get("basis")}
+    for name, v in arrays.items():
+        if v is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64).reshape(-1))
 
 
 def kernel_source_hash():
@@ -667,7 +685,8 @@ def main():
         if use_c:
             # the whole drop-in solve(): pass 1, exchange, tie rule AND the winning vertex x (every step)
             r = ep.solve_sharded(c_comm, n - m, want_vertex=True)
-            return dict(feasible=r["status"] == 0, rank=r["rank"], counts=r["counts"], zstar=r["obj"], x=r["x"])
+            return dict(feasible=r["status"] == 0, rank=r["rank"], counts=r["counts"], zstar=r["obj"], x=r["x"],
+                        basis=r["basis"])
         return lpdist.enum_solve_sharded(comm, total, True, range_fn, first_fn, bounds=my_bounds)
 
     for _ in range(args.warmup):
@@ -686,6 +705,8 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = total * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     flops_per_subset = (2.0 / 3.0) * m ** 3 + 2.0 * m ** 2
     # kernel time of pass 1 on this rank's shard alone (outside the timed region)
     k_ms = float(ep.range(my_bounds[0], my_bounds[1], args.enum_algo)[3].kernel_ms) if my_bounds[1] > my_bounds[0] else 0.0

@@ -47,7 +47,10 @@ def _worker(rank, world, port, seed, m, n, maximize, out):
 @pytest.mark.parametrize("world", [2, 3])
 @pytest.mark.parametrize("maximize", [True, False])
 def test_sharded_enumeration_gloo(world, maximize):
-    import torch.multiprocessing as mp
+    # stdlib multiprocessing, not torch's: only the spawned workers import torch.  torch in the pytest
+    # process brings its own HIP runtime and RCCL, and the library's later dlopen("librccl.so.1") would
+    # then resolve to that RCCL, bound to a HIP runtime other than the library's (test_c_abi_rccl_communicator)
+    import multiprocessing as mp
     from oracle import pyoracle as o
     from tests import lpcases
     seed, m, n = 17, 5, 12
@@ -244,7 +247,7 @@ def _batched_worker(rank, world, port, batch, m, n, out):
 def test_batched_simplex_sharded_gloo(world):
     """world-size-2/3 gloo run of the batched driver: every LP solved exactly once, by the rank the
     convention names, with the answers of an unsharded run."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp   # not torch's: see test_sharded_enumeration_gloo
     from oracle import pyoracle as o
     from tests import lpcases
     batch, m, n = 11, 6, 14
