@@ -81,12 +81,9 @@ int lp_context_create(int device, void* stream, lp_context** ctx_out) {
     return LP_OPTIMAL;
 }
 
-static void enum_destroy(lp_enum_problem* p);   // (below: releases a kept enumeration shell)
-
 void lp_context_destroy(lp_context* ctx) {
     if (!ctx) return;
-    for (void* q : ctx->enum_shells) enum_destroy(static_cast<lp_enum_problem*>(q));
-    ctx->enum_shells.clear();
+    lp_enum_release_shells(ctx);
     for (auto& b : ctx->pool) (void)hipFree(b.first);
     for (auto& hb : ctx->bundles) {
         (void)hipHostFree(hb.pinned);
@@ -631,101 +628,8 @@ int lp_bench_rankj_update(lp_simplex_problem* p, int iters, float* ms_per_launch
 }
 
 // ===========================================================================
-// enumeration
+// diagnostics of the kernels' fast divisions (the enumeration's C ABI: enum_driver.hip)
 // ===========================================================================
-
-uint64_t lp_binom(int n, int k) { return lp_host_binom(n, k); }
-
-// Cost-balanced cut of the rank space (same rule as simplexmethod_amd/dist.py:
-// balanced_shard_bounds): cost(x) = x + kShardRecordCost * (depth m-7 tree nodes before subset x).
-static const uint64_t kShardRecordCost = 160;
-int lp_enum_shard_bounds(int n, int m, int shard, int shards, uint64_t* begin_out, uint64_t* end_out) {
-    if (!begin_out || !end_out || shards <= 0 || shard < 0 || shard >= shards) return LP_BAD_ARG;
-    if (m <= 0 || n < m || n > kEnumMaxN || m > kEnumMaxM) return LP_BAD_ARG;
-    const uint64_t total = lp_host_binom(n, m);
-    if (total == 0) return LP_BAD_ARG;
-    const int d0 = m - 7;
-    // (the cost model is that of the tuned kernels' box; the general kernel's shapes — m > 16 or
-    // n - m > 16 — small trees and the direct kernel get equal-size cuts)
-    const bool prefix_shape = m >= 7 && m <= 16 && n - m >= 2 && n - m <= 16;
-    if (shards == 1 || !prefix_shape || total < (1ULL << 20)) {
-        // (dist.py uses total * k // world here; same partition property, sizes differ by <= 1)
-        *begin_out = (uint64_t)((unsigned __int128)total * (unsigned)shard / (unsigned)shards);
-        *end_out = (uint64_t)((unsigned __int128)total * (unsigned)(shard + 1) / (unsigned)shards);
-        return LP_OPTIMAL;
-    }
-    auto cost = [&](uint64_t x) -> unsigned __int128 {
-        if (x >= total) return (unsigned __int128)total + (unsigned __int128)kShardRecordCost * lp_host_binom(n - 7, d0);
-        return (unsigned __int128)x + (unsigned __int128)kShardRecordCost * lp_host_prefix_rank(n, m, x, d0);
-    };
-    const unsigned __int128 full = cost(total);
-    auto cut = [&](int k) -> uint64_t {
-        if (k <= 0) return 0;
-        if (k >= shards) return total;
-        const unsigned __int128 target = full * (unsigned)k / (unsigned)shards;
-        uint64_t lo = 0, hi = total;
-        while (lo < hi) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (cost(mid) < target) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-    };
-    *begin_out = cut(shard);
-    *end_out = cut(shard + 1);
-    return LP_OPTIMAL;
-}
-
-// The feasible list of the shared-prefix path: rank, record index and score of each entry.
-static void enum_list_release(lp_enum_problem* p) {
-    PrefixDev& pd = p->prefix;
-    lp_pool_release(p->ctx, pd.list, sizeof(unsigned long long) * pd.list_cap);
-    lp_pool_release(p->ctx, pd.scores, sizeof(double) * pd.list_cap);
-    lp_pool_release(p->ctx, pd.list_rec, sizeof(int) * pd.list_cap);
-    pd.list = nullptr;
-    pd.scores = nullptr;
-    pd.list_rec = nullptr;
-    pd.list_cap = 0;
-}
-static hipError_t enum_list_alloc(lp_enum_problem* p, unsigned long long cap) {
-    PrefixDev& pd = p->prefix;
-    size_t got = 0;
-    hipError_t e = lp_pool_alloc(p->ctx, (void**)&pd.list, sizeof(unsigned long long) * cap, &got);
-    if (e == hipSuccess) e = lp_pool_alloc(p->ctx, (void**)&pd.scores, sizeof(double) * cap, &got);
-    if (e == hipSuccess) e = lp_pool_alloc(p->ctx, (void**)&pd.list_rec, sizeof(int) * cap, &got);
-    if (e != hipSuccess) {
-        // the sizes lp_pool_release is told must be those of the failed request
-        pd.list_cap = cap;
-        enum_list_release(p);
-        return e;
-    }
-    pd.list_cap = cap;
-    return hipSuccess;
-}
-
-static void enum_destroy(lp_enum_problem* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->ctx->device);
-    (void)hipFree(p->dA); (void)hipFree(p->db); (void)hipFree(p->dc); (void)hipFree(p->dbinom);
-    (void)hipFree(p->d_pass); (void)hipFree(p->dev.chunk_best);
-    (void)hipFree(p->dvx); (void)hipFree(p->dvi);
-    (void)hipFree(p->prefix.root_cursor);
-    enum_list_release(p);
-    lp_pool_release(p->ctx, p->prefix.dense_scores, sizeof(double) * p->prefix.dense_cap);
-    lp_pool_release(p->ctx, p->prefix.items, sizeof(int4) * (size_t)p->prefix.item_cap);
-    lp_pool_release(p->ctx, p->prefix.items2, sizeof(int4) * (size_t)p->prefix.item_cap2);
-    (void)hipFree(p->prefix.item_count);
-    if (p->h_item_count) (void)hipHostFree(p->h_item_count);
-    lp_pool_release(p->ctx, p->prefix_buf[0], p->prefix_buf_bytes[0]);
-    lp_pool_release(p->ctx, p->prefix_buf[1], p->prefix_buf_bytes[1]);
-    if (p->h_pass) (void)hipHostFree(p->h_pass);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    delete p;
-}
-
-// A freed problem keeps its allocations (all sized for the largest shape) in the context for the next
-// lp_enum_upload; beyond two kept shells it is really released.
-int lp_enum_exact_division(const lp_enum_problem* p) { return (p && p->exact_div) ? 1 : 0; }
 
 int lp_debug_reciprocal(lp_context* ctx, const double* x, int n, double* fast_out, double* plain_out) {
     if (!ctx || !x || !fast_out || !plain_out || n <= 0) return LP_BAD_ARG;
@@ -737,483 +641,6 @@ int lp_debug_division(lp_context* ctx, const double* num, const double* den, int
     if (!ctx || !num || !den || !fast_out || !plain_out || n <= 0) return LP_BAD_ARG;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     return lp_simplex_debug_division(ctx, num, den, n, fast_out, plain_out);
-}
-
-void lp_enum_free(lp_enum_problem* p) {
-    if (!p) return;
-    lp_context* ctx = p->ctx;
-    if (p->complete && ctx->enum_shells.size() < 2) {
-        (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-        ctx->enum_shells.push_back(p);
-        return;
-    }
-    enum_destroy(p);
-}
-
-int lp_enum_upload(lp_context* ctx, const double* A, int m, int n, const double* b,
-                   const double* c, int maximize, lp_enum_problem** problem_out) {
-    if (!ctx || !problem_out) return LP_BAD_ARG;
-    *problem_out = nullptr;
-    if (!A || !b || !c) LP_FAIL(ctx, LP_BAD_ARG, "null problem array");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "need 0 < m <= n");
-    if (n > kEnumMaxN || m > kEnumMaxM)
-        LP_FAIL(ctx, LP_BAD_ARG, "enumeration supports n <= 64 and m <= 32 (ranks must fit 64 bits)");
-    if (lp_host_binom(n, m) == 0) LP_FAIL(ctx, LP_BAD_ARG, "C(n,m) overflows 64 bits");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned long long want_cap = 1ULL << 22;
-    bool forced_cap = false;
-    if (const char* e = getenv("LP_ENUM_LIST_CAP")) {   // tests: force the sub-range path on small problems
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v >= 64 && v < want_cap) want_cap = v;
-        forced_cap = true;
-    } else if (const char* e2 = getenv("LP_ENUM_LIST_START")) {   // tests: a small first list that may grow
-        const unsigned long long v = strtoull(e2, nullptr, 10);
-        if (v >= 64 && v < want_cap) want_cap = v;
-    }
-    lp_enum_problem* p = nullptr;
-    while (!p && !ctx->enum_shells.empty()) {   // a kept shell: every allocation is already there
-        lp_enum_problem* q = static_cast<lp_enum_problem*>(ctx->enum_shells.back());
-        ctx->enum_shells.pop_back();
-        // (a list that grew for a degenerate problem is kept unless it is far larger than the default)
-        const bool fits = forced_cap ? q->prefix.list_cap == want_cap
-                                     : (q->prefix.list_cap >= want_cap && q->prefix.list_cap <= 64 * want_cap);
-        if (fits) p = q; else enum_destroy(q);
-    }
-    const bool fresh = p == nullptr;
-    if (fresh) {
-        p = new lp_enum_problem();
-        p->ctx = ctx;
-    } else {   // forget what the previous problem left behind
-        p->list_valid = p->spec_valid = p->pchunks_valid = false;
-        p->dense_active = p->dense_hint = false;
-        p->exact_div = false;
-        p->pchunks.clear();
-        p->shard_rank = p->shard_world = -1;
-        p->last_begin = p->last_end = p->last_per_chunk = 0;
-        p->last_chunks = 0;
-        p->last_algo = 0;
-        p->list_n = 0;
-    }
-    p->complete = false;
-    EnumDev& d = p->dev;
-    d.m = m;
-    d.n = n;
-    d.lda = n + 1;
-    d.rs = m > 16 ? ((m + 1) & ~1) : 16;   // row stride of the shared-prefix records (enum_tree.hpp: rec_rs)
-    d.pad0 = 0;
-    d.maximize = maximize ? 1 : 0;
-    p->chunk_cap = 1 << 17;
-    std::vector<double> Arow((size_t)m * d.lda, 0.0);
-    for (int j = 0; j < n; ++j)
-        for (int i = 0; i < m; ++i) Arow[(size_t)i * d.lda + j] = A[(size_t)j * m + i];
-    std::vector<unsigned long long> binom((size_t)(kEnumMaxN + 1) * kBinomK, 0ULL);
-    for (int i = 0; i <= kEnumMaxN; ++i)
-        for (int k = 0; k < kBinomK; ++k) binom[(size_t)i * kBinomK + k] = lp_host_binom(i, k);
-#define LP_TRY(expr)                        \
-    do {                                    \
-        hipError_t _e = (expr);             \
-        if (_e != hipSuccess) {             \
-            ctx->last_error = #expr;        \
-            lp_enum_free(p);                \
-            return -(int)_e;                \
-        }                                   \
-    } while (0)
-    hipStream_t s = ctx->stream;
-    if (fresh) {   // sized for the largest shape (m <= 32, n <= 64): a shell serves any later problem
-        LP_TRY(hipMalloc(&p->dA, sizeof(double) * (size_t)kEnumMaxM * (kEnumMaxN + 1)));
-        LP_TRY(hipMalloc(&p->db, sizeof(double) * (size_t)kEnumMaxM));
-        LP_TRY(hipMalloc(&p->dc, sizeof(double) * (size_t)kEnumMaxN));
-        LP_TRY(hipMalloc(&p->dbinom, sizeof(unsigned long long) * binom.size()));
-        LP_TRY(hipMalloc(&p->d_pass, sizeof(EnumPassBlock)));
-        d.result = &p->d_pass->result;
-        LP_TRY(hipMalloc(&d.chunk_best, sizeof(double) * (size_t)(p->chunk_cap + 64)));
-        LP_TRY(hipMalloc(&p->dvx, sizeof(double) * (kEnumMaxM + 1)));
-        LP_TRY(hipMalloc(&p->dvi, sizeof(int) * (kEnumMaxM + 1)));
-        LP_TRY(hipHostMalloc(&p->h_pass, sizeof(EnumPassBlock)));
-        std::memset(p->h_pass, 0, sizeof(EnumPassBlock));
-        p->h_result = &p->h_pass->result;
-        p->h_list_count = &p->h_pass->list_count;
-        p->h_overflow = &p->h_pass->overflow;
-        p->h_level_counts = p->h_pass->level_counts;
-        LP_TRY(hipEventCreate(&p->ev0));
-        LP_TRY(hipEventCreate(&p->ev1));
-        LP_TRY(hipMemcpyAsync(p->dbinom, binom.data(), sizeof(unsigned long long) * binom.size(),
-                              hipMemcpyHostToDevice, s));
-    }
-    LP_TRY(hipMemcpyAsync(p->dA, Arow.data(), sizeof(double) * Arow.size(), hipMemcpyHostToDevice, s));
-    LP_TRY(hipMemcpyAsync(p->db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-    LP_TRY(hipMemcpyAsync(p->dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    if (fresh) {   // shared-prefix path: small control words, the feasible list
-        PrefixDev& pd = p->prefix;
-        pd.level_counts = p->d_pass->level_counts;
-        LP_TRY(hipMalloc(&pd.item_count, 2 * sizeof(int)));
-        LP_TRY(hipHostMalloc(&p->h_item_count, sizeof(int)));
-        pd.overflow = &p->d_pass->overflow;
-        LP_TRY(hipMalloc(&pd.root_cursor, 2 * sizeof(int)));
-        LP_TRY(enum_list_alloc(p, want_cap));
-        pd.list_count = &p->d_pass->list_count;
-        if (!ctx->dcomb6 || !ctx->dcomb5 || !ctx->dcomb4) {   // (shape-independent: once per context)
-            // leaf kernel: every 6-subset of R <= 22 columns in lexicographic order, 5 bits per index
-            std::vector<unsigned> comb6(32, 0u);
-            for (int R = 6; R <= 22; ++R) {
-                comb6[(size_t)R] = (unsigned)comb6.size();
-                int s6[6] = {0, 1, 2, 3, 4, 5};
-                for (;;) {
-                    unsigned pk = 0;
-                    for (int t = 0; t < 6; ++t) pk |= (unsigned)s6[t] << (5 * t);
-                    comb6.push_back(pk);
-                    int t = 5;
-                    while (t >= 0 && s6[t] == R - 6 + t) --t;
-                    if (t < 0) break;
-                    ++s6[t];
-                    for (int u = t + 1; u < 6; ++u) s6[u] = s6[u - 1] + 1;
-                }
-            }
-            LP_TRY(hipMalloc(&ctx->dcomb6, sizeof(unsigned) * comb6.size()));
-            LP_TRY(hipMemcpyAsync(ctx->dcomb6, comb6.data(), sizeof(unsigned) * comb6.size(), hipMemcpyHostToDevice, s));
-            // second level of the leaf kernel: every 5-subset of R <= 21 columns, same packing
-            std::vector<unsigned> comb5(32, 0u);
-            for (int R = 5; R <= 21; ++R) {
-                comb5[(size_t)R] = (unsigned)comb5.size();
-                int s5[5] = {0, 1, 2, 3, 4};
-                for (;;) {
-                    unsigned pk = 0;
-                    for (int t = 0; t < 5; ++t) pk |= (unsigned)s5[t] << (5 * t);
-                    comb5.push_back(pk);
-                    int t = 4;
-                    while (t >= 0 && s5[t] == R - 5 + t) --t;
-                    if (t < 0) break;
-                    ++s5[t];
-                    for (int u = t + 1; u < 5; ++u) s5[u] = s5[u - 1] + 1;
-                }
-            }
-            LP_TRY(hipMalloc(&ctx->dcomb5, sizeof(unsigned) * comb5.size()));
-            LP_TRY(hipMemcpyAsync(ctx->dcomb5, comb5.data(), sizeof(unsigned) * comb5.size(), hipMemcpyHostToDevice, s));
-            // third level: every 4-subset of R <= 20 columns
-            std::vector<unsigned> comb4(32, 0u);
-            for (int R = 4; R <= 20; ++R) {
-                comb4[(size_t)R] = (unsigned)comb4.size();
-                int s4[4] = {0, 1, 2, 3};
-                for (;;) {
-                    unsigned pk = 0;
-                    for (int t = 0; t < 4; ++t) pk |= (unsigned)s4[t] << (5 * t);
-                    comb4.push_back(pk);
-                    int t = 3;
-                    while (t >= 0 && s4[t] == R - 4 + t) --t;
-                    if (t < 0) break;
-                    ++s4[t];
-                    for (int u = t + 1; u < 4; ++u) s4[u] = s4[u - 1] + 1;
-                }
-            }
-            LP_TRY(hipMalloc(&ctx->dcomb4, sizeof(unsigned) * comb4.size()));
-            LP_TRY(hipMemcpyAsync(ctx->dcomb4, comb4.data(), sizeof(unsigned) * comb4.size(), hipMemcpyHostToDevice, s));
-            LP_TRY(hipStreamSynchronize(s));  // comb6 / comb5 / comb4 are locals
-        }
-        pd.comb6 = ctx->dcomb6;
-        pd.comb5 = ctx->dcomb5;
-        pd.comb4 = ctx->dcomb4;
-    }
-    LP_TRY(hipStreamSynchronize(s));
-#undef LP_TRY
-    d.A = p->dA;
-    d.b = p->db;
-    d.c = p->dc;
-    d.binom = p->dbinom;
-    p->complete = true;
-    *problem_out = p;
-    return LP_OPTIMAL;
-}
-
-static int check_range(lp_enum_problem* p, uint64_t begin, uint64_t end) {
-    const uint64_t total = lp_host_binom(p->dev.n, p->dev.m);
-    if (begin > end || end > total) LP_FAIL(p->ctx, LP_BAD_ARG, "rank range outside [0, C(n,m)]");
-    return LP_OPTIMAL;
-}
-
-// Makes the feasible list hold `nfeas` entries (20 bytes each) if the device has the memory.
-static bool enum_list_grow(lp_enum_problem* p, uint64_t nfeas) {
-    if (getenv("LP_ENUM_LIST_CAP")) return false;   // tests pin the list to exercise the sub-range path
-    const unsigned long long old_cap = p->prefix.list_cap;
-    const unsigned long long want = nfeas + nfeas / 16 + 4096;
-    if (want <= old_cap) return false;
-    (void)hipSetDevice(p->ctx->device);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    if ((size_t)want * 20 + (size_t(2) << 30) > free_b) return false;
-    enum_list_release(p);
-    if (enum_list_alloc(p, want) == hipSuccess) return true;
-    (void)hipGetLastError();
-    if (enum_list_alloc(p, old_cap) != hipSuccess) p->complete = false;   // (cannot happen: it was just released)
-    return false;
-}
-
-// One shared-prefix pass over [begin, end).  A list that overflows (a degenerate LP: up to every
-// non-singular basis is feasible) either gives way to the dense form (a large part of the range
-// feasible) or is re-allocated for the count the pass reported, if the device has the memory, and the
-// pass runs once more.
-static int enum_prefix_pass(lp_enum_problem* p, uint64_t begin, uint64_t end, double* score, uint64_t counts[3],
-                            lp_enum_stats* stats) {
-    const bool pinned = getenv("LP_ENUM_LIST_CAP") != nullptr;   // tests pin the list to exercise the sub-range path
-    const bool may_dense = p->dev.m >= 7 && !pinned;
-    auto again = [&](bool dense) {   // one more pass, times and launches added up
-        lp_enum_stats first{};
-        if (stats) first = *stats;
-        const int rc = lp_enum_prefix_range(p, begin, end, score, counts, stats, dense);
-        if (stats) {
-            stats->kernel_ms += first.kernel_ms;
-            stats->launches += first.launches;
-        }
-        return rc;
-    };
-    int rc = lp_enum_prefix_range(p, begin, end, score, counts, stats, p->dense_hint && may_dense);
-    if (p->dense_active) {
-        if (rc == LP_OPTIMAL && counts[0] * 8 < end - begin) p->dense_hint = false;   // not that degenerate after all
-        return rc;
-    }
-    if (rc == kEnumListOverflow && may_dense &&
-        (*p->h_list_count > p->prefix.list_abort || *p->h_list_count * 3 > end - begin)) {
-        // more than a third of the range is feasible (the pass reported the count), or the pass stopped
-        // early on a list 16x over capacity: the dense form — no list, every subset's score by rank —
-        // and later passes of this problem start there
-        p->dense_hint = true;
-        rc = again(true);
-        if (p->dense_active) return rc;
-    }
-    if (rc == kEnumListOverflow && enum_list_grow(p, *p->h_list_count)) rc = again(false);
-    return rc;
-}
-
-// Shared-prefix enumeration of a range in sub-ranges: because its depth m-7 nodes do not fit the level
-// buffers (large shapes: C(n-7, m-7) records), or because its feasible subsets overflow a list that
-// cannot grow.  A sub-range that still does not fit is split again.  Counts add, the best score is
-// the maximum; every sub-range keeps its best score for pass 2.
-static int enum_prefix_chunked(lp_enum_problem* p, uint64_t begin, uint64_t end, uint64_t parts0,
-                               double* score_best, uint64_t counts[3], lp_enum_stats* stats) {
-    p->pchunks.clear();
-    p->pchunks_valid = false;
-    struct Part { uint64_t b, e; };
-    std::vector<Part> todo;
-    auto split = [&](uint64_t b, uint64_t e, uint64_t parts) {   // pushes in DEscending order (stack)
-        if (parts < 2) parts = 2;
-        if (parts > e - b) parts = e - b;
-        for (uint64_t k = parts; k-- > 0;) {
-            const uint64_t pb = b + (e - b) / parts * k + std::min<uint64_t>(k, (e - b) % parts);
-            const uint64_t pe = b + (e - b) / parts * (k + 1) + std::min<uint64_t>(k + 1, (e - b) % parts);
-            todo.push_back({pb, pe});
-        }
-    };
-    split(begin, end, parts0);
-    double best = -INFINITY;
-    float ms = 0.f;
-    int launches = 0;
-    for (int k = 0; k < 3; ++k) counts[k] = 0;
-    while (!todo.empty()) {
-        const Part part = todo.back();
-        todo.pop_back();
-        double sc = -INFINITY;
-        uint64_t cn[3] = {0, 0, 0};
-        lp_enum_stats st{};
-        int rc = enum_prefix_pass(p, part.b, part.e, &sc, cn, &st);
-        if (rc == kEnumListOverflow && part.e - part.b > 1 && *p->h_list_count * 2 <= part.e - part.b) {
-            split(part.b, part.e, *p->h_list_count / (p->prefix.list_cap / 2) + 1);
-            continue;
-        }
-        if (rc == kEnumRangeTooWide && part.e - part.b > 1) {
-            split(part.b, part.e, p->split_hint + 1);
-            continue;
-        }
-        bool direct = false;
-        if (rc == LP_ITER_LIMIT || rc == kEnumListOverflow || rc == kEnumRangeTooWide) {   // no memory for the level buffers
-            rc = lp_enum_direct_range(p, part.b, part.e, &sc, cn, &st);
-            direct = true;
-        }
-        if (rc) return rc;
-        p->pchunks.push_back({part.b, part.e, sc, direct});
-        if (sc > best) best = sc;
-        for (int k = 0; k < 3; ++k) counts[k] += cn[k];
-        ms += st.kernel_ms;
-        launches += st.launches;
-    }
-    p->list_valid = false;
-    p->spec_valid = false;
-    p->pchunks_valid = true;
-    p->pchunks_begin = begin;
-    p->pchunks_end = end;
-    *score_best = best;
-    if (stats) {
-        stats->kernel_ms = ms;
-        stats->subsets = end - begin;
-        stats->launches = launches;
-    }
-    return LP_OPTIMAL;
-}
-
-int lp_enum_range(lp_enum_problem* p, uint64_t rank_begin, uint64_t rank_end, int algo,
-                  double* zbest_out, uint64_t* counts_out, lp_enum_stats* stats_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = check_range(p, rank_begin, rank_end);
-    if (rc) return rc;
-    double score = -INFINITY;
-    uint64_t counts[3] = {0, 0, 0};
-    p->list_valid = false;
-    p->spec_valid = false;
-    p->pchunks_valid = false;
-    if (algo != LP_ENUM_ALGO_AUTO && algo != LP_ENUM_ALGO_DIRECT && algo != LP_ENUM_ALGO_PREFIX)
-        LP_FAIL(ctx, LP_BAD_ARG, "unknown enumeration algorithm id");
-    if (rank_begin == rank_end) {   // an empty shard (more processes than subsets): nothing to launch
-        if (zbest_out) *zbest_out = p->dev.maximize ? -INFINITY : INFINITY;
-        if (counts_out)
-            for (int k = 0; k < 3; ++k) counts_out[k] = 0;
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        return LP_INFEASIBLE;
-    }
-    if (algo == LP_ENUM_ALGO_AUTO) {
-        // the shared-prefix path pays for its breadth-first levels (0.13-0.25 ms of launches) from ~2^15
-        // subsets on; with 32-row records (m > 16) from the start — the direct kernel's 32-lane form is
-        // five times slower per subset than its 16-lane form (scripts/enum_threshold.py)
-        const int shape = lp_enum_prefix_shape(p);
-        const uint64_t least = shape == 3 ? (1ULL << 8) : (1ULL << 15);
-        algo = (shape != 0 && rank_end - rank_begin >= least) ? LP_ENUM_ALGO_PREFIX : LP_ENUM_ALGO_DIRECT;
-    }
-    switch (algo) {
-        case LP_ENUM_ALGO_PREFIX:
-            if (!lp_enum_prefix_supported(p))
-                LP_FAIL(ctx, LP_BAD_ARG, "shared-prefix enumeration needs 6 <= m <= 32 and n-m >= 2 (m >= 7 beyond 16 x 16; n-m <= 32 for m > 16)");
-            rc = enum_prefix_pass(p, rank_begin, rank_end, &score, counts, stats_out);
-            if (rc == kEnumRangeTooWide) {
-                // more depth m-7 nodes than the level buffers hold: sub-ranges, a quarter over the
-                // exact ratio (equal rank counts do not hold equal node counts)
-                rc = enum_prefix_chunked(p, rank_begin, rank_end, p->split_hint + p->split_hint / 4 + 1, &score, counts,
-                                         stats_out);
-            } else if (rc == kEnumListOverflow) {
-                // no memory for a list that long (or LP_ENUM_LIST_CAP pins its size).  Without the list
-                // every feasible subset would be solved again from scratch for its objective, so once
-                // more than half of the range is feasible the shared prefixes save nothing: that range
-                // goes to the direct kernel as a whole; otherwise it is enumerated in sub-ranges, one
-                // list at a time.
-                if (*p->h_list_count * 2 > rank_end - rank_begin)
-                    rc = LP_ITER_LIMIT;
-                else
-                    rc = enum_prefix_chunked(p, rank_begin, rank_end, *p->h_list_count / (p->prefix.list_cap / 2) + 1,
-                                             &score, counts, stats_out);
-            }
-            if (rc != LP_ITER_LIMIT) break;
-            // no memory for the level buffers of this problem: direct path
-            [[fallthrough]];
-        case LP_ENUM_ALGO_DIRECT:
-            rc = lp_enum_direct_range(p, rank_begin, rank_end, &score, counts, stats_out);
-            break;
-        default:
-            LP_FAIL(ctx, LP_BAD_ARG, "unknown enumeration algorithm id");
-    }
-    if (rc) return rc;
-    if (zbest_out) *zbest_out = p->dev.maximize ? score : -score;
-    if (counts_out)
-        for (int k = 0; k < 3; ++k) counts_out[k] = counts[k];
-    return counts[0] ? LP_OPTIMAL : LP_INFEASIBLE;
-}
-
-int lp_enum_first_within(lp_enum_problem* p, uint64_t rank_begin, uint64_t rank_end, double zstar,
-                         double tol, uint64_t* rank_out) {
-    if (!p || !rank_out) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = check_range(p, rank_begin, rank_end);
-    if (rc) return rc;
-    const double star = p->dev.maximize ? zstar : -zstar;
-    if (p->list_valid && p->list_begin == rank_begin && p->list_end == rank_end) {
-        if (p->spec_valid && star == p->spec_star && tol == p->spec_tol) {
-            *rank_out = p->spec_first;  // already applied on the device by the range pass
-            return LP_OPTIMAL;
-        }
-        return lp_enum_list_first(p, star, tol, rank_out);  // every feasible subset is listed
-    }
-    if (p->pchunks_valid && p->pchunks_begin == rank_begin && p->pchunks_end == rank_end) {
-        // the range was enumerated in sub-ranges (ascending): the first one that holds a qualifying
-        // subset is re-run to rebuild its list; the others are skipped on their best score
-        const std::vector<lp_enum_problem::PrefixChunk> chunks = p->pchunks;
-        *rank_out = UINT64_MAX;
-        for (const auto& ch : chunks) {
-            if (!(ch.best >= star - tol)) continue;
-            uint64_t first = UINT64_MAX;
-            if (ch.direct) {
-                rc = lp_enum_direct_first(p, ch.begin, ch.end, star, tol, &first);
-            } else {
-                double sc;
-                uint64_t cn[3];
-                rc = enum_prefix_pass(p, ch.begin, ch.end, &sc, cn, nullptr);
-                if (rc == LP_OPTIMAL) rc = lp_enum_list_first(p, star, tol, &first);
-                else if (rc == LP_ITER_LIMIT || rc == kEnumListOverflow || rc == kEnumRangeTooWide)
-                    rc = lp_enum_direct_first(p, ch.begin, ch.end, star, tol, &first);
-            }
-            if (rc) return rc;
-            if (first != UINT64_MAX) {
-                *rank_out = first;
-                break;
-            }
-        }
-        p->pchunks = chunks;   // (the re-runs do not disturb the record of the range pass)
-        p->pchunks_valid = true;
-        p->pchunks_begin = rank_begin;
-        p->pchunks_end = rank_end;
-        return LP_OPTIMAL;
-    }
-    return lp_enum_direct_first(p, rank_begin, rank_end, star, tol, rank_out);
-}
-
-int lp_enum_vertex(lp_enum_problem* p, uint64_t rank, int n_orig, double* x_out, int* basis_out,
-                   double* obj_out, int* verdict_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const EnumDev& d = p->dev;
-    if (rank >= lp_host_binom(d.n, d.m)) LP_FAIL(ctx, LP_BAD_ARG, "rank >= C(n,m)");
-    if (n_orig <= 0 || n_orig > d.n) LP_FAIL(ctx, LP_BAD_ARG, "bad original variable count");
-    double xB[kEnumMaxM], z;
-    int S[kEnumMaxM], verdict;
-    int rc = lp_enum_direct_vertex(p, rank, xB, S, &z, &verdict);
-    if (rc) return rc;
-    if (x_out) {
-        for (int j = 0; j < n_orig; ++j) x_out[j] = 0.0;
-        for (int t = 0; t < d.m; ++t)
-            if (S[t] < n_orig) x_out[S[t]] = xB[t];
-    }
-    if (basis_out)
-        for (int t = 0; t < d.m; ++t) basis_out[t] = S[t];
-    if (obj_out) *obj_out = z;
-    if (verdict_out) *verdict_out = verdict;
-    return LP_OPTIMAL;
-}
-
-int lp_enum_solve(lp_context* ctx, const double* A, int m, int n, const double* b,
-                  const double* c, int maximize, int n_orig, double* x_out, int* basis_out,
-                  uint64_t* rank_out, double* obj_out, uint64_t* counts_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, "bad original variable count");
-    lp_enum_problem* p = nullptr;
-    int rc = lp_enum_upload(ctx, A, m, n, b, c, maximize, &p);
-    if (rc) return rc;
-    const uint64_t total = lp_host_binom(n, m);
-    double zstar = 0.0;
-    rc = lp_enum_range(p, 0, total, LP_ENUM_ALGO_AUTO, &zstar, counts_out, nullptr);
-    if (rc == LP_OPTIMAL) {
-        uint64_t rank = UINT64_MAX;
-        rc = lp_enum_first_within(p, 0, total, zstar, 1e-9, &rank);
-        if (rc == LP_OPTIMAL && rank == UINT64_MAX) {
-            ctx->last_error = "pass 2 found no rank within tolerance of the pass-1 optimum";
-            rc = LP_INFEASIBLE;
-        }
-        if (rc == LP_OPTIMAL) {
-            int verdict = 0;
-            rc = lp_enum_vertex(p, rank, n_orig, x_out, basis_out, obj_out, &verdict);
-            if (rank_out) *rank_out = rank;
-        }
-    }
-    lp_enum_free(p);
-    return rc;
 }
 
 // ===========================================================================

@@ -437,10 +437,7 @@ int lp_enum_direct_range(lp_enum_problem* p, uint64_t begin, uint64_t end, doubl
     if (rc) return rc;
     float ms = 0.f;
     LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    p->last_begin = begin;
-    p->last_end = end;
-    p->last_per_chunk = per_chunk;
-    p->last_chunks = chunks;
+    p->last_direct = {begin, end, per_chunk, chunks};
     *score_best = lp_key_f64(p->h_result->best_key);
     for (int k = 0; k < 3; ++k) counts[k] = p->h_result->counts[k];
     if (stats) {
@@ -457,17 +454,18 @@ int lp_enum_direct_first(lp_enum_problem* p, uint64_t begin, uint64_t end, doubl
     *rank_out = UINT64_MAX;
     if (end <= begin) return LP_OPTIMAL;
     // Narrow to the first chunk of the cached pass 1 whose best score qualifies.
-    if (begin == p->last_begin && end == p->last_end && p->last_chunks > 0) {
-        p->h_chunk_best.resize((size_t)p->last_chunks);
+    const lp_enum_problem::DirectLaunch& last = p->last_direct;
+    if (begin == last.begin && end == last.end && last.chunks > 0) {
+        p->h_chunk_best.resize((size_t)last.chunks);
         LP_HIP(ctx, hipMemcpyAsync(p->h_chunk_best.data(), p->dev.chunk_best,
-                                   sizeof(double) * (size_t)p->last_chunks, hipMemcpyDeviceToHost,
+                                   sizeof(double) * (size_t)last.chunks, hipMemcpyDeviceToHost,
                                    ctx->stream));
         LP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         int g = 0;
-        while (g < p->last_chunks && !(p->h_chunk_best[(size_t)g] >= score_star - tol)) ++g;
-        if (g == p->last_chunks) return LP_OPTIMAL;
-        const uint64_t nb = begin + (uint64_t)g * p->last_per_chunk;
-        uint64_t ne = nb + p->last_per_chunk;
+        while (g < last.chunks && !(p->h_chunk_best[(size_t)g] >= score_star - tol)) ++g;
+        if (g == last.chunks) return LP_OPTIMAL;
+        const uint64_t nb = begin + (uint64_t)g * last.per_chunk;
+        uint64_t ne = nb + last.per_chunk;
         if (ne > end) ne = end;
         begin = nb;
         end = ne;
@@ -539,21 +537,21 @@ int lp_enum_queue_dense_tail(lp_enum_problem* p, double tol, uint64_t begin, uin
     return LP_OPTIMAL;
 }
 
-int lp_enum_list_first(lp_enum_problem* p, double score_star, double tol, uint64_t* rank_out) {
+int lp_enum_list_first(lp_enum_problem* p, const EnumList& list, double score_star, double tol, uint64_t* rank_out) {
     lp_context* ctx = p->ctx;
     *rank_out = UINT64_MAX;
-    if (p->list_n == 0) return LP_OPTIMAL;
+    if (list.n == 0) return LP_OPTIMAL;
     int rc = reset_result(p);
     if (rc) return rc;
-    const uint64_t entries = p->dense_active ? p->list_end - p->list_begin : p->list_n;
+    const uint64_t entries = list.dense ? list.end - list.begin : list.n;
     const unsigned grid = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>(entries, 256), 1024);
-    if (p->dense_active)
+    if (list.dense)
         hipLaunchKernelGGL(k_enum_list_first, grid, 256, 0, ctx->stream, p->dev, (const unsigned long long*)nullptr,
-                           (unsigned long long)(p->list_end - p->list_begin), (const unsigned long long*)nullptr, 0ULL,
-                           p->prefix.dense_scores, score_star, tol, (unsigned long long)p->list_begin, 0);
+                           (unsigned long long)(list.end - list.begin), (const unsigned long long*)nullptr, 0ULL,
+                           p->prefix.dense_scores, score_star, tol, (unsigned long long)list.begin, 0);
     else
         hipLaunchKernelGGL(k_enum_list_first, grid, 256, 0, ctx->stream, p->dev, p->prefix.list,
-                           (unsigned long long)p->list_n, (const unsigned long long*)nullptr, 0ULL, p->prefix.scores,
+                           (unsigned long long)list.n, (const unsigned long long*)nullptr, 0ULL, p->prefix.scores,
                            score_star, tol, 0ULL, 0);
     rc = fetch_result(p);
     if (rc) return rc;

@@ -1,6 +1,6 @@
 // enum_leaf.hip — leaf kernels of the shared-prefix enumeration: ONE LANE PER SUBSET.
 //
-// Input: the depth m-7 records produced breadth-first by k_enum_expand (enum_prefix.hip): the
+// Input: the depth m-7 records produced breadth-first by the level kernels of enum_prefix.hip: the
 // tableau [W[:, c > last] | rhs] after the first m-7 Gauss-Jordan steps, shared by every subset
 // with that prefix.
 //
@@ -362,7 +362,7 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
 
 // FAST: the leaf kernels' hot form.  A subset whose pivots leave recip_midrange's range (and that is not
 // singular anyway) raises *viol; the kernel then sets EnumResult::range_flag, and the host repeats the pass
-// on the EXACT instantiations of the kernels (plain divisions; enum_prefix.hip: lp_enum_prefix_range).  Only
+// on the EXACT instantiations of the kernels (plain divisions; enum_driver.hip: prefix_range).  Only
 // a problem scaled to ~1e-150 or ~1e150 as a whole gets there: a non-singular subset's pivots lie within
 // 1/(eps m) = 2^48 of each other.  (Repeating the one subset in place — the exact form inlined behind the
 // fast one, or called — cost the leaf loops 50-200 bytes of spills and the thin kernel a wave per SIMD.)
@@ -800,7 +800,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
         bool sing0 = false;   // MODE 1: the first child of a paired item turned out singular
         if (FUSED) {
             // ---- the wave pivots on column `child`: lane = (row r, column group g), exactly the
-            // arithmetic of k_enum_expand (first unused row of largest |w|; l = -(w/piv) as w * (1/piv))
+            // arithmetic of the level kernels (first unused row of largest |w|; l = -(w/piv) as w * (1/piv))
             const int r = lane & (PG - 1), g = lane >> 4;
             const bool row_used = (r >= m) || ((umask >> r) & 1u);
             const double* pcol = tab + (child_col - D) * TS;

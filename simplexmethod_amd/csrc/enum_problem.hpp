@@ -84,22 +84,63 @@ struct PrefixDev {
                                       // 5 bits per index; entry of leaf l of R columns = comb6[comb6[R] + l]
 };
 
+// Test and A/B knobs of the enumeration, read from the environment once, by lp_enum_upload
+// (enum_driver.hip: read_knobs), so that a problem's route cannot change between two calls.
+struct EnumKnobs {
+    unsigned long long list_cap = 1ULL << 22;  // first feasible-list capacity (LP_ENUM_LIST_CAP / LP_ENUM_LIST_START)
+    bool list_pinned = false;        // LP_ENUM_LIST_CAP: the list neither grows nor gives way to the dense form
+    size_t level_budget = SIZE_MAX;  // LP_ENUM_LEVEL_BUDGET_KB in bytes (SIZE_MAX: by device memory)
+    bool exact_div = false;          // LP_ENUM_EXACT_DIV=1: plain divisions from the first pass on
+    int narrow_mult = -1;            // LP_ENUM_NARROW_MULT (-1: by record width)
+};
+
+// The feasible list a successful shared-prefix pass left on the device (prefix.list / scores, or in the
+// dense form prefix.dense_scores by rank - begin), and the tie rule the pass already applied to it.
+struct EnumList {
+    uint64_t begin = 0, end = 0;
+    uint64_t n = 0;                  // feasible subsets
+    bool dense = false;
+    double star = 0.0, tol = 0.0;    // the tie rule applied: the list's own best score, Solver::EPS ...
+    uint64_t first = ~0ULL;          // ... and its answer
+};
+
+// A range whose feasible subsets do not fit the list (degenerate LPs: up to every non-singular basis is
+// feasible), or whose depth m-7 nodes do not fit the level buffers, is enumerated in sub-ranges, one
+// list at a time; pass 2 re-runs only the sub-ranges whose best score can hold the winner.
+struct EnumSubRange {
+    uint64_t begin, end;
+    double best;     // best score of the sub-range (-inf: no feasible subset)
+    bool direct;     // the sub-range ran on the direct kernel (no list)
+};
+
+// What the last lp_enum_range left for pass 2 over the same range: written by lp_enum_range only,
+// read by lp_enum_first_within only.
+struct EnumRangeRecord {
+    enum Kind { kNone, kList, kSubRanges } kind = kNone;   // kNone: pass 2 runs the direct kernel
+    uint64_t begin = 0, end = 0;
+    EnumList list;                   // kList
+    std::vector<EnumSubRange> parts; // kSubRanges, ascending
+};
+
 struct lp_enum_problem {
     lp_context* ctx = nullptr;
     bool complete = false;           // every allocation of lp_enum_upload succeeded (a shell worth keeping)
+    EnumKnobs knobs;
     EnumDev dev{};
     double* dA = nullptr;
     double* db = nullptr;
     double* dc = nullptr;
     unsigned long long* dbinom = nullptr;
-    std::vector<double> hA, hb, hc;  // host copies (column-major A) for argument checks only
     EnumPassBlock* d_pass = nullptr; // the device block behind dev.result, prefix.list_count / overflow / level_counts
     EnumPassBlock* h_pass = nullptr; // pinned mirror; the four h_* pointers below point into it
     EnumResult* h_result = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // chunking of the last lp_enum_range call (pass 2 narrows to the first qualifying chunk)
-    uint64_t last_begin = 0, last_end = 0, last_per_chunk = 0;
-    int last_chunks = 0;
+    // the last direct launch of pass 1 (enum_direct.hip): how its per-chunk best scores lie in
+    // dev.chunk_best, so that pass 2 over the same range narrows to the first qualifying chunk
+    struct DirectLaunch {
+        uint64_t begin = 0, end = 0, per_chunk = 0;
+        int chunks = 0;
+    } last_direct;
     int chunk_cap = 0;
     std::vector<double> h_chunk_best;
     // vertex scratch
@@ -109,39 +150,24 @@ struct lp_enum_problem {
     PrefixDev prefix{};
     double* prefix_buf[2] = {nullptr, nullptr};
     size_t prefix_buf_bytes[2] = {0, 0};
-    int* h_item_count = nullptr;               // pinned
     int* h_level_counts = nullptr;             // pinned copy of the 32 level counts
     unsigned long long* h_list_count = nullptr;  // pinned
     int* h_overflow = nullptr;                 // pinned
-    bool list_valid = false;                   // the feasible list of the last prefix pass 1 is usable
-    uint64_t list_begin = 0, list_end = 0, list_n = 0;
-    int last_algo = 0;
     uint64_t split_hint = 0;
-    // dense form of a pass (enum_prefix.hip): chosen when a pass finds more than a third of its range
-    // feasible; dense_hint keeps later passes of this problem from listing first
-    bool dense_active = false, dense_hint = false;
+    // dense_hint: a pass found more than a third of its range feasible; later passes of this problem
+    // start in the dense form (enum_driver.hip: enum_prefix_pass)
+    bool dense_hint = false;
     // the leaf kernels divide plainly (enum_leaf.hip: leaf_verdict): set for good once a pass of the fast
     // kernels met pivots outside the fast reciprocal's exponent range, or by LP_ENUM_EXACT_DIV=1 (A/B, tests)
     bool exact_div = false;
-    // A range whose feasible subsets do not fit the list (degenerate LPs: up to every non-singular
-    // basis is feasible) is enumerated in sub-ranges, one list at a time; pass 2 re-runs only the
-    // sub-ranges whose best score can hold the winner.
-    struct PrefixChunk {
-        uint64_t begin, end;
-        double best;     // best score of the sub-range (-inf: no feasible subset)
-        bool direct;     // the sub-range ran on the direct kernel (no list)
-    };
-    std::vector<PrefixChunk> pchunks;
-    bool pchunks_valid = false;
-    uint64_t pchunks_begin = 0, pchunks_end = 0;
+    EnumRangeRecord last_range;
     // shard of the last lp_enum_solve_sharded call (enum_sharded.hip)
     int shard_rank = -1, shard_world = -1;
     uint64_t shard_lo = 0, shard_hi = 0;
-    // tie rule already applied on the device against the range's own best score (prefix path)
-    bool spec_valid = false;
-    double spec_star = 0.0, spec_tol = 0.0;
-    uint64_t spec_first = ~0ULL;
 };
+
+// enum_driver.hip: releases the enumeration shells the context keeps (lp_context_destroy)
+void lp_enum_release_shells(lp_context* ctx);
 
 // enum_direct.hip
 int lp_enum_direct_range(lp_enum_problem* p, uint64_t begin, uint64_t end, double* score_best,
@@ -150,31 +176,24 @@ int lp_enum_direct_first(lp_enum_problem* p, uint64_t begin, uint64_t end, doubl
                          double tol, uint64_t* rank_out);
 int lp_enum_direct_vertex(lp_enum_problem* p, uint64_t rank, double* xB, int* subset, double* z,
                           int* verdict);
-// smallest listed rank whose score is within tol of score_star (UINT64_MAX if none)
-int lp_enum_list_first(lp_enum_problem* p, double score_star, double tol, uint64_t* rank_out);
+// smallest rank of the list whose score is within tol of score_star (UINT64_MAX if none)
+int lp_enum_list_first(lp_enum_problem* p, const EnumList& list, double score_star, double tol, uint64_t* rank_out);
 // evaluation + tie rule against the list's own best, queued without a host round trip; records !=
 // null: the depth m-7 records of the pass (the entries are evaluated from them, enum_leaf.hip)
 int lp_enum_queue_list_tail(lp_enum_problem* p, double tol, const double* records);
 int lp_enum_queue_dense_tail(lp_enum_problem* p, double tol, uint64_t begin, uint64_t end);
 void lp_enum_queue_record_eval(lp_enum_problem* p, const double* records);
 
+// enum_prefix.hip: the root record (pg = 16 or 32 rows; also resets the pass's counters), and level t -> t+1
+// of the breadth-first phase (bound: the level's parents inside [begin, end); narrow: one wave per child)
+void lp_enum_launch_root(lp_enum_problem* p, int pg, double* dst);
+void lp_enum_launch_level(lp_enum_problem* p, int shape, int t, bool narrow, uint64_t bound, const double* src,
+                          int src_cap, double* dst, int cap, uint64_t begin, uint64_t end);
+
 // enum_leaf.hip: one lane per subset below the records of the last breadth-first level
-// (shape: lp_enum_prefix_shape — 1 = the tuned kernels, 2 / 3 = the general kernel on 16- / 32-row records)
+// (shape: enum_driver.hip: prefix_shape — 1 = the tuned kernels, 2 / 3 = the general kernel on 16- / 32-row records)
 // dense: every subset's score goes to prefix.dense_scores[rank - begin] (general kernel), no list
 int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, int level, bool fused,
                           int shape, bool dense, uint64_t begin, uint64_t end);
-
-// enum_prefix.hip
-bool lp_enum_prefix_supported(const lp_enum_problem* p);
-int lp_enum_prefix_shape(const lp_enum_problem* p);
 // enum_leaf.hip: recip_midrange(x[i]) and 1.0 / x[i] computed on the device (lp_debug_reciprocal)
 int lp_enum_debug_reciprocal(lp_context* ctx, const double* x, int n, double* fast_out, double* plain_out);
-// LP_ITER_LIMIT = "could not run here (memory / a level buffer too small), use the direct path";
-// kEnumListOverflow = the feasible list was too small: *h_list_count holds the number of feasible
-// subsets of the range, the caller splits the range (capi.hip: enum_prefix_chunked)
-constexpr int kEnumListOverflow = 1001;
-// kEnumRangeTooWide = the range has more depth m-7 nodes than the level buffers hold: the caller
-// splits it into about p->split_hint parts
-constexpr int kEnumRangeTooWide = 1002;
-int lp_enum_prefix_range(lp_enum_problem* p, uint64_t begin, uint64_t end, double* score_best,
-                         uint64_t counts[3], lp_enum_stats* stats, bool dense = false);

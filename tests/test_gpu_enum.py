@@ -814,10 +814,9 @@ def test_prefix_fast_and_plain_division_agree(ctx, m, n, seed, monkeypatch):
 
 @pytest.mark.parametrize("m,n,seed", [(16, 24, 21), (12, 26, 22), (9, 30, 23), (16, 32, 24)])
 def test_prefix_level_kernels_agree(ctx, m, n, seed, monkeypatch):
-    """The breadth-first levels in their three forms — parent staged in LDS (default for wide levels of 16-row
-    records), operands fetched from the record (LP_ENUM_EXPAND_UNSTAGED=1), one wave per child (every level
-    narrow: LP_ENUM_NARROW_MULT large) — build the same records: counts, optimum and tie-rule rank of a range
-    are identical, and equal to the direct kernel's."""
+    """The breadth-first levels in their two forms — parent staged in LDS (default for wide levels), one wave per
+    child (every level narrow: LP_ENUM_NARROW_MULT large, read when a problem is uploaded) — build the same
+    records: counts, optimum and tie-rule rank of a range are identical, and equal to the direct kernel's."""
     A, b, c, _ = lpcases.random_lp(seed, m, n)
     total = o.binom(n, m)
     lo, hi = total // 7, min(total, total // 7 + (1 << 22))
@@ -825,13 +824,13 @@ def test_prefix_level_kernels_agree(ctx, m, n, seed, monkeypatch):
     ref = p.range(lo, hi, capi.ENUM_PREFIX)[:3]
     k = p.first_within(lo, hi, ref[1]) if ref[0] == 0 else None
     assert p.range(lo, hi, capi.ENUM_DIRECT)[:3] == ref
-    for var, val in (("LP_ENUM_EXPAND_UNSTAGED", "1"), ("LP_ENUM_NARROW_MULT", "100000000")):
-        monkeypatch.setenv(var, val)
-        assert p.range(lo, hi, capi.ENUM_PREFIX)[:3] == ref, var
-        if k is not None:
-            assert p.first_within(lo, hi, ref[1]) == k
-        monkeypatch.delenv(var)
     p.free()
+    monkeypatch.setenv("LP_ENUM_NARROW_MULT", "100000000")
+    q = ctx.enum_problem(A, b, c, True)
+    assert q.range(lo, hi, capi.ENUM_PREFIX)[:3] == ref
+    if k is not None:
+        assert q.first_within(lo, hi, ref[1]) == k
+    q.free()
 
 
 @pytest.mark.parametrize("m,n,seed,window", [(12, 26, 22, 1 << 22), (14, 28, 0, None), (16, 32, 0, 1 << 26), (18, 30, 5, 1 << 24)])
