@@ -509,54 +509,27 @@ int lp_simplex_crash(lp_simplex_problem* p) {
     return hs.status == kRunning ? LP_OPTIMAL : hs.status;
 }
 
-int lp_simplex_run_launch(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
-    lp_context* ctx = p->ctx;
-    const SimplexDev& d = p->dev;
-    hipStream_t s = ctx->stream;
-    const size_t shm = 2 * sizeof(double) * (size_t)(d.m + 2) + 16;
-    if (shm > 48 * 1024) {   // (m > 3070: opt in to more dynamic LDS than the default limit)
-        if (shm > 156 * 1024) LP_FAIL(ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
-        LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_simplex_select),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+static size_t select_lds_bytes(const SimplexDev& d) { return 2 * sizeof(double) * (size_t)(d.m + 2) + 16; }
+
+int lp_launch_prepare(lp_simplex_problem* p) {
+    const size_t shm = select_lds_bytes(p->dev);
+    if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select), shm));   // (m > 3070)
+    return LP_OPTIMAL;
+}
+
+int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter) {
+    hipLaunchKernelGGL(k_state_init, 1, 1, 0, p->ctx->stream, p->dev, eps, max_iter);
+    return 1;
+}
+
+int lp_launch_queue(lp_simplex_problem* p, int batch) {
+    const size_t shm = select_lds_bytes(p->dev);
+    for (int k = 0; k < batch; ++k) {
+        hipLaunchKernelGGL(k_simplex_select, 1, 1024, shm, p->ctx->stream, p->dev);
+        lp_simplex_launch_update(p);
     }
-    int launches = 0;
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
-    hipLaunchKernelGGL(k_state_init, 1, 1, 0, s, d, eps, max_iter);
-    ++launches;
-    int batch = 16;
-    int status = kRunning;
-    // Kernels turn into no-ops once the state leaves kRunning, so pivots are queued in
-    // growing batches and the status word is polled once per batch.
-    for (;;) {
-        for (int k = 0; k < batch; ++k) {
-            hipLaunchKernelGGL(k_simplex_select, 1, 1024, shm, s, d);
-            lp_simplex_launch_update(p);
-        }
-        launches += 2 * batch;
-        LP_HIP(ctx, hipMemcpyAsync(p->h_state, d.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
-        LP_HIP(ctx, hipStreamSynchronize(s));
-        status = p->h_state->status;
-        if (status != kRunning) break;
-        if (batch < 256) batch *= 2;
-    }
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    LP_HIP(ctx, hipGetLastError());
-    float ms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    p->last_status = status;
-    p->last_algo = LP_SIMPLEX_ALGO_LAUNCH;
-    p->last_iters = p->h_state->iters;
-    if (stats) {
-        stats->status = status;
-        stats->pivots = p->h_state->iters;
-        stats->launches = launches;
-        stats->solve_ms = ms;
-        stats->update_ms = 0.f;
-        stats->update_launches = 0;
-        stats->bytes_per_pivot = 16.0 * (double)d.m * (double)(d.n + 1);
-    }
-    return status;
+    return 2 * batch;
 }
 
 int lp_simplex_extract_x(lp_simplex_problem* p, double* dx) {
@@ -564,52 +537,5 @@ int lp_simplex_extract_x(lp_simplex_problem* p, double* dx) {
     hipStream_t s = p->ctx->stream;
     hipLaunchKernelGGL(k_extract_x, lp_ceil_div(d.n, 256), 256, 0, s, d, dx);
     hipLaunchKernelGGL(k_scatter_x, lp_ceil_div(d.m, 256), 256, 0, s, d, dx);
-    return LP_OPTIMAL;
-}
-
-int lp_simplex_bench_update(lp_simplex_problem* p, int row, int col, int iters, float* ms_out) {
-    lp_context* ctx = p->ctx;
-    const SimplexDev& d = p->dev;
-    hipStream_t s = ctx->stream;
-    if (row < 0 || row >= d.m || col < 0 || col >= d.n || iters <= 0)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_bench_rank1_update: bad pivot position or iteration count");
-    // Stage a valid pivot (eta column + pivot-row copy) with the crash selector's
-    // arithmetic, then replay the update kernel.  Values drift (the same eta is
-    // re-applied), which is irrelevant for timing; the tableau is restored afterwards.
-    if (!p->dscratchT) LP_HIP(ctx, hipMalloc(&p->dscratchT, p->tableau_bytes));   // (micro-benchmarks only)
-    LP_HIP(ctx, hipMemcpyAsync(p->dscratchT, d.T, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
-    std::vector<double> lcol((size_t)d.m + 1), prow((size_t)d.ld);
-    std::vector<double> Th((size_t)(d.m + 1) * d.ld);
-    LP_HIP(ctx, hipMemcpyAsync(Th.data(), d.T, p->tableau_bytes, hipMemcpyDeviceToHost, s));
-    LP_HIP(ctx, hipStreamSynchronize(s));
-    const double ur = Th[(size_t)row * d.ld + col];
-    if (ur == 0.0) LP_FAIL(ctx, LP_BAD_ARG, "lp_bench_rank1_update: zero pivot element");
-    for (int i = 0; i <= d.m; ++i)
-        lcol[i] = (i == row) ? 1.0 : -1e-3 * Th[(size_t)i * d.ld + col] / ur;  // damped: stays finite
-    for (int j = 0; j < d.ld; ++j) prow[j] = Th[(size_t)row * d.ld + j];
-    SimplexState hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.status = kRunning;
-    hs.enter = col;
-    hs.leave = row;
-    hs.pivot_valid = 1;
-    LP_HIP(ctx, hipMemcpyAsync(d.lcol, lcol.data(), sizeof(double) * lcol.size(), hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(d.prow, prow.data(), sizeof(double) * prow.size(), hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(d.state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-    for (int k = 0; k < 3; ++k) lp_simplex_launch_update(p);  // warm-up
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
-    for (int k = 0; k < iters; ++k) lp_simplex_launch_update(p);
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    float ms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    if (ms_out) *ms_out = ms / (float)iters;
-    LP_HIP(ctx, hipMemcpyAsync(d.T, p->dscratchT, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
-    hs.status = p->last_status;
-    hs.iters = p->last_iters;
-    hs.pivot_valid = 0;
-    LP_HIP(ctx, hipMemcpyAsync(d.state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipStreamSynchronize(s));
-    LP_HIP(ctx, hipGetLastError());
     return LP_OPTIMAL;
 }

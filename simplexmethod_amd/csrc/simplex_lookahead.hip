@@ -382,127 +382,44 @@ int lp_lookahead_pick_j(int m, int n) {
 }
 
 int lp_lookahead_prepare(lp_simplex_problem* p) {
-    // one-time opt-in to > 64 KiB of dynamic LDS for the selector
+    // the selector's dynamic LDS
     const size_t bytes = sel_lds_bytes(p->dev.m, p->dev.n, p->look.J);
-    LP_HIP(p->ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_look_select),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_look_select), bytes));
     return LP_OPTIMAL;
 }
 
-int lp_lookahead_init_vectors(lp_simplex_problem* p) {
+int lp_lookahead_begin(lp_simplex_problem* p, double eps, int max_iter) {
     const SimplexDev& d = p->dev;
+    hipStream_t s = p->ctx->stream;
     const int span = (d.n + 1 > d.m) ? d.n + 1 : d.m;
-    hipLaunchKernelGGL(k_look_init, lp_ceil_div(span, 256), 256, 0, p->ctx->stream, d, p->look);
-    return LP_OPTIMAL;
-}
-
-int lp_simplex_run_lookahead(lp_simplex_problem* p, double eps, int max_iter,
-                             lp_simplex_stats* stats) {
-    lp_context* ctx = p->ctx;
-    const SimplexDev& d = p->dev;
-    const LookDev& la = p->look;
-    hipStream_t s = ctx->stream;
-    const size_t shm = sel_lds_bytes(d.m, d.n, la.J);
-    const dim3 ugrid(lp_ceil_div(d.ld / 2, LU_TX), lp_ceil_div(d.m + 1, LU_ROWS));
-    int launches = 0;
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
     hipLaunchKernelGGL(k_look_state_init, 1, 1, 0, s, d, eps, max_iter);
-    lp_lookahead_init_vectors(p);
-    launches += 2;
-    int batches = 4;
-    int status = kRunning;
-    // HIP events around the first kMaxTimed rank-J update launches (the kernel the HBM roofline
-    // is quoted on); launches after termination are no-ops and are not counted.
-    constexpr int kMaxTimed = 512;
-    if (p->upd_events.empty()) {
-        p->upd_events.resize(2 * kMaxTimed);
-        for (auto& e : p->upd_events) LP_HIP(ctx, hipEventCreate(&e));
-    }
-    int timed = 0;
-    for (;;) {
-        for (int k = 0; k < batches; ++k) {
-            hipLaunchKernelGGL(k_look_select, 1, SEL_THREADS, shm, s, d, la);
-            if (p->profile_updates && timed < kMaxTimed) LP_HIP(ctx, hipEventRecord(p->upd_events[2 * timed], s));
-            hipLaunchKernelGGL(k_look_update, ugrid, dim3(LU_TX, LU_TY), 0, s, d, la);
-            if (p->profile_updates && timed < kMaxTimed) {
-                LP_HIP(ctx, hipEventRecord(p->upd_events[2 * timed + 1], s));
-                ++timed;
-            }
-        }
-        launches += 2 * batches;
-        LP_HIP(ctx, hipMemcpyAsync(p->h_state, d.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
-        LP_HIP(ctx, hipStreamSynchronize(s));
-        status = p->h_state->status;
-        if (status != kRunning) break;
-        if (batches < 64) batches *= 2;
-    }
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    LP_HIP(ctx, hipGetLastError());
-    float ms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    p->last_status = status;
-    p->last_algo = LP_SIMPLEX_ALGO_LOOKAHEAD;
-    p->last_iters = p->h_state->iters;
-    if (stats) {
-        stats->status = status;
-        stats->pivots = p->h_state->iters;
-        stats->launches = launches;
-        stats->solve_ms = ms;
-        // update launches that did real work: one per started batch of J pivots
-        int real = (p->h_state->iters + la.J - 1) / la.J;
-        if (real > timed) real = timed;
-        float upd = 0.f;
-        for (int k = 0; k < real; ++k) {
-            float t = 0.f;
-            LP_HIP(ctx, hipEventElapsedTime(&t, p->upd_events[2 * k], p->upd_events[2 * k + 1]));
-            upd += t;
-        }
-        stats->update_ms = upd;
-        stats->update_launches = real;
-        stats->bytes_per_pivot = 16.0 * (double)d.m * (double)(d.n + 1);
-    }
-    return status;
+    hipLaunchKernelGGL(k_look_init, lp_ceil_div(span, 256), 256, 0, s, d, p->look);
+    return 2;
 }
 
-// Micro-benchmark of the rank-J update alone: stage one batch of J pivots on the problem's
-// current tableau with the selector, then replay the update launch `iters` times between two
-// HIP events (the same etas are re-applied, so values drift — irrelevant for timing; the
-// tableau and solver state are restored afterwards).
-int lp_lookahead_bench_update(lp_simplex_problem* p, int iters, float* ms_per_launch, int* pivots_out) {
-    lp_context* ctx = p->ctx;
+void lp_lookahead_launch_select(lp_simplex_problem* p) {
     const SimplexDev& d = p->dev;
-    const LookDev& la = p->look;
-    hipStream_t s = ctx->stream;
-    if (la.J < 1 || iters <= 0) LP_FAIL(ctx, LP_BAD_ARG, "look-ahead path unavailable for this problem");
-    int rc = lp_lookahead_prepare(p);
-    if (rc) return rc;
-    const size_t shm = sel_lds_bytes(d.m, d.n, la.J);
+    hipLaunchKernelGGL(k_look_select, 1, SEL_THREADS, sel_lds_bytes(d.m, d.n, p->look.J), p->ctx->stream, d, p->look);
+}
+
+void lp_lookahead_launch_update(lp_simplex_problem* p) {
+    const SimplexDev& d = p->dev;
     const dim3 ugrid(lp_ceil_div(d.ld / 2, LU_TX), lp_ceil_div(d.m + 1, LU_ROWS));
-    if (!p->dscratchT) LP_HIP(ctx, hipMalloc(&p->dscratchT, p->tableau_bytes));   // (micro-benchmarks only)
-    LP_HIP(ctx, hipMemcpyAsync(p->dscratchT, d.T, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_look_state_init, 1, 1, 0, s, d, 1e-9, 1 << 30);
-    lp_lookahead_init_vectors(p);
-    hipLaunchKernelGGL(k_look_select, 1, SEL_THREADS, shm, s, d, la);
-    int count = 0;
-    LP_HIP(ctx, hipMemcpyAsync(&count, la.count, sizeof(int), hipMemcpyDeviceToHost, s));
-    LP_HIP(ctx, hipStreamSynchronize(s));
-    if (count <= 0) LP_FAIL(ctx, LP_BAD_ARG, "no pivot could be staged on the current tableau");
-    for (int k = 0; k < 3; ++k) hipLaunchKernelGGL(k_look_update, ugrid, dim3(LU_TX, LU_TY), 0, s, d, la);
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
-    for (int k = 0; k < iters; ++k) hipLaunchKernelGGL(k_look_update, ugrid, dim3(LU_TX, LU_TY), 0, s, d, la);
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    float ms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    if (ms_per_launch) *ms_per_launch = ms / (float)iters;
-    if (pivots_out) *pivots_out = count;
-    // restore: tableau, basis bookkeeping (the selector moved it), staged-count
-    LP_HIP(ctx, hipMemcpyAsync(d.T, p->dscratchT, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(d.basis, p->dbasis0, sizeof(int) * (size_t)d.m, hipMemcpyDeviceToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(d.nonbasic, p->dnonbasic0, (size_t)d.n, hipMemcpyDeviceToDevice, s));
-    LP_HIP(ctx, hipMemsetAsync(la.count, 0, sizeof(int), s));
-    LP_HIP(ctx, hipStreamSynchronize(s));
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
+    hipLaunchKernelGGL(k_look_update, ugrid, dim3(LU_TX, LU_TY), 0, p->ctx->stream, d, p->look);
+}
+
+int lp_lookahead_queue(lp_simplex_problem* p, int batch, int* timed) {
+    hipStream_t s = p->ctx->stream;
+    const int max_timed = (int)p->upd_events.size() / 2;
+    for (int k = 0; k < batch; ++k) {
+        lp_lookahead_launch_select(p);
+        const bool time_it = p->profile_updates && *timed < max_timed;
+        if (time_it) LP_HIP(p->ctx, hipEventRecord(p->upd_events[2 * *timed], s));
+        lp_lookahead_launch_update(p);
+        if (time_it) {
+            LP_HIP(p->ctx, hipEventRecord(p->upd_events[2 * *timed + 1], s));
+            ++*timed;
+        }
+    }
+    return 2 * batch;
 }

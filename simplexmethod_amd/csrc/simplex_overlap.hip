@@ -580,14 +580,8 @@ int lp_overlap_prepare(lp_simplex_problem* p) {
     return LP_OPTIMAL;
 }
 
-int lp_simplex_run_overlap(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
-    lp_context* ctx = p->ctx;
+static OverlapDev overlap_dev(const lp_simplex_problem* p) {
     const SimplexDev& d = p->dev;
-    hipStream_t s = ctx->stream;
-    {
-        const int rc = lp_overlap_prepare(p);
-        if (rc) return rc;
-    }
     OverlapDev ov;
     ov.T[0] = d.T;
     ov.T[1] = p->ov_T;
@@ -596,16 +590,15 @@ int lp_simplex_run_overlap(lp_simplex_problem* p, double eps, int max_iter, lp_s
     ov.prow[1] = p->ov_vec;                         // ld doubles (16-byte aligned: read as double2)
     ov.lcol[1] = p->ov_vec + d.ld;                  // m + 2 doubles
     ov.slot = reinterpret_cast<int*>(p->ov_vec + d.ld + d.m + 2);   // 8 ints
-    const int fast = overlap_fast_fits(d.m, d.n) ? 1 : 0;
-    const size_t shm = lp_overlap_lds_bytes(d.m) + (fast ? sizeof(double) * (size_t)d.n : 0);
-    if (shm > 48 * 1024 && !p->ov_attr) {
-        LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_simplex_overlap<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_simplex_overlap<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        p->ov_attr = true;
-    }
-    const int nbx = lp_ceil_div(d.ld / 2, OV_TX);
+    return ov;
+}
+
+int lp_overlap_plan(lp_simplex_problem* p, OverlapPlan* plan) {
+    const SimplexDev& d = p->dev;
+    OverlapPlan& q = *plan;
+    q.fast = overlap_fast_fits(d.m, d.n) ? 1 : 0;
+    q.shm = lp_overlap_lds_bytes(d.m) + (q.fast ? sizeof(double) * (size_t)d.n : 0);
+    q.nbx = lp_ceil_div(d.ld / 2, OV_TX);
     const int nby = lp_ceil_div(d.m + 1, OV_TY * OV_RPT);
     // the update: a tile per workgroup, or — fewer than six tiles per CU — one persistent workgroup per CU with even
     // linear shares (see the kernel; two per CU, as the thread count would allow, do not fit its registers: the second
@@ -616,48 +609,37 @@ int lp_simplex_run_overlap(lp_simplex_problem* p, double eps, int max_iter, lp_s
 #ifndef LP_OVERLAP_LINEAR_WGS
 #define LP_OVERLAP_LINEAR_WGS 1
 #endif
+    const int num_cus = p->ctx->num_cus;
     const long long pairs = (long long)(d.m + 1) * (d.ld / 2);
-    const int linear = (nbx * nby < LP_OVERLAP_LINEAR_ROUNDS * ctx->num_cus && pairs < (1LL << 27)) ? 1 : 0;   // (32-bit byte offsets in the ring)
-    const unsigned grid = 1u + (unsigned)(linear ? std::max(1, std::min(nbx * nby, LP_OVERLAP_LINEAR_WGS * ctx->num_cus - 1)) : nbx * nby);
-    int launches = 0;
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
-    hipLaunchKernelGGL(k_overlap_init, 1, 1, 0, s, d, ov, eps, max_iter);
-    ++launches;
-    int batch = 16, k = 0;
-    int status = kRunning;
-    // Launches turn into no-ops once the state leaves kRunning, so they are queued in growing batches and
-    // the status word is polled once per batch.
-    for (;;) {
-        for (int q = 0; q < batch; ++q, ++k)
-            if (linear)
-                hipLaunchKernelGGL(k_simplex_overlap<true>, grid, OV_TX * OV_TY, shm, s, d, ov, k, nbx, fast);
-            else
-                hipLaunchKernelGGL(k_simplex_overlap<false>, grid, OV_TX * OV_TY, shm, s, d, ov, k, nbx, fast);
-        launches += batch;
-        LP_HIP(ctx, hipMemcpyAsync(p->h_state, d.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
-        LP_HIP(ctx, hipStreamSynchronize(s));
-        status = p->h_state->status;
-        if (status != kRunning) break;
-        if (batch < 256) batch *= 2;
-    }
-    // T_N lives in buffer N & 1 (launch N applied the last pivot; the launches behind it did nothing)
-    if (p->h_state->iters & 1) LP_HIP(ctx, hipMemcpyAsync(d.T, p->ov_T, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    LP_HIP(ctx, hipGetLastError());
-    float ms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    p->last_status = status;
-    p->last_algo = LP_SIMPLEX_ALGO_OVERLAP;
-    p->last_iters = p->h_state->iters;
-    if (stats) {
-        stats->status = status;
-        stats->pivots = p->h_state->iters;
-        stats->launches = launches;
-        stats->solve_ms = ms;
-        stats->update_ms = 0.f;
-        stats->update_launches = 0;
-        stats->bytes_per_pivot = 16.0 * (double)d.m * (double)(d.n + 1);
-    }
-    return status;
+    q.linear = (q.nbx * nby < LP_OVERLAP_LINEAR_ROUNDS * num_cus && pairs < (1LL << 27)) ? 1 : 0;   // (32-bit byte offsets in the ring)
+    q.grid = 1u + (unsigned)(q.linear ? std::max(1, std::min(q.nbx * nby, LP_OVERLAP_LINEAR_WGS * num_cus - 1)) : q.nbx * nby);
+    q.k = 0;
+    const void* kernel = q.linear ? reinterpret_cast<const void*>(k_simplex_overlap<true>)
+                                  : reinterpret_cast<const void*>(k_simplex_overlap<false>);
+    LP_HIP(p->ctx, lp_lds_opt_in(kernel, q.shm));
+    return LP_OPTIMAL;
+}
+
+int lp_overlap_begin(lp_simplex_problem* p, double eps, int max_iter) {
+    hipLaunchKernelGGL(k_overlap_init, 1, 1, 0, p->ctx->stream, p->dev, overlap_dev(p), eps, max_iter);
+    return 1;
+}
+
+int lp_overlap_queue(lp_simplex_problem* p, OverlapPlan& q, int batch) {
+    const SimplexDev& d = p->dev;
+    const OverlapDev ov = overlap_dev(p);
+    hipStream_t s = p->ctx->stream;
+    for (int b = 0; b < batch; ++b, ++q.k)
+        if (q.linear)
+            hipLaunchKernelGGL(k_simplex_overlap<true>, q.grid, OV_TX * OV_TY, q.shm, s, d, ov, q.k, q.nbx, q.fast);
+        else
+            hipLaunchKernelGGL(k_simplex_overlap<false>, q.grid, OV_TX * OV_TY, q.shm, s, d, ov, q.k, q.nbx, q.fast);
+    return batch;
+}
+
+// T_N lives in buffer N & 1 (launch N applied the last pivot; the launches behind it did nothing)
+int lp_overlap_finish(lp_simplex_problem* p) {
+    if (p->h_state->iters & 1)
+        LP_HIP(p->ctx, hipMemcpyAsync(p->dev.T, p->ov_T, p->tableau_bytes, hipMemcpyDeviceToDevice, p->ctx->stream));
+    return LP_OPTIMAL;
 }

@@ -76,7 +76,6 @@ struct lp_simplex_problem {
     double* dscratchT = nullptr;  // scratch copy used by the update micro-benchmarks (allocated on first use)
     double* ov_T = nullptr;       // simplex_overlap.hip: the second tableau buffer, and the second eta slot
     double* ov_vec = nullptr;     // (pivot row, eta column, 8 ints); both allocated on first use
-    bool ov_attr = false;         // the overlapped kernel's dynamic-LDS opt-in has been made
     int* dbasis0 = nullptr;
     unsigned char* dnonbasic0 = nullptr;
     double* dx = nullptr;         // n: extracted vertex
@@ -92,31 +91,62 @@ struct lp_simplex_problem {
     int last_algo = 0;            // LP_SIMPLEX_ALGO_* of the last run (which stamp buffer is current)
 };
 
-// simplex_launch.hip
+// simplex_driver.hip: the host side of a solve (upload, dispatch, the batch-and-poll loop, the stats record)
+int check_canonical(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                    const int* basis, int n_orig);
+// Is basis (m positions) the unit-vector basis of the column-major A, and are its costs all zero?  (*zero_costs is
+// only meaningful when *identity holds.)
+void lp_slack_identity(const double* A, int m, const double* c, const int* basis, bool* identity, bool* zero_costs);
+// Dynamic LDS above the default 48 KiB needs an opt-in.  The limit is an attribute of the kernel, not of a
+// problem, so every run sets it for the size it is about to launch with.
+hipError_t lp_lds_opt_in(const void* kernel, size_t bytes);
+
+// Each path's launch surface.  begin() queues the state-init launches of a run and returns how many it queued;
+// queue(batch) queues `batch` pivots and returns the launches queued (a negative value is a HIP error).
+
+// simplex_launch.hip: one select + one rank-1-update launch per pivot
+int lp_launch_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, opted in
+int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter);
+int lp_launch_queue(lp_simplex_problem* p, int batch);
 void lp_simplex_launch_update(lp_simplex_problem* p);
 int lp_simplex_crash(lp_simplex_problem* p);
 int lp_simplex_price_out_identity(lp_simplex_problem* p);  // unit-vector basis with non-zero costs
 int lp_simplex_force(lp_simplex_problem* p, int row, int col);  // host-chosen pivot on the current tableau
 int lp_simplex_driveout(lp_simplex_problem* p, const int* positions, int count, int n_limit, double eps, int* applied);
 int lp_simplex_phase2_costs(lp_simplex_problem* p, const double* cost, int n_real, int maximize, int n_orig);
-int lp_simplex_run_launch(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats);
 int lp_simplex_extract_x(lp_simplex_problem* p, double* dx);
-int lp_simplex_bench_update(lp_simplex_problem* p, int row, int col, int iters, float* ms_out);
 
-// simplex_overlap.hip
+// simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
+int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS
+int lp_lookahead_prepare(lp_simplex_problem* p);
+int lp_lookahead_begin(lp_simplex_problem* p, double eps, int max_iter);
+// (with profiling on, the update launches are bracketed by upd_events while *timed < upd_events.size() / 2)
+int lp_lookahead_queue(lp_simplex_problem* p, int batch, int* timed);
+void lp_lookahead_launch_select(lp_simplex_problem* p);
+void lp_lookahead_launch_update(lp_simplex_problem* p);
+
+// simplex_overlap.hip: one launch per pivot, the update of pivot k beside the selection of pivot k+1
+struct OverlapPlan {
+    size_t shm;       // the selector's dynamic LDS (every workgroup of the launch is given it)
+    int fast;         // the selector with the priced cost row in LDS
+    int linear;       // the update as persistent linear shares (else a tile per workgroup)
+    int nbx;          // column tiles of the update
+    unsigned grid;    // workgroups per launch, the selector's included
+    int k;            // launches of the pivot kernel queued so far in this run
+};
 bool lp_overlap_fits(int m);
 bool lp_overlap_auto(int m);    // what LP_SIMPLEX_ALGO_AUTO requires of the shape
 int lp_overlap_prepare(lp_simplex_problem* p);   // allocates the second tableau buffer (first use)
-int lp_simplex_run_overlap(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats);
+int lp_overlap_plan(lp_simplex_problem* p, OverlapPlan* plan);   // launch shape + the LDS opt-in
+int lp_overlap_begin(lp_simplex_problem* p, double eps, int max_iter);
+int lp_overlap_queue(lp_simplex_problem* p, OverlapPlan& plan, int batch);
+int lp_overlap_finish(lp_simplex_problem* p);    // the final tableau back to dev.T after an odd pivot count
 
-// simplex_resident.hip
+// simplex_resident.hip: the whole solve in one launch
 int lp_resident_plan(int m, int n, ResidentDev* out);   // fills G/stride/mpad/offsets; 0 if the shape does not fit
-int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats);
+// state init, hand-off areas cleared, then the kernel between res_ev0 and res_ev1
+int lp_resident_launch(lp_simplex_problem* p, double eps, int max_iter);
+// After the state word is back: *rerun = a hand-off timed out (last_error says where), nothing was written back and
+// the solve is to be re-run on another path; LP_BAD_ARG instead under LP_RESIDENT_STRICT.
+int lp_resident_finish(lp_simplex_problem* p, bool* rerun);
 int lp_simplex_debug_division(lp_context* ctx, const double* num, const double* den, int n, double* fast_out, double* plain_out);
-
-// simplex_lookahead.hip
-int lp_lookahead_pick_j(int m, int n);
-int lp_lookahead_prepare(lp_simplex_problem* p);
-int lp_lookahead_init_vectors(lp_simplex_problem* p);
-int lp_simplex_run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats);
-int lp_lookahead_bench_update(lp_simplex_problem* p, int iters, float* ms_per_launch, int* pivots_out);

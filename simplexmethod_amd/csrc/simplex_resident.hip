@@ -1068,8 +1068,7 @@ __global__ void k_resident_state_init(SimplexDev d, double eps, int max_iter) {
 
 template <int CPT, int NT>
 void launch_resident(const SimplexDev& d, const ResidentDev& rd, size_t shm, hipStream_t s, hipError_t* attr_err) {
-    *attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_simplex_resident<CPT, NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    *attr_err = lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_resident<CPT, NT>), shm);
     if (*attr_err == hipSuccess)
         hipLaunchKernelGGL((k_simplex_resident<CPT, NT>), rd.G * rd.stride, rd.mpad + 64, shm, s, d, rd);
 }
@@ -1119,12 +1118,11 @@ int lp_resident_plan(int m, int n, ResidentDev* out) {
     return 1;
 }
 
-int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
+int lp_resident_launch(lp_simplex_problem* p, double eps, int max_iter) {
     lp_context* ctx = p->ctx;
     const SimplexDev& d = p->dev;
     const ResidentDev& rd = p->res;
     hipStream_t s = ctx->stream;
-    if (rd.G < 1 || !rd.comm) LP_FAIL(ctx, LP_BAD_ARG, "chip-resident path unavailable for this problem");
     // > 80 KiB of LDS per workgroup: one workgroup per CU, so that G workgroups own G CUs
     size_t shm = resident_lds_bytes(rd.cpt == 32 ? 512 : 960, rd.cpt);   // (the instantiation's NT: see resident_lds_bytes)
     if (shm < 84 * 1024) shm = 84 * 1024;
@@ -1132,7 +1130,6 @@ int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_
     if (getenv("LP_RESIDENT_FORCE_SC1")) rdv.flags |= 1;     // tests: write-through stores on one XCD too
     if (getenv("LP_RESIDENT_SPREAD")) rdv.stride = 1;        // tests: participants on all XCDs
     if (getenv("LP_RESIDENT_INJECT_FAILURE")) rdv.flags |= 2;   // tests: the census reports a failure
-    LP_HIP(ctx, hipEventRecord(p->ev0, s));
     hipLaunchKernelGGL(k_resident_state_init, 1, 1, 0, s, d, eps, max_iter);
     LP_HIP(ctx, hipMemsetAsync(rd.comm, 0, rd.comm_bytes, s));   // every tag of every granule: epoch 0
     if (!p->res_ev0) {   // HIP events tight around the one kernel launch (lp_simplex_stats::update_ms)
@@ -1147,15 +1144,15 @@ int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_
         launch_resident<16, 960>(d, rdv, shm, s, &attr_err);
     LP_HIP(ctx, attr_err);
     LP_HIP(ctx, hipEventRecord(p->res_ev1, s));
-    LP_HIP(ctx, hipMemcpyAsync(p->h_state, d.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
-    LP_HIP(ctx, hipEventRecord(p->ev1, s));
-    LP_HIP(ctx, hipEventSynchronize(p->ev1));
-    LP_HIP(ctx, hipGetLastError());
-    float ms = 0.f, kms = 0.f;
-    LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    LP_HIP(ctx, hipEventElapsedTime(&kms, p->res_ev0, p->res_ev1));
-    int status = p->h_state->status;
-    if (status == kResidentFailed || status == kRunning) {
+    return LP_OPTIMAL;
+}
+
+int lp_resident_finish(lp_simplex_problem* p, bool* rerun) {
+    lp_context* ctx = p->ctx;
+    const ResidentDev& rd = p->res;
+    const int status = p->h_state->status;
+    *rerun = status == kResidentFailed || status == kRunning;
+    if (*rerun) {
         // a hand-off timed out (e.g. the workgroups never became co-resident because another kernel
         // holds the CUs): nothing was written back, the look-ahead / launch path solves it instead
         char msg[200];
@@ -1173,16 +1170,7 @@ int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_
             }
         }
         if (getenv("LP_RESIDENT_STRICT")) return LP_BAD_ARG;   // tests: a fallback must not hide a protocol bug
-        int rc;
-        if (p->look.J >= 2) {
-            rc = lp_lookahead_prepare(p);
-            if (rc) return rc;
-            rc = lp_simplex_run_lookahead(p, eps, max_iter, stats);
-        } else {
-            rc = lp_simplex_run_launch(p, eps, max_iter, stats);
-        }
-        if (rc >= 0 && stats) stats->solve_ms += ms;   // the caller waited for the timed-out launch too
-        return rc;
+        return LP_OPTIMAL;
     }
 #if RS_MARK_A >= 0   // diagnostic builds: the interval RS_MARK_A -> RS_MARK_B per workgroup
     {
@@ -1201,19 +1189,7 @@ int lp_simplex_run_resident(lp_simplex_problem* p, double eps, int max_iter, lp_
         }
     }
 #endif
-    p->last_status = status;
-    p->last_iters = p->h_state->iters;
-    p->last_algo = LP_SIMPLEX_ALGO_RESIDENT;
-    if (stats) {
-        stats->status = status;
-        stats->pivots = p->h_state->iters;
-        stats->launches = 2;
-        stats->solve_ms = ms;
-        stats->update_ms = kms;         // the resident kernel alone: every pivot of the solve
-        stats->update_launches = 1;
-        stats->bytes_per_pivot = 16.0 * (double)d.m * (double)(d.n + 1);
-    }
-    return status;
+    return LP_OPTIMAL;
 }
 
 int lp_simplex_debug_division(lp_context* ctx, const double* num, const double* den, int n, double* fast_out, double* plain_out) {

@@ -154,6 +154,34 @@ def test_overlap_large_shape(ctx, max_iter):
     _assert_bit_exact(g, r)
 
 
+def test_overlap_lds_opt_in_follows_the_run(ctx):
+    """The overlapped kernel's dynamic-LDS limit is an attribute of the kernel, not of a problem: a problem with a
+    smaller selector (B) run in between must not leave the limit below what A needs on A's next run.  Both take the
+    fast selector, and both need more than the default 48 KiB: lp_overlap_lds_bytes(m) + 8 n, with
+    lp_overlap_lds_bytes(m) = 16 (m + 2) + 16 + 208 (the block-chain scratch)."""
+    def lds(m, n):
+        return 16 * (m + 2) + 16 + 208 + 8 * n
+    shapes = {"A": (2048, 4096, 47), "B": (1024, 4096, 49)}
+    assert lds(2048, 4096) == 65792 and lds(1024, 4096) == 49408
+    assert all(48 * 1024 < lds(m, n) <= 78 * 1024 for m, n, _ in shapes.values())
+    probs, refs = {}, {}
+    for key, (m, n, seed) in shapes.items():
+        A, b, c, basis = lpcases.random_lp(seed, m, n)
+        refs[key] = o.simplex_tableau(A, b, c, basis, True, n - m, trace_cap=64, want_tableau=True, max_iter=2)
+        assert refs[key]["status"] == o.ITER_LIMIT and refs[key]["iters"] == 2
+        probs[key] = ctx.simplex_problem(A, b, c, basis, True, n - m)
+    for key in ("A", "B", "A"):
+        p = probs[key]
+        p.reset()
+        rc, st = p.run(max_iter=2, algo=capi.SIMPLEX_OVERLAP)
+        assert st.algo_used == capi.SIMPLEX_OVERLAP and st.fell_back == 0
+        g = p.download(trace_cap=max(st.pivots, 1), want_tableau=True)
+        g.update(status=rc, iters=st.pivots)
+        _assert_bit_exact(g, refs[key])
+    for p in probs.values():
+        p.free()
+
+
 @pytest.mark.parametrize("max_iter", [2, 3])
 def test_overlap_general_selector_and_tiled_update(ctx, max_iter):
     """1100 x 11000 (97 MB): the one-launch-per-pivot path in its OTHER forms — the priced cost row does not fit LDS
