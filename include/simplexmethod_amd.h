@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -203,6 +203,27 @@ void lp_batched_free(lp_batched_problem* p);
  * outputs).  The convention every binding uses: *lo = batch*shard/shards, *hi = batch*(shard+1)/shards
  * (64-bit arithmetic) - contiguous, disjoint, covering, sizes differing by at most one.             */
 int lp_batched_shard_bounds(int batch, int shard, int shards, int* lo, int* hi);
+
+/* Batched two-phase simplex: `batch` LPs of one shape WITHOUT a starting basis (Symmetrical MIN
+ * problems, rows with b < 0, equality rows), one LP per workgroup; per LP exactly
+ * lp_simplex_two_phase (same checks, same results).  Inputs as lp_simplex_solve_batched without
+ * basis_in; x_out batch*n_orig, basis_out batch*m, obj_out batch, iters_out batch*3 (phase I,
+ * drive-out, phase II), status_out batch.  x and obj are written for LP_OPTIMAL LPs only; the basis
+ * always.  Shapes whose tableau ((m+1) x (n+1) doubles) does not fit one CU's LDS are solved by
+ * lp_simplex_two_phase one LP after another.                                                     */
+int lp_simplex_two_phase_batched(lp_context* ctx, int batch, const double* A, int m, int n,
+                                 const double* b, const double* c, int maximize, int n_orig,
+                                 double eps, int max_iter, double* x_out, int* basis_out,
+                                 double* obj_out, int* iters_out, int* status_out);
+/* Device-resident form: a handle that lp_batched_run / _download / _free accept (run may be
+ * repeated; lp_batched_download's iters_out is then the sum of the three counts per LP).          */
+int lp_batched_two_phase_upload(lp_context* ctx, int batch, const double* A, int m, int n,
+                                const double* b, const double* c, int maximize, int n_orig,
+                                lp_batched_problem** problem_out);
+/* The three pivot counts per LP (batch*3) of the last run; LP_BAD_ARG on a plain batch.          */
+int lp_batched_phase_iters(lp_batched_problem* p, int* iters_out);
+/* 1: one LP per workgroup on the GPU, 0: per-LP fallback (either kind of batch).                 */
+int lp_batched_path(const lp_batched_problem* p);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

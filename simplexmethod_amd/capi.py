@@ -71,6 +71,12 @@ SIGNATURES = {
     "lp_batched_download": (C.c_int, [_vp, _dp, _ip, _dp, _ip, _ip]),
     "lp_batched_free": (None, [_vp]),
     "lp_batched_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip]),
+    "lp_simplex_two_phase_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int,
+                                               C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _ip, _ip]),
+    "lp_batched_two_phase_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int,
+                                              C.c_int, C.POINTER(_vp)]),
+    "lp_batched_phase_iters": (C.c_int, [_vp, _ip]),
+    "lp_batched_path": (C.c_int, [_vp]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -303,6 +309,28 @@ class Context:
     def batched_problem(self, A, b, c, basis, maximize=True, n_orig=None):
         return BatchedProblem(self, A, b, c, basis, maximize, n_orig)
 
+    def two_phase_batched(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+        """lp_simplex_two_phase_batched: A (batch, m, n), b (batch, m), c (batch, n), no basis;
+        per LP exactly two_phase().  iters: (batch, 3) = phase I, drive-out, phase II."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        n_orig = n if n_orig is None else n_orig
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        x = np.zeros((batch, n_orig))
+        bo = np.full((batch, m), -1, dtype=np.int32)
+        obj = np.full(batch, np.nan)
+        it = np.zeros((batch, 3), dtype=np.int32)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_simplex_two_phase_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c),
+                                                         int(maximize), n_orig, eps, max_iter, _d(x),
+                                                         _i(bo), _d(obj), _i(it), _i(st)))
+        return dict(status=st, x=x, basis=bo, obj=obj, iters=it)
+
+    def batched_two_phase_problem(self, A, b, c, maximize=False, n_orig=None):
+        """Device-resident two-phase batch (lp_batched_two_phase_upload)."""
+        return BatchedProblem(self, A, b, c, None, maximize, n_orig)
+
     # ---- enumeration ---------------------------------------------------------------------
     def enum_solve(self, A, b, c, maximize=True, n_orig=None):
         A = np.asarray(A, dtype=np.float64)
@@ -401,10 +429,15 @@ class BatchedProblem:
         self.n_orig = self.n if n_orig is None else n_orig
         Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
         b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
         h = _vp()
-        ctx.check(ctx.lib.lp_batched_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
-                                            _i(basis), int(maximize), self.n_orig, C.byref(h)))
+        self.two_phase = basis is None   # no starting basis: the two-phase flow
+        if self.two_phase:
+            ctx.check(ctx.lib.lp_batched_two_phase_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b),
+                                                          _d(c), int(maximize), self.n_orig, C.byref(h)))
+        else:
+            basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+            ctx.check(ctx.lib.lp_batched_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
+                                                _i(basis), int(maximize), self.n_orig, C.byref(h)))
         self.h = h
 
     def run(self, eps=EPS, max_iter=MAX_ITER):
@@ -421,6 +454,16 @@ class BatchedProblem:
         self.ctx.check(self.ctx.lib.lp_batched_download(self.h, _d(x), _i(bo), _d(obj), _i(it),
                                                         _i(st)))
         return dict(status=st, x=x, basis=bo, obj=obj, iters=it)
+
+    def phase_iters(self):
+        """(batch, 3) pivot counts of the last run: phase I, drive-out, phase II (two-phase batches)."""
+        it = np.zeros((self.batch, 3), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.lp_batched_phase_iters(self.h, _i(it)))
+        return it
+
+    def path(self):
+        """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""
+        return self.ctx.check(self.ctx.lib.lp_batched_path(self.h))
 
     def free(self):
         if getattr(self, "h", None):

@@ -25,3 +25,24 @@ struct BatchedDev {
 // batched_simplex.hip
 size_t lp_batched_lds_bytes(int m, int n, int* pitch_out);
 int lp_batched_launch(lp_context* ctx, const BatchedDev& d);
+
+// A batch of same-shape LPs solved by the two-phase flow, one LP per workgroup (batched_two_phase.hip).
+struct BatchedTwoPhaseDev {
+    int batch, m, n;        // n = canonical columns (the m artificials are implicit)
+    int pitch;              // row pitch (doubles) of the LDS tableau, odd, >= n + 1
+    int maximize;
+    int max_iter;           // per phase
+    double eps;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    double* x;              // batch x n  (full vertex)
+    int* basis_out;         // batch x m  (by position)
+    int* iters;             // batch x 3  (phase I, drive-out, phase II)
+    int* status;            // batch
+};
+
+// batched_two_phase.hip
+size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out);
+bool lp_batched_two_phase_fits(int m, int n);
+int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d);

@@ -1,8 +1,10 @@
 // capi.hip — the extern "C" boundary (include/simplexmethod_amd.h): the context, the status strings, the
 // division self-tests and the batched simplex.  The single-LP simplex is simplex_driver.hip, the
 // enumeration enum_driver.hip.
+#include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 
 #include "batched_problem.hpp"
 #include "enum_problem.hpp"
@@ -132,6 +134,9 @@ int lp_debug_division(lp_context* ctx, const double* num, const double* den, int
 // batched simplex — one LP per workgroup (batched_simplex.hip).  LPs whose initial
 // basis is not the slack identity, or whose condensed tableau does not fit one CU's
 // LDS, go through the single-LP path one after another instead.
+// A batch uploaded by lp_batched_two_phase_upload has no starting basis and runs the
+// two-phase flow, one LP per workgroup (batched_two_phase.hip); shapes that do not fit
+// go through lp_simplex_two_phase one LP after another.
 // ===========================================================================
 
 struct lp_batched_problem {
@@ -145,6 +150,14 @@ struct lp_batched_problem {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<lp_simplex_problem*> lps;  // fallback
     std::vector<int> status, iters;
+    // two-phase batch (lp_batched_two_phase_upload): no basis_in, three pivot counts per LP
+    bool two_phase = false;
+    int maximize = 0;
+    BatchedTwoPhaseDev tdev{};
+    std::vector<int> phase_iters;           // batch*3
+    std::vector<double> h_A, h_b;           // per-LP fallback: the inputs ...
+    std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
+    std::vector<int> h_basis;               // batch*m
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -259,10 +272,187 @@ int lp_batched_upload(lp_context* ctx, int batch, const double* A, int m, int n,
     return LP_OPTIMAL;
 }
 
+int lp_batched_two_phase_upload(lp_context* ctx, int batch, const double* A, int m, int n,
+                                const double* b, const double* c, int maximize, int n_orig,
+                                lp_batched_problem** problem_out) {
+    if (!ctx || !problem_out) return LP_BAD_ARG;
+    *problem_out = nullptr;
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    // the checks of lp_simplex_two_phase
+    if (!A || !b || !c) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_two_phase_upload: null argument");
+    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_two_phase_upload: bad dimensions");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    lp_batched_problem* p = new lp_batched_problem();
+    p->ctx = ctx;
+    p->two_phase = true;
+    p->batch = batch;
+    p->m = m;
+    p->n = n;
+    p->n_orig = n_orig;
+    p->maximize = maximize ? 1 : 0;
+    const size_t B = (size_t)batch;
+    p->status.assign(B, -100);
+    p->phase_iters.assign(B * 3, 0);
+    p->h_c.assign(c, c + B * n);
+    p->resident = lp_batched_two_phase_fits(m, n);
+    if (!p->resident) {   // per-LP fallback: keep the inputs for lp_simplex_two_phase
+        p->h_A.assign(A, A + B * m * n);
+        p->h_b.assign(b, b + B * m);
+        p->h_x.assign(B * n_orig, 0.0);
+        p->h_obj.assign(B, 0.0);
+        p->h_basis.assign(B * m, -1);
+        *problem_out = p;
+        return LP_OPTIMAL;
+    }
+#define LP_TRY(expr)                        \
+    do {                                    \
+        hipError_t _e = (expr);             \
+        if (_e != hipSuccess) {             \
+            ctx->last_error = #expr;        \
+            lp_batched_free(p);             \
+            return -(int)_e;                \
+        }                                   \
+    } while (0)
+    hipStream_t s = ctx->stream;
+    LP_TRY(hipMalloc(&p->dA, sizeof(double) * B * m * n));
+    LP_TRY(hipMalloc(&p->db, sizeof(double) * B * m));
+    LP_TRY(hipMalloc(&p->dc, sizeof(double) * B * n));
+    LP_TRY(hipMalloc(&p->dx, sizeof(double) * B * n));
+    LP_TRY(hipMalloc(&p->dbasis_out, sizeof(int) * B * m));
+    LP_TRY(hipMalloc(&p->diters, sizeof(int) * B * 3));
+    LP_TRY(hipMalloc(&p->dstatus, sizeof(int) * B));
+    LP_TRY(hipEventCreate(&p->ev0));
+    LP_TRY(hipEventCreate(&p->ev1));
+    LP_TRY(hipMemcpyAsync(p->dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s));
+    LP_TRY(hipMemcpyAsync(p->db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s));
+    LP_TRY(hipMemcpyAsync(p->dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s));
+    LP_TRY(hipStreamSynchronize(s));
+#undef LP_TRY
+    BatchedTwoPhaseDev& d = p->tdev;
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_batched_two_phase_lds_bytes(m, n, &d.pitch);
+    d.maximize = p->maximize;
+    d.A = p->dA;
+    d.b = p->db;
+    d.c = p->dc;
+    d.x = p->dx;
+    d.basis_out = p->dbasis_out;
+    d.iters = p->diters;
+    d.status = p->dstatus;
+    *problem_out = p;
+    return LP_OPTIMAL;
+}
+
+static int batched_two_phase_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
+    lp_context* ctx = p->ctx;
+    if (p->resident) {
+        p->tdev.eps = eps;
+        p->tdev.max_iter = max_iter;
+        LP_HIP(ctx, hipEventRecord(p->ev0, ctx->stream));
+        int rc = lp_batched_two_phase_launch(ctx, p->tdev);
+        if (rc) return rc;
+        LP_HIP(ctx, hipGetLastError());
+        LP_HIP(ctx, hipEventRecord(p->ev1, ctx->stream));
+        LP_HIP(ctx, hipEventSynchronize(p->ev1));
+        float ms = 0.f;
+        LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        if (ms_out) *ms_out = ms;
+        return LP_OPTIMAL;
+    }
+    // per-LP fallback: lp_simplex_two_phase one LP after another (host clock)
+    const auto t0 = std::chrono::steady_clock::now();
+    const int m = p->m, n = p->n;
+    for (int k = 0; k < p->batch; ++k) {
+        int rc = lp_simplex_two_phase(ctx, p->h_A.data() + (size_t)k * m * n, m, n, p->h_b.data() + (size_t)k * m,
+                                      p->h_c.data() + (size_t)k * n, p->maximize, p->n_orig, eps, max_iter,
+                                      p->h_x.data() + (size_t)k * p->n_orig, p->h_basis.data() + (size_t)k * m,
+                                      p->h_obj.data() + k, p->phase_iters.data() + (size_t)k * 3);
+        if (rc < 0 || rc > LP_INFEASIBLE) return rc;
+        p->status[(size_t)k] = rc;
+    }
+    if (ms_out) *ms_out = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return LP_OPTIMAL;
+}
+
+static int batched_two_phase_download(lp_batched_problem* p, double* x_out, int* basis_out, double* obj_out,
+                                      int* iters_out, int* status_out) {
+    lp_context* ctx = p->ctx;
+    const size_t B = (size_t)p->batch;
+    const int m = p->m, n = p->n, no = p->n_orig;
+    std::vector<double> x;
+    if (p->resident) {
+        x.resize(B * n);
+        hipStream_t s = ctx->stream;
+        LP_HIP(ctx, hipMemcpyAsync(x.data(), p->dx, sizeof(double) * B * n, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipMemcpyAsync(p->status.data(), p->dstatus, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipMemcpyAsync(p->phase_iters.data(), p->diters, sizeof(int) * B * 3, hipMemcpyDeviceToHost, s));
+        if (basis_out) LP_HIP(ctx, hipMemcpyAsync(basis_out, p->dbasis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipStreamSynchronize(s));
+    } else if (basis_out) {
+        std::memcpy(basis_out, p->h_basis.data(), sizeof(int) * B * m);
+    }
+    for (size_t k = 0; k < B; ++k) {
+        const bool ok = p->status[k] == LP_OPTIMAL;
+        if (p->resident && ok) {
+            const double* xk = x.data() + k * n;
+            if (x_out)  // x.head(n_orig)
+                for (int j = 0; j < no; ++j) x_out[k * no + j] = xk[j];
+            if (obj_out) {  // Canonical::Evaluate, Canonical.cpp:86
+                double z = 0.0;
+                const double* ck = p->h_c.data() + k * n;
+                for (int j = 0; j < n; ++j) z += ck[j] * xk[j];
+                obj_out[k] = z;
+            }
+        } else if (ok) {
+            if (x_out) std::memcpy(x_out + k * no, p->h_x.data() + k * no, sizeof(double) * no);
+            if (obj_out) obj_out[k] = p->h_obj[k];
+        }
+        const int* it = p->phase_iters.data() + k * 3;
+        if (iters_out) iters_out[k] = it[0] + it[1] + it[2];
+        if (status_out) status_out[k] = p->status[k];
+    }
+    return LP_OPTIMAL;
+}
+
+int lp_batched_phase_iters(lp_batched_problem* p, int* iters_out) {
+    if (!p || !iters_out) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!p->two_phase) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_phase_iters: not a two-phase batch");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    if (p->resident) LP_HIP(ctx, hipMemcpy(p->phase_iters.data(), p->diters, sizeof(int) * 3 * (size_t)p->batch, hipMemcpyDeviceToHost));
+    std::memcpy(iters_out, p->phase_iters.data(), sizeof(int) * 3 * (size_t)p->batch);
+    return LP_OPTIMAL;
+}
+
+int lp_batched_path(const lp_batched_problem* p) {
+    if (!p) return LP_BAD_ARG;
+    return p->resident ? 1 : 0;
+}
+
+int lp_simplex_two_phase_batched(lp_context* ctx, int batch, const double* A, int m, int n,
+                                 const double* b, const double* c, int maximize, int n_orig,
+                                 double eps, int max_iter, double* x_out, int* basis_out,
+                                 double* obj_out, int* iters_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: null argument");
+    lp_batched_problem* p = nullptr;
+    int rc = lp_batched_two_phase_upload(ctx, batch, A, m, n, b, c, maximize, n_orig, &p);
+    if (rc) return rc;
+    rc = lp_batched_run(p, eps, max_iter, nullptr);
+    if (rc == LP_OPTIMAL) rc = lp_batched_download(p, x_out, basis_out, obj_out, nullptr, status_out);
+    if (rc == LP_OPTIMAL && iters_out) rc = lp_batched_phase_iters(p, iters_out);
+    lp_batched_free(p);
+    return rc;
+}
+
 int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
     if (!p) return LP_BAD_ARG;
     lp_context* ctx = p->ctx;
     LP_HIP(ctx, hipSetDevice(ctx->device));
+    if (p->two_phase) return batched_two_phase_run(p, eps, max_iter, ms_out);
     if (p->resident) {
         p->dev.eps = eps;
         p->dev.max_iter = max_iter;
@@ -328,6 +518,7 @@ int lp_batched_download(lp_batched_problem* p, double* x_out, int* basis_out, do
     if (!p) return LP_BAD_ARG;
     lp_context* ctx = p->ctx;
     LP_HIP(ctx, hipSetDevice(ctx->device));
+    if (p->two_phase) return batched_two_phase_download(p, x_out, basis_out, obj_out, iters_out, status_out);
     if (p->resident) {
         const size_t B = (size_t)p->batch;
         std::vector<double> x(B * p->n);
