@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -79,6 +79,20 @@ int lp_context_sync(lp_context* ctx);
 int lp_simplex_solve(lp_context* ctx, const double* A, int m, int n, const double* b,
                      const double* c, const int* basis_in, int maximize, int n_orig, double eps,
                      int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out);
+
+/* Pivot rules.  DANTZIG (the default everywhere): first largest reduced cost, ratio ties toward the
+ * lowest basis position (SimplexSolover.h:152-196); it can cycle on degenerate LPs.  BLAND: the
+ * smallest eligible non-basic index with d_j > eps (max) / d_j < -eps (min) enters; among the rows
+ * with u_i > eps whose ratio xB_i / u_i is within eps of the smallest, the one whose basic variable
+ * has the smallest index leaves.  Bland's rule never cycles, and usually takes more pivots.  It runs
+ * on LP_SIMPLEX_ALGO_LAUNCH (AUTO picks it) and on the LDS form of the batched kernels.        */
+enum { LP_PIVOT_DANTZIG = 0, LP_PIVOT_BLAND = 1 };
+
+/* lp_simplex_solve with a pivot rule (any other value: LP_BAD_ARG).                             */
+int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                        const double* c, const int* basis_in, int maximize, int n_orig, double eps,
+                        int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                        int pivot_rule);
 
 /* Device-resident form (used by bench.py so that timed regions start with the
  * tableau already in HBM).                                                       */
@@ -127,6 +141,9 @@ int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const doub
 int lp_simplex_reset(lp_simplex_problem* p);
 int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
                    lp_simplex_stats* stats_out);
+/* The pivot rule of the problem's next runs (LP_PIVOT_DANTZIG after upload).  Under LP_PIVOT_BLAND,
+ * AUTO runs LP_SIMPLEX_ALGO_LAUNCH and an explicit RESIDENT, LOOKAHEAD or OVERLAP is LP_BAD_ARG.  */
+int lp_simplex_set_pivot_rule(lp_simplex_problem* p, int pivot_rule);
 /* on != 0: the next runs bracket every tableau-update launch with HIP events so that
  * lp_simplex_stats::update_ms / update_launches are filled (costs ~1-2 us per launch; off by
  * default, in which case those two fields are 0).                                         */
@@ -154,6 +171,11 @@ void lp_simplex_free(lp_simplex_problem* p);
 int lp_simplex_two_phase(lp_context* ctx, const double* A, int m, int n, const double* b,
                          const double* c, int maximize, int n_orig, double eps, int max_iter,
                          double* x_out, int* basis_out, double* obj_out, int* iters_out);
+/* lp_simplex_two_phase with a pivot rule for phase I and phase II (the drive-out is the same).  */
+int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                            const double* c, int maximize, int n_orig, double eps, int max_iter,
+                            double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                            int pivot_rule);
 /* Row `row` (0..m-1 by basis position, m = reduced costs) of the current tableau: n+1 doubles. */
 int lp_simplex_row(lp_simplex_problem* p, int row, double* out);
 /* One Gauss-Jordan pivot at (row, col) of the current tableau, chosen by the caller
@@ -188,6 +210,12 @@ int lp_simplex_solve_batched(lp_context* ctx, int batch, const double* A, int m,
                              const double* b, const double* c, const int* basis_in, int maximize,
                              int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
                              double* obj_out, int* iters_out, int* status_out);
+/* The same with a pivot rule.  Under LP_PIVOT_BLAND the batch runs the kernel's LDS form (every
+ * shape that stays on the GPU fits it); the per-LP fallback passes the rule on.                 */
+int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
+                                const double* b, const double* c, const int* basis_in, int maximize,
+                                int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
+                                double* obj_out, int* iters_out, int* status_out, int pivot_rule);
 
 typedef struct lp_batched_problem lp_batched_problem;
 int lp_batched_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
@@ -197,6 +225,8 @@ int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_ou
 int lp_batched_download(lp_batched_problem* p, double* x_out, int* basis_out, double* obj_out,
                         int* iters_out, int* status_out);
 void lp_batched_free(lp_batched_problem* p);
+/* The pivot rule of the batch's next runs, plain or two-phase (LP_PIVOT_DANTZIG after upload).  */
+int lp_batched_set_pivot_rule(lp_batched_problem* p, int pivot_rule);
 /* BASELINE.json configs[4] "1 -> 8 GPUs": the LPs of a batch are independent, so participant `shard`
  * of `shards` (one process or host thread per GPU) uploads and solves the LPs [*lo, *hi) of the batch
  * and nobody exchanges anything (replicas of the code, no collective; the caller concatenates the
@@ -215,6 +245,11 @@ int lp_simplex_two_phase_batched(lp_context* ctx, int batch, const double* A, in
                                  const double* b, const double* c, int maximize, int n_orig,
                                  double eps, int max_iter, double* x_out, int* basis_out,
                                  double* obj_out, int* iters_out, int* status_out);
+/* The same with a pivot rule for phase I and phase II.                                           */
+int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
+                                    const double* b, const double* c, int maximize, int n_orig,
+                                    double eps, int max_iter, double* x_out, int* basis_out,
+                                    double* obj_out, int* iters_out, int* status_out, int pivot_rule);
 /* Device-resident form: a handle that lp_batched_run / _download / _free accept (run may be
  * repeated; lp_batched_download's iters_out is then the sum of the three counts per LP).          */
 int lp_batched_two_phase_upload(lp_context* ctx, int batch, const double* A, int m, int n,

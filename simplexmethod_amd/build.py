@@ -131,9 +131,31 @@ def build_cpp_tests(force=False, verbose=False):
     return outs
 
 
+TESTS_REF = os.path.join(os.path.dirname(_HERE), "tests", "ref")
+TEST_REF_LIB = os.path.join(TESTS_REF, "_build", "libbland_ref.so")
+
+
+def build_test_ref(force=False, verbose=False):
+    """tests/ref/bland_ref.c -> tests/ref/_build/libbland_ref.so: the pivot-rule restatement the tests
+    compare against (plain C, no GPU; fused multiply-adds only where the source writes fma())."""
+    src = os.path.join(TESTS_REF, "bland_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(TEST_REF_LIB, [src]):
+        return TEST_REF_LIB
+    os.makedirs(os.path.dirname(TEST_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", TEST_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return TEST_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
+    build_test_ref(force, verbose)
     return hip, host
 
 

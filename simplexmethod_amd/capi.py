@@ -16,6 +16,7 @@ OPTIMAL, UNBOUNDED, ITER_LIMIT, SINGULAR, INFEASIBLE, BAD_ARG = range(6)
 SUBSET_FEASIBLE, SUBSET_INFEASIBLE, SUBSET_SINGULAR = range(3)
 SIMPLEX_AUTO, SIMPLEX_LAUNCH, SIMPLEX_LOOKAHEAD, SIMPLEX_RESIDENT, SIMPLEX_OVERLAP = 0, 1, 2, 3, 4
 ENUM_AUTO, ENUM_DIRECT, ENUM_PREFIX = 0, 1, 2
+PIVOT_DANTZIG, PIVOT_BLAND = 0, 1
 U64_MAX = (1 << 64) - 1
 EPS = 1e-9        # Solver::EPS, SimplexSolover.h:13
 MAX_ITER = 10000  # SimplexSolover.h:426
@@ -50,6 +51,9 @@ SIGNATURES = {
                                    C.c_double, C.c_int, _dp, _ip, _dp, _ip]),
     "lp_simplex_upload": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int,
                                     C.POINTER(_vp)]),
+    "lp_simplex_solve_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int,
+                                      C.c_double, C.c_int, _dp, _ip, _dp, _ip, C.c_int]),
+    "lp_simplex_set_pivot_rule": (C.c_int, [_vp, C.c_int]),
     "lp_simplex_reset": (C.c_int, [_vp]),
     "lp_simplex_run": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, C.POINTER(SimplexStats)]),
     "lp_simplex_profile": (C.c_int, [_vp, C.c_int]),
@@ -57,6 +61,8 @@ SIGNATURES = {
     "lp_simplex_free": (None, [_vp]),
     "lp_simplex_two_phase": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int,
                                        C.c_double, C.c_int, _dp, _ip, _dp, _ip]),
+    "lp_simplex_two_phase_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int,
+                                          C.c_double, C.c_int, _dp, _ip, _dp, _ip, C.c_int]),
     "lp_simplex_row": (C.c_int, [_vp, C.c_int, _dp]),
     "lp_simplex_force_pivot": (C.c_int, [_vp, C.c_int, C.c_int]),
     "lp_bench_rank1_update": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp]),
@@ -65,6 +71,10 @@ SIGNATURES = {
     "lp_simplex_solve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip,
                                            C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp,
                                            _ip, _ip]),
+    "lp_simplex_solve_batched_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip,
+                                              C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp,
+                                              _ip, _ip, C.c_int]),
+    "lp_batched_set_pivot_rule": (C.c_int, [_vp, C.c_int]),
     "lp_batched_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
                                     C.c_int, C.POINTER(_vp)]),
     "lp_batched_run": (C.c_int, [_vp, C.c_double, C.c_int, _fp]),
@@ -73,6 +83,9 @@ SIGNATURES = {
     "lp_batched_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip]),
     "lp_simplex_two_phase_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int,
                                                C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _ip, _ip]),
+    "lp_simplex_two_phase_batched_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int,
+                                                  C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _ip, _ip,
+                                                  C.c_int]),
     "lp_batched_two_phase_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int,
                                               C.c_int, C.POINTER(_vp)]),
     "lp_batched_phase_iters": (C.c_int, [_vp, _ip]),
@@ -145,6 +158,17 @@ def load():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def pivot_rule_id(rule):
+    """"dantzig" | "bland" | PIVOT_DANTZIG | PIVOT_BLAND -> the LP_PIVOT_* value (other integers pass through:
+    the library refuses them with LP_BAD_ARG)."""
+    if isinstance(rule, str):
+        names = {"dantzig": PIVOT_DANTZIG, "bland": PIVOT_BLAND}
+        if rule.lower() not in names:
+            raise ValueError(f"unknown pivot rule {rule!r} (expected 'dantzig' or 'bland')")
+        return names[rule.lower()]
+    return int(rule)
 
 
 class LPError(RuntimeError):
@@ -253,7 +277,7 @@ class Context:
         return fast, plain
 
     def simplex_solve(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
-                      max_iter=MAX_ITER):
+                      max_iter=MAX_ITER, pivot_rule="dantzig"):
         A = np.asarray(A, dtype=np.float64)
         m, n = A.shape
         n_orig = n if n_orig is None else n_orig
@@ -263,12 +287,14 @@ class Context:
         bo = np.zeros(m, dtype=np.int32)
         obj = C.c_double(float("nan"))
         it = C.c_int(0)
-        rc = self.check(self.lib.lp_simplex_solve(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis),
-                                                  int(maximize), n_orig, eps, max_iter, _d(x),
-                                                  _i(bo), C.byref(obj), C.byref(it)))
+        rc = self.check(self.lib.lp_simplex_solve_ex(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                     int(maximize), n_orig, eps, max_iter, _d(x),
+                                                     _i(bo), C.byref(obj), C.byref(it),
+                                                     pivot_rule_id(pivot_rule)))
         return dict(status=rc, x=x[:n_orig], basis=bo, obj=obj.value, iters=it.value)
 
-    def two_phase(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+    def two_phase(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER,
+                  pivot_rule="dantzig"):
         """lp_simplex_two_phase: no starting basis needed."""
         A = np.asarray(A, dtype=np.float64)
         m, n = A.shape
@@ -278,16 +304,17 @@ class Context:
         bo = np.full(m, -1, dtype=np.int32)
         obj = C.c_double(float("nan"))
         it = np.zeros(3, dtype=np.int32)
-        rc = self.check(self.lib.lp_simplex_two_phase(self.h, _d(Af), m, n, _d(b), _d(c),
-                                                      int(maximize), n_orig, eps, max_iter, _d(x),
-                                                      _i(bo), C.byref(obj), _i(it)))
+        rc = self.check(self.lib.lp_simplex_two_phase_ex(self.h, _d(Af), m, n, _d(b), _d(c),
+                                                         int(maximize), n_orig, eps, max_iter, _d(x),
+                                                         _i(bo), C.byref(obj), _i(it),
+                                                         pivot_rule_id(pivot_rule)))
         return dict(status=rc, x=x, basis=bo, obj=obj.value, iters=it.tolist())
 
     def simplex_problem(self, A, b, c, basis, maximize=True, n_orig=None):
         return SimplexProblem(self, A, b, c, basis, maximize, n_orig)
 
     def simplex_solve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
-                              max_iter=MAX_ITER):
+                              max_iter=MAX_ITER, pivot_rule="dantzig"):
         """A: (batch, m, n); b: (batch, m); c: (batch, n); basis: (batch, m)."""
         A = np.asarray(A, dtype=np.float64)
         batch, m, n = A.shape
@@ -300,16 +327,17 @@ class Context:
         obj = np.full(batch, np.nan)
         it = np.zeros(batch, dtype=np.int32)
         st = np.zeros(batch, dtype=np.int32)
-        self.check(self.lib.lp_simplex_solve_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c),
-                                                     _i(basis), int(maximize), n_orig, eps,
-                                                     max_iter, _d(x), _i(bo), _d(obj), _i(it),
-                                                     _i(st)))
+        self.check(self.lib.lp_simplex_solve_batched_ex(self.h, batch, _d(Af), m, n, _d(b), _d(c),
+                                                        _i(basis), int(maximize), n_orig, eps,
+                                                        max_iter, _d(x), _i(bo), _d(obj), _i(it),
+                                                        _i(st), pivot_rule_id(pivot_rule)))
         return dict(status=st, x=x, basis=bo, obj=obj, iters=it)
 
     def batched_problem(self, A, b, c, basis, maximize=True, n_orig=None):
         return BatchedProblem(self, A, b, c, basis, maximize, n_orig)
 
-    def two_phase_batched(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+    def two_phase_batched(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER,
+                          pivot_rule="dantzig"):
         """lp_simplex_two_phase_batched: A (batch, m, n), b (batch, m), c (batch, n), no basis;
         per LP exactly two_phase().  iters: (batch, 3) = phase I, drive-out, phase II."""
         A = np.asarray(A, dtype=np.float64)
@@ -322,9 +350,10 @@ class Context:
         obj = np.full(batch, np.nan)
         it = np.zeros((batch, 3), dtype=np.int32)
         st = np.zeros(batch, dtype=np.int32)
-        self.check(self.lib.lp_simplex_two_phase_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c),
-                                                         int(maximize), n_orig, eps, max_iter, _d(x),
-                                                         _i(bo), _d(obj), _i(it), _i(st)))
+        self.check(self.lib.lp_simplex_two_phase_batched_ex(self.h, batch, _d(Af), m, n, _d(b), _d(c),
+                                                            int(maximize), n_orig, eps, max_iter, _d(x),
+                                                            _i(bo), _d(obj), _i(it), _i(st),
+                                                            pivot_rule_id(pivot_rule)))
         return dict(status=st, x=x, basis=bo, obj=obj, iters=it)
 
     def batched_two_phase_problem(self, A, b, c, maximize=False, n_orig=None):
@@ -368,6 +397,10 @@ class SimplexProblem:
 
     def reset(self):
         self.ctx.check(self.ctx.lib.lp_simplex_reset(self.h))
+
+    def set_pivot_rule(self, rule):
+        """"dantzig" (the default after upload) or "bland", for the following runs."""
+        self.ctx.check(self.ctx.lib.lp_simplex_set_pivot_rule(self.h, pivot_rule_id(rule)))
 
     def profile(self, on=True):
         self.ctx.check(self.ctx.lib.lp_simplex_profile(self.h, int(on)))
@@ -439,6 +472,10 @@ class BatchedProblem:
             ctx.check(ctx.lib.lp_batched_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
                                                 _i(basis), int(maximize), self.n_orig, C.byref(h)))
         self.h = h
+
+    def set_pivot_rule(self, rule):
+        """"dantzig" (the default after upload) or "bland", for the following runs."""
+        self.ctx.check(self.ctx.lib.lp_batched_set_pivot_rule(self.h, pivot_rule_id(rule)))
 
     def run(self, eps=EPS, max_iter=MAX_ITER):
         ms = C.c_float(0.0)

@@ -24,7 +24,7 @@ struct BatchedDev {
 
 // batched_simplex.hip
 size_t lp_batched_lds_bytes(int m, int n, int* pitch_out);
-int lp_batched_launch(lp_context* ctx, const BatchedDev& d);
+int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule);   // LP_PIVOT_BLAND: the LDS form
 
 // A batch of same-shape LPs solved by the two-phase flow, one LP per workgroup (batched_two_phase.hip).
 struct BatchedTwoPhaseDev {
@@ -45,4 +45,4 @@ struct BatchedTwoPhaseDev {
 // batched_two_phase.hip
 size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out);
 bool lp_batched_two_phase_fits(int m, int n);
-int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d);
+int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule);

@@ -1,6 +1,7 @@
 // batched_scan.hpp — wave-level pieces shared by the one-LP-per-workgroup kernels
-// (batched_simplex.hip, batched_two_phase.hip): the LDS hand-over words and the order-dependent
-// EPS-hysteresis scans on keyed slots (see the header comment of batched_simplex.hip).
+// (batched_simplex.hip, batched_two_phase.hip): the LDS hand-over words, the order-dependent
+// EPS-hysteresis scans on keyed slots (see the header comment of batched_simplex.hip) and the two
+// selections of Bland's rule on keyed entries.
 #pragma once
 
 #include <cfloat>
@@ -140,6 +141,58 @@ __device__ __forceinline__ int wave_ratio_select(const double (&rv)[K], int m, d
         sel = first;
     }
     return sel;
+}
+
+// ---- Bland's rule (LP_PIVOT_BLAND) on keyed entries, by ONE wave (all 64 lanes) --------------------
+
+// The eligible entry of smallest key: get(s, key, eligible).  Returns its slot, -1 if none.  Pricing
+// (key = variable index, eligible = d > eps / d < -eps) and any other first-index choice.
+template <typename Get>
+__device__ int wave_min_key(int count, Get get) {
+    const int lane = threadIdx.x & 63;
+    int lkey = INT_MAX, lslot = -1;
+    for (int s = lane; s < count; s += 64) {
+        int k;
+        bool ok;
+        get(s, k, ok);
+        if (ok && k < lkey) {
+            lkey = k;
+            lslot = s;
+        }
+    }
+    const int kmin = (int)lpdev::wave_ext_u32<false>((unsigned)lkey);
+    if (kmin == INT_MAX) return -1;
+    return __builtin_amdgcn_readlane(lslot, (int)__builtin_ctzll(__ballot(lkey == kmin)));
+}
+
+// Bland's ratio test over `count` rows: get(i, theta, key) gives row i's ratio (NaN for a row outside
+// R = {u_i > eps}) and the index of its basic variable.  theta* = the smallest ratio; among the rows with
+// theta_i <= theta* + eps the one of smallest key leaves.  Returns the row, -1 if R is empty.  The ratios
+// are computed again on the second pass (same division, same bits).
+template <typename Get>
+__device__ int wave_bland_ratio(int count, double eps, Get get) {
+    const int lane = threadIdx.x & 63;
+    double lmin = INFINITY;
+    for (int i = lane; i < count; i += 64) {
+        double v;
+        int k;
+        get(i, v, k);
+        if (v < lmin) lmin = v;   // (NaN never taken)
+    }
+    const double thr = lpdev::f64_from_key(lpdev::wave_ext_key<false>(lpdev::f64_sort_key(lmin))) + eps;
+    int lkey = INT_MAX, lrow = -1;
+    for (int i = lane; i < count; i += 64) {
+        double v;
+        int k;
+        get(i, v, k);
+        if (v <= thr && k < lkey) {
+            lkey = k;
+            lrow = i;
+        }
+    }
+    const int kmin = (int)lpdev::wave_ext_u32<false>((unsigned)lkey);
+    if (kmin == INT_MAX) return -1;
+    return __builtin_amdgcn_readlane(lrow, (int)__builtin_ctzll(__ballot(lkey == kmin)));
 }
 
 }  // namespace

@@ -158,6 +158,7 @@ struct lp_batched_problem {
     std::vector<double> h_A, h_b;           // per-LP fallback: the inputs ...
     std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
     std::vector<int> h_basis;               // batch*m
+    int pivot_rule = LP_PIVOT_DANTZIG;      // lp_batched_set_pivot_rule: read by every run
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -170,6 +171,14 @@ void lp_batched_free(lp_batched_problem* p) {
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     delete p;
+}
+
+int lp_batched_set_pivot_rule(lp_batched_problem* p, int pivot_rule) {
+    if (!p) return LP_BAD_ARG;
+    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+        LP_FAIL(p->ctx, LP_BAD_ARG, "unknown pivot rule");
+    p->pivot_rule = pivot_rule;
+    return LP_OPTIMAL;
 }
 
 int lp_batched_shard_bounds(int batch, int shard, int shards, int* lo, int* hi) {
@@ -352,7 +361,7 @@ static int batched_two_phase_run(lp_batched_problem* p, double eps, int max_iter
         p->tdev.eps = eps;
         p->tdev.max_iter = max_iter;
         LP_HIP(ctx, hipEventRecord(p->ev0, ctx->stream));
-        int rc = lp_batched_two_phase_launch(ctx, p->tdev);
+        int rc = lp_batched_two_phase_launch(ctx, p->tdev, p->pivot_rule);
         if (rc) return rc;
         LP_HIP(ctx, hipGetLastError());
         LP_HIP(ctx, hipEventRecord(p->ev1, ctx->stream));
@@ -366,10 +375,10 @@ static int batched_two_phase_run(lp_batched_problem* p, double eps, int max_iter
     const auto t0 = std::chrono::steady_clock::now();
     const int m = p->m, n = p->n;
     for (int k = 0; k < p->batch; ++k) {
-        int rc = lp_simplex_two_phase(ctx, p->h_A.data() + (size_t)k * m * n, m, n, p->h_b.data() + (size_t)k * m,
-                                      p->h_c.data() + (size_t)k * n, p->maximize, p->n_orig, eps, max_iter,
-                                      p->h_x.data() + (size_t)k * p->n_orig, p->h_basis.data() + (size_t)k * m,
-                                      p->h_obj.data() + k, p->phase_iters.data() + (size_t)k * 3);
+        int rc = lp_simplex_two_phase_ex(ctx, p->h_A.data() + (size_t)k * m * n, m, n, p->h_b.data() + (size_t)k * m,
+                                         p->h_c.data() + (size_t)k * n, p->maximize, p->n_orig, eps, max_iter,
+                                         p->h_x.data() + (size_t)k * p->n_orig, p->h_basis.data() + (size_t)k * m,
+                                         p->h_obj.data() + k, p->phase_iters.data() + (size_t)k * 3, p->pivot_rule);
         if (rc < 0 || rc > LP_INFEASIBLE) return rc;
         p->status[(size_t)k] = rc;
     }
@@ -436,11 +445,21 @@ int lp_simplex_two_phase_batched(lp_context* ctx, int batch, const double* A, in
                                  const double* b, const double* c, int maximize, int n_orig,
                                  double eps, int max_iter, double* x_out, int* basis_out,
                                  double* obj_out, int* iters_out, int* status_out) {
+    return lp_simplex_two_phase_batched_ex(ctx, batch, A, m, n, b, c, maximize, n_orig, eps, max_iter, x_out,
+                                           basis_out, obj_out, iters_out, status_out, LP_PIVOT_DANTZIG);
+}
+
+int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
+                                    const double* b, const double* c, int maximize, int n_orig,
+                                    double eps, int max_iter, double* x_out, int* basis_out,
+                                    double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: null argument");
+    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_batched_problem* p = nullptr;
     int rc = lp_batched_two_phase_upload(ctx, batch, A, m, n, b, c, maximize, n_orig, &p);
     if (rc) return rc;
+    p->pivot_rule = pivot_rule;
     rc = lp_batched_run(p, eps, max_iter, nullptr);
     if (rc == LP_OPTIMAL) rc = lp_batched_download(p, x_out, basis_out, obj_out, nullptr, status_out);
     if (rc == LP_OPTIMAL && iters_out) rc = lp_batched_phase_iters(p, iters_out);
@@ -462,7 +481,7 @@ int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_ou
             p->dev.stamps_reg = std::strcmp(sv, "reg") == 0;
         }
         LP_HIP(ctx, hipEventRecord(p->ev0, ctx->stream));
-        int rc = lp_batched_launch(ctx, p->dev);
+        int rc = lp_batched_launch(ctx, p->dev, p->pivot_rule);
         if (rc) return rc;
         LP_HIP(ctx, hipEventRecord(p->ev1, ctx->stream));
         LP_HIP(ctx, hipEventSynchronize(p->ev1));
@@ -503,6 +522,7 @@ int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_ou
         lp_simplex_stats st;
         int rc = lp_simplex_reset(p->lps[(size_t)k]);
         if (rc) return rc;
+        p->lps[(size_t)k]->pivot_rule = p->pivot_rule;
         rc = lp_simplex_run(p->lps[(size_t)k], eps, max_iter, LP_SIMPLEX_ALGO_AUTO, &st);
         if (rc < 0) return rc;
         p->status[(size_t)k] = rc;
@@ -563,9 +583,20 @@ int lp_simplex_solve_batched(lp_context* ctx, int batch, const double* A, int m,
                              const double* b, const double* c, const int* basis_in, int maximize,
                              int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
                              double* obj_out, int* iters_out, int* status_out) {
+    return lp_simplex_solve_batched_ex(ctx, batch, A, m, n, b, c, basis_in, maximize, n_orig, eps, max_iter, x_out,
+                                       basis_out, obj_out, iters_out, status_out, LP_PIVOT_DANTZIG);
+}
+
+int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
+                                const double* b, const double* c, const int* basis_in, int maximize,
+                                int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
+                                double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
+    if (ctx && pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+        LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_batched_problem* p = nullptr;
     int rc = lp_batched_upload(ctx, batch, A, m, n, b, c, basis_in, maximize, n_orig, &p);
     if (rc) return rc;
+    p->pivot_rule = pivot_rule;
     rc = lp_batched_run(p, eps, max_iter, nullptr);
     if (rc == LP_OPTIMAL) rc = lp_batched_download(p, x_out, basis_out, obj_out, iters_out, status_out);
     lp_batched_free(p);

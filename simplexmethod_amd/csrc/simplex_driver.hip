@@ -428,6 +428,11 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
         return p->init_status;
     }
     const bool asked_auto = algo == LP_SIMPLEX_ALGO_AUTO;
+    if (p->pivot_rule == LP_PIVOT_BLAND) {   // Bland's selector exists for the launch pair only
+        if (algo == LP_SIMPLEX_ALGO_AUTO) algo = LP_SIMPLEX_ALGO_LAUNCH;
+        if (algo == LP_SIMPLEX_ALGO_RESIDENT || algo == LP_SIMPLEX_ALGO_LOOKAHEAD || algo == LP_SIMPLEX_ALGO_OVERLAP)
+            LP_FAIL(ctx, LP_BAD_ARG, "Bland's pivot rule runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
+    }
     if (algo == LP_SIMPLEX_ALGO_AUTO)
         algo = p->res.G >= 1 ? LP_SIMPLEX_ALGO_RESIDENT
                : p->look.J >= 3 ? LP_SIMPLEX_ALGO_LOOKAHEAD   // (depth 2, 1536 x 3072: 20.0 us per pivot against the overlapped path's 18.4)
@@ -465,6 +470,14 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
         stats_out->fell_back = (asked == LP_SIMPLEX_ALGO_RESIDENT && p->last_algo != LP_SIMPLEX_ALGO_RESIDENT) ? 1 : 0;
     }
     return rc;
+}
+
+int lp_simplex_set_pivot_rule(lp_simplex_problem* p, int pivot_rule) {
+    if (!p) return LP_BAD_ARG;
+    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+        LP_FAIL(p->ctx, LP_BAD_ARG, "unknown pivot rule");
+    p->pivot_rule = pivot_rule;
+    return LP_OPTIMAL;
 }
 
 int lp_simplex_profile(lp_simplex_problem* p, int on) {
@@ -516,11 +529,21 @@ int lp_simplex_download(lp_simplex_problem* p, double* x_out, int* basis_out, do
 int lp_simplex_solve(lp_context* ctx, const double* A, int m, int n, const double* b,
                      const double* c, const int* basis_in, int maximize, int n_orig, double eps,
                      int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out) {
+    return lp_simplex_solve_ex(ctx, A, m, n, b, c, basis_in, maximize, n_orig, eps, max_iter, x_out, basis_out,
+                               obj_out, iters_out, LP_PIVOT_DANTZIG);
+}
+
+int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                        const double* c, const int* basis_in, int maximize, int n_orig, double eps,
+                        int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                        int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "x_out is null");
+    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A, m, n, b, c, basis_in, maximize, n_orig, &p);
     if (rc) return rc;
+    p->pivot_rule = pivot_rule;
     lp_simplex_stats st;
     rc = lp_simplex_run(p, eps, max_iter, LP_SIMPLEX_ALGO_AUTO, &st);
     if (iters_out) *iters_out = st.pivots;
@@ -558,8 +581,17 @@ int lp_simplex_force_pivot(lp_simplex_problem* p, int row, int col) {
 int lp_simplex_two_phase(lp_context* ctx, const double* A, int m, int n, const double* b,
                          const double* c, int maximize, int n_orig, double eps, int max_iter,
                          double* x_out, int* basis_out, double* obj_out, int* iters_out) {
+    return lp_simplex_two_phase_ex(ctx, A, m, n, b, c, maximize, n_orig, eps, max_iter, x_out, basis_out, obj_out,
+                                   iters_out, LP_PIVOT_DANTZIG);
+}
+
+int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                            const double* c, int maximize, int n_orig, double eps, int max_iter,
+                            double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                            int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!A || !b || !c || !x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: null argument");
+    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: bad dimensions");
     const int na = n + m;
     std::vector<double> A1((size_t)m * na, 0.0), b1((size_t)m), c1((size_t)na, 0.0), xa((size_t)na);
@@ -599,6 +631,7 @@ int lp_simplex_two_phase(lp_context* ctx, const double* A, int m, int n, const d
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
     if (rc) return rc;
+    p->pivot_rule = pivot_rule;   // phase I and phase II; the drive-out has its own rule
     stage("upload");
     lp_simplex_stats st;
     rc = lp_simplex_run(p, eps, max_iter, LP_SIMPLEX_ALGO_AUTO, &st);

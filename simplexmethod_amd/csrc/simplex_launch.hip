@@ -138,6 +138,137 @@ __global__ __launch_bounds__(1024) void k_simplex_select(SimplexDev d) {
 }
 
 // ---------------------------------------------------------------------------
+// select under Bland's rule (LP_PIVOT_BLAND): same launch shape, LDS and staging as
+// k_simplex_select; only the two choices differ.
+//   entering: the smallest non-basic j with d_j > eps (max) / d_j < -eps (min) — a first-hit
+//             min-index reduction by wave 0, one tile of 64*K entries at a time, stopping at the
+//             first tile with a hit;
+//   leaving:  R = {i : u_i > eps}, theta* = min over R of xB_i / u_i, then the row of the tie set
+//             {i in R : theta_i <= theta* + eps} whose basic variable has the smallest index.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_simplex_select_bland(SimplexDev d) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_u = s_dyn;
+    double* s_ratio = s_dyn + (d.m + 2);
+    int* s_int = reinterpret_cast<int*>(s_dyn + 2 * (d.m + 2));
+    int& s_enter = s_int[0];
+    int& s_leave = s_int[1];
+    int& s_flag = s_int[2];
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    const double* drow = d.T + (size_t)m * ld;
+    if (tid < 64) {
+        constexpr int K = 16;
+        int e = INT_MAX;
+        for (int base = 0; base < n && e == INT_MAX; base += 64 * K) {
+            int first = INT_MAX;
+#pragma unroll
+            for (int k = K - 1; k >= 0; --k) {   // (descending: the lane keeps its smallest hit)
+                const int j = base + k * 64 + tid;
+                if (j < n && d.nonbasic[j]) {
+                    const double v = drow[j];
+                    if (d.maximize ? (v > eps) : (v < -eps)) first = j;
+                }
+            }
+            e = lpdev::wave_min_i32(first);
+        }
+        if (tid == 0) {
+            s_enter = e == INT_MAX ? -1 : e;
+            s_flag = 0;
+        }
+    }
+    __syncthreads();
+    const int e = s_enter;
+    if (e < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // u = column e; rows outside R hold NaN, which neither the min nor the tie test takes
+    int any_pos = 0;
+    for (int i = tid; i <= m; i += blockDim.x) {
+        const double ui = d.T[(size_t)i * ld + e];
+        s_u[i] = ui;
+        if (i < m) {
+            s_ratio[i] = (ui > eps) ? d.T[(size_t)i * ld + n] / ui : NAN;
+            if (!(ui <= eps)) any_pos = 1;
+        }
+    }
+    if (any_pos) s_flag = 1;
+    __syncthreads();
+    if (!s_flag) {
+        if (tid == 0) {
+            st->status = LP_UNBOUNDED;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    if (tid < 64) {
+        double lmin = INFINITY;
+        for (int i = tid; i < m; i += 64) {
+            const double v = s_ratio[i];
+            if (v < lmin) lmin = v;
+        }
+        const double thr = lpdev::wave_ext_f64<false>(lmin) + eps;   // theta* + eps
+        int key = INT_MAX, pos = -1;
+        for (int i = tid; i < m; i += 64)
+            if (s_ratio[i] <= thr && d.basis[i] < key) {
+                key = d.basis[i];
+                pos = i;
+            }
+        const int kmin = lpdev::wave_min_i32(key);
+        int r = -1;
+        if (kmin != INT_MAX) r = __builtin_amdgcn_readlane(pos, (int)__builtin_ctzll(__ballot(key == kmin)));
+        if (tid == 0) s_leave = r;
+    }
+    __syncthreads();
+    const int r = s_leave;
+    if (r < 0) {
+        if (tid == 0) {
+            st->status = LP_UNBOUNDED;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    const double ur = s_u[r];
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_u[i] / ur;
+    const double* trow = d.T + (size_t)r * ld;
+    for (int j = tid; j < ld; j += blockDim.x) d.prow[j] = trow[j];
+    if (tid == 0) {
+        const int old = d.basis[r];
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // rank-1 Gauss-Jordan update: T_i += l_i * T_r (i != r), T_r *= 1/u_r; column e
 // becomes the exact unit vector.  HBM-bound: every element read once, written
 // once (16*m*(n+1) algorithmic bytes per pivot).  Each thread owns one 16-B
@@ -511,10 +642,15 @@ int lp_simplex_crash(lp_simplex_problem* p) {
 
 static size_t select_lds_bytes(const SimplexDev& d) { return 2 * sizeof(double) * (size_t)(d.m + 2) + 16; }
 
+static const void* select_kernel(const lp_simplex_problem* p) {
+    return p->pivot_rule == LP_PIVOT_BLAND ? reinterpret_cast<const void*>(k_simplex_select_bland)
+                                           : reinterpret_cast<const void*>(k_simplex_select);
+}
+
 int lp_launch_prepare(lp_simplex_problem* p) {
     const size_t shm = select_lds_bytes(p->dev);
     if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
-    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select), shm));   // (m > 3070)
+    LP_HIP(p->ctx, lp_lds_opt_in(select_kernel(p), shm));   // (m > 3070)
     return LP_OPTIMAL;
 }
 
@@ -525,8 +661,12 @@ int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter) {
 
 int lp_launch_queue(lp_simplex_problem* p, int batch) {
     const size_t shm = select_lds_bytes(p->dev);
+    const bool bland = p->pivot_rule == LP_PIVOT_BLAND;
     for (int k = 0; k < batch; ++k) {
-        hipLaunchKernelGGL(k_simplex_select, 1, 1024, shm, p->ctx->stream, p->dev);
+        if (bland)
+            hipLaunchKernelGGL(k_simplex_select_bland, 1, 1024, shm, p->ctx->stream, p->dev);
+        else
+            hipLaunchKernelGGL(k_simplex_select, 1, 1024, shm, p->ctx->stream, p->dev);
         lp_simplex_launch_update(p);
     }
     return 2 * batch;

@@ -89,6 +89,7 @@ struct lp_simplex_problem {
     int last_status = -100;
     int last_iters = 0;
     int last_algo = 0;            // LP_SIMPLEX_ALGO_* of the last run (which stamp buffer is current)
+    int pivot_rule = LP_PIVOT_DANTZIG;   // lp_simplex_set_pivot_rule: read by every run
 };
 
 // simplex_driver.hip: the host side of a solve (upload, dispatch, the batch-and-poll loop, the stats record)
@@ -104,7 +105,7 @@ hipError_t lp_lds_opt_in(const void* kernel, size_t bytes);
 // Each path's launch surface.  begin() queues the state-init launches of a run and returns how many it queued;
 // queue(batch) queues `batch` pivots and returns the launches queued (a negative value is a HIP error).
 
-// simplex_launch.hip: one select + one rank-1-update launch per pivot
+// simplex_launch.hip: one select + one rank-1-update launch per pivot (the selector of p->pivot_rule)
 int lp_launch_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, opted in
 int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter);
 int lp_launch_queue(lp_simplex_problem* p, int batch);

@@ -31,7 +31,14 @@ public:
         int status = LP_OPTIMAL;
     };
 
+    // The pivot rule of solve() and twoPhaseSimplex(): Dantzig's (the reference's, the default) or Bland's,
+    // which never cycles on degenerate problems and usually takes more pivots (include/simplexmethod_amd.h).
+    enum class PivotRule { Dantzig = LP_PIVOT_DANTZIG, Bland = LP_PIVOT_BLAND };
+
     explicit Solver(const Canonical& problem, int device = 0) : _problem(problem), _device(device) {}
+
+    void setPivotRule(PivotRule rule) { _rule = rule; }
+    PivotRule pivotRule() const { return _rule; }
 
     // Throws std::runtime_error (unbounded / iteration limit / singular basis) like the
     // reference (:126, :443, :450).
@@ -48,9 +55,10 @@ public:
         Result r;
         r.x = lpla::VectorXd::Zero(n_orig);
         r.basis.assign((size_t)m, -1);
-        r.status = lp_simplex_solve(ctx, A.data(), m, n, b.data(), c.data(), basis.data(),
-                                    _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
-                                    r.x.data(), r.basis.data(), &r.objective, &r.iterations);
+        r.status = lp_simplex_solve_ex(ctx, A.data(), m, n, b.data(), c.data(), basis.data(),
+                                       _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
+                                       r.x.data(), r.basis.data(), &r.objective, &r.iterations,
+                                       static_cast<int>(_rule));
         if (throw_on_failure) lpgpu::throw_for_status(r.status, ctx);
         return r;
     }
@@ -74,9 +82,10 @@ public:
         r.x = lpla::VectorXd::Zero(n_orig);
         r.basis.assign((size_t)m, -1);
         int it[3] = {0, 0, 0};
-        r.status = lp_simplex_two_phase(ctx, A.data(), m, n, b.data(), c.data(),
-                                        _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
-                                        r.x.data(), r.basis.data(), &r.objective, it);
+        r.status = lp_simplex_two_phase_ex(ctx, A.data(), m, n, b.data(), c.data(),
+                                           _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
+                                           r.x.data(), r.basis.data(), &r.objective, it,
+                                           static_cast<int>(_rule));
         r.iterations = it[0] + it[1] + it[2];
         if (phase_iterations)
             for (int k = 0; k < 3; ++k) phase_iterations[k] = it[k];
@@ -87,4 +96,5 @@ public:
 private:
     Canonical _problem;  // deep copy, as in the reference (:285)
     int _device;
+    PivotRule _rule = PivotRule::Dantzig;
 };
