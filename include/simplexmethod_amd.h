@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -176,6 +176,27 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
                             const double* c, int maximize, int n_orig, double eps, int max_iter,
                             double* x_out, int* basis_out, double* obj_out, int* iters_out,
                             int pivot_rule);
+/* ---- Re-solve from a given basis ---------------------------------------------------------------
+ * For the loop solve, change b (tighten a row, branch) or c, solve again from the old optimal basis.
+ * The basis is installed as lp_simplex_upload installs it (the crash; LP_SINGULAR if singular), then:
+ *   - primal feasible (no xB_t < -eps): the plain primal simplex, exactly lp_simplex_run(AUTO);
+ *   - else dual feasible (no non-basic d_j > eps for max, d_j < -eps for min): the dual simplex.  The
+ *     leaving position is the EPS-hysteresis chain (min) over the xB_t < -eps in position order (none:
+ *     LP_OPTIMAL); the entering column the same chain over d_j / T[r][j] (max) or -d_j / T[r][j] (min) of
+ *     the non-basic j with T[r][j] < -eps, in index order (none: LP_INFEASIBLE).  max_iter bounds its pivots;
+ *   - else LP_BAD_ARG: the basis is no valid start.
+ * Dantzig's rule only: a problem or batch set to LP_PIVOT_BLAND returns LP_BAD_ARG.
+ * iters_out: 2 ints per LP = dual pivots, primal pivots (one of them is 0; the crash is not counted).
+ * Note: lp_simplex_solve from a basis that is not primal feasible is NOT a valid re-solve.          */
+/* On an lp_simplex_upload handle (after upload or lp_simplex_reset).  The dual simplex runs the launch
+ * pair per pivot (stats_out->algo_used = LP_SIMPLEX_ALGO_LAUNCH).                                   */
+int lp_simplex_resolve_run(lp_simplex_problem* p, double eps, int max_iter, int* iters_out,
+                           lp_simplex_stats* stats_out);
+/* One-shot: upload, re-solve, download (arguments as lp_simplex_solve; x and obj for LP_OPTIMAL only). */
+int lp_simplex_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                       const int* basis_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                       int* basis_out, double* obj_out, int* iters_out);
+
 /* Row `row` (0..m-1 by basis position, m = reduced costs) of the current tableau: n+1 doubles. */
 int lp_simplex_row(lp_simplex_problem* p, int row, double* out);
 /* One Gauss-Jordan pivot at (row, col) of the current tableau, chosen by the caller
@@ -257,8 +278,28 @@ int lp_batched_two_phase_upload(lp_context* ctx, int batch, const double* A, int
                                 lp_batched_problem** problem_out);
 /* The three pivot counts per LP (batch*3) of the last run; LP_BAD_ARG on a plain batch.          */
 int lp_batched_phase_iters(lp_batched_problem* p, int* iters_out);
-/* 1: one LP per workgroup on the GPU, 0: per-LP fallback (either kind of batch).                 */
+/* 1: one LP per workgroup on the GPU, 0: per-LP fallback (any kind of batch).                    */
 int lp_batched_path(const lp_batched_problem* p);
+
+/* Batched re-solve: `batch` LPs of one shape, each from its given basis, one LP per workgroup; per LP
+ * exactly lp_simplex_resolve.  Inputs as lp_simplex_solve_batched; iters_out batch*2 (dual, primal),
+ * status_out batch (per-LP statuses, LP_BAD_ARG for a basis that is no valid start).  Shapes beyond the
+ * batched two-phase kernel's (lp_simplex_two_phase_batched) are re-solved one LP after another.     */
+int lp_simplex_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                               const double* c, const int* basis_in, int maximize, int n_orig, double eps,
+                               int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                               int* status_out);
+/* Device-resident form: a handle that lp_batched_run (repeatable), _download (iters_out = the sum of the
+ * two counts), _path and _free accept.                                                              */
+int lp_batched_resolve_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                              const double* c, const int* basis_in, int maximize, int n_orig,
+                              lp_batched_problem** problem_out);
+/* Replaces b (batch*m) and/or the starting bases (batch*m) of a re-solve batch; either may be NULL; A and c
+ * stay.  The branch-and-bound loop: download basis_out, change b, set_start, run.  LP_BAD_ARG on a plain
+ * or two-phase batch or for a basis index outside [0, n).                                             */
+int lp_batched_set_start(lp_batched_problem* p, const double* b, const int* basis_in);
+/* The two pivot counts per LP (batch*2: dual, primal) of the last run; LP_BAD_ARG on another kind.   */
+int lp_batched_resolve_iters(lp_batched_problem* p, int* iters_out);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

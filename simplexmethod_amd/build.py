@@ -152,10 +152,31 @@ def build_test_ref(force=False, verbose=False):
     return TEST_REF_LIB
 
 
+RESOLVE_REF_LIB = os.path.join(TESTS_REF, "_build", "libresolve_ref.so")
+
+
+def build_resolve_ref(force=False, verbose=False):
+    """tests/ref/resolve_ref.c -> tests/ref/_build/libresolve_ref.so: the re-solve from a given basis
+    (primal or dual simplex) the tests compare against; flags as build_test_ref."""
+    src = os.path.join(TESTS_REF, "resolve_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(RESOLVE_REF_LIB, [src]):
+        return RESOLVE_REF_LIB
+    os.makedirs(os.path.dirname(RESOLVE_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", RESOLVE_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return RESOLVE_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
     build_test_ref(force, verbose)
+    build_resolve_ref(force, verbose)
     return hip, host
 
 

@@ -90,6 +90,15 @@ SIGNATURES = {
                                               C.c_int, C.POINTER(_vp)]),
     "lp_batched_phase_iters": (C.c_int, [_vp, _ip]),
     "lp_batched_path": (C.c_int, [_vp]),
+    "lp_simplex_resolve_run": (C.c_int, [_vp, C.c_double, C.c_int, _ip, C.POINTER(SimplexStats)]),
+    "lp_simplex_resolve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double,
+                                     C.c_int, _dp, _ip, _dp, _ip]),
+    "lp_simplex_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
+                                             C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _ip, _ip]),
+    "lp_batched_resolve_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
+                                            C.c_int, C.POINTER(_vp)]),
+    "lp_batched_set_start": (C.c_int, [_vp, _dp, _ip]),
+    "lp_batched_resolve_iters": (C.c_int, [_vp, _ip]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -310,6 +319,47 @@ class Context:
                                                          pivot_rule_id(pivot_rule)))
         return dict(status=rc, x=x, basis=bo, obj=obj.value, iters=it.tolist())
 
+    def simplex_resolve(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+        """lp_simplex_resolve: re-solve from `basis` (primal simplex if it is primal feasible, dual simplex if
+        it is only dual feasible).  iters = (dual pivots, primal pivots).  A basis that is neither primal nor dual
+        feasible raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        n_orig = n if n_orig is None else n_orig
+        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        x = np.zeros(max(n_orig, 1))
+        bo = np.zeros(m, dtype=np.int32)
+        obj = C.c_double(float("nan"))
+        it = np.zeros(2, dtype=np.int32)
+        rc = self.check(self.lib.lp_simplex_resolve(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
+                                                    n_orig, eps, max_iter, _d(x), _i(bo), C.byref(obj), _i(it)))
+        return dict(status=rc, x=x[:n_orig], basis=bo, obj=obj.value, iters=(int(it[0]), int(it[1])))
+
+    def resolve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+        """lp_simplex_resolve_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m); per LP
+        exactly simplex_resolve().  iters: (batch, 2) = dual, primal pivots."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        n_orig = n if n_orig is None else n_orig
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        x = np.zeros((batch, n_orig))
+        bo = np.zeros((batch, m), dtype=np.int32)
+        obj = np.full(batch, np.nan)
+        it = np.zeros((batch, 2), dtype=np.int32)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_simplex_resolve_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                       int(maximize), n_orig, eps, max_iter, _d(x), _i(bo), _d(obj),
+                                                       _i(it), _i(st)))
+        return dict(status=st, x=x, basis=bo, obj=obj, iters=it)
+
+    def batched_resolve_problem(self, A, b, c, basis, maximize=True, n_orig=None):
+        """Device-resident re-solve batch (lp_batched_resolve_upload): set_start(), run(), download(),
+        resolve_iters()."""
+        return BatchedProblem(self, A, b, c, basis, maximize, n_orig, resolve=True)
+
     def simplex_problem(self, A, b, c, basis, maximize=True, n_orig=None):
         return SimplexProblem(self, A, b, c, basis, maximize, n_orig)
 
@@ -410,6 +460,13 @@ class SimplexProblem:
         rc = self.ctx.check(self.ctx.lib.lp_simplex_run(self.h, eps, max_iter, algo, C.byref(st)))
         return rc, st
 
+    def resolve(self, eps=EPS, max_iter=MAX_ITER):
+        """lp_simplex_resolve_run on the current tableau: (status, stats, (dual pivots, primal pivots))."""
+        st = SimplexStats()
+        it = np.zeros(2, dtype=np.int32)
+        rc = self.ctx.check(self.ctx.lib.lp_simplex_resolve_run(self.h, eps, max_iter, _i(it), C.byref(st)))
+        return rc, st, (int(it[0]), int(it[1]))
+
     def download(self, trace_cap=0, want_tableau=False):
         x = np.zeros(self.n_orig)
         bo = np.zeros(self.m, dtype=np.int32)
@@ -455,7 +512,7 @@ class SimplexProblem:
 
 
 class BatchedProblem:
-    def __init__(self, ctx, A, b, c, basis, maximize=True, n_orig=None):
+    def __init__(self, ctx, A, b, c, basis, maximize=True, n_orig=None, resolve=False):
         A = np.asarray(A, dtype=np.float64)
         self.ctx = ctx
         self.batch, self.m, self.n = A.shape
@@ -464,7 +521,11 @@ class BatchedProblem:
         b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
         h = _vp()
         self.two_phase = basis is None   # no starting basis: the two-phase flow
-        if self.two_phase:
+        if resolve:
+            basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+            ctx.check(ctx.lib.lp_batched_resolve_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
+                                                        _i(basis), int(maximize), self.n_orig, C.byref(h)))
+        elif self.two_phase:
             ctx.check(ctx.lib.lp_batched_two_phase_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b),
                                                           _d(c), int(maximize), self.n_orig, C.byref(h)))
         else:
@@ -496,6 +557,21 @@ class BatchedProblem:
         """(batch, 3) pivot counts of the last run: phase I, drive-out, phase II (two-phase batches)."""
         it = np.zeros((self.batch, 3), dtype=np.int32)
         self.ctx.check(self.ctx.lib.lp_batched_phase_iters(self.h, _i(it)))
+        return it
+
+    def set_start(self, b=None, basis=None):
+        """Re-solve batches: new right-hand sides (batch, m) and/or starting bases (batch, m); A and c stay."""
+        b = None if b is None else _f64(b).reshape(-1)
+        basis = None if basis is None else np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        for a in (b, basis):
+            if a is not None and a.size != self.batch * self.m:
+                raise ValueError(f"set_start: expected {self.batch * self.m} entries, got {a.size}")
+        self.ctx.check(self.ctx.lib.lp_batched_set_start(self.h, _d(b), _i(basis)))
+
+    def resolve_iters(self):
+        """(batch, 2) pivot counts of the last run: dual, primal (re-solve batches)."""
+        it = np.zeros((self.batch, 2), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.lp_batched_resolve_iters(self.h, _i(it)))
         return it
 
     def path(self):

@@ -46,3 +46,24 @@ struct BatchedTwoPhaseDev {
 size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out);
 bool lp_batched_two_phase_fits(int m, int n);
 int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule);
+
+// A batch of same-shape LPs re-solved from given bases, one LP per workgroup (batched_resolve.hip): the
+// primal simplex when a basis is primal feasible, the dual simplex when it is only dual feasible.
+struct BatchedResolveDev {
+    int batch, m, n;
+    int pitch;              // row pitch (doubles) of the LDS tableau: lp_batched_two_phase_lds_bytes
+    int maximize;
+    int max_iter;
+    double eps;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const int* basis_in;    // batch x m
+    double* x;              // batch x n  (full vertex)
+    int* basis_out;         // batch x m  (by position)
+    int* iters;             // batch x 2  (dual pivots, primal pivots)
+    int* status;            // batch
+};
+
+// batched_resolve.hip (the shapes of lp_batched_two_phase_fits)
+int lp_batched_resolve_launch(lp_context* ctx, const BatchedResolveDev& d);

@@ -136,7 +136,8 @@ int lp_debug_division(lp_context* ctx, const double* num, const double* den, int
 // LDS, go through the single-LP path one after another instead.
 // A batch uploaded by lp_batched_two_phase_upload has no starting basis and runs the
 // two-phase flow, one LP per workgroup (batched_two_phase.hip); shapes that do not fit
-// go through lp_simplex_two_phase one LP after another.
+// go through lp_simplex_two_phase one LP after another.  A batch uploaded by lp_batched_resolve_upload is
+// re-solved from its given bases (batched_resolve.hip).
 // ===========================================================================
 
 struct lp_batched_problem {
@@ -159,6 +160,12 @@ struct lp_batched_problem {
     std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
     std::vector<int> h_basis;               // batch*m
     int pivot_rule = LP_PIVOT_DANTZIG;      // lp_batched_set_pivot_rule: read by every run
+    // re-solve batch (lp_batched_resolve_upload): given bases, two pivot counts per LP; the per-LP fallback keeps
+    // h_A, h_b, h_basis_in and its outputs in h_x, h_obj, h_basis
+    bool resolve = false;
+    BatchedResolveDev rdev{};
+    std::vector<int> resolve_iters;         // batch*2: dual, primal
+    std::vector<int> h_basis_in;            // batch*m
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -426,6 +433,220 @@ static int batched_two_phase_download(lp_batched_problem* p, double* x_out, int*
     return LP_OPTIMAL;
 }
 
+// ===========================================================================
+// re-solve batch: every LP from its given basis, primal or dual simplex (batched_resolve.hip); shapes
+// beyond lp_batched_two_phase_fits go through lp_simplex_upload + lp_simplex_resolve_run one LP after another
+// ===========================================================================
+
+int lp_batched_resolve_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                              const double* c, const int* basis_in, int maximize, int n_orig,
+                              lp_batched_problem** problem_out) {
+    if (!ctx || !problem_out) return LP_BAD_ARG;
+    *problem_out = nullptr;
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    for (int k = 0; k < batch; ++k) {
+        int rc = check_canonical(ctx, A ? A + (size_t)k * m * n : nullptr, m, n,
+                                 b ? b + (size_t)k * m : nullptr, c ? c + (size_t)k * n : nullptr,
+                                 basis_in ? basis_in + (size_t)k * m : nullptr, n_orig);
+        if (rc) return rc;
+    }
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    lp_batched_problem* p = new lp_batched_problem();
+    p->ctx = ctx;
+    p->resolve = true;
+    p->batch = batch;
+    p->m = m;
+    p->n = n;
+    p->n_orig = n_orig;
+    p->maximize = maximize ? 1 : 0;
+    const size_t B = (size_t)batch;
+    p->status.assign(B, -100);
+    p->resolve_iters.assign(B * 2, 0);
+    p->h_c.assign(c, c + B * n);
+    p->resident = lp_batched_two_phase_fits(m, n);
+    if (!p->resident) {   // per-LP fallback: keep the inputs for lp_simplex_resolve_run
+        p->h_A.assign(A, A + B * m * n);
+        p->h_b.assign(b, b + B * m);
+        p->h_basis_in.assign(basis_in, basis_in + B * m);
+        p->h_x.assign(B * n_orig, 0.0);
+        p->h_obj.assign(B, 0.0);
+        p->h_basis.assign(basis_in, basis_in + B * m);
+        *problem_out = p;
+        return LP_OPTIMAL;
+    }
+#define LP_TRY(expr)                        \
+    do {                                    \
+        hipError_t _e = (expr);             \
+        if (_e != hipSuccess) {             \
+            ctx->last_error = #expr;        \
+            lp_batched_free(p);             \
+            return -(int)_e;                \
+        }                                   \
+    } while (0)
+    hipStream_t s = ctx->stream;
+    LP_TRY(hipMalloc(&p->dA, sizeof(double) * B * m * n));
+    LP_TRY(hipMalloc(&p->db, sizeof(double) * B * m));
+    LP_TRY(hipMalloc(&p->dc, sizeof(double) * B * n));
+    LP_TRY(hipMalloc(&p->dx, sizeof(double) * B * n));
+    LP_TRY(hipMalloc(&p->dbasis_in, sizeof(int) * B * m));
+    LP_TRY(hipMalloc(&p->dbasis_out, sizeof(int) * B * m));
+    LP_TRY(hipMalloc(&p->diters, sizeof(int) * B * 2));
+    LP_TRY(hipMalloc(&p->dstatus, sizeof(int) * B));
+    LP_TRY(hipEventCreate(&p->ev0));
+    LP_TRY(hipEventCreate(&p->ev1));
+    LP_TRY(hipMemcpyAsync(p->dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s));
+    LP_TRY(hipMemcpyAsync(p->db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s));
+    LP_TRY(hipMemcpyAsync(p->dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s));
+    LP_TRY(hipMemcpyAsync(p->dbasis_in, basis_in, sizeof(int) * B * m, hipMemcpyHostToDevice, s));
+    LP_TRY(hipStreamSynchronize(s));
+#undef LP_TRY
+    BatchedResolveDev& d = p->rdev;
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_batched_two_phase_lds_bytes(m, n, &d.pitch);
+    d.maximize = p->maximize;
+    d.A = p->dA;
+    d.b = p->db;
+    d.c = p->dc;
+    d.basis_in = p->dbasis_in;
+    d.x = p->dx;
+    d.basis_out = p->dbasis_out;
+    d.iters = p->diters;
+    d.status = p->dstatus;
+    *problem_out = p;
+    return LP_OPTIMAL;
+}
+
+int lp_batched_set_start(lp_batched_problem* p, const double* b, const int* basis_in) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!p->resolve) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_set_start: not a re-solve batch");
+    const size_t B = (size_t)p->batch, m = (size_t)p->m;
+    if (basis_in)
+        for (size_t k = 0; k < B * m; ++k)
+            if (basis_in[k] < 0 || basis_in[k] >= p->n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    if (!p->resident) {
+        if (b) p->h_b.assign(b, b + B * m);
+        if (basis_in) p->h_basis_in.assign(basis_in, basis_in + B * m);
+        return LP_OPTIMAL;
+    }
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if (b) LP_HIP(ctx, hipMemcpyAsync(p->db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s));
+    if (basis_in) LP_HIP(ctx, hipMemcpyAsync(p->dbasis_in, basis_in, sizeof(int) * B * m, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipStreamSynchronize(s));
+    return LP_OPTIMAL;
+}
+
+static int batched_resolve_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
+    lp_context* ctx = p->ctx;
+    if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "the re-solve runs Dantzig's rule only");
+    if (p->resident) {
+        p->rdev.eps = eps;
+        p->rdev.max_iter = max_iter;
+        LP_HIP(ctx, hipEventRecord(p->ev0, ctx->stream));
+        int rc = lp_batched_resolve_launch(ctx, p->rdev);
+        if (rc) return rc;
+        LP_HIP(ctx, hipGetLastError());
+        LP_HIP(ctx, hipEventRecord(p->ev1, ctx->stream));
+        LP_HIP(ctx, hipEventSynchronize(p->ev1));
+        float ms = 0.f;
+        LP_HIP(ctx, hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        if (ms_out) *ms_out = ms;
+        return LP_OPTIMAL;
+    }
+    // per-LP fallback: the single-LP re-solve one LP after another (host clock)
+    const auto t0 = std::chrono::steady_clock::now();
+    const int m = p->m, n = p->n, no = p->n_orig;
+    for (int k = 0; k < p->batch; ++k) {
+        lp_simplex_problem* q = nullptr;
+        int rc = lp_simplex_upload(ctx, p->h_A.data() + (size_t)k * m * n, m, n, p->h_b.data() + (size_t)k * m,
+                                   p->h_c.data() + (size_t)k * n, p->h_basis_in.data() + (size_t)k * m, p->maximize,
+                                   no, &q);
+        if (rc) return rc;
+        rc = lp_simplex_resolve_run(q, eps, max_iter, p->resolve_iters.data() + (size_t)k * 2, nullptr);
+        if (rc >= 0) {
+            const bool ok = rc == LP_OPTIMAL;
+            const int drc = lp_simplex_download(q, ok ? p->h_x.data() + (size_t)k * no : nullptr,
+                                                p->h_basis.data() + (size_t)k * m, ok ? p->h_obj.data() + k : nullptr,
+                                                nullptr, nullptr, 0, nullptr);
+            if (drc) rc = drc;
+        }
+        lp_simplex_free(q);
+        if (rc < 0) return rc;
+        p->status[(size_t)k] = rc;
+    }
+    ctx->last_error.clear();   // (a basis that is no valid start is a per-LP status here)
+    if (ms_out) *ms_out = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return LP_OPTIMAL;
+}
+
+static int batched_resolve_download(lp_batched_problem* p, double* x_out, int* basis_out, double* obj_out,
+                                    int* iters_out, int* status_out) {
+    lp_context* ctx = p->ctx;
+    const size_t B = (size_t)p->batch;
+    const int m = p->m, n = p->n, no = p->n_orig;
+    std::vector<double> x;
+    if (p->resident) {
+        x.resize(B * n);
+        hipStream_t s = ctx->stream;
+        LP_HIP(ctx, hipMemcpyAsync(x.data(), p->dx, sizeof(double) * B * n, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipMemcpyAsync(p->status.data(), p->dstatus, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipMemcpyAsync(p->resolve_iters.data(), p->diters, sizeof(int) * B * 2, hipMemcpyDeviceToHost, s));
+        if (basis_out) LP_HIP(ctx, hipMemcpyAsync(basis_out, p->dbasis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s));
+        LP_HIP(ctx, hipStreamSynchronize(s));
+    } else if (basis_out) {
+        std::memcpy(basis_out, p->h_basis.data(), sizeof(int) * B * m);
+    }
+    for (size_t k = 0; k < B; ++k) {
+        const bool ok = p->status[k] == LP_OPTIMAL;
+        if (p->resident && ok) {
+            const double* xk = x.data() + k * n;
+            if (x_out)
+                for (int j = 0; j < no; ++j) x_out[k * no + j] = xk[j];
+            if (obj_out) {  // Canonical::Evaluate, Canonical.cpp:86
+                double z = 0.0;
+                const double* ck = p->h_c.data() + k * n;
+                for (int j = 0; j < n; ++j) z += ck[j] * xk[j];
+                obj_out[k] = z;
+            }
+        } else if (ok) {
+            if (x_out) std::memcpy(x_out + k * no, p->h_x.data() + k * no, sizeof(double) * no);
+            if (obj_out) obj_out[k] = p->h_obj[k];
+        }
+        if (iters_out) iters_out[k] = p->resolve_iters[k * 2] + p->resolve_iters[k * 2 + 1];
+        if (status_out) status_out[k] = p->status[k];
+    }
+    return LP_OPTIMAL;
+}
+
+int lp_batched_resolve_iters(lp_batched_problem* p, int* iters_out) {
+    if (!p || !iters_out) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!p->resolve) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_resolve_iters: not a re-solve batch");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    if (p->resident) LP_HIP(ctx, hipMemcpy(p->resolve_iters.data(), p->diters, sizeof(int) * 2 * (size_t)p->batch, hipMemcpyDeviceToHost));
+    std::memcpy(iters_out, p->resolve_iters.data(), sizeof(int) * 2 * (size_t)p->batch);
+    return LP_OPTIMAL;
+}
+
+int lp_simplex_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                               const double* c, const int* basis_in, int maximize, int n_orig, double eps,
+                               int max_iter, double* x_out, int* basis_out, double* obj_out, int* iters_out,
+                               int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_resolve_batched: null argument");
+    lp_batched_problem* p = nullptr;
+    int rc = lp_batched_resolve_upload(ctx, batch, A, m, n, b, c, basis_in, maximize, n_orig, &p);
+    if (rc) return rc;
+    rc = lp_batched_run(p, eps, max_iter, nullptr);
+    if (rc == LP_OPTIMAL) rc = lp_batched_download(p, x_out, basis_out, obj_out, nullptr, status_out);
+    if (rc == LP_OPTIMAL && iters_out) rc = lp_batched_resolve_iters(p, iters_out);
+    lp_batched_free(p);
+    return rc;
+}
+
 int lp_batched_phase_iters(lp_batched_problem* p, int* iters_out) {
     if (!p || !iters_out) return LP_BAD_ARG;
     lp_context* ctx = p->ctx;
@@ -472,6 +693,7 @@ int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_ou
     lp_context* ctx = p->ctx;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     if (p->two_phase) return batched_two_phase_run(p, eps, max_iter, ms_out);
+    if (p->resolve) return batched_resolve_run(p, eps, max_iter, ms_out);
     if (p->resident) {
         p->dev.eps = eps;
         p->dev.max_iter = max_iter;
@@ -539,6 +761,7 @@ int lp_batched_download(lp_batched_problem* p, double* x_out, int* basis_out, do
     lp_context* ctx = p->ctx;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     if (p->two_phase) return batched_two_phase_download(p, x_out, basis_out, obj_out, iters_out, status_out);
+    if (p->resolve) return batched_resolve_download(p, x_out, basis_out, obj_out, iters_out, status_out);
     if (p->resident) {
         const size_t B = (size_t)p->batch;
         std::vector<double> x(B * p->n);

@@ -104,6 +104,20 @@ int run_launch(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats
     return record_run(p, LP_SIMPLEX_ALGO_LAUNCH, launches, ms, 0.f, 0, stats);
 }
 
+// The dual simplex of a re-solve: the dual selector + rank-1 update pair per pivot, polled as run_launch.
+int run_dual(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
+    int rc = lp_dual_prepare(p);
+    if (rc) return rc;
+    LP_HIP(p->ctx, hipEventRecord(p->ev0, p->ctx->stream));
+    int launches = lp_launch_begin(p, eps, max_iter);
+    rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return lp_dual_queue(p, batch); });
+    if (rc) return rc;
+    float ms = 0.f;
+    rc = close_window(p, &ms);
+    if (rc) return rc;
+    return record_run(p, LP_SIMPLEX_ALGO_LAUNCH, launches, ms, 0.f, 0, stats);
+}
+
 int run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
     lp_context* ctx = p->ctx;
     int rc = lp_lookahead_prepare(p);
@@ -472,6 +486,37 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
     return rc;
 }
 
+int lp_simplex_resolve_run(lp_simplex_problem* p, double eps, int max_iter, int* iters_out,
+                           lp_simplex_stats* stats_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+    if (iters_out) iters_out[0] = iters_out[1] = 0;
+    if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "the re-solve runs Dantzig's rule only");
+    if (p->init_status != LP_OPTIMAL) {   // the crash found the basis singular
+        if (stats_out) stats_out->status = p->init_status;
+        p->last_status = p->init_status;
+        return p->init_status;
+    }
+    int flags = 0;
+    int rc = lp_simplex_classify(p, eps, &flags);
+    if (rc) return rc;
+    if (!(flags & 1)) {   // primal feasible: the plain solve, every algorithm AUTO may pick
+        rc = lp_simplex_run(p, eps, max_iter, LP_SIMPLEX_ALGO_AUTO, stats_out);
+        if (iters_out && rc >= 0) iters_out[1] = p->last_iters;
+        return rc;
+    }
+    if (flags & 2) LP_FAIL(ctx, LP_BAD_ARG, "re-solve: the basis is neither primal nor dual feasible");
+    rc = run_dual(p, eps, max_iter, stats_out);
+    if (stats_out) {
+        stats_out->algo_used = LP_SIMPLEX_ALGO_LAUNCH;
+        stats_out->fell_back = 0;
+    }
+    if (iters_out && rc >= 0) iters_out[0] = p->last_iters;
+    return rc;
+}
+
 int lp_simplex_set_pivot_rule(lp_simplex_problem* p, int pivot_rule) {
     if (!p) return LP_BAD_ARG;
     if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
@@ -547,6 +592,25 @@ int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const do
     lp_simplex_stats st;
     rc = lp_simplex_run(p, eps, max_iter, LP_SIMPLEX_ALGO_AUTO, &st);
     if (iters_out) *iters_out = st.pivots;
+    if (rc == LP_OPTIMAL) {
+        rc = lp_simplex_download(p, x_out, basis_out, obj_out, nullptr, nullptr, 0, nullptr);
+    } else if (rc > 0 && basis_out) {
+        (void)lp_simplex_download(p, nullptr, basis_out, nullptr, nullptr, nullptr, 0, nullptr);
+    }
+    lp_simplex_free(p);
+    return rc;
+}
+
+int lp_simplex_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                       const int* basis_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                       int* basis_out, double* obj_out, int* iters_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "x_out is null");
+    if (iters_out) iters_out[0] = iters_out[1] = 0;
+    lp_simplex_problem* p = nullptr;
+    int rc = lp_simplex_upload(ctx, A, m, n, b, c, basis_in, maximize, n_orig, &p);
+    if (rc) return rc;
+    rc = lp_simplex_resolve_run(p, eps, max_iter, iters_out, nullptr);
     if (rc == LP_OPTIMAL) {
         rc = lp_simplex_download(p, x_out, basis_out, obj_out, nullptr, nullptr, 0, nullptr);
     } else if (rc > 0 && basis_out) {

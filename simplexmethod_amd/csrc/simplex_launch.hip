@@ -269,6 +269,108 @@ __global__ __launch_bounds__(1024) void k_simplex_select_bland(SimplexDev d) {
 }
 
 // ---------------------------------------------------------------------------
+// select of the DUAL simplex (lp_simplex_resolve_run on a basis that is dual but not primal feasible):
+// same launch shape, LDS and staging as k_simplex_select, so k_simplex_update applies the pivot.
+//   leaving:  r = the EPS-hysteresis chain (min) over xB_i with xB_i < -eps, i in position order (column n,
+//             stride ld); none: optimal;
+//   entering: e = the same chain over q_j = d_j / T[r][j] (max) or -d_j / T[r][j] (min) of the non-basic j
+//             with T[r][j] < -eps, in index order; none: infeasible (row r sums non-negative terms to xB_r < 0).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_simplex_select_dual(SimplexDev d) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_u = s_dyn;
+    int* s_int = reinterpret_cast<int*>(s_dyn + 2 * (d.m + 2));
+    int& s_enter = s_int[0];
+    int& s_leave = s_int[1];
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    if (tid < 64) {
+        double best;
+        auto load_x = [&](int i, bool& ok) {
+            const double v = d.T[(size_t)i * ld + n];
+            ok = v < -eps;
+            return v;
+        };
+        const int r = lpdev::wave_chain_select<false>(m, eps, best, load_x);
+        int e = -1;
+        if (r >= 0) {
+            const double* trow = d.T + (size_t)r * ld;
+            const double* drow = d.T + (size_t)m * ld;
+            auto load_q = [&](int j, bool& ok) {
+                const double a = trow[j];
+                ok = d.nonbasic[j] != 0 && a < -eps;
+                return d.maximize ? drow[j] / a : -drow[j] / a;
+            };
+            e = lpdev::wave_chain_select<false>(n, eps, best, load_q);
+        }
+        if (tid == 0) {
+            s_leave = r;
+            s_enter = e;
+        }
+    }
+    __syncthreads();
+    const int r = s_leave, e = s_enter;
+    if (r < 0 || e < 0) {
+        if (tid == 0) {
+            st->status = r < 0 ? LP_OPTIMAL : LP_INFEASIBLE;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    for (int i = tid; i <= m; i += blockDim.x) s_u[i] = d.T[(size_t)i * ld + e];
+    __syncthreads();
+    const double ur = s_u[r];
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_u[i] / ur;
+    const double* trow = d.T + (size_t)r * ld;
+    for (int j = tid; j < ld; j += blockDim.x) d.prow[j] = trow[j];
+    if (tid == 0) {
+        const int old = d.basis[r];
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+// Which loop a re-solve runs, from the current tableau: st->pad0 = bit 0 primal infeasible (some xB_i < -eps),
+// bit 1 dual infeasible (some non-basic d_j > eps for max, d_j < -eps for min).  One workgroup.
+__global__ __launch_bounds__(1024) void k_simplex_classify(SimplexDev d, double eps) {
+    const int tid = threadIdx.x, m = d.m, n = d.n, ld = d.ld;
+    int pinf = 0, dinf = 0;
+    for (int i = tid; i < m; i += blockDim.x)
+        if (d.T[(size_t)i * ld + n] < -eps) pinf = 1;
+    const double* drow = d.T + (size_t)m * ld;
+    for (int j = tid; j < n; j += blockDim.x)
+        if (d.nonbasic[j] && (d.maximize ? (drow[j] > eps) : (drow[j] < -eps))) dinf = 1;
+    pinf = __syncthreads_or(pinf);
+    dinf = __syncthreads_or(dinf);
+    if (tid == 0) d.state->pad0 = (pinf ? 1 : 0) | (dinf ? 2 : 0);
+}
+
+// ---------------------------------------------------------------------------
 // rank-1 Gauss-Jordan update: T_i += l_i * T_r (i != r), T_r *= 1/u_r; column e
 // becomes the exact unit vector.  HBM-bound: every element read once, written
 // once (16*m*(n+1) algorithmic bytes per pivot).  Each thread owns one 16-B
@@ -678,4 +780,33 @@ int lp_simplex_extract_x(lp_simplex_problem* p, double* dx) {
     hipLaunchKernelGGL(k_extract_x, lp_ceil_div(d.n, 256), 256, 0, s, d, dx);
     hipLaunchKernelGGL(k_scatter_x, lp_ceil_div(d.m, 256), 256, 0, s, d, dx);
     return LP_OPTIMAL;
+}
+
+// ---- the re-solve (lp_simplex_resolve_run): classification, then the dual selector + rank-1 update pairs
+
+int lp_simplex_classify(lp_simplex_problem* p, double eps, int* flags) {
+    lp_context* ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_simplex_classify, 1, 1024, 0, s, p->dev, eps);
+    LP_HIP(ctx, hipMemcpyAsync(p->h_state, p->dev.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
+    LP_HIP(ctx, hipStreamSynchronize(s));
+    LP_HIP(ctx, hipGetLastError());
+    *flags = p->h_state->pad0;
+    return LP_OPTIMAL;
+}
+
+int lp_dual_prepare(lp_simplex_problem* p) {
+    const size_t shm = select_lds_bytes(p->dev);
+    if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_dual), shm));
+    return LP_OPTIMAL;
+}
+
+int lp_dual_queue(lp_simplex_problem* p, int batch) {
+    const size_t shm = select_lds_bytes(p->dev);
+    for (int k = 0; k < batch; ++k) {
+        hipLaunchKernelGGL(k_simplex_select_dual, 1, 1024, shm, p->ctx->stream, p->dev);
+        lp_simplex_launch_update(p);
+    }
+    return 2 * batch;
 }

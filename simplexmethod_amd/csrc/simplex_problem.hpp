@@ -117,6 +117,12 @@ int lp_simplex_driveout(lp_simplex_problem* p, const int* positions, int count, 
 int lp_simplex_phase2_costs(lp_simplex_problem* p, const double* cost, int n_real, int maximize, int n_orig);
 int lp_simplex_extract_x(lp_simplex_problem* p, double* dx);
 
+// simplex_launch.hip: the re-solve from a given basis (lp_simplex_resolve_run).  classify: *flags = bit 0 primal
+// infeasible, bit 1 dual infeasible (one host sync); the dual path then queues the dual selector + rank-1 update.
+int lp_simplex_classify(lp_simplex_problem* p, double eps, int* flags);
+int lp_dual_prepare(lp_simplex_problem* p);
+int lp_dual_queue(lp_simplex_problem* p, int batch);
+
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS
 int lp_lookahead_prepare(lp_simplex_problem* p);
