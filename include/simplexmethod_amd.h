@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -300,6 +300,34 @@ int lp_batched_resolve_upload(lp_context* ctx, int batch, const double* A, int m
 int lp_batched_set_start(lp_batched_problem* p, const double* b, const int* basis_in);
 /* The two pivot counts per LP (batch*2: dual, primal) of the last run; LP_BAD_ARG on another kind.   */
 int lp_batched_resolve_iters(lp_batched_problem* p, int* iters_out);
+
+/* ---- Dual solution at a basis ------------------------------------------------------------------
+ * Shadow prices y (m), reduced costs d (n) and the dual objective w for the LP (A, b, c) as given and a
+ * basis of m column indices (by position); the optimisation sense does not matter: y_i = dz/db_i.
+ *   1. T = [B^T | c_B] (m x (m+1)): row t is column basis[t] of A followed by c[basis[t]];
+ *   2. lp_simplex_upload's crash on T with the identity basis 0..m-1 (column t pivots on the unused row of
+ *      first-max |T[i][t]|; LP_SINGULAR when minp <= DBL_EPSILON*m*maxp, or for a repeated index);
+ *      y[t] = the right-hand side of the row that column t pivoted on;
+ *   3. d[j] = c[j] - sum_i A[i][j] y[i], one fused multiply-add chain per column in row order; basic columns
+ *      exactly 0.0;  4. w = b^T y, one chain in row order.
+ * At an optimal basis: max problems have d <= eps, min problems d >= -eps, and w = c^T x.  A basis index
+ * outside [0, n) is LP_BAD_ARG.  y, d and w are NaN for an LP whose status is not LP_OPTIMAL.  The bits do not
+ * depend on the path.  Every output pointer is required.                                              */
+/* One LP; returns its status (LP_OPTIMAL, LP_SINGULAR, LP_BAD_ARG).                                   */
+int lp_basis_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                   const int* basis, double* y_out, double* d_out, double* w_out);
+/* `batch` LPs of one shape (arrays concatenated per LP as in lp_simplex_solve_batched; y_out batch*m,
+ * d_out batch*n, w_out batch), one LP per workgroup when lp_basis_duals_fits(m), else one LP after
+ * another; per-LP statuses in status_out (an index out of range: LP_BAD_ARG for that LP).             */
+int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                           const double* c, const int* basis, double* y_out, double* d_out, double* w_out,
+                           int* status_out);
+/* The duals of every LP of a batch handle (plain, two-phase or re-solve) at its final basis after
+ * lp_batched_run, read where the run left A, b, c and the bases.  LPs whose run status is not LP_OPTIMAL
+ * keep it in status_out and get NaN.  LP_BAD_ARG before the first run.                                */
+int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out);
+/* 1: m fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: m <= 140), 0 otherwise.               */
+int lp_basis_duals_fits(int m);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

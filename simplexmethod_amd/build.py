@@ -172,11 +172,32 @@ def build_resolve_ref(force=False, verbose=False):
     return RESOLVE_REF_LIB
 
 
+DUALS_REF_LIB = os.path.join(TESTS_REF, "_build", "libduals_ref.so")
+
+
+def build_duals_ref(force=False, verbose=False):
+    """tests/ref/duals_ref.c -> tests/ref/_build/libduals_ref.so: the dual solution at a given basis the
+    tests compare against; flags as build_test_ref."""
+    src = os.path.join(TESTS_REF, "duals_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(DUALS_REF_LIB, [src]):
+        return DUALS_REF_LIB
+    os.makedirs(os.path.dirname(DUALS_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", DUALS_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return DUALS_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
     build_test_ref(force, verbose)
     build_resolve_ref(force, verbose)
+    build_duals_ref(force, verbose)
     return hip, host
 
 

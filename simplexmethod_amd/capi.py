@@ -99,6 +99,10 @@ SIGNATURES = {
                                             C.c_int, C.POINTER(_vp)]),
     "lp_batched_set_start": (C.c_int, [_vp, _dp, _ip]),
     "lp_batched_resolve_iters": (C.c_int, [_vp, _ip]),
+    "lp_basis_duals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "lp_basis_duals_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _ip]),
+    "lp_batched_duals": (C.c_int, [_vp, _dp, _dp, _dp, _ip]),
+    "lp_basis_duals_fits": (C.c_int, [C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -363,6 +367,38 @@ class Context:
     def simplex_problem(self, A, b, c, basis, maximize=True, n_orig=None):
         return SimplexProblem(self, A, b, c, basis, maximize, n_orig)
 
+    # ---- the dual solution at a basis --------------------------------------------------------
+    def basis_duals(self, A, b, c, basis):
+        """lp_basis_duals: shadow prices y (m), reduced costs d (n) and w = b.y of the LP (A, b, c) at `basis`.
+        dict(status, y, d, w); y, d, w are NaN unless status is OPTIMAL.  An index out of range raises LPError
+        with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        y, d, w = np.zeros(m), np.zeros(n), C.c_double(0.0)
+        rc = self.check(self.lib.lp_basis_duals(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), _d(y), _d(d),
+                                                C.byref(w)))
+        return dict(status=rc, y=y, d=d, w=w.value)
+
+    def basis_duals_batched(self, A, b, c, basis):
+        """lp_basis_duals_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).
+        dict(status (batch), y (batch, m), d (batch, n), w (batch))."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        y, d, w = np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_basis_duals_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis), _d(y),
+                                                   _d(d), _d(w), _i(st)))
+        return dict(status=st, y=y, d=d, w=w)
+
+    def basis_duals_fits(self, m):
+        """lp_basis_duals_fits: True if m runs the one-LP-per-workgroup kernel."""
+        return bool(self.lib.lp_basis_duals_fits(m))
+
     def simplex_solve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
                               max_iter=MAX_ITER, pivot_rule="dantzig"):
         """A: (batch, m, n); b: (batch, m); c: (batch, n); basis: (batch, m)."""
@@ -573,6 +609,14 @@ class BatchedProblem:
         it = np.zeros((self.batch, 2), dtype=np.int32)
         self.ctx.check(self.ctx.lib.lp_batched_resolve_iters(self.h, _i(it)))
         return it
+
+    def duals(self):
+        """lp_batched_duals after run(): dict(status (batch), y (batch, m), d (batch, n), w (batch)) at each LP's
+        final basis; LPs whose run status is not OPTIMAL keep it and get NaN."""
+        y, d, w = np.zeros((self.batch, self.m)), np.zeros((self.batch, self.n)), np.zeros(self.batch)
+        st = np.zeros(self.batch, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.lp_batched_duals(self.h, _d(y), _d(d), _d(w), _i(st)))
+        return dict(status=st, y=y, d=d, w=w)
 
     def path(self):
         """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""

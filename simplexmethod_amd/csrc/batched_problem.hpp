@@ -67,3 +67,26 @@ struct BatchedResolveDev {
 
 // batched_resolve.hip (the shapes of lp_batched_two_phase_fits)
 int lp_batched_resolve_launch(lp_context* ctx, const BatchedResolveDev& d);
+
+// The dual solution at given bases, one LP per workgroup (basis_duals.hip): y = B^-T c_B by the crash on
+// [B^T | c_B], d = c - A^T y, w = b^T y.
+struct BasisDualsDev {
+    int batch, m, n;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const int* basis;       // batch x m (by position)
+    const int* run_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it and gets NaN
+    double* y;              // batch x m
+    double* d;              // batch x n
+    double* w;              // batch
+    int* status;            // batch
+};
+
+// basis_duals.hip
+size_t lp_basis_duals_lds_bytes(int m);
+int lp_basis_duals_launch(lp_context* ctx, const BasisDualsDev& d);   // lp_basis_duals_fits(m) shapes
+// One LP of any m on the device (the basis in range): the crash by the single-LP launch pair, then the reduced
+// costs; dA .. dbasis and dy, dd, dw are device pointers.  Returns LP_OPTIMAL / LP_SINGULAR (outputs untouched).
+int lp_basis_duals_device(lp_context* ctx, const double* dA, int m, int n, const double* db, const double* dc,
+                          const int* dbasis, double* dy, double* dd, double* dw);

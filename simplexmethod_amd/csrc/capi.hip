@@ -166,6 +166,7 @@ struct lp_batched_problem {
     BatchedResolveDev rdev{};
     std::vector<int> resolve_iters;         // batch*2: dual, primal
     std::vector<int> h_basis_in;            // batch*m
+    bool ran = false;                       // a run completed: lp_batched_duals has final bases to read
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -228,7 +229,9 @@ int lp_batched_upload(lp_context* ctx, int batch, const double* A, int m, int n,
     int pitch = 0;
     const size_t lds = lp_batched_lds_bytes(m, n, &pitch);
     p->resident = identity && lds <= 160 * 1024;
-    if (!p->resident) {
+    if (!p->resident) {   // per-LP fallback; the inputs are kept for lp_batched_duals
+        p->h_A.assign(A, A + (size_t)batch * m * n);
+        p->h_b.assign(b, b + (size_t)batch * m);
         for (int k = 0; k < batch; ++k) {
             lp_simplex_problem* q = nullptr;
             int rc = lp_simplex_upload(ctx, A + (size_t)k * m * n, m, n, b + (size_t)k * m,
@@ -688,8 +691,7 @@ int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A,
     return rc;
 }
 
-int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
-    if (!p) return LP_BAD_ARG;
+static int batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
     lp_context* ctx = p->ctx;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     if (p->two_phase) return batched_two_phase_run(p, eps, max_iter, ms_out);
@@ -753,6 +755,13 @@ int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_ou
     }
     if (ms_out) *ms_out = total;
     return LP_OPTIMAL;
+}
+
+int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
+    if (!p) return LP_BAD_ARG;
+    const int rc = batched_run(p, eps, max_iter, ms_out);
+    p->ran = rc == LP_OPTIMAL;
+    return rc;
 }
 
 int lp_batched_download(lp_batched_problem* p, double* x_out, int* basis_out, double* obj_out,
@@ -824,6 +833,176 @@ int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int
     if (rc == LP_OPTIMAL) rc = lp_batched_download(p, x_out, basis_out, obj_out, iters_out, status_out);
     lp_batched_free(p);
     return rc;
+}
+
+// ===========================================================================
+// the dual solution at a given basis (basis_duals.hip): one LP per workgroup for lp_basis_duals_fits(m), the
+// single-LP launch pair one LP after another beyond it
+// ===========================================================================
+
+int lp_basis_duals_fits(int m) { return m > 0 && lp_basis_duals_lds_bytes(m) <= 160 * 1024 ? 1 : 0; }
+
+// Duals of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): LPs whose run status is
+// not LP_OPTIMAL keep it and get NaN.  Outputs to the host.
+static int duals_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
+                           const double* dc, const int* dbasis, const int* drun_status, double* y_out, double* d_out,
+                           double* w_out, int* status_out) {
+    hipStream_t s = ctx->stream;
+    const size_t B = (size_t)batch;
+    const size_t bytes = sizeof(double) * B * ((size_t)m + n + 1) + sizeof(int) * B;
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, bytes));
+    BasisDualsDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.basis = dbasis;
+    d.run_status = drun_status;
+    d.y = reinterpret_cast<double*>(buf);
+    d.d = d.y + B * m;
+    d.w = d.d + B * n;
+    d.status = reinterpret_cast<int*>(d.w + B);
+    int rc = LP_OPTIMAL;
+    if (lp_basis_duals_fits(m)) {
+        rc = lp_basis_duals_launch(ctx, d);
+    } else {   // one LP after another: statuses and bases checked on the host
+        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
+        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && drun_status)
+            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            LP_HIP(ctx, e);
+        }
+        for (size_t k = 0; k < B && rc >= 0; ++k) {
+            if (st[k] == LP_OPTIMAL)
+                for (int t = 0; t < m; ++t)
+                    if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
+            if (st[k] != LP_OPTIMAL) continue;
+            rc = lp_basis_duals_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
+                                       d.y + k * m, d.d + k * n, d.w + k);
+            if (rc >= 0) st[k] = rc;
+        }
+        if (rc >= 0) {
+            rc = LP_OPTIMAL;
+            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = -(int)e;
+        }
+    }
+    if (rc == LP_OPTIMAL) {
+        hipError_t e = hipMemcpyAsync(y_out, d.y, sizeof(double) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_out, d.d, sizeof(double) * B * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(w_out, d.w, sizeof(double) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("basis duals: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    }
+    (void)hipFree(buf);
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without duals: NaN (the per-LP path leaves their outputs unwritten)
+    for (size_t k = 0; k < B; ++k) {
+        if (status_out[k] == LP_OPTIMAL) continue;
+        for (int t = 0; t < m; ++t) y_out[k * m + t] = NAN;
+        for (int j = 0; j < n; ++j) d_out[k * n + j] = NAN;
+        w_out[k] = NAN;
+    }
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` LPs, then duals_on_device.
+static int duals_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                        const int* basis, double* y_out, double* d_out, double* w_out, int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    int* dbasis = reinterpret_cast<int*>(dc + B * n);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = LP_OPTIMAL;
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("basis duals upload: ") + hipGetErrorString(e);
+        rc = -(int)e;
+    } else {
+        rc = duals_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, y_out, d_out, w_out, status_out);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int lp_basis_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                   const int* basis, double* y_out, double* d_out, double* w_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: bad dimensions");
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    int status = LP_OPTIMAL;
+    const int rc = duals_upload(ctx, 1, A, m, n, b, c, basis, y_out, d_out, w_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                           const double* c, const int* basis, double* y_out, double* d_out, double* w_out,
+                           int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: bad dimensions");
+    return duals_upload(ctx, batch, A, m, n, b, c, basis, y_out, d_out, w_out, status_out);
+}
+
+int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!y_out || !d_out || !w_out || !status_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: null argument");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: the batch has not run");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int m = p->m, n = p->n;
+    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
+        return duals_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, y_out, d_out,
+                               w_out, status_out);
+    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
+    std::vector<int> basis((size_t)m);
+    for (size_t k = 0; k < (size_t)p->batch; ++k) {
+        double* y = y_out + k * m;
+        double* d = d_out + k * n;
+        int st = p->status[k];
+        if (st == LP_OPTIMAL) {
+            if (p->two_phase || p->resolve) {
+                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
+            } else {
+                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+            }
+            st = lp_basis_duals(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m, p->h_c.data() + k * n,
+                                basis.data(), y, d, w_out + k);
+            if (st < 0) return st;
+        }
+        status_out[k] = st;
+        if (st != LP_OPTIMAL) {
+            for (int t = 0; t < m; ++t) y[t] = NAN;
+            for (int j = 0; j < n; ++j) d[j] = NAN;
+            w_out[k] = NAN;
+        }
+    }
+    ctx->last_error.clear();
+    return LP_OPTIMAL;
 }
 
 }  // extern "C"

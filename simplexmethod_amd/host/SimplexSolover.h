@@ -12,6 +12,7 @@
 // problem's basis indices and needs no feasible starting basis.
 #pragma once
 
+#include <limits>
 #include <stdexcept>
 #include <vector>
 
@@ -91,6 +92,42 @@ public:
             for (int k = 0; k < 3; ++k) phase_iterations[k] = it[k];
         if (throw_on_failure) lpgpu::throw_for_status(r.status, ctx);
         return r;
+    }
+
+    // The dual solution at a result's final basis (lp_basis_duals): shadow prices y (dz/db for max and min
+    // alike), reduced costs d = c - A^T y (exactly 0 on the basis) and the dual objective b.y.  At an optimum
+    // of a max problem d <= EPS, of a min problem d >= -EPS, and objective equals the primal objective.
+    // status: LP_OPTIMAL, LP_SINGULAR (y, d and objective NaN); a result that is not LP_OPTIMAL keeps its
+    // status and gets NaN.
+    struct Duals {
+        lpla::VectorXd y, d;
+        double objective = 0.0;
+        int status = LP_OPTIMAL;
+    };
+
+    Duals duals(const Result& r) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        Duals out;
+        out.y = lpla::VectorXd::Zero(m);
+        out.d = lpla::VectorXd::Zero(n);
+        out.status = r.status;
+        if (r.status == LP_OPTIMAL) {
+            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::duals: basis size != rows(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.status = lp_basis_duals(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(), out.y.data(),
+                                        out.d.data(), &out.objective);
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        if (out.status != LP_OPTIMAL) {
+            for (int i = 0; i < m; ++i) out.y[i] = nan;
+            for (int j = 0; j < n; ++j) out.d[j] = nan;
+            out.objective = nan;
+        }
+        return out;
     }
 
 private:
