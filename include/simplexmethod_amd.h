@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -328,6 +328,44 @@ int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, i
 int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out);
 /* 1: m fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: m <= 140), 0 otherwise.               */
 int lp_basis_duals_fits(int m);
+
+/* ---- RHS and cost ranging at a basis -----------------------------------------------------------
+ * How far each b_i and each c_j can move, one at a time, before the given basis (m column indices by position)
+ * stops being primal (b) or dual (c) feasible, and the variable that leaves or enters at each end.  The ranges
+ * describe the basis passed in: its optimality is not checked (as lp_basis_duals).  At a degenerate optimum a
+ * range can be narrower than the interval over which the optimal value stays linear.  Everything in fp64:
+ *   1. B^-1 and xB by lp_basis_duals's crash applied to [B | I | b] (B's column t = A's column basis[t]);
+ *   2. d: exactly lp_basis_duals's reduced costs;  3. alpha[t][j] = (B^-1 A)[t][j] for non-basic j, one fused
+ *      multiply-add chain per entry in row order;
+ *   4. row i: r_t = -xB[t] / B^-1[t][i]; over t with B^-1[t][i] > eps the lower end b_i + max r_t, over t with
+ *      B^-1[t][i] < -eps the upper end b_i + min r_t; the leaving column basis[t] at each end;
+ *   5. non-basic column j: max problem [-inf, c_j - d_j], min problem [c_j - d_j, +inf] (the finite end enters j).
+ *      Basic column basis[t]: rho_j = d_j / alpha[t][j] over non-basic j with |alpha| > eps; max problem:
+ *      alpha > eps gives the lower end c + max rho, alpha < -eps the upper end c + min rho (a min problem swaps
+ *      the sides); the entering column j at each end.
+ * The first index wins a tie (its own value is reported, signed zeros included).  An empty side is -inf / +inf
+ * with index -1.  Outputs come in interleaved pairs: [2k] lower end, [2k+1] upper end.  LP_SINGULAR when either
+ * crash is singular; LP_BAD_ARG for a basis index outside [0, n) or eps < 0 / NaN.  Values are NaN and indices -1
+ * for an LP whose status is not LP_OPTIMAL.  The bits do not depend on the path.  Every output pointer is required. */
+/* One LP; returns its status (LP_OPTIMAL, LP_SINGULAR, LP_BAD_ARG).  rhs_out / rhs_var_out 2m, cost_out /
+ * cost_var_out 2n.                                                                                     */
+int lp_basis_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                     const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                     double* cost_out, int* cost_var_out);
+/* `batch` LPs of one shape and sense (arrays concatenated per LP as in lp_basis_duals_batched; outputs batch*2m and
+ * batch*2n), one LP per workgroup when lp_basis_ranging_fits(m, n), else one LP after another; per-LP statuses in
+ * status_out.                                                                                          */
+int lp_basis_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                             const double* c, const int* basis, int maximize, double eps, double* rhs_out,
+                             int* rhs_var_out, double* cost_out, int* cost_var_out, int* status_out);
+/* The ranges of every LP of a batch handle (plain, two-phase or re-solve) at its final basis after lp_batched_run,
+ * for the LP as the caller gave it (rows a two-phase run sign-flipped never show) and the handle's sense.  LPs
+ * whose run status is not LP_OPTIMAL keep it in status_out and get NaN.  LP_BAD_ARG before the first run.  */
+int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* rhs_var_out, double* cost_out,
+                       int* cost_var_out, int* status_out);
+/* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: m <= 132 for n = m, 128 x 256, and every
+ * batched two-phase / re-solve shape with m <= 132), 0 otherwise.                                      */
+int lp_basis_ranging_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

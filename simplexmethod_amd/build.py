@@ -192,12 +192,33 @@ def build_duals_ref(force=False, verbose=False):
     return DUALS_REF_LIB
 
 
+RANGING_REF_LIB = os.path.join(TESTS_REF, "_build", "libranging_ref.so")
+
+
+def build_ranging_ref(force=False, verbose=False):
+    """tests/ref/ranging_ref.c (which includes duals_ref.c) -> tests/ref/_build/libranging_ref.so: RHS and cost
+    ranging at a given basis the tests compare against; flags as build_duals_ref."""
+    src = os.path.join(TESTS_REF, "ranging_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(RANGING_REF_LIB, [src, os.path.join(TESTS_REF, "duals_ref.c")]):
+        return RANGING_REF_LIB
+    os.makedirs(os.path.dirname(RANGING_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", RANGING_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return RANGING_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
     build_test_ref(force, verbose)
     build_resolve_ref(force, verbose)
     build_duals_ref(force, verbose)
+    build_ranging_ref(force, verbose)
     return hip, host
 
 

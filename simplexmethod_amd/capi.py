@@ -103,6 +103,12 @@ SIGNATURES = {
     "lp_basis_duals_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _ip]),
     "lp_batched_duals": (C.c_int, [_vp, _dp, _dp, _dp, _ip]),
     "lp_basis_duals_fits": (C.c_int, [C.c_int]),
+    "lp_basis_ranging": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_double, _dp, _ip, _dp,
+                                   _ip]),
+    "lp_basis_ranging_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_double,
+                                           _dp, _ip, _dp, _ip, _ip]),
+    "lp_batched_ranging": (C.c_int, [_vp, C.c_double, _dp, _ip, _dp, _ip, _ip]),
+    "lp_basis_ranging_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -241,6 +247,15 @@ def gen_lp(seed, m, n):
     c[:no] = u[no * m + m:]
     basis = np.arange(no, n, dtype=np.int32)
     return A, b, c, basis
+
+
+def _ranging_dict(status, rhs, rhs_var, cost, cost_var):
+    """Interleaved (lower, upper) pairs of the ranging calls -> dict(status, b_lo, b_hi, b_leave, c_lo, c_hi,
+    c_enter); the last axis of b_leave / c_enter is (lower end, upper end)."""
+    return dict(status=status, b_lo=rhs[..., 0::2], b_hi=rhs[..., 1::2],
+                b_leave=rhs_var.reshape(rhs_var.shape[:-1] + (-1, 2)),
+                c_lo=cost[..., 0::2], c_hi=cost[..., 1::2],
+                c_enter=cost_var.reshape(cost_var.shape[:-1] + (-1, 2)))
 
 
 class Context:
@@ -398,6 +413,42 @@ class Context:
     def basis_duals_fits(self, m):
         """lp_basis_duals_fits: True if m runs the one-LP-per-workgroup kernel."""
         return bool(self.lib.lp_basis_duals_fits(m))
+
+    # ---- RHS and cost ranging at a basis ------------------------------------------------------
+    def basis_ranging(self, A, b, c, basis, maximize=True, eps=EPS):
+        """lp_basis_ranging: how far each b_i and c_j can move before `basis` stops being feasible / optimal.
+        dict(status, b_lo, b_hi (m), b_leave (m, 2), c_lo, c_hi (n), c_enter (n, 2)): the ends and the leaving /
+        entering column at each (-1 for an infinite end); NaN and -1 unless status is OPTIMAL.  An index out of
+        range or a negative eps raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        rhs, cost = np.zeros(2 * m), np.zeros(2 * n)
+        rv, cv = np.zeros(2 * m, np.int32), np.zeros(2 * n, np.int32)
+        rc = self.check(self.lib.lp_basis_ranging(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
+                                                  float(eps), _d(rhs), _i(rv), _d(cost), _i(cv)))
+        return _ranging_dict(rc, rhs, rv, cost, cv)
+
+    def basis_ranging_batched(self, A, b, c, basis, maximize=True, eps=EPS):
+        """lp_basis_ranging_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).  The dict of
+        basis_ranging with a leading batch axis; status (batch)."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        rhs, cost = np.zeros((batch, 2 * m)), np.zeros((batch, 2 * n))
+        rv, cv = np.zeros((batch, 2 * m), np.int32), np.zeros((batch, 2 * n), np.int32)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_basis_ranging_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                     int(maximize), float(eps), _d(rhs), _i(rv), _d(cost), _i(cv),
+                                                     _i(st)))
+        return _ranging_dict(st, rhs, rv, cost, cv)
+
+    def basis_ranging_fits(self, m, n):
+        """lp_basis_ranging_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
+        return bool(self.lib.lp_basis_ranging_fits(m, n))
 
     def simplex_solve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
                               max_iter=MAX_ITER, pivot_rule="dantzig"):
@@ -617,6 +668,16 @@ class BatchedProblem:
         st = np.zeros(self.batch, dtype=np.int32)
         self.ctx.check(self.ctx.lib.lp_batched_duals(self.h, _d(y), _d(d), _d(w), _i(st)))
         return dict(status=st, y=y, d=d, w=w)
+
+    def ranging(self, eps=EPS):
+        """lp_batched_ranging after run(): the dict of Context.basis_ranging_batched at each LP's final basis and the
+        handle's sense; LPs whose run status is not OPTIMAL keep it and get NaN."""
+        B, m, n = self.batch, self.m, self.n
+        rhs, cost = np.zeros((B, 2 * m)), np.zeros((B, 2 * n))
+        rv, cv = np.zeros((B, 2 * m), np.int32), np.zeros((B, 2 * n), np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.lp_batched_ranging(self.h, float(eps), _d(rhs), _i(rv), _d(cost), _i(cv), _i(st)))
+        return _ranging_dict(st, rhs, rv, cost, cv)
 
     def path(self):
         """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""

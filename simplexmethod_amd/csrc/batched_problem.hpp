@@ -90,3 +90,32 @@ int lp_basis_duals_launch(lp_context* ctx, const BasisDualsDev& d);   // lp_basi
 // costs; dA .. dbasis and dy, dd, dw are device pointers.  Returns LP_OPTIMAL / LP_SINGULAR (outputs untouched).
 int lp_basis_duals_device(lp_context* ctx, const double* dA, int m, int n, const double* db, const double* dc,
                           const int* dbasis, double* dy, double* dd, double* dw);
+
+// RHS and cost ranging at given bases, one LP per workgroup (basis_ranging.hip): B^-1 and xB by the crash on
+// [B | I | b] (kept in place), d as basis_duals.hip, alpha = B^-1 A_N, then the ratio reductions.  Outputs in
+// interleaved pairs (lower end, upper end).
+struct BasisRangingDev {
+    int batch, m, n;
+    int maximize;
+    double eps;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const int* basis;       // batch x m (by position)
+    const int* run_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it and gets NaN
+    double* rhs;            // batch x 2m
+    int* rhs_var;           // batch x 2m: the leaving column at each end
+    double* cost;           // batch x 2n
+    int* cost_var;          // batch x 2n: the entering column at each end
+    int* status;            // batch
+};
+
+// basis_ranging.hip
+size_t lp_basis_ranging_lds_bytes(int m, int n);
+int lp_basis_ranging_launch(lp_context* ctx, const BasisRangingDev& d);   // lp_basis_ranging_fits(m, n) shapes
+// One LP of any shape on the device (the basis in range, eps >= 0): the crash on [B | I | b] by the single-LP launch
+// pair, d by lp_basis_duals_device, B^-1 A, then the reductions; every pointer is a device pointer.  Returns
+// LP_OPTIMAL / LP_SINGULAR (outputs untouched).
+int lp_basis_ranging_device(lp_context* ctx, const double* dA, int m, int n, const double* db, const double* dc,
+                            const int* dbasis, int maximize, double eps, double* drhs, int* drhs_var, double* dcost,
+                            int* dcost_var);

@@ -166,7 +166,7 @@ struct lp_batched_problem {
     BatchedResolveDev rdev{};
     std::vector<int> resolve_iters;         // batch*2: dual, primal
     std::vector<int> h_basis_in;            // batch*m
-    bool ran = false;                       // a run completed: lp_batched_duals has final bases to read
+    bool ran = false;                       // a run completed: lp_batched_duals / _ranging have final bases to read
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -229,6 +229,7 @@ int lp_batched_upload(lp_context* ctx, int batch, const double* A, int m, int n,
     int pitch = 0;
     const size_t lds = lp_batched_lds_bytes(m, n, &pitch);
     p->resident = identity && lds <= 160 * 1024;
+    p->maximize = maximize ? 1 : 0;   // (the sense lp_batched_ranging reads)
     if (!p->resident) {   // per-LP fallback; the inputs are kept for lp_batched_duals
         p->h_A.assign(A, A + (size_t)batch * m * n);
         p->h_b.assign(b, b + (size_t)batch * m);
@@ -1000,6 +1001,199 @@ int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double
             for (int j = 0; j < n; ++j) d[j] = NAN;
             w_out[k] = NAN;
         }
+    }
+    ctx->last_error.clear();
+    return LP_OPTIMAL;
+}
+
+// ===========================================================================
+// RHS and cost ranging at a given basis (basis_ranging.hip): one LP per workgroup for lp_basis_ranging_fits(m, n),
+// the single-LP path one LP after another beyond it
+// ===========================================================================
+
+int lp_basis_ranging_fits(int m, int n) {
+    return m > 0 && n >= m && lp_basis_ranging_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
+}
+
+// NaN values and -1 indices for LP k
+static void ranging_nan(size_t k, int m, int n, double* rhs, int* rhs_var, double* cost, int* cost_var) {
+    for (size_t q = 0; q < 2 * (size_t)m; ++q) {
+        rhs[k * 2 * m + q] = NAN;
+        rhs_var[k * 2 * m + q] = -1;
+    }
+    for (size_t q = 0; q < 2 * (size_t)n; ++q) {
+        cost[k * 2 * n + q] = NAN;
+        cost_var[k * 2 * n + q] = -1;
+    }
+}
+
+// Ranges of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): LPs whose run status is
+// not LP_OPTIMAL keep it and get NaN.  Outputs to the host.
+static int ranging_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
+                             const double* dc, const int* dbasis, const int* drun_status, int maximize, double eps,
+                             double* rhs_out, int* rhs_var_out, double* cost_out, int* cost_var_out,
+                             int* status_out) {
+    hipStream_t s = ctx->stream;
+    const size_t B = (size_t)batch, nr = B * 2 * m, nc = B * 2 * n;
+    const size_t bytes = sizeof(double) * (nr + nc) + sizeof(int) * (nr + nc + B);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, bytes));
+    BasisRangingDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.basis = dbasis;
+    d.run_status = drun_status;
+    d.rhs = reinterpret_cast<double*>(buf);
+    d.cost = d.rhs + nr;
+    d.rhs_var = reinterpret_cast<int*>(d.cost + nc);
+    d.cost_var = d.rhs_var + nr;
+    d.status = d.cost_var + nc;
+    int rc = LP_OPTIMAL;
+    if (lp_basis_ranging_fits(m, n)) {
+        rc = lp_basis_ranging_launch(ctx, d);
+    } else {   // one LP after another: statuses and bases checked on the host
+        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
+        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && drun_status)
+            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            LP_HIP(ctx, e);
+        }
+        for (size_t k = 0; k < B && rc >= 0; ++k) {
+            if (st[k] == LP_OPTIMAL)
+                for (int t = 0; t < m; ++t)
+                    if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
+            if (st[k] != LP_OPTIMAL) continue;
+            rc = lp_basis_ranging_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
+                                         d.maximize, eps, d.rhs + k * 2 * m, d.rhs_var + k * 2 * m,
+                                         d.cost + k * 2 * n, d.cost_var + k * 2 * n);
+            if (rc >= 0) st[k] = rc;
+        }
+        if (rc >= 0) {
+            rc = LP_OPTIMAL;
+            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = -(int)e;
+        }
+    }
+    if (rc == LP_OPTIMAL) {
+        hipError_t e = hipMemcpyAsync(rhs_out, d.rhs, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(rhs_var_out, d.rhs_var, sizeof(int) * nr, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d.cost, sizeof(double) * nc, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(cost_var_out, d.cost_var, sizeof(int) * nc, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("basis ranging: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    }
+    (void)hipFree(buf);
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without ranges: NaN (the per-LP path leaves their outputs unwritten)
+    for (size_t k = 0; k < B; ++k)
+        if (status_out[k] != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` LPs, then ranging_on_device.
+static int ranging_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                          const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                          double* cost_out, int* cost_var_out, int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    int* dbasis = reinterpret_cast<int*>(dc + B * n);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = LP_OPTIMAL;
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("basis ranging upload: ") + hipGetErrorString(e);
+        rc = -(int)e;
+    } else {
+        rc = ranging_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, maximize, eps, rhs_out, rhs_var_out,
+                               cost_out, cost_var_out, status_out);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int lp_basis_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                     const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                     double* cost_out, int* cost_var_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: bad dimensions");
+    ranging_nan(0, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: eps must be >= 0");
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    int status = LP_OPTIMAL;
+    const int rc = ranging_upload(ctx, 1, A, m, n, b, c, basis, maximize, eps, rhs_out, rhs_var_out, cost_out,
+                                  cost_var_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                             const double* c, const int* basis, int maximize, double eps, double* rhs_out,
+                             int* rhs_var_out, double* cost_out, int* cost_var_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: eps must be >= 0");
+    return ranging_upload(ctx, batch, A, m, n, b, c, basis, maximize, eps, rhs_out, rhs_var_out, cost_out,
+                          cost_var_out, status_out);
+}
+
+int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* rhs_var_out, double* cost_out,
+                       int* cost_var_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: eps must be >= 0");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: the batch has not run");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int m = p->m, n = p->n;
+    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
+        return ranging_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, p->maximize,
+                                 eps, rhs_out, rhs_var_out, cost_out, cost_var_out, status_out);
+    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
+    std::vector<int> basis((size_t)m);
+    for (size_t k = 0; k < (size_t)p->batch; ++k) {
+        int st = p->status[k];
+        if (st == LP_OPTIMAL) {
+            if (p->two_phase || p->resolve) {
+                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
+            } else {
+                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+            }
+            st = lp_basis_ranging(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m, p->h_c.data() + k * n,
+                                  basis.data(), p->maximize, eps, rhs_out + k * 2 * m, rhs_var_out + k * 2 * m,
+                                  cost_out + k * 2 * n, cost_var_out + k * 2 * n);
+            if (st < 0) return st;
+        }
+        status_out[k] = st;
+        if (st != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
     }
     ctx->last_error.clear();
     return LP_OPTIMAL;

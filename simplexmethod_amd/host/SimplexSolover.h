@@ -130,6 +130,65 @@ public:
         return out;
     }
 
+    // RHS and cost ranging at a result's final basis (lp_basis_ranging) with EPS and the problem's sense: for each
+    // b_i and c_j the interval over which that basis stays feasible / optimal (the others fixed), and the column
+    // that leaves (b) or enters (c) at each end, -1 at an infinite end.  The ranges describe the basis, whose
+    // optimality is not re-checked; at a degenerate optimum they can be narrower than the interval over which the
+    // optimal value stays linear.  status: LP_OPTIMAL, LP_SINGULAR (NaN, -1); a result that is not LP_OPTIMAL
+    // keeps its status and gets NaN.
+    struct Ranging {
+        lpla::VectorXd b_lo, b_hi, c_lo, c_hi;
+        std::vector<int> b_leave_lo, b_leave_hi, c_enter_lo, c_enter_hi;
+        int status = LP_OPTIMAL;
+    };
+
+    Ranging ranging(const Result& r) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        std::vector<double> rhs(2 * (size_t)m, std::numeric_limits<double>::quiet_NaN()),
+            cost(2 * (size_t)n, std::numeric_limits<double>::quiet_NaN());
+        std::vector<int> rv(2 * (size_t)m, -1), cv(2 * (size_t)n, -1);
+        Ranging out;
+        out.status = r.status;
+        if (r.status == LP_OPTIMAL) {
+            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::ranging: basis size != rows(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.status = lp_basis_ranging(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
+                                          _problem.IsMaximization() ? 1 : 0, EPS, rhs.data(), rv.data(), cost.data(),
+                                          cv.data());
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        out.b_lo = lpla::VectorXd::Zero(m);
+        out.b_hi = lpla::VectorXd::Zero(m);
+        out.c_lo = lpla::VectorXd::Zero(n);
+        out.c_hi = lpla::VectorXd::Zero(n);
+        out.b_leave_lo.assign((size_t)m, -1);
+        out.b_leave_hi.assign((size_t)m, -1);
+        out.c_enter_lo.assign((size_t)n, -1);
+        out.c_enter_hi.assign((size_t)n, -1);
+        const bool ok = out.status == LP_OPTIMAL;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int i = 0; i < m; ++i) {
+            out.b_lo[i] = ok ? rhs[2 * (size_t)i] : nan;
+            out.b_hi[i] = ok ? rhs[2 * (size_t)i + 1] : nan;
+            if (ok) {
+                out.b_leave_lo[(size_t)i] = rv[2 * (size_t)i];
+                out.b_leave_hi[(size_t)i] = rv[2 * (size_t)i + 1];
+            }
+        }
+        for (int j = 0; j < n; ++j) {
+            out.c_lo[j] = ok ? cost[2 * (size_t)j] : nan;
+            out.c_hi[j] = ok ? cost[2 * (size_t)j + 1] : nan;
+            if (ok) {
+                out.c_enter_lo[(size_t)j] = cv[2 * (size_t)j];
+                out.c_enter_hi[(size_t)j] = cv[2 * (size_t)j + 1];
+            }
+        }
+        return out;
+    }
+
 private:
     Canonical _problem;  // deep copy, as in the reference (:285)
     int _device;
