@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -366,6 +366,51 @@ int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* 
 /* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: m <= 132 for n = m, 128 x 256, and every
  * batched two-phase / re-solve shape with m <= 132), 0 otherwise.                                      */
 int lp_basis_ranging_fits(int m, int n);
+
+/* ---- Farkas and unbounded-ray certificates at a basis ------------------------------------------
+ * Evidence for an LP_INFEASIBLE or LP_UNBOUNDED verdict, computed after the fact at the basis the solver stopped at
+ * (every solver path stops before it pivots on the failing row or column).  A basis index n+i (0 <= i < m) is the
+ * artificial of row i, column s_i e_i with s_i = -1 when b[i] < -eps and +1 otherwise (the two-phase row flip), so
+ * a phase-I basis passes as it is.  Everything in fp64:
+ *   1. B^-1 and xB by lp_basis_ranging's crash on [B | I | b]; alpha[t][j] = (B^-1 A)[t][j], one fused
+ *      multiply-add chain per entry in row order;
+ *   2. phase-I case (an artificial is basic): f = -(sum of the rows of B^-1 at the artificial positions, in
+ *      position order).  FARKAS when the artificials' values xB, summed in artificial-index order, exceed eps and
+ *      every original column has g_j = f^T A_j >= -eps (one chain in row order);
+ *   3. dual-simplex case (no artificial, some xB[t] < -eps): the first position t with xB[t] < -eps and
+ *      alpha[t][j] >= -eps for every non-basic j gives FARKAS with f = B^-1[t][:] and index t;
+ *   4. ray case (otherwise): d_j = c_j - sum_t c[basis[t]] alpha[t][j], one chain in position order.  These bits
+ *      are not lp_basis_duals's d.  The first non-basic j with d_j > eps (max) or d_j < -eps (min) and
+ *      alpha[t][j] <= eps for every t gives RAY: r[j] = 1, r[basis[t]] = -alpha[t][j], +0.0 elsewhere; index j.
+ * A FARKAS vector satisfies A^T f >= -eps and b^T f < 0; a RAY satisfies A r = 0 (to rounding), r >= -eps and
+ * c^T r = d_j.  value: b^T f (one chain in row order) or d_j; index: t, j, or -1 (phase I, NONE).  farkas (m) is
+ * NaN unless the kind is FARKAS, ray (n) NaN unless it is RAY, value NaN for NONE.  A certificate is emitted only
+ * when it passes its own eps test: at the eps boundary the answer is NONE, never a wrong vector.  LP_SINGULAR when
+ * the crash is singular or an index repeats; LP_BAD_ARG for an index outside [0, n+m) or eps < 0 / NaN.  The bits
+ * do not depend on the path.  Every output pointer is required.                                          */
+enum { LP_CERT_NONE = 0, LP_CERT_FARKAS = 1, LP_CERT_RAY = 2 };
+/* One LP; returns its status (LP_OPTIMAL: the certificate was computed and kind_out says what was found;
+ * LP_SINGULAR, LP_BAD_ARG).  farkas_out m, ray_out n, one kind / value / index.                              */
+int lp_basis_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                         const int* basis, int maximize, double eps, int* kind_out, double* farkas_out,
+                         double* ray_out, double* value_out, int* index_out);
+/* `batch` LPs of one shape and sense (arrays concatenated per LP as in lp_basis_ranging_batched; farkas_out
+ * batch*m, ray_out batch*n, kind / value / index / status batch), one LP per workgroup when
+ * lp_basis_certificate_fits(m, n), else one LP after another; per-LP statuses in status_out.             */
+int lp_basis_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                 const double* c, const int* basis, int maximize, double eps, int* kind_out,
+                                 double* farkas_out, double* ray_out, double* value_out, int* index_out,
+                                 int* status_out);
+/* The certificates of a batch handle (plain, two-phase or re-solve) after lp_batched_run, at each LP's final basis,
+ * for the LP as the caller gave it (never the rows a two-phase run sign-flipped) and the handle's sense.  Only LPs
+ * whose run ended LP_INFEASIBLE or LP_UNBOUNDED get one; every other LP gets NONE and NaN.  status_out holds the run
+ * status, or LP_SINGULAR (LP_BAD_ARG) when the certificate's crash (basis) fails.  LP_BAD_ARG before the first
+ * run.                                                                                                  */
+int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, double* farkas_out, double* ray_out,
+                            double* value_out, int* index_out, int* status_out);
+/* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: 128 x 256, and every batched two-phase /
+ * re-solve shape with m <= 132), 0 otherwise.                                                           */
+int lp_basis_certificate_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

@@ -212,6 +212,28 @@ def build_ranging_ref(force=False, verbose=False):
     return RANGING_REF_LIB
 
 
+CERTIFICATE_REF_LIB = os.path.join(TESTS_REF, "_build", "libcertificate_ref.so")
+
+
+def build_certificate_ref(force=False, verbose=False):
+    """tests/ref/certificate_ref.c (which includes ranging_ref.c and duals_ref.c) ->
+    tests/ref/_build/libcertificate_ref.so: Farkas and ray certificates at a given basis the tests compare against;
+    flags as build_ranging_ref."""
+    src = os.path.join(TESTS_REF, "certificate_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "ranging_ref.c"), os.path.join(TESTS_REF, "duals_ref.c")]
+    if not force and _newer(CERTIFICATE_REF_LIB, deps):
+        return CERTIFICATE_REF_LIB
+    os.makedirs(os.path.dirname(CERTIFICATE_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", CERTIFICATE_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return CERTIFICATE_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -219,6 +241,7 @@ def build_all(force=False, verbose=False):
     build_resolve_ref(force, verbose)
     build_duals_ref(force, verbose)
     build_ranging_ref(force, verbose)
+    build_certificate_ref(force, verbose)
     return hip, host
 
 

@@ -17,6 +17,7 @@ SUBSET_FEASIBLE, SUBSET_INFEASIBLE, SUBSET_SINGULAR = range(3)
 SIMPLEX_AUTO, SIMPLEX_LAUNCH, SIMPLEX_LOOKAHEAD, SIMPLEX_RESIDENT, SIMPLEX_OVERLAP = 0, 1, 2, 3, 4
 ENUM_AUTO, ENUM_DIRECT, ENUM_PREFIX = 0, 1, 2
 PIVOT_DANTZIG, PIVOT_BLAND = 0, 1
+CERT_NONE, CERT_FARKAS, CERT_RAY = 0, 1, 2
 U64_MAX = (1 << 64) - 1
 EPS = 1e-9        # Solver::EPS, SimplexSolover.h:13
 MAX_ITER = 10000  # SimplexSolover.h:426
@@ -109,6 +110,12 @@ SIGNATURES = {
                                            _dp, _ip, _dp, _ip, _ip]),
     "lp_batched_ranging": (C.c_int, [_vp, C.c_double, _dp, _ip, _dp, _ip, _ip]),
     "lp_basis_ranging_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_certificate": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_double, _ip, _dp,
+                                       _dp, _dp, _ip]),
+    "lp_basis_certificate_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
+                                               C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
+    "lp_batched_certificates": (C.c_int, [_vp, C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
+    "lp_basis_certificate_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -450,6 +457,44 @@ class Context:
         """lp_basis_ranging_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
         return bool(self.lib.lp_basis_ranging_fits(m, n))
 
+    # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
+    def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):
+        """lp_basis_certificate: evidence for an infeasible or unbounded verdict at `basis` (index n+i: the
+        artificial of row i).  dict(status, kind (CERT_NONE / CERT_FARKAS / CERT_RAY), farkas (m), ray (n), value,
+        index): farkas NaN unless the kind is FARKAS, ray NaN unless it is RAY.  status OPTIMAL means the
+        certificate was computed; SINGULAR for a singular crash or a repeated index.  An index out of range or a
+        negative eps raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        kind, index = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        farkas, ray, value = np.zeros(m), np.zeros(n), np.zeros(1)
+        rc = self.check(self.lib.lp_basis_certificate(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
+                                                      float(eps), _i(kind), _d(farkas), _d(ray), _d(value),
+                                                      _i(index)))
+        return dict(status=rc, kind=int(kind[0]), farkas=farkas, ray=ray, value=float(value[0]),
+                    index=int(index[0]))
+
+    def basis_certificate_batched(self, A, b, c, basis, maximize=True, eps=EPS):
+        """lp_basis_certificate_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).  The dict
+        of basis_certificate with a leading batch axis; status, kind, value and index (batch)."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        kind, index, st = np.zeros(batch, np.int32), np.zeros(batch, np.int32), np.zeros(batch, np.int32)
+        farkas, ray, value = np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
+        self.check(self.lib.lp_basis_certificate_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                         int(maximize), float(eps), _i(kind), _d(farkas), _d(ray),
+                                                         _d(value), _i(index), _i(st)))
+        return dict(status=st, kind=kind, farkas=farkas, ray=ray, value=value, index=index)
+
+    def basis_certificate_fits(self, m, n):
+        """lp_basis_certificate_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
+        return bool(self.lib.lp_basis_certificate_fits(m, n))
+
     def simplex_solve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
                               max_iter=MAX_ITER, pivot_rule="dantzig"):
         """A: (batch, m, n); b: (batch, m); c: (batch, n); basis: (batch, m)."""
@@ -678,6 +723,17 @@ class BatchedProblem:
         st = np.zeros(B, dtype=np.int32)
         self.ctx.check(self.ctx.lib.lp_batched_ranging(self.h, float(eps), _d(rhs), _i(rv), _d(cost), _i(cv), _i(st)))
         return _ranging_dict(st, rhs, rv, cost, cv)
+
+    def certificates(self, eps=EPS):
+        """lp_batched_certificates after run(): the dict of Context.basis_certificate_batched at each LP's final
+        basis and the handle's sense.  Only LPs whose run ended INFEASIBLE or UNBOUNDED get a certificate; status
+        holds the run status (SINGULAR if the certificate's crash fails)."""
+        B, m, n = self.batch, self.m, self.n
+        kind, index, st = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        farkas, ray, value = np.zeros((B, m)), np.zeros((B, n)), np.zeros(B)
+        self.ctx.check(self.ctx.lib.lp_batched_certificates(self.h, float(eps), _i(kind), _d(farkas), _d(ray),
+                                                            _d(value), _i(index), _i(st)))
+        return dict(status=st, kind=kind, farkas=farkas, ray=ray, value=value, index=index)
 
     def path(self):
         """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""

@@ -119,3 +119,34 @@ int lp_basis_ranging_launch(lp_context* ctx, const BasisRangingDev& d);   // lp_
 int lp_basis_ranging_device(lp_context* ctx, const double* dA, int m, int n, const double* db, const double* dc,
                             const int* dbasis, int maximize, double eps, double* drhs, int* drhs_var, double* dcost,
                             int* dcost_var);
+
+// Farkas and unbounded-ray certificates at given bases, one LP per workgroup (basis_certificate.hip): B^-1 and xB
+// by the ranging crash on [B | I | b] (kept in place; basis index n+i is the artificial s_i e_i of row i), then the
+// case's alpha chains and first-index reductions.
+struct BasisCertificateDev {
+    int batch, m, n;
+    int maximize;
+    double eps;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const int* basis;       // batch x m (by position), indices in [0, n+m)
+    const int* run_status;  // batch, or nullptr: only LPs whose entry is LP_INFEASIBLE / LP_UNBOUNDED get a
+                            // certificate, the others keep their entry and get NONE
+    int* kind;              // batch: LP_CERT_*
+    double* farkas;         // batch x m
+    double* ray;            // batch x n
+    double* value;          // batch
+    int* index;             // batch
+    int* status;            // batch
+};
+
+// basis_certificate.hip
+size_t lp_basis_certificate_lds_bytes(int m, int n);
+int lp_basis_certificate_launch(lp_context* ctx, const BasisCertificateDev& d);   // lp_basis_certificate_fits shapes
+// One LP of any shape on the device (the basis in range without repeats, eps >= 0): the crash on [B | I | b] by the
+// single-LP launch pair, B^-1 A, then the reductions; every pointer is a device pointer.  Returns LP_OPTIMAL /
+// LP_SINGULAR (outputs untouched).
+int lp_basis_certificate_device(lp_context* ctx, const double* dA, int m, int n, const double* db, const double* dc,
+                                const int* dbasis, int maximize, double eps, int* dkind, double* dfarkas,
+                                double* dray, double* dvalue, int* dindex);

@@ -166,7 +166,7 @@ struct lp_batched_problem {
     BatchedResolveDev rdev{};
     std::vector<int> resolve_iters;         // batch*2: dual, primal
     std::vector<int> h_basis_in;            // batch*m
-    bool ran = false;                       // a run completed: lp_batched_duals / _ranging have final bases to read
+    bool ran = false;                       // a run completed: lp_batched_duals / _ranging / _certificates have final bases to read
 };
 
 void lp_batched_free(lp_batched_problem* p) {
@@ -1194,6 +1194,222 @@ int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* 
         }
         status_out[k] = st;
         if (st != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
+    }
+    ctx->last_error.clear();
+    return LP_OPTIMAL;
+}
+
+// ===========================================================================
+// Farkas and unbounded-ray certificates at a given basis (basis_certificate.hip): one LP per workgroup for
+// lp_basis_certificate_fits(m, n), the single-LP path one LP after another beyond it
+// ===========================================================================
+
+int lp_basis_certificate_fits(int m, int n) {
+    return m > 0 && n > 0 && lp_basis_certificate_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
+}
+
+// NONE, NaN values and index -1 for LP k
+static void certificate_none(size_t k, int m, int n, int* kind, double* farkas, double* ray, double* value,
+                             int* index) {
+    kind[k] = LP_CERT_NONE;
+    for (size_t q = 0; q < (size_t)m; ++q) farkas[k * m + q] = NAN;
+    for (size_t q = 0; q < (size_t)n; ++q) ray[k * n + q] = NAN;
+    value[k] = NAN;
+    index[k] = -1;
+}
+
+// The basis check of one LP on the host: LP_BAD_ARG (an index outside [0, n+m)), LP_SINGULAR (a repeat), else
+// LP_OPTIMAL.
+static int certificate_basis_check(const int* basis, int m, int n) {
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n + m) return LP_BAD_ARG;
+    std::vector<char> seen((size_t)n + m, 0);
+    for (int t = 0; t < m; ++t) {
+        if (seen[(size_t)basis[t]]) return LP_SINGULAR;
+        seen[(size_t)basis[t]] = 1;
+    }
+    return LP_OPTIMAL;
+}
+
+// Certificates of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): only LPs whose run
+// status is LP_INFEASIBLE / LP_UNBOUNDED get one, the others keep it and get NONE.  Outputs to the host.
+static int certificate_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
+                                 const double* dc, const int* dbasis, const int* drun_status, int maximize,
+                                 double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out,
+                                 int* index_out, int* status_out) {
+    hipStream_t s = ctx->stream;
+    const size_t B = (size_t)batch, nf = B * m, nr = B * n;
+    const size_t bytes = sizeof(double) * (nf + nr + B) + sizeof(int) * 3 * B;
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, bytes));
+    BasisCertificateDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.basis = dbasis;
+    d.run_status = drun_status;
+    d.farkas = reinterpret_cast<double*>(buf);
+    d.ray = d.farkas + nf;
+    d.value = d.ray + nr;
+    d.kind = reinterpret_cast<int*>(d.value + B);
+    d.index = d.kind + B;
+    d.status = d.index + B;
+    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
+    int rc = LP_OPTIMAL;
+    if (lp_basis_certificate_fits(m, n)) {
+        rc = lp_basis_certificate_launch(ctx, d);
+    } else {   // one LP after another: statuses and bases checked on the host
+        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
+        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && drun_status)
+            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            LP_HIP(ctx, e);
+        }
+        for (size_t k = 0; k < B && rc >= 0; ++k) {
+            done[k] = 0;
+            if (drun_status && st[k] != LP_INFEASIBLE && st[k] != LP_UNBOUNDED) continue;
+            int cs = certificate_basis_check(basis.data() + k * m, m, n);
+            if (cs == LP_OPTIMAL) {
+                rc = lp_basis_certificate_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
+                                                 d.maximize, eps, d.kind + k, d.farkas + k * m, d.ray + k * n,
+                                                 d.value + k, d.index + k);
+                if (rc < 0) break;
+                cs = rc;
+                done[k] = cs == LP_OPTIMAL;
+            }
+            if (cs != LP_OPTIMAL) st[k] = cs;
+        }
+        if (rc >= 0) {
+            rc = LP_OPTIMAL;
+            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = -(int)e;
+        }
+    }
+    if (rc == LP_OPTIMAL) {
+        hipError_t e = hipMemcpyAsync(farkas_out, d.farkas, sizeof(double) * nf, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(ray_out, d.ray, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(value_out, d.value, sizeof(double) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(kind_out, d.kind, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(index_out, d.index, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("basis certificate: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    }
+    (void)hipFree(buf);
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without a certificate on the per-LP path: NONE (their outputs were left unwritten)
+    for (size_t k = 0; k < B; ++k)
+        if (!done[k]) certificate_none(k, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` LPs, then certificate_on_device.
+static int certificate_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                              const double* c, const int* basis, int maximize, double eps, int* kind_out,
+                              double* farkas_out, double* ray_out, double* value_out, int* index_out,
+                              int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    int* dbasis = reinterpret_cast<int*>(dc + B * n);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = LP_OPTIMAL;
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("basis certificate upload: ") + hipGetErrorString(e);
+        rc = -(int)e;
+    } else {
+        rc = certificate_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, maximize, eps, kind_out,
+                                   farkas_out, ray_out, value_out, index_out, status_out);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int lp_basis_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                         const int* basis, int maximize, double eps, int* kind_out, double* farkas_out,
+                         double* ray_out, double* value_out, int* index_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: null argument");
+    if (m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: bad dimensions");
+    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: eps must be >= 0");
+    const int cs = certificate_basis_check(basis, m, n);
+    if (cs == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    if (cs == LP_SINGULAR) return LP_SINGULAR;
+    int status = LP_OPTIMAL;
+    const int rc = certificate_upload(ctx, 1, A, m, n, b, c, basis, maximize, eps, kind_out, farkas_out, ray_out,
+                                      value_out, index_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                 const double* c, const int* basis, int maximize, double eps, int* kind_out,
+                                 double* farkas_out, double* ray_out, double* value_out, int* index_out,
+                                 int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: null argument");
+    if (batch <= 0 || m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: eps must be >= 0");
+    return certificate_upload(ctx, batch, A, m, n, b, c, basis, maximize, eps, kind_out, farkas_out, ray_out,
+                              value_out, index_out, status_out);
+}
+
+int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, double* farkas_out, double* ray_out,
+                            double* value_out, int* index_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: eps must be >= 0");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: the batch has not run");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int m = p->m, n = p->n;
+    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
+        return certificate_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus,
+                                     p->maximize, eps, kind_out, farkas_out, ray_out, value_out, index_out,
+                                     status_out);
+    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
+    std::vector<int> basis((size_t)m);
+    for (size_t k = 0; k < (size_t)p->batch; ++k) {
+        int st = p->status[k];
+        certificate_none(k, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+        if (st == LP_INFEASIBLE || st == LP_UNBOUNDED) {
+            if (p->two_phase || p->resolve) {
+                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
+            } else {
+                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+            }
+            const int cs = lp_basis_certificate(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m,
+                                                p->h_c.data() + k * n, basis.data(), p->maximize, eps, kind_out + k,
+                                                farkas_out + k * m, ray_out + k * n, value_out + k, index_out + k);
+            if (cs < 0) return cs;
+            if (cs != LP_OPTIMAL) st = cs;
+        }
+        status_out[k] = st;
     }
     ctx->last_error.clear();
     return LP_OPTIMAL;

@@ -157,3 +157,7 @@ int lp_resident_launch(lp_simplex_problem* p, double eps, int max_iter);
 // the solve is to be re-run on another path; LP_BAD_ARG instead under LP_RESIDENT_STRICT.
 int lp_resident_finish(lp_simplex_problem* p, bool* rerun);
 int lp_simplex_debug_division(lp_context* ctx, const double* num, const double* den, int n, double* fast_out, double* plain_out);
+
+// basis_ranging.hip: alpha (m x n, row-major) = B^-1 A from a tableau [B | I | b] that lp_simplex_crash left in
+// position order, one fma chain per entry in row order; queued on ctx's stream.
+void lp_binv_times_a_launch(lp_context* ctx, const SimplexDev& s, const double* dA, int n, double* alpha);

@@ -189,6 +189,45 @@ public:
         return out;
     }
 
+    // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
+    // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
+    // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
+    // A x = b); LP_CERT_RAY: A ray = 0, ray >= -EPS and c.ray = value improving (the objective is unbounded);
+    // LP_CERT_NONE: nothing that passes its own EPS test.  farkas / ray are NaN unless the kind is theirs.
+    // status: the result's LP_INFEASIBLE / LP_UNBOUNDED when a certificate was computed, LP_SINGULAR when the
+    // crash fails; any other result keeps its status and gets NONE.
+    struct Certificate {
+        int kind = LP_CERT_NONE;
+        lpla::VectorXd farkas, ray;
+        double value = std::numeric_limits<double>::quiet_NaN();
+        int index = -1;
+        int status = LP_OPTIMAL;
+    };
+
+    Certificate certificate(const Result& r) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        Certificate out;
+        out.farkas = lpla::VectorXd::Zero(m);
+        out.ray = lpla::VectorXd::Zero(n);
+        for (int i = 0; i < m; ++i) out.farkas[i] = nan;
+        for (int j = 0; j < n; ++j) out.ray[j] = nan;
+        out.status = r.status;
+        if (r.status == LP_INFEASIBLE || r.status == LP_UNBOUNDED) {
+            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::certificate: basis size != rows(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            const int st = lp_basis_certificate(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
+                                                _problem.IsMaximization() ? 1 : 0, EPS, &out.kind, out.farkas.data(),
+                                                out.ray.data(), &out.value, &out.index);
+            if (st < 0 || st == LP_BAD_ARG) lpgpu::throw_for_status(st, ctx);
+            if (st != LP_OPTIMAL) out.status = st;
+        }
+        return out;
+    }
+
 private:
     Canonical _problem;  // deep copy, as in the reference (:285)
     int _device;
