@@ -116,6 +116,13 @@ SIGNATURES = {
                                                C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
     "lp_batched_certificates": (C.c_int, [_vp, C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
     "lp_basis_certificate_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_parametric": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _dp, C.c_double, C.c_double,
+                                      C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "lp_basis_parametric_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _dp,
+                                              C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _ip]),
+    "lp_batched_parametric": (C.c_int, [_vp, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip,
+                                        _ip]),
+    "lp_basis_parametric_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -254,6 +261,22 @@ def gen_lp(seed, m, n):
     c[:no] = u[no * m + m:]
     basis = np.arange(no, n, dtype=np.int32)
     return A, b, c, basis
+
+
+MAX_BREAKS = 64   # default bound on the breakpoints of a parametric path
+
+
+def _parametric_out(batch, m, max_breaks):
+    """Zeroed output arrays of the batched parametric calls: nseg, t, obj, slope, enter, leave, basis, status."""
+    mb = int(max_breaks)
+    return (np.zeros(batch, np.int32), np.zeros((batch, mb + 2)), np.zeros((batch, mb + 2)),
+            np.zeros((batch, mb + 1)), np.zeros((batch, mb + 1), np.int32), np.zeros((batch, mb + 1), np.int32),
+            np.zeros((batch, m), np.int32), np.zeros(batch, np.int32))
+
+
+def _parametric_dict(out):
+    nseg, t, obj, slope, enter, leave, basis, st = out
+    return dict(status=st, nseg=nseg, t=t, obj=obj, slope=slope, enter=enter, leave=leave, basis=basis)
 
 
 def _ranging_dict(status, rhs, rhs_var, cost, cost_var):
@@ -456,6 +479,49 @@ class Context:
     def basis_ranging_fits(self, m, n):
         """lp_basis_ranging_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
         return bool(self.lib.lp_basis_ranging_fits(m, n))
+
+    # ---- parametric right-hand side from an optimal basis --------------------------------------
+    def basis_parametric(self, A, b, c, basis, d, t_max=np.inf, maximize=True, eps=EPS, max_breaks=MAX_BREAKS):
+        """lp_basis_parametric: the optimal value along b + t d for t in [0, t_max] from the optimal `basis`.
+        dict(status, t (nseg+1), obj (nseg+1), slope (nseg), enter (nseg), leave (nseg), basis (m)): breakpoints,
+        the optimal value at each, the slope of each segment and the pivot that ends it (enter -1 on the last one).
+        status OPTIMAL (reached t_max), INFEASIBLE (infeasible past t[-1]), ITER_LIMIT (max_breaks pivots done) or
+        SINGULAR (empty arrays).  A basis that is not optimal at t = 0, an index out of range, t_max < 0, eps < 0 or
+        max_breaks < 0 raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        Af, b, c, d = colmajor(A), _f64(b), _f64(c), _f64(d)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        out = _parametric_out(1, m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, _ = out
+        rc = self.check(self.lib.lp_basis_parametric(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
+                                                     _d(d), float(t_max), float(eps), int(max_breaks), _i(nseg),
+                                                     _d(t), _d(obj), _d(slope), _i(enter), _i(leave), _i(bo)))
+        ns = int(nseg[0])
+        return dict(status=rc, t=t[0, :ns + 1] if ns else t[0, :0], obj=obj[0, :ns + 1] if ns else obj[0, :0],
+                    slope=slope[0, :ns], enter=enter[0, :ns], leave=leave[0, :ns], basis=bo[0])
+
+    def basis_parametric_batched(self, A, b, c, basis, d, t_max=np.inf, maximize=True, eps=EPS,
+                                 max_breaks=MAX_BREAKS):
+        """lp_basis_parametric_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m), d (batch, m).
+        dict(status (batch), nseg (batch), t, obj (batch, max_breaks+2), slope, enter, leave (batch, max_breaks+1),
+        basis (batch, m)), padded with NaN / -1 past each path."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c, d = _f64(b).reshape(-1), _f64(c).reshape(-1), _f64(d).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        out = _parametric_out(batch, m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, st = out
+        self.check(self.lib.lp_basis_parametric_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                        int(maximize), _d(d), float(t_max), float(eps),
+                                                        int(max_breaks), _i(nseg), _d(t), _d(obj), _d(slope),
+                                                        _i(enter), _i(leave), _i(bo), _i(st)))
+        return _parametric_dict(out)
+
+    def basis_parametric_fits(self, m, n):
+        """lp_basis_parametric_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
+        return bool(self.lib.lp_basis_parametric_fits(m, n))
 
     # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
     def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):
@@ -734,6 +800,19 @@ class BatchedProblem:
         self.ctx.check(self.ctx.lib.lp_batched_certificates(self.h, float(eps), _i(kind), _d(farkas), _d(ray),
                                                             _d(value), _i(index), _i(st)))
         return dict(status=st, kind=kind, farkas=farkas, ray=ray, value=value, index=index)
+
+    def parametric(self, d, t_max=np.inf, eps=EPS, max_breaks=MAX_BREAKS):
+        """lp_batched_parametric after run(): the dict of Context.basis_parametric_batched from each LP's final basis,
+        d (batch, m), with the handle's sense; LPs whose run status is not OPTIMAL keep it and get nseg 0."""
+        d = _f64(d).reshape(-1)
+        if d.size != self.batch * self.m:
+            raise ValueError(f"parametric: expected {self.batch * self.m} direction entries, got {d.size}")
+        out = _parametric_out(self.batch, self.m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, st = out
+        self.ctx.check(self.ctx.lib.lp_batched_parametric(self.h, _d(d), float(t_max), float(eps), int(max_breaks),
+                                                          _i(nseg), _d(t), _d(obj), _d(slope), _i(enter), _i(leave),
+                                                          _i(bo), _i(st)))
+        return _parametric_dict(out)
 
     def path(self):
         """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""

@@ -221,6 +221,11 @@ int bench_replay(lp_simplex_problem* p, int iters, float* ms_per_launch, Stage s
 
 }  // namespace
 
+int lp_poll_pivots(lp_simplex_problem* p, const std::function<int(int)>& queue) {
+    int launches = 0;
+    return poll_batches(p, 16, 256, &launches, queue);
+}
+
 extern "C" {
 
 void lp_simplex_free(lp_simplex_problem* p) {

@@ -1,6 +1,8 @@
 // simplex_problem.hpp — device-side state of one single-LP tableau solve.
 #pragma once
 
+#include <functional>
+
 #include "lp_internal.hpp"
 
 struct SimplexState {
@@ -122,6 +124,9 @@ int lp_simplex_extract_x(lp_simplex_problem* p, double* dx);
 int lp_simplex_classify(lp_simplex_problem* p, double eps, int* flags);
 int lp_dual_prepare(lp_simplex_problem* p);
 int lp_dual_queue(lp_simplex_problem* p, int batch);
+// simplex_driver.hip: the batch-and-poll loop of the launch paths for pivot pairs queued outside it (queue(batch)
+// queues `batch` pivots and returns the launches queued); returns once the state word has left kRunning.
+int lp_poll_pivots(lp_simplex_problem* p, const std::function<int(int)>& queue);
 
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS
