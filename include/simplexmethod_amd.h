@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -452,6 +452,50 @@ int lp_batched_parametric(lp_batched_problem* p, const double* d, double t_max, 
 /* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB, e.g. the batched two-phase 64 x 192 class),
  * 0 otherwise.                                                                                              */
 int lp_basis_parametric_fits(int m, int n);
+
+/* ---- Parametric cost from an optimal basis ------------------------------------------------------
+ * The optimal value z*(t) = opt { (c + t g)^T x : A x = b, x >= 0 } for t from 0 up to t_max, walked exactly from the
+ * given optimal basis (m column indices by position) by one primal pivot per breakpoint.  z* is piecewise linear in t:
+ * convex for a max problem, concave for a min problem.  A negative direction of t is -g.  Everything in fp64:
+ *   1. T = [A | b ; c | 0 ; g | 0]; the basis is installed by lp_simplex_resolve's crash over all m+2 rows (skipped
+ *      for the slack identity with c_B = 0 and g_B = 0): row m holds the reduced costs d of c, row m+1 the reduced
+ *      costs delta of g;
+ *   2. the basis must be primal feasible (no xB_t < -eps) and dual feasible (no non-basic d_j > eps for max,
+ *      d_j < -eps for min) at t = 0, else LP_BAD_ARG (re-solve first);
+ *   3. segment k from t_k (t_0 = +0.0): over non-basic j ascending with delta_j > eps (max) or delta_j < -eps (min),
+ *      tau_j = -d_j / delta_j; the breakpoint is the first strict minimum (a tie keeps the first index),
+ *      t* = tau > t_k ? tau : t_k.  No candidate, or t* >= t_max: the path ends at t_max (LP_OPTIMAL).  Else the
+ *      chosen column e enters and the leaving position is the primal ratio test over column e (ratios xB_i / u_i
+ *      for u_i > eps, the EPS-hysteresis chain in position order).  None: the path ends at t* (LP_UNBOUNDED:
+ *      unbounded for every t > t*).  max_breaks pivots done: the path ends at t* (LP_ITER_LIMIT).  Else the oracle's
+ *      pivot over every column and both cost rows, t_{k+1} = t*;
+ *   4. obj[k] = sum_t (c + t_k g)[basis[t]] * xB_t, with the cost entry fma(t_k, g, c), and slope[k] =
+ *      sum_t g[basis[t]] * xB_t, each one fused multiply-add chain in position order with segment k's basis;
+ *      enter[k] / leave[k]: the variables of the pivot that ends segment k.  The last segment has leave -1 and enter
+ *      the column that would enter (LP_UNBOUNDED, LP_ITER_LIMIT) or -1 (ended at t_max).  obj[nseg] is the chain at
+ *      the final end with the last basis; at an end of +inf it is obj[nseg-1] when the last slope is 0, else +inf /
+ *      -inf by the slope's sign.
+ * Outputs: as lp_basis_parametric: nseg (1 .. max_breaks+1), t[0..nseg], obj[0..nseg], slope / enter / leave
+ * [0..nseg-1] and the final basis by position.  Entries past the path are NaN (values) and -1 (indices).  LP_SINGULAR
+ * (a singular or repeated basis) and LP_BAD_ARG give nseg 0, NaN / -1 and the given basis back.  LP_BAD_ARG also for
+ * a NULL g or output, t_max < 0 / NaN, eps < 0 / NaN, max_breaks < 0 or a basis index outside [0, n).  The bits do
+ * not depend on the path. */
+/* One LP; returns its status (LP_OPTIMAL, LP_UNBOUNDED, LP_ITER_LIMIT, LP_SINGULAR, LP_BAD_ARG).  g n; t_out /
+ * obj_out max_breaks+2, slope_out / enter_out / leave_out max_breaks+1, basis_out m.                      */
+int lp_basis_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out);
+/* `batch` LPs of one shape and sense (arrays concatenated per LP as in lp_basis_ranging_batched; g batch*n; per-LP
+ * strides max_breaks+2 for t / obj, max_breaks+1 for slope / enter / leave, m for basis_out), one LP per workgroup
+ * when lp_basis_parametric_cost_fits(m, n), else one LP after another; per-LP statuses in status_out.       */
+int lp_basis_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out);
+/* The cost paths of every LP of a batch handle (plain, two-phase or re-solve, fallback handles included) after
+ * lp_batched_run, from each LP's final basis, for the LP as the caller gave it (rows a two-phase run sign-flipped never
+ * show) and the handle's sense; g is batch*n, the outputs as lp_basis_parametric_cost_batched.  LPs whose run status is
+ * not LP_OPTIMAL keep it in status_out and get nseg 0.  The handle's pivot rule does not matter.  LP_BAD_ARG before
+ * the first run.                                                                                           */
+int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out);
+/* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB, e.g. the batched two-phase 64 x 192 class),
+ * 0 otherwise.                                                                                              */
+int lp_basis_parametric_cost_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

@@ -123,6 +123,14 @@ SIGNATURES = {
     "lp_batched_parametric": (C.c_int, [_vp, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip]),
     "lp_basis_parametric_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_parametric_cost": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _dp, C.c_double,
+                                           C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "lp_basis_parametric_cost_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, _dp,
+                                                   C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip,
+                                                   _ip]),
+    "lp_batched_parametric_cost": (C.c_int, [_vp, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip,
+                                             _ip, _ip]),
+    "lp_basis_parametric_cost_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -523,6 +531,50 @@ class Context:
         """lp_basis_parametric_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
         return bool(self.lib.lp_basis_parametric_fits(m, n))
 
+    # ---- parametric cost from an optimal basis -------------------------------------------------
+    def basis_parametric_cost(self, A, b, c, basis, g, t_max=np.inf, maximize=True, eps=EPS, max_breaks=MAX_BREAKS):
+        """lp_basis_parametric_cost: the optimal value along c + t g for t in [0, t_max] from the optimal `basis`.
+        dict(status, t (nseg+1), obj (nseg+1), slope (nseg), enter (nseg), leave (nseg), basis (m)): breakpoints,
+        the optimal value at each, the slope of each segment and the pivot that ends it (leave -1 on the last one).
+        status OPTIMAL (reached t_max), UNBOUNDED (unbounded past t[-1]), ITER_LIMIT (max_breaks pivots done) or
+        SINGULAR (empty arrays).  A basis that is not optimal at t = 0, an index out of range, t_max < 0, eps < 0 or
+        max_breaks < 0 raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        Af, b, c, g = colmajor(A), _f64(b), _f64(c), _f64(g)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        out = _parametric_out(1, m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, _ = out
+        rc = self.check(self.lib.lp_basis_parametric_cost(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                          int(maximize), _d(g), float(t_max), float(eps),
+                                                          int(max_breaks), _i(nseg), _d(t), _d(obj), _d(slope),
+                                                          _i(enter), _i(leave), _i(bo)))
+        ns = int(nseg[0])
+        return dict(status=rc, t=t[0, :ns + 1] if ns else t[0, :0], obj=obj[0, :ns + 1] if ns else obj[0, :0],
+                    slope=slope[0, :ns], enter=enter[0, :ns], leave=leave[0, :ns], basis=bo[0])
+
+    def basis_parametric_cost_batched(self, A, b, c, basis, g, t_max=np.inf, maximize=True, eps=EPS,
+                                      max_breaks=MAX_BREAKS):
+        """lp_basis_parametric_cost_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m),
+        g (batch, n).  dict(status (batch), nseg (batch), t, obj (batch, max_breaks+2), slope, enter, leave
+        (batch, max_breaks+1), basis (batch, m)), padded with NaN / -1 past each path."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c, g = _f64(b).reshape(-1), _f64(c).reshape(-1), _f64(g).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        out = _parametric_out(batch, m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, st = out
+        self.check(self.lib.lp_basis_parametric_cost_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
+                                                             int(maximize), _d(g), float(t_max), float(eps),
+                                                             int(max_breaks), _i(nseg), _d(t), _d(obj), _d(slope),
+                                                             _i(enter), _i(leave), _i(bo), _i(st)))
+        return _parametric_dict(out)
+
+    def basis_parametric_cost_fits(self, m, n):
+        """lp_basis_parametric_cost_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
+        return bool(self.lib.lp_basis_parametric_cost_fits(m, n))
+
     # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
     def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):
         """lp_basis_certificate: evidence for an infeasible or unbounded verdict at `basis` (index n+i: the
@@ -812,6 +864,20 @@ class BatchedProblem:
         self.ctx.check(self.ctx.lib.lp_batched_parametric(self.h, _d(d), float(t_max), float(eps), int(max_breaks),
                                                           _i(nseg), _d(t), _d(obj), _d(slope), _i(enter), _i(leave),
                                                           _i(bo), _i(st)))
+        return _parametric_dict(out)
+
+    def parametric_cost(self, g, t_max=np.inf, eps=EPS, max_breaks=MAX_BREAKS):
+        """lp_batched_parametric_cost after run(): the dict of Context.basis_parametric_cost_batched from each LP's
+        final basis, g (batch, n), with the handle's sense; LPs whose run status is not OPTIMAL keep it and get
+        nseg 0."""
+        g = _f64(g).reshape(-1)
+        if g.size != self.batch * self.n:
+            raise ValueError(f"parametric_cost: expected {self.batch * self.n} cost direction entries, got {g.size}")
+        out = _parametric_out(self.batch, self.m, max(int(max_breaks), 0))
+        nseg, t, obj, slope, enter, leave, bo, st = out
+        self.ctx.check(self.ctx.lib.lp_batched_parametric_cost(self.h, _d(g), float(t_max), float(eps),
+                                                               int(max_breaks), _i(nseg), _d(t), _d(obj), _d(slope),
+                                                               _i(enter), _i(leave), _i(bo), _i(st)))
         return _parametric_dict(out)
 
     def path(self):

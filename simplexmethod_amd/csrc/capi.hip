@@ -1677,4 +1677,242 @@ int lp_batched_parametric(lp_batched_problem* p, const double* d, double t_max, 
     return LP_OPTIMAL;
 }
 
+// ===========================================================================
+// Parametric cost from an optimal basis (basis_parametric_cost.hip): one LP per workgroup for
+// lp_basis_parametric_cost_fits(m, n), the single-LP launch path one LP after another beyond it
+// ===========================================================================
+
+int lp_basis_parametric_cost_fits(int m, int n) {
+    return m > 0 && n >= m && lp_basis_parametric_cost_lds_bytes(m, n, nullptr) <= 160 * 1024 ? 1 : 0;
+}
+
+// Cost paths of `batch` LPs whose inputs (g included) are on the device; drun_status (device, or nullptr): LPs whose run
+// status is not LP_OPTIMAL keep it and get nseg 0.  Outputs to the host.
+static int parametric_cost_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
+                                     const double* dc, const int* dbasis, const int* drun_status, const double* dg,
+                                     int maximize, double t_max, double eps, int mb, int* nseg_out, double* t_out,
+                                     double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out,
+                                     int* status_out) {
+    hipStream_t s = ctx->stream;
+    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
+    const size_t bytes = sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, bytes));
+    BasisParametricCostDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_basis_parametric_cost_lds_bytes(m, n, &d.pitch);
+    d.max_breaks = mb;
+    d.eps = eps;
+    d.t_max = t_max;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.g = dg;
+    d.basis = dbasis;
+    d.run_status = drun_status;
+    d.t = reinterpret_cast<double*>(buf);
+    d.obj = d.t + nt;
+    d.slope = d.obj + nt;
+    d.enter = reinterpret_cast<int*>(d.slope + ns);
+    d.leave = d.enter + ns;
+    d.basis_out = d.leave + ns;
+    d.nseg = d.basis_out + B * m;
+    d.status = d.nseg + B;
+    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
+    std::vector<int> basis;         // per-LP path: the given bases
+    int rc = LP_OPTIMAL;
+    if (lp_basis_parametric_cost_fits(m, n)) {
+        rc = lp_basis_parametric_cost_launch(ctx, d, maximize);
+    } else {   // one LP after another: statuses and bases checked on the host
+        std::vector<int> st(B, LP_OPTIMAL);
+        basis.resize(B * m);
+        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && drun_status)
+            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            LP_HIP(ctx, e);
+        }
+        for (size_t k = 0; k < B && rc >= 0; ++k) {
+            done[k] = 0;
+            if (st[k] != LP_OPTIMAL) continue;
+            for (int t = 0; t < m; ++t)
+                if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
+            if (st[k] != LP_OPTIMAL) continue;
+            rc = lp_basis_parametric_cost_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
+                                            dg + k * n, maximize, t_max, eps, mb, d.nseg + k, d.t + k * (mb + 2),
+                                            d.obj + k * (mb + 2), d.slope + k * (mb + 1), d.enter + k * (mb + 1),
+                                            d.leave + k * (mb + 1), d.basis_out + k * m);
+            if (rc < 0) break;
+            st[k] = rc;
+            done[k] = rc == LP_OPTIMAL || rc == LP_UNBOUNDED || rc == LP_ITER_LIMIT;
+        }
+        if (rc >= 0) {
+            rc = LP_OPTIMAL;
+            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = -(int)e;
+        }
+    }
+    if (rc == LP_OPTIMAL) {
+        hipError_t e = hipMemcpyAsync(t_out, d.t, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(obj_out, d.obj, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(slope_out, d.slope, sizeof(double) * ns, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(enter_out, d.enter, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(leave_out, d.leave, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(basis_out, d.basis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nseg_out, d.nseg, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("basis parametric cost: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    }
+    (void)hipFree(buf);
+    if (rc != LP_OPTIMAL) return rc;
+    if (!basis.empty())   // the per-LP path writes the path only: the rest is NaN / -1, and LPs without one get it all
+        for (size_t k = 0; k < B; ++k) {
+            if (!done[k]) {
+                parametric_none(k, m, mb, basis.data() + k * m, nseg_out, t_out, obj_out, slope_out, enter_out,
+                                leave_out, basis_out);
+                continue;
+            }
+            const int ns_k = nseg_out[k];
+            for (int q = ns_k + 1; q < mb + 2; ++q) t_out[k * (mb + 2) + q] = obj_out[k * (mb + 2) + q] = NAN;
+            for (int q = ns_k; q < mb + 1; ++q) {
+                slope_out[k * (mb + 1) + q] = NAN;
+                enter_out[k * (mb + 1) + q] = leave_out[k * (mb + 1) + q] = -1;
+            }
+        }
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` LPs and their cost directions, then parametric_cost_on_device.
+static int parametric_cost_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                  const double* c, const int* basis, int maximize, const double* g, double t_max,
+                                  double eps, int mb, int* nseg_out, double* t_out, double* obj_out, double* slope_out,
+                                  int* enter_out, int* leave_out, int* basis_out, int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + 2 * n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    double* dg = dc + B * n;
+    int* dbasis = reinterpret_cast<int*>(dg + B * n);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dg, g, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = LP_OPTIMAL;
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("basis parametric cost upload: ") + hipGetErrorString(e);
+        rc = -(int)e;
+    } else {
+        rc = parametric_cost_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, dg, maximize, t_max, eps, mb,
+                                       nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int lp_basis_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                             const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks,
+                             int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                             int* leave_out, int* basis_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: bad dimensions");
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: max_breaks must be >= 0");
+    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+    int rc = parametric_args(ctx, "lp_basis_parametric_cost", t_max, eps, max_breaks);
+    if (rc) return rc;
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    int status = LP_OPTIMAL;
+    rc = parametric_cost_upload(ctx, 1, A, m, n, b, c, basis, maximize, g, t_max, eps, max_breaks, nseg_out, t_out,
+                                obj_out, slope_out, enter_out, leave_out, basis_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: the basis is not optimal at t = 0");
+    return status;
+}
+
+int lp_basis_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                     const double* c, const int* basis, int maximize, const double* g, double t_max,
+                                     double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
+                                     double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: bad dimensions");
+    const int rc = parametric_args(ctx, "lp_basis_parametric_cost_batched", t_max, eps, max_breaks);
+    if (rc) return rc;
+    return parametric_cost_upload(ctx, batch, A, m, n, b, c, basis, maximize, g, t_max, eps, max_breaks, nseg_out, t_out,
+                                  obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+}
+
+int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_max, double eps, int max_breaks,
+                               int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                               int* leave_out, int* basis_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: null argument");
+    int rc = parametric_args(ctx, "lp_batched_parametric_cost", t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: the batch has not run");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int m = p->m, n = p->n, mb = max_breaks;
+    const size_t B = (size_t)p->batch;
+    if (p->resident) {   // A, b, c, the final bases and the run statuses where the run left them; g goes up
+        double* dg = nullptr;
+        LP_HIP(ctx, hipMalloc(&dg, sizeof(double) * B * n));
+        hipError_t e = hipMemcpyAsync(dg, g, sizeof(double) * B * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(dg);
+            LP_HIP(ctx, e);
+        }
+        rc = parametric_cost_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, dg,
+                                       p->maximize, t_max, eps, mb, nseg_out, t_out, obj_out, slope_out, enter_out,
+                                       leave_out, basis_out, status_out);
+        (void)hipFree(dg);
+        return rc;
+    }
+    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
+    std::vector<int> basis((size_t)m);
+    for (size_t k = 0; k < B; ++k) {
+        if (p->two_phase || p->resolve) {
+            std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
+        } else {
+            rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
+            if (rc) return rc;
+        }
+        int st = p->status[k];
+        parametric_none(k, m, mb, basis.data(), nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+        if (st == LP_OPTIMAL) {
+            st = lp_basis_parametric_cost(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m,
+                                          p->h_c.data() + k * n, basis.data(), p->maximize, g + k * n, t_max, eps, mb,
+                                          nseg_out + k, t_out + k * (mb + 2), obj_out + k * (mb + 2),
+                                          slope_out + k * (mb + 1), enter_out + k * (mb + 1), leave_out + k * (mb + 1),
+                                          basis_out + k * m);
+            if (st < 0) return st;
+        }
+        status_out[k] = st;
+    }
+    ctx->last_error.clear();
+    return LP_OPTIMAL;
+}
+
 }  // extern "C"

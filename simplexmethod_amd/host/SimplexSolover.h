@@ -236,6 +236,47 @@ public:
         return out;
     }
 
+    // The optimal value along c + t g for t in [0, tMax] (lp_basis_parametric_cost) from a result's final basis, with
+    // EPS and the problem's sense, in the Parametric form of parametricRhs: breakpoints t (nseg+1), the optimal value
+    // at each (obj, nseg+1), the slope of each segment and the pivot that ends it (enter / leave, nseg; leave -1 on the
+    // last segment).  status: LP_OPTIMAL (reached tMax), LP_UNBOUNDED (unbounded past the last t), LP_ITER_LIMIT (more
+    // than MAX_BREAKS breakpoints), LP_SINGULAR; a result that is not LP_OPTIMAL keeps its status and gets no
+    // segments.
+    Parametric parametricCost(const Result& r, const lpla::VectorXd& g, double tMax) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        Parametric out;
+        out.status = r.status;
+        out.basis = r.basis;
+        int nseg = 0;
+        std::vector<double> t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1);
+        std::vector<int> enter(MAX_BREAKS + 1), leave(MAX_BREAKS + 1);
+        if (r.status == LP_OPTIMAL) {
+            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::parametricCost: basis size != rows(A)");
+            if ((int)g.size() != n) throw std::invalid_argument("Solver::parametricCost: g size != cols(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.basis.assign((size_t)m, -1);
+            out.status = lp_basis_parametric_cost(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
+                                                  _problem.IsMaximization() ? 1 : 0, g.data(), tMax, EPS, MAX_BREAKS,
+                                                  &nseg, t.data(), obj.data(), slope.data(), enter.data(),
+                                                  leave.data(), out.basis.data());
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+        out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+        out.slope = lpla::VectorXd::Zero(nseg);
+        for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
+            out.t[k] = t[(size_t)k];
+            out.obj[k] = obj[(size_t)k];
+        }
+        for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
+        out.enter.assign(enter.begin(), enter.begin() + nseg);
+        out.leave.assign(leave.begin(), leave.begin() + nseg);
+        return out;
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
