@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -496,6 +496,40 @@ int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_
 /* 1: the shape fits the one-LP-per-workgroup kernel (its LDS <= 160 KB, e.g. the batched two-phase 64 x 192 class),
  * 0 otherwise.                                                                                              */
 int lp_basis_parametric_cost_fits(int m, int n);
+
+/* =========================================================================
+ * Integer LPs: depth-first branch-and-bound, one problem per workgroup (the definition is
+ * tests/ref/mip_ref.c).  The columns j with integer[j] = 1 (j < n_orig; one mask of n entries for the whole batch)
+ * must be integral.  The root starts from `basis` as lp_simplex_resolve does (primal feasible -> primal simplex, else
+ * dual feasible -> dual simplex, else LP_BAD_ARG; singular -> LP_SINGULAR) and is bit-identical to it.  x_j is
+ * integral iff min(f, 1-f) <= int_tol, f = x_j - floor(x_j); the most fractional marked variable branches (ties to
+ * the lowest index), the side nearer to its value first.  Each branch appends one row and one slack (variable
+ * n + level): the first child to the parent's final tableau in tableau form (dual simplex), the second child by a
+ * crash from A, the path's branch rows and the parent's basis.  A node is pruned unless its LP optimum beats the
+ * incumbent by more than gap.  Dantzig's rule only.
+ *   - max_depth (0..64) bounds the appended rows: a fractional node there is abandoned and the search goes on;
+ *     max_nodes (>= 1) bounds the node LP solves (the root is 1) and max_iter each node's pivots: either stops the
+ *     search.  Any of the three makes the status LP_ITER_LIMIT with the incumbent kept.  A node whose crash gives
+ *     LP_SINGULAR or LP_BAD_ARG stops the search with that status (not expected on well-conditioned input).
+ *   - status: LP_OPTIMAL (the incumbent is optimal), LP_INFEASIBLE (no integer point, or the root is infeasible),
+ *     LP_UNBOUNDED (the root relaxation), LP_ITER_LIMIT, LP_SINGULAR / LP_BAD_ARG.
+ *   - found_out 0/1; x_out (n_orig) and obj_out the incumbent, NaN without one; bound_out the best LP objective
+ *     over the incumbent and the nodes left open or abandoned (equal to obj_out on LP_OPTIMAL; +-inf when the root
+ *     relaxation is unbounded or unfinished; NaN with neither); stats_out[4] = nodes solved, dual pivots, primal
+ *     pivots, deepest level (crash pivots not counted).
+ *   - only shapes with lp_mip_fits(m, n, max_depth) run: the others get LP_BAD_ARG.  There is no per-LP host path.
+ * ========================================================================= */
+int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
+/* A batch of problems of one shape and one mask: A batch*m*n, b batch*m, c batch*n, basis batch*m; outputs x_out
+ * batch*n_orig, obj_out / bound_out / found_out / status_out batch, stats_out batch*4.                          */
+int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out);
+/* From the final bases of a plain, two-phase or re-solve batch after lp_batched_run (LP_BAD_ARG before the first
+ * run, and for a batch set to LP_PIVOT_BLAND).  LPs whose run did not end LP_OPTIMAL keep their status.  Outputs as
+ * lp_mip_solve_batched.                                                                                         */
+int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out);
+/* 1: the search's LDS carve (the (m+max_depth+1) x (n+max_depth+1) tableau and the per-level records) fits one
+ * CU's 160 KB and max_depth is in [0, 64]; 0 otherwise.                                                      */
+int lp_mip_fits(int m, int n, int max_depth);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

@@ -276,6 +276,27 @@ def build_parametric_cost_ref(force=False, verbose=False):
     return PARAMETRIC_COST_REF_LIB
 
 
+MIP_REF_LIB = os.path.join(TESTS_REF, "_build", "libmip_ref.so")
+
+
+def build_mip_ref(force=False, verbose=False):
+    """tests/ref/mip_ref.c (which includes resolve_ref.c) -> tests/ref/_build/libmip_ref.so: the depth-first
+    branch-and-bound the tests compare against; flags as build_resolve_ref."""
+    src = os.path.join(TESTS_REF, "mip_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "resolve_ref.c")]
+    if not force and _newer(MIP_REF_LIB, deps):
+        return MIP_REF_LIB
+    os.makedirs(os.path.dirname(MIP_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", MIP_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return MIP_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -286,6 +307,7 @@ def build_all(force=False, verbose=False):
     build_certificate_ref(force, verbose)
     build_parametric_ref(force, verbose)
     build_parametric_cost_ref(force, verbose)
+    build_mip_ref(force, verbose)
     return hip, host
 
 

@@ -131,6 +131,14 @@ SIGNATURES = {
     "lp_batched_parametric_cost": (C.c_int, [_vp, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip,
                                              _ip, _ip]),
     "lp_basis_parametric_cost_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_mip_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_double,
+                               C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]),
+    "lp_mip_solve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int, _ip,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                       _ip, _ip, _ip]),
+    "lp_batched_mip": (C.c_int, [_vp, _ip, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                 _dp, _ip, _ip, _ip]),
+    "lp_mip_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -272,6 +280,27 @@ def gen_lp(seed, m, n):
 
 
 MAX_BREAKS = 64   # default bound on the breakpoints of a parametric path
+INT_TOL = 1e-6    # branch-and-bound defaults: integrality tolerance, pruning gap, depth and node limits
+GAP = 1e-9
+MAX_DEPTH = 32
+MAX_NODES = 100000
+
+
+def _mip_out(batch, n_orig):
+    return (np.zeros((batch, n_orig)), np.zeros(batch), np.zeros(batch), np.zeros(batch, np.int32),
+            np.zeros((batch, 4), np.int32), np.zeros(batch, np.int32))
+
+
+def _mip_dict(out):
+    x, obj, bound, found, stats, st = out
+    return dict(status=st, found=found, x=x, obj=obj, bound=bound, stats=stats)
+
+
+def _mask(integer, n):
+    integer = np.ascontiguousarray(integer, dtype=np.int32).reshape(-1)
+    if integer.size != n:
+        raise ValueError(f"integer mask: expected {n} entries, got {integer.size}")
+    return integer
 
 
 def _parametric_out(batch, m, max_breaks):
@@ -574,6 +603,50 @@ class Context:
     def basis_parametric_cost_fits(self, m, n):
         """lp_basis_parametric_cost_fits: True if an m x n LP runs the one-LP-per-workgroup kernel."""
         return bool(self.lib.lp_basis_parametric_cost_fits(m, n))
+
+    # ---- depth-first branch-and-bound for integer LPs -------------------------------------------
+    def mip(self, A, b, c, basis, integer, maximize=True, n_orig=None, eps=EPS, int_tol=INT_TOL, gap=GAP,
+            max_depth=MAX_DEPTH, max_nodes=MAX_NODES, max_iter=MAX_ITER):
+        """lp_mip_solve: opt c.x, A x = b, x >= 0, x_j integral where integer[j] (n entries, 0/1, j < n_orig), from
+        the root basis `basis` (as resolve: primal or dual feasible).  dict(status, found, x (n_orig), obj, bound,
+        stats (nodes, dual pivots, primal pivots, deepest level)); x and obj NaN without an incumbent.  A basis that
+        is no valid start, a bad argument or a shape beyond mip_fits raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        integer = _mask(integer, n)
+        x, obj, bound, found, stats, _ = _mip_out(1, n_orig)
+        rc = self.check(self.lib.lp_mip_solve(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize), n_orig,
+                                              _i(integer), float(eps), float(int_tol), float(gap), int(max_depth),
+                                              int(max_nodes), int(max_iter), _d(x), _d(obj), _d(bound), _i(found),
+                                              _i(stats)))
+        return dict(status=rc, found=int(found[0]), x=x[0], obj=float(obj[0]), bound=float(bound[0]),
+                    stats=tuple(int(v) for v in stats[0]))
+
+    def mip_batched(self, A, b, c, basis, integer, maximize=True, n_orig=None, eps=EPS, int_tol=INT_TOL, gap=GAP,
+                    max_depth=MAX_DEPTH, max_nodes=MAX_NODES, max_iter=MAX_ITER):
+        """lp_mip_solve_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m), one mask (n).
+        dict(status, found, obj, bound (batch), x (batch, n_orig), stats (batch, 4))."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        integer = _mask(integer, n)
+        out = _mip_out(batch, n_orig)
+        x, obj, bound, found, stats, st = out
+        self.check(self.lib.lp_mip_solve_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
+                                                 n_orig, _i(integer), float(eps), float(int_tol), float(gap),
+                                                 int(max_depth), int(max_nodes), int(max_iter), _d(x), _d(obj),
+                                                 _d(bound), _i(found), _i(stats), _i(st)))
+        return _mip_dict(out)
+
+    def mip_fits(self, m, n, max_depth=MAX_DEPTH):
+        """lp_mip_fits: True if an m x n problem searched to max_depth fits one CU's LDS."""
+        return bool(self.lib.lp_mip_fits(m, n, max_depth))
 
     # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
     def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):
@@ -879,6 +952,18 @@ class BatchedProblem:
                                                                int(max_breaks), _i(nseg), _d(t), _d(obj), _d(slope),
                                                                _i(enter), _i(leave), _i(bo), _i(st)))
         return _parametric_dict(out)
+
+    def mip(self, integer, eps=EPS, int_tol=INT_TOL, gap=GAP, max_depth=MAX_DEPTH, max_nodes=MAX_NODES,
+            max_iter=MAX_ITER):
+        """lp_batched_mip after run(): the dict of Context.mip_batched from each LP's final basis with the handle's
+        sense; LPs whose run status is not OPTIMAL keep it (found 0, NaN)."""
+        integer = _mask(integer, self.n)
+        out = _mip_out(self.batch, self.n_orig)
+        x, obj, bound, found, stats, st = out
+        self.ctx.check(self.ctx.lib.lp_batched_mip(self.h, _i(integer), float(eps), float(int_tol), float(gap),
+                                                   int(max_depth), int(max_nodes), int(max_iter), _d(x), _d(obj),
+                                                   _d(bound), _i(found), _i(stats), _i(st)))
+        return _mip_dict(out)
 
     def path(self):
         """1: one LP per workgroup on the GPU; 0: the per-LP fallback."""

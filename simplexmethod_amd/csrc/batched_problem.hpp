@@ -223,3 +223,31 @@ int lp_basis_parametric_cost_device(lp_context* ctx, const double* dA, int m, in
                                     const double* dc, const int* dbasis, const double* dg, int maximize, double t_max,
                                     double eps, int max_breaks, int* dnseg, double* dt, double* dobj, double* dslope,
                                     int* denter, int* dleave, int* dbasis_out);
+
+// Depth-first branch-and-bound, one integer LP per workgroup (batched_mip.hip): the re-solve's root, then per node a
+// row appended in tableau form (first child) or a crash from A and the path's branch rows (second child).
+#define LP_MIP_MAX_DEPTH 64
+struct BatchedMipDev {
+    int batch, m, n, n_orig;
+    int maximize;
+    int max_iter;           // per node
+    int max_depth, max_nodes;
+    double eps, int_tol, gap;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const int* basis_in;    // batch x m (by position): the root's start
+    const int* run_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it (found 0, NaN outputs)
+    const int* integer;     // n: the mask, one for the whole batch
+    double* x;              // batch x n_orig: the incumbent, NaN without one
+    double* obj;            // batch
+    double* bound;          // batch
+    int* found;             // batch
+    int* stats;             // batch x 4: nodes, dual pivots, primal pivots, deepest level
+    int* status;            // batch
+};
+
+// batched_mip.hip
+size_t lp_mip_lds_bytes(int m, int n, int max_depth);
+bool lp_mip_fits_shape(int m, int n, int max_depth);
+int lp_batched_mip_launch(lp_context* ctx, const BatchedMipDev& d);   // fitting shapes, else LP_BAD_ARG

@@ -86,41 +86,7 @@ __global__ __launch_bounds__(NT) void k_batched_resolve(BatchedResolveDev d) {
 #include "batched_resolve_crash.hpp"
 
     // ---- the dual loop: leaving position, then entering slot, both chains by wave 0
-    auto dual = [&](int& iters) -> int {
-        if (d.max_iter <= 0) return LP_ITER_LIMIT;
-        for (;;) {
-            if (wave == 0) {
-                double best;
-                const int r0 = wave_scan_keyed<false>(m, eps, best, [&](int t, double& v, int& k, bool& ok) {
-                    v = T[(size_t)t * pitch + n];
-                    k = t;
-                    ok = v < -eps;
-                });
-                int se0 = -1;
-                if (r0 >= 0) {
-                    const double* rrow = T + (size_t)r0 * pitch;
-                    const double* drow = T + (size_t)m * pitch;
-                    se0 = wave_scan_keyed<false>(n, eps, best, [&](int s, double& v, int& k, bool& ok) {
-                        const double a = rrow[s];
-                        k = slotvar[s];
-                        ok = k < n && a < -eps;
-                        v = maximize ? drow[s] / a : -drow[s] / a;
-                    });
-                }
-                if (lane == 0) {
-                    pub[0] = se0;
-                    pub[1] = r0;
-                }
-            }
-            __syncthreads();
-            const int se = pub[0], r = pub[1];
-            if (r < 0) return LP_OPTIMAL;
-            if (se < 0) return LP_INFEASIBLE;
-            pivot(r, se);
-            ++iters;
-            if (iters >= d.max_iter) return LP_ITER_LIMIT;
-        }
-    };
+#include "batched_dual_loop.hpp"
 
     int it[2] = {0, 0};   // dual pivots, primal pivots
     if (status == LP_OPTIMAL) {

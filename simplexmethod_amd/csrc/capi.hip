@@ -1915,4 +1915,195 @@ int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_
     return LP_OPTIMAL;
 }
 
+// ===========================================================================
+// Depth-first branch-and-bound (batched_mip.hip): one integer LP per workgroup for lp_mip_fits shapes only; there is
+// no per-LP host fallback
+// ===========================================================================
+
+int lp_mip_fits(int m, int n, int max_depth) { return lp_mip_fits_shape(m, n, max_depth) ? 1 : 0; }
+
+// The search parameters and the mask (the basis and the problem arrays are checked by the callers).
+static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, const int* integer, double int_tol,
+                    double gap, int max_depth, int max_nodes) {
+    if (!integer) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (max_depth < 0 || max_depth > LP_MIP_MAX_DEPTH)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_depth must be in [0, 64]");
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": int_tol must be in [0, 0.5)");
+    if (!(gap >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": gap must be >= 0");
+    if (max_nodes < 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_nodes must be >= 1");
+    for (int j = 0; j < n; ++j) {
+        if (integer[j] != 0 && integer[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": mask entries must be 0 or 1");
+        if (integer[j] && j >= n_orig)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the mask marks a column beyond n_orig");
+    }
+    if (!lp_mip_fits_shape(m, n, max_depth))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_mip_fits)");
+    return LP_OPTIMAL;
+}
+
+// The search of `batch` problems whose A, b, c and root bases are on the device; drun_status (device, or nullptr):
+// problems whose entry is not LP_OPTIMAL keep it.  The mask goes up; outputs to the host.
+static int mip_on_device(lp_context* ctx, int batch, int m, int n, int n_orig, const double* dA, const double* db,
+                         const double* dc, const int* dbasis, const int* drun_status, const int* integer, int maximize,
+                         double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter,
+                         double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
+                         int* status_out) {
+    hipStream_t s = ctx->stream;
+    const size_t B = (size_t)batch;
+    const size_t bytes = sizeof(double) * (B * n_orig + 2 * B) + sizeof(int) * (B * 6 + n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, bytes));
+    BatchedMipDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.n_orig = n_orig;
+    d.maximize = maximize ? 1 : 0;
+    d.max_iter = max_iter;
+    d.max_depth = max_depth;
+    d.max_nodes = max_nodes;
+    d.eps = eps;
+    d.int_tol = int_tol;
+    d.gap = gap;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.basis_in = dbasis;
+    d.run_status = drun_status;
+    d.x = reinterpret_cast<double*>(buf);
+    d.obj = d.x + B * n_orig;
+    d.bound = d.obj + B;
+    d.found = reinterpret_cast<int*>(d.bound + B);
+    d.stats = d.found + B;
+    d.status = d.stats + B * 4;
+    int* dmask = d.status + B;
+    d.integer = dmask;
+    hipError_t e = hipMemcpyAsync(dmask, integer, sizeof(int) * n, hipMemcpyHostToDevice, s);
+    int rc = e == hipSuccess ? lp_batched_mip_launch(ctx, d) : -(int)e;
+    if (rc == LP_OPTIMAL) {
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(x_out, d.x, sizeof(double) * B * n_orig, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(obj_out, d.obj, sizeof(double) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(bound_out, d.bound, sizeof(double) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(found_out, d.found, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(stats_out, d.stats, sizeof(int) * B * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("batched MIP: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    } else if (rc < 0) {
+        ctx->last_error = std::string("batched MIP upload: ") + hipGetErrorString(e);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+// Uploads `batch` problems and their root bases, then mip_on_device.
+static int mip_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                      const int* basis, int maximize, int n_orig, const int* run_status, const int* integer,
+                      double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter,
+                      double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
+                      int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * (m + 1)));
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    int* dbasis = reinterpret_cast<int*>(dc + B * n);
+    int* drun = dbasis + B * m;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && run_status) e = hipMemcpyAsync(drun, run_status, sizeof(int) * B, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = LP_OPTIMAL;
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("batched MIP upload: ") + hipGetErrorString(e);
+        rc = -(int)e;
+    } else {
+        rc = mip_on_device(ctx, batch, m, n, n_orig, dA, db, dc, dbasis, run_status ? drun : nullptr, integer,
+                           maximize, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out,
+                           found_out, stats_out, status_out);
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const int* basis,
+                 int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth,
+                 int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
+                 int* stats_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: null argument");
+    int rc = check_canonical(ctx, A, m, n, b, c, basis, n_orig);
+    if (rc) return rc;
+    rc = mip_args(ctx, "lp_mip_solve", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = mip_upload(ctx, 1, A, m, n, b, c, basis, maximize, n_orig, nullptr, integer, eps, int_tol, gap, max_depth,
+                    max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: the basis is neither primal nor dual feasible");
+    return status;
+}
+
+int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                         const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol,
+                         double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
+                         double* bound_out, int* found_out, int* stats_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve_batched: null argument");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    for (int k = 0; k < batch; ++k) {
+        int rc = check_canonical(ctx, A ? A + (size_t)k * m * n : nullptr, m, n, b ? b + (size_t)k * m : nullptr,
+                                 c ? c + (size_t)k * n : nullptr, basis ? basis + (size_t)k * m : nullptr, n_orig);
+        if (rc) return rc;
+    }
+    const int rc = mip_args(ctx, "lp_mip_solve_batched", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    return mip_upload(ctx, batch, A, m, n, b, c, basis, maximize, n_orig, nullptr, integer, eps, int_tol, gap,
+                      max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, status_out);
+}
+
+int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double int_tol, double gap, int max_depth,
+                   int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
+                   int* stats_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: null argument");
+    int rc = mip_args(ctx, "lp_batched_mip", p->m, p->n, p->n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: Dantzig's rule only");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: the batch has not run");
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int m = p->m, n = p->n;
+    const size_t B = (size_t)p->batch;
+    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
+        return mip_on_device(ctx, p->batch, m, n, p->n_orig, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, integer,
+                             p->maximize, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out,
+                             bound_out, found_out, stats_out, status_out);
+    // per-LP runs: the kept inputs and each LP's final basis go up, then the same kernel
+    std::vector<int> basis(B * m);
+    for (size_t k = 0; k < B; ++k) {
+        if (p->two_phase || p->resolve) {
+            std::memcpy(basis.data() + k * m, p->h_basis.data() + k * m, sizeof(int) * m);
+        } else {
+            rc = lp_simplex_download(p->lps[k], nullptr, basis.data() + k * m, nullptr, nullptr, nullptr, 0, nullptr);
+            if (rc) return rc;
+        }
+    }
+    return mip_upload(ctx, p->batch, p->h_A.data(), m, n, p->h_b.data(), p->h_c.data(), basis.data(), p->maximize,
+                      p->n_orig, p->status.data(), integer, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out,
+                      obj_out, bound_out, found_out, stats_out, status_out);
+}
+
 }  // extern "C"

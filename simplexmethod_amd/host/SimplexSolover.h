@@ -277,6 +277,57 @@ public:
         return out;
     }
 
+    // Depth-first branch-and-bound (lp_mip_solve) with EPS and the problem's sense: the columns j with integer[j]
+    // (one entry per column of A, none past the original variables) must be integral.  The root starts from the
+    // problem's own basis, or from a result's final basis in the second form (a result that is not LP_OPTIMAL keeps
+    // its status and gets found = false).  status: LP_OPTIMAL (the incumbent is optimal), LP_INFEASIBLE,
+    // LP_UNBOUNDED (the root relaxation), LP_ITER_LIMIT (a depth, node or pivot limit: bound - objective is the gap
+    // left), LP_SINGULAR.  x holds the original variables of the incumbent, NaN without one.  A basis that is no
+    // valid start, a bad mask or a shape beyond lp_mip_fits throws std::invalid_argument.
+    struct IntegerResult {
+        int status = LP_OPTIMAL;
+        bool found = false;
+        lpla::VectorXd x;
+        double objective = std::numeric_limits<double>::quiet_NaN();
+        double bound = std::numeric_limits<double>::quiet_NaN();
+        int nodes = 0;
+    };
+    static constexpr double INT_TOL = 1e-6;
+    static constexpr double MIP_GAP = 1e-9;
+
+    IntegerResult branchAndBound(const std::vector<bool>& integer, int maxDepth = 32, int maxNodes = 100000) const {
+        Result r;
+        r.status = LP_OPTIMAL;
+        r.basis = _problem.GetBasisIndices();
+        return branchAndBound(integer, r, maxDepth, maxNodes);
+    }
+
+    IntegerResult branchAndBound(const std::vector<bool>& integer, const Result& r, int maxDepth = 32,
+                                 int maxNodes = 100000) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
+        IntegerResult out;
+        out.status = r.status;
+        out.x = lpla::VectorXd::Zero(no);
+        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        if (r.status != LP_OPTIMAL) return out;
+        if ((int)integer.size() != n) throw std::invalid_argument("Solver::branchAndBound: mask size != cols(A)");
+        if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::branchAndBound: basis size != rows(A)");
+        std::vector<int> mask((size_t)n);
+        for (int j = 0; j < n; ++j) mask[(size_t)j] = integer[(size_t)j] ? 1 : 0;
+        lp_context* ctx = lpgpu::context(_device);
+        int found = 0, stats[4] = {0, 0, 0, 0};
+        out.status = lp_mip_solve(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
+                                  _problem.IsMaximization() ? 1 : 0, no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth,
+                                  maxNodes, MAX_ITER, out.x.data(), &out.objective, &out.bound, &found, stats);
+        if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        out.found = found != 0;
+        out.nodes = stats[0];
+        return out;
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
