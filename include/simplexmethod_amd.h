@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -530,6 +530,31 @@ int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double
 /* 1: the search's LDS carve (the (m+max_depth+1) x (n+max_depth+1) tableau and the per-level records) fits one
  * CU's 160 KB and max_depth is in [0, 64]; 0 otherwise.                                                      */
 int lp_mip_fits(int m, int n, int max_depth);
+
+/* =========================================================================
+ * Bounded variables: the two-phase bounded-variable primal simplex, one LP per workgroup (the
+ * definition is tests/ref/bounded_ref.c).  Problem: opt c.x, A x = b, lo <= x <= hi with lo[n] finite and hi[n]
+ * finite or +inf (lo_j == hi_j: a fixed column).  The variables are shifted to x - lo in [0, hi - lo]; an upper
+ * bound is kept out of the tableau: the ratio test also stops a basic variable at its upper bound, an entering
+ * variable that reaches its own upper bound first FLIPS to it (no pivot), and a column at its upper bound is held
+ * complemented.  The phases are lp_simplex_two_phase's (rows with b' < -eps change sign, phase I over m artificials,
+ * LP_INFEASIBLE iff their sum > eps, the same drive-out with LP_SINGULAR, phase II on the phase-I tableau with the
+ * artificials barred).  Dantzig's rule only.  With lo = 0 and hi = +inf the result is lp_simplex_two_phase's.
+ *   - LP_BAD_ARG for a NaN or infinite lo_j, a NaN hi_j, a NULL pointer or a shape beyond lp_simplex_bounded_fits
+ *     (there is no per-LP host path); an LP with some hi_j < lo_j is LP_INFEASIBLE without an iteration.
+ *   - max_iter bounds each phase's iterations; an iteration is a pivot or a bound flip.
+ *   - outputs: x_out (n_orig) and obj_out (sum_{j<n} c_j x_j) for LP_OPTIMAL only; basis_out (m) and at_upper_out
+ *     (n, 0/1: 1 = the column is held complemented, i.e. at its upper bound when non-basic) always; iters_out[4] =
+ *     phase-I pivots, drive-out pivots, phase-II pivots, bound flips.  Every output pointer is required.
+ * ========================================================================= */
+int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
+/* A batch of LPs of one shape: A batch*m*n, b batch*m, c / lo / hi batch*n; outputs x_out batch*n_orig, basis_out
+ * batch*m, at_upper_out batch*n, obj_out / status_out batch, iters_out batch*4.  A bad lo or hi in any LP refuses
+ * the whole call (LP_BAD_ARG); an LP with hi < lo is LP_INFEASIBLE and the others are solved.                      */
+int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out);
+/* 1: the kernel's LDS carve (the (m+1) x (n+1) tableau, hi - lo and lo per column) fits one CU's 160 KB (64 x 192
+ * does), 0 otherwise.  A host call: no context, no device.                                                      */
+int lp_simplex_bounded_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

@@ -297,6 +297,26 @@ def build_mip_ref(force=False, verbose=False):
     return MIP_REF_LIB
 
 
+BOUNDED_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_ref.so")
+
+
+def build_bounded_ref(force=False, verbose=False):
+    """tests/ref/bounded_ref.c -> tests/ref/_build/libbounded_ref.so: the two-phase bounded-variable simplex the tests
+    compare against; flags as build_test_ref."""
+    src = os.path.join(TESTS_REF, "bounded_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(BOUNDED_REF_LIB, [src]):
+        return BOUNDED_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -308,6 +328,7 @@ def build_all(force=False, verbose=False):
     build_parametric_ref(force, verbose)
     build_parametric_cost_ref(force, verbose)
     build_mip_ref(force, verbose)
+    build_bounded_ref(force, verbose)
     return hip, host
 
 

@@ -251,3 +251,28 @@ struct BatchedMipDev {
 size_t lp_mip_lds_bytes(int m, int n, int max_depth);
 bool lp_mip_fits_shape(int m, int n, int max_depth);
 int lp_batched_mip_launch(lp_context* ctx, const BatchedMipDev& d);   // fitting shapes, else LP_BAD_ARG
+
+// A batch of same-shape LPs with variable bounds lo <= x <= hi solved by the two-phase bounded-variable simplex, one LP
+// per workgroup (batched_bounded.hip; the definition is tests/ref/bounded_ref.c).
+struct BatchedBoundedDev {
+    int batch, m, n;        // n = canonical columns (the m artificials are implicit)
+    int pitch;              // row pitch (doubles) of the LDS tableau, odd, >= n + 1
+    int maximize;
+    int max_iter;           // per phase: pivots plus bound flips
+    double eps;
+    const double* A;        // batch x (m*n), each column-major
+    const double* b;        // batch x m
+    const double* c;        // batch x n
+    const double* lo;       // batch x n, finite
+    const double* hi;       // batch x n, finite or +inf
+    double* x;              // batch x n  (full vertex; written for LP_OPTIMAL only)
+    int* basis_out;         // batch x m  (by position)
+    int* at_upper;          // batch x n  (0/1: the column is held complemented)
+    int* iters;             // batch x 4  (phase-I pivots, drive-out pivots, phase-II pivots, bound flips)
+    int* status;            // batch
+};
+
+// batched_bounded.hip
+size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
+bool lp_bounded_fits_shape(int m, int n);
+int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d);   // fitting shapes, else LP_BAD_ARG

@@ -2106,4 +2106,126 @@ int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double
                       obj_out, bound_out, found_out, stats_out, status_out);
 }
 
+
+// ===========================================================================
+// Bounded-variable simplex (batched_bounded.hip): one LP per workgroup for lp_simplex_bounded_fits shapes only; there
+// is no per-LP host fallback
+// ===========================================================================
+
+int lp_simplex_bounded_fits(int m, int n) { return lp_bounded_fits_shape(m, n) ? 1 : 0; }
+
+// The checks of both entry points: pointers, dimensions, the bounds of every LP (lo finite, hi not NaN) and the fit.
+static int bounded_args(lp_context* ctx, const char* who, int batch, const double* A, int m, int n, const double* b,
+                        const double* c, const double* lo, const double* hi, int n_orig) {
+    if (!A || !b || !c || !lo || !hi) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    const size_t N = (size_t)batch * n;
+    for (size_t j = 0; j < N; ++j) {
+        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
+        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
+    }
+    if (!lp_bounded_fits_shape(m, n))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_simplex_bounded_fits)");
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` LPs, runs k_batched_bounded and downloads; x (n_orig) and obj (over all n columns, as
+// lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.
+static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                         const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                         double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out,
+                         int* status_out) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch;
+    const size_t dbl = B * ((size_t)m * n + m + 4 * (size_t)n), ints = B * ((size_t)m + n + 4 + 1);
+    char* buf = nullptr;
+    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * ints));
+    BatchedBoundedDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_bounded_lds_bytes(m, n, &d.pitch);
+    d.maximize = maximize ? 1 : 0;
+    d.max_iter = max_iter;
+    d.eps = eps;
+    double* dA = reinterpret_cast<double*>(buf);
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    double* dlo = dc + B * n;
+    double* dhi = dlo + B * n;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.lo = dlo;
+    d.hi = dhi;
+    d.x = dhi + B * n;
+    d.basis_out = reinterpret_cast<int*>(d.x + B * n);
+    d.at_upper = d.basis_out + B * m;
+    d.iters = d.at_upper + B * n;
+    d.status = d.iters + B * 4;
+    std::vector<double> x(B * n);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dlo, lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dhi, hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    int rc = e == hipSuccess ? lp_batched_bounded_launch(ctx, d) : -(int)e;
+    if (rc == LP_OPTIMAL) {
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(x.data(), d.x, sizeof(double) * B * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(basis_out, d.basis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(at_upper_out, d.at_upper, sizeof(int) * B * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(iters_out, d.iters, sizeof(int) * B * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("batched bounded simplex: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    } else if (rc < 0) {
+        ctx->last_error = std::string("batched bounded simplex upload: ") + hipGetErrorString(e);
+    }
+    (void)hipFree(buf);
+    if (rc) return rc;
+    for (size_t k = 0; k < B; ++k) {
+        if (status_out[k] != LP_OPTIMAL) continue;
+        const double* xk = x.data() + k * n;
+        for (int j = 0; j < n_orig; ++j) x_out[k * n_orig + j] = xk[j];
+        double z = 0.0;   // Canonical::Evaluate, Canonical.cpp:86
+        const double* ck = c + k * n;
+        for (int j = 0; j < n; ++j) z += ck[j] * xk[j];
+        obj_out[k] = z;
+    }
+    return LP_OPTIMAL;
+}
+
+int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                       const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                       double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded: null argument");
+    int rc = bounded_args(ctx, "lp_simplex_bounded", 1, A, m, n, b, c, lo, hi, n_orig);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out,
+                       obj_out, iters_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                               const double* c, const double* lo, const double* hi, int maximize, int n_orig,
+                               double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
+                               double* obj_out, int* iters_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_batched: null argument");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    const int rc = bounded_args(ctx, "lp_simplex_bounded_batched", batch, A, m, n, b, c, lo, hi, n_orig);
+    if (rc) return rc;
+    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out,
+                         at_upper_out, obj_out, iters_out, status_out);
+}
+
 }  // extern "C"

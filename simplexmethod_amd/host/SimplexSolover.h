@@ -328,6 +328,43 @@ public:
         return out;
     }
 
+    // The two-phase bounded-variable simplex (lp_simplex_bounded) with EPS, MAX_ITER and the problem's sense:
+    // lo <= x <= hi per column of A (lo finite, hi finite or +inf, lo == hi a fixed column).  The problem's basis
+    // indices are ignored.  atUpper[j] = 1 where the column is held complemented (a non-basic column at its upper
+    // bound); iterations = phase-I pivots, drive-out pivots, phase-II pivots, bound flips.  x (the original
+    // variables) and objective are NaN unless LP_OPTIMAL.  Throws like twoPhaseSimplex (std::runtime_error for
+    // infeasible, unbounded, iteration limit, dependent rows) unless throw_on_failure is false; bad bounds, wrong
+    // sizes or a shape beyond lp_simplex_bounded_fits throw std::invalid_argument either way.
+    struct BoundedResult {
+        lpla::VectorXd x;
+        std::vector<int> basis;
+        std::vector<int> atUpper;
+        double objective = std::numeric_limits<double>::quiet_NaN();
+        int iterations[4] = {0, 0, 0, 0};
+        int status = LP_OPTIMAL;
+    };
+
+    BoundedResult boundedSimplex(const std::vector<double>& lo, const std::vector<double>& hi,
+                                 bool throw_on_failure = true) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedSimplex: lo / hi size != cols(A)");
+        BoundedResult out;
+        out.x = lpla::VectorXd::Zero(no);
+        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        out.basis.assign((size_t)m, -1);
+        out.atUpper.assign((size_t)n, 0);
+        lp_context* ctx = lpgpu::context(_device);
+        out.status = lp_simplex_bounded(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                        _problem.IsMaximization() ? 1 : 0, no, EPS, MAX_ITER, out.x.data(),
+                                        out.basis.data(), out.atUpper.data(), &out.objective, out.iterations);
+        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        return out;
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
