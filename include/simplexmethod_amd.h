@@ -323,8 +323,9 @@ int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, i
                            const double* c, const int* basis, double* y_out, double* d_out, double* w_out,
                            int* status_out);
 /* The duals of every LP of a batch handle (plain, two-phase or re-solve) at its final basis after
- * lp_batched_run, read where the run left A, b, c and the bases.  LPs whose run status is not LP_OPTIMAL
- * keep it in status_out and get NaN.  LP_BAD_ARG before the first run.                                */
+ * lp_batched_run: a resident handle reads A, b, c and the bases where the run left them, any other handle
+ * uploads the inputs it keeps once.  LPs whose run status is not LP_OPTIMAL keep it in status_out and get
+ * NaN.  LP_BAD_ARG before the first run.                                                              */
 int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out);
 /* 1: m fits the one-LP-per-workgroup kernel (its LDS <= 160 KB: m <= 140), 0 otherwise.               */
 int lp_basis_duals_fits(int m);

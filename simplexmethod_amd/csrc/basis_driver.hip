@@ -1,0 +1,927 @@
+// basis_driver.hip — the host side of every analysis that starts from an LP and a basis: the dual solution
+// (basis_duals.hip), ranging (basis_ranging.hip), certificates (basis_certificate.hip), the parametric right-hand
+// side (basis_parametric.hip), the parametric cost (basis_parametric_cost.hip) and branch-and-bound
+// (batched_mip.hip).  Each analysis has three entry points: lp_basis_X (one LP), lp_basis_X_batched (a batch from
+// the host) and lp_batched_X (a batch handle after its run).  All three put the inputs on the device (upload, or
+// where a resident run left them: batch_inputs) and call X_on_device, which launches the analysis's kernel when the
+// shape fits it and otherwise runs its single-LP device path one LP after another (per_lp).
+#include <cmath>
+#include <functional>
+
+#include "batched_problem.hpp"
+#include "lp_internal.hpp"
+#include "simplex_problem.hpp"
+
+// Device pointers to the inputs of a batch.
+struct BasisInputs {
+    const double *A = nullptr, *b = nullptr, *c = nullptr;
+    const int* basis = nullptr;
+    const int* run_status = nullptr;   // nullptr: every LP is taken as it is
+    const double* extra = nullptr;     // d (m per LP) or g (n per LP) of the parametric analyses
+};
+
+// One allocation held by `buf` for the non-null host arrays among A, b, c, `extra` (extra_len doubles per LP), the
+// bases and the run statuses; the copies are queued, then one sync.  Sets the device pointers of what went up.
+static int upload(lp_context* ctx, const char* what, lp_device_buffer& buf, int batch, int m, int n,
+                  const double* A, const double* b, const double* c, const double* extra, size_t extra_len,
+                  const int* basis, const int* run_status, BasisInputs& in) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch;
+    struct Part {
+        const void* host;
+        size_t bytes;
+    };
+    const Part parts[6] = {{A, sizeof(double) * B * m * n}, {b, sizeof(double) * B * m},
+                           {c, sizeof(double) * B * n},     {extra, sizeof(double) * B * extra_len},
+                           {basis, sizeof(int) * B * m},    {run_status, sizeof(int) * B}};   // doubles first
+    size_t bytes = 0;
+    for (const Part& q : parts) bytes += q.host ? q.bytes : 0;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, bytes));
+    const void* dev[6] = {};
+    hipError_t e = hipSuccess;
+    for (size_t i = 0, off = 0; i < 6; ++i) {
+        if (!parts[i].host) continue;
+        dev[i] = buf.ptr + off;
+        if (e == hipSuccess) e = hipMemcpyAsync(buf.ptr + off, parts[i].host, parts[i].bytes, hipMemcpyHostToDevice,
+                                                ctx->stream);
+        off += parts[i].bytes;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string(what) + " upload: " + hipGetErrorString(e));
+    if (A) in.A = static_cast<const double*>(dev[0]);
+    if (b) in.b = static_cast<const double*>(dev[1]);
+    if (c) in.c = static_cast<const double*>(dev[2]);
+    if (extra) in.extra = static_cast<const double*>(dev[3]);
+    if (basis) in.basis = static_cast<const int*>(dev[4]);
+    if (run_status) in.run_status = static_cast<const int*>(dev[5]);
+    return LP_OPTIMAL;
+}
+
+// The inputs of a batch handle after its run.  A resident handle's A, b, c, final bases and run statuses are where
+// the run left them, and only `extra` goes up.  Any other handle uploads its kept inputs, each LP's final basis and
+// the run statuses with it: the same route as a batch of its shape from the host.
+static int batch_inputs(lp_batched_problem* p, const char* what, lp_device_buffer& buf, const double* extra,
+                        size_t extra_len, BasisInputs& in) {
+    lp_context* ctx = p->ctx;
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const int batch = p->batch, m = p->m, n = p->n;
+    if (p->resident) {
+        in.A = p->dA;
+        in.b = p->db;
+        in.c = p->dc;
+        in.basis = p->dbasis_out;
+        in.run_status = p->dstatus;
+        if (!extra) return LP_OPTIMAL;
+        return upload(ctx, what, buf, batch, m, n, nullptr, nullptr, nullptr, extra, extra_len, nullptr, nullptr, in);
+    }
+    std::vector<int> basis;
+    if (p->two_phase || p->resolve) {
+        basis = p->h_basis;
+    } else {
+        basis.resize((size_t)batch * m);
+        for (size_t k = 0; k < (size_t)batch; ++k) {
+            const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data() + k * m, nullptr, nullptr, nullptr, 0,
+                                               nullptr);
+            if (rc) return rc;
+        }
+    }
+    return upload(ctx, what, buf, batch, m, n, p->h_A.data(), p->h_b.data(), p->h_c.data(), extra, extra_len,
+                  basis.data(), p->status.data(), in);
+}
+
+// Basis checks on the host: LP_BAD_ARG for an index outside [0, n), else LP_OPTIMAL.
+static int basis_in_range(const int* basis, int m, int n) {
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n) return LP_BAD_ARG;
+    return LP_OPTIMAL;
+}
+
+// The certificates' basis check: LP_BAD_ARG (an index outside [0, n+m)), LP_SINGULAR (a repeat), else LP_OPTIMAL.
+static int certificate_basis_check(const int* basis, int m, int n) {
+    for (int t = 0; t < m; ++t)
+        if (basis[t] < 0 || basis[t] >= n + m) return LP_BAD_ARG;
+    std::vector<char> seen((size_t)n + m, 0);
+    for (int t = 0; t < m; ++t) {
+        if (seen[(size_t)basis[t]]) return LP_SINGULAR;
+        seen[(size_t)basis[t]] = 1;
+    }
+    return LP_OPTIMAL;
+}
+
+static bool run_optimal(int st) { return st == LP_OPTIMAL; }
+static bool run_failed(int st) { return st == LP_INFEASIBLE || st == LP_UNBOUNDED; }
+static bool wrote_optimal(int rc) { return rc == LP_OPTIMAL; }
+
+// The per-LP path beyond a kernel's fit.  The bases and run statuses come to the host (`basis`).  LP k is taken
+// when it has no run status or `eligible` accepts it, and goes through `run(k)` (its lp_basis_X_device call) when
+// `check` passes its basis; a failed check, or a return code other than LP_OPTIMAL, becomes its status.  done[k]:
+// `written` accepts LP k's return code (its outputs were written).  The statuses go to dstatus.
+static int per_lp(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int* dstatus,
+                  bool (*eligible)(int), int (*check)(const int*, int, int), const std::function<int(size_t)>& run,
+                  bool (*written)(int), std::vector<char>& done, std::vector<int>& basis) {
+    const size_t B = (size_t)batch;
+    std::vector<int> st(B, LP_OPTIMAL);
+    basis.resize(B * m);
+    done.assign(B, 0);
+    const int rc = lp_download(ctx, "per-LP path", {{basis.data(), in.basis, sizeof(int) * B * m},
+                                                     {st.data(), in.run_status, in.run_status ? sizeof(int) * B : 0}});
+    if (rc) return rc;
+    for (size_t k = 0; k < B; ++k) {
+        if (in.run_status && !eligible(st[k])) continue;
+        int cs = check(basis.data() + k * m, m, n);
+        if (cs == LP_OPTIMAL) {
+            cs = run(k);
+            if (cs < 0) return cs;
+            done[k] = written(cs);
+        }
+        if (cs != LP_OPTIMAL) st[k] = cs;
+    }
+    LP_HIP(ctx, hipMemcpyAsync(dstatus, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
+    LP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LP_OPTIMAL;
+}
+
+extern "C" {
+
+// ===========================================================================
+// the dual solution at a given basis (basis_duals.hip)
+// ===========================================================================
+
+int lp_basis_duals_fits(int m) { return m > 0 && lp_basis_duals_lds_bytes(m) <= 160 * 1024 ? 1 : 0; }
+
+
+// Duals of `batch` LPs whose inputs are on the device: LPs whose run status is not LP_OPTIMAL keep it and get NaN.
+static int duals_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, double* y_out,
+                           double* d_out, double* w_out, int* status_out) {
+    const size_t B = (size_t)batch;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * B * ((size_t)m + n + 1) + sizeof(int) * B));
+    BasisDualsDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.basis = in.basis;
+    d.run_status = in.run_status;
+    d.y = reinterpret_cast<double*>(buf.ptr);
+    d.d = d.y + B * m;
+    d.w = d.d + B * n;
+    d.status = reinterpret_cast<int*>(d.w + B);
+    int rc;
+    if (lp_basis_duals_fits(m)) {
+        rc = lp_basis_duals_launch(ctx, d);
+    } else {
+        std::vector<char> done;
+        std::vector<int> basis;
+        rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
+            return lp_basis_duals_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n, in.basis + k * m,
+                                         d.y + k * m, d.d + k * n, d.w + k);
+        }, wrote_optimal, done, basis);
+    }
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "basis duals", {{y_out, d.y, sizeof(double) * B * m},
+                                              {d_out, d.d, sizeof(double) * B * n},
+                                              {w_out, d.w, sizeof(double) * B},
+                                              {status_out, d.status, sizeof(int) * B}});
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without duals: NaN (the per-LP path leaves their outputs unwritten)
+    for (size_t k = 0; k < B; ++k) {
+        if (status_out[k] == LP_OPTIMAL) continue;
+        for (int t = 0; t < m; ++t) y_out[k * m + t] = NAN;
+        for (int j = 0; j < n; ++j) d_out[k * n + j] = NAN;
+        w_out[k] = NAN;
+    }
+    return LP_OPTIMAL;
+}
+
+int lp_basis_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                   const int* basis, double* y_out, double* d_out, double* w_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: bad dimensions");
+    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    int rc = upload(ctx, "basis duals", buf, 1, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    if (rc == LP_OPTIMAL) rc = duals_on_device(ctx, 1, m, n, in, y_out, d_out, w_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                           const double* c, const int* basis, double* y_out, double* d_out, double* w_out,
+                           int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: bad dimensions");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = upload(ctx, "basis duals", buf, batch, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    return rc ? rc : duals_on_device(ctx, batch, m, n, in, y_out, d_out, w_out, status_out);
+}
+
+int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!y_out || !d_out || !w_out || !status_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: null argument");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = batch_inputs(p, "basis duals", buf, nullptr, 0, in);
+    return rc ? rc : duals_on_device(ctx, p->batch, p->m, p->n, in, y_out, d_out, w_out, status_out);
+}
+
+// ===========================================================================
+// RHS and cost ranging at a given basis (basis_ranging.hip)
+// ===========================================================================
+
+int lp_basis_ranging_fits(int m, int n) {
+    return m > 0 && n >= m && lp_basis_ranging_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
+}
+
+
+// NaN values and -1 indices for LP k
+static void ranging_nan(size_t k, int m, int n, double* rhs, int* rhs_var, double* cost, int* cost_var) {
+    for (size_t q = 0; q < 2 * (size_t)m; ++q) {
+        rhs[k * 2 * m + q] = NAN;
+        rhs_var[k * 2 * m + q] = -1;
+    }
+    for (size_t q = 0; q < 2 * (size_t)n; ++q) {
+        cost[k * 2 * n + q] = NAN;
+        cost_var[k * 2 * n + q] = -1;
+    }
+}
+
+// Ranges of `batch` LPs whose inputs are on the device: LPs whose run status is not LP_OPTIMAL keep it and get NaN.
+static int ranging_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
+                             double eps, double* rhs_out, int* rhs_var_out, double* cost_out, int* cost_var_out,
+                             int* status_out) {
+    const size_t B = (size_t)batch, nr = B * 2 * m, nc = B * 2 * n;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (nr + nc) + sizeof(int) * (nr + nc + B)));
+    BasisRangingDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.basis = in.basis;
+    d.run_status = in.run_status;
+    d.rhs = reinterpret_cast<double*>(buf.ptr);
+    d.cost = d.rhs + nr;
+    d.rhs_var = reinterpret_cast<int*>(d.cost + nc);
+    d.cost_var = d.rhs_var + nr;
+    d.status = d.cost_var + nc;
+    int rc;
+    if (lp_basis_ranging_fits(m, n)) {
+        rc = lp_basis_ranging_launch(ctx, d);
+    } else {
+        std::vector<char> done;
+        std::vector<int> basis;
+        rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
+            return lp_basis_ranging_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n, in.basis + k * m,
+                                           d.maximize, eps, d.rhs + k * 2 * m, d.rhs_var + k * 2 * m,
+                                           d.cost + k * 2 * n, d.cost_var + k * 2 * n);
+        }, wrote_optimal, done, basis);
+    }
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "basis ranging", {{rhs_out, d.rhs, sizeof(double) * nr},
+                                                {rhs_var_out, d.rhs_var, sizeof(int) * nr},
+                                                {cost_out, d.cost, sizeof(double) * nc},
+                                                {cost_var_out, d.cost_var, sizeof(int) * nc},
+                                                {status_out, d.status, sizeof(int) * B}});
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without ranges: NaN (the per-LP path leaves their outputs unwritten)
+    for (size_t k = 0; k < B; ++k)
+        if (status_out[k] != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
+    return LP_OPTIMAL;
+}
+
+int lp_basis_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                     const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                     double* cost_out, int* cost_var_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: bad dimensions");
+    ranging_nan(0, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: eps must be >= 0");
+    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    int rc = upload(ctx, "basis ranging", buf, 1, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    if (rc == LP_OPTIMAL)
+        rc = ranging_on_device(ctx, 1, m, n, in, maximize, eps, rhs_out, rhs_var_out, cost_out, cost_var_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                             const double* c, const int* basis, int maximize, double eps, double* rhs_out,
+                             int* rhs_var_out, double* cost_out, int* cost_var_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: eps must be >= 0");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = upload(ctx, "basis ranging", buf, batch, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    return rc ? rc
+              : ranging_on_device(ctx, batch, m, n, in, maximize, eps, rhs_out, rhs_var_out, cost_out, cost_var_out,
+                                  status_out);
+}
+
+int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* rhs_var_out, double* cost_out,
+                       int* cost_var_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: eps must be >= 0");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = batch_inputs(p, "basis ranging", buf, nullptr, 0, in);
+    return rc ? rc
+              : ranging_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, eps, rhs_out, rhs_var_out, cost_out,
+                                  cost_var_out, status_out);
+}
+
+// ===========================================================================
+// Farkas and unbounded-ray certificates at a given basis (basis_certificate.hip)
+// ===========================================================================
+
+int lp_basis_certificate_fits(int m, int n) {
+    return m > 0 && n > 0 && lp_basis_certificate_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
+}
+
+
+// NONE, NaN values and index -1 for LP k
+static void certificate_none(size_t k, int m, int n, int* kind, double* farkas, double* ray, double* value,
+                             int* index) {
+    kind[k] = LP_CERT_NONE;
+    for (size_t q = 0; q < (size_t)m; ++q) farkas[k * m + q] = NAN;
+    for (size_t q = 0; q < (size_t)n; ++q) ray[k * n + q] = NAN;
+    value[k] = NAN;
+    index[k] = -1;
+}
+
+// Certificates of `batch` LPs whose inputs are on the device: with run statuses, only LPs whose run status is
+// LP_INFEASIBLE / LP_UNBOUNDED get one, the others keep it and get NONE.
+static int certificate_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
+                                 double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out,
+                                 int* index_out, int* status_out) {
+    const size_t B = (size_t)batch, nf = B * m, nr = B * n;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (nf + nr + B) + sizeof(int) * 3 * B));
+    BasisCertificateDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.basis = in.basis;
+    d.run_status = in.run_status;
+    d.farkas = reinterpret_cast<double*>(buf.ptr);
+    d.ray = d.farkas + nf;
+    d.value = d.ray + nr;
+    d.kind = reinterpret_cast<int*>(d.value + B);
+    d.index = d.kind + B;
+    d.status = d.index + B;
+    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
+    int rc;
+    if (lp_basis_certificate_fits(m, n)) {
+        rc = lp_basis_certificate_launch(ctx, d);
+    } else {
+        std::vector<int> basis;
+        rc = per_lp(ctx, batch, m, n, in, d.status, run_failed, certificate_basis_check, [&](size_t k) {
+            return lp_basis_certificate_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n,
+                                               in.basis + k * m, d.maximize, eps, d.kind + k, d.farkas + k * m,
+                                               d.ray + k * n, d.value + k, d.index + k);
+        }, wrote_optimal, done, basis);
+    }
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "basis certificate", {{farkas_out, d.farkas, sizeof(double) * nf},
+                                                    {ray_out, d.ray, sizeof(double) * nr},
+                                                    {value_out, d.value, sizeof(double) * B},
+                                                    {kind_out, d.kind, sizeof(int) * B},
+                                                    {index_out, d.index, sizeof(int) * B},
+                                                    {status_out, d.status, sizeof(int) * B}});
+    if (rc != LP_OPTIMAL) return rc;
+    // LPs without a certificate on the per-LP path: NONE (their outputs were left unwritten)
+    for (size_t k = 0; k < B; ++k)
+        if (!done[k]) certificate_none(k, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    return LP_OPTIMAL;
+}
+
+int lp_basis_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                         const int* basis, int maximize, double eps, int* kind_out, double* farkas_out,
+                         double* ray_out, double* value_out, int* index_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: null argument");
+    if (m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: bad dimensions");
+    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: eps must be >= 0");
+    const int cs = certificate_basis_check(basis, m, n);
+    if (cs == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    if (cs == LP_SINGULAR) return LP_SINGULAR;
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    int rc = upload(ctx, "basis certificate", buf, 1, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    if (rc == LP_OPTIMAL)
+        rc = certificate_on_device(ctx, 1, m, n, in, maximize, eps, kind_out, farkas_out, ray_out, value_out,
+                                   index_out, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                 const double* c, const int* basis, int maximize, double eps, int* kind_out,
+                                 double* farkas_out, double* ray_out, double* value_out, int* index_out,
+                                 int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: null argument");
+    if (batch <= 0 || m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: eps must be >= 0");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = upload(ctx, "basis certificate", buf, batch, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    return rc ? rc
+              : certificate_on_device(ctx, batch, m, n, in, maximize, eps, kind_out, farkas_out, ray_out, value_out,
+                                      index_out, status_out);
+}
+
+int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, double* farkas_out, double* ray_out,
+                            double* value_out, int* index_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: eps must be >= 0");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    const int rc = batch_inputs(p, "basis certificate", buf, nullptr, 0, in);
+    return rc ? rc
+              : certificate_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, eps, kind_out, farkas_out, ray_out,
+                                      value_out, index_out, status_out);
+}
+
+// ===========================================================================
+// Parametric right-hand side and parametric cost from an optimal basis (basis_parametric.hip,
+// basis_parametric_cost.hip)
+// ===========================================================================
+
+int lp_basis_parametric_fits(int m, int n) {
+    return m > 0 && n >= m && lp_basis_parametric_lds_bytes(m, n, nullptr) <= 160 * 1024 ? 1 : 0;
+}
+
+int lp_basis_parametric_cost_fits(int m, int n) {
+    return m > 0 && n >= m && lp_basis_parametric_cost_lds_bytes(m, n, nullptr) <= 160 * 1024 ? 1 : 0;
+}
+
+
+// LP k without a path: nseg 0, NaN / -1, the given basis (host) back
+static void parametric_none(size_t k, int m, int mb, const int* basis, int* nseg, double* t, double* obj,
+                            double* slope, int* enter, int* leave, int* basis_out) {
+    nseg[k] = 0;
+    for (size_t q = 0; q < (size_t)mb + 2; ++q) {
+        t[k * (mb + 2) + q] = NAN;
+        obj[k * (mb + 2) + q] = NAN;
+    }
+    for (size_t q = 0; q < (size_t)mb + 1; ++q) {
+        slope[k * (mb + 1) + q] = NAN;
+        enter[k * (mb + 1) + q] = -1;
+        leave[k * (mb + 1) + q] = -1;
+    }
+    if (basis) std::memcpy(basis_out + k * m, basis, sizeof(int) * (size_t)m);
+}
+
+// After the per-LP path (basis: the given bases), which writes the path only: the rest is NaN / -1, and LPs without
+// one get it all.
+static void parametric_pad(size_t B, int m, int mb, const std::vector<char>& done, const std::vector<int>& basis,
+                           int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                           int* leave_out, int* basis_out) {
+    for (size_t k = 0; k < B; ++k) {
+        if (!done[k]) {
+            parametric_none(k, m, mb, basis.data() + k * m, nseg_out, t_out, obj_out, slope_out, enter_out,
+                            leave_out, basis_out);
+            continue;
+        }
+        const int ns_k = nseg_out[k];
+        for (int q = ns_k + 1; q < mb + 2; ++q) t_out[k * (mb + 2) + q] = obj_out[k * (mb + 2) + q] = NAN;
+        for (int q = ns_k; q < mb + 1; ++q) {
+            slope_out[k * (mb + 1) + q] = NAN;
+            enter_out[k * (mb + 1) + q] = leave_out[k * (mb + 1) + q] = -1;
+        }
+    }
+}
+
+// The argument checks shared by the entry points of both parametric analyses (LP_OPTIMAL when they pass)
+static int parametric_args(lp_context* ctx, const char* fn, double t_max, double eps, int max_breaks) {
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": max_breaks must be >= 0");
+    if (!(t_max >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": t_max must be >= 0");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": eps must be >= 0");
+    return LP_OPTIMAL;
+}
+
+// Paths of `batch` LPs whose inputs (d in in.extra) are on the device: LPs whose run status is not LP_OPTIMAL keep it
+// and get nseg 0.
+static int parametric_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
+                                double t_max, double eps, int mb, int* nseg_out, double* t_out, double* obj_out,
+                                double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
+    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B)));
+    BasisParametricDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_basis_parametric_lds_bytes(m, n, &d.pitch);
+    d.max_breaks = mb;
+    d.eps = eps;
+    d.t_max = t_max;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.dir = in.extra;
+    d.basis = in.basis;
+    d.run_status = in.run_status;
+    d.t = reinterpret_cast<double*>(buf.ptr);
+    d.obj = d.t + nt;
+    d.slope = d.obj + nt;
+    d.enter = reinterpret_cast<int*>(d.slope + ns);
+    d.leave = d.enter + ns;
+    d.basis_out = d.leave + ns;
+    d.nseg = d.basis_out + B * m;
+    d.status = d.nseg + B;
+    std::vector<char> done;
+    std::vector<int> basis;   // per-LP path: the given bases
+    int rc;
+    if (lp_basis_parametric_fits(m, n)) {
+        rc = lp_basis_parametric_launch(ctx, d, maximize);
+    } else {
+        rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
+            return lp_basis_parametric_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n,
+                                              in.basis + k * m, in.extra + k * m, maximize, t_max, eps, mb,
+                                              d.nseg + k, d.t + k * (mb + 2), d.obj + k * (mb + 2),
+                                              d.slope + k * (mb + 1), d.enter + k * (mb + 1), d.leave + k * (mb + 1),
+                                              d.basis_out + k * m);
+        }, [](int st) { return st == LP_OPTIMAL || st == LP_INFEASIBLE || st == LP_ITER_LIMIT; }, done, basis);
+    }
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "basis parametric", {{t_out, d.t, sizeof(double) * nt},
+                                                   {obj_out, d.obj, sizeof(double) * nt},
+                                                   {slope_out, d.slope, sizeof(double) * ns},
+                                                   {enter_out, d.enter, sizeof(int) * ns},
+                                                   {leave_out, d.leave, sizeof(int) * ns},
+                                                   {basis_out, d.basis_out, sizeof(int) * B * m},
+                                                   {nseg_out, d.nseg, sizeof(int) * B},
+                                                   {status_out, d.status, sizeof(int) * B}});
+    if (rc != LP_OPTIMAL) return rc;
+    if (!basis.empty())
+        parametric_pad(B, m, mb, done, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+    return LP_OPTIMAL;
+}
+
+// Cost paths of `batch` LPs whose inputs (g in in.extra) are on the device: LPs whose run status is not LP_OPTIMAL
+// keep it and get nseg 0.
+static int parametric_cost_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
+                                     double t_max, double eps, int mb, int* nseg_out, double* t_out, double* obj_out,
+                                     double* slope_out, int* enter_out, int* leave_out, int* basis_out,
+                                     int* status_out) {
+    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B)));
+    BasisParametricCostDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    (void)lp_basis_parametric_cost_lds_bytes(m, n, &d.pitch);
+    d.max_breaks = mb;
+    d.eps = eps;
+    d.t_max = t_max;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.g = in.extra;
+    d.basis = in.basis;
+    d.run_status = in.run_status;
+    d.t = reinterpret_cast<double*>(buf.ptr);
+    d.obj = d.t + nt;
+    d.slope = d.obj + nt;
+    d.enter = reinterpret_cast<int*>(d.slope + ns);
+    d.leave = d.enter + ns;
+    d.basis_out = d.leave + ns;
+    d.nseg = d.basis_out + B * m;
+    d.status = d.nseg + B;
+    std::vector<char> done;
+    std::vector<int> basis;   // per-LP path: the given bases
+    int rc;
+    if (lp_basis_parametric_cost_fits(m, n)) {
+        rc = lp_basis_parametric_cost_launch(ctx, d, maximize);
+    } else {
+        rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
+            return lp_basis_parametric_cost_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n,
+                                                   in.basis + k * m, in.extra + k * n, maximize, t_max, eps, mb,
+                                                   d.nseg + k, d.t + k * (mb + 2), d.obj + k * (mb + 2),
+                                                   d.slope + k * (mb + 1), d.enter + k * (mb + 1),
+                                                   d.leave + k * (mb + 1), d.basis_out + k * m);
+        }, [](int st) { return st == LP_OPTIMAL || st == LP_UNBOUNDED || st == LP_ITER_LIMIT; }, done, basis);
+    }
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "basis parametric cost", {{t_out, d.t, sizeof(double) * nt},
+                                                        {obj_out, d.obj, sizeof(double) * nt},
+                                                        {slope_out, d.slope, sizeof(double) * ns},
+                                                        {enter_out, d.enter, sizeof(int) * ns},
+                                                        {leave_out, d.leave, sizeof(int) * ns},
+                                                        {basis_out, d.basis_out, sizeof(int) * B * m},
+                                                        {nseg_out, d.nseg, sizeof(int) * B},
+                                                        {status_out, d.status, sizeof(int) * B}});
+    if (rc != LP_OPTIMAL) return rc;
+    if (!basis.empty())
+        parametric_pad(B, m, mb, done, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+    return LP_OPTIMAL;
+}
+
+int lp_basis_parametric(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                        const int* basis, int maximize, const double* d, double t_max, double eps, int max_breaks,
+                        int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                        int* leave_out, int* basis_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: bad dimensions");
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: max_breaks must be >= 0");
+    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+    int rc = parametric_args(ctx, "lp_basis_parametric", t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    rc = upload(ctx, "basis parametric", buf, 1, m, n, A, b, c, d, (size_t)m, basis, nullptr, in);
+    if (rc == LP_OPTIMAL)
+        rc = parametric_on_device(ctx, 1, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out, obj_out,
+                                  slope_out, enter_out, leave_out, basis_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: the basis is not optimal at t = 0");
+    return status;
+}
+
+int lp_basis_parametric_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                const double* c, const int* basis, int maximize, const double* d, double t_max,
+                                double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
+                                double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: bad dimensions");
+    int rc = parametric_args(ctx, "lp_basis_parametric_batched", t_max, eps, max_breaks);
+    if (rc) return rc;
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = upload(ctx, "basis parametric", buf, batch, m, n, A, b, c, d, (size_t)m, basis, nullptr, in);
+    return rc ? rc
+              : parametric_on_device(ctx, batch, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out,
+                                     obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+}
+
+int lp_batched_parametric(lp_batched_problem* p, const double* d, double t_max, double eps, int max_breaks,
+                          int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                          int* leave_out, int* basis_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: null argument");
+    int rc = parametric_args(ctx, "lp_batched_parametric", t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = batch_inputs(p, "basis parametric", buf, d, (size_t)p->m, in);
+    return rc ? rc
+              : parametric_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, t_max, eps, max_breaks, nseg_out,
+                                     t_out, obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+}
+
+int lp_basis_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                             const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks,
+                             int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                             int* leave_out, int* basis_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: bad dimensions");
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: max_breaks must be >= 0");
+    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+    int rc = parametric_args(ctx, "lp_basis_parametric_cost", t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    rc = upload(ctx, "basis parametric cost", buf, 1, m, n, A, b, c, g, (size_t)n, basis, nullptr, in);
+    if (rc == LP_OPTIMAL)
+        rc = parametric_cost_on_device(ctx, 1, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out, obj_out,
+                                       slope_out, enter_out, leave_out, basis_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: the basis is not optimal at t = 0");
+    return status;
+}
+
+int lp_basis_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                     const double* c, const int* basis, int maximize, const double* g, double t_max,
+                                     double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
+                                     double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
+        !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: bad dimensions");
+    int rc = parametric_args(ctx, "lp_basis_parametric_cost_batched", t_max, eps, max_breaks);
+    if (rc) return rc;
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = upload(ctx, "basis parametric cost", buf, batch, m, n, A, b, c, g, (size_t)n, basis, nullptr, in);
+    return rc ? rc
+              : parametric_cost_on_device(ctx, batch, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out,
+                                          obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+}
+
+int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_max, double eps, int max_breaks,
+                               int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                               int* leave_out, int* basis_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: null argument");
+    int rc = parametric_args(ctx, "lp_batched_parametric_cost", t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = batch_inputs(p, "basis parametric cost", buf, g, (size_t)p->n, in);
+    return rc ? rc
+              : parametric_cost_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, t_max, eps, max_breaks,
+                                          nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out,
+                                          status_out);
+}
+
+// ===========================================================================
+// Depth-first branch-and-bound (batched_mip.hip): one integer LP per workgroup for lp_mip_fits shapes only; there is
+// no per-LP path
+// ===========================================================================
+
+int lp_mip_fits(int m, int n, int max_depth) { return lp_mip_fits_shape(m, n, max_depth) ? 1 : 0; }
+
+
+// The search parameters and the mask (the basis and the problem arrays are checked by the callers).
+static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, const int* integer, double int_tol,
+                    double gap, int max_depth, int max_nodes) {
+    if (!integer) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (max_depth < 0 || max_depth > LP_MIP_MAX_DEPTH)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_depth must be in [0, 64]");
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": int_tol must be in [0, 0.5)");
+    if (!(gap >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": gap must be >= 0");
+    if (max_nodes < 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_nodes must be >= 1");
+    for (int j = 0; j < n; ++j) {
+        if (integer[j] != 0 && integer[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": mask entries must be 0 or 1");
+        if (integer[j] && j >= n_orig)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the mask marks a column beyond n_orig");
+    }
+    if (!lp_mip_fits_shape(m, n, max_depth))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_mip_fits)");
+    return LP_OPTIMAL;
+}
+
+// The search of `batch` problems whose A, b, c and root bases are on the device: problems whose run status is not
+// LP_OPTIMAL keep it.  The mask goes up.
+static int mip_on_device(lp_context* ctx, int batch, int m, int n, int n_orig, const BasisInputs& in,
+                         const int* integer, int maximize, double eps, double int_tol, double gap, int max_depth,
+                         int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out,
+                         int* found_out, int* stats_out, int* status_out) {
+    const size_t B = (size_t)batch;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (B * n_orig + 2 * B) + sizeof(int) * (B * 6 + n)));
+    BatchedMipDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.n_orig = n_orig;
+    d.maximize = maximize ? 1 : 0;
+    d.max_iter = max_iter;
+    d.max_depth = max_depth;
+    d.max_nodes = max_nodes;
+    d.eps = eps;
+    d.int_tol = int_tol;
+    d.gap = gap;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.basis_in = in.basis;
+    d.run_status = in.run_status;
+    d.x = reinterpret_cast<double*>(buf.ptr);
+    d.obj = d.x + B * n_orig;
+    d.bound = d.obj + B;
+    d.found = reinterpret_cast<int*>(d.bound + B);
+    d.stats = d.found + B;
+    d.status = d.stats + B * 4;
+    int* dmask = d.status + B;
+    d.integer = dmask;
+    hipError_t e = hipMemcpyAsync(dmask, integer, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched MIP upload: ") + hipGetErrorString(e));
+    const int rc = lp_batched_mip_launch(ctx, d);
+    if (rc) return rc;
+    e = hipGetLastError();
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched MIP: ") + hipGetErrorString(e));
+    return lp_download(ctx, "batched MIP", {{x_out, d.x, sizeof(double) * B * n_orig},
+                                            {obj_out, d.obj, sizeof(double) * B},
+                                            {bound_out, d.bound, sizeof(double) * B},
+                                            {found_out, d.found, sizeof(int) * B},
+                                            {stats_out, d.stats, sizeof(int) * B * 4},
+                                            {status_out, d.status, sizeof(int) * B}});
+}
+
+int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const int* basis,
+                 int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth,
+                 int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
+                 int* stats_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: null argument");
+    int rc = check_canonical(ctx, A, m, n, b, c, basis, n_orig);
+    if (rc) return rc;
+    rc = mip_args(ctx, "lp_mip_solve", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    lp_device_buffer buf;
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    rc = upload(ctx, "batched MIP", buf, 1, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    if (rc == LP_OPTIMAL)
+        rc = mip_on_device(ctx, 1, m, n, n_orig, in, integer, maximize, eps, int_tol, gap, max_depth, max_nodes,
+                           max_iter, x_out, obj_out, bound_out, found_out, stats_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: the basis is neither primal nor dual feasible");
+    return status;
+}
+
+int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                         const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol,
+                         double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
+                         double* bound_out, int* found_out, int* stats_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve_batched: null argument");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    for (int k = 0; k < batch; ++k) {
+        int rc = check_canonical(ctx, A ? A + (size_t)k * m * n : nullptr, m, n, b ? b + (size_t)k * m : nullptr,
+                                 c ? c + (size_t)k * n : nullptr, basis ? basis + (size_t)k * m : nullptr, n_orig);
+        if (rc) return rc;
+    }
+    int rc = mip_args(ctx, "lp_mip_solve_batched", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = upload(ctx, "batched MIP", buf, batch, m, n, A, b, c, nullptr, 0, basis, nullptr, in);
+    return rc ? rc
+              : mip_on_device(ctx, batch, m, n, n_orig, in, integer, maximize, eps, int_tol, gap, max_depth,
+                              max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, status_out);
+}
+
+int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double int_tol, double gap, int max_depth,
+                   int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
+                   int* stats_out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: null argument");
+    int rc = mip_args(ctx, "lp_batched_mip", p->m, p->n, p->n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: Dantzig's rule only");
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = batch_inputs(p, "batched MIP", buf, nullptr, 0, in);
+    return rc ? rc
+              : mip_on_device(ctx, p->batch, p->m, p->n, p->n_orig, in, integer, p->maximize, eps, int_tol, gap,
+                              max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out,
+                              status_out);
+}
+
+}  // extern "C"

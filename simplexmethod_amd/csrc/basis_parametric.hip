@@ -442,26 +442,21 @@ int lp_basis_parametric_device(lp_context* ctx, const double* dA, int m, int n, 
     sd.maximize = maximize ? 1 : 0;
     // one allocation: T, the pristine copy the crash permutes through, lcol, prow, state, basis, rowpos, rowused,
     // nonbasic, the run record
-    const size_t bytes = 2 * q.tableau_bytes + sizeof(double) * ((size_t)m + 1 + ld) + sizeof(SimplexState) +
-                         sizeof(int) * 2 * (size_t)m + (size_t)m + (size_t)n + 1 + sizeof(ParamRun) + 10 * 16;
-    char* arena = nullptr;
-    LP_HIP(ctx, hipMalloc(&arena, bytes));
-    char* cur = arena;
-    auto carve = [&](size_t n_bytes) {
-        char* r = cur;
-        cur += (n_bytes + 15) & ~(size_t)15;
-        return r;
+    ParamRun* run;
+    auto pieces = [&](lp_carver& cv) {
+        sd.T = cv.take<double>(q.tableau_bytes);
+        q.dT0 = cv.take<double>(q.tableau_bytes);
+        sd.lcol = cv.take<double>(sizeof(double) * ((size_t)m + 1));
+        sd.prow = cv.take<double>(sizeof(double) * (size_t)ld);
+        sd.state = cv.take<SimplexState>(sizeof(SimplexState));
+        sd.basis = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowpos = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowused = cv.take<unsigned char>((size_t)m);
+        sd.nonbasic = cv.take<unsigned char>((size_t)n + 1);
+        run = cv.take<ParamRun>(sizeof(ParamRun));
     };
-    sd.T = reinterpret_cast<double*>(carve(q.tableau_bytes));
-    q.dT0 = reinterpret_cast<double*>(carve(q.tableau_bytes));
-    sd.lcol = reinterpret_cast<double*>(carve(sizeof(double) * ((size_t)m + 1)));
-    sd.prow = reinterpret_cast<double*>(carve(sizeof(double) * (size_t)ld));
-    sd.state = reinterpret_cast<SimplexState*>(carve(sizeof(SimplexState)));
-    sd.basis = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowpos = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowused = reinterpret_cast<unsigned char*>(carve((size_t)m));
-    sd.nonbasic = reinterpret_cast<unsigned char*>(carve((size_t)n + 1));
-    ParamRun* run = reinterpret_cast<ParamRun*>(carve(sizeof(ParamRun)));
+    char* arena = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&arena, pieces));
     ParamOut o{dc, t_max, max_breaks, dnseg, dt, dobj, dslope, denter, dleave};
     SimplexState* hstate = nullptr;
     int rc = LP_OPTIMAL;

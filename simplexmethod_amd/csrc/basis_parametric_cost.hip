@@ -506,27 +506,21 @@ int lp_basis_parametric_cost_device(lp_context* ctx, const double* dA, int m, in
     sd.maximize = maximize ? 1 : 0;
     // one allocation: T (m+2 rows), the crash's permutation buffer (m+1 rows), lcol (m+2), prow, state, basis,
     // rowpos, rowused, nonbasic, the run record
-    const size_t bytes = row_bytes * (size_t)(2 * m + 3) + sizeof(double) * ((size_t)m + 2 + ld) +
-                         sizeof(SimplexState) + sizeof(int) * 2 * (size_t)m + (size_t)m + (size_t)n +
-                         sizeof(CostRun) + 10 * 16;
-    char* arena = nullptr;
-    LP_HIP(ctx, hipMalloc(&arena, bytes));
-    char* cur = arena;
-    auto carve = [&](size_t n_bytes) {
-        char* r = cur;
-        cur += (n_bytes + 15) & ~(size_t)15;
-        return r;
+    CostRun* run;
+    auto pieces = [&](lp_carver& cv) {
+        sd.T = cv.take<double>(row_bytes * (size_t)(m + 2));
+        q.dT0 = cv.take<double>(q.tableau_bytes);
+        sd.lcol = cv.take<double>(sizeof(double) * ((size_t)m + 2));
+        sd.prow = cv.take<double>(row_bytes);
+        sd.state = cv.take<SimplexState>(sizeof(SimplexState));
+        sd.basis = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowpos = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowused = cv.take<unsigned char>((size_t)m);
+        sd.nonbasic = cv.take<unsigned char>((size_t)n);
+        run = cv.take<CostRun>(sizeof(CostRun));
     };
-    sd.T = reinterpret_cast<double*>(carve(row_bytes * (size_t)(m + 2)));
-    q.dT0 = reinterpret_cast<double*>(carve(q.tableau_bytes));
-    sd.lcol = reinterpret_cast<double*>(carve(sizeof(double) * ((size_t)m + 2)));
-    sd.prow = reinterpret_cast<double*>(carve(row_bytes));
-    sd.state = reinterpret_cast<SimplexState*>(carve(sizeof(SimplexState)));
-    sd.basis = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowpos = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowused = reinterpret_cast<unsigned char*>(carve((size_t)m));
-    sd.nonbasic = reinterpret_cast<unsigned char*>(carve((size_t)n));
-    CostRun* run = reinterpret_cast<CostRun*>(carve(sizeof(CostRun)));
+    char* arena = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&arena, pieces));
     lp_simplex_problem qv;   // the update's view: rows 0..m+1 (m+1 "constraint" rows and the g row)
     qv.ctx = ctx;
     qv.dev = sd;

@@ -467,30 +467,25 @@ int lp_basis_ranging_device(lp_context* ctx, const double* dA, int m, int n, con
     sd.ld = ld;
     // one allocation: T, the pristine copy the crash permutes through, lcol, prow, state, basis, rowpos, rowused;
     // alpha, y, d, w and the basic flags
-    const size_t bytes = 2 * q.tableau_bytes + sizeof(double) * ((size_t)m + 1 + ld) + sizeof(SimplexState) +
-                         sizeof(int) * 2 * (size_t)m + (size_t)m + sizeof(double) * ((size_t)m * n + m + n + 1) +
-                         sizeof(int) * (size_t)n + 13 * 16;   // (+ the carve's alignment)
-    char* arena = nullptr;
-    LP_HIP(ctx, hipMalloc(&arena, bytes));
-    char* cur = arena;
-    auto carve = [&](size_t n_bytes) {
-        char* r = cur;
-        cur += (n_bytes + 15) & ~(size_t)15;
-        return r;
+    double *alpha, *dy, *dd, *dw;
+    int* basic;
+    auto pieces = [&](lp_carver& cv) {
+        sd.T = cv.take<double>(q.tableau_bytes);
+        q.dT0 = cv.take<double>(q.tableau_bytes);
+        sd.lcol = cv.take<double>(sizeof(double) * ((size_t)m + 1));
+        sd.prow = cv.take<double>(sizeof(double) * (size_t)ld);
+        sd.state = cv.take<SimplexState>(sizeof(SimplexState));
+        sd.basis = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowpos = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowused = cv.take<unsigned char>((size_t)m);
+        alpha = cv.take<double>(sizeof(double) * (size_t)m * n);
+        dy = cv.take<double>(sizeof(double) * (size_t)m);
+        dd = cv.take<double>(sizeof(double) * (size_t)n);
+        dw = cv.take<double>(sizeof(double));
+        basic = cv.take<int>(sizeof(int) * (size_t)n);
     };
-    sd.T = reinterpret_cast<double*>(carve(q.tableau_bytes));
-    q.dT0 = reinterpret_cast<double*>(carve(q.tableau_bytes));
-    sd.lcol = reinterpret_cast<double*>(carve(sizeof(double) * ((size_t)m + 1)));
-    sd.prow = reinterpret_cast<double*>(carve(sizeof(double) * (size_t)ld));
-    sd.state = reinterpret_cast<SimplexState*>(carve(sizeof(SimplexState)));
-    sd.basis = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowpos = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)m));
-    sd.rowused = reinterpret_cast<unsigned char*>(carve((size_t)m));
-    double* alpha = reinterpret_cast<double*>(carve(sizeof(double) * (size_t)m * n));
-    double* dy = reinterpret_cast<double*>(carve(sizeof(double) * (size_t)m));
-    double* dd = reinterpret_cast<double*>(carve(sizeof(double) * (size_t)n));
-    double* dw = reinterpret_cast<double*>(carve(sizeof(double)));
-    int* basic = reinterpret_cast<int*>(carve(sizeof(int) * (size_t)n));
+    char* arena = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&arena, pieces));
     int rc = LP_OPTIMAL;
     hipError_t e = hipMemsetAsync(basic, 0, sizeof(int) * (size_t)n, s);
     if (e != hipSuccess) rc = -(int)e;

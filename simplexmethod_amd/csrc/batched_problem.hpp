@@ -276,3 +276,34 @@ struct BatchedBoundedDev {
 size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
 bool lp_bounded_fits_shape(int m, int n);
 int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
+
+// A batch handle of the C ABI (capi.hip: upload, run, download); the analyses of basis_driver.hip read its inputs and
+// final bases after a run.
+struct lp_batched_problem {
+    lp_context* ctx = nullptr;
+    int batch = 0, m = 0, n = 0, n_orig = 0;
+    bool resident = false;              // true: LDS-resident kernel; false: per-LP fallback
+    BatchedDev dev{};
+    double *dA = nullptr, *db = nullptr, *dc = nullptr, *dx = nullptr;
+    int *dbasis_in = nullptr, *dbasis_out = nullptr, *diters = nullptr, *dstatus = nullptr;
+    std::vector<double> h_c;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<lp_simplex_problem*> lps;  // fallback
+    std::vector<int> status, iters;
+    // two-phase batch (lp_batched_two_phase_upload): no basis_in, three pivot counts per LP
+    bool two_phase = false;
+    int maximize = 0;
+    BatchedTwoPhaseDev tdev{};
+    std::vector<int> phase_iters;           // batch*3
+    std::vector<double> h_A, h_b;           // per-LP fallback: the inputs ...
+    std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
+    std::vector<int> h_basis;               // batch*m
+    int pivot_rule = LP_PIVOT_DANTZIG;      // lp_batched_set_pivot_rule: read by every run
+    // re-solve batch (lp_batched_resolve_upload): given bases, two pivot counts per LP; the per-LP fallback keeps
+    // h_A, h_b, h_basis_in and its outputs in h_x, h_obj, h_basis
+    bool resolve = false;
+    BatchedResolveDev rdev{};
+    std::vector<int> resolve_iters;         // batch*2: dual, primal
+    std::vector<int> h_basis_in;            // batch*m
+    bool ran = false;                       // a run completed: lp_batched_duals / _ranging / _certificates have final bases to read
+};

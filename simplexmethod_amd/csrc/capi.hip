@@ -1,6 +1,8 @@
 // capi.hip — the extern "C" boundary (include/simplexmethod_amd.h): the context, the status strings, the
-// division self-tests and the batched simplex.  The single-LP simplex is simplex_driver.hip, the
-// enumeration enum_driver.hip.
+// division self-tests, the batched simplex handle (plain, two-phase and re-solve batches) and the bounded-variable
+// simplex.  The single-LP simplex is simplex_driver.hip, the enumeration enum_driver.hip, and every analysis that
+// starts from an LP and a basis (duals, ranging, certificates, parametric RHS and cost, branch-and-bound)
+// basis_driver.hip.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -139,35 +141,6 @@ int lp_debug_division(lp_context* ctx, const double* num, const double* den, int
 // go through lp_simplex_two_phase one LP after another.  A batch uploaded by lp_batched_resolve_upload is
 // re-solved from its given bases (batched_resolve.hip).
 // ===========================================================================
-
-struct lp_batched_problem {
-    lp_context* ctx = nullptr;
-    int batch = 0, m = 0, n = 0, n_orig = 0;
-    bool resident = false;              // true: LDS-resident kernel; false: per-LP fallback
-    BatchedDev dev{};
-    double *dA = nullptr, *db = nullptr, *dc = nullptr, *dx = nullptr;
-    int *dbasis_in = nullptr, *dbasis_out = nullptr, *diters = nullptr, *dstatus = nullptr;
-    std::vector<double> h_c;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<lp_simplex_problem*> lps;  // fallback
-    std::vector<int> status, iters;
-    // two-phase batch (lp_batched_two_phase_upload): no basis_in, three pivot counts per LP
-    bool two_phase = false;
-    int maximize = 0;
-    BatchedTwoPhaseDev tdev{};
-    std::vector<int> phase_iters;           // batch*3
-    std::vector<double> h_A, h_b;           // per-LP fallback: the inputs ...
-    std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
-    std::vector<int> h_basis;               // batch*m
-    int pivot_rule = LP_PIVOT_DANTZIG;      // lp_batched_set_pivot_rule: read by every run
-    // re-solve batch (lp_batched_resolve_upload): given bases, two pivot counts per LP; the per-LP fallback keeps
-    // h_A, h_b, h_basis_in and its outputs in h_x, h_obj, h_basis
-    bool resolve = false;
-    BatchedResolveDev rdev{};
-    std::vector<int> resolve_iters;         // batch*2: dual, primal
-    std::vector<int> h_basis_in;            // batch*m
-    bool ran = false;                       // a run completed: lp_batched_duals / _ranging / _certificates have final bases to read
-};
 
 void lp_batched_free(lp_batched_problem* p) {
     if (!p) return;
@@ -837,1277 +810,6 @@ int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int
 }
 
 // ===========================================================================
-// the dual solution at a given basis (basis_duals.hip): one LP per workgroup for lp_basis_duals_fits(m), the
-// single-LP launch pair one LP after another beyond it
-// ===========================================================================
-
-int lp_basis_duals_fits(int m) { return m > 0 && lp_basis_duals_lds_bytes(m) <= 160 * 1024 ? 1 : 0; }
-
-// Duals of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): LPs whose run status is
-// not LP_OPTIMAL keep it and get NaN.  Outputs to the host.
-static int duals_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
-                           const double* dc, const int* dbasis, const int* drun_status, double* y_out, double* d_out,
-                           double* w_out, int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch;
-    const size_t bytes = sizeof(double) * B * ((size_t)m + n + 1) + sizeof(int) * B;
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BasisDualsDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.basis = dbasis;
-    d.run_status = drun_status;
-    d.y = reinterpret_cast<double*>(buf);
-    d.d = d.y + B * m;
-    d.w = d.d + B * n;
-    d.status = reinterpret_cast<int*>(d.w + B);
-    int rc = LP_OPTIMAL;
-    if (lp_basis_duals_fits(m)) {
-        rc = lp_basis_duals_launch(ctx, d);
-    } else {   // one LP after another: statuses and bases checked on the host
-        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
-        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && drun_status)
-            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            LP_HIP(ctx, e);
-        }
-        for (size_t k = 0; k < B && rc >= 0; ++k) {
-            if (st[k] == LP_OPTIMAL)
-                for (int t = 0; t < m; ++t)
-                    if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
-            if (st[k] != LP_OPTIMAL) continue;
-            rc = lp_basis_duals_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
-                                       d.y + k * m, d.d + k * n, d.w + k);
-            if (rc >= 0) st[k] = rc;
-        }
-        if (rc >= 0) {
-            rc = LP_OPTIMAL;
-            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = -(int)e;
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        hipError_t e = hipMemcpyAsync(y_out, d.y, sizeof(double) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_out, d.d, sizeof(double) * B * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(w_out, d.w, sizeof(double) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("basis duals: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    }
-    (void)hipFree(buf);
-    if (rc != LP_OPTIMAL) return rc;
-    // LPs without duals: NaN (the per-LP path leaves their outputs unwritten)
-    for (size_t k = 0; k < B; ++k) {
-        if (status_out[k] == LP_OPTIMAL) continue;
-        for (int t = 0; t < m; ++t) y_out[k * m + t] = NAN;
-        for (int j = 0; j < n; ++j) d_out[k * n + j] = NAN;
-        w_out[k] = NAN;
-    }
-    return LP_OPTIMAL;
-}
-
-// Uploads `batch` LPs, then duals_on_device.
-static int duals_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
-                        const int* basis, double* y_out, double* d_out, double* w_out, int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    int* dbasis = reinterpret_cast<int*>(dc + B * n);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("basis duals upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = duals_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, y_out, d_out, w_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-int lp_basis_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                   const int* basis, double* y_out, double* d_out, double* w_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals: bad dimensions");
-    for (int t = 0; t < m; ++t)
-        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    int status = LP_OPTIMAL;
-    const int rc = duals_upload(ctx, 1, A, m, n, b, c, basis, y_out, d_out, w_out, &status);
-    return rc ? rc : status;
-}
-
-int lp_basis_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                           const double* c, const int* basis, double* y_out, double* d_out, double* w_out,
-                           int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !y_out || !d_out || !w_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_duals_batched: bad dimensions");
-    return duals_upload(ctx, batch, A, m, n, b, c, basis, y_out, d_out, w_out, status_out);
-}
-
-int lp_batched_duals(lp_batched_problem* p, double* y_out, double* d_out, double* w_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!y_out || !d_out || !w_out || !status_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: null argument");
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_duals: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n;
-    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
-        return duals_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, y_out, d_out,
-                               w_out, status_out);
-    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
-    std::vector<int> basis((size_t)m);
-    for (size_t k = 0; k < (size_t)p->batch; ++k) {
-        double* y = y_out + k * m;
-        double* d = d_out + k * n;
-        int st = p->status[k];
-        if (st == LP_OPTIMAL) {
-            if (p->two_phase || p->resolve) {
-                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
-            } else {
-                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
-                if (rc) return rc;
-            }
-            st = lp_basis_duals(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m, p->h_c.data() + k * n,
-                                basis.data(), y, d, w_out + k);
-            if (st < 0) return st;
-        }
-        status_out[k] = st;
-        if (st != LP_OPTIMAL) {
-            for (int t = 0; t < m; ++t) y[t] = NAN;
-            for (int j = 0; j < n; ++j) d[j] = NAN;
-            w_out[k] = NAN;
-        }
-    }
-    ctx->last_error.clear();
-    return LP_OPTIMAL;
-}
-
-// ===========================================================================
-// RHS and cost ranging at a given basis (basis_ranging.hip): one LP per workgroup for lp_basis_ranging_fits(m, n),
-// the single-LP path one LP after another beyond it
-// ===========================================================================
-
-int lp_basis_ranging_fits(int m, int n) {
-    return m > 0 && n >= m && lp_basis_ranging_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
-}
-
-// NaN values and -1 indices for LP k
-static void ranging_nan(size_t k, int m, int n, double* rhs, int* rhs_var, double* cost, int* cost_var) {
-    for (size_t q = 0; q < 2 * (size_t)m; ++q) {
-        rhs[k * 2 * m + q] = NAN;
-        rhs_var[k * 2 * m + q] = -1;
-    }
-    for (size_t q = 0; q < 2 * (size_t)n; ++q) {
-        cost[k * 2 * n + q] = NAN;
-        cost_var[k * 2 * n + q] = -1;
-    }
-}
-
-// Ranges of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): LPs whose run status is
-// not LP_OPTIMAL keep it and get NaN.  Outputs to the host.
-static int ranging_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
-                             const double* dc, const int* dbasis, const int* drun_status, int maximize, double eps,
-                             double* rhs_out, int* rhs_var_out, double* cost_out, int* cost_var_out,
-                             int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch, nr = B * 2 * m, nc = B * 2 * n;
-    const size_t bytes = sizeof(double) * (nr + nc) + sizeof(int) * (nr + nc + B);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BasisRangingDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    d.maximize = maximize ? 1 : 0;
-    d.eps = eps;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.basis = dbasis;
-    d.run_status = drun_status;
-    d.rhs = reinterpret_cast<double*>(buf);
-    d.cost = d.rhs + nr;
-    d.rhs_var = reinterpret_cast<int*>(d.cost + nc);
-    d.cost_var = d.rhs_var + nr;
-    d.status = d.cost_var + nc;
-    int rc = LP_OPTIMAL;
-    if (lp_basis_ranging_fits(m, n)) {
-        rc = lp_basis_ranging_launch(ctx, d);
-    } else {   // one LP after another: statuses and bases checked on the host
-        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
-        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && drun_status)
-            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            LP_HIP(ctx, e);
-        }
-        for (size_t k = 0; k < B && rc >= 0; ++k) {
-            if (st[k] == LP_OPTIMAL)
-                for (int t = 0; t < m; ++t)
-                    if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
-            if (st[k] != LP_OPTIMAL) continue;
-            rc = lp_basis_ranging_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
-                                         d.maximize, eps, d.rhs + k * 2 * m, d.rhs_var + k * 2 * m,
-                                         d.cost + k * 2 * n, d.cost_var + k * 2 * n);
-            if (rc >= 0) st[k] = rc;
-        }
-        if (rc >= 0) {
-            rc = LP_OPTIMAL;
-            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = -(int)e;
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        hipError_t e = hipMemcpyAsync(rhs_out, d.rhs, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(rhs_var_out, d.rhs_var, sizeof(int) * nr, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d.cost, sizeof(double) * nc, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(cost_var_out, d.cost_var, sizeof(int) * nc, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("basis ranging: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    }
-    (void)hipFree(buf);
-    if (rc != LP_OPTIMAL) return rc;
-    // LPs without ranges: NaN (the per-LP path leaves their outputs unwritten)
-    for (size_t k = 0; k < B; ++k)
-        if (status_out[k] != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
-    return LP_OPTIMAL;
-}
-
-// Uploads `batch` LPs, then ranging_on_device.
-static int ranging_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
-                          const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
-                          double* cost_out, int* cost_var_out, int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    int* dbasis = reinterpret_cast<int*>(dc + B * n);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("basis ranging upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = ranging_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, maximize, eps, rhs_out, rhs_var_out,
-                               cost_out, cost_var_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-int lp_basis_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                     const int* basis, int maximize, double eps, double* rhs_out, int* rhs_var_out,
-                     double* cost_out, int* cost_var_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: bad dimensions");
-    ranging_nan(0, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging: eps must be >= 0");
-    for (int t = 0; t < m; ++t)
-        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    int status = LP_OPTIMAL;
-    const int rc = ranging_upload(ctx, 1, A, m, n, b, c, basis, maximize, eps, rhs_out, rhs_var_out, cost_out,
-                                  cost_var_out, &status);
-    return rc ? rc : status;
-}
-
-int lp_basis_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                             const double* c, const int* basis, int maximize, double eps, double* rhs_out,
-                             int* rhs_var_out, double* cost_out, int* cost_var_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: bad dimensions");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_ranging_batched: eps must be >= 0");
-    return ranging_upload(ctx, batch, A, m, n, b, c, basis, maximize, eps, rhs_out, rhs_var_out, cost_out,
-                          cost_var_out, status_out);
-}
-
-int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* rhs_var_out, double* cost_out,
-                       int* cost_var_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!rhs_out || !rhs_var_out || !cost_out || !cost_var_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: eps must be >= 0");
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_ranging: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n;
-    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
-        return ranging_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, p->maximize,
-                                 eps, rhs_out, rhs_var_out, cost_out, cost_var_out, status_out);
-    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
-    std::vector<int> basis((size_t)m);
-    for (size_t k = 0; k < (size_t)p->batch; ++k) {
-        int st = p->status[k];
-        if (st == LP_OPTIMAL) {
-            if (p->two_phase || p->resolve) {
-                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
-            } else {
-                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
-                if (rc) return rc;
-            }
-            st = lp_basis_ranging(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m, p->h_c.data() + k * n,
-                                  basis.data(), p->maximize, eps, rhs_out + k * 2 * m, rhs_var_out + k * 2 * m,
-                                  cost_out + k * 2 * n, cost_var_out + k * 2 * n);
-            if (st < 0) return st;
-        }
-        status_out[k] = st;
-        if (st != LP_OPTIMAL) ranging_nan(k, m, n, rhs_out, rhs_var_out, cost_out, cost_var_out);
-    }
-    ctx->last_error.clear();
-    return LP_OPTIMAL;
-}
-
-// ===========================================================================
-// Farkas and unbounded-ray certificates at a given basis (basis_certificate.hip): one LP per workgroup for
-// lp_basis_certificate_fits(m, n), the single-LP path one LP after another beyond it
-// ===========================================================================
-
-int lp_basis_certificate_fits(int m, int n) {
-    return m > 0 && n > 0 && lp_basis_certificate_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
-}
-
-// NONE, NaN values and index -1 for LP k
-static void certificate_none(size_t k, int m, int n, int* kind, double* farkas, double* ray, double* value,
-                             int* index) {
-    kind[k] = LP_CERT_NONE;
-    for (size_t q = 0; q < (size_t)m; ++q) farkas[k * m + q] = NAN;
-    for (size_t q = 0; q < (size_t)n; ++q) ray[k * n + q] = NAN;
-    value[k] = NAN;
-    index[k] = -1;
-}
-
-// The basis check of one LP on the host: LP_BAD_ARG (an index outside [0, n+m)), LP_SINGULAR (a repeat), else
-// LP_OPTIMAL.
-static int certificate_basis_check(const int* basis, int m, int n) {
-    for (int t = 0; t < m; ++t)
-        if (basis[t] < 0 || basis[t] >= n + m) return LP_BAD_ARG;
-    std::vector<char> seen((size_t)n + m, 0);
-    for (int t = 0; t < m; ++t) {
-        if (seen[(size_t)basis[t]]) return LP_SINGULAR;
-        seen[(size_t)basis[t]] = 1;
-    }
-    return LP_OPTIMAL;
-}
-
-// Certificates of `batch` LPs whose inputs are on the device; drun_status (device, or nullptr): only LPs whose run
-// status is LP_INFEASIBLE / LP_UNBOUNDED get one, the others keep it and get NONE.  Outputs to the host.
-static int certificate_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
-                                 const double* dc, const int* dbasis, const int* drun_status, int maximize,
-                                 double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out,
-                                 int* index_out, int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch, nf = B * m, nr = B * n;
-    const size_t bytes = sizeof(double) * (nf + nr + B) + sizeof(int) * 3 * B;
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BasisCertificateDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    d.maximize = maximize ? 1 : 0;
-    d.eps = eps;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.basis = dbasis;
-    d.run_status = drun_status;
-    d.farkas = reinterpret_cast<double*>(buf);
-    d.ray = d.farkas + nf;
-    d.value = d.ray + nr;
-    d.kind = reinterpret_cast<int*>(d.value + B);
-    d.index = d.kind + B;
-    d.status = d.index + B;
-    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
-    int rc = LP_OPTIMAL;
-    if (lp_basis_certificate_fits(m, n)) {
-        rc = lp_basis_certificate_launch(ctx, d);
-    } else {   // one LP after another: statuses and bases checked on the host
-        std::vector<int> st(B, LP_OPTIMAL), basis(B * m);
-        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && drun_status)
-            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            LP_HIP(ctx, e);
-        }
-        for (size_t k = 0; k < B && rc >= 0; ++k) {
-            done[k] = 0;
-            if (drun_status && st[k] != LP_INFEASIBLE && st[k] != LP_UNBOUNDED) continue;
-            int cs = certificate_basis_check(basis.data() + k * m, m, n);
-            if (cs == LP_OPTIMAL) {
-                rc = lp_basis_certificate_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
-                                                 d.maximize, eps, d.kind + k, d.farkas + k * m, d.ray + k * n,
-                                                 d.value + k, d.index + k);
-                if (rc < 0) break;
-                cs = rc;
-                done[k] = cs == LP_OPTIMAL;
-            }
-            if (cs != LP_OPTIMAL) st[k] = cs;
-        }
-        if (rc >= 0) {
-            rc = LP_OPTIMAL;
-            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = -(int)e;
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        hipError_t e = hipMemcpyAsync(farkas_out, d.farkas, sizeof(double) * nf, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(ray_out, d.ray, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(value_out, d.value, sizeof(double) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(kind_out, d.kind, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(index_out, d.index, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("basis certificate: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    }
-    (void)hipFree(buf);
-    if (rc != LP_OPTIMAL) return rc;
-    // LPs without a certificate on the per-LP path: NONE (their outputs were left unwritten)
-    for (size_t k = 0; k < B; ++k)
-        if (!done[k]) certificate_none(k, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
-    return LP_OPTIMAL;
-}
-
-// Uploads `batch` LPs, then certificate_on_device.
-static int certificate_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                              const double* c, const int* basis, int maximize, double eps, int* kind_out,
-                              double* farkas_out, double* ray_out, double* value_out, int* index_out,
-                              int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    int* dbasis = reinterpret_cast<int*>(dc + B * n);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("basis certificate upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = certificate_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, maximize, eps, kind_out,
-                                   farkas_out, ray_out, value_out, index_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-int lp_basis_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                         const int* basis, int maximize, double eps, int* kind_out, double* farkas_out,
-                         double* ray_out, double* value_out, int* index_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: null argument");
-    if (m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: bad dimensions");
-    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate: eps must be >= 0");
-    const int cs = certificate_basis_check(basis, m, n);
-    if (cs == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    if (cs == LP_SINGULAR) return LP_SINGULAR;
-    int status = LP_OPTIMAL;
-    const int rc = certificate_upload(ctx, 1, A, m, n, b, c, basis, maximize, eps, kind_out, farkas_out, ray_out,
-                                      value_out, index_out, &status);
-    return rc ? rc : status;
-}
-
-int lp_basis_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                                 const double* c, const int* basis, int maximize, double eps, int* kind_out,
-                                 double* farkas_out, double* ray_out, double* value_out, int* index_out,
-                                 int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: null argument");
-    if (batch <= 0 || m <= 0 || n <= 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: bad dimensions");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_certificate_batched: eps must be >= 0");
-    return certificate_upload(ctx, batch, A, m, n, b, c, basis, maximize, eps, kind_out, farkas_out, ray_out,
-                              value_out, index_out, status_out);
-}
-
-int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, double* farkas_out, double* ray_out,
-                            double* value_out, int* index_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!kind_out || !farkas_out || !ray_out || !value_out || !index_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: eps must be >= 0");
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_certificates: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n;
-    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
-        return certificate_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus,
-                                     p->maximize, eps, kind_out, farkas_out, ray_out, value_out, index_out,
-                                     status_out);
-    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
-    std::vector<int> basis((size_t)m);
-    for (size_t k = 0; k < (size_t)p->batch; ++k) {
-        int st = p->status[k];
-        certificate_none(k, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
-        if (st == LP_INFEASIBLE || st == LP_UNBOUNDED) {
-            if (p->two_phase || p->resolve) {
-                std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
-            } else {
-                const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
-                if (rc) return rc;
-            }
-            const int cs = lp_basis_certificate(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m,
-                                                p->h_c.data() + k * n, basis.data(), p->maximize, eps, kind_out + k,
-                                                farkas_out + k * m, ray_out + k * n, value_out + k, index_out + k);
-            if (cs < 0) return cs;
-            if (cs != LP_OPTIMAL) st = cs;
-        }
-        status_out[k] = st;
-    }
-    ctx->last_error.clear();
-    return LP_OPTIMAL;
-}
-
-// ===========================================================================
-// Parametric right-hand side from an optimal basis (basis_parametric.hip): one LP per workgroup for
-// lp_basis_parametric_fits(m, n), the single-LP launch path one LP after another beyond it
-// ===========================================================================
-
-int lp_basis_parametric_fits(int m, int n) {
-    return m > 0 && n >= m && lp_basis_parametric_lds_bytes(m, n, nullptr) <= 160 * 1024 ? 1 : 0;
-}
-
-// LP k without a path: nseg 0, NaN / -1, the given basis (host) back
-static void parametric_none(size_t k, int m, int mb, const int* basis, int* nseg, double* t, double* obj,
-                            double* slope, int* enter, int* leave, int* basis_out) {
-    nseg[k] = 0;
-    for (size_t q = 0; q < (size_t)mb + 2; ++q) {
-        t[k * (mb + 2) + q] = NAN;
-        obj[k * (mb + 2) + q] = NAN;
-    }
-    for (size_t q = 0; q < (size_t)mb + 1; ++q) {
-        slope[k * (mb + 1) + q] = NAN;
-        enter[k * (mb + 1) + q] = -1;
-        leave[k * (mb + 1) + q] = -1;
-    }
-    if (basis) std::memcpy(basis_out + k * m, basis, sizeof(int) * (size_t)m);
-}
-
-// Paths of `batch` LPs whose inputs (d included) are on the device; drun_status (device, or nullptr): LPs whose run
-// status is not LP_OPTIMAL keep it and get nseg 0.  Outputs to the host.
-static int parametric_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
-                                const double* dc, const int* dbasis, const int* drun_status, const double* ddir,
-                                int maximize, double t_max, double eps, int mb, int* nseg_out, double* t_out,
-                                double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out,
-                                int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
-    const size_t bytes = sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BasisParametricDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    (void)lp_basis_parametric_lds_bytes(m, n, &d.pitch);
-    d.max_breaks = mb;
-    d.eps = eps;
-    d.t_max = t_max;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.dir = ddir;
-    d.basis = dbasis;
-    d.run_status = drun_status;
-    d.t = reinterpret_cast<double*>(buf);
-    d.obj = d.t + nt;
-    d.slope = d.obj + nt;
-    d.enter = reinterpret_cast<int*>(d.slope + ns);
-    d.leave = d.enter + ns;
-    d.basis_out = d.leave + ns;
-    d.nseg = d.basis_out + B * m;
-    d.status = d.nseg + B;
-    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
-    std::vector<int> basis;         // per-LP path: the given bases
-    int rc = LP_OPTIMAL;
-    if (lp_basis_parametric_fits(m, n)) {
-        rc = lp_basis_parametric_launch(ctx, d, maximize);
-    } else {   // one LP after another: statuses and bases checked on the host
-        std::vector<int> st(B, LP_OPTIMAL);
-        basis.resize(B * m);
-        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && drun_status)
-            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            LP_HIP(ctx, e);
-        }
-        for (size_t k = 0; k < B && rc >= 0; ++k) {
-            done[k] = 0;
-            if (st[k] != LP_OPTIMAL) continue;
-            for (int t = 0; t < m; ++t)
-                if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
-            if (st[k] != LP_OPTIMAL) continue;
-            rc = lp_basis_parametric_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
-                                            ddir + k * m, maximize, t_max, eps, mb, d.nseg + k, d.t + k * (mb + 2),
-                                            d.obj + k * (mb + 2), d.slope + k * (mb + 1), d.enter + k * (mb + 1),
-                                            d.leave + k * (mb + 1), d.basis_out + k * m);
-            if (rc < 0) break;
-            st[k] = rc;
-            done[k] = rc == LP_OPTIMAL || rc == LP_INFEASIBLE || rc == LP_ITER_LIMIT;
-        }
-        if (rc >= 0) {
-            rc = LP_OPTIMAL;
-            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = -(int)e;
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        hipError_t e = hipMemcpyAsync(t_out, d.t, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(obj_out, d.obj, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(slope_out, d.slope, sizeof(double) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(enter_out, d.enter, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(leave_out, d.leave, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(basis_out, d.basis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(nseg_out, d.nseg, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("basis parametric: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    }
-    (void)hipFree(buf);
-    if (rc != LP_OPTIMAL) return rc;
-    if (!basis.empty())   // the per-LP path writes the path only: the rest is NaN / -1, and LPs without one get it all
-        for (size_t k = 0; k < B; ++k) {
-            if (!done[k]) {
-                parametric_none(k, m, mb, basis.data() + k * m, nseg_out, t_out, obj_out, slope_out, enter_out,
-                                leave_out, basis_out);
-                continue;
-            }
-            const int ns_k = nseg_out[k];
-            for (int q = ns_k + 1; q < mb + 2; ++q) t_out[k * (mb + 2) + q] = obj_out[k * (mb + 2) + q] = NAN;
-            for (int q = ns_k; q < mb + 1; ++q) {
-                slope_out[k * (mb + 1) + q] = NAN;
-                enter_out[k * (mb + 1) + q] = leave_out[k * (mb + 1) + q] = -1;
-            }
-        }
-    return LP_OPTIMAL;
-}
-
-// Uploads `batch` LPs and their directions, then parametric_on_device.
-static int parametric_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                             const double* c, const int* basis, int maximize, const double* dir, double t_max,
-                             double eps, int mb, int* nseg_out, double* t_out, double* obj_out, double* slope_out,
-                             int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + 2 * m + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    double* ddir = dc + B * n;
-    int* dbasis = reinterpret_cast<int*>(ddir + B * m);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ddir, dir, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("basis parametric upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = parametric_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, ddir, maximize, t_max, eps, mb,
-                                  nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-// The argument checks shared by the three entry points (LP_OPTIMAL when they pass)
-static int parametric_args(lp_context* ctx, const char* fn, double t_max, double eps, int max_breaks) {
-    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": max_breaks must be >= 0");
-    if (!(t_max >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": t_max must be >= 0");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(fn) + ": eps must be >= 0");
-    return LP_OPTIMAL;
-}
-
-int lp_basis_parametric(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                        const int* basis, int maximize, const double* d, double t_max, double eps, int max_breaks,
-                        int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
-                        int* leave_out, int* basis_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: bad dimensions");
-    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: max_breaks must be >= 0");
-    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-    int rc = parametric_args(ctx, "lp_basis_parametric", t_max, eps, max_breaks);
-    if (rc) return rc;
-    for (int t = 0; t < m; ++t)
-        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    int status = LP_OPTIMAL;
-    rc = parametric_upload(ctx, 1, A, m, n, b, c, basis, maximize, d, t_max, eps, max_breaks, nseg_out, t_out,
-                           obj_out, slope_out, enter_out, leave_out, basis_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: the basis is not optimal at t = 0");
-    return status;
-}
-
-int lp_basis_parametric_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                                const double* c, const int* basis, int maximize, const double* d, double t_max,
-                                double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
-                                double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: bad dimensions");
-    const int rc = parametric_args(ctx, "lp_basis_parametric_batched", t_max, eps, max_breaks);
-    if (rc) return rc;
-    return parametric_upload(ctx, batch, A, m, n, b, c, basis, maximize, d, t_max, eps, max_breaks, nseg_out, t_out,
-                             obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
-}
-
-int lp_batched_parametric(lp_batched_problem* p, const double* d, double t_max, double eps, int max_breaks,
-                          int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
-                          int* leave_out, int* basis_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: null argument");
-    int rc = parametric_args(ctx, "lp_batched_parametric", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n, mb = max_breaks;
-    const size_t B = (size_t)p->batch;
-    if (p->resident) {   // A, b, c, the final bases and the run statuses where the run left them; d goes up
-        double* ddir = nullptr;
-        LP_HIP(ctx, hipMalloc(&ddir, sizeof(double) * B * m));
-        hipError_t e = hipMemcpyAsync(ddir, d, sizeof(double) * B * m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(ddir);
-            LP_HIP(ctx, e);
-        }
-        rc = parametric_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, ddir,
-                                  p->maximize, t_max, eps, mb, nseg_out, t_out, obj_out, slope_out, enter_out,
-                                  leave_out, basis_out, status_out);
-        (void)hipFree(ddir);
-        return rc;
-    }
-    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
-    std::vector<int> basis((size_t)m);
-    for (size_t k = 0; k < B; ++k) {
-        if (p->two_phase || p->resolve) {
-            std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
-        } else {
-            rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-        int st = p->status[k];
-        parametric_none(k, m, mb, basis.data(), nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-        if (st == LP_OPTIMAL) {
-            st = lp_basis_parametric(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m,
-                                     p->h_c.data() + k * n, basis.data(), p->maximize, d + k * m, t_max, eps, mb,
-                                     nseg_out + k, t_out + k * (mb + 2), obj_out + k * (mb + 2),
-                                     slope_out + k * (mb + 1), enter_out + k * (mb + 1), leave_out + k * (mb + 1),
-                                     basis_out + k * m);
-            if (st < 0) return st;
-        }
-        status_out[k] = st;
-    }
-    ctx->last_error.clear();
-    return LP_OPTIMAL;
-}
-
-// ===========================================================================
-// Parametric cost from an optimal basis (basis_parametric_cost.hip): one LP per workgroup for
-// lp_basis_parametric_cost_fits(m, n), the single-LP launch path one LP after another beyond it
-// ===========================================================================
-
-int lp_basis_parametric_cost_fits(int m, int n) {
-    return m > 0 && n >= m && lp_basis_parametric_cost_lds_bytes(m, n, nullptr) <= 160 * 1024 ? 1 : 0;
-}
-
-// Cost paths of `batch` LPs whose inputs (g included) are on the device; drun_status (device, or nullptr): LPs whose run
-// status is not LP_OPTIMAL keep it and get nseg 0.  Outputs to the host.
-static int parametric_cost_on_device(lp_context* ctx, int batch, int m, int n, const double* dA, const double* db,
-                                     const double* dc, const int* dbasis, const int* drun_status, const double* dg,
-                                     int maximize, double t_max, double eps, int mb, int* nseg_out, double* t_out,
-                                     double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* basis_out,
-                                     int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
-    const size_t bytes = sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BasisParametricCostDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    (void)lp_basis_parametric_cost_lds_bytes(m, n, &d.pitch);
-    d.max_breaks = mb;
-    d.eps = eps;
-    d.t_max = t_max;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.g = dg;
-    d.basis = dbasis;
-    d.run_status = drun_status;
-    d.t = reinterpret_cast<double*>(buf);
-    d.obj = d.t + nt;
-    d.slope = d.obj + nt;
-    d.enter = reinterpret_cast<int*>(d.slope + ns);
-    d.leave = d.enter + ns;
-    d.basis_out = d.leave + ns;
-    d.nseg = d.basis_out + B * m;
-    d.status = d.nseg + B;
-    std::vector<char> done(B, 1);   // the LP's outputs were written on the device
-    std::vector<int> basis;         // per-LP path: the given bases
-    int rc = LP_OPTIMAL;
-    if (lp_basis_parametric_cost_fits(m, n)) {
-        rc = lp_basis_parametric_cost_launch(ctx, d, maximize);
-    } else {   // one LP after another: statuses and bases checked on the host
-        std::vector<int> st(B, LP_OPTIMAL);
-        basis.resize(B * m);
-        hipError_t e = hipMemcpyAsync(basis.data(), dbasis, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && drun_status)
-            e = hipMemcpyAsync(st.data(), drun_status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(buf);
-            LP_HIP(ctx, e);
-        }
-        for (size_t k = 0; k < B && rc >= 0; ++k) {
-            done[k] = 0;
-            if (st[k] != LP_OPTIMAL) continue;
-            for (int t = 0; t < m; ++t)
-                if (basis[k * m + t] < 0 || basis[k * m + t] >= n) st[k] = LP_BAD_ARG;
-            if (st[k] != LP_OPTIMAL) continue;
-            rc = lp_basis_parametric_cost_device(ctx, dA + k * m * n, m, n, db + k * m, dc + k * n, dbasis + k * m,
-                                            dg + k * n, maximize, t_max, eps, mb, d.nseg + k, d.t + k * (mb + 2),
-                                            d.obj + k * (mb + 2), d.slope + k * (mb + 1), d.enter + k * (mb + 1),
-                                            d.leave + k * (mb + 1), d.basis_out + k * m);
-            if (rc < 0) break;
-            st[k] = rc;
-            done[k] = rc == LP_OPTIMAL || rc == LP_UNBOUNDED || rc == LP_ITER_LIMIT;
-        }
-        if (rc >= 0) {
-            rc = LP_OPTIMAL;
-            e = hipMemcpyAsync(d.status, st.data(), sizeof(int) * B, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = -(int)e;
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        hipError_t e = hipMemcpyAsync(t_out, d.t, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(obj_out, d.obj, sizeof(double) * nt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(slope_out, d.slope, sizeof(double) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(enter_out, d.enter, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(leave_out, d.leave, sizeof(int) * ns, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(basis_out, d.basis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(nseg_out, d.nseg, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("basis parametric cost: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    }
-    (void)hipFree(buf);
-    if (rc != LP_OPTIMAL) return rc;
-    if (!basis.empty())   // the per-LP path writes the path only: the rest is NaN / -1, and LPs without one get it all
-        for (size_t k = 0; k < B; ++k) {
-            if (!done[k]) {
-                parametric_none(k, m, mb, basis.data() + k * m, nseg_out, t_out, obj_out, slope_out, enter_out,
-                                leave_out, basis_out);
-                continue;
-            }
-            const int ns_k = nseg_out[k];
-            for (int q = ns_k + 1; q < mb + 2; ++q) t_out[k * (mb + 2) + q] = obj_out[k * (mb + 2) + q] = NAN;
-            for (int q = ns_k; q < mb + 1; ++q) {
-                slope_out[k * (mb + 1) + q] = NAN;
-                enter_out[k * (mb + 1) + q] = leave_out[k * (mb + 1) + q] = -1;
-            }
-        }
-    return LP_OPTIMAL;
-}
-
-// Uploads `batch` LPs and their cost directions, then parametric_cost_on_device.
-static int parametric_cost_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                                  const double* c, const int* basis, int maximize, const double* g, double t_max,
-                                  double eps, int mb, int* nseg_out, double* t_out, double* obj_out, double* slope_out,
-                                  int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + 2 * n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * m));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    double* dg = dc + B * n;
-    int* dbasis = reinterpret_cast<int*>(dg + B * n);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dg, g, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("basis parametric cost upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = parametric_cost_on_device(ctx, batch, m, n, dA, db, dc, dbasis, nullptr, dg, maximize, t_max, eps, mb,
-                                       nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-int lp_basis_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                             const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks,
-                             int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
-                             int* leave_out, int* basis_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: bad dimensions");
-    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: max_breaks must be >= 0");
-    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-    int rc = parametric_args(ctx, "lp_basis_parametric_cost", t_max, eps, max_breaks);
-    if (rc) return rc;
-    for (int t = 0; t < m; ++t)
-        if (basis[t] < 0 || basis[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    int status = LP_OPTIMAL;
-    rc = parametric_cost_upload(ctx, 1, A, m, n, b, c, basis, maximize, g, t_max, eps, max_breaks, nseg_out, t_out,
-                                obj_out, slope_out, enter_out, leave_out, basis_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: the basis is not optimal at t = 0");
-    return status;
-}
-
-int lp_basis_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                                     const double* c, const int* basis, int maximize, const double* g, double t_max,
-                                     double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
-                                     double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: bad dimensions");
-    const int rc = parametric_args(ctx, "lp_basis_parametric_cost_batched", t_max, eps, max_breaks);
-    if (rc) return rc;
-    return parametric_cost_upload(ctx, batch, A, m, n, b, c, basis, maximize, g, t_max, eps, max_breaks, nseg_out, t_out,
-                                  obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
-}
-
-int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_max, double eps, int max_breaks,
-                               int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
-                               int* leave_out, int* basis_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: null argument");
-    int rc = parametric_args(ctx, "lp_batched_parametric_cost", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n, mb = max_breaks;
-    const size_t B = (size_t)p->batch;
-    if (p->resident) {   // A, b, c, the final bases and the run statuses where the run left them; g goes up
-        double* dg = nullptr;
-        LP_HIP(ctx, hipMalloc(&dg, sizeof(double) * B * n));
-        hipError_t e = hipMemcpyAsync(dg, g, sizeof(double) * B * n, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(dg);
-            LP_HIP(ctx, e);
-        }
-        rc = parametric_cost_on_device(ctx, p->batch, m, n, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, dg,
-                                       p->maximize, t_max, eps, mb, nseg_out, t_out, obj_out, slope_out, enter_out,
-                                       leave_out, basis_out, status_out);
-        (void)hipFree(dg);
-        return rc;
-    }
-    // per-LP fallback: the single-LP call on the kept inputs and each LP's final basis
-    std::vector<int> basis((size_t)m);
-    for (size_t k = 0; k < B; ++k) {
-        if (p->two_phase || p->resolve) {
-            std::memcpy(basis.data(), p->h_basis.data() + k * m, sizeof(int) * m);
-        } else {
-            rc = lp_simplex_download(p->lps[k], nullptr, basis.data(), nullptr, nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-        int st = p->status[k];
-        parametric_none(k, m, mb, basis.data(), nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-        if (st == LP_OPTIMAL) {
-            st = lp_basis_parametric_cost(ctx, p->h_A.data() + k * m * n, m, n, p->h_b.data() + k * m,
-                                          p->h_c.data() + k * n, basis.data(), p->maximize, g + k * n, t_max, eps, mb,
-                                          nseg_out + k, t_out + k * (mb + 2), obj_out + k * (mb + 2),
-                                          slope_out + k * (mb + 1), enter_out + k * (mb + 1), leave_out + k * (mb + 1),
-                                          basis_out + k * m);
-            if (st < 0) return st;
-        }
-        status_out[k] = st;
-    }
-    ctx->last_error.clear();
-    return LP_OPTIMAL;
-}
-
-// ===========================================================================
-// Depth-first branch-and-bound (batched_mip.hip): one integer LP per workgroup for lp_mip_fits shapes only; there is
-// no per-LP host fallback
-// ===========================================================================
-
-int lp_mip_fits(int m, int n, int max_depth) { return lp_mip_fits_shape(m, n, max_depth) ? 1 : 0; }
-
-// The search parameters and the mask (the basis and the problem arrays are checked by the callers).
-static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, const int* integer, double int_tol,
-                    double gap, int max_depth, int max_nodes) {
-    if (!integer) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
-    if (max_depth < 0 || max_depth > LP_MIP_MAX_DEPTH)
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_depth must be in [0, 64]");
-    if (!(int_tol >= 0.0 && int_tol < 0.5)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": int_tol must be in [0, 0.5)");
-    if (!(gap >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": gap must be >= 0");
-    if (max_nodes < 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_nodes must be >= 1");
-    for (int j = 0; j < n; ++j) {
-        if (integer[j] != 0 && integer[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": mask entries must be 0 or 1");
-        if (integer[j] && j >= n_orig)
-            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the mask marks a column beyond n_orig");
-    }
-    if (!lp_mip_fits_shape(m, n, max_depth))
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_mip_fits)");
-    return LP_OPTIMAL;
-}
-
-// The search of `batch` problems whose A, b, c and root bases are on the device; drun_status (device, or nullptr):
-// problems whose entry is not LP_OPTIMAL keep it.  The mask goes up; outputs to the host.
-static int mip_on_device(lp_context* ctx, int batch, int m, int n, int n_orig, const double* dA, const double* db,
-                         const double* dc, const int* dbasis, const int* drun_status, const int* integer, int maximize,
-                         double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter,
-                         double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
-                         int* status_out) {
-    hipStream_t s = ctx->stream;
-    const size_t B = (size_t)batch;
-    const size_t bytes = sizeof(double) * (B * n_orig + 2 * B) + sizeof(int) * (B * 6 + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, bytes));
-    BatchedMipDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    d.n_orig = n_orig;
-    d.maximize = maximize ? 1 : 0;
-    d.max_iter = max_iter;
-    d.max_depth = max_depth;
-    d.max_nodes = max_nodes;
-    d.eps = eps;
-    d.int_tol = int_tol;
-    d.gap = gap;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.basis_in = dbasis;
-    d.run_status = drun_status;
-    d.x = reinterpret_cast<double*>(buf);
-    d.obj = d.x + B * n_orig;
-    d.bound = d.obj + B;
-    d.found = reinterpret_cast<int*>(d.bound + B);
-    d.stats = d.found + B;
-    d.status = d.stats + B * 4;
-    int* dmask = d.status + B;
-    d.integer = dmask;
-    hipError_t e = hipMemcpyAsync(dmask, integer, sizeof(int) * n, hipMemcpyHostToDevice, s);
-    int rc = e == hipSuccess ? lp_batched_mip_launch(ctx, d) : -(int)e;
-    if (rc == LP_OPTIMAL) {
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(x_out, d.x, sizeof(double) * B * n_orig, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(obj_out, d.obj, sizeof(double) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(bound_out, d.bound, sizeof(double) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(found_out, d.found, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(stats_out, d.stats, sizeof(int) * B * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("batched MIP: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    } else if (rc < 0) {
-        ctx->last_error = std::string("batched MIP upload: ") + hipGetErrorString(e);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-// Uploads `batch` problems and their root bases, then mip_on_device.
-static int mip_upload(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
-                      const int* basis, int maximize, int n_orig, const int* run_status, const int* integer,
-                      double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter,
-                      double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
-                      int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch, dbl = B * ((size_t)m * n + m + n);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * B * (m + 1)));
-    double* dA = reinterpret_cast<double*>(buf);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    int* dbasis = reinterpret_cast<int*>(dc + B * n);
-    int* drun = dbasis + B * m;
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && run_status) e = hipMemcpyAsync(drun, run_status, sizeof(int) * B, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = LP_OPTIMAL;
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("batched MIP upload: ") + hipGetErrorString(e);
-        rc = -(int)e;
-    } else {
-        rc = mip_on_device(ctx, batch, m, n, n_orig, dA, db, dc, dbasis, run_status ? drun : nullptr, integer,
-                           maximize, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out,
-                           found_out, stats_out, status_out);
-    }
-    (void)hipFree(buf);
-    return rc;
-}
-
-int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const int* basis,
-                 int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth,
-                 int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
-                 int* stats_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: null argument");
-    int rc = check_canonical(ctx, A, m, n, b, c, basis, n_orig);
-    if (rc) return rc;
-    rc = mip_args(ctx, "lp_mip_solve", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    rc = mip_upload(ctx, 1, A, m, n, b, c, basis, maximize, n_orig, nullptr, integer, eps, int_tol, gap, max_depth,
-                    max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: the basis is neither primal nor dual feasible");
-    return status;
-}
-
-int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
-                         const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol,
-                         double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
-                         double* bound_out, int* found_out, int* stats_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve_batched: null argument");
-    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
-    for (int k = 0; k < batch; ++k) {
-        int rc = check_canonical(ctx, A ? A + (size_t)k * m * n : nullptr, m, n, b ? b + (size_t)k * m : nullptr,
-                                 c ? c + (size_t)k * n : nullptr, basis ? basis + (size_t)k * m : nullptr, n_orig);
-        if (rc) return rc;
-    }
-    const int rc = mip_args(ctx, "lp_mip_solve_batched", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
-    if (rc) return rc;
-    return mip_upload(ctx, batch, A, m, n, b, c, basis, maximize, n_orig, nullptr, integer, eps, int_tol, gap,
-                      max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, status_out);
-}
-
-int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double int_tol, double gap, int max_depth,
-                   int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
-                   int* stats_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: null argument");
-    int rc = mip_args(ctx, "lp_batched_mip", p->m, p->n, p->n_orig, integer, int_tol, gap, max_depth, max_nodes);
-    if (rc) return rc;
-    if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: Dantzig's rule only");
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: the batch has not run");
-    LP_HIP(ctx, hipSetDevice(ctx->device));
-    const int m = p->m, n = p->n;
-    const size_t B = (size_t)p->batch;
-    if (p->resident)   // A, b, c, the final bases and the run statuses where the run left them
-        return mip_on_device(ctx, p->batch, m, n, p->n_orig, p->dA, p->db, p->dc, p->dbasis_out, p->dstatus, integer,
-                             p->maximize, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out,
-                             bound_out, found_out, stats_out, status_out);
-    // per-LP runs: the kept inputs and each LP's final basis go up, then the same kernel
-    std::vector<int> basis(B * m);
-    for (size_t k = 0; k < B; ++k) {
-        if (p->two_phase || p->resolve) {
-            std::memcpy(basis.data() + k * m, p->h_basis.data() + k * m, sizeof(int) * m);
-        } else {
-            rc = lp_simplex_download(p->lps[k], nullptr, basis.data() + k * m, nullptr, nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-    }
-    return mip_upload(ctx, p->batch, p->h_A.data(), m, n, p->h_b.data(), p->h_c.data(), basis.data(), p->maximize,
-                      p->n_orig, p->status.data(), integer, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out,
-                      obj_out, bound_out, found_out, stats_out, status_out);
-}
-
-
-// ===========================================================================
 // Bounded-variable simplex (batched_bounded.hip): one LP per workgroup for lp_simplex_bounded_fits shapes only; there
 // is no per-LP host fallback
 // ===========================================================================
@@ -2138,8 +840,8 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     LP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch;
     const size_t dbl = B * ((size_t)m * n + m + 4 * (size_t)n), ints = B * ((size_t)m + n + 4 + 1);
-    char* buf = nullptr;
-    LP_HIP(ctx, hipMalloc(&buf, sizeof(double) * dbl + sizeof(int) * ints));
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * dbl + sizeof(int) * ints));
     BatchedBoundedDev d{};
     d.batch = batch;
     d.m = m;
@@ -2148,7 +850,7 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     d.maximize = maximize ? 1 : 0;
     d.max_iter = max_iter;
     d.eps = eps;
-    double* dA = reinterpret_cast<double*>(buf);
+    double* dA = reinterpret_cast<double*>(buf.ptr);
     double* db = dA + B * m * n;
     double* dc = db + B * m;
     double* dlo = dc + B * n;
@@ -2170,23 +872,16 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dlo, lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dhi, hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    int rc = e == hipSuccess ? lp_batched_bounded_launch(ctx, d) : -(int)e;
-    if (rc == LP_OPTIMAL) {
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(x.data(), d.x, sizeof(double) * B * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(basis_out, d.basis_out, sizeof(int) * B * m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(at_upper_out, d.at_upper, sizeof(int) * B * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(iters_out, d.iters, sizeof(int) * B * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(status_out, d.status, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("batched bounded simplex: ") + hipGetErrorString(e);
-            rc = -(int)e;
-        }
-    } else if (rc < 0) {
-        ctx->last_error = std::string("batched bounded simplex upload: ") + hipGetErrorString(e);
-    }
-    (void)hipFree(buf);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex upload: ") + hipGetErrorString(e));
+    int rc = lp_batched_bounded_launch(ctx, d);
+    if (rc) return rc;
+    e = hipGetLastError();
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex: ") + hipGetErrorString(e));
+    rc = lp_download(ctx, "batched bounded simplex", {{x.data(), d.x, sizeof(double) * B * n},
+                                                      {basis_out, d.basis_out, sizeof(int) * B * m},
+                                                      {at_upper_out, d.at_upper, sizeof(int) * B * n},
+                                                      {iters_out, d.iters, sizeof(int) * B * 4},
+                                                      {status_out, d.status, sizeof(int) * B}});
     if (rc) return rc;
     for (size_t k = 0; k < B; ++k) {
         if (status_out[k] != LP_OPTIMAL) continue;

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -89,6 +90,59 @@ inline void lp_pool_release(lp_context* ctx, void* p, size_t bytes) {
         (ctx)->last_error = (msg);   \
         return (code);               \
     } while (0)
+
+// Owns one device allocation for the length of a call: freed on every return path.
+struct lp_device_buffer {
+    char* ptr = nullptr;
+    lp_device_buffer() = default;
+    lp_device_buffer(const lp_device_buffer&) = delete;
+    lp_device_buffer& operator=(const lp_device_buffer&) = delete;
+    ~lp_device_buffer() { (void)hipFree(ptr); }
+};
+
+// Hands out 16-byte-aligned pieces of one device allocation in the order they are asked for.  A carve list runs
+// twice through lp_carve_malloc: first on a carver without a base, which only measures, then over the allocation,
+// so the allocation's size always comes from the list that hands out the pointers.
+struct lp_carver {
+    char* base = nullptr;
+    size_t used = 0;
+    template <typename T>
+    T* take(size_t bytes) {
+        T* r = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += (bytes + 15) & ~(size_t)15;
+        return r;
+    }
+};
+
+// hipMalloc of exactly what `list(lp_carver&)` takes, then `list` again over the allocation.
+template <typename List>
+inline hipError_t lp_carve_malloc(char** arena, List&& list) {
+    lp_carver measure;
+    list(measure);
+    const hipError_t e = hipMalloc(arena, measure.used);
+    if (e != hipSuccess) return e;
+    lp_carver cut{*arena};
+    list(cut);
+    return hipSuccess;
+}
+
+// One device-to-host copy of lp_download.
+struct lp_d2h {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+
+// Queues the copies on the context's stream (those of 0 bytes are skipped), then one sync.  A failure is
+// "<label>: <HIP error>" in last_error and -(hipError_t) returned.
+inline int lp_download(lp_context* ctx, const char* label, std::initializer_list<lp_d2h> copies) {
+    hipError_t e = hipSuccess;
+    for (const lp_d2h& q : copies)
+        if (e == hipSuccess && q.bytes) e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string(label) + ": " + hipGetErrorString(e));
+    return LP_OPTIMAL;
+}
 
 template <typename T>
 static inline T lp_ceil_div(T a, T b) {

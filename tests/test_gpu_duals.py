@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from simplexmethod_amd import capi
+from tests import certcases as CC
 from tests import duals_ref as D
 from tests import lpcases
 from tests import resolve_ref as R
@@ -135,6 +136,22 @@ def test_fallback_handle(ctx):
     _same(g, D.duals_batched(A, b, c, s["basis"], s["status"]))
     for k in range(3):
         _strong(g["w"][k], s["obj"][k])
+
+
+def test_fallback_handle_keeps_run_statuses(ctx):
+    """A plain fallback handle with unbounded LPs (test_gpu_certificate's): only the LP_OPTIMAL ones get duals."""
+    A, b, c, basis, names = CC.plain_mix(40, 6, 16, 40)
+    basis = basis[:, ::-1].copy()   # the slack basis, positions reversed
+    p = ctx.batched_problem(A, b, c, basis, True)
+    try:
+        assert p.path() == 0
+        p.run()
+        s = p.download()
+        g = p.duals()
+    finally:
+        p.free()
+    assert [int(v) for v in s["status"]] == [0 if f == "optimal" else 1 for f in names]
+    _same(g, D.duals_batched(A, b, c, s["basis"], s["status"]))
 
 
 def test_mixed_batch_keeps_run_statuses(ctx):

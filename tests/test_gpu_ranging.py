@@ -6,6 +6,7 @@ import pytest
 
 from oracle import pyoracle as o
 from simplexmethod_amd import capi
+from tests import certcases as CC
 from tests import duals_ref as D
 from tests import lpcases
 from tests import ranging_ref as RR
@@ -136,6 +137,22 @@ def test_fallback_handle(ctx):
         p.free()
     assert (s["status"] == capi.OPTIMAL).all()
     _same(g, RR.ranging_batched(A, b, c, s["basis"], False, run_status=s["status"]))
+
+
+def test_fallback_handle_keeps_run_statuses(ctx):
+    """A plain fallback handle with unbounded LPs (test_gpu_certificate's): only the LP_OPTIMAL ones get ranges."""
+    A, b, c, basis, names = CC.plain_mix(40, 6, 16, 40)
+    basis = basis[:, ::-1].copy()   # the slack basis, positions reversed
+    p = ctx.batched_problem(A, b, c, basis, True)
+    try:
+        assert p.path() == 0
+        p.run()
+        s = p.download()
+        g = p.ranging()
+    finally:
+        p.free()
+    assert [int(v) for v in s["status"]] == [0 if f == "optimal" else 1 for f in names]
+    _same(g, RR.ranging_batched(A, b, c, s["basis"], True, run_status=s["status"]))
 
 
 def test_mixed_batch_keeps_run_statuses(ctx):
