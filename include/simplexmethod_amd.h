@@ -70,7 +70,9 @@ int lp_context_sync(lp_context* ctx);
 
 /* One-shot: upload, solve on the GPU, download.
  * basis_in : Canonical::GetBasisIndices() (m entries, by basis position).
- * eps      : Solver::EPS (1e-9, SimplexSolover.h:13).
+ * eps      : Solver::EPS (1e-9, SimplexSolover.h:13).  Every solve entry of this header that takes eps
+ *            (single, re-solve, two-phase, batched, bounded, MIP) requires eps >= 0 (+0.0, -0.0 and +inf
+ *            included) and returns LP_BAD_ARG for eps < 0 or NaN.
  * max_iter : MAX_ITER (10000, SimplexSolover.h:426).
  * x_out    : n_orig doubles = solve()'s return value (:435-439).
  * basis_out: m ints, final basis BY POSITION (the reference's local N, :419).
@@ -226,7 +228,8 @@ int lp_debug_simplex_stamps(lp_simplex_problem* p, int cap_pivots, unsigned long
 /* Batched simplex (BASELINE.json configs[4]): `batch` independent LPs of one
  * shape, one LP per workgroup.  Arrays are concatenated per LP: A batch*m*n
  * (each column-major), b batch*m, c batch*n, basis_in batch*m; outputs x_out
- * batch*n_orig, basis_out batch*m, obj_out/iters_out/status_out batch.           */
+ * batch*n_orig, basis_out batch*m, obj_out/iters_out/status_out batch.  eps as lp_simplex_solve
+ * (LP_BAD_ARG for eps < 0 or NaN, here and in lp_batched_run).               */
 int lp_simplex_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n,
                              const double* b, const double* c, const int* basis_in, int maximize,
                              int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
@@ -513,7 +516,7 @@ int lp_basis_parametric_cost_fits(int m, int n);
  *     search.  Any of the three makes the status LP_ITER_LIMIT with the incumbent kept.  A node whose crash gives
  *     LP_SINGULAR or LP_BAD_ARG stops the search with that status (not expected on well-conditioned input).
  *   - status: LP_OPTIMAL (the incumbent is optimal), LP_INFEASIBLE (no integer point, or the root is infeasible),
- *     LP_UNBOUNDED (the root relaxation), LP_ITER_LIMIT, LP_SINGULAR / LP_BAD_ARG.
+ *     LP_UNBOUNDED (the root relaxation), LP_ITER_LIMIT, LP_SINGULAR / LP_BAD_ARG (eps < 0 or NaN among others).
  *   - found_out 0/1; x_out (n_orig) and obj_out the incumbent, NaN without one; bound_out the best LP objective
  *     over the incumbent and the nodes left open or abandoned (equal to obj_out on LP_OPTIMAL; +-inf when the root
  *     relaxation is unbounded or unfinished; NaN with neither); stats_out[4] = nodes solved, dual pivots, primal
@@ -541,7 +544,7 @@ int lp_mip_fits(int m, int n, int max_depth);
  * complemented.  The phases are lp_simplex_two_phase's (rows with b' < -eps change sign, phase I over m artificials,
  * LP_INFEASIBLE iff their sum > eps, the same drive-out with LP_SINGULAR, phase II on the phase-I tableau with the
  * artificials barred).  Dantzig's rule only.  With lo = 0 and hi = +inf the result is lp_simplex_two_phase's.
- *   - LP_BAD_ARG for a NaN or infinite lo_j, a NaN hi_j, a NULL pointer or a shape beyond lp_simplex_bounded_fits
+ *   - LP_BAD_ARG for a NaN or infinite lo_j, a NaN hi_j, eps < 0 or NaN, a NULL pointer or a shape beyond lp_simplex_bounded_fits
  *     (there is no per-LP host path); an LP with some hi_j < lo_j is LP_INFEASIBLE without an iteration.
  *   - max_iter bounds each phase's iterations; an iteration is a pivot or a bound flip.
  *   - outputs: x_out (n_orig) and obj_out (sum_{j<n} c_j x_j) for LP_OPTIMAL only; basis_out (m) and at_upper_out

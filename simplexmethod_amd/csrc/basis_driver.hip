@@ -865,6 +865,7 @@ int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b
     if (!ctx) return LP_BAD_ARG;
     if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve: eps must be >= 0");
     int rc = check_canonical(ctx, A, m, n, b, c, basis, n_orig);
     if (rc) return rc;
     rc = mip_args(ctx, "lp_mip_solve", m, n, n_orig, integer, int_tol, gap, max_depth, max_nodes);
@@ -888,6 +889,7 @@ int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int
     if (!ctx) return LP_BAD_ARG;
     if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_solve_batched: eps must be >= 0");
     if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
     for (int k = 0; k < batch; ++k) {
         int rc = check_canonical(ctx, A ? A + (size_t)k * m * n : nullptr, m, n, b ? b + (size_t)k * m : nullptr,
@@ -911,6 +913,7 @@ int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double
     lp_context* ctx = p->ctx;
     if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: eps must be >= 0");
     int rc = mip_args(ctx, "lp_batched_mip", p->m, p->n, p->n_orig, integer, int_tol, gap, max_depth, max_nodes);
     if (rc) return rc;
     if (p->pivot_rule != LP_PIVOT_DANTZIG) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_mip: Dantzig's rule only");

@@ -614,6 +614,7 @@ int lp_simplex_resolve_batched(lp_context* ctx, int batch, const double* A, int 
                                int* status_out) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_resolve_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_resolve_batched: eps must be >= 0");
     lp_batched_problem* p = nullptr;
     int rc = lp_batched_resolve_upload(ctx, batch, A, m, n, b, c, basis_in, maximize, n_orig, &p);
     if (rc) return rc;
@@ -653,6 +654,7 @@ int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A,
                                     double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: eps must be >= 0");
     if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_batched_problem* p = nullptr;
     int rc = lp_batched_two_phase_upload(ctx, batch, A, m, n, b, c, maximize, n_orig, &p);
@@ -733,6 +735,7 @@ static int batched_run(lp_batched_problem* p, double eps, int max_iter, float* m
 
 int lp_batched_run(lp_batched_problem* p, double eps, int max_iter, float* ms_out) {
     if (!p) return LP_BAD_ARG;
+    if (!(eps >= 0.0)) LP_FAIL(p->ctx, LP_BAD_ARG, "lp_batched_run: eps must be >= 0");
     const int rc = batched_run(p, eps, max_iter, ms_out);
     p->ran = rc == LP_OPTIMAL;
     return rc;
@@ -799,6 +802,7 @@ int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int
                                 double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
     if (ctx && pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
         LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
+    if (ctx && !(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_solve_batched: eps must be >= 0");
     lp_batched_problem* p = nullptr;
     int rc = lp_batched_upload(ctx, batch, A, m, n, b, c, basis_in, maximize, n_orig, &p);
     if (rc) return rc;
@@ -901,6 +905,7 @@ int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const dou
     if (!ctx) return LP_BAD_ARG;
     if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded: eps must be >= 0");
     int rc = bounded_args(ctx, "lp_simplex_bounded", 1, A, m, n, b, c, lo, hi, n_orig);
     if (rc) return rc;
     int status = LP_OPTIMAL;
@@ -916,6 +921,7 @@ int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int 
     if (!ctx) return LP_BAD_ARG;
     if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !status_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_batched: eps must be >= 0");
     if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
     const int rc = bounded_args(ctx, "lp_simplex_bounded_batched", batch, A, m, n, b, c, lo, hi, n_orig);
     if (rc) return rc;

@@ -439,6 +439,7 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
                    lp_simplex_stats* stats_out) {
     if (!p) return LP_BAD_ARG;
     lp_context* ctx = p->ctx;
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_run: eps must be >= 0");
     LP_HIP(ctx, hipSetDevice(ctx->device));
     if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
     if (p->init_status != LP_OPTIMAL) {  // "Singular basis matrix", SimplexSolover.h:125-126
@@ -495,6 +496,7 @@ int lp_simplex_resolve_run(lp_simplex_problem* p, double eps, int max_iter, int*
                            lp_simplex_stats* stats_out) {
     if (!p) return LP_BAD_ARG;
     lp_context* ctx = p->ctx;
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_resolve_run: eps must be >= 0");
     LP_HIP(ctx, hipSetDevice(ctx->device));
     if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
     if (iters_out) iters_out[0] = iters_out[1] = 0;
@@ -589,6 +591,7 @@ int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const do
                         int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "x_out is null");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_solve: eps must be >= 0");
     if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A, m, n, b, c, basis_in, maximize, n_orig, &p);
@@ -611,6 +614,7 @@ int lp_simplex_resolve(lp_context* ctx, const double* A, int m, int n, const dou
                        int* basis_out, double* obj_out, int* iters_out) {
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "x_out is null");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_resolve: eps must be >= 0");
     if (iters_out) iters_out[0] = iters_out[1] = 0;
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A, m, n, b, c, basis_in, maximize, n_orig, &p);
@@ -660,6 +664,7 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
                             int pivot_rule) {
     if (!ctx) return LP_BAD_ARG;
     if (!A || !b || !c || !x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: eps must be >= 0");
     if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: bad dimensions");
     const int na = n + m;

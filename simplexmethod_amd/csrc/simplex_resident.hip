@@ -205,12 +205,23 @@ __device__ __forceinline__ double nan_to(double v, double sentinel) { return (v 
 // first index of the approximate minimum, whatever the last bits of the true quotients are.  Anything else is a "near-
 // tie" and takes the exact replay with true divisions (MODE_RSLOW).  The minimum's VALUE is not used downstream: the
 // pivot needs the row r and the exact column entry u_r.
-constexpr double kRatioSlack = 0x1p-48, kRatioCap = 32768.0;
+// The argument needs eps >= kRatioEpsFloor.  An entry v behind the minimum M (q~_v >= q~_M) has q_M - q_v <= 2^-51
+// (|q~_M| + |q~_v|) (1 + 2^-50) < 2^-35 under the cap; the chain takes it only if q_v < fl(q_M - eps), i.e. if q_M - q_v
+// exceeds eps less half an ulp of q_M (<= 2^-38 under the cap).  With eps >= 2^-30 that needs a gap 31 times the
+// largest possible one; with eps = 0 a row behind that is a single ulp smaller would be missed, in the slice or in a
+// slice behind the winner's.  The floor also bounds every eligible u_i from below (u_i > eps >= 2^-30), so 1/u_i is a
+// normal number (u_i = 5e-324 has none: its ratio would turn into NaN and the row vanish from the ranking); above it,
+// xB_i * (1/u_i) keeps the 2-ulp bound whatever xB_i is, except where it underflows (an absolute error below 2^-1074,
+// far below eps) or lies far above the cap (no verdict changes), and for u_i >= 2^1022, where 1/u_i is subnormal.
+// Below the floor the host launches the EXACT instantiation: its slice verdicts always fail and it leaves "no row
+// eligible" to the replay too, so that EVERY ratio test takes the exact replay (and the pivot loop tests no eps).
+constexpr double kRatioSlack = 0x1p-48, kRatioCap = 32768.0, kRatioEpsFloor = 0x1p-30;
 constexpr int RS_SLICES = 16;   // slice records per workgroup and parity: [0..15] the A granules, [16..31] the B granules
 
 // CPT columns per workgroup; NT = upper bound of the row threads (the launch uses mpad = m rounded up to
-// 64 row threads PLUS ONE COMMUNICATION WAVE: blockDim = mpad + 64).
-template <int CPT, int NT>
+// 64 row threads PLUS ONE COMMUNICATION WAVE: blockDim = mpad + 64).  EXACT: eps < kRatioEpsFloor, every ratio test
+// takes the exact replay.
+template <int CPT, int NT, bool EXACT>
 __global__ __launch_bounds__(NT + 64) void k_simplex_resident(SimplexDev d, ResidentDev rd) {
     static_assert(CPT == 32 || CPT == 16, "the slab is two vectors of 16 or 8 doubles");
     constexpr int HALF = CPT / 2;
@@ -434,8 +445,8 @@ __global__ __launch_bounds__(NT + 64) void k_simplex_resident(SimplexDev d, Resi
             const double Mv_ = lpdev::f64_from_key(rk_);                                             \
             const double Mhi_ = (Mv_ + eps) + kRatioSlack * fabs(Mv_);                               \
             const unsigned long long near_ = __ballot(lane < L_ && !(Mhi_ < vlow_));                 \
-            const bool ok_ = any_ && near_ == 0ULL && fabs(Mv_) < kRatioCap;                         \
             const double uL_ = lpdev::wave_bcast_f64((UP), L_);                                      \
+            const bool ok_ = !EXACT && any_ && near_ == 0ULL && fabs(Mv_) < kRatioCap; /* kRatioEpsFloor */ \
             if (lane < 2) {                                                                          \
                 const v4i g_ = lane == 0 ? r_pack(ep, any_ ? (unsigned)(wave * 64 + L_ + 1) : 0u, ok_ ? 1u : 0u, rk_) \
                                          : r_pack(ep, 0u, 0u, (unsigned long long)__double_as_longlong(uL_)); \
@@ -610,7 +621,8 @@ __global__ __launch_bounds__(NT + 64) void k_simplex_resident(SimplexDev d, Resi
                     mode = MODE_FAIL;
                     if (lane == 0) sh.ctl->fail = 8;   // code 8: slice poll
                 } else if (M2 == kPosInf) {
-                    mode = MODE_UNBOUNDED;   // no row of the entering column is eligible (:179)
+                    // no row of the entering column is eligible (:179) — below kRatioEpsFloor the replay decides
+                    mode = EXACT ? MODE_RSLOW : MODE_UNBOUNDED;
                 } else {
                     const int W2 = (int)__builtin_ctzll(h2);   // first slice attaining the minimum (row order)
                     const int okW = __builtin_amdgcn_readlane(okl, W2);
@@ -1066,11 +1078,11 @@ __global__ void k_resident_state_init(SimplexDev d, double eps, int max_iter) {
     st->eps = eps;
 }
 
-template <int CPT, int NT>
+template <int CPT, int NT, bool EXACT>
 void launch_resident(const SimplexDev& d, const ResidentDev& rd, size_t shm, hipStream_t s, hipError_t* attr_err) {
-    *attr_err = lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_resident<CPT, NT>), shm);
+    *attr_err = lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_resident<CPT, NT, EXACT>), shm);
     if (*attr_err == hipSuccess)
-        hipLaunchKernelGGL((k_simplex_resident<CPT, NT>), rd.G * rd.stride, rd.mpad + 64, shm, s, d, rd);
+        hipLaunchKernelGGL((k_simplex_resident<CPT, NT, EXACT>), rd.G * rd.stride, rd.mpad + 64, shm, s, d, rd);
 }
 
 // ---- self-test of lpdev::mid_div against the compiler's division (lp_debug_division) ----
@@ -1138,10 +1150,11 @@ int lp_resident_launch(lp_simplex_problem* p, double eps, int max_iter) {
     }
     LP_HIP(ctx, hipEventRecord(p->res_ev0, s));
     hipError_t attr_err = hipSuccess;
+    const bool exact = !(eps >= kRatioEpsFloor);   // (the entries refuse eps < 0 and NaN)
     if (rd.cpt == 32)
-        launch_resident<32, 512>(d, rdv, shm, s, &attr_err);
+        (exact ? launch_resident<32, 512, true> : launch_resident<32, 512, false>)(d, rdv, shm, s, &attr_err);
     else
-        launch_resident<16, 960>(d, rdv, shm, s, &attr_err);
+        (exact ? launch_resident<16, 960, true> : launch_resident<16, 960, false>)(d, rdv, shm, s, &attr_err);
     LP_HIP(ctx, attr_err);
     LP_HIP(ctx, hipEventRecord(p->res_ev1, s));
     return LP_OPTIMAL;
