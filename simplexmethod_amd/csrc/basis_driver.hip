@@ -74,19 +74,8 @@ static int batch_inputs(lp_batched_problem* p, const char* what, lp_device_buffe
         if (!extra) return LP_OPTIMAL;
         return upload(ctx, what, buf, batch, m, n, nullptr, nullptr, nullptr, extra, extra_len, nullptr, nullptr, in);
     }
-    std::vector<int> basis;
-    if (p->two_phase || p->resolve) {
-        basis = p->h_basis;
-    } else {
-        basis.resize((size_t)batch * m);
-        for (size_t k = 0; k < (size_t)batch; ++k) {
-            const int rc = lp_simplex_download(p->lps[k], nullptr, basis.data() + k * m, nullptr, nullptr, nullptr, 0,
-                                               nullptr);
-            if (rc) return rc;
-        }
-    }
     return upload(ctx, what, buf, batch, m, n, p->h_A.data(), p->h_b.data(), p->h_c.data(), extra, extra_len,
-                  basis.data(), p->status.data(), in);
+                  p->h_basis.data(), p->status.data(), in);
 }
 
 // Basis checks on the host: LP_BAD_ARG for an index outside [0, n), else LP_OPTIMAL.

@@ -277,33 +277,38 @@ size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
 bool lp_bounded_fits_shape(int m, int n);
 int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
 
-// A batch handle of the C ABI (capi.hip: upload, run, download); the analyses of basis_driver.hip read its inputs and
-// final bases after a run.
+// A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
+// inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP
+// entry its per-LP fallback calls; everything else is the same for the three kinds.
+enum lp_batched_kind {
+    LP_BATCHED_PLAIN,       // lp_batched_upload: from given bases, one pivot count per LP
+    LP_BATCHED_TWO_PHASE,   // lp_batched_two_phase_upload: no starting basis; phase I, drive-out, phase II
+    LP_BATCHED_RESOLVE      // lp_batched_resolve_upload: re-solved from given bases; dual pivots, primal pivots
+};
+
 struct lp_batched_problem {
     lp_context* ctx = nullptr;
+    lp_batched_kind kind = LP_BATCHED_PLAIN;
     int batch = 0, m = 0, n = 0, n_orig = 0;
-    bool resident = false;              // true: LDS-resident kernel; false: per-LP fallback
-    BatchedDev dev{};
+    int maximize = 0;
+    int iter_width = 1;                 // pivot counts per LP: 1, 3, 2 (by kind)
+    int pivot_rule = LP_PIVOT_DANTZIG;  // lp_batched_set_pivot_rule: read by every run
+    bool resident = false;              // true: one LP per workgroup on the GPU; false: per-LP fallback
+    bool ran = false;                   // a run completed: the analyses have final bases to read
+    std::vector<double> h_c;            // the costs (the objective of download)
+    std::vector<int> status, iters;     // of the last run: batch, batch*iter_width (a resident handle's: as of the last download)
+    // resident: one device allocation and the pieces carved from it (dbasis_in: not for two-phase batches)
+    char* arena = nullptr;
+    int pitch = 0;                      // row pitch of the kernel's LDS tableau
     double *dA = nullptr, *db = nullptr, *dc = nullptr, *dx = nullptr;
     int *dbasis_in = nullptr, *dbasis_out = nullptr, *diters = nullptr, *dstatus = nullptr;
-    std::vector<double> h_c;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<lp_simplex_problem*> lps;  // fallback
-    std::vector<int> status, iters;
-    // two-phase batch (lp_batched_two_phase_upload): no basis_in, three pivot counts per LP
-    bool two_phase = false;
-    int maximize = 0;
-    BatchedTwoPhaseDev tdev{};
-    std::vector<int> phase_iters;           // batch*3
-    std::vector<double> h_A, h_b;           // per-LP fallback: the inputs ...
-    std::vector<double> h_x, h_obj;         // ... and its outputs (x batch*n_orig, obj batch)
+    unsigned long long* dstamps = nullptr;   // BatchedDev::stamps (LP_BATCHED_STAMPS), allocated by the first run
+    int stamps_reg = 0;
+    // per-LP fallback: the inputs, and what each LP's run left (x and obj of LP_OPTIMAL LPs only)
+    std::vector<double> h_A, h_b;
+    std::vector<int> h_basis_in;            // batch*m (not for two-phase batches)
+    std::vector<lp_simplex_problem*> lps;   // plain batches: the uploaded LPs, kept between runs
+    std::vector<double> h_x, h_obj;         // batch*n_orig, batch
     std::vector<int> h_basis;               // batch*m
-    int pivot_rule = LP_PIVOT_DANTZIG;      // lp_batched_set_pivot_rule: read by every run
-    // re-solve batch (lp_batched_resolve_upload): given bases, two pivot counts per LP; the per-LP fallback keeps
-    // h_A, h_b, h_basis_in and its outputs in h_x, h_obj, h_basis
-    bool resolve = false;
-    BatchedResolveDev rdev{};
-    std::vector<int> resolve_iters;         // batch*2: dual, primal
-    std::vector<int> h_basis_in;            // batch*m
-    bool ran = false;                       // a run completed: lp_batched_duals / _ranging / _certificates have final bases to read
 };

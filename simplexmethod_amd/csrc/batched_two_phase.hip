@@ -28,7 +28,7 @@
 //
 // FITS (the one predicate, lp_batched_two_phase_fits): lp_batched_two_phase_lds_bytes(m, n) <= 160 KB,
 // one CU's LDS.  Canonical 64 x 192 takes 104 KB.  Batches of shapes beyond it are solved by the
-// host with lp_simplex_two_phase, one LP after another (capi.hip).
+// host with lp_simplex_two_phase, one LP after another (batched_driver.hip).
 #include "device_select.hpp"
 #include "lp_internal.hpp"
 #include "batched_problem.hpp"

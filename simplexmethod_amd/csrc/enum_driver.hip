@@ -4,6 +4,7 @@
 // levels, enum_leaf.hip: leaves, enum_direct.hip: the direct kernel and the lists' tails); this file decides.
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 
 #include "enum_problem.hpp"
 #include "enum_tree.hpp"
@@ -580,47 +581,40 @@ int lp_enum_upload(lp_context* ctx, const double* A, int m, int n, const double*
     std::vector<unsigned long long> binom((size_t)(kEnumMaxN + 1) * kBinomK, 0ULL);
     for (int i = 0; i <= kEnumMaxN; ++i)
         for (int k = 0; k < kBinomK; ++k) binom[(size_t)i * kBinomK + k] = lp_host_binom(i, k);
-#define LP_TRY(expr)                        \
-    do {                                    \
-        hipError_t _e = (expr);             \
-        if (_e != hipSuccess) {             \
-            ctx->last_error = #expr;        \
-            lp_enum_free(p);                \
-            return -(int)_e;                \
-        }                                   \
-    } while (0)
+    // (a failed call below frees p with what it holds so far: p->complete is still false)
+    std::unique_ptr<lp_enum_problem, void (*)(lp_enum_problem*)> owner(p, lp_enum_free);
     hipStream_t s = ctx->stream;
     if (fresh) {   // sized for the largest shape (m <= 32, n <= 64): a shell serves any later problem
-        LP_TRY(hipMalloc(&p->dA, sizeof(double) * (size_t)kEnumMaxM * (kEnumMaxN + 1)));
-        LP_TRY(hipMalloc(&p->db, sizeof(double) * (size_t)kEnumMaxM));
-        LP_TRY(hipMalloc(&p->dc, sizeof(double) * (size_t)kEnumMaxN));
-        LP_TRY(hipMalloc(&p->dbinom, sizeof(unsigned long long) * binom.size()));
-        LP_TRY(hipMalloc(&p->d_pass, sizeof(EnumPassBlock)));
+        LP_HIP(ctx, hipMalloc(&p->dA, sizeof(double) * (size_t)kEnumMaxM * (kEnumMaxN + 1)));
+        LP_HIP(ctx, hipMalloc(&p->db, sizeof(double) * (size_t)kEnumMaxM));
+        LP_HIP(ctx, hipMalloc(&p->dc, sizeof(double) * (size_t)kEnumMaxN));
+        LP_HIP(ctx, hipMalloc(&p->dbinom, sizeof(unsigned long long) * binom.size()));
+        LP_HIP(ctx, hipMalloc(&p->d_pass, sizeof(EnumPassBlock)));
         d.result = &p->d_pass->result;
-        LP_TRY(hipMalloc(&d.chunk_best, sizeof(double) * (size_t)(p->chunk_cap + 64)));
-        LP_TRY(hipMalloc(&p->dvx, sizeof(double) * (kEnumMaxM + 1)));
-        LP_TRY(hipMalloc(&p->dvi, sizeof(int) * (kEnumMaxM + 1)));
-        LP_TRY(hipHostMalloc(&p->h_pass, sizeof(EnumPassBlock)));
+        LP_HIP(ctx, hipMalloc(&d.chunk_best, sizeof(double) * (size_t)(p->chunk_cap + 64)));
+        LP_HIP(ctx, hipMalloc(&p->dvx, sizeof(double) * (kEnumMaxM + 1)));
+        LP_HIP(ctx, hipMalloc(&p->dvi, sizeof(int) * (kEnumMaxM + 1)));
+        LP_HIP(ctx, hipHostMalloc(&p->h_pass, sizeof(EnumPassBlock)));
         std::memset(p->h_pass, 0, sizeof(EnumPassBlock));
         p->h_result = &p->h_pass->result;
         p->h_list_count = &p->h_pass->list_count;
         p->h_overflow = &p->h_pass->overflow;
         p->h_level_counts = p->h_pass->level_counts;
-        LP_TRY(hipEventCreate(&p->ev0));
-        LP_TRY(hipEventCreate(&p->ev1));
-        LP_TRY(hipMemcpyAsync(p->dbinom, binom.data(), sizeof(unsigned long long) * binom.size(),
-                              hipMemcpyHostToDevice, s));
+        LP_HIP(ctx, hipEventCreate(&p->ev0));
+        LP_HIP(ctx, hipEventCreate(&p->ev1));
+        LP_HIP(ctx, hipMemcpyAsync(p->dbinom, binom.data(), sizeof(unsigned long long) * binom.size(),
+                                   hipMemcpyHostToDevice, s));
     }
-    LP_TRY(hipMemcpyAsync(p->dA, Arow.data(), sizeof(double) * Arow.size(), hipMemcpyHostToDevice, s));
-    LP_TRY(hipMemcpyAsync(p->db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-    LP_TRY(hipMemcpyAsync(p->dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(p->dA, Arow.data(), sizeof(double) * Arow.size(), hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(p->db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(p->dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     if (fresh) {   // shared-prefix path: small control words, the feasible list
         PrefixDev& pd = p->prefix;
         pd.level_counts = p->d_pass->level_counts;
-        LP_TRY(hipMalloc(&pd.item_count, 2 * sizeof(int)));
+        LP_HIP(ctx, hipMalloc(&pd.item_count, 2 * sizeof(int)));
         pd.overflow = &p->d_pass->overflow;
-        LP_TRY(hipMalloc(&pd.root_cursor, 2 * sizeof(int)));
-        LP_TRY(enum_list_alloc(p, knobs.list_cap));
+        LP_HIP(ctx, hipMalloc(&pd.root_cursor, 2 * sizeof(int)));
+        LP_HIP(ctx, enum_list_alloc(p, knobs.list_cap));
         pd.list_count = &p->d_pass->list_count;
         if (!ctx->dcomb6 || !ctx->dcomb5 || !ctx->dcomb4) {   // (shape-independent: once per context)
             // the leaf kernels' 6-, 5- and 4-subsets of up to 22, 21 and 20 columns (first, second, third level)
@@ -628,23 +622,22 @@ int lp_enum_upload(lp_context* ctx, const double* A, int m, int n, const double*
             std::vector<unsigned> tab[3];
             for (int i = 0; i < 3; ++i) {
                 tab[i] = subset_table(6 - i, 22 - i);
-                LP_TRY(hipMalloc(dtab[i], sizeof(unsigned) * tab[i].size()));
-                LP_TRY(hipMemcpyAsync(*dtab[i], tab[i].data(), sizeof(unsigned) * tab[i].size(), hipMemcpyHostToDevice, s));
+                LP_HIP(ctx, hipMalloc(dtab[i], sizeof(unsigned) * tab[i].size()));
+                LP_HIP(ctx, hipMemcpyAsync(*dtab[i], tab[i].data(), sizeof(unsigned) * tab[i].size(), hipMemcpyHostToDevice, s));
             }
-            LP_TRY(hipStreamSynchronize(s));  // the tables are locals
+            LP_HIP(ctx, hipStreamSynchronize(s));  // the tables are locals
         }
         pd.comb6 = ctx->dcomb6;
         pd.comb5 = ctx->dcomb5;
         pd.comb4 = ctx->dcomb4;
     }
-    LP_TRY(hipStreamSynchronize(s));
-#undef LP_TRY
+    LP_HIP(ctx, hipStreamSynchronize(s));
     d.A = p->dA;
     d.b = p->db;
     d.c = p->dc;
     d.binom = p->dbinom;
     p->complete = true;
-    *problem_out = p;
+    *problem_out = owner.release();
     return LP_OPTIMAL;
 }
 

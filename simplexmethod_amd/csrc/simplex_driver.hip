@@ -747,7 +747,7 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
             rc = lp_simplex_download(p, x_out, N.data(), obj_out, nullptr, nullptr, 0, nullptr);
         else if (rc > 0)
             (void)lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
-    } else if (rc == LP_SINGULAR || rc == LP_INFEASIBLE) {
+    } else if (rc > 0) {   // (phase I's iteration limit too: the basis reached, as the batched kernel reports it)
         (void)lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
     }
     stage("phase II download");

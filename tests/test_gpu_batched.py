@@ -5,7 +5,7 @@ import pytest
 
 from oracle import pyoracle as o
 from simplexmethod_amd import capi
-from tests import lpcases
+from tests import handlecases, lpcases
 
 pytestmark = pytest.mark.gpu
 
@@ -117,3 +117,47 @@ def test_fuzz_shapes_and_signed_data(ctx):
         max_iter = int(rng.choice([1, 3, 10000]))
         g = ctx.simplex_solve_batched(A, b, c, basis, maximize, n, max_iter=max_iter)
         _check(g, A, b, c, basis, maximize, n, max_iter=max_iter)
+
+
+def _general_batch(seeds, m, n):
+    """Non-slack starting bases (lpcases.general_lp): the per-LP fallback."""
+    probs = [lpcases.general_lp(s, m, n) for s in seeds]
+    return tuple(np.stack([q[i] for q in probs]) for i in range(4))
+
+
+def test_fallback_handle_rerun(ctx):
+    """State kept between the runs of one fallback handle: run, download, run, download."""
+    A, b, c, basis = _general_batch(range(12), 10, 24)
+    n = A.shape[2]
+    p = ctx.batched_problem(A, b, c, basis, True, n)
+    try:
+        assert p.path() == 0
+        for g in handlecases.run_twice(p):
+            _check(g, A, b, c, basis, True, n)
+    finally:
+        p.free()
+
+
+@pytest.mark.parametrize("path,limit", [(1, 11), (0, 8)])
+def test_handle_limit_then_rerun(ctx, path, limit):
+    """A limit that stops some LPs of the batch and not others, then the default limit and the first limit again on
+    the same handle; x and obj of the stopped LPs stay unwritten.  Resident: capi.gen_lp(s, 32, 64), 6 to 21 pivots;
+    fallback: general_lp(s, 10, 24), 5 to 10."""
+    if path:
+        A, b, c, basis = _batch(range(12), 32, 64)
+        no = 32
+    else:
+        A, b, c, basis = _general_batch(range(12), 10, 24)
+        no = A.shape[2]
+    limited = {o.simplex_tableau(A[k], b[k], c[k], basis[k], True, no, max_iter=limit)["status"] for k in range(12)}
+    assert limited == {o.OPTIMAL, o.ITER_LIMIT}
+    p = ctx.batched_problem(A, b, c, basis, True, no)
+    try:
+        assert p.path() == path
+        first, second, third = handlecases.limit_default_limit(p, limit)
+    finally:
+        p.free()
+    _check(first, A, b, c, basis, True, no, max_iter=limit)
+    _check(second, A, b, c, basis, True, no)
+    _check(third, A, b, c, basis, True, no, max_iter=limit)
+    assert (second["status"] == o.OPTIMAL).all()

@@ -9,7 +9,7 @@ import pytest
 
 from oracle import pyoracle as o
 from simplexmethod_amd import capi
-from tests import lpcases
+from tests import handlecases, lpcases
 
 pytestmark = pytest.mark.gpu
 
@@ -174,3 +174,40 @@ def test_handle_rerun_iters_and_shards(ctx):
         assert np.array_equal(np.concatenate([q[key] for q in parts]), whole[key], equal_nan=True), key
     assert np.array_equal(whole["iters"], it_first)
     _assert_same(whole, _oracle(cases))
+
+
+def test_fallback_handle_rerun(ctx):
+    """State kept between the runs of one fallback handle: run, download, run, download."""
+    cases = [lpcases.min_lp(seed, 128, 128) for seed in range(3)]
+    A, b, c = _stack(cases)
+    p = ctx.batched_two_phase_problem(A, b, c, n_orig=128)
+    try:
+        assert p.path() == 0
+        for g in handlecases.run_twice(p, p.phase_iters):
+            _assert_same(g, _oracle(cases))
+    finally:
+        p.free()
+
+
+@pytest.mark.parametrize("path,limit", [(1, 18), (0, 450)])
+def test_handle_limit_then_rerun(ctx, path, limit):
+    """A per-phase limit that stops some LPs of the batch and not others, then the default limit and the first limit
+    again on the same handle; x and obj of the stopped LPs stay unwritten.  Resident: 16 x 32 + 16, phase I takes 16
+    to 23 pivots; fallback: 128 x 128 + 128, phase I takes 329 to 508."""
+    if path:
+        cases = [lpcases.min_lp(seed, 16, 32, equalities=seed % 3, negative_rows=seed % 4) for seed in range(12)]
+    else:
+        cases = [lpcases.min_lp(seed, 128, 128) for seed in range(6)]
+    limited, full = _oracle(cases, max_iter=limit), _oracle(cases)
+    assert {r["status"] for r in limited} == {o.OPTIMAL, o.ITER_LIMIT}
+    assert all(r["status"] == o.OPTIMAL for r in full)
+    A, b, c = _stack(cases)
+    p = ctx.batched_two_phase_problem(A, b, c, n_orig=cases[0][3])
+    try:
+        assert p.path() == path
+        first, second, third = handlecases.limit_default_limit(p, limit, p.phase_iters)
+    finally:
+        p.free()
+    _assert_same(first, limited)
+    _assert_same(second, full)
+    _assert_same(third, limited)

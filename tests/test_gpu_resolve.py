@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from simplexmethod_amd import capi
-from tests import lpcases
+from tests import handlecases, lpcases
 from tests import resolve_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +118,25 @@ def test_batched_fallback_shape(ctx):
     A, b2, c, B = _perturbed(ctx, 5, 128, 256, 31)
     refs = _refs(A, b2, c, B)
     _assert_same(_solve(ctx, A, b2, c, B, want_path=0), refs)
+
+
+@pytest.mark.parametrize("path,batch,m,n,seed0,limit", [(1, 12, 32, 96, 4242, 8), (0, 6, 128, 256, 31, 20)])
+def test_handle_limit_then_rerun(ctx, path, batch, m, n, seed0, limit):
+    """A limit that stops some LPs of the batch and not others, then the default limit and the first limit again on
+    the same handle; x and obj of the stopped LPs stay unwritten.  Resident: 0 to 22 dual pivots; fallback: 1 to 56."""
+    A, b2, c, B = _perturbed(ctx, batch, m, n, seed0)
+    limited, full = _refs(A, b2, c, B, max_iter=limit), _refs(A, b2, c, B)
+    assert {r["status"] for r in limited} == {capi.OPTIMAL, capi.ITER_LIMIT}
+    assert all(r["status"] == capi.OPTIMAL for r in full)
+    p = ctx.batched_resolve_problem(A, b2, c, B)
+    try:
+        assert p.path() == path
+        first, second, third = handlecases.limit_default_limit(p, limit, p.resolve_iters)
+    finally:
+        p.free()
+    _assert_same(first, limited)
+    _assert_same(second, full)
+    _assert_same(third, limited)
 
 
 @pytest.mark.parametrize("m,n", [(32, 96), (128, 256)])

@@ -128,6 +128,19 @@ def test_gpu_bit_exact_vs_oracle(ctx, seed, m, k, eq, neg, zr):
 
 
 @gpu
+@pytest.mark.parametrize("limit", [5, 12])
+def test_gpu_phase_one_limit_reports_the_basis_reached(ctx, limit):
+    """Phase I takes 16 pivots here: a lower limit ends it with LP_ITER_LIMIT, and basis_out is the basis it had
+    reached (artificials n + i among it), not the identity it started from."""
+    A, b, c, no = lpcases.min_lp(3, 16, 12, equalities=3, negative_rows=4, zero_rhs=2)
+    r = o.two_phase(A, b, c, maximize=False, n_orig=no, max_iter=limit)
+    assert r["status"] == o.ITER_LIMIT and list(r["iters"]) == [limit, 0, 0]
+    g = ctx.two_phase(A, b, c, maximize=False, n_orig=no, max_iter=limit)
+    _same(g, r)
+    assert np.array_equal(g["basis"], r["basis"])
+
+
+@gpu
 def test_gpu_corner_shapes(ctx):
     """One row; every row negated; a maximisation (bounded: negative costs); equality rows only."""
     cases = []
