@@ -560,6 +560,29 @@ int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int 
  * does), 0 otherwise.  A host call: no context, no device.                                                      */
 int lp_simplex_bounded_fits(int m, int n);
 
+/* ---- Bounded variables: the re-solve from a basis -------------------------------------------------------------
+ * The LP of lp_simplex_bounded re-solved from basis_in (m, by position, every index in [0, n)) and at_upper_in (n,
+ * 0/1), normally the basis_out and at_upper_out of an earlier solve, after a change of lo, hi, b or c (DESIGN.md
+ * §4.5k; the definition is tests/ref/bounded_resolve_ref.c).  Under any change of lo, hi or b an optimal basis stays
+ * dual feasible, so tightening a bound costs a few dual pivots instead of a two-phase solve.  The tableau is built on
+ * the shifted variables with every flagged column held complemented, the basis is installed by lp_simplex_resolve's
+ * crash (LP_SINGULAR: the given basis and flags are returned), and then:
+ *   - no basic variable below its lower or above its finite upper bound by more than eps: the bounded primal loop of
+ *     lp_simplex_bounded's phase II (pivots and bound flips; max_iter bounds their sum);
+ *   - else, no reduced cost of the wrong sign beyond eps: the bounded dual simplex.  The leaving position is the most
+ *     violated one (a variable above its upper bound is complemented first and leaves at that bound), the entering
+ *     column lp_simplex_resolve's dual ratio test; no entering column: LP_INFEASIBLE.  max_iter bounds the dual pivots;
+ *   - else LP_BAD_ARG: the basis is no valid start (in a batch: that LP's status, the others are solved).
+ * An LP with some hi_j < lo_j is LP_INFEASIBLE with zero counters and the given basis and flags.  LP_BAD_ARG also for a
+ * basis index outside [0, n), a flag that is not 0 or 1, a flag on a column with hi_j = +inf, and everything
+ * lp_simplex_bounded refuses (in a batch these refuse the whole call).  Outputs as lp_simplex_bounded, except
+ * iters_out[3] = dual pivots, primal pivots, bound flips (the crash is not counted).  With lo = 0, hi = +inf and no
+ * flag the result is lp_simplex_resolve_batched's.  Shapes: lp_simplex_bounded_fits.                                */
+int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
+/* A batch of LPs of one shape: arrays as lp_simplex_bounded_batched, basis_in batch*m, at_upper_in batch*n, iters_out
+ * batch*3.                                                                                                        */
+int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out);
+
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec
  * README.md:27,40-42; per-basis kernel = Canonical::GetBasicSolution /

@@ -317,6 +317,27 @@ def build_bounded_ref(force=False, verbose=False):
     return BOUNDED_REF_LIB
 
 
+BOUNDED_RESOLVE_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_resolve_ref.so")
+
+
+def build_bounded_resolve_ref(force=False, verbose=False):
+    """tests/ref/bounded_resolve_ref.c (which includes bounded_ref.c) -> tests/ref/_build/libbounded_resolve_ref.so:
+    the bounded-variable re-solve from a given basis the tests compare against; flags as build_bounded_ref."""
+    src = os.path.join(TESTS_REF, "bounded_resolve_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "bounded_ref.c")]
+    if not force and _newer(BOUNDED_RESOLVE_REF_LIB, deps):
+        return BOUNDED_RESOLVE_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_RESOLVE_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_RESOLVE_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_RESOLVE_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -329,6 +350,7 @@ def build_all(force=False, verbose=False):
     build_parametric_cost_ref(force, verbose)
     build_mip_ref(force, verbose)
     build_bounded_ref(force, verbose)
+    build_bounded_resolve_ref(force, verbose)
     return hip, host
 
 

@@ -144,6 +144,11 @@ SIGNATURES = {
     "lp_simplex_bounded_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                              C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, _ip]),
     "lp_simplex_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int,
+                                             C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
+    "lp_simplex_bounded_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                     C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip,
+                                                     _ip]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -699,6 +704,60 @@ class Context:
     def bounded_fits(self, m, n):
         """lp_simplex_bounded_fits: True if an m x n bounded LP fits one CU's LDS."""
         return bool(self.lib.lp_simplex_bounded_fits(m, n))
+
+    def bounded_resolve(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
+                        max_iter=MAX_ITER):
+        """lp_simplex_bounded_resolve: the LP of bounded() re-solved from `basis` (m) and `at_upper` (n, 0/1), normally
+        an earlier result's, after a change of lo, hi, b or c: the bounded primal loop if the basis is primal feasible,
+        the bounded dual simplex if it is only dual feasible.  dict as bounded() with iters = (dual pivots, primal
+        pivots, bound flips).  A basis that is neither, a bad index or flag, a bad bound or a shape beyond bounded_fits
+        raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
+        if basis.size != m or at_upper.size != n:
+            raise ValueError("basis must have m and at_upper n entries")
+        x = np.full(n_orig, np.nan)
+        bo = np.full(m, -1, dtype=np.int32)
+        up = np.zeros(n, dtype=np.int32)
+        obj = np.full(1, np.nan)
+        it = np.zeros(3, dtype=np.int32)
+        rc = self.check(self.lib.lp_simplex_bounded_resolve(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                            _i(basis), _i(at_upper), int(maximize), n_orig, float(eps),
+                                                            int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it)))
+        return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
+
+    def bounded_resolve_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
+                                max_iter=MAX_ITER):
+        """lp_simplex_bounded_resolve_batched: arrays as bounded_batched(), basis (batch, m), at_upper (batch, n).
+        dict as bounded_batched() with iters (batch, 3); per LP exactly bounded_resolve(), except that a basis that
+        is no valid start is that LP's status BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
+        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
+            raise ValueError("b, c, lo, hi must have batch*m, batch*n entries")
+        if basis.size != batch * m or at_upper.size != batch * n:
+            raise ValueError("basis, at_upper must have batch*m, batch*n entries")
+        x = np.full((batch, n_orig), np.nan)
+        bo = np.full((batch, m), -1, dtype=np.int32)
+        up = np.zeros((batch, n), dtype=np.int32)
+        obj = np.full(batch, np.nan)
+        it = np.zeros((batch, 3), dtype=np.int32)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_simplex_bounded_resolve_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                               _i(basis), _i(at_upper), int(maximize), n_orig,
+                                                               float(eps), int(max_iter), _d(x), _i(bo), _i(up),
+                                                               _d(obj), _i(it), _i(st)))
+        return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
     def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):

@@ -1,0 +1,192 @@
+// batched_bounded_resolve.hip — many bounded-variable LPs of one shape RE-SOLVED FROM GIVEN BASES AND COMPLEMENT
+// FLAGS, ONE LP PER WORKGROUP.
+//
+// The case of a branch, a fixing or a what-if on an LP that lp_simplex_bounded has solved: under any change of lo, hi
+// or b the old optimal basis stays dual feasible, so a few dual pivots replace the two-phase solve.  Each workgroup
+// runs tests/ref/bounded_resolve_ref.c for its LP:
+//   - the tableau [A | b'; c | 0] of the shifted variables x' = x - lo with every flagged column held complemented
+//     (-A_ij, -c_j); b' is one serial fma chain per row, over the columns with lo_j != 0 and then over the flagged ones;
+//   - the basis installed by batched_resolve_crash.hpp (skipped for the slack identity with zero costs);
+//   - classify: a position is violated below (xB_t < -eps) or above (U finite, U - xB_t < -eps).  None violated: the
+//     bounded primal loop (batched_bounded_loop.hpp, phase-II form); else no slot of a variable < n with d > eps (max)
+//     / d < -eps (min): the bounded dual loop (batched_bounded_dual_loop.hpp); else LP_BAD_ARG for this LP.
+// hi < lo in some column (U_j < 0, see batched_bounded.hip) ends the LP LP_INFEASIBLE before the crash.
+//
+// Layout and FITS: batched_bounded.hip's (batched_bounded_carve.hpp, lp_simplex_bounded_fits); the basis and the
+// flags are read from HBM.  After the crash the lcol buffer holds the row permutation until the rows are in position
+// order.  There is no host fallback: larger shapes get LP_BAD_ARG.
+#include <cfloat>
+#include <climits>
+
+#include "device_select.hpp"
+#include "lp_internal.hpp"
+#include "batched_problem.hpp"
+#include "batched_scan.hpp"
+#include "batched_bounded_carve.hpp"
+
+namespace {
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve(BatchedBoundedResolveDev d) {
+    constexpr bool BLAND = false;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    char* base = reinterpret_cast<char*>(smem);
+    const int m = d.m, n = d.n, W = n + 1;
+    const BoundedCarve K = bounded_carve(m, n);
+    const int pitch = K.pitch;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int lp = blockIdx.x;
+    // ---- LDS carve
+    Published* pubs = reinterpret_cast<Published*>(smem);
+    double* T = reinterpret_cast<double*>(base + K.T);
+    double* prow = reinterpret_cast<double*>(base + K.prow);
+    double* lcol = reinterpret_cast<double*>(base + K.lcol);
+    double* U = reinterpret_cast<double*>(base + K.U);
+    double* lov = reinterpret_cast<double*>(base + K.lov);
+    int* slotvar = reinterpret_cast<int*>(base + K.slotvar);
+    int* basis = reinterpret_cast<int*>(base + K.basis);
+    int* up = reinterpret_cast<int*>(base + K.up);
+    int* pub = pubs->v;   // [0] entering slot / crash row, [1] leaving position, [2] action / verdict, [3] block_any
+
+    const double* A = d.A + (size_t)lp * m * n;
+    const double* b = d.b + (size_t)lp * m;
+    const double* c = d.c + (size_t)lp * n;
+    const double* lo = d.lo + (size_t)lp * n;
+    const double* hi = d.hi + (size_t)lp * n;
+    const int* N = d.basis_in + (size_t)lp * m;
+    const int* upin = d.at_upper_in + (size_t)lp * n;
+    const double eps = d.eps;
+    const bool maximize = d.maximize != 0;
+    // block-wide OR through pub[3] (batched_resolve.hip)
+    auto block_any = [&](int flag) {
+        if (tid == 0) pub[3] = 0;
+        __syncthreads();
+        if (flag) pub[3] = 1;
+        __syncthreads();
+        const bool any = pub[3] != 0;
+        __syncthreads();
+        return any;
+    };
+
+    // ---- load: slots = the columns in order (a flagged one sign-changed, cost included), basis = the artificials
+    int bad = 0;
+    for (int s = tid; s < n; s += NT) {
+        const double l = lo[s], u = hi[s] - l;
+        const int f = upin[s];
+        slotvar[s] = s;
+        up[s] = f;
+        lov[s] = l;
+        U[s] = u;
+        T[(size_t)m * pitch + s] = f ? -c[s] : c[s];
+        if (u < 0.0) bad = 1;
+    }
+    if (tid == 0) T[(size_t)m * pitch + n] = 0.0;
+    for (int t = tid; t < m; t += NT) basis[t] = n + t;
+    for (int e = tid; e < m * n; e += NT) {   // coalesced along the rows of a column
+        const int s = e / m, i = e - s * m;
+        const double a = A[e];
+        T[(size_t)i * pitch + s] = upin[s] ? -a : a;
+    }
+    const bool crossed = block_any(bad);
+    // ---- b' (one chain per row): the shift over lo_j != 0, then the complements over the flagged columns
+    if (!crossed) {
+        for (int i = tid; i < m; i += NT) {
+            const double* row = T + (size_t)i * pitch;
+            double acc = b[i];
+            for (int j = 0; j < n; ++j) {
+                const double l = lov[j];
+                if (l != 0.0) acc = fma(up[j] ? row[j] : -row[j], l, acc);   // (-A_ij: a flagged slot holds it)
+            }
+            for (int j = 0; j < n; ++j)
+                if (up[j]) acc = fma(row[j], U[j], acc);
+            T[(size_t)i * pitch + n] = acc;
+        }
+    }
+    // the crash is skipped when the basic columns, as loaded, are the unit vectors in order and their costs are zero
+    int not_identity = 0;
+    if (!crossed) {
+        for (int e = tid; e < m * m; e += NT) {
+            const int t = e / m, i = e - t * m;
+            if (T[(size_t)i * pitch + N[t]] != ((i == t) ? 1.0 : 0.0)) not_identity = 1;
+        }
+        for (int t = tid; t < m; t += NT)
+            if (T[(size_t)m * pitch + N[t]] != 0.0) not_identity = 1;
+    }
+    const bool identity = !block_any(not_identity);
+
+    // ---- pivot(r, se); the bounded primal loop; the bounded dual loop
+#include "batched_lds_loop.hpp"
+#include "batched_bounded_loop.hpp"
+#include "batched_bounded_dual_loop.hpp"
+    (void)simplex;   // (batched_lds_loop.hpp's unbounded loop: only its pivot is used here)
+
+    int it[3] = {0, 0, 0};   // dual pivots, primal pivots, bound flips
+    int status = crossed ? LP_INFEASIBLE : LP_OPTIMAL;
+    if (!crossed) {
+#include "batched_resolve_crash.hpp"
+    }
+    if (!crossed && status == LP_OPTIMAL) {
+        // ---- classification: two block reductions over the crashed tableau
+        int pinf = 0, dinf = 0;
+        for (int t = tid; t < m; t += NT) {
+            const double xb = T[(size_t)t * pitch + n], u = U[basis[t]];
+            if (xb < -eps || (u < INFINITY && u - xb < -eps)) pinf = 1;
+        }
+        const double* drow = T + (size_t)m * pitch;
+        for (int s = tid; s < n; s += NT)
+            if (slotvar[s] < n && (maximize ? (drow[s] > eps) : (drow[s] < -eps))) dinf = 1;
+        const bool violated = block_any(pinf);
+        const bool dual_feasible = !block_any(dinf);
+        if (!violated)
+            status = bounded_simplex(true, maximize, it[1], it[2]);   // artificial slots barred
+        else if (dual_feasible)
+            status = bounded_dual(it[0]);
+        else
+            status = LP_BAD_ARG;
+        __syncthreads();
+    }
+    // ---- outputs as batched_bounded.hip: x for LP_OPTIMAL; basis, flags and counters always (the given basis when
+    // the crash failed or some hi < lo: the flags are the given ones then)
+    if (status == LP_OPTIMAL) {
+        for (int j = tid; j < n; j += NT) prow[j] = 0.0;
+        __syncthreads();
+        for (int t = tid; t < m; t += NT)
+            if (basis[t] < n) prow[basis[t]] = T[(size_t)t * pitch + n];
+        __syncthreads();
+        double* x = d.x + (size_t)lp * n;
+        for (int j = tid; j < n; j += NT) {
+            const double v = prow[j];
+            const double w = up[j] ? U[j] - v : v;
+            x[j] = lov[j] == 0.0 ? w : lov[j] + w;
+        }
+    }
+    const bool given = crossed || status == LP_SINGULAR;
+    for (int t = tid; t < m; t += NT) d.basis_out[(size_t)lp * m + t] = given ? N[t] : basis[t];
+    for (int j = tid; j < n; j += NT) d.at_upper[(size_t)lp * n + j] = up[j];
+    if (tid == 0) {
+        int* io = d.iters + (size_t)lp * 3;
+        io[0] = it[0];
+        io[1] = it[1];
+        io[2] = it[2];
+        d.status[lp] = status;
+    }
+}
+
+template <int NT>
+int bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, size_t shm) {
+    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_bounded_resolve<NT>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_batched_bounded_resolve<NT>, d.batch, NT, shm, ctx->stream, d);
+    return LP_OPTIMAL;
+}
+
+}  // namespace
+
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d) {
+    if (!lp_bounded_fits_shape(d.m, d.n))
+        LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: the shape does not fit one CU's LDS");
+    const size_t shm = lp_bounded_lds_bytes(d.m, d.n, nullptr);
+    // block size as lp_batched_bounded_launch
+    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return bounded_resolve_launch<256>(ctx, d, shm);
+    return bounded_resolve_launch<1024>(ctx, d, shm);
+}

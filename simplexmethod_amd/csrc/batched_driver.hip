@@ -5,8 +5,9 @@
 // that is written once: batched_upload, run_resident / run_per_lp behind lp_batched_run, and lp_batched_download.
 // A resident handle runs one LP per workgroup; any other handle (a plain batch whose bases are not the slack
 // identity, a shape beyond one CU's LDS) goes through the single-LP entries of simplex_driver.hip one LP after
-// another and keeps each LP's results on the host.  The bounded-variable simplex (batched_bounded.hip) has no handle
-// and no fallback: bounded_solve uploads, launches and downloads in one call.
+// another and keeps each LP's results on the host.  The bounded-variable simplex (batched_bounded.hip) and its re-solve
+// from given bases (batched_bounded_resolve.hip) have no handle and no fallback: bounded_solve uploads, launches and
+// downloads in one call.
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -525,37 +526,47 @@ int lp_simplex_resolve_batched(lp_context* ctx, int batch, const double* A, int 
 }  // extern "C"
 
 // ===========================================================================
-// Bounded-variable simplex (batched_bounded.hip): one LP per workgroup for lp_simplex_bounded_fits shapes only; there
-// is no handle and no per-LP host fallback
+// Bounded-variable simplex (batched_bounded.hip) and its re-solve from given bases (batched_bounded_resolve.hip): one LP
+// per workgroup for lp_simplex_bounded_fits shapes only; there is no handle and no per-LP host fallback
 // ===========================================================================
 
-// The checks of both entry points: pointers, dimensions, the bounds of every LP (lo finite, hi not NaN) and the fit.
+// The checks of the entry points: pointers, dimensions, the bounds of every LP (lo finite, hi not NaN) and the fit; for
+// a re-solve (warm) also the start of every LP: basis indices in [0, n), flags 0 or 1, and 1 only under a finite hi.
 static int bounded_args(lp_context* ctx, const char* who, int batch, const double* A, int m, int n, const double* b,
-                        const double* c, const double* lo, const double* hi, int n_orig) {
-    if (!A || !b || !c || !lo || !hi) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+                        const double* c, const double* lo, const double* hi, int n_orig, bool warm = false,
+                        const int* basis_in = nullptr, const int* at_upper_in = nullptr) {
+    if (!A || !b || !c || !lo || !hi || (warm && (!basis_in || !at_upper_in)))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
     if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
     const size_t N = (size_t)batch * n;
     for (size_t j = 0; j < N; ++j) {
         if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
         if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
+        if (!warm) continue;
+        if (at_upper_in[j] != 0 && at_upper_in[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
+        if (at_upper_in[j] && std::isinf(hi[j]))
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
     }
+    for (size_t t = 0; warm && t < (size_t)batch * m; ++t)
+        if (basis_in[t] < 0 || basis_in[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
     if (!lp_bounded_fits_shape(m, n))
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_simplex_bounded_fits)");
     return LP_OPTIMAL;
 }
 
-// Uploads `batch` LPs, runs k_batched_bounded and downloads; x (n_orig) and obj (over all n columns, as
+// Uploads `batch` LPs, runs k_batched_bounded (basis_in null: 4 counters per LP) or k_batched_bounded_resolve (from
+// basis_in and at_upper_in: 3 counters per LP) and downloads; x (n_orig) and obj (over all n columns, as
 // lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.
 static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
-                         const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
-                         double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out,
-                         int* status_out) {
+                         const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
+                         int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
+                         double* obj_out, int* iters_out, int* status_out) {
     LP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch;
-    const size_t dbl = B * ((size_t)m * n + m + 4 * (size_t)n), ints = B * ((size_t)m + n + 4 + 1);
+    const size_t B = (size_t)batch, iw = basis_in ? 3 : 4;
+    const size_t dbl = B * ((size_t)m * n + m + 4 * (size_t)n), ints = B * ((basis_in ? 2 : 1) * ((size_t)m + n) + iw + 1);
     lp_device_buffer buf;
     LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * dbl + sizeof(int) * ints));
-    BatchedBoundedDev d{};
+    BatchedBoundedResolveDev d{};
     d.batch = batch;
     d.m = m;
     d.n = n;
@@ -577,7 +588,11 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     d.basis_out = reinterpret_cast<int*>(d.x + B * n);
     d.at_upper = d.basis_out + B * m;
     d.iters = d.at_upper + B * n;
-    d.status = d.iters + B * 4;
+    d.status = d.iters + B * iw;
+    int* dbasis_in = d.status + B;
+    int* dup_in = dbasis_in + B * m;
+    d.basis_in = dbasis_in;
+    d.at_upper_in = dup_in;
     std::vector<double> x(B * n);
     hipStream_t s = ctx->stream;
     hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
@@ -585,15 +600,17 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dlo, lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dhi, hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(dbasis_in, basis_in, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(dup_in, at_upper_in, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex upload: ") + hipGetErrorString(e));
-    int rc = lp_batched_bounded_launch(ctx, d);
+    int rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d) : lp_batched_bounded_launch(ctx, d);
     if (rc) return rc;
     e = hipGetLastError();
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex: ") + hipGetErrorString(e));
     rc = lp_download(ctx, "batched bounded simplex", {{x.data(), d.x, sizeof(double) * B * n},
                                                       {basis_out, d.basis_out, sizeof(int) * B * m},
                                                       {at_upper_out, d.at_upper, sizeof(int) * B * n},
-                                                      {iters_out, d.iters, sizeof(int) * B * 4},
+                                                      {iters_out, d.iters, sizeof(int) * B * iw},
                                                       {status_out, d.status, sizeof(int) * B}});
     if (rc) return rc;
     for (size_t k = 0; k < B; ++k)
@@ -615,8 +632,8 @@ int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const dou
     int rc = bounded_args(ctx, "lp_simplex_bounded", 1, A, m, n, b, c, lo, hi, n_orig);
     if (rc) return rc;
     int status = LP_OPTIMAL;
-    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out,
-                       obj_out, iters_out, &status);
+    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, nullptr, nullptr, maximize, n_orig, eps, max_iter, x_out, basis_out,
+                       at_upper_out, obj_out, iters_out, &status);
     return rc ? rc : status;
 }
 
@@ -631,8 +648,43 @@ int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int 
     if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
     const int rc = bounded_args(ctx, "lp_simplex_bounded_batched", batch, A, m, n, b, c, lo, hi, n_orig);
     if (rc) return rc;
-    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out,
-                         at_upper_out, obj_out, iters_out, status_out);
+    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, nullptr, nullptr, maximize, n_orig, eps, max_iter, x_out,
+                         basis_out, at_upper_out, obj_out, iters_out, status_out);
+}
+
+int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                               const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                               int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
+                               int* at_upper_out, double* obj_out, int* iters_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: eps must be >= 0");
+    int rc = bounded_args(ctx, "lp_simplex_bounded_resolve", 1, A, m, n, b, c, lo, hi, n_orig, true, basis_in, at_upper_in);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps, max_iter, x_out,
+                       basis_out, at_upper_out, obj_out, iters_out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: the basis is neither primal nor dual feasible");
+    return status;
+}
+
+int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                       const double* c, const double* lo, const double* hi, const int* basis_in,
+                                       const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
+                                       double* x_out, int* basis_out, int* at_upper_out, double* obj_out,
+                                       int* iters_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_batched: eps must be >= 0");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    const int rc = bounded_args(ctx, "lp_simplex_bounded_resolve_batched", batch, A, m, n, b, c, lo, hi, n_orig, true,
+                                basis_in, at_upper_in);
+    if (rc) return rc;
+    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps, max_iter, x_out,
+                         basis_out, at_upper_out, obj_out, iters_out, status_out);
 }
 
 }  // extern "C"

@@ -277,6 +277,17 @@ size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
 bool lp_bounded_fits_shape(int m, int n);
 int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
 
+// The same batch re-solved from given bases and complement flags, one LP per workgroup (batched_bounded_resolve.hip;
+// the definition is tests/ref/bounded_resolve_ref.c).  max_iter bounds the dual pivots, or the primal pivots plus
+// flips; iters is batch x 3 (dual pivots, primal pivots, bound flips).
+struct BatchedBoundedResolveDev : BatchedBoundedDev {
+    const int* basis_in;     // batch x m (by position), every index in [0, n)
+    const int* at_upper_in;  // batch x n (0/1; 1 only where hi is finite)
+};
+
+// batched_bounded_resolve.hip
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d);   // fitting shapes, else LP_BAD_ARG
+
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP
 // entry its per-LP fallback calls; everything else is the same for the three kinds.

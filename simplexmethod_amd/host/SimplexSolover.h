@@ -365,6 +365,35 @@ public:
         return out;
     }
 
+    // The same problem under the bounds lo, hi re-solved from the basis and flags of an earlier result
+    // (lp_simplex_bounded_resolve): the bounded primal loop if `from` is still primal feasible, the bounded dual
+    // simplex if it is only dual feasible, which it stays under any change of the bounds.  iterations = dual pivots,
+    // primal pivots, bound flips, 0.  Exceptions as boundedSimplex; a start that is neither primal nor dual feasible,
+    // a flag on a column without an upper bound or a basis index outside the columns throw std::invalid_argument.
+    BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
+                                 const BoundedResult& from, bool throw_on_failure = true) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedResolve: lo / hi size != cols(A)");
+        if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+            throw std::invalid_argument("Solver::boundedResolve: the start's basis / atUpper size != rows(A) / cols(A)");
+        BoundedResult out;
+        out.x = lpla::VectorXd::Zero(no);
+        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        out.basis.assign((size_t)m, -1);
+        out.atUpper.assign((size_t)n, 0);
+        lp_context* ctx = lpgpu::context(_device);
+        out.status = lp_simplex_bounded_resolve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                from.basis.data(), from.atUpper.data(),
+                                                _problem.IsMaximization() ? 1 : 0, no, EPS, MAX_ITER, out.x.data(),
+                                                out.basis.data(), out.atUpper.data(), &out.objective, out.iterations);
+        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        return out;
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
