@@ -583,6 +583,35 @@ int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, c
  * batch*3.                                                                                                        */
 int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out);
 
+/* ---- Bounded variables: branch-and-bound over the bounds ------------------------------------------------------
+ * The LP of lp_simplex_bounded with the columns j < n_orig of integer[j] = 1 integral (one mask of n entries for the
+ * whole batch), searched depth first from basis_in and at_upper_in, normally what lp_simplex_bounded returned
+ * (the definition is tests/ref/mip_bounded_ref.c).  A branch changes one bound (hi_j = floor(v) or
+ * lo_j = ceil(v)), so the tableau stays (m+1) x (n+1) at every depth, where lp_mip_solve appends a row and a slack per
+ * level.  The root is lp_simplex_bounded_resolve's result bit for bit.  The integrality test, the branching variable
+ * (most fractional, ties to the lowest index), the nearer side first and the pruning by gap are lp_mip_solve's.  The
+ * first child changes the bound on the parent's final tableau (one held value moves) and runs the bounded dual
+ * simplex; the second child is lp_simplex_bounded_resolve from the path's bounds and the basis and flags recorded when
+ * the level branched.
+ *   - LP_BAD_ARG for everything lp_simplex_bounded_resolve and lp_mip_solve refuse (max_depth in [0, 1024] here), and
+ *     for a marked column whose lo_j, or whose finite hi_j, is not an integer (in a batch these refuse the whole call);
+ *   - max_depth bounds the bound changes on a path (a fractional node there is abandoned), max_nodes (>= 1) the node
+ *     LP solves (the root is 1), max_iter each node's pivots plus bound flips; status, found_out, x_out, obj_out and
+ *     bound_out as lp_mip_solve.  A node LP that ends neither LP_OPTIMAL nor LP_INFEASIBLE stops the search with its
+ *     status;
+ *   - stats_out[5] = nodes solved, dual pivots, primal pivots, bound flips, deepest level (crash pivots not counted);
+ *   - only shapes with lp_mip_bounded_fits(m, n, max_depth) run: the others get LP_BAD_ARG.  There is no per-LP host
+ *     path.                                                                                                        */
+int lp_mip_bounded_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
+/* A batch of problems of one shape and one mask: arrays as lp_simplex_bounded_resolve_batched; outputs x_out
+ * batch*n_orig, obj_out / bound_out / found_out / status_out batch, stats_out batch*5.  root_status (batch ints, may
+ * be NULL) chains a cold lp_simplex_bounded_batched: an LP whose entry is not LP_OPTIMAL keeps that status, gets NaN /
+ * 0 outputs and no search (its basis and flags are not read by the search, but must pass the checks: give zeros).  */
+int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, const int* root_status, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out);
+/* 1: lp_simplex_bounded_fits' carve plus max_depth records of 24 + 4 m + 4 ceil(n / 32) bytes fits one CU's 160 KB and
+ * max_depth is in [0, 1024] (64 x 192 at depth 64, 32 x 96 at 256, 16 x 40 at 1024); 0 otherwise.  A host call.      */
+int lp_mip_bounded_fits(int m, int n, int max_depth);
+
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec
  * README.md:27,40-42; per-basis kernel = Canonical::GetBasicSolution /

@@ -338,6 +338,28 @@ def build_bounded_resolve_ref(force=False, verbose=False):
     return BOUNDED_RESOLVE_REF_LIB
 
 
+MIP_BOUNDED_REF_LIB = os.path.join(TESTS_REF, "_build", "libmip_bounded_ref.so")
+
+
+def build_mip_bounded_ref(force=False, verbose=False):
+    """tests/ref/mip_bounded_ref.c (which includes bounded_resolve_ref.c and bounded_ref.c) ->
+    tests/ref/_build/libmip_bounded_ref.so: the branch-and-bound over variable bounds the tests compare against; flags
+    as build_bounded_resolve_ref."""
+    src = os.path.join(TESTS_REF, "mip_bounded_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "bounded_resolve_ref.c"), os.path.join(TESTS_REF, "bounded_ref.c")]
+    if not force and _newer(MIP_BOUNDED_REF_LIB, deps):
+        return MIP_BOUNDED_REF_LIB
+    os.makedirs(os.path.dirname(MIP_BOUNDED_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", MIP_BOUNDED_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return MIP_BOUNDED_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -351,6 +373,7 @@ def build_all(force=False, verbose=False):
     build_mip_ref(force, verbose)
     build_bounded_ref(force, verbose)
     build_bounded_resolve_ref(force, verbose)
+    build_mip_bounded_ref(force, verbose)
     return hip, host
 
 

@@ -149,6 +149,13 @@ SIGNATURES = {
     "lp_simplex_bounded_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                      C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip,
                                                      _ip]),
+    "lp_mip_bounded_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int, _ip,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                       _ip, _ip]),
+    "lp_mip_bounded_solve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
+                                               C.c_int, C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
+                                               C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "lp_mip_bounded_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -294,11 +301,12 @@ INT_TOL = 1e-6    # branch-and-bound defaults: integrality tolerance, pruning ga
 GAP = 1e-9
 MAX_DEPTH = 32
 MAX_NODES = 100000
+MAX_DEPTH_BOUNDED = 64   # the bounded search keeps no tableau rows per level
 
 
-def _mip_out(batch, n_orig):
+def _mip_out(batch, n_orig, width=4):
     return (np.zeros((batch, n_orig)), np.zeros(batch), np.zeros(batch), np.zeros(batch, np.int32),
-            np.zeros((batch, 4), np.int32), np.zeros(batch, np.int32))
+            np.zeros((batch, width), np.int32), np.zeros(batch, np.int32))
 
 
 def _mip_dict(out):
@@ -758,6 +766,77 @@ class Context:
                                                                float(eps), int(max_iter), _d(x), _i(bo), _i(up),
                                                                _d(obj), _i(it), _i(st)))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
+
+    # ---- branch-and-bound over the bounds of a bounded-variable LP -----------------------------
+    def mip_bounded_solve(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,
+                          int_tol=INT_TOL, gap=GAP, max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES,
+                          max_iter=MAX_ITER):
+        """lp_mip_bounded_solve: opt c.x, A x = b, lo <= x <= hi, x_j integral where integer[j] (n entries, 0/1,
+        j < n_orig), searched by changing bounds from `basis` (m) and `at_upper` (n), normally bounded()'s result.
+        dict(status, found, x (n_orig), obj, bound, stats (nodes, dual pivots, primal pivots, bound flips, deepest
+        level)); x and obj NaN without an incumbent.  A start that is no valid one, a fractional bound on a marked
+        column, a bad argument or a shape beyond mip_bounded_fits raises LPError with code BAD_ARG."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
+        if basis.size != m or at_upper.size != n:
+            raise ValueError("basis must have m and at_upper n entries")
+        integer = _mask(integer, n)
+        x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5)
+        rc = self.check(self.lib.lp_mip_bounded_solve(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
+                                                      _i(at_upper), int(maximize), n_orig, _i(integer), float(eps),
+                                                      float(int_tol), float(gap), int(max_depth), int(max_nodes),
+                                                      int(max_iter), _d(x), _d(obj), _d(bound), _i(found), _i(stats)))
+        return dict(status=rc, found=int(found[0]), x=x[0], obj=float(obj[0]), bound=float(bound[0]),
+                    stats=tuple(int(v) for v in stats[0]))
+
+    def mip_bounded_solve_batched(self, A, b, c, lo, hi, integer, basis=None, at_upper=None, root_status=None,
+                                  maximize=True, n_orig=None, eps=EPS, int_tol=INT_TOL, gap=GAP,
+                                  max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES, max_iter=MAX_ITER):
+        """lp_mip_bounded_solve_batched: arrays as bounded_resolve_batched(), one mask (n); root_status (batch) or
+        None.  basis=None runs bounded_batched() first and searches from its bases and flags, its statuses passed as
+        root_status: an LP whose cold solve is not OPTIMAL keeps that status.  dict(status, found, obj, bound (batch),
+        x (batch, n_orig), stats (batch, 5))."""
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        if basis is None:
+            if at_upper is not None or root_status is not None:
+                raise ValueError("at_upper and root_status go with basis")
+            cold = self.bounded_batched(A, b, c, lo, hi, maximize, n_orig, eps, max_iter)
+            root_status = cold["status"]
+            ok = root_status == OPTIMAL   # (an unfinished LP's basis may hold artificials: not read, but checked)
+            basis = np.where(ok[:, None], cold["basis"], 0)
+            at_upper = np.where(ok[:, None], cold["at_upper"], 0)
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
+        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
+        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
+        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
+            raise ValueError("b, c, lo, hi must have batch*m, batch*n entries")
+        if basis.size != batch * m or at_upper.size != batch * n:
+            raise ValueError("basis, at_upper must have batch*m, batch*n entries")
+        if root_status is not None:
+            root_status = np.ascontiguousarray(root_status, dtype=np.int32).reshape(-1)
+            if root_status.size != batch:
+                raise ValueError("root_status must have batch entries")
+        integer = _mask(integer, n)
+        out = _mip_out(batch, n_orig, 5)
+        x, obj, bound, found, stats, st = out
+        self.check(self.lib.lp_mip_bounded_solve_batched(
+            self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
+            _i(root_status), int(maximize), n_orig, _i(integer), float(eps),
+            float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter), _d(x), _d(obj), _d(bound),
+            _i(found), _i(stats), _i(st)))
+        return _mip_dict(out)
+
+    def mip_bounded_fits(self, m, n, max_depth=MAX_DEPTH_BOUNDED):
+        """lp_mip_bounded_fits: True if an m x n bounded problem searched to max_depth fits one CU's LDS."""
+        return bool(self.lib.lp_mip_bounded_fits(m, n, max_depth))
 
     # ---- Farkas and unbounded-ray certificates at a basis -------------------------------------
     def basis_certificate(self, A, b, c, basis, maximize=True, eps=EPS):

@@ -780,12 +780,14 @@ int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_
 int lp_mip_fits(int m, int n, int max_depth) { return lp_mip_fits_shape(m, n, max_depth) ? 1 : 0; }
 
 
-// The search parameters and the mask (the basis and the problem arrays are checked by the callers).
-static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, const int* integer, double int_tol,
-                    double gap, int max_depth, int max_nodes) {
+}  // extern "C"
+
+// The search parameters and the mask, for both searches (max_depth in [0, depth_cap]).
+int lp_mip_check_search(lp_context* ctx, const char* who, int n, int n_orig, const int* integer, double int_tol,
+                        double gap, int max_depth, int depth_cap, int max_nodes) {
     if (!integer) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
-    if (max_depth < 0 || max_depth > LP_MIP_MAX_DEPTH)
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_depth must be in [0, 64]");
+    if (max_depth < 0 || max_depth > depth_cap)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_depth must be in [0, " + std::to_string(depth_cap) + "]");
     if (!(int_tol >= 0.0 && int_tol < 0.5)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": int_tol must be in [0, 0.5)");
     if (!(gap >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": gap must be >= 0");
     if (max_nodes < 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_nodes must be >= 1");
@@ -794,6 +796,16 @@ static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, 
         if (integer[j] && j >= n_orig)
             LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the mask marks a column beyond n_orig");
     }
+    return LP_OPTIMAL;
+}
+
+extern "C" {
+
+// The search parameters, the mask and the fit (the basis and the problem arrays are checked by the callers).
+static int mip_args(lp_context* ctx, const char* who, int m, int n, int n_orig, const int* integer, double int_tol,
+                    double gap, int max_depth, int max_nodes) {
+    const int rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_MAX_DEPTH, max_nodes);
+    if (rc) return rc;
     if (!lp_mip_fits_shape(m, n, max_depth))
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_mip_fits)");
     return LP_OPTIMAL;

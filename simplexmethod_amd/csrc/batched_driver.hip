@@ -7,7 +7,8 @@
 // identity, a shape beyond one CU's LDS) goes through the single-LP entries of simplex_driver.hip one LP after
 // another and keeps each LP's results on the host.  The bounded-variable simplex (batched_bounded.hip) and its re-solve
 // from given bases (batched_bounded_resolve.hip) have no handle and no fallback: bounded_solve uploads, launches and
-// downloads in one call.
+// downloads in one call; the branch-and-bound over the bounds (batched_mip_bounded.hip) does the same through
+// mip_bounded_solve and shares bounded_args and bounded_upload.
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -554,6 +555,45 @@ static int bounded_args(lp_context* ctx, const char* who, int batch, const doubl
     return LP_OPTIMAL;
 }
 
+// The inputs of `batch` bounded LPs on the device: one allocation, the doubles first.  out_d / out_i: room for the
+// caller's outputs (and further int inputs) behind them.
+struct BoundedInputs {
+    double *A, *b, *c, *lo, *hi, *out_d;
+    int *basis_in, *at_upper_in, *out_i;   // the first two: nullptr without a start
+};
+
+// Allocates and queues the uploads (the start too when basis_in is given); the launch that follows on the context's
+// stream orders itself behind them.
+static int bounded_upload(lp_context* ctx, lp_device_buffer& buf, int batch, const double* A, int m, int n,
+                          const double* b, const double* c, const double* lo, const double* hi, const int* basis_in,
+                          const int* at_upper_in, size_t out_doubles, size_t out_ints, BoundedInputs& in) {
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch;
+    const size_t dbl = B * ((size_t)m * n + m + 3 * (size_t)n) + out_doubles;
+    const size_t ints = (basis_in ? B * ((size_t)m + n) : 0) + out_ints;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * dbl + sizeof(int) * ints));
+    in.A = reinterpret_cast<double*>(buf.ptr);
+    in.b = in.A + B * m * n;
+    in.c = in.b + B * m;
+    in.lo = in.c + B * n;
+    in.hi = in.lo + B * n;
+    in.out_d = in.hi + B * n;
+    int* ip = reinterpret_cast<int*>(in.out_d + out_doubles);
+    in.basis_in = basis_in ? ip : nullptr;
+    in.at_upper_in = basis_in ? ip + B * m : nullptr;
+    in.out_i = basis_in ? ip + B * ((size_t)m + n) : ip;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(in.A, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(in.b, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(in.c, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(in.lo, lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(in.hi, hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(in.basis_in, basis_in, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(in.at_upper_in, at_upper_in, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex upload: ") + hipGetErrorString(e));
+    return LP_OPTIMAL;
+}
+
 // Uploads `batch` LPs, runs k_batched_bounded (basis_in null: 4 counters per LP) or k_batched_bounded_resolve (from
 // basis_in and at_upper_in: 3 counters per LP) and downloads; x (n_orig) and obj (over all n columns, as
 // lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.
@@ -561,11 +601,12 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
                          const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
                          int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
                          double* obj_out, int* iters_out, int* status_out) {
-    LP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, iw = basis_in ? 3 : 4;
-    const size_t dbl = B * ((size_t)m * n + m + 4 * (size_t)n), ints = B * ((basis_in ? 2 : 1) * ((size_t)m + n) + iw + 1);
     lp_device_buffer buf;
-    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * dbl + sizeof(int) * ints));
+    BoundedInputs in;
+    int rc = bounded_upload(ctx, buf, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, B * n,
+                            B * ((size_t)m + n + iw + 1), in);
+    if (rc) return rc;
     BatchedBoundedResolveDev d{};
     d.batch = batch;
     d.m = m;
@@ -574,38 +615,22 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     d.maximize = maximize ? 1 : 0;
     d.max_iter = max_iter;
     d.eps = eps;
-    double* dA = reinterpret_cast<double*>(buf.ptr);
-    double* db = dA + B * m * n;
-    double* dc = db + B * m;
-    double* dlo = dc + B * n;
-    double* dhi = dlo + B * n;
-    d.A = dA;
-    d.b = db;
-    d.c = dc;
-    d.lo = dlo;
-    d.hi = dhi;
-    d.x = dhi + B * n;
-    d.basis_out = reinterpret_cast<int*>(d.x + B * n);
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.lo = in.lo;
+    d.hi = in.hi;
+    d.x = in.out_d;
+    d.basis_out = in.out_i;
     d.at_upper = d.basis_out + B * m;
     d.iters = d.at_upper + B * n;
     d.status = d.iters + B * iw;
-    int* dbasis_in = d.status + B;
-    int* dup_in = dbasis_in + B * m;
-    d.basis_in = dbasis_in;
-    d.at_upper_in = dup_in;
+    d.basis_in = in.basis_in;
+    d.at_upper_in = in.at_upper_in;
     std::vector<double> x(B * n);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dA, A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dlo, lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dhi, hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(dbasis_in, basis_in, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && basis_in) e = hipMemcpyAsync(dup_in, at_upper_in, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex upload: ") + hipGetErrorString(e));
-    int rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d) : lp_batched_bounded_launch(ctx, d);
+    rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d) : lp_batched_bounded_launch(ctx, d);
     if (rc) return rc;
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex: ") + hipGetErrorString(e));
     rc = lp_download(ctx, "batched bounded simplex", {{x.data(), d.x, sizeof(double) * B * n},
                                                       {basis_out, d.basis_out, sizeof(int) * B * m},
@@ -616,6 +641,86 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     for (size_t k = 0; k < B; ++k)
         if (status_out[k] == LP_OPTIMAL) finish_x_obj(x.data() + k * n, c + k * n, n, n_orig, x_out + k * n_orig, obj_out + k);
     return LP_OPTIMAL;
+}
+
+// Branch-and-bound over the bounds (batched_mip_bounded.hip): the checks of the bounded re-solve and of the search
+// (lp_mip_check_search, basis_driver.hip), integral bounds on the marked columns, and the fit.
+static int mip_bounded_args(lp_context* ctx, const char* who, int batch, const double* A, int m, int n, const double* b,
+                            const double* c, const double* lo, const double* hi, const int* basis_in,
+                            const int* at_upper_in, int n_orig, const int* integer, double int_tol, double gap,
+                            int max_depth, int max_nodes) {
+    int rc = bounded_args(ctx, who, batch, A, m, n, b, c, lo, hi, n_orig, true, basis_in, at_upper_in);
+    if (rc) return rc;
+    rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_BOUNDED_MAX_DEPTH, max_nodes);
+    if (rc) return rc;
+    for (size_t k = 0; k < (size_t)batch; ++k)
+        for (int j = 0; j < n_orig; ++j) {
+            const double l = lo[k * n + j], h = hi[k * n + j];
+            if (integer[j] && (l != std::floor(l) || (std::isfinite(h) && h != std::floor(h))))
+                LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": an integer column has a fractional bound");
+        }
+    if (!lp_mip_bounded_fits_shape(m, n, max_depth))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_mip_bounded_fits)");
+    return LP_OPTIMAL;
+}
+
+// Uploads `batch` problems with their starts, the mask and root_status (may be null), runs k_batched_mip_bounded and
+// downloads.
+static int mip_bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                             const double* c, const double* lo, const double* hi, const int* basis_in,
+                             const int* at_upper_in, const int* root_status, int maximize, int n_orig,
+                             const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes,
+                             int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
+                             int* stats_out, int* status_out) {
+    const size_t B = (size_t)batch;
+    lp_device_buffer buf;
+    BoundedInputs in;
+    int rc = bounded_upload(ctx, buf, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, B * ((size_t)n_orig + 2),
+                            B * 8 + n, in);
+    if (rc) return rc;
+    BatchedMipBoundedDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.n_orig = n_orig;
+    d.maximize = maximize ? 1 : 0;
+    d.max_iter = max_iter;
+    d.max_depth = max_depth;
+    d.max_nodes = max_nodes;
+    d.eps = eps;
+    d.int_tol = int_tol;
+    d.gap = gap;
+    d.A = in.A;
+    d.b = in.b;
+    d.c = in.c;
+    d.lo = in.lo;
+    d.hi = in.hi;
+    d.basis_in = in.basis_in;
+    d.at_upper_in = in.at_upper_in;
+    d.x = in.out_d;
+    d.obj = d.x + B * n_orig;
+    d.bound = d.obj + B;
+    d.found = in.out_i;
+    d.stats = d.found + B;
+    d.status = d.stats + B * 5;
+    int* droot = d.status + B;
+    int* dmask = droot + B;
+    d.root_status = root_status ? droot : nullptr;
+    d.integer = dmask;
+    hipError_t e = hipMemcpyAsync(dmask, integer, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && root_status)
+        e = hipMemcpyAsync(droot, root_status, sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded MIP upload: ") + hipGetErrorString(e));
+    rc = lp_batched_mip_bounded_launch(ctx, d);
+    if (rc) return rc;
+    e = hipGetLastError();
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded MIP: ") + hipGetErrorString(e));
+    return lp_download(ctx, "batched bounded MIP", {{x_out, d.x, sizeof(double) * B * n_orig},
+                                                    {obj_out, d.obj, sizeof(double) * B},
+                                                    {bound_out, d.bound, sizeof(double) * B},
+                                                    {found_out, d.found, sizeof(int) * B},
+                                                    {stats_out, d.stats, sizeof(int) * B * 5},
+                                                    {status_out, d.status, sizeof(int) * B}});
 }
 
 extern "C" {
@@ -685,6 +790,48 @@ int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double*
     if (rc) return rc;
     return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps, max_iter, x_out,
                          basis_out, at_upper_out, obj_out, iters_out, status_out);
+}
+
+int lp_mip_bounded_fits(int m, int n, int max_depth) { return lp_mip_bounded_fits_shape(m, n, max_depth) ? 1 : 0; }
+
+int lp_mip_bounded_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                         const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
+                         int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth,
+                         int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out,
+                         int* found_out, int* stats_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: eps must be >= 0");
+    int rc = mip_bounded_args(ctx, "lp_mip_bounded_solve", 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in, n_orig,
+                              integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = mip_bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in, nullptr, maximize, n_orig, integer, eps,
+                           int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out,
+                           &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: the basis is neither primal nor dual feasible");
+    return status;
+}
+
+int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                 const double* c, const double* lo, const double* hi, const int* basis_in,
+                                 const int* at_upper_in, const int* root_status, int maximize, int n_orig,
+                                 const int* integer, double eps, double int_tol, double gap, int max_depth,
+                                 int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out,
+                                 int* found_out, int* stats_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_batched: null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_batched: eps must be >= 0");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    const int rc = mip_bounded_args(ctx, "lp_mip_bounded_solve_batched", batch, A, m, n, b, c, lo, hi, basis_in,
+                                    at_upper_in, n_orig, integer, int_tol, gap, max_depth, max_nodes);
+    if (rc) return rc;
+    return mip_bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, root_status, maximize, n_orig,
+                             integer, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out,
+                             found_out, stats_out, status_out);
 }
 
 }  // extern "C"

@@ -251,6 +251,9 @@ struct BatchedMipDev {
 size_t lp_mip_lds_bytes(int m, int n, int max_depth);
 bool lp_mip_fits_shape(int m, int n, int max_depth);
 int lp_batched_mip_launch(lp_context* ctx, const BatchedMipDev& d);   // fitting shapes, else LP_BAD_ARG
+// basis_driver.hip: the checks both searches share (the mask, int_tol, gap, max_nodes, max_depth in [0, depth_cap])
+int lp_mip_check_search(lp_context* ctx, const char* who, int n, int n_orig, const int* integer, double int_tol,
+                        double gap, int max_depth, int depth_cap, int max_nodes);
 
 // A batch of same-shape LPs with variable bounds lo <= x <= hi solved by the two-phase bounded-variable simplex, one LP
 // per workgroup (batched_bounded.hip; the definition is tests/ref/bounded_ref.c).
@@ -287,6 +290,39 @@ struct BatchedBoundedResolveDev : BatchedBoundedDev {
 
 // batched_bounded_resolve.hip
 int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d);   // fitting shapes, else LP_BAD_ARG
+
+// Depth-first branch-and-bound over variable bounds, one mixed-integer bounded LP per workgroup
+// (batched_mip_bounded.hip; the definition is tests/ref/mip_bounded_ref.c): the bounded re-solve at the root, then per
+// node one bound changed on the live tableau (first child) or the re-solve's install from the path's bounds and the
+// recorded basis and flags (second child).  The tableau never grows, so the depth is bounded by the records alone.
+#define LP_MIP_BOUNDED_MAX_DEPTH 1024
+struct BatchedMipBoundedDev {
+    int batch, m, n, n_orig;
+    int maximize;
+    int max_iter;            // per node: dual pivots, or primal pivots plus flips
+    int max_depth, max_nodes;
+    double eps, int_tol, gap;
+    const double* A;         // batch x (m*n), each column-major
+    const double* b;         // batch x m
+    const double* c;         // batch x n
+    const double* lo;        // batch x n, finite
+    const double* hi;        // batch x n, finite or +inf
+    const int* basis_in;     // batch x m (by position), every index in [0, n): the root's start
+    const int* at_upper_in;  // batch x n (0/1; 1 only where hi is finite)
+    const int* root_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it (found 0, NaN outputs)
+    const int* integer;      // n: the mask, one for the whole batch
+    double* x;               // batch x n_orig: the incumbent, NaN without one
+    double* obj;             // batch
+    double* bound;           // batch
+    int* found;              // batch
+    int* stats;              // batch x 5: nodes, dual pivots, primal pivots, bound flips, deepest level
+    int* status;             // batch
+};
+
+// batched_mip_bounded.hip
+size_t lp_mip_bounded_lds_bytes(int m, int n, int max_depth);
+bool lp_mip_bounded_fits_shape(int m, int n, int max_depth);
+int lp_batched_mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
 
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP

@@ -394,6 +394,51 @@ public:
         return out;
     }
 
+    // Depth-first branch-and-bound over the bounds (lp_mip_bounded_solve) with EPS, INT_TOL, MIP_GAP, MAX_ITER and the
+    // problem's sense: the bounded problem of boundedSimplex with the columns j of integer[j] integral (their lo and
+    // finite hi must be integers).  A branch changes one bound, so the depth is not traded against the shape: maxDepth
+    // goes to 1024.  The first form solves the relaxation by boundedSimplex first; the second starts from a result's
+    // basis and flags (a result that is not LP_OPTIMAL keeps its status and gets found = false).  IntegerResult as
+    // branchAndBound.  Exceptions as boundedResolve (wrong sizes, a start that is no valid one, bad bounds) and
+    // branchAndBound (a bad mask, a shape beyond lp_mip_bounded_fits): std::invalid_argument.
+    IntegerResult boundedBranchAndBound(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                        const std::vector<double>& hi, int maxDepth = 64,
+                                        int maxNodes = 100000) const {
+        return boundedBranchAndBound(integer, lo, hi, boundedSimplex(lo, hi, false), maxDepth, maxNodes);
+    }
+
+    IntegerResult boundedBranchAndBound(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                        const std::vector<double>& hi, const BoundedResult& from, int maxDepth = 64,
+                                        int maxNodes = 100000) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
+        IntegerResult out;
+        out.status = from.status;
+        out.x = lpla::VectorXd::Zero(no);
+        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        if (from.status != LP_OPTIMAL) return out;
+        if ((int)integer.size() != n) throw std::invalid_argument("Solver::boundedBranchAndBound: mask size != cols(A)");
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedBranchAndBound: lo / hi size != cols(A)");
+        if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+            throw std::invalid_argument(
+                "Solver::boundedBranchAndBound: the start's basis / atUpper size != rows(A) / cols(A)");
+        std::vector<int> mask((size_t)n);
+        for (int j = 0; j < n; ++j) mask[(size_t)j] = integer[(size_t)j] ? 1 : 0;
+        lp_context* ctx = lpgpu::context(_device);
+        int found = 0, stats[5] = {0, 0, 0, 0, 0};
+        out.status = lp_mip_bounded_solve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                          from.basis.data(), from.atUpper.data(), _problem.IsMaximization() ? 1 : 0,
+                                          no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER,
+                                          out.x.data(), &out.objective, &out.bound, &found, stats);
+        if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        out.found = found != 0;
+        out.nodes = stats[0];
+        return out;
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
