@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -87,8 +87,21 @@ int lp_simplex_solve(lp_context* ctx, const double* A, int m, int n, const doubl
  * smallest eligible non-basic index with d_j > eps (max) / d_j < -eps (min) enters; among the rows
  * with u_i > eps whose ratio xB_i / u_i is within eps of the smallest, the one whose basic variable
  * has the smallest index leaves.  Bland's rule never cycles, and usually takes more pivots.  It runs
- * on LP_SIMPLEX_ALGO_LAUNCH (AUTO picks it) and on the LDS form of the batched kernels.        */
-enum { LP_PIVOT_DANTZIG = 0, LP_PIVOT_BLAND = 1 };
+ * on LP_SIMPLEX_ALGO_LAUNCH (AUTO picks it) and on the LDS form of the batched kernels.
+ * DEVEX: primal Devex pricing with Dantzig's ratio test.  One fp64 weight w_j per column, all exactly
+ * 1.0 at the start of every run of the primal loop (each lp_simplex_run, each phase of the two-phase
+ * flow; the drive-out pivots neither read nor update weights; no other reset).  A non-basic column
+ * that may enter with d_j > eps (max) / d_j < -eps (min) is scored s_j = (d_j * d_j) / w_j; the
+ * largest score enters, exact ties to the smallest index (no eps on scores; none eligible: optimal).
+ * The leaving row is Dantzig's.  Then, from the old pivot row r, the old pivot element u_r and the
+ * old w_e:  w_j = fmax(w_j, (t * t) * w_e) with t = T[r][j] / u_r for every non-basic j != e (the
+ * artificial columns of phase II included), and w_v = fmax(w_e / (u_r * u_r), 1.0) for the leaving
+ * variable v.  No fused multiply-add in any of it.  Devex is no anti-cycling rule.  It is expected to
+ * help on badly scaled or large LPs, where it takes several times fewer pivots than Dantzig's rule;
+ * it runs where Bland's rule runs (LP_SIMPLEX_ALGO_LAUNCH, which AUTO picks, and the LDS form of the
+ * batched kernels), i.e. on forms that are slower per pivot than the ones Dantzig's AUTO chooses
+ * (chip-resident, overlapped, register-resident batched): on small well-scaled LPs it loses.     */
+enum { LP_PIVOT_DANTZIG = 0, LP_PIVOT_BLAND = 1, LP_PIVOT_DEVEX = 2 };
 
 /* lp_simplex_solve with a pivot rule (any other value: LP_BAD_ARG).                             */
 int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
@@ -143,8 +156,9 @@ int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const doub
 int lp_simplex_reset(lp_simplex_problem* p);
 int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
                    lp_simplex_stats* stats_out);
-/* The pivot rule of the problem's next runs (LP_PIVOT_DANTZIG after upload).  Under LP_PIVOT_BLAND,
- * AUTO runs LP_SIMPLEX_ALGO_LAUNCH and an explicit RESIDENT, LOOKAHEAD or OVERLAP is LP_BAD_ARG.  */
+/* The pivot rule of the problem's next runs (LP_PIVOT_DANTZIG after upload).  Under LP_PIVOT_BLAND and
+ * LP_PIVOT_DEVEX, AUTO runs LP_SIMPLEX_ALGO_LAUNCH and an explicit RESIDENT, LOOKAHEAD or OVERLAP is
+ * LP_BAD_ARG.  The Devex weights (n doubles on the device) are allocated by the first Devex run.   */
 int lp_simplex_set_pivot_rule(lp_simplex_problem* p, int pivot_rule);
 /* on != 0: the next runs bracket every tableau-update launch with HIP events so that
  * lp_simplex_stats::update_ms / update_launches are filled (costs ~1-2 us per launch; off by
@@ -187,7 +201,7 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
  *     LP_OPTIMAL); the entering column the same chain over d_j / T[r][j] (max) or -d_j / T[r][j] (min) of
  *     the non-basic j with T[r][j] < -eps, in index order (none: LP_INFEASIBLE).  max_iter bounds its pivots;
  *   - else LP_BAD_ARG: the basis is no valid start.
- * Dantzig's rule only: a problem or batch set to LP_PIVOT_BLAND returns LP_BAD_ARG.
+ * Dantzig's rule only: a problem or batch set to LP_PIVOT_BLAND or LP_PIVOT_DEVEX returns LP_BAD_ARG.
  * iters_out: 2 ints per LP = dual pivots, primal pivots (one of them is 0; the crash is not counted).
  * Note: lp_simplex_solve from a basis that is not primal feasible is NOT a valid re-solve.          */
 /* On an lp_simplex_upload handle (after upload or lp_simplex_reset).  The dual simplex runs the launch
@@ -235,7 +249,10 @@ int lp_simplex_solve_batched(lp_context* ctx, int batch, const double* A, int m,
                              int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
                              double* obj_out, int* iters_out, int* status_out);
 /* The same with a pivot rule.  Under LP_PIVOT_BLAND the batch runs the kernel's LDS form (every
- * shape that stays on the GPU fits it); the per-LP fallback passes the rule on.                 */
+ * shape that stays on the GPU fits it); the per-LP fallback passes the rule on.  Under LP_PIVOT_DEVEX
+ * the LDS form carries n - m more doubles, the weights: a batch that runs one LP per workgroup and
+ * whose carve no longer fits 160 KiB with them (lp_batched_devex_fits(m, n, 0) == 0) returns
+ * LP_BAD_ARG from the run.                                                                       */
 int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
                                 const double* b, const double* c, const int* basis_in, int maximize,
                                 int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
@@ -251,6 +268,11 @@ int lp_batched_download(lp_batched_problem* p, double* x_out, int* basis_out, do
 void lp_batched_free(lp_batched_problem* p);
 /* The pivot rule of the batch's next runs, plain or two-phase (LP_PIVOT_DANTZIG after upload).  */
 int lp_batched_set_pivot_rule(lp_batched_problem* p, int pivot_rule);
+/* 1 if the one-LP-per-workgroup kernel of a plain (two_phase == 0: (m+1) x (n-m+1) tableau, n - m weights)
+ * or two-phase (two_phase != 0: (m+1) x (n+1) tableau, n weights) batch holds the shape under LP_PIVOT_DEVEX,
+ * else 0.  A batch that runs one LP per workgroup under the other rules and has 0 here returns LP_BAD_ARG
+ * from lp_batched_run under Devex; batches that go LP by LP anyway are not concerned.               */
+int lp_batched_devex_fits(int m, int n, int two_phase);
 /* BASELINE.json configs[4] "1 -> 8 GPUs": the LPs of a batch are independent, so participant `shard`
  * of `shards` (one process or host thread per GPU) uploads and solves the LPs [*lo, *hi) of the batch
  * and nobody exchanges anything (replicas of the code, no collective; the caller concatenates the
@@ -269,7 +291,8 @@ int lp_simplex_two_phase_batched(lp_context* ctx, int batch, const double* A, in
                                  const double* b, const double* c, int maximize, int n_orig,
                                  double eps, int max_iter, double* x_out, int* basis_out,
                                  double* obj_out, int* iters_out, int* status_out);
-/* The same with a pivot rule for phase I and phase II.                                           */
+/* The same with a pivot rule for phase I and phase II (LP_PIVOT_DEVEX: n more doubles of LDS, see
+ * lp_batched_devex_fits(m, n, 1)).                                                               */
 int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n,
                                     const double* b, const double* c, int maximize, int n_orig,
                                     double eps, int max_iter, double* x_out, int* basis_out,
@@ -528,7 +551,7 @@ int lp_mip_solve(lp_context* ctx, const double* A, int m, int n, const double* b
  * batch*n_orig, obj_out / bound_out / found_out / status_out batch, stats_out batch*4.                          */
 int lp_mip_solve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const int* basis, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out);
 /* From the final bases of a plain, two-phase or re-solve batch after lp_batched_run (LP_BAD_ARG before the first
- * run, and for a batch set to LP_PIVOT_BLAND).  LPs whose run did not end LP_OPTIMAL keep their status.  Outputs as
+ * run, and for a batch set to LP_PIVOT_BLAND or LP_PIVOT_DEVEX).  LPs whose run did not end LP_OPTIMAL keep their status.  Outputs as
  * lp_mip_solve_batched.                                                                                         */
 int lp_batched_mip(lp_batched_problem* p, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out);
 /* 1: the search's LDS carve (the (m+max_depth+1) x (n+max_depth+1) tableau and the per-level records) fits one

@@ -152,6 +152,26 @@ def build_test_ref(force=False, verbose=False):
     return TEST_REF_LIB
 
 
+DEVEX_REF_LIB = os.path.join(TESTS_REF, "_build", "libdevex_ref.so")
+
+
+def build_test_devex_ref(force=False, verbose=False):
+    """tests/ref/devex_ref.c -> tests/ref/_build/libdevex_ref.so: the Devex restatement the tests compare
+    against; flags as build_test_ref."""
+    src = os.path.join(TESTS_REF, "devex_ref.c")
+    if not os.path.exists(src):
+        return None
+    if not force and _newer(DEVEX_REF_LIB, [src]):
+        return DEVEX_REF_LIB
+    os.makedirs(os.path.dirname(DEVEX_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", DEVEX_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return DEVEX_REF_LIB
+
+
 RESOLVE_REF_LIB = os.path.join(TESTS_REF, "_build", "libresolve_ref.so")
 
 
@@ -364,6 +384,7 @@ def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
     build_test_ref(force, verbose)
+    build_test_devex_ref(force, verbose)
     build_resolve_ref(force, verbose)
     build_duals_ref(force, verbose)
     build_ranging_ref(force, verbose)

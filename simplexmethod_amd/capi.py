@@ -16,7 +16,7 @@ OPTIMAL, UNBOUNDED, ITER_LIMIT, SINGULAR, INFEASIBLE, BAD_ARG = range(6)
 SUBSET_FEASIBLE, SUBSET_INFEASIBLE, SUBSET_SINGULAR = range(3)
 SIMPLEX_AUTO, SIMPLEX_LAUNCH, SIMPLEX_LOOKAHEAD, SIMPLEX_RESIDENT, SIMPLEX_OVERLAP = 0, 1, 2, 3, 4
 ENUM_AUTO, ENUM_DIRECT, ENUM_PREFIX = 0, 1, 2
-PIVOT_DANTZIG, PIVOT_BLAND = 0, 1
+PIVOT_DANTZIG, PIVOT_BLAND, PIVOT_DEVEX = 0, 1, 2
 CERT_NONE, CERT_FARKAS, CERT_RAY = 0, 1, 2
 U64_MAX = (1 << 64) - 1
 EPS = 1e-9        # Solver::EPS, SimplexSolover.h:13
@@ -76,6 +76,7 @@ SIGNATURES = {
                                               C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp,
                                               _ip, _ip, C.c_int]),
     "lp_batched_set_pivot_rule": (C.c_int, [_vp, C.c_int]),
+    "lp_batched_devex_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "lp_batched_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
                                     C.c_int, C.POINTER(_vp)]),
     "lp_batched_run": (C.c_int, [_vp, C.c_double, C.c_int, _fp]),
@@ -227,12 +228,12 @@ def load():
 
 
 def pivot_rule_id(rule):
-    """"dantzig" | "bland" | PIVOT_DANTZIG | PIVOT_BLAND -> the LP_PIVOT_* value (other integers pass through:
-    the library refuses them with LP_BAD_ARG)."""
+    """"dantzig" | "bland" | "devex" | PIVOT_DANTZIG | PIVOT_BLAND | PIVOT_DEVEX -> the LP_PIVOT_* value (other
+    integers pass through: the library refuses them with LP_BAD_ARG)."""
     if isinstance(rule, str):
-        names = {"dantzig": PIVOT_DANTZIG, "bland": PIVOT_BLAND}
+        names = {"dantzig": PIVOT_DANTZIG, "bland": PIVOT_BLAND, "devex": PIVOT_DEVEX}
         if rule.lower() not in names:
-            raise ValueError(f"unknown pivot rule {rule!r} (expected 'dantzig' or 'bland')")
+            raise ValueError(f"unknown pivot rule {rule!r} (expected 'dantzig', 'bland' or 'devex')")
         return names[rule.lower()]
     return int(rule)
 
@@ -494,6 +495,11 @@ class Context:
         self.check(self.lib.lp_basis_duals_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis), _d(y),
                                                    _d(d), _d(w), _i(st)))
         return dict(status=st, y=y, d=d, w=w)
+
+    def batched_devex_fits(self, m, n, two_phase=False):
+        """lp_batched_devex_fits: True if the one-LP-per-workgroup kernel (plain or two-phase) holds an m x n LP
+        together with its Devex weights."""
+        return bool(self.lib.lp_batched_devex_fits(m, n, int(bool(two_phase))))
 
     def basis_duals_fits(self, m):
         """lp_basis_duals_fits: True if m runs the one-LP-per-workgroup kernel."""
@@ -962,7 +968,7 @@ class SimplexProblem:
         self.ctx.check(self.ctx.lib.lp_simplex_reset(self.h))
 
     def set_pivot_rule(self, rule):
-        """"dantzig" (the default after upload) or "bland", for the following runs."""
+        """"dantzig" (the default after upload), "bland" or "devex", for the following runs."""
         self.ctx.check(self.ctx.lib.lp_simplex_set_pivot_rule(self.h, pivot_rule_id(rule)))
 
     def profile(self, on=True):
@@ -1048,7 +1054,7 @@ class BatchedProblem:
         self.h = h
 
     def set_pivot_rule(self, rule):
-        """"dantzig" (the default after upload) or "bland", for the following runs."""
+        """"dantzig" (the default after upload), "bland" or "devex", for the following runs."""
         self.ctx.check(self.ctx.lib.lp_batched_set_pivot_rule(self.h, pivot_rule_id(rule)))
 
     def run(self, eps=EPS, max_iter=MAX_ITER):

@@ -198,10 +198,16 @@ int lp_batched_set_start(lp_batched_problem* p, const double* b, const int* basi
 
 int lp_batched_set_pivot_rule(lp_batched_problem* p, int pivot_rule) {
     if (!p) return LP_BAD_ARG;
-    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+    if (!lp_pivot_rule_known(pivot_rule))
         LP_FAIL(p->ctx, LP_BAD_ARG, "unknown pivot rule");
     p->pivot_rule = pivot_rule;
     return LP_OPTIMAL;
+}
+
+int lp_batched_devex_fits(int m, int n, int two_phase) {
+    if (m <= 0 || n < m) return 0;
+    if (two_phase) return lp_batched_two_phase_devex_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
+    return n > m && lp_batched_devex_lds_bytes(m, n) <= 160 * 1024 ? 1 : 0;
 }
 
 int lp_batched_shard_bounds(int batch, int shard, int shards, int* lo, int* hi) {
@@ -480,7 +486,7 @@ int lp_simplex_solve_batched_ex(lp_context* ctx, int batch, const double* A, int
                                 const double* b, const double* c, const int* basis_in, int maximize,
                                 int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
                                 double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
-    if (ctx && pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+    if (ctx && !lp_pivot_rule_known(pivot_rule))
         LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     if (ctx && !(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_solve_batched: eps must be >= 0");
     lp_batched_problem* p = nullptr;
@@ -504,7 +510,7 @@ int lp_simplex_two_phase_batched_ex(lp_context* ctx, int batch, const double* A,
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase_batched: eps must be >= 0");
-    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_batched_problem* p = nullptr;
     const int rc = lp_batched_two_phase_upload(ctx, batch, A, m, n, b, c, maximize, n_orig, &p);
     if (rc) return rc;

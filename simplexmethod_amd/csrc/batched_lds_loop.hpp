@@ -3,6 +3,9 @@
 // has defined constexpr bool BLAND and the LDS carve (T, pitch, W, prow, lcol, slotvar, basis, pub), m, n, eps,
 // tid, wave, lane and d.max_iter.  Not a standalone header.  Shared by inclusion rather than through an inlined
 // __device__ function, which changed the register allocation of the existing kernels (batched_two_phase_body.hpp).
+// Under the macro LP_BATCHED_DEVEX (k_batched_two_phase_devex only, with BLAND = false and the carve's wts, one
+// double per slot) simplex() sets the weights to 1.0 when it starts, prices on d * d / w and updates the weights
+// after the ratio test; pivot() — and so the drive-out — never touches them.
     // ---- one Gauss-Jordan pivot on (row r, slot se) with tableau_pivot's arithmetic; slot se
     // receives the leaving variable's column (the eta column itself).  All threads.
     const int G = NT / W > 0 ? NT / W : 1;   // row groups: a thread owns one column and every G-th row
@@ -32,7 +35,23 @@
     // basis position, both by wave 0.  Phase II bars the artificial slots.
     auto simplex = [&](bool phase2, bool maximize, int& iters) -> int {
         if (d.max_iter <= 0) return LP_ITER_LIMIT;
+#ifdef LP_BATCHED_DEVEX
+        for (int s = tid; s < n; s += NT) wts[s] = 1.0;
+        __syncthreads();
+#endif
         for (;;) {
+#ifdef LP_BATCHED_DEVEX
+            if (wave == 0) {   // the eligible slot of largest score d * d / w, ties to the smallest variable index
+                const double* drow = T + (size_t)m * pitch;
+                const int se0 = wave_argmax_keyed(n, [&](int s, double& v, int& k, bool& ok) {
+                    const double dj = drow[s];
+                    v = (dj * dj) / wts[s];
+                    k = slotvar[s];
+                    ok = (!phase2 || k < n) && (maximize ? (dj > eps) : (dj < -eps));
+                });
+                if (lane == 0) pub[0] = se0;
+            } else
+#endif
             if (wave == 0 && BLAND) {
                 const double* drow = T + (size_t)m * pitch;
                 const int se0 = wave_min_key(n, [&](int s, int& k, bool& ok) {
@@ -103,6 +122,18 @@
                     r = wave_scan_keyed<false>(m, eps, theta, getr);
                 }
                 if (!__any(any_pos)) r = -1;
+#ifdef LP_BATCHED_DEVEX
+                if (r >= 0) {   // weights from the old row r, the old pivot element and the entering slot's old weight;
+                                // slot se will hold the leaving variable
+                    const double ur = T[(size_t)r * pitch + se], we = wts[se];
+                    for (int s = lane; s < n; s += 64)
+                        if (s != se) {
+                            const double t = T[(size_t)r * pitch + s] / ur;
+                            wts[s] = fmax(wts[s], (t * t) * we);
+                        }
+                    if (lane == 0) wts[se] = fmax(we / (ur * ur), 1.0);
+                }
+#endif
                 if (lane == 0) pub[1] = r;
             }
             __syncthreads();

@@ -24,7 +24,8 @@ struct BatchedDev {
 
 // batched_simplex.hip
 size_t lp_batched_lds_bytes(int m, int n, int* pitch_out);
-int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule);   // LP_PIVOT_BLAND: the LDS form
+int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule);   // LP_PIVOT_BLAND, LP_PIVOT_DEVEX: the LDS form
+size_t lp_batched_devex_lds_bytes(int m, int n);   // the LDS form's carve + n - m weights
 
 // A batch of same-shape LPs solved by the two-phase flow, one LP per workgroup (batched_two_phase.hip).
 struct BatchedTwoPhaseDev {
@@ -45,6 +46,7 @@ struct BatchedTwoPhaseDev {
 // batched_two_phase.hip
 size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out);
 bool lp_batched_two_phase_fits(int m, int n);
+size_t lp_batched_two_phase_devex_lds_bytes(int m, int n);   // the carve + n weights
 int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule);
 
 // A batch of same-shape LPs re-solved from given bases, one LP per workgroup (batched_resolve.hip): the

@@ -195,4 +195,31 @@ __device__ int wave_bland_ratio(int count, double eps, Get get) {
     return __builtin_amdgcn_readlane(lrow, (int)__builtin_ctzll(__ballot(lkey == kmin)));
 }
 
+// ---- Devex pricing (LP_PIVOT_DEVEX) on keyed entries, by ONE wave (all 64 lanes) -------------------
+
+// The eligible entry of largest score, exact ties to the smallest key: get(s, score, key, eligible).  Returns
+// its slot, -1 if none.  Scores are >= 0 or NaN; a NaN score fails every comparison and is never taken.  No eps
+// is involved, so the result does not depend on the order of the slots.
+template <typename Get>
+__device__ int wave_argmax_keyed(int count, Get get) {
+    const int lane = threadIdx.x & 63;
+    double lv = -1.0;
+    int lkey = INT_MAX, lslot = -1;
+    for (int s = lane; s < count; s += 64) {
+        double v;
+        int k;
+        bool ok;
+        get(s, v, k, ok);
+        if (ok && (v > lv || (v == lv && k < lkey))) {
+            lv = v;
+            lkey = k;
+            lslot = s;
+        }
+    }
+    const double M = lpdev::f64_from_key(lpdev::wave_ext_key<true>(lpdev::f64_sort_key(lv)));
+    const int kmin = (int)lpdev::wave_ext_u32<false>((unsigned)((lv == M && lslot >= 0) ? lkey : INT_MAX));
+    if (kmin == INT_MAX) return -1;
+    return __builtin_amdgcn_readlane(lslot, (int)__builtin_ctzll(__ballot(lv == M && lkey == kmin)));
+}
+
 }  // namespace

@@ -44,6 +44,17 @@ __global__ __launch_bounds__(1024) void k_batched_simplex_bland(BatchedDev d) {
 #include "batched_simplex_body.hpp"
 }
 
+// The same kernel under Devex pricing (LP_PIVOT_DEVEX): one weight per slot behind the carve (nn doubles more:
+// lp_batched_devex_lds_bytes), all 1.0 at the start.  Wave 0 updates them from the staged pivot row right after the
+// reduced-cost row and prices on d * d / w (batched_scan.hpp: wave_argmax_keyed) while the other waves apply the
+// rank-1 update, as under the other rules; the ratio test is Dantzig's.
+__global__ __launch_bounds__(1024) void k_batched_simplex_devex(BatchedDev d) {
+    constexpr bool STAMPS = false, BLAND = false;
+#define LP_BATCHED_DEVEX
+#include "batched_simplex_body.hpp"
+#undef LP_BATCHED_DEVEX
+}
+
 }  // namespace
 
 // Pricing (:152-174) by one wave over up to 64*K entries held in REGISTERS: entry (lane + 64*q) has
@@ -626,7 +637,21 @@ size_t lp_batched_lds_bytes(int m, int n, int* pitch_out) {
     return (bytes + 15) & ~(size_t)15;
 }
 
+size_t lp_batched_devex_lds_bytes(int m, int n) {
+    const size_t bytes = lp_batched_lds_bytes(m, n, nullptr) + sizeof(double) * (size_t)(n - m);   // + the slots' weights
+    return (bytes + 15) & ~(size_t)15;
+}
+
 int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule) {
+    if (pivot_rule == LP_PIVOT_DEVEX) {   // the LDS form only, with the weights behind its carve
+        const size_t shm = lp_batched_devex_lds_bytes(d.m, d.n);
+        if (shm > 160 * 1024)
+            LP_FAIL(ctx, LP_BAD_ARG, "batched Devex: the tableau and the weights do not fit one CU's LDS (lp_batched_devex_fits)");
+        LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_simplex_devex),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+        hipLaunchKernelGGL(k_batched_simplex_devex, d.batch, 1024, shm, ctx->stream, d);
+        return LP_OPTIMAL;
+    }
     if (pivot_rule == LP_PIVOT_BLAND) {   // the LDS form only (the register form is Dantzig's)
         const size_t shm = lp_batched_lds_bytes(d.m, d.n, nullptr);
         LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_simplex_bland),

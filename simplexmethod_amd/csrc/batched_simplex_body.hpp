@@ -3,6 +3,9 @@
 // which define the constexpr bools STAMPS and BLAND first.  Not a standalone header.  The body is shared
 // by inclusion rather than through an inlined __device__ function because that form changed the register
 // allocation of the existing instantiations; included, their device code stays exactly what it was.
+// k_batched_simplex_devex defines the macro LP_BATCHED_DEVEX around the inclusion (with BLAND = false): the
+// lines under it add the Devex weights (one per slot, behind the carve), their update and the pricing on
+// scores; no other kernel sees them.
     extern __shared__ __attribute__((aligned(16))) double smem[];
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev = STAMPS ? __builtin_readcyclecounter() : 0;
@@ -26,6 +29,10 @@
     int* slotvar = reinterpret_cast<int*>(ratio + m); // nn : variable held by each slot
     int* basis = slotvar + nn;                        // m  : N by position
     int* posofvar = basis + m;                        // n  : scratch for the initial split
+#ifdef LP_BATCHED_DEVEX
+    double* wts = reinterpret_cast<double*>(posofvar + n);   // nn : Devex weight of each slot's variable (2n ints in front)
+    for (int s = tid; s < nn; s += nt) wts[s] = 1.0;
+#endif
 
     const double* A = d.A + (size_t)lp * m * n;
     const double* b = d.b + (size_t)lp * m;
@@ -64,6 +71,19 @@
     // for pivot k+1 WHILE the other waves apply pivot k's update to the constraint rows: wave 0
     // updates the reduced-cost row first, which is all the pricing reads.
     auto price = [&]() {
+#ifdef LP_BATCHED_DEVEX
+        {   // the eligible slot of largest score d * d / w, ties to the smallest variable index
+            const double* drow = T + (size_t)m * pitch;
+            const int se0 = wave_argmax_keyed(nn, [&](int s, double& v, int& k, bool& ok) {
+                const double dj = drow[s];
+                v = (dj * dj) / wts[s];
+                k = slotvar[s];
+                ok = d.maximize ? (dj > eps) : (dj < -eps);
+            });
+            if (lane == 0) pub[0] = se0;
+            return;
+        }
+#endif
         if constexpr (BLAND) {
             const double* drow = T + (size_t)m * pitch;
             const int se0 = wave_min_key(nn, [&](int s, int& k, bool& ok) {
@@ -174,6 +194,18 @@
             const double lm = lcol[m];
             double* drow = T + (size_t)m * pitch;
             for (int j = lane; j < W; j += 64) drow[j] = (j == se) ? lm : fma(lm, prow[j], drow[j]);
+#ifdef LP_BATCHED_DEVEX
+            {   // weights from the old pivot row, the old pivot element and the entering slot's old weight;
+                // slot se takes the leaving variable's weight together with its column
+                const double we = wts[se];
+                for (int j = lane; j < nn; j += 64)
+                    if (j != se) {
+                        const double t = prow[j] / ur;
+                        wts[j] = fmax(wts[j], (t * t) * we);
+                    }
+                if (lane == 0) wts[se] = fmax(we / (ur * ur), 1.0);
+            }
+#endif
             if (lane == 0) {
                 const int ve = slotvar[se];
                 slotvar[se] = basis[r];

@@ -51,14 +51,30 @@ __global__ __launch_bounds__(NT) void k_batched_two_phase_bland(BatchedTwoPhaseD
 #include "batched_two_phase_body.hpp"
 }
 
+// The same kernel under Devex pricing (LP_PIVOT_DEVEX) in phase I and phase II: one weight per slot behind the
+// carve (n doubles more: lp_batched_two_phase_devex_lds_bytes), set to 1.0 when each phase starts; pricing on
+// d * d / w (batched_scan.hpp: wave_argmax_keyed), Dantzig's ratio test, and the weight update by wave 0 before
+// the pivot.  The drive-out is the same under every rule and leaves the weights alone.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_two_phase_devex(BatchedTwoPhaseDev d) {
+    constexpr bool BLAND = false;
+#define LP_BATCHED_DEVEX
+#include "batched_two_phase_body.hpp"
+#undef LP_BATCHED_DEVEX
+}
+
 template <int NT>
 int two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule) {
-    const size_t shm = lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr);
-    const void* kernel = pivot_rule == LP_PIVOT_BLAND ? reinterpret_cast<const void*>(k_batched_two_phase_bland<NT>)
-                                                      : reinterpret_cast<const void*>(k_batched_two_phase<NT>);
+    const size_t shm = pivot_rule == LP_PIVOT_DEVEX ? lp_batched_two_phase_devex_lds_bytes(d.m, d.n)
+                                                    : lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr);
+    const void* kernel = pivot_rule == LP_PIVOT_BLAND   ? reinterpret_cast<const void*>(k_batched_two_phase_bland<NT>)
+                         : pivot_rule == LP_PIVOT_DEVEX ? reinterpret_cast<const void*>(k_batched_two_phase_devex<NT>)
+                                                        : reinterpret_cast<const void*>(k_batched_two_phase<NT>);
     LP_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     if (pivot_rule == LP_PIVOT_BLAND)
         hipLaunchKernelGGL(k_batched_two_phase_bland<NT>, d.batch, NT, shm, ctx->stream, d);
+    else if (pivot_rule == LP_PIVOT_DEVEX)
+        hipLaunchKernelGGL(k_batched_two_phase_devex<NT>, d.batch, NT, shm, ctx->stream, d);
     else
         hipLaunchKernelGGL(k_batched_two_phase<NT>, d.batch, NT, shm, ctx->stream, d);
     return LP_OPTIMAL;
@@ -75,6 +91,11 @@ size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out) {
     return (bytes + 15) & ~(size_t)15;
 }
 
+size_t lp_batched_two_phase_devex_lds_bytes(int m, int n) {
+    // (the carve's ints end on a 4-byte boundary when n + m is odd; its size is rounded up to 16, which holds the pad)
+    return lp_batched_two_phase_lds_bytes(m, n, nullptr) + (((sizeof(double) * (size_t)n) + 15) & ~(size_t)15);
+}
+
 bool lp_batched_two_phase_fits(int m, int n) {
     return m > 0 && n >= m && lp_batched_two_phase_lds_bytes(m, n, nullptr) <= 160 * 1024;
 }
@@ -82,6 +103,8 @@ bool lp_batched_two_phase_fits(int m, int n) {
 int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule) {
     if (!lp_batched_two_phase_fits(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "batched two-phase: the shape does not fit one CU's LDS");
+    if (pivot_rule == LP_PIVOT_DEVEX && lp_batched_two_phase_devex_lds_bytes(d.m, d.n) > 160 * 1024)
+        LP_FAIL(ctx, LP_BAD_ARG, "batched two-phase Devex: the tableau and the weights do not fit one CU's LDS (lp_batched_devex_fits)");
     // small tableaus: four waves, so that several LPs share a CU; the rest: sixteen
     if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return two_phase_launch<256>(ctx, d, pivot_rule);
     return two_phase_launch<1024>(ctx, d, pivot_rule);

@@ -3,6 +3,8 @@
 // true), which define the constexpr bool BLAND first.  Not a standalone header.  The body is shared by
 // inclusion rather than through an inlined __device__ function because that form changed the register
 // allocation of the existing instantiations; included, their device code stays exactly what it was.
+// k_batched_two_phase_devex<NT> defines the macro LP_BATCHED_DEVEX around the inclusion (with BLAND = false):
+// the carve then ends with the Devex weights, which batched_lds_loop.hpp's simplex() owns.
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int m = d.m, n = d.n, W = n + 1, pitch = d.pitch;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -14,6 +16,9 @@
     double* lcol = prow + W;                              // m+1
     int* slotvar = reinterpret_cast<int*>(lcol + m + 1);  // n
     int* basis = slotvar + n;                             // m
+#ifdef LP_BATCHED_DEVEX
+    double* wts = reinterpret_cast<double*>(basis + m + ((n + m) & 1));   // n : Devex weight of each slot's variable
+#endif
     int* pub = pubs->v;   // [0] entering slot, [1] leaving position, [2] infeasible: published by wave 0
 
     const double* A = d.A + (size_t)lp * m * n;

@@ -149,6 +149,11 @@ static inline T lp_ceil_div(T a, T b) {
     return (a + b - 1) / b;
 }
 
+// The pivot rules the _ex entries and the two setters accept.
+static inline bool lp_pivot_rule_known(int rule) {
+    return rule == LP_PIVOT_DANTZIG || rule == LP_PIVOT_BLAND || rule == LP_PIVOT_DEVEX;
+}
+
 // Host-side combinatorics shared by the enumeration paths (exact u64; 0 = overflow).
 uint64_t lp_host_binom(int n, int k);
 // rank, among the t-subsets of {0 .. n-m+t-1}, of the first t elements of the rank-th m-subset of

@@ -237,6 +237,7 @@ void lp_simplex_free(lp_simplex_problem* p) {
     (void)hipFree(p->dscratchT);
     (void)hipFree(p->ov_T);
     (void)hipFree(p->ov_vec);
+    (void)hipFree(p->dweights);
     (void)hipFree(p->look.stamps);
     if (p->h_state) {   // pinned block + events: kept for the next problem of this context
         lp_context::HostBundle hb;
@@ -453,6 +454,11 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
         if (algo == LP_SIMPLEX_ALGO_RESIDENT || algo == LP_SIMPLEX_ALGO_LOOKAHEAD || algo == LP_SIMPLEX_ALGO_OVERLAP)
             LP_FAIL(ctx, LP_BAD_ARG, "Bland's pivot rule runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
     }
+    if (p->pivot_rule == LP_PIVOT_DEVEX) {   // so does the Devex selector
+        if (algo == LP_SIMPLEX_ALGO_AUTO) algo = LP_SIMPLEX_ALGO_LAUNCH;
+        if (algo == LP_SIMPLEX_ALGO_RESIDENT || algo == LP_SIMPLEX_ALGO_LOOKAHEAD || algo == LP_SIMPLEX_ALGO_OVERLAP)
+            LP_FAIL(ctx, LP_BAD_ARG, "Devex pricing runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
+    }
     if (algo == LP_SIMPLEX_ALGO_AUTO)
         algo = p->res.G >= 1 ? LP_SIMPLEX_ALGO_RESIDENT
                : p->look.J >= 3 ? LP_SIMPLEX_ALGO_LOOKAHEAD   // (depth 2, 1536 x 3072: 20.0 us per pivot against the overlapped path's 18.4)
@@ -526,7 +532,7 @@ int lp_simplex_resolve_run(lp_simplex_problem* p, double eps, int max_iter, int*
 
 int lp_simplex_set_pivot_rule(lp_simplex_problem* p, int pivot_rule) {
     if (!p) return LP_BAD_ARG;
-    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND)
+    if (!lp_pivot_rule_known(pivot_rule))
         LP_FAIL(p->ctx, LP_BAD_ARG, "unknown pivot rule");
     p->pivot_rule = pivot_rule;
     return LP_OPTIMAL;
@@ -592,7 +598,7 @@ int lp_simplex_solve_ex(lp_context* ctx, const double* A, int m, int n, const do
     if (!ctx) return LP_BAD_ARG;
     if (!x_out) LP_FAIL(ctx, LP_BAD_ARG, "x_out is null");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_solve: eps must be >= 0");
-    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A, m, n, b, c, basis_in, maximize, n_orig, &p);
     if (rc) return rc;
@@ -665,7 +671,7 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
     if (!ctx) return LP_BAD_ARG;
     if (!A || !b || !c || !x_out) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: eps must be >= 0");
-    if (pivot_rule != LP_PIVOT_DANTZIG && pivot_rule != LP_PIVOT_BLAND) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, "unknown pivot rule");
     if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_two_phase: bad dimensions");
     const int na = n + m;
     std::vector<double> A1((size_t)m * na, 0.0), b1((size_t)m), c1((size_t)na, 0.0), xa((size_t)na);

@@ -269,6 +269,186 @@ __global__ __launch_bounds__(1024) void k_simplex_select_bland(SimplexDev d) {
 }
 
 // ---------------------------------------------------------------------------
+// select under Devex pricing (LP_PIVOT_DEVEX): same launch shape and staging as k_simplex_select; the
+// weights w (n doubles, lp_simplex_problem::dweights, all 1.0 at the start of a run) come as an extra
+// argument, so SimplexDev and the other kernels' arguments are what they were.
+//   entering: the non-basic j with d_j > eps (max) / d_j < -eps (min) of largest score
+//             s_j = (d_j * d_j) / w_j, exact ties to the smallest j — an arg-max of (s_j, -j) by the whole
+//             workgroup (n is several thousand here): each thread over its columns in ascending order, then
+//             the wave, then the sixteen wave results.  A NaN score is never taken.
+//   leaving:  Dantzig's ratio test, as in k_simplex_select;
+//   weights:  in the loop that copies the old row r to d.prow, from the old ur = T[r][e] and we = w_e:
+//             w_j = fmax(w_j, (t * t) * we), t = T[r][j] / ur, for every j != e; then the leaving variable
+//             v = basis[r] gets w_v = fmax(we / (ur * ur), 1.0).  A basic j != v has T[r][j] = +-0 exactly, so
+//             its weight stays (fmax drops the NaN of 0 * inf); no weight of a basic column is ever read.
+// 16 doubles + 16 ints of LDS behind the three ints of k_simplex_select hold the waves' results.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_simplex_select_devex(SimplexDev d, double* w) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_u = s_dyn;
+    double* s_ratio = s_dyn + (d.m + 2);
+    int* s_int = reinterpret_cast<int*>(s_dyn + 2 * (d.m + 2));
+    int& s_enter = s_int[0];
+    int& s_leave = s_int[1];
+    int& s_flag = s_int[2];
+    double* s_score = s_dyn + 2 * (d.m + 2) + 2;
+    int* s_col = reinterpret_cast<int*>(s_score + 16);
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    const double* drow = d.T + (size_t)m * ld;
+    {
+        double best = -1.0;
+        int col = INT_MAX;
+        constexpr int K = 4;   // columns per thread and step: their loads are in flight together
+        for (int j0 = tid; j0 < n; j0 += K * (int)blockDim.x) {
+            double v[K], wj[K];
+            bool nb[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int j = j0 + k * (int)blockDim.x;
+                nb[k] = j < n && d.nonbasic[j] != 0;
+                v[k] = j < n ? drow[j] : 0.0;
+                wj[k] = j < n ? w[j] : 1.0;
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const double s = (v[k] * v[k]) / wj[k];
+                if (nb[k] && (d.maximize ? (v[k] > eps) : (v[k] < -eps)) && s > best) {
+                    best = s;  // j ascending per thread: strict > keeps the smallest index
+                    col = j0 + k * (int)blockDim.x;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double ob = __shfl_xor(best, off, 64);
+            const int oc = __shfl_xor(col, off, 64);
+            if (ob > best || (ob == best && oc < col)) {
+                best = ob;
+                col = oc;
+            }
+        }
+        if ((tid & 63) == 0) {
+            s_score[tid >> 6] = best;
+            s_col[tid >> 6] = col;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
+                if (s_score[q] > best || (s_score[q] == best && s_col[q] < col)) {
+                    best = s_score[q];
+                    col = s_col[q];
+                }
+            s_enter = col == INT_MAX ? -1 : col;
+            s_flag = 0;
+        }
+    }
+    __syncthreads();
+    const int e = s_enter;
+    if (e < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    int any_pos = 0;
+    for (int i = tid; i <= m; i += blockDim.x) {
+        const double ui = d.T[(size_t)i * ld + e];
+        s_u[i] = ui;
+        if (i < m) {
+            s_ratio[i] = (ui > eps) ? d.T[(size_t)i * ld + n] / ui : INFINITY;
+            if (!(ui <= eps)) any_pos = 1;
+        }
+    }
+    if (any_pos) s_flag = 1;
+    __syncthreads();
+    if (!s_flag) {
+        if (tid == 0) {
+            st->status = LP_UNBOUNDED;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    if (tid < 64) {
+        double theta;
+        auto load = [&](int i, bool& ok) {
+            ok = true;  // ineligible rows hold +inf, which the < scan never takes
+            return s_ratio[i];
+        };
+        const int r = lpdev::wave_chain_select<false>(m, eps, theta, load);
+        if (tid == 0) s_leave = r;
+    }
+    __syncthreads();
+    const int r = s_leave;
+    if (r < 0) {
+        if (tid == 0) {
+            st->status = LP_UNBOUNDED;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    const double ur = s_u[r];
+    const double we = w[e];       // (every thread reads the old w_e and basis[r] before the barrier below;
+    const int old = d.basis[r];   //  the loop never writes w_e or w_old)
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_u[i] / ur;
+    const double* trow = d.T + (size_t)r * ld;
+    for (int j0 = tid; j0 < ld; j0 += 4 * (int)blockDim.x) {   // (four columns per step, as in the pricing)
+        double a[4], wj[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k * (int)blockDim.x;
+            a[k] = j < ld ? trow[j] : 0.0;
+            wj[k] = j < n ? w[j] : 1.0;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k * (int)blockDim.x;
+            if (j < ld) d.prow[j] = a[k];
+            if (j < n && j != e && j != old) {
+                const double t = a[k] / ur;
+                w[j] = fmax(wj[k], (t * t) * we);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        w[old] = fmax(we / (ur * ur), 1.0);
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+__global__ __launch_bounds__(256) void k_devex_reset_weights(double* w, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) w[j] = 1.0;
+}
+
+// ---------------------------------------------------------------------------
 // select of the DUAL simplex (lp_simplex_resolve_run on a basis that is dual but not primal feasible):
 // same launch shape, LDS and staging as k_simplex_select, so k_simplex_update applies the pivot.
 //   leaving:  r = the EPS-hysteresis chain (min) over xB_i with xB_i < -eps, i in position order (column n,
@@ -742,31 +922,40 @@ int lp_simplex_crash(lp_simplex_problem* p) {
     return hs.status == kRunning ? LP_OPTIMAL : hs.status;
 }
 
-static size_t select_lds_bytes(const SimplexDev& d) { return 2 * sizeof(double) * (size_t)(d.m + 2) + 16; }
+// (Devex: 16 doubles + 16 ints more, the waves' pricing results)
+static size_t select_lds_bytes(const lp_simplex_problem* p) {
+    return 2 * sizeof(double) * (size_t)(p->dev.m + 2) + 16 + (p->pivot_rule == LP_PIVOT_DEVEX ? 192 : 0);
+}
 
 static const void* select_kernel(const lp_simplex_problem* p) {
-    return p->pivot_rule == LP_PIVOT_BLAND ? reinterpret_cast<const void*>(k_simplex_select_bland)
-                                           : reinterpret_cast<const void*>(k_simplex_select);
+    return p->pivot_rule == LP_PIVOT_BLAND   ? reinterpret_cast<const void*>(k_simplex_select_bland)
+           : p->pivot_rule == LP_PIVOT_DEVEX ? reinterpret_cast<const void*>(k_simplex_select_devex)
+                                             : reinterpret_cast<const void*>(k_simplex_select);
 }
 
 int lp_launch_prepare(lp_simplex_problem* p) {
-    const size_t shm = select_lds_bytes(p->dev);
+    const size_t shm = select_lds_bytes(p);
     if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
     LP_HIP(p->ctx, lp_lds_opt_in(select_kernel(p), shm));   // (m > 3070)
+    if (p->pivot_rule == LP_PIVOT_DEVEX && !p->dweights)   // first Devex run of this problem
+        LP_HIP(p->ctx, hipMalloc(&p->dweights, sizeof(double) * (size_t)p->dev.n));
     return LP_OPTIMAL;
 }
 
 int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter) {
     hipLaunchKernelGGL(k_state_init, 1, 1, 0, p->ctx->stream, p->dev, eps, max_iter);
-    return 1;
+    if (p->pivot_rule != LP_PIVOT_DEVEX) return 1;
+    hipLaunchKernelGGL(k_devex_reset_weights, lp_ceil_div(p->dev.n, 256), 256, 0, p->ctx->stream, p->dweights, p->dev.n);
+    return 2;
 }
 
 int lp_launch_queue(lp_simplex_problem* p, int batch) {
-    const size_t shm = select_lds_bytes(p->dev);
-    const bool bland = p->pivot_rule == LP_PIVOT_BLAND;
+    const size_t shm = select_lds_bytes(p);
     for (int k = 0; k < batch; ++k) {
-        if (bland)
+        if (p->pivot_rule == LP_PIVOT_BLAND)
             hipLaunchKernelGGL(k_simplex_select_bland, 1, 1024, shm, p->ctx->stream, p->dev);
+        else if (p->pivot_rule == LP_PIVOT_DEVEX)
+            hipLaunchKernelGGL(k_simplex_select_devex, 1, 1024, shm, p->ctx->stream, p->dev, p->dweights);
         else
             hipLaunchKernelGGL(k_simplex_select, 1, 1024, shm, p->ctx->stream, p->dev);
         lp_simplex_launch_update(p);
@@ -796,14 +985,14 @@ int lp_simplex_classify(lp_simplex_problem* p, double eps, int* flags) {
 }
 
 int lp_dual_prepare(lp_simplex_problem* p) {
-    const size_t shm = select_lds_bytes(p->dev);
+    const size_t shm = select_lds_bytes(p);
     if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "simplex: m too large for the selector's LDS");
     LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_dual), shm));
     return LP_OPTIMAL;
 }
 
 int lp_dual_queue(lp_simplex_problem* p, int batch) {
-    const size_t shm = select_lds_bytes(p->dev);
+    const size_t shm = select_lds_bytes(p);
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(k_simplex_select_dual, 1, 1024, shm, p->ctx->stream, p->dev);
         lp_simplex_launch_update(p);

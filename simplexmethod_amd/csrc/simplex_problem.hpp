@@ -78,6 +78,7 @@ struct lp_simplex_problem {
     double* dscratchT = nullptr;  // scratch copy used by the update micro-benchmarks (allocated on first use)
     double* ov_T = nullptr;       // simplex_overlap.hip: the second tableau buffer, and the second eta slot
     double* ov_vec = nullptr;     // (pivot row, eta column, 8 ints); both allocated on first use
+    double* dweights = nullptr;   // simplex_launch.hip: the n Devex weights (LP_PIVOT_DEVEX), allocated on first use
     int* dbasis0 = nullptr;
     unsigned char* dnonbasic0 = nullptr;
     double* dx = nullptr;         // n: extracted vertex

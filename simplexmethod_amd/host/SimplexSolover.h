@@ -32,9 +32,11 @@ public:
         int status = LP_OPTIMAL;
     };
 
-    // The pivot rule of solve() and twoPhaseSimplex(): Dantzig's (the reference's, the default) or Bland's,
-    // which never cycles on degenerate problems and usually takes more pivots (include/simplexmethod_amd.h).
-    enum class PivotRule { Dantzig = LP_PIVOT_DANTZIG, Bland = LP_PIVOT_BLAND };
+    // The pivot rule of solve() and twoPhaseSimplex(): Dantzig's (the reference's, the default), Bland's,
+    // which never cycles on degenerate problems and usually takes more pivots, or Devex pricing, which takes
+    // fewer pivots on badly scaled or large problems and runs on a slower-per-pivot path
+    // (include/simplexmethod_amd.h).
+    enum class PivotRule { Dantzig = LP_PIVOT_DANTZIG, Bland = LP_PIVOT_BLAND, Devex = LP_PIVOT_DEVEX };
 
     explicit Solver(const Canonical& problem, int device = 0) : _problem(problem), _device(device) {}
 
