@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits; lp_basis_bounded_duals, lp_basis_bounded_duals_batched, lp_basis_bounded_ranging, lp_basis_bounded_ranging_batched, lp_basis_bounded_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -634,6 +634,46 @@ int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, in
 /* 1: lp_simplex_bounded_fits' carve plus max_depth records of 24 + 4 m + 4 ceil(n / 32) bytes fits one CU's 160 KB and
  * max_depth is in [0, 1024] (64 x 192 at depth 64, 32 x 96 at 256, 16 x 40 at 1024); 0 otherwise.  A host call.      */
 int lp_mip_bounded_fits(int m, int n, int max_depth);
+
+/* ---- Bounded variables: the dual solution and ranging at a basis ------------------------------------------------
+ * The LP of lp_simplex_bounded analysed at basis (m, by position, every index in [0, n)) and at_upper (n, 0/1),
+ * normally the basis_out and at_upper_out of a solve (the definition is
+ * tests/ref/bounded_sens_ref.c).  Everything is in the caller's original variables: a non-basic column is held at
+ * v_j = hi_j when flagged, else lo_j; the flag of a basic column is not read.
+ *   - b' = b - sum A_j v_j over the non-basic columns (one fma chain per row, j ascending, v_j != 0.0 only); xB and
+ *     B^-1 by lp_basis_ranging's crash on [B | I | b']; x_out = xB on the basis and v elsewhere: the point the basis
+ *     and the flags define;
+ *   - y_out and d_out are lp_basis_duals' (basic d exactly 0.0); w_out = b.y + sum d_j v_j over the non-basic columns
+ *     (lp_basis_duals' chain continued over j ascending, v_j != 0.0 only), which is c.x at an optimal basis.  Optimal
+ *     means, under max, d_j <= eps at a lower bound and d_j >= -eps at an upper bound, under min the other way
+ *     round; this is not checked;
+ *   - RHS range of row i: with beta_t = B^-1[t][i], L_t / H_t the bounds of basis[t], the ratios (L_t - xB[t]) / beta_t
+ *     and, H_t finite, (H_t - xB[t]) / beta_t (-xB[t] / beta_t when L_t == 0.0, as lp_basis_ranging); a ratio goes to
+ *     the lower end (max) or the upper end (min) by the sign of beta_t beyond eps.  rhs_out[2i], [2i+1] = b_i + delta,
+ *     rhs_var_out the leaving variable, rhs_side_out the bound it leaves at (0 lower, 1 upper); an empty side is
+ *     -inf / +inf, -1 and -1.  The first position wins a tie;
+ *   - cost ranges: the sense of a non-basic j is maximize XOR at_upper[j]: [-inf, c_j - d_j] if set, else
+ *     [c_j - d_j, +inf] (a fixed column is ranged by its flag like any other); a basic column's ends are
+ *     c + d_j / alpha[t][j] over the non-basic j with |alpha| > eps, a lower-end candidate (max) if (alpha > eps)
+ *     equals j's sense, else an upper-end candidate (min).  cost_var_out is the entering column, -1 at an infinite
+ *     end.  The first column wins a tie;
+ *   - the status: LP_OPTIMAL, LP_SINGULAR (a crash failed; a repeated index ends here) or LP_INFEASIBLE (some
+ *     hi_j < lo_j); then every value is NaN and every index and side -1.  LP_BAD_ARG for everything
+ *     lp_simplex_bounded_resolve refuses about lo, hi, the basis and the flags, a NULL pointer (every output is
+ *     required), for ranging eps < 0 or NaN, and a shape beyond lp_basis_bounded_fits (there is no per-LP host path).
+ * With lo = 0, hi = +inf and no flag the results are lp_basis_duals' and lp_basis_ranging's bit for bit.            */
+int lp_basis_bounded_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, double* x_out, double* y_out, double* d_out, double* w_out);
+/* A batch of LPs of one shape: arrays concatenated per LP (A batch*m*n, b batch*m, c / lo / hi / at_upper batch*n,
+ * basis batch*m; x_out / d_out batch*n, y_out batch*m, w_out / status_out batch).  A bad bound, index or flag in any
+ * LP refuses the whole call (LP_BAD_ARG); an LP with hi < lo is LP_INFEASIBLE and the others are computed.         */
+int lp_basis_bounded_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, double* x_out, double* y_out, double* d_out, double* w_out, int* status_out);
+/* rhs_out / rhs_var_out / rhs_side_out 2m, cost_out / cost_var_out 2n: interleaved pairs (lower end, upper end).   */
+int lp_basis_bounded_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out, double* cost_out, int* cost_var_out);
+/* A batch of LPs of one shape and sense: inputs as lp_basis_bounded_duals_batched; rhs_* batch*2m, cost_* batch*2n. */
+int lp_basis_bounded_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out, double* cost_out, int* cost_var_out, int* status_out);
+/* 1: lp_simplex_bounded_fits(m, n) and the analysis kernel's LDS carve (lp_basis_ranging_fits' plus the held values
+ * and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.                   */
+int lp_basis_bounded_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

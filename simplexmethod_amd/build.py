@@ -380,6 +380,28 @@ def build_mip_bounded_ref(force=False, verbose=False):
     return MIP_BOUNDED_REF_LIB
 
 
+BOUNDED_SENS_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_sens_ref.so")
+
+
+def build_bounded_sens_ref(force=False, verbose=False):
+    """tests/ref/bounded_sens_ref.c (which includes ranging_ref.c and duals_ref.c) ->
+    tests/ref/_build/libbounded_sens_ref.so: the dual solution and ranging of a bounded-variable LP at a given basis
+    and flags the tests compare against; flags as build_ranging_ref."""
+    src = os.path.join(TESTS_REF, "bounded_sens_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "ranging_ref.c"), os.path.join(TESTS_REF, "duals_ref.c")]
+    if not force and _newer(BOUNDED_SENS_REF_LIB, deps):
+        return BOUNDED_SENS_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_SENS_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_SENS_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_SENS_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -395,6 +417,7 @@ def build_all(force=False, verbose=False):
     build_bounded_ref(force, verbose)
     build_bounded_resolve_ref(force, verbose)
     build_mip_bounded_ref(force, verbose)
+    build_bounded_sens_ref(force, verbose)
     return hip, host
 
 

@@ -157,6 +157,14 @@ SIGNATURES = {
                                                C.c_int, C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
                                                C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "lp_mip_bounded_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "lp_basis_bounded_duals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "lp_basis_bounded_duals_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                 _dp, _dp, _dp, _dp, _ip]),
+    "lp_basis_bounded_ranging": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                           C.c_double, _dp, _ip, _ip, _dp, _ip]),
+    "lp_basis_bounded_ranging_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                   C.c_int, C.c_double, _dp, _ip, _ip, _dp, _ip, _ip]),
+    "lp_basis_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -772,6 +780,71 @@ class Context:
                                                                float(eps), int(max_iter), _d(x), _i(bo), _i(up),
                                                                _d(obj), _i(it), _i(st)))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
+
+    # ---- the dual solution and ranging of a bounded-variable LP at a basis ----------------------
+    def _bounded_basis_in(self, A, b, c, lo, hi, basis, at_upper, batched):
+        A = np.asarray(A, dtype=np.float64)
+        batch, m, n = A.shape if batched else (1,) + A.shape
+        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1) if batched else colmajor(A)
+        b, c, lo, hi = (_f64(v).reshape(-1) for v in (b, c, lo, hi))
+        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
+        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
+            raise ValueError("b, c, lo, hi must have m, n, n, n entries per LP")
+        if basis.size != batch * m or at_upper.size != batch * n:
+            raise ValueError("basis must have m and at_upper n entries per LP")
+        return batch, m, n, Af, b, c, lo, hi, basis, at_upper
+
+    def bounded_duals(self, A, b, c, lo, hi, basis, at_upper):
+        """lp_basis_bounded_duals: the LP of bounded() at `basis` (m) and `at_upper` (n, 0/1), normally a result's: the
+        point x (n) they define, shadow prices y (m), reduced costs d (n) and w = b.y + sum d_j x_j over the non-basic
+        columns (c.x at an optimum), in the original variables.  dict(status, x, y, d, w); NaN unless status is
+        OPTIMAL (SINGULAR: a crash failed; INFEASIBLE: some hi < lo).  A bad bound, index or flag or a shape beyond
+        basis_bounded_fits raises LPError with code BAD_ARG."""
+        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        x, y, d, w = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(1)
+        rc = self.check(self.lib.lp_basis_bounded_duals(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
+                                                        _i(at_upper), _d(x), _d(y), _d(d), _d(w)))
+        return dict(status=rc, x=x, y=y, d=d, w=float(w[0]))
+
+    def bounded_duals_batched(self, A, b, c, lo, hi, basis, at_upper):
+        """lp_basis_bounded_duals_batched: A (batch, m, n), b (batch, m), c / lo / hi / at_upper (batch, n), basis
+        (batch, m).  The dict of bounded_duals with a leading batch axis; status (batch)."""
+        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        x, y, d, w = np.zeros((batch, n)), np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_basis_bounded_duals_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                           _i(basis), _i(at_upper), _d(x), _d(y), _d(d), _d(w), _i(st)))
+        return dict(status=st, x=x, y=y, d=d, w=w)
+
+    def bounded_ranging(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
+        """lp_basis_bounded_ranging: how far each b_i and c_j can move before `basis` and `at_upper` stop being
+        feasible / optimal for the LP of bounded().  The dict of basis_ranging plus b_side (m, 2): the bound the
+        leaving variable leaves at (0 lower, 1 upper, -1 for an infinite end); NaN and -1 unless status is OPTIMAL."""
+        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        rhs, cost = np.zeros(2 * m), np.zeros(2 * n)
+        rv, rs, cv = np.zeros(2 * m, np.int32), np.zeros(2 * m, np.int32), np.zeros(2 * n, np.int32)
+        rc = self.check(self.lib.lp_basis_bounded_ranging(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
+                                                          _i(at_upper), int(maximize), float(eps), _d(rhs), _i(rv),
+                                                          _i(rs), _d(cost), _i(cv)))
+        return dict(_ranging_dict(rc, rhs, rv, cost, cv), b_side=rs.reshape(-1, 2))
+
+    def bounded_ranging_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
+        """lp_basis_bounded_ranging_batched: arrays as bounded_duals_batched.  The dict of bounded_ranging with a
+        leading batch axis; status (batch)."""
+        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        rhs, cost = np.zeros((batch, 2 * m)), np.zeros((batch, 2 * n))
+        rv, rs = np.zeros((batch, 2 * m), np.int32), np.zeros((batch, 2 * m), np.int32)
+        cv = np.zeros((batch, 2 * n), np.int32)
+        st = np.zeros(batch, dtype=np.int32)
+        self.check(self.lib.lp_basis_bounded_ranging_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                             _i(basis), _i(at_upper), int(maximize), float(eps),
+                                                             _d(rhs), _i(rv), _i(rs), _d(cost), _i(cv), _i(st)))
+        return dict(_ranging_dict(st, rhs, rv, cost, cv), b_side=rs.reshape(batch, -1, 2))
+
+    def basis_bounded_fits(self, m, n):
+        """lp_basis_bounded_fits: True if an m x n bounded LP runs the analysis kernel."""
+        return bool(self.lib.lp_basis_bounded_fits(m, n))
 
     # ---- branch-and-bound over the bounds of a bounded-variable LP -----------------------------
     def mip_bounded_solve(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,

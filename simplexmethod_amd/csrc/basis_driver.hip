@@ -5,6 +5,8 @@
 // the host) and lp_batched_X (a batch handle after its run).  All three put the inputs on the device (upload, or
 // where a resident run left them: batch_inputs) and call X_on_device, which launches the analysis's kernel when the
 // shape fits it and otherwise runs its single-LP device path one LP after another (per_lp).
+// The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip) have two entry points each (one LP, a
+// batch from the host) and no per-LP path: bounded_sens uploads, launches and downloads in one call.
 #include <cmath>
 #include <functional>
 
@@ -341,6 +343,202 @@ int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* 
     return rc ? rc
               : ranging_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, eps, rhs_out, rhs_var_out, cost_out,
                                   cost_var_out, status_out);
+}
+
+// ===========================================================================
+// The dual solution and ranging of a bounded-variable LP at a given basis and flags (basis_bounded.hip): one LP per
+// workgroup for lp_basis_bounded_fits shapes only; as in the bounded family there is no handle and no per-LP path
+// ===========================================================================
+
+int lp_basis_bounded_fits(int m, int n) { return lp_basis_bounded_fits_shape(m, n) ? 1 : 0; }
+
+// The checks of lp_simplex_bounded_resolve on every LP of the batch (the pointers and dimensions are the caller's):
+// lo finite, hi not NaN, flags 0 or 1 and 1 only under a finite hi, basis indices in [0, n), and the fit.
+static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m, int n, const double* lo,
+                              const double* hi, const int* basis, const int* at_upper) {
+    const size_t N = (size_t)batch * n;
+    for (size_t j = 0; j < N; ++j) {
+        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
+        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
+        if (at_upper[j] != 0 && at_upper[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
+        if (at_upper[j] && hi[j] == INFINITY)   // (hi = -inf is a crossed bound: that LP's LP_INFEASIBLE)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
+    }
+    if (basis_in_range(basis, batch * m, n)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
+    if (!lp_basis_bounded_fits_shape(m, n))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_basis_bounded_fits)");
+    return LP_OPTIMAL;
+}
+
+// NaN for LP k of the duals outputs
+static void bounded_duals_nan(size_t k, int m, int n, double* x, double* y, double* d, double* w) {
+    for (size_t j = 0; j < (size_t)n; ++j) x[k * n + j] = d[k * n + j] = NAN;
+    for (size_t t = 0; t < (size_t)m; ++t) y[k * m + t] = NAN;
+    w[k] = NAN;
+}
+
+// NaN values, -1 indices and sides for LP k of the ranging outputs
+static void bounded_ranging_nan(size_t k, int m, int n, double* rhs, int* rhs_var, int* rhs_side, double* cost,
+                                int* cost_var) {
+    ranging_nan(k, m, n, rhs, rhs_var, cost, cost_var);
+    for (size_t q = 0; q < 2 * (size_t)m; ++q) rhs_side[k * 2 * m + q] = -1;
+}
+
+// The host arrays of `batch` bounded LPs with their bases and flags, and the output arrays of the two analyses.
+struct BoundedSensIn {
+    int batch, m, n;
+    const double *A, *b, *c, *lo, *hi;
+    const int *basis, *at_upper;
+};
+struct BoundedDualsOut {
+    double *x, *y, *d, *w;
+};
+struct BoundedRangingOut {
+    double* rhs;
+    int *rhs_var, *rhs_side;
+    double* cost;
+    int* cost_var;
+};
+
+// One allocation for the inputs and the outputs of the batch, one launch of k_batched_bounded_sens, one download:
+// the ranging launch when `ro` is given (maximize and eps are its), else the duals launch into `du`.
+static int bounded_sens(lp_context* ctx, const BoundedSensIn& in, const BoundedDualsOut* du, const BoundedRangingOut* ro,
+                        int maximize, double eps, int* status_out) {
+    const bool ranging = ro != nullptr;
+    const int batch = in.batch, m = in.m, n = in.n;
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, nr = B * 2 * m, nc = B * 2 * n;
+    const size_t in_d = B * ((size_t)m * n + m + 3 * (size_t)n), in_i = B * ((size_t)m + n);
+    const size_t out_d = ranging ? nr + nc : B * (2 * (size_t)n + m + 1), out_i = (ranging ? 2 * nr + nc : 0) + B;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (in_d + out_d) + sizeof(int) * (in_i + out_i)));
+    double* dA = reinterpret_cast<double*>(buf.ptr);   // the doubles first
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    double* dlo = dc + B * n;
+    double* dhi = dlo + B * n;
+    double* dout = dhi + B * n;
+    int* dbasis = reinterpret_cast<int*>(dout + out_d);
+    int* dup = dbasis + B * m;
+    int* iout = dup + B * n;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, in.A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, in.b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, in.c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dlo, in.lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dhi, in.hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, in.basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dup, in.at_upper, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("bounded basis analysis upload: ") + hipGetErrorString(e));
+    BasisBoundedDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.lo = dlo;
+    d.hi = dhi;
+    d.basis = dbasis;
+    d.at_upper = dup;
+    int rc;
+    if (ranging) {
+        d.rhs = dout;
+        d.cost = d.rhs + nr;
+        d.rhs_var = iout;
+        d.rhs_side = d.rhs_var + nr;
+        d.cost_var = d.rhs_side + nr;
+        d.status = d.cost_var + nc;
+        rc = lp_basis_bounded_launch(ctx, d, true);
+        if (rc == LP_OPTIMAL)
+            rc = lp_download(ctx, "bounded basis ranging", {{ro->rhs, d.rhs, sizeof(double) * nr},
+                                                            {ro->cost, d.cost, sizeof(double) * nc},
+                                                            {ro->rhs_var, d.rhs_var, sizeof(int) * nr},
+                                                            {ro->rhs_side, d.rhs_side, sizeof(int) * nr},
+                                                            {ro->cost_var, d.cost_var, sizeof(int) * nc},
+                                                            {status_out, d.status, sizeof(int) * B}});
+    } else {
+        d.x = dout;
+        d.d = d.x + B * n;
+        d.y = d.d + B * n;
+        d.w = d.y + B * m;
+        d.status = iout;
+        rc = lp_basis_bounded_launch(ctx, d, false);
+        if (rc == LP_OPTIMAL)
+            rc = lp_download(ctx, "bounded basis duals", {{du->x, d.x, sizeof(double) * B * n},
+                                                          {du->d, d.d, sizeof(double) * B * n},
+                                                          {du->y, d.y, sizeof(double) * B * m},
+                                                          {du->w, d.w, sizeof(double) * B},
+                                                          {status_out, d.status, sizeof(int) * B}});
+    }
+    return rc;
+}
+
+int lp_basis_bounded_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                           const double* lo, const double* hi, const int* basis, const int* at_upper, double* x_out,
+                           double* y_out, double* d_out, double* w_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !x_out || !y_out || !d_out || !w_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals: bad dimensions");
+    bounded_duals_nan(0, m, n, x_out, y_out, d_out, w_out);
+    int rc = bounded_basis_args(ctx, "lp_basis_bounded_duals", 1, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    const BoundedDualsOut out{x_out, y_out, d_out, w_out};
+    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, &out, nullptr, 0, 0.0, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_bounded_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                   const double* c, const double* lo, const double* hi, const int* basis,
+                                   const int* at_upper, double* x_out, double* y_out, double* d_out, double* w_out,
+                                   int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !x_out || !y_out || !d_out || !w_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals_batched: bad dimensions");
+    const int rc = bounded_basis_args(ctx, "lp_basis_bounded_duals_batched", batch, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    const BoundedDualsOut out{x_out, y_out, d_out, w_out};
+    return bounded_sens(ctx, {batch, m, n, A, b, c, lo, hi, basis, at_upper}, &out, nullptr, 0, 0.0, status_out);
+}
+
+int lp_basis_bounded_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                             const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize,
+                             double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out, double* cost_out,
+                             int* cost_var_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !rhs_out || !rhs_var_out || !rhs_side_out ||
+        !cost_out || !cost_var_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: bad dimensions");
+    bounded_ranging_nan(0, m, n, rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: eps must be >= 0");
+    int rc = bounded_basis_args(ctx, "lp_basis_bounded_ranging", 1, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    const BoundedRangingOut out{rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out};
+    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, &out, maximize, eps, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_bounded_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                     const double* c, const double* lo, const double* hi, const int* basis,
+                                     const int* at_upper, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                                     int* rhs_side_out, double* cost_out, int* cost_var_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !rhs_out || !rhs_var_out || !rhs_side_out ||
+        !cost_out || !cost_var_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging_batched: eps must be >= 0");
+    const int rc = bounded_basis_args(ctx, "lp_basis_bounded_ranging_batched", batch, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    const BoundedRangingOut out{rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out};
+    return bounded_sens(ctx, {batch, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, &out, maximize, eps, status_out);
 }
 
 // ===========================================================================

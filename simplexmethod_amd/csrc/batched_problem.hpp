@@ -326,6 +326,37 @@ size_t lp_mip_bounded_lds_bytes(int m, int n, int max_depth);
 bool lp_mip_bounded_fits_shape(int m, int n, int max_depth);
 int lp_batched_mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
 
+// The dual solution and RHS / cost ranging of bounded-variable LPs at given bases and at-upper flags, one LP per
+// workgroup (basis_bounded.hip; the definition is tests/ref/bounded_sens_ref.c).  The duals launch writes x, y, d, w;
+// the ranging launch writes rhs .. cost_var in interleaved pairs (lower end, upper end).
+struct BasisBoundedDev {
+    int batch, m, n;
+    int maximize;            // ranging only
+    double eps;              // ranging only
+    const double* A;         // batch x (m*n), each column-major
+    const double* b;         // batch x m
+    const double* c;         // batch x n
+    const double* lo;        // batch x n, finite
+    const double* hi;        // batch x n, finite or +inf
+    const int* basis;        // batch x m (by position), every index in [0, n)
+    const int* at_upper;     // batch x n (0/1; 1 only where hi is finite)
+    double* x;               // batch x n: the point the basis and the flags define
+    double* y;               // batch x m
+    double* d;               // batch x n
+    double* w;               // batch
+    double* rhs;             // batch x 2m
+    int* rhs_var;            // batch x 2m: the leaving column at each end
+    int* rhs_side;           // batch x 2m: 0 it leaves at its lower bound, 1 at its upper bound
+    double* cost;            // batch x 2n
+    int* cost_var;           // batch x 2n: the entering column at each end
+    int* status;             // batch: LP_OPTIMAL, LP_SINGULAR or LP_INFEASIBLE (crossed bounds)
+};
+
+// basis_bounded.hip
+size_t lp_basis_bounded_lds_bytes(int m, int n);
+bool lp_basis_bounded_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
+int lp_basis_bounded_launch(lp_context* ctx, const BasisBoundedDev& d, bool ranging);   // fitting shapes, else LP_BAD_ARG
+
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP
 // entry its per-LP fallback calls; everything else is the same for the three kinds.

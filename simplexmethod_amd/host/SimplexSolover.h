@@ -396,6 +396,113 @@ public:
         return out;
     }
 
+    // The dual solution of the bounded problem at a result's basis and flags (lp_basis_bounded_duals), in the original
+    // variables: the point x (all columns of A) the basis and the flags define, shadow prices y, reduced costs d
+    // (exactly 0 on the basis) and objective = b.y + sum d_j x_j over the non-basic columns, which equals c.x at an
+    // optimum.  There a max problem has d <= EPS at a lower bound and d >= -EPS at an upper bound, a min problem the
+    // other way round.  status: LP_OPTIMAL, LP_SINGULAR or LP_INFEASIBLE (some hi < lo), the last two with NaN; a
+    // result that is not LP_OPTIMAL keeps its status and gets NaN.  Wrong sizes, bad bounds, a bad flag or index or a
+    // shape beyond lp_basis_bounded_fits throw std::invalid_argument.
+    struct BoundedDuals {
+        lpla::VectorXd x, y, d;
+        double objective = std::numeric_limits<double>::quiet_NaN();
+        int status = LP_OPTIMAL;
+    };
+
+    BoundedDuals boundedDuals(const std::vector<double>& lo, const std::vector<double>& hi,
+                              const BoundedResult& from) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedDuals: lo / hi size != cols(A)");
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        BoundedDuals out;
+        out.x = lpla::VectorXd::Zero(n);
+        out.y = lpla::VectorXd::Zero(m);
+        out.d = lpla::VectorXd::Zero(n);
+        out.status = from.status;
+        if (from.status == LP_OPTIMAL) {
+            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+                throw std::invalid_argument("Solver::boundedDuals: the result's basis / atUpper size != rows(A) / cols(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.status = lp_basis_bounded_duals(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                from.basis.data(), from.atUpper.data(), out.x.data(), out.y.data(),
+                                                out.d.data(), &out.objective);
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        if (out.status != LP_OPTIMAL) {
+            for (int j = 0; j < n; ++j) out.x[j] = out.d[j] = nan;
+            for (int i = 0; i < m; ++i) out.y[i] = nan;
+            out.objective = nan;
+        }
+        return out;
+    }
+
+    // RHS and cost ranging of the bounded problem at a result's basis and flags (lp_basis_bounded_ranging) with EPS and
+    // the problem's sense: the fields of Ranging, plus for each end of a b range the bound its leaving variable leaves
+    // at (b_side_lo / b_side_hi: 0 lower, 1 upper, -1 at an infinite end).  A non-basic column at its upper bound is
+    // ranged with the opposite sense.  Statuses and exceptions as boundedDuals.
+    struct BoundedRanging : Ranging {
+        std::vector<int> b_side_lo, b_side_hi;
+    };
+
+    BoundedRanging boundedRanging(const std::vector<double>& lo, const std::vector<double>& hi,
+                                  const BoundedResult& from) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedRanging: lo / hi size != cols(A)");
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        std::vector<double> rhs(2 * (size_t)m, nan), cost(2 * (size_t)n, nan);
+        std::vector<int> rv(2 * (size_t)m, -1), rs(2 * (size_t)m, -1), cv(2 * (size_t)n, -1);
+        BoundedRanging out;
+        out.status = from.status;
+        if (from.status == LP_OPTIMAL) {
+            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+                throw std::invalid_argument("Solver::boundedRanging: the result's basis / atUpper size != rows(A) / cols(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.status = lp_basis_bounded_ranging(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                  from.basis.data(), from.atUpper.data(),
+                                                  _problem.IsMaximization() ? 1 : 0, EPS, rhs.data(), rv.data(),
+                                                  rs.data(), cost.data(), cv.data());
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        const bool ok = out.status == LP_OPTIMAL;
+        out.b_lo = lpla::VectorXd::Zero(m);
+        out.b_hi = lpla::VectorXd::Zero(m);
+        out.c_lo = lpla::VectorXd::Zero(n);
+        out.c_hi = lpla::VectorXd::Zero(n);
+        out.b_leave_lo.assign((size_t)m, -1);
+        out.b_leave_hi.assign((size_t)m, -1);
+        out.b_side_lo.assign((size_t)m, -1);
+        out.b_side_hi.assign((size_t)m, -1);
+        out.c_enter_lo.assign((size_t)n, -1);
+        out.c_enter_hi.assign((size_t)n, -1);
+        for (int i = 0; i < m; ++i) {
+            out.b_lo[i] = ok ? rhs[2 * (size_t)i] : nan;
+            out.b_hi[i] = ok ? rhs[2 * (size_t)i + 1] : nan;
+            if (ok) {
+                out.b_leave_lo[(size_t)i] = rv[2 * (size_t)i];
+                out.b_leave_hi[(size_t)i] = rv[2 * (size_t)i + 1];
+                out.b_side_lo[(size_t)i] = rs[2 * (size_t)i];
+                out.b_side_hi[(size_t)i] = rs[2 * (size_t)i + 1];
+            }
+        }
+        for (int j = 0; j < n; ++j) {
+            out.c_lo[j] = ok ? cost[2 * (size_t)j] : nan;
+            out.c_hi[j] = ok ? cost[2 * (size_t)j + 1] : nan;
+            if (ok) {
+                out.c_enter_lo[(size_t)j] = cv[2 * (size_t)j];
+                out.c_enter_hi[(size_t)j] = cv[2 * (size_t)j + 1];
+            }
+        }
+        return out;
+    }
+
     // Depth-first branch-and-bound over the bounds (lp_mip_bounded_solve) with EPS, INT_TOL, MIP_GAP, MAX_ITER and the
     // problem's sense: the bounded problem of boundedSimplex with the columns j of integer[j] integral (their lo and
     // finite hi must be integers).  A branch changes one bound, so the depth is not traded against the shape: maxDepth
