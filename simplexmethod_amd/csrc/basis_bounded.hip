@@ -73,15 +73,8 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_sens(BasisBoundedDev d) 
     const double* hi = d.hi + (size_t)lp * n;
     const int* N = d.basis + (size_t)lp * m;
     const int* up = d.at_upper + (size_t)lp * n;
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[2] = 0;
-        __syncthreads();
-        if (flag) pub[2] = 1;
-        __syncthreads();
-        const bool any = pub[2] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 2;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     int status = LP_OPTIMAL;
     {
@@ -340,12 +333,7 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_sens(BasisBoundedDev d) 
 
 template <int NT, bool RANGING>
 int bounded_sens_launch(lp_context* ctx, const BasisBoundedDev& d) {
-    const size_t shm = lp_basis_bounded_lds_bytes(d.m, d.n);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_bounded_sens<NT, RANGING>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_batched_bounded_sens<NT, RANGING>), d.batch, NT, shm, ctx->stream, d);
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
+    return lp_launch_per_lp(ctx, k_batched_bounded_sens<NT, RANGING>, NT, lp_basis_bounded_lds_bytes(d.m, d.n), d);
 }
 
 }  // namespace

@@ -93,15 +93,8 @@ __global__ __launch_bounds__(NT) void k_batched_certificate(BasisCertificateDev 
     const int* N = d.basis + (size_t)lp * m;
     double* farkas = d.farkas + (size_t)lp * m;
     double* ray = d.ray + (size_t)lp * n;
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[2] = 0;
-        __syncthreads();
-        if (flag) pub[2] = 1;
-        __syncthreads();
-        const bool any = pub[2] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 2;   // block_any's word of pub
+#include "batched_block_any.hpp"
     auto binv = [&](int t, int i) { return T[(size_t)rowpos[t] * pitch + slot[i]]; };
     auto xb = [&](int t) { return T[(size_t)rowpos[t] * pitch + m]; };
 
@@ -282,12 +275,7 @@ __global__ __launch_bounds__(NT) void k_batched_certificate(BasisCertificateDev 
 
 template <int NT, bool MX>
 int batched_certificate_launch(lp_context* ctx, const BasisCertificateDev& d) {
-    const size_t shm = lp_basis_certificate_lds_bytes(d.m, d.n);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_certificate<NT, MX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_batched_certificate<NT, MX>), d.batch, NT, shm, ctx->stream, d);
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
+    return lp_launch_per_lp(ctx, k_batched_certificate<NT, MX>, NT, lp_basis_certificate_lds_bytes(d.m, d.n), d);
 }
 
 // ---- the single-LP path beyond lp_basis_certificate_fits

@@ -51,15 +51,8 @@ __global__ __launch_bounds__(NT) void k_batched_duals(BasisDualsDev d) {
     const int* N = d.basis + (size_t)lp * m;
     double* y = d.y + (size_t)lp * m;
     double* dd = d.d + (size_t)lp * n;
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[2] = 0;
-        __syncthreads();
-        if (flag) pub[2] = 1;
-        __syncthreads();
-        const bool any = pub[2] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 2;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     int status = d.run_status ? d.run_status[lp] : LP_OPTIMAL;
     if (status == LP_OPTIMAL) {
@@ -195,12 +188,7 @@ __global__ __launch_bounds__(NT) void k_batched_duals(BasisDualsDev d) {
 
 template <int NT>
 int batched_duals_launch(lp_context* ctx, const BasisDualsDev& d) {
-    const size_t shm = lp_basis_duals_lds_bytes(d.m);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_duals<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_duals<NT>, d.batch, NT, shm, ctx->stream, d);
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
+    return lp_launch_per_lp(ctx, k_batched_duals<NT>, NT, lp_basis_duals_lds_bytes(d.m), d);
 }
 
 // ---- the single-LP path beyond lp_basis_duals_fits

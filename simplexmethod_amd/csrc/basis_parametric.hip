@@ -62,15 +62,8 @@ __global__ __launch_bounds__(NT) void k_batched_parametric(BasisParametricDev d)
     double* slope_out = d.slope + (size_t)lp * (MB + 1);
     int* enter_out = d.enter + (size_t)lp * (MB + 1);
     int* leave_out = d.leave + (size_t)lp * (MB + 1);
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[3] = 0;
-        __syncthreads();
-        if (flag) pub[3] = 1;
-        __syncthreads();
-        const bool any = pub[3] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 3;   // block_any's word of pub
+#include "batched_block_any.hpp"
     // sum_t c[basis[t]] * fma(tt, delta_t, beta_t), the chain in position order (one lane)
     auto value_at = [&](double tt) {
         double s = 0.0;
@@ -120,14 +113,9 @@ __global__ __launch_bounds__(NT) void k_batched_parametric(BasisParametricDev d)
         const double* drow = T + (size_t)m * pitch;
         if (status == LP_OPTIMAL) {
             // ---- start check: primal and dual feasible at t = 0
-            int pinf = 0, dinf = 0;
-            for (int t = tid; t < m; t += NT)
-                if (T[(size_t)t * pitch + n] < -eps) pinf = 1;
-            for (int s = tid; s < n; s += NT)
-                if (slotvar[s] < n && (MX ? (drow[s] > eps) : (drow[s] < -eps))) dinf = 1;
-            const bool primal_bad = block_any(pinf);
-            const bool dual_bad = block_any(dinf);
-            if (primal_bad || dual_bad) status = LP_BAD_ARG;
+            constexpr bool maximize = MX;
+#include "batched_resolve_classify.hpp"
+            if (!primal_feasible || !dual_feasible) status = LP_BAD_ARG;
         }
         if (status == LP_OPTIMAL) {
             // ---- the segments: wave 0 selects (tk, tend, zk, sk wave-uniform; lane 0 writes the records)
@@ -214,16 +202,6 @@ __global__ __launch_bounds__(NT) void k_batched_parametric(BasisParametricDev d)
         d.nseg[lp] = nseg;
         d.status[lp] = status;
     }
-}
-
-template <int NT, bool MX>
-int batched_parametric_launch(lp_context* ctx, const BasisParametricDev& d) {
-    const size_t shm = lp_basis_parametric_lds_bytes(d.m, d.n, nullptr);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_parametric<NT, MX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_batched_parametric<NT, MX>), d.batch, NT, shm, ctx->stream, d);
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
 }
 
 // ---- the single-LP path beyond lp_basis_parametric_fits
@@ -419,10 +397,10 @@ int lp_basis_parametric_launch(lp_context* ctx, const BasisParametricDev& d, int
     if (!lp_basis_parametric_fits(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "basis parametric: the shape does not fit one CU's LDS");
     if (d.batch <= 0) return LP_OPTIMAL;
-    // small tableaus: four waves, so that several LPs share a CU; the rest: sixteen (batched_resolve.hip's split)
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096)
-        return maximize ? batched_parametric_launch<256, true>(ctx, d) : batched_parametric_launch<256, false>(ctx, d);
-    return maximize ? batched_parametric_launch<1024, true>(ctx, d) : batched_parametric_launch<1024, false>(ctx, d);
+    const size_t cells = (size_t)(d.m + 1) * (d.n + 1), shm = lp_basis_parametric_lds_bytes(d.m, d.n, nullptr);
+    if (maximize)
+        return lp_launch_per_lp(ctx, cells, k_batched_parametric<256, true>, k_batched_parametric<1024, true>, shm, d);
+    return lp_launch_per_lp(ctx, cells, k_batched_parametric<256, false>, k_batched_parametric<1024, false>, shm, d);
 }
 
 // One LP of any size on the device: A, b, c, d, basis already there (ranges checked by the caller).

@@ -70,15 +70,8 @@ __global__ __launch_bounds__(NT) void k_batched_ranging(BasisRangingDev d) {
     int* rhs_var = d.rhs_var + (size_t)lp * 2 * m;
     double* cost = d.cost + (size_t)lp * 2 * n;
     int* cost_var = d.cost_var + (size_t)lp * 2 * n;
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[2] = 0;
-        __syncthreads();
-        if (flag) pub[2] = 1;
-        __syncthreads();
-        const bool any = pub[2] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 2;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     int status = d.run_status ? d.run_status[lp] : LP_OPTIMAL;
     if (status == LP_OPTIMAL) {
@@ -271,12 +264,7 @@ __global__ __launch_bounds__(NT) void k_batched_ranging(BasisRangingDev d) {
 
 template <int NT, bool MX>
 int batched_ranging_launch(lp_context* ctx, const BasisRangingDev& d) {
-    const size_t shm = lp_basis_ranging_lds_bytes(d.m, d.n);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_ranging<NT, MX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_batched_ranging<NT, MX>), d.batch, NT, shm, ctx->stream, d);
-    LP_HIP(ctx, hipGetLastError());
-    return LP_OPTIMAL;
+    return lp_launch_per_lp(ctx, k_batched_ranging<NT, MX>, NT, lp_basis_ranging_lds_bytes(d.m, d.n), d);
 }
 
 // ---- the single-LP path beyond lp_basis_ranging_fits

@@ -204,14 +204,6 @@ __global__ __launch_bounds__(NT) void k_batched_bounded(BatchedBoundedDev d) {
     }
 }
 
-template <int NT>
-int bounded_launch(lp_context* ctx, const BatchedBoundedDev& d, size_t shm) {
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_bounded<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_bounded<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out) {
@@ -227,8 +219,6 @@ bool lp_bounded_fits_shape(int m, int n) {
 int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d) {
     if (!lp_bounded_fits_shape(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "batched bounded simplex: the shape does not fit one CU's LDS");
-    const size_t shm = lp_bounded_lds_bytes(d.m, d.n, nullptr);
-    // small tableaus: four waves, so that several LPs share a CU; the rest: sixteen
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return bounded_launch<256>(ctx, d, shm);
-    return bounded_launch<1024>(ctx, d, shm);
+    return lp_launch_per_lp(ctx, (size_t)(d.m + 1) * (d.n + 1), k_batched_bounded<256>, k_batched_bounded<1024>,
+                            lp_bounded_lds_bytes(d.m, d.n, nullptr), d);
 }

@@ -57,16 +57,8 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_resolve(BatchedBoundedRe
     const int* upin = d.at_upper_in + (size_t)lp * n;
     const double eps = d.eps;
     const bool maximize = d.maximize != 0;
-    // block-wide OR through pub[3] (batched_resolve.hip)
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[3] = 0;
-        __syncthreads();
-        if (flag) pub[3] = 1;
-        __syncthreads();
-        const bool any = pub[3] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 3;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     // ---- load: slots = the columns in order (a flagged one sign-changed, cost included), basis = the artificials
     int bad = 0;
@@ -172,21 +164,11 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_resolve(BatchedBoundedRe
     }
 }
 
-template <int NT>
-int bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, size_t shm) {
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_bounded_resolve<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_bounded_resolve<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d) {
     if (!lp_bounded_fits_shape(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: the shape does not fit one CU's LDS");
-    const size_t shm = lp_bounded_lds_bytes(d.m, d.n, nullptr);
-    // block size as lp_batched_bounded_launch
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return bounded_resolve_launch<256>(ctx, d, shm);
-    return bounded_resolve_launch<1024>(ctx, d, shm);
+    return lp_launch_per_lp(ctx, (size_t)(d.m + 1) * (d.n + 1), k_batched_bounded_resolve<256>,
+                            k_batched_bounded_resolve<1024>, lp_bounded_lds_bytes(d.m, d.n, nullptr), d);
 }

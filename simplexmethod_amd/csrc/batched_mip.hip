@@ -118,15 +118,8 @@ __global__ __launch_bounds__(NT) void k_batched_mip(BatchedMipDev d) {
     // the current shape: the included loops read m (rows), n (slots; eligible keys are < n) and W = n + 1
     int m = m0, n = n0, W = n0 + 1;
 
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[3] = 0;
-        __syncthreads();
-        if (flag) pub[3] = 1;
-        __syncthreads();
-        const bool any = pub[3] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 3;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     // ---- root: T = [A | b; c | 0]; slots = the columns in order, basis = the artificials by row
     for (int s = tid; s < n0; s += NT) slotvar[s] = s;
@@ -167,14 +160,8 @@ __global__ __launch_bounds__(NT) void k_batched_mip(BatchedMipDev d) {
     // ---- classification (two block reductions), then the matching loop; pivots counted per node (max_iter each)
     int nodes = 1, st_dual = 0, st_primal = 0, deepest = 0;
     auto classify_run = [&]() __attribute__((always_inline)) -> int {
-        int pinf = 0, dinf = 0;
-        for (int t = tid; t < m; t += NT)
-            if (T[(size_t)t * pitch + n] < -eps) pinf = 1;
         const double* drow = T + (size_t)m * pitch;
-        for (int s = tid; s < n; s += NT)
-            if (slotvar[s] < n && (maximize ? (drow[s] > eps) : (drow[s] < -eps))) dinf = 1;
-        const bool primal_feasible = !block_any(pinf);
-        const bool dual_feasible = !block_any(dinf);
+#include "batched_resolve_classify.hpp"
         int st = LP_BAD_ARG, itd = 0, itp = 0;
         if (primal_feasible)
             st = simplex(true, maximize, itp);
@@ -373,14 +360,6 @@ __global__ __launch_bounds__(NT) void k_batched_mip(BatchedMipDev d) {
     }
 }
 
-template <int NT>
-int mip_launch(lp_context* ctx, const BatchedMipDev& d, size_t shm) {
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_mip<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_mip<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 size_t lp_mip_lds_bytes(int m, int n, int max_depth) { return mip_carve(m, n, max_depth).bytes; }
@@ -393,8 +372,7 @@ bool lp_mip_fits_shape(int m, int n, int max_depth) {
 int lp_batched_mip_launch(lp_context* ctx, const BatchedMipDev& d) {
     if (!lp_mip_fits_shape(d.m, d.n, d.max_depth))
         LP_FAIL(ctx, LP_BAD_ARG, "batched MIP: the shape does not fit one CU's LDS");
-    const size_t shm = lp_mip_lds_bytes(d.m, d.n, d.max_depth);
-    // small tableaus: four waves, so that several problems share a CU; the rest: sixteen
-    if ((size_t)(d.m + d.max_depth + 1) * (d.n + d.max_depth + 1) <= 4096) return mip_launch<256>(ctx, d, shm);
-    return mip_launch<1024>(ctx, d, shm);
+    // the cells of the deepest level's tableau
+    return lp_launch_per_lp(ctx, (size_t)(d.m + d.max_depth + 1) * (d.n + d.max_depth + 1), k_batched_mip<256>,
+                            k_batched_mip<1024>, lp_mip_lds_bytes(d.m, d.n, d.max_depth), d);
 }

@@ -118,15 +118,8 @@ void k_batched_mip_bounded(BatchedMipBoundedDev d) {
     }
     for (int j = tid; j < no; j += NT) xo[j] = NAN;
 
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[3] = 0;
-        __syncthreads();
-        if (flag) pub[3] = 1;
-        __syncthreads();
-        const bool any = pub[3] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 3;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     // ---- pivot(r, se); the bounded primal loop; the bounded dual loop
 #include "batched_lds_loop.hpp"
@@ -423,14 +416,6 @@ void k_batched_mip_bounded(BatchedMipBoundedDev d) {
     }
 }
 
-template <int NT>
-int mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d, size_t shm) {
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_mip_bounded<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_mip_bounded<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 size_t lp_mip_bounded_lds_bytes(int m, int n, int max_depth) { return mip_bounded_carve(m, n, max_depth).bytes; }
@@ -443,8 +428,6 @@ bool lp_mip_bounded_fits_shape(int m, int n, int max_depth) {
 int lp_batched_mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d) {
     if (!lp_mip_bounded_fits_shape(d.m, d.n, d.max_depth))
         LP_FAIL(ctx, LP_BAD_ARG, "batched bounded MIP: the shape does not fit one CU's LDS");
-    const size_t shm = lp_mip_bounded_lds_bytes(d.m, d.n, d.max_depth);
-    // block size as lp_batched_bounded_launch
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return mip_bounded_launch<256>(ctx, d, shm);
-    return mip_bounded_launch<1024>(ctx, d, shm);
+    return lp_launch_per_lp(ctx, (size_t)(d.m + 1) * (d.n + 1), k_batched_mip_bounded<256>, k_batched_mip_bounded<1024>,
+                            lp_mip_bounded_lds_bytes(d.m, d.n, d.max_depth), d);
 }

@@ -3,6 +3,25 @@
 
 #include "lp_internal.hpp"
 
+// The launch of every one-LP-per-workgroup kernel: d.batch workgroups of `threads`, `shm` bytes of dynamic LDS (the
+// attribute first: the carves go beyond the default limit), on the context's stream.
+template <class Dev>
+int lp_launch_per_lp(lp_context* ctx, void (*kernel)(Dev), int threads, size_t shm, const Dev& d) {
+    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)shm));
+    hipLaunchKernelGGL(kernel, d.batch, threads, shm, ctx->stream, d);
+    LP_HIP(ctx, hipGetLastError());
+    return LP_OPTIMAL;
+}
+
+// The block-size rule of the kernels that hold a whole tableau of `cells` entries in LDS.  Small tableaus: four waves,
+// so that several LPs share a CU; the rest: sixteen.
+template <class Dev>
+int lp_launch_per_lp(lp_context* ctx, size_t cells, void (*k256)(Dev), void (*k1024)(Dev), size_t shm, const Dev& d) {
+    if (cells <= 4096) return lp_launch_per_lp(ctx, k256, 256, shm, d);
+    return lp_launch_per_lp(ctx, k1024, 1024, shm, d);
+}
+
 struct BatchedDev {
     int batch, m, n;
     int pitch;        // row pitch (doubles) of the condensed LDS tableau, odd

@@ -48,16 +48,8 @@ __global__ __launch_bounds__(NT) void k_batched_resolve(BatchedResolveDev d) {
     const int* N = d.basis_in + (size_t)lp * m;
     const double eps = d.eps;
     const bool maximize = d.maximize != 0;
-    // block-wide OR through pub[3] (__syncthreads_or would add static LDS beside the 160 KB of the largest shapes)
-    auto block_any = [&](int flag) {
-        if (tid == 0) pub[3] = 0;
-        __syncthreads();
-        if (flag) pub[3] = 1;
-        __syncthreads();
-        const bool any = pub[3] != 0;
-        __syncthreads();
-        return any;
-    };
+    constexpr int ANY_WORD = 3;   // block_any's word of pub
+#include "batched_block_any.hpp"
 
     // ---- T = [A | b; c | 0]; slots = the columns in order, basis = the artificials by row
     for (int s = tid; s < n; s += NT) slotvar[s] = s;
@@ -91,14 +83,8 @@ __global__ __launch_bounds__(NT) void k_batched_resolve(BatchedResolveDev d) {
     int it[2] = {0, 0};   // dual pivots, primal pivots
     if (status == LP_OPTIMAL) {
         // ---- classification: two block reductions over the crashed tableau
-        int pinf = 0, dinf = 0;
-        for (int t = tid; t < m; t += NT)
-            if (T[(size_t)t * pitch + n] < -eps) pinf = 1;
         const double* drow = T + (size_t)m * pitch;
-        for (int s = tid; s < n; s += NT)
-            if (slotvar[s] < n && (maximize ? (drow[s] > eps) : (drow[s] < -eps))) dinf = 1;
-        const bool primal_feasible = !block_any(pinf);
-        const bool dual_feasible = !block_any(dinf);
+#include "batched_resolve_classify.hpp"
         if (primal_feasible)
             status = simplex(true, maximize, it[1]);   // phase II's form: artificial slots barred
         else if (dual_feasible)
@@ -123,21 +109,11 @@ __global__ __launch_bounds__(NT) void k_batched_resolve(BatchedResolveDev d) {
     }
 }
 
-template <int NT>
-int resolve_launch(lp_context* ctx, const BatchedResolveDev& d) {
-    const size_t shm = lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr);
-    LP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched_resolve<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_batched_resolve<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 int lp_batched_resolve_launch(lp_context* ctx, const BatchedResolveDev& d) {
     if (!lp_batched_two_phase_fits(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "batched re-solve: the shape does not fit one CU's LDS");
-    // small tableaus: four waves, so that several LPs share a CU; the rest: sixteen
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return resolve_launch<256>(ctx, d);
-    return resolve_launch<1024>(ctx, d);
+    return lp_launch_per_lp(ctx, (size_t)(d.m + 1) * (d.n + 1), k_batched_resolve<256>, k_batched_resolve<1024>,
+                            lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr), d);
 }

@@ -63,23 +63,6 @@ __global__ __launch_bounds__(NT) void k_batched_two_phase_devex(BatchedTwoPhaseD
 #undef LP_BATCHED_DEVEX
 }
 
-template <int NT>
-int two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, int pivot_rule) {
-    const size_t shm = pivot_rule == LP_PIVOT_DEVEX ? lp_batched_two_phase_devex_lds_bytes(d.m, d.n)
-                                                    : lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr);
-    const void* kernel = pivot_rule == LP_PIVOT_BLAND   ? reinterpret_cast<const void*>(k_batched_two_phase_bland<NT>)
-                         : pivot_rule == LP_PIVOT_DEVEX ? reinterpret_cast<const void*>(k_batched_two_phase_devex<NT>)
-                                                        : reinterpret_cast<const void*>(k_batched_two_phase<NT>);
-    LP_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    if (pivot_rule == LP_PIVOT_BLAND)
-        hipLaunchKernelGGL(k_batched_two_phase_bland<NT>, d.batch, NT, shm, ctx->stream, d);
-    else if (pivot_rule == LP_PIVOT_DEVEX)
-        hipLaunchKernelGGL(k_batched_two_phase_devex<NT>, d.batch, NT, shm, ctx->stream, d);
-    else
-        hipLaunchKernelGGL(k_batched_two_phase<NT>, d.batch, NT, shm, ctx->stream, d);
-    return LP_OPTIMAL;
-}
-
 }  // namespace
 
 size_t lp_batched_two_phase_lds_bytes(int m, int n, int* pitch_out) {
@@ -105,7 +88,12 @@ int lp_batched_two_phase_launch(lp_context* ctx, const BatchedTwoPhaseDev& d, in
         LP_FAIL(ctx, LP_BAD_ARG, "batched two-phase: the shape does not fit one CU's LDS");
     if (pivot_rule == LP_PIVOT_DEVEX && lp_batched_two_phase_devex_lds_bytes(d.m, d.n) > 160 * 1024)
         LP_FAIL(ctx, LP_BAD_ARG, "batched two-phase Devex: the tableau and the weights do not fit one CU's LDS (lp_batched_devex_fits)");
-    // small tableaus: four waves, so that several LPs share a CU; the rest: sixteen
-    if ((size_t)(d.m + 1) * (d.n + 1) <= 4096) return two_phase_launch<256>(ctx, d, pivot_rule);
-    return two_phase_launch<1024>(ctx, d, pivot_rule);
+    const size_t cells = (size_t)(d.m + 1) * (d.n + 1);
+    if (pivot_rule == LP_PIVOT_DEVEX)
+        return lp_launch_per_lp(ctx, cells, k_batched_two_phase_devex<256>, k_batched_two_phase_devex<1024>,
+                                lp_batched_two_phase_devex_lds_bytes(d.m, d.n), d);
+    const size_t shm = lp_batched_two_phase_lds_bytes(d.m, d.n, nullptr);
+    if (pivot_rule == LP_PIVOT_BLAND)
+        return lp_launch_per_lp(ctx, cells, k_batched_two_phase_bland<256>, k_batched_two_phase_bland<1024>, shm, d);
+    return lp_launch_per_lp(ctx, cells, k_batched_two_phase<256>, k_batched_two_phase<1024>, shm, d);
 }
