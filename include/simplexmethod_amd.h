@@ -675,6 +675,54 @@ int lp_basis_bounded_ranging_batched(lp_context* ctx, int batch, const double* A
  * and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.                   */
 int lp_basis_bounded_fits(int m, int n);
 
+/* ---- Bounded variables: Farkas and unbounded-ray certificates at a basis ----------------------------------------
+ * Evidence for an LP_INFEASIBLE or LP_UNBOUNDED verdict of lp_simplex_bounded, lp_simplex_bounded_resolve or
+ * lp_mip_bounded_solve, computed after the fact at the basis_out (m, by position, every index in [0, n+m): n+i is the
+ * artificial of row i) and at_upper_out (n, 0/1) they stopped at (the definition is
+ * tests/ref/bounded_certificate_ref.c).  Everything is fp64 and in the caller's original variables, as in
+ * lp_basis_bounded_duals: a non-basic column is held at v_j = hi_j when flagged, else lo_j; the flag of a basic column
+ * is not read.
+ *   1. b' = b - sum A_j v_j is lp_basis_bounded_duals' chain; b0 = b - sum A_j lo_j (one fma chain per row, j ascending,
+ *      lo_j != 0.0 only) decides the artificial of row i, the column s_i e_i with s_i = -1 when b0_i < -eps and +1
+ *      otherwise: lp_simplex_bounded's row flip, so its phase-I basis passes as it is;
+ *   2. B^-1 and xB by lp_basis_ranging's crash on [B | I | b']; alpha[t][j] = (B^-1 A)[t][j], one fma chain per entry
+ *      in row order;
+ *   3. a weight vector g over the original columns passes the sign test when every non-basic j has g_j >= -eps if held
+ *      at lo_j and g_j <= eps if held at hi_j (basic columns are not tested; a fixed column is tested by its flag);
+ *   4. phase-I case (an artificial is basic): f = -(sum of the rows of B^-1 at the artificial positions, in position
+ *      order), g_j = f^T A_j.  FARKAS when the artificials' xB, summed in artificial-index order, exceed eps and g
+ *      passes.  value = b'^T f (one chain in row order), index -1;
+ *   5. dual-simplex case (no artificial, some position violated: xB[t] < L_t - eps, or xB[t] > H_t + eps with H_t
+ *      finite; L_t, H_t the bounds of basis[t]): the first violated t whose row passes gives FARKAS with index t; below:
+ *      f = B^-1[t][:], g = alpha[t][:]; above: f = -B^-1[t][:], g = -alpha[t][:].  value = b'^T f, then - L_t (when
+ *      L_t != 0.0) below, + H_t above: xB[t] - L_t or H_t - xB[t] up to rounding;
+ *   6. ray case (otherwise): d_j = c_j - sum_t c[basis[t]] alpha[t][j], one chain in position order (lp_basis_certificate's
+ *      d, not the duals').  The first non-basic, unflagged j with hi_j = +inf, d_j > eps (max) or d_j < -eps (min), and
+ *      for every t alpha[t][j] <= eps and (alpha[t][j] >= -eps or H_t = +inf) gives RAY: r[j] = 1,
+ *      r[basis[t]] = -alpha[t][j], +0.0 elsewhere; value d_j, index j.
+ * What a certificate proves, with g = A^T f.  FARKAS: f^T b < min over the box of f^T A x = sum_j min(g_j lo_j,
+ * g_j hi_j), so no x in the box satisfies A x = b.  RAY: A r = 0 (to rounding), r >= -eps, r_k <= eps wherever hi_k is
+ * finite, and c^T r = d_j of the improving sign.  A certificate is emitted only when it passes its own eps test: at the
+ * eps boundary the answer is NONE, never a wrong vector.  Outputs as lp_basis_certificate (the LP_CERT_* kinds; farkas m,
+ * NaN unless FARKAS; ray n, NaN unless RAY; value NaN for NONE; index), every pointer required.
+ *   - the status: LP_OPTIMAL (computed; kind_out says what was found), LP_SINGULAR (the crash failed or an index
+ *     repeats) or LP_INFEASIBLE (some hi_j < lo_j: crossed bounds need no vector); the last two with NONE, NaN and -1.
+ *     LP_BAD_ARG for everything lp_basis_bounded_duals refuses about lo, hi and the flags, a basis index outside
+ *     [0, n+m), eps < 0 or NaN, a NULL pointer and a shape beyond lp_basis_bounded_certificate_fits (there is no per-LP
+ *     host path).
+ * With lo = 0, hi = +inf and no flag every output is lp_basis_certificate's bit for bit.                          */
+int lp_basis_bounded_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out, int* index_out);
+/* A batch of LPs of one shape and sense: arrays as lp_basis_bounded_duals_batched; farkas_out batch*m, ray_out batch*n,
+ * kind / value / index / status batch.  run_status (batch ints, may be NULL) chains a bounded solve, re-solve or
+ * branch-and-bound: an LP whose entry is neither LP_INFEASIBLE nor LP_UNBOUNDED keeps that status, gets NONE / NaN / -1
+ * and its basis is not crashed (it must still pass the checks); an LP whose certificate was computed keeps its entry as
+ * its status too (LP_OPTIMAL without run_status), as in lp_batched_certificates.  A bad bound, index or flag in any LP
+ * refuses the whole call (LP_BAD_ARG); a singular basis and crossed bounds are that LP's status.                    */
+int lp_basis_bounded_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, const int* run_status, int maximize, double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out, int* index_out, int* status_out);
+/* 1: lp_simplex_bounded_fits(m, n) and the certificate kernel's LDS carve (lp_basis_certificate_fits' plus b', the held
+ * values and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.            */
+int lp_basis_bounded_certificate_fits(int m, int n);
+
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec
  * README.md:27,40-42; per-basis kernel = Canonical::GetBasicSolution /

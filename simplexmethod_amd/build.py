@@ -402,6 +402,28 @@ def build_bounded_sens_ref(force=False, verbose=False):
     return BOUNDED_SENS_REF_LIB
 
 
+BOUNDED_CERTIFICATE_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_certificate_ref.so")
+
+
+def build_bounded_certificate_ref(force=False, verbose=False):
+    """tests/ref/bounded_certificate_ref.c (which includes certificate_ref.c, ranging_ref.c and duals_ref.c) ->
+    tests/ref/_build/libbounded_certificate_ref.so: Farkas and ray certificates of a bounded-variable LP at a given
+    basis and flags the tests compare against; flags as build_certificate_ref."""
+    src = os.path.join(TESTS_REF, "bounded_certificate_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("certificate_ref.c", "ranging_ref.c", "duals_ref.c")]
+    if not force and _newer(BOUNDED_CERTIFICATE_REF_LIB, deps):
+        return BOUNDED_CERTIFICATE_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_CERTIFICATE_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_CERTIFICATE_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_CERTIFICATE_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -418,6 +440,7 @@ def build_all(force=False, verbose=False):
     build_bounded_resolve_ref(force, verbose)
     build_mip_bounded_ref(force, verbose)
     build_bounded_sens_ref(force, verbose)
+    build_bounded_certificate_ref(force, verbose)
     return hip, host
 
 

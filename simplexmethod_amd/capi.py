@@ -165,6 +165,11 @@ SIGNATURES = {
     "lp_basis_bounded_ranging_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                    C.c_int, C.c_double, _dp, _ip, _ip, _dp, _ip, _ip]),
     "lp_basis_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_certificate": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                               C.c_double, _ip, _dp, _dp, _dp, _ip]),
+    "lp_basis_bounded_certificate_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
+                                                       _ip, _ip, C.c_int, C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
+    "lp_basis_bounded_certificate_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -845,6 +850,47 @@ class Context:
     def basis_bounded_fits(self, m, n):
         """lp_basis_bounded_fits: True if an m x n bounded LP runs the analysis kernel."""
         return bool(self.lib.lp_basis_bounded_fits(m, n))
+
+    # ---- Farkas and unbounded-ray certificates of a bounded-variable LP at a basis --------------
+    def basis_bounded_certificate(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
+        """lp_basis_bounded_certificate: evidence for an infeasible or unbounded verdict of the LP of bounded() at
+        `basis` (m; index n+i: the artificial of row i) and `at_upper` (n, 0/1), normally a result's, in the original
+        variables.  The dict of basis_certificate: FARKAS proves f.b < min over the box of f^T A x, RAY is a direction
+        of the box along which the objective improves without limit.  status OPTIMAL means the certificate was
+        computed; SINGULAR for a singular crash or a repeated index, INFEASIBLE for some hi < lo (then NONE).  A bad
+        bound, index or flag, a negative eps or a shape beyond basis_bounded_certificate_fits raises LPError with code
+        BAD_ARG."""
+        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        kind, index = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        farkas, ray, value = np.zeros(m), np.zeros(n), np.zeros(1)
+        rc = self.check(self.lib.lp_basis_bounded_certificate(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                              _i(basis), _i(at_upper), int(maximize), float(eps),
+                                                              _i(kind), _d(farkas), _d(ray), _d(value), _i(index)))
+        return dict(status=rc, kind=int(kind[0]), farkas=farkas, ray=ray, value=float(value[0]), index=int(index[0]))
+
+    def basis_bounded_certificate_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS,
+                                          run_status=None):
+        """lp_basis_bounded_certificate_batched: arrays as bounded_duals_batched; run_status (batch) or None, normally
+        the statuses of the bounded_batched(), bounded_resolve_batched() or mip_bounded_solve_batched() call the bases
+        come from: only LPs whose entry is INFEASIBLE or UNBOUNDED get a certificate (and keep the entry as their
+        status when it was computed), the others keep their entry and get NONE.  The dict of
+        basis_bounded_certificate with a leading batch axis; status, kind, value and index (batch)."""
+        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        if run_status is not None:
+            run_status = np.ascontiguousarray(run_status, dtype=np.int32).reshape(-1)
+            if run_status.size != batch:
+                raise ValueError("run_status must have batch entries")
+        kind, index, st = np.zeros(batch, np.int32), np.zeros(batch, np.int32), np.zeros(batch, np.int32)
+        farkas, ray, value = np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
+        self.check(self.lib.lp_basis_bounded_certificate_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo),
+                                                                 _d(hi), _i(basis), _i(at_upper), _i(run_status),
+                                                                 int(maximize), float(eps), _i(kind), _d(farkas),
+                                                                 _d(ray), _d(value), _i(index), _i(st)))
+        return dict(status=st, kind=kind, farkas=farkas, ray=ray, value=value, index=index)
+
+    def basis_bounded_certificate_fits(self, m, n):
+        """lp_basis_bounded_certificate_fits: True if an m x n bounded LP runs the certificate kernel."""
+        return bool(self.lib.lp_basis_bounded_certificate_fits(m, n))
 
     # ---- branch-and-bound over the bounds of a bounded-variable LP -----------------------------
     def mip_bounded_solve(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,

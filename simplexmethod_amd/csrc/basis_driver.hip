@@ -5,8 +5,9 @@
 // the host) and lp_batched_X (a batch handle after its run).  All three put the inputs on the device (upload, or
 // where a resident run left them: batch_inputs) and call X_on_device, which launches the analysis's kernel when the
 // shape fits it and otherwise runs its single-LP device path one LP after another (per_lp).
-// The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip) have two entry points each (one LP, a
-// batch from the host) and no per-LP path: bounded_sens uploads, launches and downloads in one call.
+// The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip, basis_bounded_certificate.hip) have two
+// entry points each (one LP, a batch from the host) and no per-LP path: bounded_sens and bounded_certificate upload,
+// launch and download in one call.
 #include <cmath>
 #include <functional>
 
@@ -353,9 +354,10 @@ int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* 
 int lp_basis_bounded_fits(int m, int n) { return lp_basis_bounded_fits_shape(m, n) ? 1 : 0; }
 
 // The checks of lp_simplex_bounded_resolve on every LP of the batch (the pointers and dimensions are the caller's):
-// lo finite, hi not NaN, flags 0 or 1 and 1 only under a finite hi, basis indices in [0, n), and the fit.
+// lo finite, hi not NaN, flags 0 or 1 and 1 only under a finite hi, basis indices in [0, n), or in [0, n + m) for the
+// certificates (`artificials`), and the fit of the analysis's kernel.
 static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m, int n, const double* lo,
-                              const double* hi, const int* basis, const int* at_upper) {
+                              const double* hi, const int* basis, const int* at_upper, bool artificials = false) {
     const size_t N = (size_t)batch * n;
     for (size_t j = 0; j < N; ++j) {
         if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
@@ -364,9 +366,11 @@ static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m
         if (at_upper[j] && hi[j] == INFINITY)   // (hi = -inf is a crossed bound: that LP's LP_INFEASIBLE)
             LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
     }
-    if (basis_in_range(basis, batch * m, n)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
-    if (!lp_basis_bounded_fits_shape(m, n))
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_basis_bounded_fits)");
+    if (basis_in_range(basis, batch * m, artificials ? n + m : n))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
+    if (artificials ? !lp_basis_bounded_certificate_fits_shape(m, n) : !lp_basis_bounded_fits_shape(m, n))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_basis_bounded" +
+                                     (artificials ? "_certificate" : "") + "_fits)");
     return LP_OPTIMAL;
 }
 
@@ -664,6 +668,118 @@ int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, do
     return rc ? rc
               : certificate_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, eps, kind_out, farkas_out, ray_out,
                                       value_out, index_out, status_out);
+}
+
+// ===========================================================================
+// Farkas and unbounded-ray certificates of a bounded-variable LP at a given basis and flags
+// (basis_bounded_certificate.hip): one LP per workgroup for lp_basis_bounded_certificate_fits shapes only
+// ===========================================================================
+
+int lp_basis_bounded_certificate_fits(int m, int n) { return lp_basis_bounded_certificate_fits_shape(m, n) ? 1 : 0; }
+
+struct BoundedCertificateOut {
+    int* kind;
+    double *farkas, *ray, *value;
+    int* index;
+};
+
+// One allocation for the inputs and the outputs of the batch, uploads queued on the context's stream, one launch of
+// k_batched_bounded_certificate, one download.  run_status may be nullptr.
+static int bounded_certificate(lp_context* ctx, const BoundedSensIn& in, const int* run_status, int maximize, double eps,
+                               const BoundedCertificateOut& out, int* status_out) {
+    const int batch = in.batch, m = in.m, n = in.n;
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, nf = B * m, nr = B * n;
+    const size_t in_d = B * ((size_t)m * n + m + 3 * (size_t)n), in_i = B * ((size_t)m + n + (run_status ? 1 : 0));
+    const size_t out_d = nf + nr + B, out_i = 3 * B;
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (in_d + out_d) + sizeof(int) * (in_i + out_i)));
+    double* dA = reinterpret_cast<double*>(buf.ptr);   // the doubles first
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    double* dlo = dc + B * n;
+    double* dhi = dlo + B * n;
+    double* dout = dhi + B * n;
+    int* dbasis = reinterpret_cast<int*>(dout + out_d);
+    int* dup = dbasis + B * m;
+    int* drun = dup + B * n;
+    int* iout = drun + (run_status ? B : 0);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, in.A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, in.b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, in.c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dlo, in.lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dhi, in.hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, in.basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dup, in.at_upper, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && run_status) e = hipMemcpyAsync(drun, run_status, sizeof(int) * B, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("bounded basis certificate upload: ") + hipGetErrorString(e));
+    BasisBoundedCertificateDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.eps = eps;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.lo = dlo;
+    d.hi = dhi;
+    d.basis = dbasis;
+    d.at_upper = dup;
+    d.run_status = run_status ? drun : nullptr;
+    d.farkas = dout;
+    d.ray = d.farkas + nf;
+    d.value = d.ray + nr;
+    d.kind = iout;
+    d.index = d.kind + B;
+    d.status = d.index + B;
+    int rc = lp_basis_bounded_certificate_launch(ctx, d);
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "bounded basis certificate", {{out.farkas, d.farkas, sizeof(double) * nf},
+                                                            {out.ray, d.ray, sizeof(double) * nr},
+                                                            {out.value, d.value, sizeof(double) * B},
+                                                            {out.kind, d.kind, sizeof(int) * B},
+                                                            {out.index, d.index, sizeof(int) * B},
+                                                            {status_out, d.status, sizeof(int) * B}});
+    return rc;
+}
+
+int lp_basis_bounded_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                 const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                 int maximize, double eps, int* kind_out, double* farkas_out, double* ray_out,
+                                 double* value_out, int* index_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !kind_out || !farkas_out || !ray_out || !value_out ||
+        !index_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: bad dimensions");
+    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: eps must be >= 0");
+    int rc = bounded_basis_args(ctx, "lp_basis_bounded_certificate", 1, m, n, lo, hi, basis, at_upper, true);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = bounded_certificate(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, maximize, eps,
+                             {kind_out, farkas_out, ray_out, value_out, index_out}, &status);
+    return rc ? rc : status;
+}
+
+int lp_basis_bounded_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                         const double* c, const double* lo, const double* hi, const int* basis,
+                                         const int* at_upper, const int* run_status, int maximize, double eps,
+                                         int* kind_out, double* farkas_out, double* ray_out, double* value_out,
+                                         int* index_out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !kind_out || !farkas_out || !ray_out || !value_out ||
+        !index_out || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate_batched: null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate_batched: bad dimensions");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate_batched: eps must be >= 0");
+    const int rc = bounded_basis_args(ctx, "lp_basis_bounded_certificate_batched", batch, m, n, lo, hi, basis, at_upper,
+                                      true);
+    if (rc) return rc;
+    return bounded_certificate(ctx, {batch, m, n, A, b, c, lo, hi, basis, at_upper}, run_status, maximize, eps,
+                               {kind_out, farkas_out, ray_out, value_out, index_out}, status_out);
 }
 
 // ===========================================================================

@@ -7,7 +7,7 @@
 //   barriers: three per call (clear, set, read); the word is free again when the call returns
 //   included by: k_batched_resolve, k_batched_bounded_resolve, k_batched_mip, k_batched_mip_bounded,
 //             k_batched_parametric, k_batched_parametric_cost (ANY_WORD 3); k_batched_duals, k_batched_ranging,
-//             k_batched_certificate, k_batched_bounded_sens (ANY_WORD 2)
+//             k_batched_certificate, k_batched_bounded_sens, k_batched_bounded_certificate (ANY_WORD 2)
 // (__syncthreads_or would add static LDS beside the 160 KB of the largest shapes)
     auto block_any = [&](int flag) {
         if (tid == 0) pub[ANY_WORD] = 0;

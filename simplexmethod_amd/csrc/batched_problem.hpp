@@ -376,6 +376,35 @@ size_t lp_basis_bounded_lds_bytes(int m, int n);
 bool lp_basis_bounded_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
 int lp_basis_bounded_launch(lp_context* ctx, const BasisBoundedDev& d, bool ranging);   // fitting shapes, else LP_BAD_ARG
 
+// Farkas and unbounded-ray certificates of bounded-variable LPs at given bases and at-upper flags, one LP per
+// workgroup (basis_bounded_certificate.hip; the definition is tests/ref/bounded_certificate_ref.c): the ranging crash
+// on [B | I | b'] with the artificials' columns, then the case's alpha chains under the box's sign test.
+struct BasisBoundedCertificateDev {
+    int batch, m, n;
+    int maximize;
+    double eps;
+    const double* A;         // batch x (m*n), each column-major
+    const double* b;         // batch x m
+    const double* c;         // batch x n
+    const double* lo;        // batch x n, finite
+    const double* hi;        // batch x n, finite or +inf
+    const int* basis;        // batch x m (by position), indices in [0, n+m)
+    const int* at_upper;     // batch x n (0/1; 1 only where hi is finite)
+    const int* run_status;   // batch, or nullptr: only LPs whose entry is LP_INFEASIBLE / LP_UNBOUNDED get a
+                             // certificate, the others keep their entry and get NONE
+    int* kind;               // batch: LP_CERT_*
+    double* farkas;          // batch x m
+    double* ray;             // batch x n
+    double* value;           // batch
+    int* index;              // batch
+    int* status;             // batch
+};
+
+// basis_bounded_certificate.hip
+size_t lp_basis_bounded_certificate_lds_bytes(int m, int n);
+bool lp_basis_bounded_certificate_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
+int lp_basis_bounded_certificate_launch(lp_context* ctx, const BasisBoundedCertificateDev& d);   // fitting shapes
+
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP
 // entry its per-LP fallback calls; everything else is the same for the three kinds.

@@ -587,6 +587,45 @@ public:
         return out;
     }
 
+    // Evidence for a bounded result that is not optimal (lp_basis_bounded_certificate) at its basis and flags, under
+    // the bounds lo, hi it was solved with, with the given eps and the problem's sense, in the original variables.  A
+    // basis index n+i is row i's artificial, so the phase-I basis of an infeasible boundedSimplex(lo, hi, false) result
+    // passes as it is, as does the basis an infeasible or unbounded boundedResolve stopped at.  kind LP_CERT_FARKAS:
+    // with g = A^T farkas, b.farkas < sum_j min(g_j lo_j, g_j hi_j) (no x in the box solves A x = b); LP_CERT_RAY:
+    // A ray = 0, ray >= -eps, ray_k <= eps wherever hi_k is finite and c.ray = value improving; LP_CERT_NONE: nothing
+    // that passes its own eps test.  status: the result's LP_INFEASIBLE / LP_UNBOUNDED when a certificate was computed
+    // (an LP with some hi < lo is LP_INFEASIBLE with NONE), LP_SINGULAR when the crash fails; any other result keeps
+    // its status and gets NONE.  Exceptions as boundedDuals.
+    Certificate boundedCertificate(const std::vector<double>& lo, const std::vector<double>& hi,
+                                   const BoundedResult& from, double eps = EPS) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedCertificate: lo / hi size != cols(A)");
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        Certificate out;
+        out.farkas = lpla::VectorXd::Zero(m);
+        out.ray = lpla::VectorXd::Zero(n);
+        for (int i = 0; i < m; ++i) out.farkas[i] = nan;
+        for (int j = 0; j < n; ++j) out.ray[j] = nan;
+        out.status = from.status;
+        if (from.status == LP_INFEASIBLE || from.status == LP_UNBOUNDED) {
+            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+                throw std::invalid_argument(
+                    "Solver::boundedCertificate: the result's basis / atUpper size != rows(A) / cols(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            const int st = lp_basis_bounded_certificate(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                        from.basis.data(), from.atUpper.data(),
+                                                        _problem.IsMaximization() ? 1 : 0, eps, &out.kind,
+                                                        out.farkas.data(), out.ray.data(), &out.value, &out.index);
+            if (st < 0 || st == LP_BAD_ARG) lpgpu::throw_for_status(st, ctx);
+            if (st != LP_OPTIMAL) out.status = st;
+        }
+        return out;
+    }
+
 private:
     Canonical _problem;  // deep copy, as in the reference (:285)
     int _device;
