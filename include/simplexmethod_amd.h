@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits; lp_basis_bounded_duals, lp_basis_bounded_duals_batched, lp_basis_bounded_ranging, lp_basis_bounded_ranging_batched, lp_basis_bounded_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits; lp_basis_bounded_duals, lp_basis_bounded_duals_batched, lp_basis_bounded_ranging, lp_basis_bounded_ranging_batched, lp_basis_bounded_fits; lp_basis_bounded_parametric, lp_basis_bounded_parametric_batched, lp_basis_bounded_parametric_cost, lp_basis_bounded_parametric_cost_batched, lp_basis_bounded_parametric_fits, lp_basis_bounded_parametric_cost_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -722,6 +722,55 @@ int lp_basis_bounded_certificate_batched(lp_context* ctx, int batch, const doubl
 /* 1: lp_simplex_bounded_fits(m, n) and the certificate kernel's LDS carve (lp_basis_certificate_fits' plus b', the held
  * values and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.            */
 int lp_basis_bounded_certificate_fits(int m, int n);
+
+/* ---- Parametric right-hand side and parametric cost of a bounded-variable LP (the definition is
+ * tests/ref/bounded_parametric_ref.c, numbered steps in its header) ----
+ * lp_basis_parametric and lp_basis_parametric_cost for A x = b, lo <= x <= hi: every breakpoint of
+ *   z*(t) = opt { c.x : A x = b + t d, lo <= x <= hi }        (lp_basis_bounded_parametric, d of m entries), or of
+ *   z*(t) = opt { (c + t g).x : A x = b, lo <= x <= hi }      (lp_basis_bounded_parametric_cost, g of n entries)
+ * for t from 0 up to t_max (+inf allowed), from the basis[m] and at_upper[n] that lp_simplex_bounded, its re-solve or
+ * lp_mip_bounded returned at t = 0.  The bounds do not move with t.
+ *   - the tableau is lp_simplex_bounded_resolve's (x = lo + x', flagged columns held complemented) with d as a second
+ *     right-hand column or g as a second cost row; the given basis is installed by its crash and must be primal and
+ *     dual feasible at t = 0 under eps (no position below 0 or above its width, no improving reduced cost), else
+ *     LP_BAD_ARG: re-solve first;
+ *   - RHS path: per segment the first strict minimum over the positions of tau = -beta_t / delta_t (delta_t < -eps) and
+ *     tau = (U_t - beta_t) / delta_t (delta_t > eps, U_t finite); t* = max(tau, t_k).  The blocking variable leaves by
+ *     one dual pivot (the re-solve's entering chain over its row, read complemented when it is blocked above).  Ends:
+ *     LP_OPTIMAL at t_max, LP_INFEASIBLE at t* when nothing can enter (no feasible point beyond), LP_ITER_LIMIT at t*
+ *     after max_breaks pivots.  For max z* is concave in t, for min convex;
+ *   - cost path: per segment the first strict minimum over the non-basic columns in index order of tau = -d_j / delta_j
+ *     (delta_j > eps for max, < -eps for min); the column enters by lp_simplex_bounded's ratio test: a pivot (the
+ *     leaving variable may stop at its upper bound) or a bound flip, which is recorded as a breakpoint with
+ *     enter = leave.  Ends: LP_OPTIMAL at t_max, LP_UNBOUNDED at t* (no row blocks and the column has no upper bound),
+ *     LP_ITER_LIMIT at t* after max_breaks pivots and flips.  For max z* is convex in t, for min concave;
+ *   - outputs as lp_basis_parametric (nseg_out; t_out / obj_out max_breaks+2; slope_out / enter_out / leave_out
+ *     max_breaks+1; basis_out m; NaN / -1 past the path), obj and slope in the caller's variables (a non-basic column
+ *     counts at the bound it is held at), and beside them side_out (max_breaks+1): the bound at which leave_out[k]
+ *     stops, 0 lower, 1 upper, -1 where leave_out[k] is -1 (for a flip: the bound flipped to), and at_upper_out (n): the
+ *     flags that go with basis_out.  Every pointer is required;
+ *   - the status: the path's end as above; LP_SINGULAR (the crash failed or an index repeats), LP_INFEASIBLE with
+ *     nseg 0 (some hi_j < lo_j) and LP_BAD_ARG for a start that is not optimal: these give nseg 0, NaN / -1 and the
+ *     given basis and flags back.  LP_BAD_ARG also for everything lp_basis_bounded_duals refuses about lo, hi, the
+ *     flags and the basis, t_max < 0 or NaN, eps < 0 or NaN, max_breaks < 0, a NULL pointer and a shape beyond the
+ *     path's fits call (there is no per-LP host path; nothing is launched).
+ * With lo = 0, hi = +inf and no flag every output shared with lp_basis_parametric / lp_basis_parametric_cost equals
+ * theirs bit for bit, side_out is 0 wherever leave_out >= 0 and at_upper_out is 0.                                 */
+int lp_basis_bounded_parametric(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, const double* d, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out);
+int lp_basis_bounded_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out);
+/* A batch of LPs of one shape and sense, one LP per workgroup: input arrays as lp_basis_bounded_duals_batched, d batch*m
+ * or g batch*n; output arrays and per-LP strides as lp_basis_parametric_batched, side_out the size of leave_out,
+ * at_upper_out batch*n, status_out batch.  run_status (batch ints, may be NULL) chains lp_simplex_bounded_batched or
+ * lp_simplex_bounded_resolve_batched: an LP whose entry is not LP_OPTIMAL keeps it, gets nseg 0, NaN / -1 and its basis
+ * and flags back, and is not crashed.  A bad bound, index or flag in any LP refuses the whole call (LP_BAD_ARG); a
+ * singular basis, crossed bounds and a start that is not optimal are that LP's status.                              */
+int lp_basis_bounded_parametric_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, const int* run_status, int maximize, const double* d, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out, int* status_out);
+int lp_basis_bounded_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, const int* run_status, int maximize, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out, int* status_out);
+/* 1: lp_simplex_bounded_fits(m, n) and the path's LDS carve (the bounded re-solve's with one more right-hand column,
+ * or one more cost row, plus hi, c, g and the slot of every column) fits one CU's 160 KB (64 x 192 does for both); 0
+ * otherwise.  Host calls, no context.                                                                              */
+int lp_basis_bounded_parametric_fits(int m, int n);
+int lp_basis_bounded_parametric_cost_fits(int m, int n);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

@@ -424,6 +424,28 @@ def build_bounded_certificate_ref(force=False, verbose=False):
     return BOUNDED_CERTIFICATE_REF_LIB
 
 
+BOUNDED_PARAMETRIC_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_parametric_ref.so")
+
+
+def build_bounded_parametric_ref(force=False, verbose=False):
+    """tests/ref/bounded_parametric_ref.c (which includes bounded_resolve_ref.c and bounded_ref.c) ->
+    tests/ref/_build/libbounded_parametric_ref.so: the parametric right-hand-side and cost paths of a bounded-variable
+    LP from an optimal basis and flags the tests compare against; flags as build_bounded_resolve_ref."""
+    src = os.path.join(TESTS_REF, "bounded_parametric_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("bounded_resolve_ref.c", "bounded_ref.c")]
+    if not force and _newer(BOUNDED_PARAMETRIC_REF_LIB, deps):
+        return BOUNDED_PARAMETRIC_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_PARAMETRIC_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_PARAMETRIC_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_PARAMETRIC_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -441,6 +463,7 @@ def build_all(force=False, verbose=False):
     build_mip_bounded_ref(force, verbose)
     build_bounded_sens_ref(force, verbose)
     build_bounded_certificate_ref(force, verbose)
+    build_bounded_parametric_ref(force, verbose)
     return hip, host
 
 

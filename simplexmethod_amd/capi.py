@@ -170,6 +170,20 @@ SIGNATURES = {
     "lp_basis_bounded_certificate_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
                                                        _ip, _ip, C.c_int, C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
     "lp_basis_bounded_certificate_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_parametric": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, _dp,
+                                              C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _ip,
+                                              _ip]),
+    "lp_basis_bounded_parametric_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
+                                                      _ip, _ip, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip,
+                                                      _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "lp_basis_bounded_parametric_cost": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                   _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip,
+                                                   _ip, _ip, _ip]),
+    "lp_basis_bounded_parametric_cost_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                           _ip, _ip, _ip, C.c_int, _dp, C.c_double, C.c_double,
+                                                           C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "lp_basis_bounded_parametric_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_parametric_cost_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -891,6 +905,87 @@ class Context:
     def basis_bounded_certificate_fits(self, m, n):
         """lp_basis_bounded_certificate_fits: True if an m x n bounded LP runs the certificate kernel."""
         return bool(self.lib.lp_basis_bounded_certificate_fits(m, n))
+
+    # ---- parametric right-hand side and cost of a bounded-variable LP from an optimal basis -------
+    def _bounded_parametric(self, fn, width, A, b, c, lo, hi, basis, at_upper, direction, t_max, maximize, eps,
+                            max_breaks):
+        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        direction = _f64(direction).reshape(-1)
+        if direction.size != (n if width == "n" else m):
+            raise ValueError("the direction must have %s entries" % width)
+        mb = max(int(max_breaks), 0)
+        nseg, t, obj, slope, enter, leave, bo, _ = _parametric_out(1, m, mb)
+        side, up = np.zeros((1, mb + 1), np.int32), np.zeros(n, np.int32)
+        rc = self.check(fn(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize),
+                           _d(direction), float(t_max), float(eps), int(max_breaks), _i(nseg), _d(t), _d(obj),
+                           _d(slope), _i(enter), _i(leave), _i(side), _i(bo), _i(up)))
+        ns = int(nseg[0])
+        return dict(status=rc, t=t[0, :ns + 1] if ns else t[0, :0], obj=obj[0, :ns + 1] if ns else obj[0, :0],
+                    slope=slope[0, :ns], enter=enter[0, :ns], leave=leave[0, :ns], side=side[0, :ns], basis=bo[0],
+                    at_upper=up)
+
+    def _bounded_parametric_batched(self, fn, width, A, b, c, lo, hi, basis, at_upper, direction, t_max, maximize, eps,
+                                    max_breaks, run_status):
+        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        direction = _f64(direction).reshape(-1)
+        if direction.size != batch * (n if width == "n" else m):
+            raise ValueError("the direction must have %s entries per LP" % width)
+        if run_status is not None:
+            run_status = np.ascontiguousarray(run_status, dtype=np.int32).reshape(-1)
+            if run_status.size != batch:
+                raise ValueError("run_status must have batch entries")
+        mb = max(int(max_breaks), 0)
+        out = _parametric_out(batch, m, mb)
+        nseg, t, obj, slope, enter, leave, bo, st = out
+        side, up = np.zeros((batch, mb + 1), np.int32), np.zeros((batch, n), np.int32)
+        self.check(fn(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
+                      _i(run_status), int(maximize), _d(direction), float(t_max), float(eps), int(max_breaks), _i(nseg),
+                      _d(t), _d(obj), _d(slope), _i(enter), _i(leave), _i(side), _i(bo), _i(up), _i(st)))
+        return dict(_parametric_dict(out), side=side, at_upper=up)
+
+    def bounded_parametric(self, A, b, c, lo, hi, basis, at_upper, d, t_max=np.inf, maximize=True, eps=EPS,
+                           max_breaks=MAX_BREAKS):
+        """lp_basis_bounded_parametric: the optimal value of the LP of bounded() along b + t d for t in [0, t_max] from
+        the optimal `basis` (m) and `at_upper` (n, 0/1), normally a result's.  The dict of basis_parametric plus side
+        (nseg): the bound at which leave[k] stops (0 lower, 1 upper, -1 on a last segment that reached t_max) and
+        at_upper (n): the flags that go with the final basis.  status OPTIMAL (reached t_max), INFEASIBLE (infeasible
+        past t[-1], or some hi < lo: empty arrays), ITER_LIMIT (max_breaks pivots done) or SINGULAR (empty arrays).  A
+        basis that is not optimal at t = 0, a bad bound, index or flag, t_max < 0, eps < 0, max_breaks < 0 or a shape
+        beyond bounded_parametric_fits raises LPError with code BAD_ARG."""
+        return self._bounded_parametric(self.lib.lp_basis_bounded_parametric, "m", A, b, c, lo, hi, basis, at_upper, d,
+                                        t_max, maximize, eps, max_breaks)
+
+    def bounded_parametric_batched(self, A, b, c, lo, hi, basis, at_upper, d, t_max=np.inf, maximize=True, eps=EPS,
+                                   max_breaks=MAX_BREAKS, run_status=None):
+        """lp_basis_bounded_parametric_batched: arrays as bounded_duals_batched, d (batch, m); run_status (batch) or
+        None, normally the statuses of the bounded_batched() or bounded_resolve_batched() call the bases come from: an
+        LP whose entry is not OPTIMAL keeps it and gets nseg 0.  The dict of basis_parametric_batched plus side
+        (batch, max_breaks+1) and at_upper (batch, n), padded with NaN / -1 past each path."""
+        return self._bounded_parametric_batched(self.lib.lp_basis_bounded_parametric_batched, "m", A, b, c, lo, hi,
+                                                basis, at_upper, d, t_max, maximize, eps, max_breaks, run_status)
+
+    def bounded_parametric_cost(self, A, b, c, lo, hi, basis, at_upper, g, t_max=np.inf, maximize=True, eps=EPS,
+                                max_breaks=MAX_BREAKS):
+        """lp_basis_bounded_parametric_cost: the optimal value of the LP of bounded() along c + t g for t in
+        [0, t_max].  The dict of bounded_parametric; a bound flip is a breakpoint with enter[k] == leave[k] and side[k]
+        the bound flipped to.  status OPTIMAL (reached t_max), UNBOUNDED (unbounded past t[-1]), ITER_LIMIT
+        (max_breaks pivots and flips done), INFEASIBLE (some hi < lo: empty arrays) or SINGULAR (empty arrays)."""
+        return self._bounded_parametric(self.lib.lp_basis_bounded_parametric_cost, "n", A, b, c, lo, hi, basis,
+                                        at_upper, g, t_max, maximize, eps, max_breaks)
+
+    def bounded_parametric_cost_batched(self, A, b, c, lo, hi, basis, at_upper, g, t_max=np.inf, maximize=True,
+                                        eps=EPS, max_breaks=MAX_BREAKS, run_status=None):
+        """lp_basis_bounded_parametric_cost_batched: as bounded_parametric_batched with g (batch, n)."""
+        return self._bounded_parametric_batched(self.lib.lp_basis_bounded_parametric_cost_batched, "n", A, b, c, lo,
+                                                hi, basis, at_upper, g, t_max, maximize, eps, max_breaks, run_status)
+
+    def bounded_parametric_fits(self, m, n):
+        """lp_basis_bounded_parametric_fits: True if an m x n bounded LP runs the RHS path's kernel."""
+        return bool(self.lib.lp_basis_bounded_parametric_fits(m, n))
+
+    def bounded_parametric_cost_fits(self, m, n):
+        """lp_basis_bounded_parametric_cost_fits: True if an m x n bounded LP runs the cost path's kernel."""
+        return bool(self.lib.lp_basis_bounded_parametric_cost_fits(m, n))
 
     # ---- branch-and-bound over the bounds of a bounded-variable LP -----------------------------
     def mip_bounded_solve(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,

@@ -5,9 +5,9 @@
 // the host) and lp_batched_X (a batch handle after its run).  All three put the inputs on the device (upload, or
 // where a resident run left them: batch_inputs) and call X_on_device, which launches the analysis's kernel when the
 // shape fits it and otherwise runs its single-LP device path one LP after another (per_lp).
-// The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip, basis_bounded_certificate.hip) have two
-// entry points each (one LP, a batch from the host) and no per-LP path: bounded_sens and bounded_certificate upload,
-// launch and download in one call.
+// The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip, basis_bounded_certificate.hip,
+// basis_bounded_parametric.hip) have two entry points each (one LP, a batch from the host) and no per-LP path:
+// bounded_sens, bounded_certificate and bounded_parametric upload, launch and download in one call.
 #include <cmath>
 #include <functional>
 
@@ -355,9 +355,9 @@ int lp_basis_bounded_fits(int m, int n) { return lp_basis_bounded_fits_shape(m, 
 
 // The checks of lp_simplex_bounded_resolve on every LP of the batch (the pointers and dimensions are the caller's):
 // lo finite, hi not NaN, flags 0 or 1 and 1 only under a finite hi, basis indices in [0, n), or in [0, n + m) for the
-// certificates (`artificials`), and the fit of the analysis's kernel.
-static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m, int n, const double* lo,
-                              const double* hi, const int* basis, const int* at_upper, bool artificials = false) {
+// certificates (`artificials`): bounded_basis_values; bounded_basis_args adds the fit of the analysis's kernel.
+static int bounded_basis_values(lp_context* ctx, const char* who, int batch, int m, int n, const double* lo,
+                                const double* hi, const int* basis, const int* at_upper, bool artificials) {
     const size_t N = (size_t)batch * n;
     for (size_t j = 0; j < N; ++j) {
         if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
@@ -368,6 +368,13 @@ static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m
     }
     if (basis_in_range(basis, batch * m, artificials ? n + m : n))
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
+    return LP_OPTIMAL;
+}
+
+static int bounded_basis_args(lp_context* ctx, const char* who, int batch, int m, int n, const double* lo,
+                              const double* hi, const int* basis, const int* at_upper, bool artificials = false) {
+    const int rc = bounded_basis_values(ctx, who, batch, m, n, lo, hi, basis, at_upper, artificials);
+    if (rc) return rc;
     if (artificials ? !lp_basis_bounded_certificate_fits_shape(m, n) : !lp_basis_bounded_fits_shape(m, n))
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_basis_bounded" +
                                      (artificials ? "_certificate" : "") + "_fits)");
@@ -1084,6 +1091,209 @@ int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_
               : parametric_cost_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, t_max, eps, max_breaks,
                                           nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out,
                                           status_out);
+}
+
+// ===========================================================================
+// Parametric right-hand side and parametric cost of a bounded-variable LP from an optimal basis and its at-upper flags
+// (basis_bounded_parametric.hip): one LP per workgroup for lp_basis_bounded_parametric_fits / _cost_fits shapes only;
+// as in the bounded family there is no handle and no per-LP path
+// ===========================================================================
+
+int lp_basis_bounded_parametric_fits(int m, int n) { return lp_basis_bounded_parametric_fits_shape(m, n, false) ? 1 : 0; }
+
+int lp_basis_bounded_parametric_cost_fits(int m, int n) {
+    return lp_basis_bounded_parametric_fits_shape(m, n, true) ? 1 : 0;
+}
+
+struct BoundedParametricOut {
+    int* nseg;
+    double *t, *obj, *slope;
+    int *enter, *leave, *side, *basis, *at_upper;
+};
+
+// LP k without a path: parametric_none, side -1 and the given flags (host) back
+static void bounded_parametric_none(size_t k, int m, int n, int mb, const int* basis, const int* at_upper,
+                                    const BoundedParametricOut& o) {
+    parametric_none(k, m, mb, basis, o.nseg, o.t, o.obj, o.slope, o.enter, o.leave, o.basis);
+    for (size_t q = 0; q < (size_t)mb + 1; ++q) o.side[k * (mb + 1) + q] = -1;
+    std::memcpy(o.at_upper + k * n, at_upper, sizeof(int) * (size_t)n);
+}
+
+// The checks every entry point of the two analyses shares after its null and dimension checks: the path's arguments,
+// the bounds, flags and indices of every LP, and the fit of the path's kernel
+static int bounded_parametric_args(lp_context* ctx, const char* who, const BoundedSensIn& in, bool cost, double t_max,
+                                   double eps, int max_breaks) {
+    int rc = parametric_args(ctx, who, t_max, eps, max_breaks);
+    if (rc) return rc;
+    rc = bounded_basis_values(ctx, who, in.batch, in.m, in.n, in.lo, in.hi, in.basis, in.at_upper, false);
+    if (rc) return rc;
+    if (!lp_basis_bounded_parametric_fits_shape(in.m, in.n, cost))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the shape does not fit one CU's LDS (lp_basis_bounded_parametric" +
+                                     (cost ? "_cost" : "") + "_fits)");
+    return LP_OPTIMAL;
+}
+
+// One allocation for the inputs and the outputs of the batch, uploads queued on the context's stream, one launch of
+// k_batched_bounded_parametric or k_batched_bounded_parametric_cost, one download.  `dir` is d (m per LP) or g (n per
+// LP); run_status may be nullptr.
+static int bounded_parametric(lp_context* ctx, const BoundedSensIn& in, const double* dir, bool cost,
+                              const int* run_status, int maximize, double t_max, double eps, int mb,
+                              const BoundedParametricOut& out, int* status_out) {
+    const int batch = in.batch, m = in.m, n = in.n;
+    LP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1), nd = B * (cost ? n : m);
+    const size_t in_d = B * ((size_t)m * n + m + 3 * (size_t)n) + nd, in_i = B * ((size_t)m + n + (run_status ? 1 : 0));
+    const size_t out_d = 2 * nt + ns, out_i = 3 * ns + B * ((size_t)m + n + 2);
+    lp_device_buffer buf;
+    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (in_d + out_d) + sizeof(int) * (in_i + out_i)));
+    double* dA = reinterpret_cast<double*>(buf.ptr);   // the doubles first
+    double* db = dA + B * m * n;
+    double* dc = db + B * m;
+    double* dlo = dc + B * n;
+    double* dhi = dlo + B * n;
+    double* ddir = dhi + B * n;
+    double* dout = ddir + nd;
+    int* dbasis = reinterpret_cast<int*>(dout + out_d);
+    int* dup = dbasis + B * m;
+    int* drun = dup + B * n;
+    int* iout = drun + (run_status ? B : 0);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dA, in.A, sizeof(double) * B * m * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, in.b, sizeof(double) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, in.c, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dlo, in.lo, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dhi, in.hi, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ddir, dir, sizeof(double) * nd, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbasis, in.basis, sizeof(int) * B * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dup, in.at_upper, sizeof(int) * B * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && run_status) e = hipMemcpyAsync(drun, run_status, sizeof(int) * B, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("bounded basis parametric upload: ") + hipGetErrorString(e));
+    BasisBoundedParametricDev d{};
+    d.batch = batch;
+    d.m = m;
+    d.n = n;
+    d.maximize = maximize ? 1 : 0;
+    d.max_breaks = mb;
+    d.eps = eps;
+    d.t_max = t_max;
+    d.A = dA;
+    d.b = db;
+    d.c = dc;
+    d.lo = dlo;
+    d.hi = dhi;
+    d.dir = ddir;
+    d.basis = dbasis;
+    d.at_upper = dup;
+    d.run_status = run_status ? drun : nullptr;
+    d.t = dout;
+    d.obj = d.t + nt;
+    d.slope = d.obj + nt;
+    d.enter = iout;
+    d.leave = d.enter + ns;
+    d.side = d.leave + ns;
+    d.basis_out = d.side + ns;
+    d.at_upper_out = d.basis_out + B * m;
+    d.nseg = d.at_upper_out + B * n;
+    d.status = d.nseg + B;
+    int rc = lp_basis_bounded_parametric_launch(ctx, d, cost);
+    if (rc == LP_OPTIMAL)
+        rc = lp_download(ctx, "bounded basis parametric", {{out.t, d.t, sizeof(double) * nt},
+                                                           {out.obj, d.obj, sizeof(double) * nt},
+                                                           {out.slope, d.slope, sizeof(double) * ns},
+                                                           {out.enter, d.enter, sizeof(int) * ns},
+                                                           {out.leave, d.leave, sizeof(int) * ns},
+                                                           {out.side, d.side, sizeof(int) * ns},
+                                                           {out.basis, d.basis_out, sizeof(int) * B * m},
+                                                           {out.at_upper, d.at_upper_out, sizeof(int) * B * n},
+                                                           {out.nseg, d.nseg, sizeof(int) * B},
+                                                           {status_out, d.status, sizeof(int) * B}});
+    return rc;
+}
+
+// The single-LP entry of either path
+static int bounded_parametric_one(lp_context* ctx, const char* who, bool cost, const double* A, int m, int n,
+                                  const double* b, const double* c, const double* lo, const double* hi,
+                                  const int* basis, const int* at_upper, int maximize, const double* dir, double t_max,
+                                  double eps, int max_breaks, const BoundedParametricOut& out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !dir || !out.nseg || !out.t || !out.obj || !out.slope ||
+        !out.enter || !out.leave || !out.side || !out.basis || !out.at_upper)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_breaks must be >= 0");
+    bounded_parametric_none(0, m, n, max_breaks, basis, at_upper, out);
+    const BoundedSensIn in{1, m, n, A, b, c, lo, hi, basis, at_upper};
+    int rc = bounded_parametric_args(ctx, who, in, cost, t_max, eps, max_breaks);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = bounded_parametric(ctx, in, dir, cost, nullptr, maximize, t_max, eps, max_breaks, out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is not optimal at t = 0");
+    return status;
+}
+
+// The batched entry of either path
+static int bounded_parametric_many(lp_context* ctx, const char* who, bool cost, int batch, const double* A, int m,
+                                   int n, const double* b, const double* c, const double* lo, const double* hi,
+                                   const int* basis, const int* at_upper, const int* run_status, int maximize,
+                                   const double* dir, double t_max, double eps, int max_breaks,
+                                   const BoundedParametricOut& out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !dir || !out.nseg || !out.t || !out.obj || !out.slope ||
+        !out.enter || !out.leave || !out.side || !out.basis || !out.at_upper || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    const BoundedSensIn in{batch, m, n, A, b, c, lo, hi, basis, at_upper};
+    const int rc = bounded_parametric_args(ctx, who, in, cost, t_max, eps, max_breaks);
+    if (rc) return rc;
+    return bounded_parametric(ctx, in, dir, cost, run_status, maximize, t_max, eps, max_breaks, out, status_out);
+}
+
+int lp_basis_bounded_parametric(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                int maximize, const double* d, double t_max, double eps, int max_breaks,
+                                int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                                int* leave_out, int* side_out, int* basis_out, int* at_upper_out) {
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric", false, A, m, n, b, c, lo, hi, basis, at_upper,
+                                  maximize, d, t_max, eps, max_breaks,
+                                  {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                   at_upper_out});
+}
+
+int lp_basis_bounded_parametric_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                        const double* c, const double* lo, const double* hi, const int* basis,
+                                        const int* at_upper, const int* run_status, int maximize, const double* d,
+                                        double t_max, double eps, int max_breaks, int* nseg_out, double* t_out,
+                                        double* obj_out, double* slope_out, int* enter_out, int* leave_out,
+                                        int* side_out, int* basis_out, int* at_upper_out, int* status_out) {
+    return bounded_parametric_many(ctx, "lp_basis_bounded_parametric_batched", false, batch, A, m, n, b, c, lo, hi,
+                                   basis, at_upper, run_status, maximize, d, t_max, eps, max_breaks,
+                                   {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                    at_upper_out}, status_out);
+}
+
+int lp_basis_bounded_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                     const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                     int maximize, const double* g, double t_max, double eps, int max_breaks,
+                                     int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                                     int* leave_out, int* side_out, int* basis_out, int* at_upper_out) {
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric_cost", true, A, m, n, b, c, lo, hi, basis,
+                                  at_upper, maximize, g, t_max, eps, max_breaks,
+                                  {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                   at_upper_out});
+}
+
+int lp_basis_bounded_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n,
+                                             const double* b, const double* c, const double* lo, const double* hi,
+                                             const int* basis, const int* at_upper, const int* run_status,
+                                             int maximize, const double* g, double t_max, double eps, int max_breaks,
+                                             int* nseg_out, double* t_out, double* obj_out, double* slope_out,
+                                             int* enter_out, int* leave_out, int* side_out, int* basis_out,
+                                             int* at_upper_out, int* status_out) {
+    return bounded_parametric_many(ctx, "lp_basis_bounded_parametric_cost_batched", true, batch, A, m, n, b, c, lo,
+                                   hi, basis, at_upper, run_status, maximize, g, t_max, eps, max_breaks,
+                                   {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                    at_upper_out}, status_out);
 }
 
 // ===========================================================================

@@ -405,6 +405,41 @@ size_t lp_basis_bounded_certificate_lds_bytes(int m, int n);
 bool lp_basis_bounded_certificate_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
 int lp_basis_bounded_certificate_launch(lp_context* ctx, const BasisBoundedCertificateDev& d);   // fitting shapes
 
+// Parametric right-hand-side and parametric cost paths of bounded-variable LPs from given optimal bases and at-upper
+// flags, one LP per workgroup (basis_bounded_parametric.hip; the definition is tests/ref/bounded_parametric_ref.c): the
+// bounded re-solve's tableau with one more right-hand column (b + t dir) or one more cost row (c + t dir), then one
+// dual pivot, primal pivot or bound flip per breakpoint of z*(t).
+struct BasisBoundedParametricDev {
+    int batch, m, n;
+    int maximize;
+    int max_breaks;
+    double eps, t_max;
+    const double* A;         // batch x (m*n), each column-major
+    const double* b;         // batch x m
+    const double* c;         // batch x n
+    const double* lo;        // batch x n, finite
+    const double* hi;        // batch x n, finite or +inf
+    const double* dir;       // batch x m (the RHS path's d) or batch x n (the cost path's g)
+    const int* basis;        // batch x m (by position), every index in [0, n)
+    const int* at_upper;     // batch x n (0/1; 1 only where hi is finite)
+    const int* run_status;   // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it and gets nseg 0
+    int* nseg;               // batch
+    double* t;               // batch x (max_breaks+2)
+    double* obj;             // batch x (max_breaks+2)
+    double* slope;           // batch x (max_breaks+1)
+    int* enter;              // batch x (max_breaks+1)
+    int* leave;              // batch x (max_breaks+1)
+    int* side;               // batch x (max_breaks+1): 0 leave[k] stops at its lower bound, 1 at its upper bound
+    int* basis_out;          // batch x m: the final basis (the given one without a path)
+    int* at_upper_out;       // batch x n: the final flags (the given ones without a path)
+    int* status;             // batch
+};
+
+// basis_bounded_parametric.hip (cost: the cost path's kernel and carve)
+size_t lp_basis_bounded_parametric_lds_bytes(int m, int n, bool cost);
+bool lp_basis_bounded_parametric_fits_shape(int m, int n, bool cost);   // lp_bounded_fits_shape and the carve <= 160 KiB
+int lp_basis_bounded_parametric_launch(lp_context* ctx, const BasisBoundedParametricDev& d, bool cost);   // fitting shapes
+
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP
 // entry its per-LP fallback calls; everything else is the same for the three kinds.

@@ -626,7 +626,76 @@ public:
         return out;
     }
 
+    // The optimal value of the bounded problem along b + t d (boundedParametricRhs, lp_basis_bounded_parametric) or
+    // along c + t g (boundedParametricCost, lp_basis_bounded_parametric_cost) for t in [0, tMax], from a bounded
+    // result's basis and flags under the bounds lo, hi it was solved with, with EPS and the problem's sense: the fields
+    // of Parametric, plus side (nseg): the bound at which leave[k] stops (0 lower, 1 upper, -1 where leave[k] is -1),
+    // and atUpper: the flags that go with the final basis.  On the cost path a bound flip is a breakpoint with
+    // enter[k] == leave[k] and side[k] the bound flipped to.  status: LP_OPTIMAL (reached tMax), LP_INFEASIBLE (RHS
+    // path: infeasible past the last t; either path: some hi < lo, no segments), LP_UNBOUNDED (cost path: unbounded
+    // past the last t), LP_ITER_LIMIT (more than MAX_BREAKS breakpoints), LP_SINGULAR; a result that is not
+    // LP_OPTIMAL keeps its status and gets no segments.  Exceptions as boundedDuals, with lp_basis_bounded_parametric_fits
+    // / _cost_fits as the shape's limit; a result that is not optimal at t = 0 throws std::invalid_argument too.
+    struct BoundedParametric : Parametric {
+        std::vector<int> side, atUpper;
+    };
+
+    BoundedParametric boundedParametricRhs(const std::vector<double>& lo, const std::vector<double>& hi,
+                                           const BoundedResult& from, const lpla::VectorXd& d, double tMax) const {
+        return boundedParametric(false, lo, hi, from, d, tMax);
+    }
+
+    BoundedParametric boundedParametricCost(const std::vector<double>& lo, const std::vector<double>& hi,
+                                            const BoundedResult& from, const lpla::VectorXd& g, double tMax) const {
+        return boundedParametric(true, lo, hi, from, g, tMax);
+    }
+
 private:
+    BoundedParametric boundedParametric(bool cost, const std::vector<double>& lo, const std::vector<double>& hi,
+                                        const BoundedResult& from, const lpla::VectorXd& dir, double tMax) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument("Solver::boundedParametric: lo / hi size != cols(A)");
+        BoundedParametric out;
+        out.status = from.status;
+        out.basis = from.basis;
+        out.atUpper = from.atUpper;
+        int nseg = 0;
+        std::vector<double> t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1);
+        std::vector<int> enter(MAX_BREAKS + 1), leave(MAX_BREAKS + 1), side(MAX_BREAKS + 1);
+        if (from.status == LP_OPTIMAL) {
+            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
+                throw std::invalid_argument(
+                    "Solver::boundedParametric: the result's basis / atUpper size != rows(A) / cols(A)");
+            if ((int)dir.size() != (cost ? n : m))
+                throw std::invalid_argument(cost ? "Solver::boundedParametricCost: g size != cols(A)"
+                                                 : "Solver::boundedParametricRhs: d size != rows(A)");
+            lp_context* ctx = lpgpu::context(_device);
+            out.basis.assign((size_t)m, -1);
+            out.atUpper.assign((size_t)n, 0);
+            out.status = (cost ? lp_basis_bounded_parametric_cost : lp_basis_bounded_parametric)(
+                ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), from.basis.data(), from.atUpper.data(),
+                _problem.IsMaximization() ? 1 : 0, dir.data(), tMax, EPS, MAX_BREAKS, &nseg, t.data(), obj.data(),
+                slope.data(), enter.data(), leave.data(), side.data(), out.basis.data(), out.atUpper.data());
+            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        }
+        out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+        out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+        out.slope = lpla::VectorXd::Zero(nseg);
+        for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
+            out.t[k] = t[(size_t)k];
+            out.obj[k] = obj[(size_t)k];
+        }
+        for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
+        out.enter.assign(enter.begin(), enter.begin() + nseg);
+        out.leave.assign(leave.begin(), leave.begin() + nseg);
+        out.side.assign(side.begin(), side.begin() + nseg);
+        return out;
+    }
+
     Canonical _problem;  // deep copy, as in the reference (:285)
     int _device;
     PivotRule _rule = PivotRule::Dantzig;
