@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits; lp_basis_bounded_duals, lp_basis_bounded_duals_batched, lp_basis_bounded_ranging, lp_basis_bounded_ranging_batched, lp_basis_bounded_fits; lp_basis_bounded_parametric, lp_basis_bounded_parametric_batched, lp_basis_bounded_parametric_cost, lp_basis_bounded_parametric_cost_batched, lp_basis_bounded_parametric_fits, lp_basis_bounded_parametric_cost_fits */
+#define LP_ABI_VERSION 4 /* 2: lp_simplex_stats grew algo_used / fell_back; lp_enum_shard_abstain, lp_batched_shard_bounds; 3: LP_SIMPLEX_ALGO_OVERLAP, lp_enum_exact_division, lp_debug_reciprocal; 4: lp_debug_division; added within 4 (new entry points only): lp_simplex_two_phase_batched, lp_batched_two_phase_upload, lp_batched_phase_iters, lp_batched_path; LP_PIVOT_DANTZIG / LP_PIVOT_BLAND, lp_simplex_set_pivot_rule, lp_batched_set_pivot_rule, lp_simplex_solve_ex, lp_simplex_two_phase_ex, lp_simplex_solve_batched_ex, lp_simplex_two_phase_batched_ex; lp_simplex_resolve_run, lp_simplex_resolve, lp_simplex_resolve_batched, lp_batched_resolve_upload, lp_batched_set_start, lp_batched_resolve_iters; lp_basis_duals, lp_basis_duals_batched, lp_batched_duals, lp_basis_duals_fits; lp_basis_ranging, lp_basis_ranging_batched, lp_batched_ranging, lp_basis_ranging_fits; LP_CERT_NONE / LP_CERT_FARKAS / LP_CERT_RAY, lp_basis_certificate, lp_basis_certificate_batched, lp_batched_certificates, lp_basis_certificate_fits; lp_basis_parametric, lp_basis_parametric_batched, lp_batched_parametric, lp_basis_parametric_fits; lp_basis_parametric_cost, lp_basis_parametric_cost_batched, lp_batched_parametric_cost, lp_basis_parametric_cost_fits; lp_mip_solve, lp_mip_solve_batched, lp_batched_mip, lp_mip_fits; lp_simplex_bounded, lp_simplex_bounded_batched, lp_simplex_bounded_fits; LP_PIVOT_DEVEX, lp_batched_devex_fits; lp_basis_bounded_duals, lp_basis_bounded_duals_batched, lp_basis_bounded_ranging, lp_basis_bounded_ranging_batched, lp_basis_bounded_fits; lp_basis_bounded_parametric, lp_basis_bounded_parametric_batched, lp_basis_bounded_parametric_cost, lp_basis_bounded_parametric_cost_batched, lp_basis_bounded_parametric_fits, lp_basis_bounded_parametric_cost_fits; lp_simplex_bounded_ex, lp_simplex_bounded_batched_ex, lp_simplex_bounded_resolve_ex, lp_simplex_bounded_resolve_batched_ex, lp_simplex_bounded_rule_fits */
 
 /* Status codes; the C++ wrappers map them back to the
  * reference's exception types and messages.                                     */
@@ -566,7 +566,7 @@ int lp_mip_fits(int m, int n, int max_depth);
  * variable that reaches its own upper bound first FLIPS to it (no pivot), and a column at its upper bound is held
  * complemented.  The phases are lp_simplex_two_phase's (rows with b' < -eps change sign, phase I over m artificials,
  * LP_INFEASIBLE iff their sum > eps, the same drive-out with LP_SINGULAR, phase II on the phase-I tableau with the
- * artificials barred).  Dantzig's rule only.  With lo = 0 and hi = +inf the result is lp_simplex_two_phase's.
+ * artificials barred).  Dantzig's rule (another rule: lp_simplex_bounded_ex).  With lo = 0 and hi = +inf the result is lp_simplex_two_phase's.
  *   - LP_BAD_ARG for a NaN or infinite lo_j, a NaN hi_j, eps < 0 or NaN, a NULL pointer or a shape beyond lp_simplex_bounded_fits
  *     (there is no per-LP host path); an LP with some hi_j < lo_j is LP_INFEASIBLE without an iteration.
  *   - max_iter bounds each phase's iterations; an iteration is a pivot or a bound flip.
@@ -605,6 +605,36 @@ int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, c
 /* A batch of LPs of one shape: arrays as lp_simplex_bounded_batched, basis_in batch*m, at_upper_in batch*n, iters_out
  * batch*3.                                                                                                        */
 int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The bounded-variable simplex and its re-solve under a pivot rule.  Arguments and outputs are those of the entry
+ * without _ex, with the rule appended: LP_PIVOT_DANTZIG runs the kernel of that entry and is bit-identical to it in
+ * every output; any other value than the three rules is LP_BAD_ARG.  Only the iteration of the primal loop depends on
+ * the rule (the definition is tests/ref/bounded_rules_ref.c); it holds in phase I and in phase II, and the drive-out is
+ * the same under every rule.
+ *   - LP_PIVOT_BLAND: the eligible column of smallest index enters.  The row values are Dantzig's bounded ratios,
+ *     theta* = min(min_t v_t, U_e) exactly; among the rows with v_t <= theta* + eps, keyed by their basic variable, and
+ *     the entering variable itself, keyed by its index, when U_e <= theta* + eps, the smallest key wins: a bound flip
+ *     if it is the entering variable, else the pivot (after the complement when a_r < -eps).  The smallest-subscript
+ *     rule for bounded variables: no cycling, e.g. on Beale's LP with boxed columns, where Dantzig's rule ends
+ *     LP_ITER_LIMIT.
+ *   - LP_PIVOT_DEVEX: one fp64 weight per column slot, 1.0 when each phase's loop (the re-solve's primal loop) starts;
+ *     the eligible column of largest d*d/w enters, exact ties to the smallest index.  Ratio test, flip decision and
+ *     complement are Dantzig's; a flip leaves the weights alone; before a pivot w_s = max(w_s, (T_rs/u_r)^2 w_e) and
+ *     w_se = max(w_e/u_r^2, 1), as in lp_simplex_two_phase_batched_ex.
+ * In the re-solve the rule governs the primal branch only: the crash, the classification and the dual branch are
+ * unchanged, and their result under any rule is lp_simplex_bounded_resolve's bit for bit.  With lo = 0, hi = +inf and
+ * no flag every output under a rule equals lp_simplex_two_phase_batched_ex's under that rule bit for bit.
+ * Shapes: lp_simplex_bounded_rule_fits; a shape that fits plain but not with Devex's weights is LP_BAD_ARG under
+ * LP_PIVOT_DEVEX, and nothing is launched.  The branch-and-bound over bounds stays with Dantzig's rule.            */
+int lp_simplex_bounded_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule);
+int lp_simplex_bounded_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule);
+int lp_simplex_bounded_resolve_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule);
+int lp_simplex_bounded_resolve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule);
+/* Host call, no context.  1: the shape runs under pivot_rule: lp_simplex_bounded_fits(m, n) for LP_PIVOT_DANTZIG and
+ * LP_PIVOT_BLAND; under LP_PIVOT_DEVEX the LDS carve with n more doubles, the weights, must still fit 160 KiB.  0
+ * otherwise, and for an unknown rule.                                                                                */
+int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule);
 
 /* ---- Bounded variables: branch-and-bound over the bounds ------------------------------------------------------
  * The LP of lp_simplex_bounded with the columns j < n_orig of integer[j] = 1 integral (one mask of n entries for the

@@ -446,6 +446,50 @@ def build_bounded_parametric_ref(force=False, verbose=False):
     return BOUNDED_PARAMETRIC_REF_LIB
 
 
+BOUNDED_RULES_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_rules_ref.so")
+
+
+def build_bounded_rules_ref(force=False, verbose=False):
+    """tests/ref/bounded_rules_ref.c (which includes bounded_ref.c) -> tests/ref/_build/libbounded_rules_ref.so: the
+    two-phase bounded-variable simplex under Dantzig's, Bland's or the Devex rule the tests compare against; flags as
+    build_bounded_ref."""
+    src = os.path.join(TESTS_REF, "bounded_rules_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src, os.path.join(TESTS_REF, "bounded_ref.c")]
+    if not force and _newer(BOUNDED_RULES_REF_LIB, deps):
+        return BOUNDED_RULES_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_RULES_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_RULES_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_RULES_REF_LIB
+
+
+BOUNDED_RESOLVE_RULES_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_resolve_rules_ref.so")
+
+
+def build_bounded_resolve_rules_ref(force=False, verbose=False):
+    """tests/ref/bounded_resolve_rules_ref.c (which includes bounded_resolve_ref.c, bounded_ref.c and
+    bounded_rules_ref.c) -> tests/ref/_build/libbounded_resolve_rules_ref.so: the bounded-variable re-solve whose primal
+    branch runs under a pivot rule; flags as build_bounded_ref."""
+    src = os.path.join(TESTS_REF, "bounded_resolve_rules_ref.c")
+    if not os.path.exists(src):
+        return None
+    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("bounded_rules_ref.c", "bounded_resolve_ref.c", "bounded_ref.c")]
+    if not force and _newer(BOUNDED_RESOLVE_RULES_REF_LIB, deps):
+        return BOUNDED_RESOLVE_RULES_REF_LIB
+    os.makedirs(os.path.dirname(BOUNDED_RESOLVE_RULES_REF_LIB), exist_ok=True)
+    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
+           "-o", BOUNDED_RESOLVE_RULES_REF_LIB, src, "-lm"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return BOUNDED_RESOLVE_RULES_REF_LIB
+
+
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
@@ -464,6 +508,8 @@ def build_all(force=False, verbose=False):
     build_bounded_sens_ref(force, verbose)
     build_bounded_certificate_ref(force, verbose)
     build_bounded_parametric_ref(force, verbose)
+    build_bounded_rules_ref(force, verbose)
+    build_bounded_resolve_rules_ref(force, verbose)
     return hip, host
 
 

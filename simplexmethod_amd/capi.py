@@ -150,6 +150,16 @@ SIGNATURES = {
     "lp_simplex_bounded_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                      C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip,
                                                      _ip]),
+    "lp_simplex_bounded_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double,
+                                        C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
+    "lp_simplex_bounded_batched_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
+                                                C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, _ip, C.c_int]),
+    "lp_simplex_bounded_resolve_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
+    "lp_simplex_bounded_resolve_batched_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
+                                                        _ip, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
+                                                        _ip, _ip, C.c_int]),
+    "lp_simplex_bounded_rule_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "lp_mip_bounded_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int, _ip,
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                        _ip, _ip]),
@@ -700,8 +710,17 @@ class Context:
         return bool(self.lib.lp_mip_fits(m, n, max_depth))
 
     # ---- bounded-variable simplex -------------------------------------------------------------
-    def bounded(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+    def _bounded_call(self, name, pivot_rule, *args):
+        """The entry `name` of the bounded family, or with a pivot_rule its _ex form with the rule appended."""
+        if pivot_rule is None:
+            return self.check(getattr(self.lib, name)(*args))
+        return self.check(getattr(self.lib, name + "_ex")(*args, pivot_rule_id(pivot_rule)))
+
+    def bounded(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER, pivot_rule=None):
         """lp_simplex_bounded: opt c.x, A x = b, lo <= x <= hi (lo finite, hi finite or inf), no starting basis.
+        pivot_rule ("dantzig", "bland", "devex" or a PIVOT_* value; None: the entry without a rule, which is Dantzig's)
+        goes through lp_simplex_bounded_ex and holds in both phases; an unknown rule or, under Devex, a shape beyond
+        bounded_rule_fits raises LPError with code BAD_ARG.
         dict(status, x (n_orig), basis (m), at_upper (n, 0/1), obj, iters (phase-I pivots, drive-out pivots, phase-II
         pivots, bound flips)); x NaN and obj NaN unless OPTIMAL.  A bad bound or a shape beyond bounded_fits raises
         LPError with code BAD_ARG."""
@@ -714,15 +733,15 @@ class Context:
         up = np.zeros(n, dtype=np.int32)
         obj = np.full(1, np.nan)
         it = np.zeros(4, dtype=np.int32)
-        rc = self.check(self.lib.lp_simplex_bounded(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), int(maximize),
-                                                    n_orig, float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj),
-                                                    _i(it)))
+        rc = self._bounded_call("lp_simplex_bounded", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                int(maximize), n_orig, float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it))
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
-    def bounded_batched(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+    def bounded_batched(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER,
+                        pivot_rule=None):
         """lp_simplex_bounded_batched: A (batch, m, n), b (batch, m), c / lo / hi (batch, n).  dict(status (batch),
         x (batch, n_orig), basis (batch, m), at_upper (batch, n), obj (batch), iters (batch, 4)); per LP exactly
-        bounded()."""
+        bounded(), pivot_rule included (lp_simplex_bounded_batched_ex)."""
         A = np.asarray(A, dtype=np.float64)
         batch, m, n = A.shape
         n_orig = n if n_orig is None else int(n_orig)
@@ -737,22 +756,28 @@ class Context:
         obj = np.full(batch, np.nan)
         it = np.zeros((batch, 4), dtype=np.int32)
         st = np.zeros(batch, dtype=np.int32)
-        self.check(self.lib.lp_simplex_bounded_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
-                                                       int(maximize), n_orig, float(eps), int(max_iter), _d(x), _i(bo),
-                                                       _i(up), _d(obj), _i(it), _i(st)))
+        self._bounded_call("lp_simplex_bounded_batched", pivot_rule, self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo),
+                           _d(hi), int(maximize), n_orig, float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj),
+                           _i(it), _i(st))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     def bounded_fits(self, m, n):
         """lp_simplex_bounded_fits: True if an m x n bounded LP fits one CU's LDS."""
         return bool(self.lib.lp_simplex_bounded_fits(m, n))
 
+    def bounded_rule_fits(self, m, n, pivot_rule):
+        """lp_simplex_bounded_rule_fits: True if an m x n bounded LP fits one CU's LDS under pivot_rule: bounded_fits,
+        and under PIVOT_DEVEX with n more doubles, the weights.  False for an unknown rule."""
+        return bool(self.lib.lp_simplex_bounded_rule_fits(m, n, pivot_rule_id(pivot_rule)))
+
     def bounded_resolve(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                        max_iter=MAX_ITER):
+                        max_iter=MAX_ITER, pivot_rule=None):
         """lp_simplex_bounded_resolve: the LP of bounded() re-solved from `basis` (m) and `at_upper` (n, 0/1), normally
         an earlier result's, after a change of lo, hi, b or c: the bounded primal loop if the basis is primal feasible,
         the bounded dual simplex if it is only dual feasible.  dict as bounded() with iters = (dual pivots, primal
         pivots, bound flips).  A basis that is neither, a bad index or flag, a bad bound or a shape beyond bounded_fits
-        raises LPError with code BAD_ARG."""
+        raises LPError with code BAD_ARG.  pivot_rule as in bounded() (lp_simplex_bounded_resolve_ex): it governs the
+        primal loop only; the dual simplex is the same under every rule."""
         A = np.asarray(A, dtype=np.float64)
         m, n = A.shape
         n_orig = n if n_orig is None else int(n_orig)
@@ -766,16 +791,17 @@ class Context:
         up = np.zeros(n, dtype=np.int32)
         obj = np.full(1, np.nan)
         it = np.zeros(3, dtype=np.int32)
-        rc = self.check(self.lib.lp_simplex_bounded_resolve(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
-                                                            _i(basis), _i(at_upper), int(maximize), n_orig, float(eps),
-                                                            int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it)))
+        rc = self._bounded_call("lp_simplex_bounded_resolve", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c), _d(lo),
+                                _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter), _d(x),
+                                _i(bo), _i(up), _d(obj), _i(it))
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                                max_iter=MAX_ITER):
+                                max_iter=MAX_ITER, pivot_rule=None):
         """lp_simplex_bounded_resolve_batched: arrays as bounded_batched(), basis (batch, m), at_upper (batch, n).
         dict as bounded_batched() with iters (batch, 3); per LP exactly bounded_resolve(), except that a basis that
-        is no valid start is that LP's status BAD_ARG."""
+        is no valid start is that LP's status BAD_ARG.  pivot_rule as in bounded_resolve()
+        (lp_simplex_bounded_resolve_batched_ex)."""
         A = np.asarray(A, dtype=np.float64)
         batch, m, n = A.shape
         n_orig = n if n_orig is None else int(n_orig)
@@ -794,10 +820,9 @@ class Context:
         obj = np.full(batch, np.nan)
         it = np.zeros((batch, 3), dtype=np.int32)
         st = np.zeros(batch, dtype=np.int32)
-        self.check(self.lib.lp_simplex_bounded_resolve_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
-                                                               _i(basis), _i(at_upper), int(maximize), n_orig,
-                                                               float(eps), int(max_iter), _d(x), _i(bo), _i(up),
-                                                               _d(obj), _i(it), _i(st)))
+        self._bounded_call("lp_simplex_bounded_resolve_batched", pivot_rule, self.h, batch, _d(Af), m, n, _d(b), _d(c),
+                           _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter),
+                           _d(x), _i(bo), _i(up), _d(obj), _i(it), _i(st))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     # ---- the dual solution and ranging of a bounded-variable LP at a basis ----------------------

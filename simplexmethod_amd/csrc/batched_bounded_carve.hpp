@@ -1,16 +1,18 @@
 // batched_bounded_carve.hpp — the LDS carve of the bounded-variable kernels (batched_bounded.hip,
 // batched_bounded_resolve.hip; the layout is described in the former), computed alike on the host (the launch's
-// dynamic LDS size) and in the kernel.  Included after batched_scan.hpp (Published).
+// dynamic LDS size) and in the kernel.  Included after batched_scan.hpp (Published).  With `weights` the carve carries
+// one more region behind the ints, wts (n doubles, 8-byte aligned): the Devex weights of the rule kernels; without it
+// the carve is what it always was.
 #pragma once
 
 namespace {
 
 struct BoundedCarve {
     int pitch;
-    size_t T, prow, lcol, U, lov, slotvar, basis, up, bytes;   // byte offsets
+    size_t T, prow, lcol, U, lov, slotvar, basis, up, wts, bytes;   // byte offsets (wts: 0 without weights)
 };
 
-__host__ __device__ inline BoundedCarve bounded_carve(int m, int n) {
+__host__ __device__ inline BoundedCarve bounded_carve(int m, int n, bool weights = false) {
     BoundedCarve k{};
     const int W = n + 1;
     k.pitch = (W & 1) ? W : W + 1;   // odd pitch: conflict-free column reads
@@ -31,6 +33,11 @@ __host__ __device__ inline BoundedCarve bounded_carve(int m, int n) {
     o += sizeof(int) * (size_t)m;
     k.up = o;
     o += sizeof(int) * (size_t)n;
+    if (weights) {
+        o = (o + 7) & ~(size_t)7;
+        k.wts = o;
+        o += sizeof(double) * (size_t)n;
+    }
     k.bytes = (o + 15) & ~(size_t)15;
     return k;
 }

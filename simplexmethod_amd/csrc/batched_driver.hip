@@ -602,11 +602,12 @@ static int bounded_upload(lp_context* ctx, lp_device_buffer& buf, int batch, con
 
 // Uploads `batch` LPs, runs k_batched_bounded (basis_in null: 4 counters per LP) or k_batched_bounded_resolve (from
 // basis_in and at_upper_in: 3 counters per LP) and downloads; x (n_orig) and obj (over all n columns, as
-// lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.
+// lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.  pivot_rule picks the kernel's rule form (the
+// re-solve: of its primal branch); LP_PIVOT_DANTZIG is the kernel the entries without _ex launch.
 static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
                          const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
                          int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
-                         double* obj_out, int* iters_out, int* status_out) {
+                         double* obj_out, int* iters_out, int* status_out, int pivot_rule = LP_PIVOT_DANTZIG) {
     const size_t B = (size_t)batch, iw = basis_in ? 3 : 4;
     lp_device_buffer buf;
     BoundedInputs in;
@@ -634,7 +635,7 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     d.basis_in = in.basis_in;
     d.at_upper_in = in.at_upper_in;
     std::vector<double> x(B * n);
-    rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d) : lp_batched_bounded_launch(ctx, d);
+    rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d, pivot_rule) : lp_batched_bounded_launch(ctx, d, pivot_rule);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex: ") + hipGetErrorString(e));
@@ -729,73 +730,109 @@ static int mip_bounded_solve(lp_context* ctx, int batch, const double* A, int m,
                                                     {status_out, d.status, sizeof(int) * B}});
 }
 
+// The rule check of the bounded _ex entries: a known rule, and under Devex room for the weights too.  Nothing is
+// launched on a refusal.
+static int bounded_rule_args(lp_context* ctx, const char* who, int m, int n, int pivot_rule) {
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown pivot rule");
+    if (!lp_bounded_rule_fits_shape(m, n, pivot_rule))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the tableau and the Devex weights do not fit one CU's LDS (lp_simplex_bounded_rule_fits)");
+    return LP_OPTIMAL;
+}
+
+// The eight entries of the family in one: single (batch 1, status_out null: the status is the return value) or
+// batched, cold or from given bases (warm), under pivot_rule.  The entries without _ex pass LP_PIVOT_DANTZIG.
+static int bounded_entry(lp_context* ctx, const char* who, bool batched, bool warm, int batch, const double* A, int m,
+                         int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in,
+                         const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                         int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out,
+                         int pivot_rule) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || (batched && !status_out))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
+    int rc = bounded_args(ctx, who, batch, A, m, n, b, c, lo, hi, n_orig, warm, basis_in, at_upper_in);
+    if (rc) return rc;
+    rc = bounded_rule_args(ctx, who, m, n, pivot_rule);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    rc = bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, warm ? basis_in : nullptr, warm ? at_upper_in : nullptr,
+                       maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
+                       batched ? status_out : &status, pivot_rule);
+    if (rc || batched) return rc;
+    if (warm && status == LP_BAD_ARG)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
+    return status;
+}
+
 extern "C" {
 
 int lp_simplex_bounded_fits(int m, int n) { return lp_bounded_fits_shape(m, n) ? 1 : 0; }
 
-int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                       const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
-                       double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded: eps must be >= 0");
-    int rc = bounded_args(ctx, "lp_simplex_bounded", 1, A, m, n, b, c, lo, hi, n_orig);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, nullptr, nullptr, maximize, n_orig, eps, max_iter, x_out, basis_out,
-                       at_upper_out, obj_out, iters_out, &status);
-    return rc ? rc : status;
+int lp_simplex_bounded(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                       const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                       int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
+    return bounded_entry(ctx, "lp_simplex_bounded", false, false, 1, A, m, n, b, c, lo, hi, nullptr, nullptr,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, nullptr,
+                         LP_PIVOT_DANTZIG);
 }
 
-int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                               const double* c, const double* lo, const double* hi, int maximize, int n_orig,
-                               double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
-                               double* obj_out, int* iters_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_batched: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_batched: eps must be >= 0");
-    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
-    const int rc = bounded_args(ctx, "lp_simplex_bounded_batched", batch, A, m, n, b, c, lo, hi, n_orig);
-    if (rc) return rc;
-    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, nullptr, nullptr, maximize, n_orig, eps, max_iter, x_out,
-                         basis_out, at_upper_out, obj_out, iters_out, status_out);
+int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                               const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                               double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out) {
+    return bounded_entry(ctx, "lp_simplex_bounded_batched", true, false, batch, A, m, n, b, c, lo, hi, nullptr, nullptr,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
+                         LP_PIVOT_DANTZIG);
 }
 
-int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                               const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
-                               int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
-                               int* at_upper_out, double* obj_out, int* iters_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: eps must be >= 0");
-    int rc = bounded_args(ctx, "lp_simplex_bounded_resolve", 1, A, m, n, b, c, lo, hi, n_orig, true, basis_in, at_upper_in);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    rc = bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps, max_iter, x_out,
-                       basis_out, at_upper_out, obj_out, iters_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve: the basis is neither primal nor dual feasible");
-    return status;
+int lp_simplex_bounded_resolve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                               const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                               int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve", false, true, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, nullptr,
+                         LP_PIVOT_DANTZIG);
 }
 
-int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
-                                       const double* c, const double* lo, const double* hi, const int* basis_in,
-                                       const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
-                                       double* x_out, int* basis_out, int* at_upper_out, double* obj_out,
-                                       int* iters_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_batched: null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_batched: eps must be >= 0");
-    if (batch <= 0) LP_FAIL(ctx, LP_BAD_ARG, "batch must be positive");
-    const int rc = bounded_args(ctx, "lp_simplex_bounded_resolve_batched", batch, A, m, n, b, c, lo, hi, n_orig, true,
-                                basis_in, at_upper_in);
-    if (rc) return rc;
-    return bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps, max_iter, x_out,
-                         basis_out, at_upper_out, obj_out, iters_out, status_out);
+int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                                       const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
+                                       double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve_batched", true, true, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
+                         LP_PIVOT_DANTZIG);
+}
+
+int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule) { return lp_bounded_rule_fits_shape(m, n, pivot_rule) ? 1 : 0; }
+
+int lp_simplex_bounded_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                          const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                          int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule) {
+    return bounded_entry(ctx, "lp_simplex_bounded_ex", false, false, 1, A, m, n, b, c, lo, hi, nullptr, nullptr,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, nullptr,
+                         pivot_rule);
+}
+
+int lp_simplex_bounded_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                                  const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                                  double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
+    return bounded_entry(ctx, "lp_simplex_bounded_batched_ex", true, false, batch, A, m, n, b, c, lo, hi, nullptr, nullptr,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
+                         pivot_rule);
+}
+
+int lp_simplex_bounded_resolve_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                                  const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                                  int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve_ex", false, true, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, nullptr,
+                         pivot_rule);
+}
+
+int lp_simplex_bounded_resolve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                                          const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
+                                          double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve_batched_ex", true, true, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
+                         pivot_rule);
 }
 
 int lp_mip_bounded_fits(int m, int n, int max_depth) { return lp_mip_bounded_fits_shape(m, n, max_depth) ? 1 : 0; }

@@ -299,7 +299,10 @@ struct BatchedBoundedDev {
 // batched_bounded.hip
 size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
 bool lp_bounded_fits_shape(int m, int n);
-int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
+size_t lp_bounded_devex_lds_bytes(int m, int n);                    // the carve with the Devex weights behind it
+bool lp_bounded_rule_fits_shape(int m, int n, int pivot_rule);      // a known rule, lp_bounded_fits_shape, Devex: the weights too
+// fitting shapes (under the rule), else LP_BAD_ARG; LP_PIVOT_DANTZIG launches the kernel there has always been
+int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d, int pivot_rule = LP_PIVOT_DANTZIG);
 
 // The same batch re-solved from given bases and complement flags, one LP per workgroup (batched_bounded_resolve.hip;
 // the definition is tests/ref/bounded_resolve_ref.c).  max_iter bounds the dual pivots, or the primal pivots plus
@@ -310,7 +313,8 @@ struct BatchedBoundedResolveDev : BatchedBoundedDev {
 };
 
 // batched_bounded_resolve.hip
-int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d);   // fitting shapes, else LP_BAD_ARG
+// fitting shapes (under the rule), else LP_BAD_ARG; the rule governs the primal branch only
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule = LP_PIVOT_DANTZIG);
 
 // Depth-first branch-and-bound over variable bounds, one mixed-integer bounded LP per workgroup
 // (batched_mip_bounded.hip; the definition is tests/ref/mip_bounded_ref.c): the bounded re-solve at the root, then per

@@ -195,6 +195,38 @@ __device__ int wave_bland_ratio(int count, double eps, Get get) {
     return __builtin_amdgcn_readlane(lrow, (int)__builtin_ctzll(__ballot(lkey == kmin)));
 }
 
+// Bland's ratio test of the bounded-variable loop: as wave_bland_ratio, with the entering variable's own candidate:
+// its width ue (+inf: none) takes part in the minimum, theta* = min(min_i theta_i, ue), and, when ue <= theta* + eps,
+// in the choice by smallest key with its variable index ekey.  Returns the leaving row, -2 when the entering variable
+// itself wins (a bound flip), -1 when theta* = +inf (unbounded).
+template <typename Get>
+__device__ int wave_bland_ratio_entering(int count, double eps, double ue, int ekey, Get get) {
+    const int lane = threadIdx.x & 63;
+    double lmin = ue;
+    for (int i = lane; i < count; i += 64) {
+        double v;
+        int k;
+        get(i, v, k);
+        if (v < lmin) lmin = v;   // (NaN never taken)
+    }
+    const double theta = lpdev::f64_from_key(lpdev::wave_ext_key<false>(lpdev::f64_sort_key(lmin)));
+    if (!(theta < INFINITY)) return -1;
+    const double thr = theta + eps;
+    int lkey = (ue <= thr) ? ekey : INT_MAX, lrow = -2;
+    for (int i = lane; i < count; i += 64) {
+        double v;
+        int k;
+        get(i, v, k);
+        if (v <= thr && k < lkey) {
+            lkey = k;
+            lrow = i;
+        }
+    }
+    const int kmin = (int)lpdev::wave_ext_u32<false>((unsigned)lkey);
+    if (kmin == INT_MAX) return -1;
+    return __builtin_amdgcn_readlane(lrow, (int)__builtin_ctzll(__ballot(lkey == kmin)));
+}
+
 // ---- Devex pricing (LP_PIVOT_DEVEX) on keyed entries, by ONE wave (all 64 lanes) -------------------
 
 // The eligible entry of largest score, exact ties to the smallest key: get(s, score, key, eligible).  Returns

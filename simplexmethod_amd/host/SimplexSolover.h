@@ -14,6 +14,7 @@
 
 #include <limits>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "Canonical.h"
@@ -348,23 +349,16 @@ public:
 
     BoundedResult boundedSimplex(const std::vector<double>& lo, const std::vector<double>& hi,
                                  bool throw_on_failure = true) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedSimplex: lo / hi size != cols(A)");
-        BoundedResult out;
-        out.x = lpla::VectorXd::Zero(no);
-        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
-        out.basis.assign((size_t)m, -1);
-        out.atUpper.assign((size_t)n, 0);
-        lp_context* ctx = lpgpu::context(_device);
-        out.status = lp_simplex_bounded(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                        _problem.IsMaximization() ? 1 : 0, no, EPS, MAX_ITER, out.x.data(),
-                                        out.basis.data(), out.atUpper.data(), &out.objective, out.iterations);
-        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
-        return out;
+        return boundedRun("Solver::boundedSimplex", lo, hi, nullptr, nullptr, throw_on_failure);
+    }
+
+    // The same under a pivot rule (lp_simplex_bounded_ex), in phase I and phase II: PivotRule::Bland cannot cycle,
+    // PivotRule::Devex prices on d*d/w and needs cols(A) more doubles of LDS (lp_simplex_bounded_rule_fits, else
+    // std::invalid_argument); PivotRule::Dantzig is the form above bit for bit.  The forms without a rule ignore
+    // setPivotRule.
+    BoundedResult boundedSimplex(const std::vector<double>& lo, const std::vector<double>& hi, PivotRule rule,
+                                 bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedSimplex", lo, hi, nullptr, &rule, throw_on_failure);
     }
 
     // The same problem under the bounds lo, hi re-solved from the basis and flags of an earlier result
@@ -374,26 +368,14 @@ public:
     // a flag on a column without an upper bound or a basis index outside the columns throw std::invalid_argument.
     BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
                                  const BoundedResult& from, bool throw_on_failure = true) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedResolve: lo / hi size != cols(A)");
-        if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-            throw std::invalid_argument("Solver::boundedResolve: the start's basis / atUpper size != rows(A) / cols(A)");
-        BoundedResult out;
-        out.x = lpla::VectorXd::Zero(no);
-        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
-        out.basis.assign((size_t)m, -1);
-        out.atUpper.assign((size_t)n, 0);
-        lp_context* ctx = lpgpu::context(_device);
-        out.status = lp_simplex_bounded_resolve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                from.basis.data(), from.atUpper.data(),
-                                                _problem.IsMaximization() ? 1 : 0, no, EPS, MAX_ITER, out.x.data(),
-                                                out.basis.data(), out.atUpper.data(), &out.objective, out.iterations);
-        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
-        return out;
+        return boundedRun("Solver::boundedResolve", lo, hi, &from, nullptr, throw_on_failure);
+    }
+
+    // The same under a pivot rule (lp_simplex_bounded_resolve_ex): the rule governs the primal loop only; the dual
+    // simplex is the same under every rule.
+    BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
+                                 const BoundedResult& from, PivotRule rule, bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolve", lo, hi, &from, &rule, throw_on_failure);
     }
 
     // The dual solution of the bounded problem at a result's basis and flags (lp_basis_bounded_duals), in the original
@@ -693,6 +675,46 @@ private:
         out.enter.assign(enter.begin(), enter.begin() + nseg);
         out.leave.assign(leave.begin(), leave.begin() + nseg);
         out.side.assign(side.begin(), side.begin() + nseg);
+        return out;
+    }
+
+    // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form
+    BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
+                             const BoundedResult* from, const PivotRule* rule, bool throw_on_failure) const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        const lpla::VectorXd& b = _problem.GetRightHandSide();
+        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
+        if ((int)lo.size() != n || (int)hi.size() != n)
+            throw std::invalid_argument(std::string(who) + ": lo / hi size != cols(A)");
+        if (from && ((int)from->basis.size() != m || (int)from->atUpper.size() != n))
+            throw std::invalid_argument(std::string(who) + ": the start's basis / atUpper size != rows(A) / cols(A)");
+        BoundedResult out;
+        out.x = lpla::VectorXd::Zero(no);
+        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        out.basis.assign((size_t)m, -1);
+        out.atUpper.assign((size_t)n, 0);
+        lp_context* ctx = lpgpu::context(_device);
+        const int mx = _problem.IsMaximization() ? 1 : 0;
+        if (!from && !rule)
+            out.status = lp_simplex_bounded(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no, EPS,
+                                            MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
+                                            &out.objective, out.iterations);
+        else if (!from)
+            out.status = lp_simplex_bounded_ex(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no, EPS,
+                                               MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
+                                               &out.objective, out.iterations, (int)*rule);
+        else if (!rule)
+            out.status = lp_simplex_bounded_resolve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                    from->basis.data(), from->atUpper.data(), mx, no, EPS, MAX_ITER,
+                                                    out.x.data(), out.basis.data(), out.atUpper.data(), &out.objective,
+                                                    out.iterations);
+        else
+            out.status = lp_simplex_bounded_resolve_ex(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
+                                                       from->basis.data(), from->atUpper.data(), mx, no, EPS, MAX_ITER,
+                                                       out.x.data(), out.basis.data(), out.atUpper.data(),
+                                                       &out.objective, out.iterations, (int)*rule);
+        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
         return out;
     }
 
