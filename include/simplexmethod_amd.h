@@ -583,6 +583,23 @@ int lp_simplex_bounded_batched(lp_context* ctx, int batch, const double* A, int 
  * does), 0 otherwise.  A host call: no context, no device.                                                      */
 int lp_simplex_bounded_fits(int m, int n);
 
+/* ---- Bounded variables: shapes beyond one workgroup's LDS ------------------------------------------------------
+ * The LP of lp_simplex_bounded on the tableau in HBM (the definition is still
+ * tests/ref/bounded_ref.c, and the results equal it bit for bit): the flow of lp_simplex_two_phase with one selector
+ * and one rank-1 update launch per iteration.  The selector takes the bounded ratio test; a bound flip is done inside
+ * it (two columns, O(m)) and streams no tableau, a pivot whose leaving variable leaves at its upper bound is staged
+ * complemented.  Arguments, outputs, statuses and refusals are lp_simplex_bounded's with one difference: there is no
+ * lp_simplex_bounded_fits limit (the limits are lp_simplex_two_phase's: device memory for the (m+1) x (n+m+1)
+ * tableau, and m <= 9980 for the selector's LDS).  At a shape that also fits LDS the result is lp_simplex_bounded's.
+ *   - LP_BAD_ARG for a NaN or infinite lo_j, a NaN hi_j, eps < 0 or NaN, or a NULL pointer; an LP with some
+ *     hi_j < lo_j is LP_INFEASIBLE without an iteration (zero counters, basis n + t, no flag).
+ *   - max_iter bounds the pivots plus flips of each phase; iters_out[4] = phase-I pivots, drive-out pivots, phase-II
+ *     pivots, bound flips.
+ *   - Dantzig's rule only.  Out of scope on this path: Bland's rule and Devex pricing, a re-solve from a basis, and
+ *     the analyses (duals, ranging, certificates, parametrics, branch and bound); those stay at
+ *     lp_simplex_bounded_fits shapes.  lp_simplex_bounded itself is unchanged and still refuses larger shapes.   */
+int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
+
 /* ---- Bounded variables: the re-solve from a basis -------------------------------------------------------------
  * The LP of lp_simplex_bounded re-solved from basis_in (m, by position, every index in [0, n)) and at_upper_in (n,
  * 0/1), normally the basis_out and at_upper_out of an earlier solve, after a change of lo, hi, b or c (DESIGN.md

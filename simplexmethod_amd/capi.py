@@ -145,6 +145,8 @@ SIGNATURES = {
     "lp_simplex_bounded_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                              C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, _ip]),
     "lp_simplex_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_simplex_bounded_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+                                           C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
     "lp_simplex_bounded_resolve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int,
                                              C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
     "lp_simplex_bounded_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -760,6 +762,23 @@ class Context:
                            _d(hi), int(maximize), n_orig, float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj),
                            _i(it), _i(st))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
+
+    def bounded_large(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+        """lp_simplex_bounded_large: the LP of bounded() on the tableau in HBM, at any shape two_phase() runs (no
+        bounded_fits limit); Dantzig's rule.  Returns the dict of bounded(), equal to it where both run."""
+        A = np.asarray(A, dtype=np.float64)
+        m, n = A.shape
+        n_orig = n if n_orig is None else int(n_orig)
+        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
+        x = np.full(n_orig, np.nan)
+        bo = np.full(m, -1, dtype=np.int32)
+        up = np.zeros(n, dtype=np.int32)
+        obj = np.full(1, np.nan)
+        it = np.zeros(4, dtype=np.int32)
+        rc = self.check(self.lib.lp_simplex_bounded_large(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
+                                                          int(maximize), n_orig, float(eps), int(max_iter), _d(x),
+                                                          _i(bo), _i(up), _d(obj), _i(it)))
+        return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_fits(self, m, n):
         """lp_simplex_bounded_fits: True if an m x n bounded LP fits one CU's LDS."""

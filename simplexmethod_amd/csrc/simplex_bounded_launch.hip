@@ -1,0 +1,175 @@
+// simplex_bounded_launch.hip — the bounded-variable simplex on the HBM tableau of simplex_launch.hip
+// (lp_simplex_bounded_large): one select + one rank-1-update launch per iteration, at any shape the launch pair runs.
+//
+// The definition is tests/ref/bounded_ref.c, which is stated on a condensed slot tableau.  Here the tableau is the full
+// one of SimplexDev: (m+1) x ld row-major, one column per variable (the m artificials are columns n_lp .. n_lp+m-1 of
+// the phase-I problem, so d.n = n_lp + m), xB in column d.n, row m the reduced costs.  The reference's slot of the
+// entering variable receives the eta column; on the full tableau that is the leaving variable's own column after the
+// update, fma(l_i, 1, 0) = l_i, because a basic column is the exact unit vector.  Every other entry goes through the
+// same operations in the same order, so the results are the reference's bit for bit.
+//
+// Beside the tableau (BoundedLargeDev, kept out of SimplexDev and SimplexState so that the kernels of
+// simplex_launch.hip are what they were):
+//   U[d.n]   hi - lo per variable, +inf for the artificials;
+//   up[d.n]  1 = the tableau holds U_j - x'_j in place of x'_j (what at_upper_out reports);
+//   flips    bound flips since the start of the solve (both phases).
+// SimplexState::iters counts the pivots plus flips of the running phase, which is what max_iter bounds.
+//
+// A bound flip is done inside the selector (two strided columns, O(m)) and leaves pivot_valid = 0, so the
+// k_simplex_update queued behind it returns at once: a flip streams no tableau.  A pivot is staged for the unchanged
+// k_simplex_update; when the leaving variable leaves at its upper bound (a_r < -eps) the staged pivot row is the
+// complemented one (negated over the columns, xB_r = U - xB_r, the leaving variable's own entry +1 again), and since
+// the update writes row r from the staged copy alone, row r of the tableau itself need not be touched first.
+#include "device_select.hpp"
+#include "lp_internal.hpp"
+#include "simplex_problem.hpp"
+
+namespace {
+
+constexpr int kRunning = -100;  // SimplexState::status while pivoting
+
+// Launch shape and LDS as k_simplex_select (u[m+1], ratio[m], 3 ints) plus one double, the selected ratio theta.
+__global__ __launch_bounds__(1024) void k_simplex_select_bounded(SimplexDev d, BoundedLargeDev bd) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_u = s_dyn;
+    double* s_ratio = s_dyn + (d.m + 2);
+    double& s_theta = s_dyn[2 * (d.m + 2)];
+    int* s_int = reinterpret_cast<int*>(s_dyn + 2 * (d.m + 2) + 2);
+    int& s_enter = s_int[0];
+    int& s_leave = s_int[1];
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {   // pivots plus flips of this phase
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // pricing: k_simplex_select's (phase II: the artificial columns carry no non-basic flag)
+    const double* drow = d.T + (size_t)m * ld;
+    if (tid < 64) {
+        double best;
+        int e;
+        auto load = [&](int j, bool& ok) {
+            ok = d.nonbasic[j] != 0;
+            return drow[j];
+        };
+        if (d.maximize)
+            e = lpdev::wave_chain_select<true>(n, eps, best, load);
+        else
+            e = lpdev::wave_chain_select<false>(n, eps, best, load);
+        const bool optimal = d.maximize ? (best <= eps) : (best >= -eps);
+        if (tid == 0) s_enter = optimal ? -1 : e;
+    }
+    __syncthreads();
+    const int e = s_enter;
+    if (e < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // column e, and per basis position the step at which its variable reaches 0 (a > eps) or its upper bound
+    // (a < -eps, U finite)
+    for (int i = tid; i <= m; i += blockDim.x) {
+        const double a = d.T[(size_t)i * ld + e];
+        s_u[i] = a;
+        if (i < m) {
+            const double xb = d.T[(size_t)i * ld + n], u = bd.U[d.basis[i]];
+            s_ratio[i] = (a > eps) ? xb / a : (a < -eps && u < INFINITY) ? (xb - u) / a : INFINITY;
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        double theta;
+        auto load = [&](int i, bool& ok) {
+            ok = true;  // ineligible rows hold +inf, which the < scan never takes
+            return s_ratio[i];
+        };
+        const int r = lpdev::wave_chain_select<false>(m, eps, theta, load);
+        if (tid == 0) {
+            s_leave = r;
+            s_theta = theta;
+        }
+    }
+    __syncthreads();
+    const int r = s_leave;
+    const double ue = bd.U[e];
+    if (r < 0 && !(ue < INFINITY)) {
+        if (tid == 0) {
+            st->status = LP_UNBOUNDED;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    if (r < 0 || ue <= s_theta) {   // bound flip: e goes to its other bound, the basis stays
+        for (int i = tid; i <= m; i += blockDim.x) {
+            const size_t row = (size_t)i * ld;
+            d.T[row + n] = fma(-ue, s_u[i], d.T[row + n]);
+            d.T[row + e] = -s_u[i];
+        }
+        if (tid == 0) {
+            bd.up[e] ^= 1;
+            *bd.flips += 1;
+            st->iters += 1;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // pivot on row r; a_r < -eps: the leaving variable leaves at its upper bound and is complemented first
+    const int old = d.basis[r];   // (every thread reads it before the barrier below; thread 0 writes it after)
+    const bool comp = s_u[r] < -eps;
+    const double ur = comp ? -s_u[r] : s_u[r];
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_u[i] / ur;
+    const double* trow = d.T + (size_t)r * ld;
+    const double uold = bd.U[old];
+    for (int j = tid; j < ld; j += blockDim.x) {
+        double v = trow[j];
+        if (comp) v = (j < n) ? -v : (j == n) ? uold - v : v;
+        if (j == old) v = 1.0;   // the leaving variable's own column: the unit column again (a no-op without comp)
+        d.prow[j] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (comp) bd.up[old] ^= 1;
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        st->iters += 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+size_t select_bounded_lds_bytes(const lp_simplex_problem* p) {
+    return sizeof(double) * (2 * (size_t)(p->dev.m + 2) + 2) + 16;
+}
+
+}  // namespace
+
+int lp_bounded_large_prepare(lp_simplex_problem* p) {
+    const size_t shm = select_bounded_lds_bytes(p);
+    if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_large: m too large for the selector's LDS");
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_bounded), shm));
+    return LP_OPTIMAL;
+}
+
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch) {
+    const size_t shm = select_bounded_lds_bytes(p);
+    for (int k = 0; k < batch; ++k) {
+        hipLaunchKernelGGL(k_simplex_select_bounded, 1, 1024, shm, p->ctx->stream, p->dev, bd);
+        lp_simplex_launch_update(p);
+    }
+    return 2 * batch;
+}

@@ -118,6 +118,24 @@ int run_dual(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* 
     return record_run(p, LP_SIMPLEX_ALGO_LAUNCH, launches, ms, 0.f, 0, stats);
 }
 
+// One phase of lp_simplex_bounded_large: the bounded selector + rank-1 update pair per iteration, polled as
+// run_launch.  *iters = the pivots plus flips of the phase, *flips = the flips since the start of the solve.
+int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int max_iter, int* iters,
+                      int* flips) {
+    lp_context* ctx = p->ctx;
+    int launches = lp_launch_begin(p, eps, max_iter);
+    int rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return lp_bounded_large_queue(p, bd, batch); });
+    if (rc) return rc;
+    rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
+    if (rc) return rc;
+    LP_HIP(ctx, hipGetLastError());
+    *iters = p->h_state->iters;
+    p->last_status = p->h_state->status;
+    p->last_iters = p->h_state->iters;
+    p->last_algo = LP_SIMPLEX_ALGO_LAUNCH;
+    return p->h_state->status;
+}
+
 int run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
     lp_context* ctx = p->ctx;
     int rc = lp_lookahead_prepare(p);
@@ -761,6 +779,149 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
     stage("free");
     if (basis_out) std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
     if (iters_out) std::memcpy(iters_out, it, sizeof(it));
+    return rc;
+}
+
+// The bounded-variable two-phase simplex on the HBM tableau (tests/ref/bounded_ref.c is the definition): the flow of
+// lp_simplex_two_phase_ex with the selector of simplex_bounded_launch.hip in both phases.  The set-up arithmetic
+// (shift, sign changes, U, the phase-II costs of complemented columns, the outputs) runs here on the host in the
+// reference's order; every pivot and flip runs on the GPU.
+int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                             const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                             double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
+    const char* who = "lp_simplex_bounded_large";
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    for (int j = 0; j < n; ++j) {
+        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
+        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
+    }
+    const int na = n + m;
+    int it[4] = {0, 0, 0, 0};
+    for (int t = 0; t < m; ++t) basis_out[t] = n + t;
+    for (int j = 0; j < n; ++j) at_upper_out[j] = 0;
+    std::memcpy(iters_out, it, sizeof(it));
+    for (int j = 0; j < n; ++j)
+        if (hi[j] < lo[j]) LP_FAIL(ctx, LP_INFEASIBLE, std::string(who) + ": some hi_j < lo_j");
+
+    // shift x = lo + x' (b' accumulated in ascending j, lo_j == 0 skipped), U = hi - lo, then make_b_nonneg and
+    // createAuxiliaryProblem on [A | b'] as lp_simplex_two_phase_ex
+    std::vector<double> A1((size_t)m * na, 0.0), b1((size_t)m), c1((size_t)na, 0.0), xa((size_t)na), U((size_t)na);
+    std::vector<int> N((size_t)m), up((size_t)na, 0);
+    for (int j = 0; j < n; ++j) U[(size_t)j] = hi[j] - lo[j];
+    for (int k = n; k < na; ++k) U[(size_t)k] = INFINITY;
+    for (int i = 0; i < m; ++i) b1[(size_t)i] = b[i];
+    for (int j = 0; j < n; ++j) {   // (column by column: A is column-major; per row the order is ascending j)
+        if (lo[j] == 0.0) continue;
+        const double* src = A + (size_t)j * m;
+        for (int i = 0; i < m; ++i) b1[(size_t)i] = std::fma(-src[i], lo[j], b1[(size_t)i]);
+    }
+    std::vector<char> flip((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        flip[(size_t)i] = b1[(size_t)i] < -eps;
+        if (flip[(size_t)i]) b1[(size_t)i] = -b1[(size_t)i];
+        A1[(size_t)(n + i) * m + i] = 1.0;
+    }
+    for (int j = 0; j < n; ++j) {
+        const double* src = A + (size_t)j * m;
+        double* dst = A1.data() + (size_t)j * m;
+        for (int i = 0; i < m; ++i) dst[i] = flip[(size_t)i] ? -src[i] : src[i];
+    }
+    for (int j = n; j < na; ++j) c1[(size_t)j] = 1.0;
+    for (int t = 0; t < m; ++t) N[(size_t)t] = n + t;
+
+    lp_simplex_problem* p = nullptr;
+    int rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
+    if (rc) return rc;
+    std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)> owner(p, lp_simplex_free);
+    rc = lp_bounded_large_prepare(p);
+    if (rc) return rc;
+    // the bound state beside the tableau
+    hipStream_t s = ctx->stream;
+    lp_device_buffer buf;
+    BoundedLargeDev bd{};
+    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
+        bd.U = cv.take<double>(sizeof(double) * (size_t)na);
+        bd.up = cv.take<int>(sizeof(int) * (size_t)na);
+        bd.flips = cv.take<int>(sizeof(int));
+    }));
+    LP_HIP(ctx, hipMemcpyAsync(bd.U, U.data(), sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemsetAsync(bd.up, 0, sizeof(int) * (size_t)na, s));
+    LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
+    // (buf is freed before the problem on every return path; hipFree waits for the queued kernels)
+    auto download_flags = [&]() { return lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}}); };
+
+    // ---- phase I: minimise the sum of the artificials
+    int iters = 0, flips1 = 0, flips = 0;
+    rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips1);
+    if (rc < 0) return rc;
+    it[0] = iters - flips1;
+    it[3] = flips1;
+    if (rc == LP_OPTIMAL) rc = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+    if (rc == LP_OPTIMAL) {
+        double sum = 0.0;   // the artificials' values in artificial-index order
+        for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
+        if (sum > eps) {
+            rc = LP_INFEASIBLE;
+            ctx->last_error = std::string(who) + ": the problem has no feasible solution (phase I optimum > eps)";
+        }
+    }
+    if (rc == LP_OPTIMAL) {   // the drive-out of lp_simplex_two_phase_ex: no bound enters it
+        std::vector<int> positions;
+        for (int pos = 0; pos < m; ++pos)
+            if (N[(size_t)pos] >= n) positions.push_back(pos);
+        if (!positions.empty()) {
+            rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, &it[1]);
+            if (rc == LP_SINGULAR)
+                ctx->last_error = std::string(who) + ": an artificial variable cannot leave the basis (linearly dependent constraints)";
+        }
+    }
+    if (rc >= 0) {
+        const int rf = download_flags();
+        if (rf) rc = rf;
+    }
+    // ---- phase II on the phase-I tableau: a complemented column's cost changes sign
+    if (rc == LP_OPTIMAL) {
+        std::vector<double> c2((size_t)n);
+        for (int j = 0; j < n; ++j) c2[(size_t)j] = up[(size_t)j] ? -c[j] : c[j];
+        rc = lp_simplex_phase2_costs(p, c2.data(), n, maximize, n);   // (n_orig = n: the download below returns every v_j)
+    }
+    if (rc == LP_OPTIMAL) {
+        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips);
+        if (rc >= 0) {
+            it[2] = iters - (flips - flips1);
+            it[3] = flips;
+            int rd;
+            if (rc == LP_OPTIMAL)
+                rd = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+            else
+                rd = lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+            if (rd == LP_OPTIMAL) rd = download_flags();
+            if (rd) rc = rd;
+        }
+    } else if (rc > 0) {   // the basis reached, as the one-LP-per-workgroup kernel reports it
+        const int rd = lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+        if (rd) rc = rd;
+    }
+    (void)hipStreamSynchronize(s);
+    if (rc < 0) return rc;
+    if (rc == LP_OPTIMAL) {   // step 9 of the reference: un-complement, un-shift, then the objective in index order
+        for (int j = 0; j < n; ++j) {
+            const double v = xa[(size_t)j];
+            const double w = up[(size_t)j] ? U[(size_t)j] - v : v;
+            xa[(size_t)j] = lo[j] == 0.0 ? w : lo[j] + w;
+        }
+        double z = 0.0;
+        for (int j = 0; j < n; ++j) z += c[j] * xa[(size_t)j];
+        for (int j = 0; j < n_orig; ++j) x_out[j] = xa[(size_t)j];
+        *obj_out = z;
+    }
+    std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
+    for (int j = 0; j < n; ++j) at_upper_out[j] = up[(size_t)j];
+    std::memcpy(iters_out, it, sizeof(it));
     return rc;
 }
 

@@ -129,6 +129,16 @@ int lp_dual_queue(lp_simplex_problem* p, int batch);
 // queues `batch` pivots and returns the launches queued); returns once the state word has left kRunning.
 int lp_poll_pivots(lp_simplex_problem* p, const std::function<int(int)>& queue);
 
+// simplex_bounded_launch.hip: the bounded-variable selector + the rank-1 update per iteration
+// (lp_simplex_bounded_large).  The bound state lives beside the tableau, one entry per tableau column.
+struct BoundedLargeDev {
+    double* U;    // dev.n: hi - lo, +inf for the artificials
+    int* up;      // dev.n: 1 = the column is held complemented
+    int* flips;   // bound flips since the start of the solve
+};
+int lp_bounded_large_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, opted in
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
+
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS
 int lp_lookahead_prepare(lp_simplex_problem* p);

@@ -361,6 +361,14 @@ public:
         return boundedRun("Solver::boundedSimplex", lo, hi, nullptr, &rule, throw_on_failure);
     }
 
+    // The same at any shape twoPhaseSimplex runs (lp_simplex_bounded_large): the tableau stays in device memory, one
+    // selector and one update launch per iteration, Dantzig's rule; no lp_simplex_bounded_fits limit.  Result and
+    // exceptions as boundedSimplex(lo, hi), and equal to it where both run.
+    BoundedResult boundedSimplexLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                      bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedSimplexLarge", lo, hi, nullptr, nullptr, throw_on_failure, true);
+    }
+
     // The same problem under the bounds lo, hi re-solved from the basis and flags of an earlier result
     // (lp_simplex_bounded_resolve): the bounded primal loop if `from` is still primal feasible, the bounded dual
     // simplex if it is only dual feasible, which it stays under any change of the bounds.  iterations = dual pivots,
@@ -678,9 +686,11 @@ private:
         return out;
     }
 
-    // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form
+    // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form;
+    // large (from and rule null): boundedSimplexLarge
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
-                             const BoundedResult* from, const PivotRule* rule, bool throw_on_failure) const {
+                             const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
+                             bool large = false) const {
         const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
         const lpla::VectorXd& b = _problem.GetRightHandSide();
         const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
@@ -696,7 +706,11 @@ private:
         out.atUpper.assign((size_t)n, 0);
         lp_context* ctx = lpgpu::context(_device);
         const int mx = _problem.IsMaximization() ? 1 : 0;
-        if (!from && !rule)
+        if (large)
+            out.status = lp_simplex_bounded_large(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no,
+                                                  EPS, MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
+                                                  &out.objective, out.iterations);
+        else if (!from && !rule)
             out.status = lp_simplex_bounded(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no, EPS,
                                             MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                             &out.objective, out.iterations);
