@@ -3,6 +3,7 @@
 The built files live under simplexmethod_amd/_build/ (git-ignored, but they travel
 to the GPU box with the repo snapshot).  hipcc cross-compiles without a GPU.
 """
+import functools
 import os
 import shutil
 import subprocess
@@ -132,384 +133,74 @@ def build_cpp_tests(force=False, verbose=False):
 
 
 TESTS_REF = os.path.join(os.path.dirname(_HERE), "tests", "ref")
-TEST_REF_LIB = os.path.join(TESTS_REF, "_build", "libbland_ref.so")
+
+# The restatements the tests compare against (plain C, no GPU; only tests load them): name -> the names whose
+# <name>_ref.c the source tests/ref/<name>_ref.c #includes, directly or through another.
+REFS = {
+    "bland": (),
+    "devex": (),
+    "resolve": (),
+    "duals": (),
+    "ranging": ("duals",),
+    "certificate": ("ranging", "duals"),
+    "parametric": ("resolve",),
+    "parametric_cost": ("resolve",),
+    "mip": ("resolve",),
+    "bounded": (),
+    "bounded_resolve": ("bounded",),
+    "mip_bounded": ("bounded_resolve", "bounded"),
+    "bounded_sens": ("ranging", "duals"),
+    "bounded_certificate": ("certificate", "ranging", "duals"),
+    "bounded_parametric": ("bounded_resolve", "bounded"),
+    "bounded_rules": ("bounded",),
+    "bounded_resolve_rules": ("bounded_resolve", "bounded", "bounded_rules"),
+}
 
 
-def build_test_ref(force=False, verbose=False):
-    """tests/ref/bland_ref.c -> tests/ref/_build/libbland_ref.so: the pivot-rule restatement the tests
-    compare against (plain C, no GPU; fused multiply-adds only where the source writes fma())."""
-    src = os.path.join(TESTS_REF, "bland_ref.c")
+def build_ref(name, force=False, verbose=False):
+    """tests/ref/<name>_ref.c -> tests/ref/_build/lib<name>_ref.so, rebuilt when the source or a file it includes is
+    newer; None without the source.  Fused multiply-adds only where the source writes fma()."""
+    src = os.path.join(TESTS_REF, name + "_ref.c")
+    lib = os.path.join(TESTS_REF, "_build", "lib" + name + "_ref.so")
     if not os.path.exists(src):
         return None
-    if not force and _newer(TEST_REF_LIB, [src]):
-        return TEST_REF_LIB
-    os.makedirs(os.path.dirname(TEST_REF_LIB), exist_ok=True)
+    deps = [src] + [os.path.join(TESTS_REF, inc + "_ref.c") for inc in REFS[name]]
+    if not force and _newer(lib, deps):
+        return lib
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
     cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", TEST_REF_LIB, src, "-lm"]
+           "-o", lib, src, "-lm"]
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
-    return TEST_REF_LIB
-
-
-DEVEX_REF_LIB = os.path.join(TESTS_REF, "_build", "libdevex_ref.so")
-
-
-def build_test_devex_ref(force=False, verbose=False):
-    """tests/ref/devex_ref.c -> tests/ref/_build/libdevex_ref.so: the Devex restatement the tests compare
-    against; flags as build_test_ref."""
-    src = os.path.join(TESTS_REF, "devex_ref.c")
-    if not os.path.exists(src):
-        return None
-    if not force and _newer(DEVEX_REF_LIB, [src]):
-        return DEVEX_REF_LIB
-    os.makedirs(os.path.dirname(DEVEX_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", DEVEX_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return DEVEX_REF_LIB
-
-
-RESOLVE_REF_LIB = os.path.join(TESTS_REF, "_build", "libresolve_ref.so")
-
-
-def build_resolve_ref(force=False, verbose=False):
-    """tests/ref/resolve_ref.c -> tests/ref/_build/libresolve_ref.so: the re-solve from a given basis
-    (primal or dual simplex) the tests compare against; flags as build_test_ref."""
-    src = os.path.join(TESTS_REF, "resolve_ref.c")
-    if not os.path.exists(src):
-        return None
-    if not force and _newer(RESOLVE_REF_LIB, [src]):
-        return RESOLVE_REF_LIB
-    os.makedirs(os.path.dirname(RESOLVE_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", RESOLVE_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return RESOLVE_REF_LIB
-
-
-DUALS_REF_LIB = os.path.join(TESTS_REF, "_build", "libduals_ref.so")
-
-
-def build_duals_ref(force=False, verbose=False):
-    """tests/ref/duals_ref.c -> tests/ref/_build/libduals_ref.so: the dual solution at a given basis the
-    tests compare against; flags as build_test_ref."""
-    src = os.path.join(TESTS_REF, "duals_ref.c")
-    if not os.path.exists(src):
-        return None
-    if not force and _newer(DUALS_REF_LIB, [src]):
-        return DUALS_REF_LIB
-    os.makedirs(os.path.dirname(DUALS_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", DUALS_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return DUALS_REF_LIB
-
-
-RANGING_REF_LIB = os.path.join(TESTS_REF, "_build", "libranging_ref.so")
-
-
-def build_ranging_ref(force=False, verbose=False):
-    """tests/ref/ranging_ref.c (which includes duals_ref.c) -> tests/ref/_build/libranging_ref.so: RHS and cost
-    ranging at a given basis the tests compare against; flags as build_duals_ref."""
-    src = os.path.join(TESTS_REF, "ranging_ref.c")
-    if not os.path.exists(src):
-        return None
-    if not force and _newer(RANGING_REF_LIB, [src, os.path.join(TESTS_REF, "duals_ref.c")]):
-        return RANGING_REF_LIB
-    os.makedirs(os.path.dirname(RANGING_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", RANGING_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return RANGING_REF_LIB
-
-
-CERTIFICATE_REF_LIB = os.path.join(TESTS_REF, "_build", "libcertificate_ref.so")
-
-
-def build_certificate_ref(force=False, verbose=False):
-    """tests/ref/certificate_ref.c (which includes ranging_ref.c and duals_ref.c) ->
-    tests/ref/_build/libcertificate_ref.so: Farkas and ray certificates at a given basis the tests compare against;
-    flags as build_ranging_ref."""
-    src = os.path.join(TESTS_REF, "certificate_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "ranging_ref.c"), os.path.join(TESTS_REF, "duals_ref.c")]
-    if not force and _newer(CERTIFICATE_REF_LIB, deps):
-        return CERTIFICATE_REF_LIB
-    os.makedirs(os.path.dirname(CERTIFICATE_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", CERTIFICATE_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return CERTIFICATE_REF_LIB
-
-
-PARAMETRIC_REF_LIB = os.path.join(TESTS_REF, "_build", "libparametric_ref.so")
-
-
-def build_parametric_ref(force=False, verbose=False):
-    """tests/ref/parametric_ref.c (which includes resolve_ref.c) -> tests/ref/_build/libparametric_ref.so: the
-    parametric right-hand-side path from an optimal basis the tests compare against; flags as build_resolve_ref."""
-    src = os.path.join(TESTS_REF, "parametric_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "resolve_ref.c")]
-    if not force and _newer(PARAMETRIC_REF_LIB, deps):
-        return PARAMETRIC_REF_LIB
-    os.makedirs(os.path.dirname(PARAMETRIC_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", PARAMETRIC_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return PARAMETRIC_REF_LIB
-
-
-PARAMETRIC_COST_REF_LIB = os.path.join(TESTS_REF, "_build", "libparametric_cost_ref.so")
-
-
-def build_parametric_cost_ref(force=False, verbose=False):
-    """tests/ref/parametric_cost_ref.c (which includes resolve_ref.c) -> tests/ref/_build/libparametric_cost_ref.so:
-    the parametric cost path from an optimal basis the tests compare against; flags as build_resolve_ref."""
-    src = os.path.join(TESTS_REF, "parametric_cost_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "resolve_ref.c")]
-    if not force and _newer(PARAMETRIC_COST_REF_LIB, deps):
-        return PARAMETRIC_COST_REF_LIB
-    os.makedirs(os.path.dirname(PARAMETRIC_COST_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", PARAMETRIC_COST_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return PARAMETRIC_COST_REF_LIB
-
-
-MIP_REF_LIB = os.path.join(TESTS_REF, "_build", "libmip_ref.so")
-
-
-def build_mip_ref(force=False, verbose=False):
-    """tests/ref/mip_ref.c (which includes resolve_ref.c) -> tests/ref/_build/libmip_ref.so: the depth-first
-    branch-and-bound the tests compare against; flags as build_resolve_ref."""
-    src = os.path.join(TESTS_REF, "mip_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "resolve_ref.c")]
-    if not force and _newer(MIP_REF_LIB, deps):
-        return MIP_REF_LIB
-    os.makedirs(os.path.dirname(MIP_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", MIP_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return MIP_REF_LIB
-
-
-BOUNDED_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_ref.so")
-
-
-def build_bounded_ref(force=False, verbose=False):
-    """tests/ref/bounded_ref.c -> tests/ref/_build/libbounded_ref.so: the two-phase bounded-variable simplex the tests
-    compare against; flags as build_test_ref."""
-    src = os.path.join(TESTS_REF, "bounded_ref.c")
-    if not os.path.exists(src):
-        return None
-    if not force and _newer(BOUNDED_REF_LIB, [src]):
-        return BOUNDED_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_REF_LIB
-
-
-BOUNDED_RESOLVE_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_resolve_ref.so")
-
-
-def build_bounded_resolve_ref(force=False, verbose=False):
-    """tests/ref/bounded_resolve_ref.c (which includes bounded_ref.c) -> tests/ref/_build/libbounded_resolve_ref.so:
-    the bounded-variable re-solve from a given basis the tests compare against; flags as build_bounded_ref."""
-    src = os.path.join(TESTS_REF, "bounded_resolve_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "bounded_ref.c")]
-    if not force and _newer(BOUNDED_RESOLVE_REF_LIB, deps):
-        return BOUNDED_RESOLVE_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_RESOLVE_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_RESOLVE_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_RESOLVE_REF_LIB
-
-
-MIP_BOUNDED_REF_LIB = os.path.join(TESTS_REF, "_build", "libmip_bounded_ref.so")
-
-
-def build_mip_bounded_ref(force=False, verbose=False):
-    """tests/ref/mip_bounded_ref.c (which includes bounded_resolve_ref.c and bounded_ref.c) ->
-    tests/ref/_build/libmip_bounded_ref.so: the branch-and-bound over variable bounds the tests compare against; flags
-    as build_bounded_resolve_ref."""
-    src = os.path.join(TESTS_REF, "mip_bounded_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "bounded_resolve_ref.c"), os.path.join(TESTS_REF, "bounded_ref.c")]
-    if not force and _newer(MIP_BOUNDED_REF_LIB, deps):
-        return MIP_BOUNDED_REF_LIB
-    os.makedirs(os.path.dirname(MIP_BOUNDED_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", MIP_BOUNDED_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return MIP_BOUNDED_REF_LIB
-
-
-BOUNDED_SENS_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_sens_ref.so")
-
-
-def build_bounded_sens_ref(force=False, verbose=False):
-    """tests/ref/bounded_sens_ref.c (which includes ranging_ref.c and duals_ref.c) ->
-    tests/ref/_build/libbounded_sens_ref.so: the dual solution and ranging of a bounded-variable LP at a given basis
-    and flags the tests compare against; flags as build_ranging_ref."""
-    src = os.path.join(TESTS_REF, "bounded_sens_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "ranging_ref.c"), os.path.join(TESTS_REF, "duals_ref.c")]
-    if not force and _newer(BOUNDED_SENS_REF_LIB, deps):
-        return BOUNDED_SENS_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_SENS_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_SENS_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_SENS_REF_LIB
-
-
-BOUNDED_CERTIFICATE_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_certificate_ref.so")
-
-
-def build_bounded_certificate_ref(force=False, verbose=False):
-    """tests/ref/bounded_certificate_ref.c (which includes certificate_ref.c, ranging_ref.c and duals_ref.c) ->
-    tests/ref/_build/libbounded_certificate_ref.so: Farkas and ray certificates of a bounded-variable LP at a given
-    basis and flags the tests compare against; flags as build_certificate_ref."""
-    src = os.path.join(TESTS_REF, "bounded_certificate_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("certificate_ref.c", "ranging_ref.c", "duals_ref.c")]
-    if not force and _newer(BOUNDED_CERTIFICATE_REF_LIB, deps):
-        return BOUNDED_CERTIFICATE_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_CERTIFICATE_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_CERTIFICATE_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_CERTIFICATE_REF_LIB
-
-
-BOUNDED_PARAMETRIC_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_parametric_ref.so")
-
-
-def build_bounded_parametric_ref(force=False, verbose=False):
-    """tests/ref/bounded_parametric_ref.c (which includes bounded_resolve_ref.c and bounded_ref.c) ->
-    tests/ref/_build/libbounded_parametric_ref.so: the parametric right-hand-side and cost paths of a bounded-variable
-    LP from an optimal basis and flags the tests compare against; flags as build_bounded_resolve_ref."""
-    src = os.path.join(TESTS_REF, "bounded_parametric_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("bounded_resolve_ref.c", "bounded_ref.c")]
-    if not force and _newer(BOUNDED_PARAMETRIC_REF_LIB, deps):
-        return BOUNDED_PARAMETRIC_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_PARAMETRIC_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_PARAMETRIC_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_PARAMETRIC_REF_LIB
-
-
-BOUNDED_RULES_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_rules_ref.so")
-
-
-def build_bounded_rules_ref(force=False, verbose=False):
-    """tests/ref/bounded_rules_ref.c (which includes bounded_ref.c) -> tests/ref/_build/libbounded_rules_ref.so: the
-    two-phase bounded-variable simplex under Dantzig's, Bland's or the Devex rule the tests compare against; flags as
-    build_bounded_ref."""
-    src = os.path.join(TESTS_REF, "bounded_rules_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src, os.path.join(TESTS_REF, "bounded_ref.c")]
-    if not force and _newer(BOUNDED_RULES_REF_LIB, deps):
-        return BOUNDED_RULES_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_RULES_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_RULES_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_RULES_REF_LIB
-
-
-BOUNDED_RESOLVE_RULES_REF_LIB = os.path.join(TESTS_REF, "_build", "libbounded_resolve_rules_ref.so")
-
-
-def build_bounded_resolve_rules_ref(force=False, verbose=False):
-    """tests/ref/bounded_resolve_rules_ref.c (which includes bounded_resolve_ref.c, bounded_ref.c and
-    bounded_rules_ref.c) -> tests/ref/_build/libbounded_resolve_rules_ref.so: the bounded-variable re-solve whose primal
-    branch runs under a pivot rule; flags as build_bounded_ref."""
-    src = os.path.join(TESTS_REF, "bounded_resolve_rules_ref.c")
-    if not os.path.exists(src):
-        return None
-    deps = [src] + [os.path.join(TESTS_REF, f) for f in ("bounded_rules_ref.c", "bounded_resolve_ref.c", "bounded_ref.c")]
-    if not force and _newer(BOUNDED_RESOLVE_RULES_REF_LIB, deps):
-        return BOUNDED_RESOLVE_RULES_REF_LIB
-    os.makedirs(os.path.dirname(BOUNDED_RESOLVE_RULES_REF_LIB), exist_ok=True)
-    cmd = ["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra",
-           "-o", BOUNDED_RESOLVE_RULES_REF_LIB, src, "-lm"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return BOUNDED_RESOLVE_RULES_REF_LIB
+    return lib
+
+
+# The per-reference entry points the tests and their helpers call: build_ref with the name bound
+build_test_ref = functools.partial(build_ref, "bland")
+build_test_devex_ref = functools.partial(build_ref, "devex")
+build_resolve_ref = functools.partial(build_ref, "resolve")
+build_duals_ref = functools.partial(build_ref, "duals")
+build_ranging_ref = functools.partial(build_ref, "ranging")
+build_certificate_ref = functools.partial(build_ref, "certificate")
+build_parametric_ref = functools.partial(build_ref, "parametric")
+build_parametric_cost_ref = functools.partial(build_ref, "parametric_cost")
+build_mip_ref = functools.partial(build_ref, "mip")
+build_bounded_ref = functools.partial(build_ref, "bounded")
+build_bounded_resolve_ref = functools.partial(build_ref, "bounded_resolve")
+build_mip_bounded_ref = functools.partial(build_ref, "mip_bounded")
+build_bounded_sens_ref = functools.partial(build_ref, "bounded_sens")
+build_bounded_certificate_ref = functools.partial(build_ref, "bounded_certificate")
+build_bounded_parametric_ref = functools.partial(build_ref, "bounded_parametric")
+build_bounded_rules_ref = functools.partial(build_ref, "bounded_rules")
+build_bounded_resolve_rules_ref = functools.partial(build_ref, "bounded_resolve_rules")
 
 
 def build_all(force=False, verbose=False):
     hip, host = build_hip(force, verbose), build_host(force, verbose)
     build_cpp_tests(force, verbose)
-    build_test_ref(force, verbose)
-    build_test_devex_ref(force, verbose)
-    build_resolve_ref(force, verbose)
-    build_duals_ref(force, verbose)
-    build_ranging_ref(force, verbose)
-    build_certificate_ref(force, verbose)
-    build_parametric_ref(force, verbose)
-    build_parametric_cost_ref(force, verbose)
-    build_mip_ref(force, verbose)
-    build_bounded_ref(force, verbose)
-    build_bounded_resolve_ref(force, verbose)
-    build_mip_bounded_ref(force, verbose)
-    build_bounded_sens_ref(force, verbose)
-    build_bounded_certificate_ref(force, verbose)
-    build_bounded_parametric_ref(force, verbose)
-    build_bounded_rules_ref(force, verbose)
-    build_bounded_resolve_rules_ref(force, verbose)
+    for name in REFS:
+        build_ref(name, force, verbose)
     return hip, host
 
 

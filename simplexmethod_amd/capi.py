@@ -5,6 +5,7 @@ object is missing, and `Context()` raises if no gfx950 device is usable.
 Matrices are passed as (m, n) numpy arrays and converted to the ABI's column-major
 layout (Eigen's default, /root/reference/src/ProblemTypes/Canonical.cpp:10).
 """
+import collections
 import ctypes as C
 import os
 
@@ -300,6 +301,29 @@ def colmajor(A):
     return np.ascontiguousarray(A.T).reshape(-1)
 
 
+PackedLP = collections.namedtuple("PackedLP", "batch m n A b c basis lo hi at_upper")
+
+
+def pack_lp(A, b, c, basis=None, lo=None, hi=None, at_upper=None, *, batched=False):
+    """The ABI's form of an LP's arrays, or with `batched` of A (batch, m, n) and (batch, ...) vectors: a PackedLP
+    with A column-major per LP and every array flat and contiguous, float64 (A, b, c, lo, hi) or int32 (basis,
+    at_upper); what is not given stays None.  b and basis hold m entries per LP, the others n: anything else raises
+    ValueError."""
+    A = np.asarray(A, dtype=np.float64)
+    batch, m, n = A.shape if batched else (1,) + A.shape
+    Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1) if batched else colmajor(A)
+    out = []
+    for name, v, dtype, per in (("b", b, np.float64, m), ("c", c, np.float64, n), ("basis", basis, np.int32, m),
+                                ("lo", lo, np.float64, n), ("hi", hi, np.float64, n),
+                                ("at_upper", at_upper, np.int32, n)):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=dtype).reshape(-1)
+            if v.size != batch * per:
+                raise ValueError(f"{name}: expected {per} entries per LP ({batch * per}), got {v.size}")
+        out.append(v)
+    return PackedLP(batch, m, n, Af, *out)
+
+
 # ---- synthetic LPs (SURVEY.md §8(d)); bit-identical to oracle/lp_oracle.c:orc_gen_lp ----
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -359,6 +383,14 @@ def _mask(integer, n):
     if integer.size != n:
         raise ValueError(f"integer mask: expected {n} entries, got {integer.size}")
     return integer
+
+
+def _direction(v, size, what="the direction must have {size} entries, got {got}"):
+    """The direction of a parametric call, flat float64; ValueError(`what`) unless it has `size` entries."""
+    v = _f64(v).reshape(-1)
+    if v.size != size:
+        raise ValueError(what.format(size=size, got=v.size))
+    return v
 
 
 def _parametric_out(batch, m, max_breaks):
@@ -431,11 +463,9 @@ class Context:
 
     def simplex_solve(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
                       max_iter=MAX_ITER, pivot_rule="dantzig"):
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else n_orig
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
         x = np.zeros(max(n_orig, 1))
         bo = np.zeros(m, dtype=np.int32)
         obj = C.c_double(float("nan"))
@@ -449,10 +479,9 @@ class Context:
     def two_phase(self, A, b, c, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER,
                   pivot_rule="dantzig"):
         """lp_simplex_two_phase: no starting basis needed."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c)
+        m, n, Af, b, c = p.m, p.n, p.A, p.b, p.c
         n_orig = n if n_orig is None else n_orig
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
         x = np.zeros(n_orig)
         bo = np.full(m, -1, dtype=np.int32)
         obj = C.c_double(float("nan"))
@@ -467,11 +496,9 @@ class Context:
         """lp_simplex_resolve: re-solve from `basis` (primal simplex if it is primal feasible, dual simplex if
         it is only dual feasible).  iters = (dual pivots, primal pivots).  A basis that is neither primal nor dual
         feasible raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else n_orig
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
         x = np.zeros(max(n_orig, 1))
         bo = np.zeros(m, dtype=np.int32)
         obj = C.c_double(float("nan"))
@@ -483,12 +510,9 @@ class Context:
     def resolve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS, max_iter=MAX_ITER):
         """lp_simplex_resolve_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m); per LP
         exactly simplex_resolve().  iters: (batch, 2) = dual, primal pivots."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else n_orig
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
         x = np.zeros((batch, n_orig))
         bo = np.zeros((batch, m), dtype=np.int32)
         obj = np.full(batch, np.nan)
@@ -512,10 +536,8 @@ class Context:
         """lp_basis_duals: shadow prices y (m), reduced costs d (n) and w = b.y of the LP (A, b, c) at `basis`.
         dict(status, y, d, w); y, d, w are NaN unless status is OPTIMAL.  An index out of range raises LPError
         with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         y, d, w = np.zeros(m), np.zeros(n), C.c_double(0.0)
         rc = self.check(self.lib.lp_basis_duals(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), _d(y), _d(d),
                                                 C.byref(w)))
@@ -524,11 +546,8 @@ class Context:
     def basis_duals_batched(self, A, b, c, basis):
         """lp_basis_duals_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).
         dict(status (batch), y (batch, m), d (batch, n), w (batch))."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         y, d, w = np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
         st = np.zeros(batch, dtype=np.int32)
         self.check(self.lib.lp_basis_duals_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis), _d(y),
@@ -550,10 +569,8 @@ class Context:
         dict(status, b_lo, b_hi (m), b_leave (m, 2), c_lo, c_hi (n), c_enter (n, 2)): the ends and the leaving /
         entering column at each (-1 for an infinite end); NaN and -1 unless status is OPTIMAL.  An index out of
         range or a negative eps raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         rhs, cost = np.zeros(2 * m), np.zeros(2 * n)
         rv, cv = np.zeros(2 * m, np.int32), np.zeros(2 * n, np.int32)
         rc = self.check(self.lib.lp_basis_ranging(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
@@ -563,11 +580,8 @@ class Context:
     def basis_ranging_batched(self, A, b, c, basis, maximize=True, eps=EPS):
         """lp_basis_ranging_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).  The dict of
         basis_ranging with a leading batch axis; status (batch)."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         rhs, cost = np.zeros((batch, 2 * m)), np.zeros((batch, 2 * n))
         rv, cv = np.zeros((batch, 2 * m), np.int32), np.zeros((batch, 2 * n), np.int32)
         st = np.zeros(batch, dtype=np.int32)
@@ -588,10 +602,9 @@ class Context:
         status OPTIMAL (reached t_max), INFEASIBLE (infeasible past t[-1]), ITER_LIMIT (max_breaks pivots done) or
         SINGULAR (empty arrays).  A basis that is not optimal at t = 0, an index out of range, t_max < 0, eps < 0 or
         max_breaks < 0 raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
-        Af, b, c, d = colmajor(A), _f64(b), _f64(c), _f64(d)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
+        d = _direction(d, m)
         out = _parametric_out(1, m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, _ = out
         rc = self.check(self.lib.lp_basis_parametric(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
@@ -606,11 +619,9 @@ class Context:
         """lp_basis_parametric_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m), d (batch, m).
         dict(status (batch), nseg (batch), t, obj (batch, max_breaks+2), slope, enter, leave (batch, max_breaks+1),
         basis (batch, m)), padded with NaN / -1 past each path."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c, d = _f64(b).reshape(-1), _f64(c).reshape(-1), _f64(d).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
+        d = _direction(d, batch * m)
         out = _parametric_out(batch, m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, st = out
         self.check(self.lib.lp_basis_parametric_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
@@ -631,10 +642,9 @@ class Context:
         status OPTIMAL (reached t_max), UNBOUNDED (unbounded past t[-1]), ITER_LIMIT (max_breaks pivots done) or
         SINGULAR (empty arrays).  A basis that is not optimal at t = 0, an index out of range, t_max < 0, eps < 0 or
         max_breaks < 0 raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
-        Af, b, c, g = colmajor(A), _f64(b), _f64(c), _f64(g)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
+        g = _direction(g, n)
         out = _parametric_out(1, m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, _ = out
         rc = self.check(self.lib.lp_basis_parametric_cost(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis),
@@ -650,11 +660,9 @@ class Context:
         """lp_basis_parametric_cost_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m),
         g (batch, n).  dict(status (batch), nseg (batch), t, obj (batch, max_breaks+2), slope, enter, leave
         (batch, max_breaks+1), basis (batch, m)), padded with NaN / -1 past each path."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c, g = _f64(b).reshape(-1), _f64(c).reshape(-1), _f64(g).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
+        g = _direction(g, batch * n)
         out = _parametric_out(batch, m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, st = out
         self.check(self.lib.lp_basis_parametric_cost_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
@@ -674,11 +682,9 @@ class Context:
         the root basis `basis` (as resolve: primal or dual feasible).  dict(status, found, x (n_orig), obj, bound,
         stats (nodes, dual pivots, primal pivots, deepest level)); x and obj NaN without an incumbent.  A basis that
         is no valid start, a bad argument or a shape beyond mip_fits raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else int(n_orig)
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
         integer = _mask(integer, n)
         x, obj, bound, found, stats, _ = _mip_out(1, n_orig)
         rc = self.check(self.lib.lp_mip_solve(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize), n_orig,
@@ -692,12 +698,9 @@ class Context:
                     max_depth=MAX_DEPTH, max_nodes=MAX_NODES, max_iter=MAX_ITER):
         """lp_mip_solve_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m), one mask (n).
         dict(status, found, obj, bound (batch), x (batch, n_orig), stats (batch, 4))."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else int(n_orig)
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
         integer = _mask(integer, n)
         out = _mip_out(batch, n_orig)
         x, obj, bound, found, stats, st = out
@@ -726,10 +729,9 @@ class Context:
         dict(status, x (n_orig), basis (m), at_upper (n, 0/1), obj, iters (phase-I pivots, drive-out pivots, phase-II
         pivots, bound flips)); x NaN and obj NaN unless OPTIMAL.  A bad bound or a shape beyond bounded_fits raises
         LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, lo=lo, hi=hi)
+        m, n, Af, b, c, lo, hi = p.m, p.n, p.A, p.b, p.c, p.lo, p.hi
         n_orig = n if n_orig is None else int(n_orig)
-        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
         x = np.full(n_orig, np.nan)
         bo = np.full(m, -1, dtype=np.int32)
         up = np.zeros(n, dtype=np.int32)
@@ -744,14 +746,9 @@ class Context:
         """lp_simplex_bounded_batched: A (batch, m, n), b (batch, m), c / lo / hi (batch, n).  dict(status (batch),
         x (batch, n_orig), basis (batch, m), at_upper (batch, n), obj (batch), iters (batch, 4)); per LP exactly
         bounded(), pivot_rule included (lp_simplex_bounded_batched_ex)."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, lo=lo, hi=hi, batched=True)
+        batch, m, n, Af, b, c, lo, hi = p.batch, p.m, p.n, p.A, p.b, p.c, p.lo, p.hi
         n_orig = n if n_orig is None else int(n_orig)
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
-        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
-            raise ValueError("b, c, lo, hi must have batch*m, batch*n entries")
         x = np.full((batch, n_orig), np.nan)
         bo = np.full((batch, m), -1, dtype=np.int32)
         up = np.zeros((batch, n), dtype=np.int32)
@@ -766,10 +763,9 @@ class Context:
     def bounded_large(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
         """lp_simplex_bounded_large: the LP of bounded() on the tableau in HBM, at any shape two_phase() runs (no
         bounded_fits limit); Dantzig's rule.  Returns the dict of bounded(), equal to it where both run."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, lo=lo, hi=hi)
+        m, n, Af, b, c, lo, hi = p.m, p.n, p.A, p.b, p.c, p.lo, p.hi
         n_orig = n if n_orig is None else int(n_orig)
-        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
         x = np.full(n_orig, np.nan)
         bo = np.full(m, -1, dtype=np.int32)
         up = np.zeros(n, dtype=np.int32)
@@ -797,14 +793,9 @@ class Context:
         pivots, bound flips).  A basis that is neither, a bad index or flag, a bad bound or a shape beyond bounded_fits
         raises LPError with code BAD_ARG.  pivot_rule as in bounded() (lp_simplex_bounded_resolve_ex): it governs the
         primal loop only; the dual simplex is the same under every rule."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
-        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
-        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
-        if basis.size != m or at_upper.size != n:
-            raise ValueError("basis must have m and at_upper n entries")
         x = np.full(n_orig, np.nan)
         bo = np.full(m, -1, dtype=np.int32)
         up = np.zeros(n, dtype=np.int32)
@@ -821,18 +812,10 @@ class Context:
         dict as bounded_batched() with iters (batch, 3); per LP exactly bounded_resolve(), except that a basis that
         is no valid start is that LP's status BAD_ARG.  pivot_rule as in bounded_resolve()
         (lp_simplex_bounded_resolve_batched_ex)."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
-        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
-        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
-            raise ValueError("b, c, lo, hi must have batch*m, batch*n entries")
-        if basis.size != batch * m or at_upper.size != batch * n:
-            raise ValueError("basis, at_upper must have batch*m, batch*n entries")
         x = np.full((batch, n_orig), np.nan)
         bo = np.full((batch, m), -1, dtype=np.int32)
         up = np.zeros((batch, n), dtype=np.int32)
@@ -845,26 +828,14 @@ class Context:
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     # ---- the dual solution and ranging of a bounded-variable LP at a basis ----------------------
-    def _bounded_basis_in(self, A, b, c, lo, hi, basis, at_upper, batched):
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape if batched else (1,) + A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1) if batched else colmajor(A)
-        b, c, lo, hi = (_f64(v).reshape(-1) for v in (b, c, lo, hi))
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
-        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
-        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
-            raise ValueError("b, c, lo, hi must have m, n, n, n entries per LP")
-        if basis.size != batch * m or at_upper.size != batch * n:
-            raise ValueError("basis must have m and at_upper n entries per LP")
-        return batch, m, n, Af, b, c, lo, hi, basis, at_upper
-
     def bounded_duals(self, A, b, c, lo, hi, basis, at_upper):
         """lp_basis_bounded_duals: the LP of bounded() at `basis` (m) and `at_upper` (n, 0/1), normally a result's: the
         point x (n) they define, shadow prices y (m), reduced costs d (n) and w = b.y + sum d_j x_j over the non-basic
         columns (c.x at an optimum), in the original variables.  dict(status, x, y, d, w); NaN unless status is
         OPTIMAL (SINGULAR: a crash failed; INFEASIBLE: some hi < lo).  A bad bound, index or flag or a shape beyond
         basis_bounded_fits raises LPError with code BAD_ARG."""
-        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         x, y, d, w = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(1)
         rc = self.check(self.lib.lp_basis_bounded_duals(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
                                                         _i(at_upper), _d(x), _d(y), _d(d), _d(w)))
@@ -873,7 +844,9 @@ class Context:
     def bounded_duals_batched(self, A, b, c, lo, hi, basis, at_upper):
         """lp_basis_bounded_duals_batched: A (batch, m, n), b (batch, m), c / lo / hi / at_upper (batch, n), basis
         (batch, m).  The dict of bounded_duals with a leading batch axis; status (batch)."""
-        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
         x, y, d, w = np.zeros((batch, n)), np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
         st = np.zeros(batch, dtype=np.int32)
         self.check(self.lib.lp_basis_bounded_duals_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
@@ -884,7 +857,8 @@ class Context:
         """lp_basis_bounded_ranging: how far each b_i and c_j can move before `basis` and `at_upper` stop being
         feasible / optimal for the LP of bounded().  The dict of basis_ranging plus b_side (m, 2): the bound the
         leaving variable leaves at (0 lower, 1 upper, -1 for an infinite end); NaN and -1 unless status is OPTIMAL."""
-        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         rhs, cost = np.zeros(2 * m), np.zeros(2 * n)
         rv, rs, cv = np.zeros(2 * m, np.int32), np.zeros(2 * m, np.int32), np.zeros(2 * n, np.int32)
         rc = self.check(self.lib.lp_basis_bounded_ranging(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
@@ -895,7 +869,9 @@ class Context:
     def bounded_ranging_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
         """lp_basis_bounded_ranging_batched: arrays as bounded_duals_batched.  The dict of bounded_ranging with a
         leading batch axis; status (batch)."""
-        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
         rhs, cost = np.zeros((batch, 2 * m)), np.zeros((batch, 2 * n))
         rv, rs = np.zeros((batch, 2 * m), np.int32), np.zeros((batch, 2 * m), np.int32)
         cv = np.zeros((batch, 2 * n), np.int32)
@@ -918,7 +894,8 @@ class Context:
         computed; SINGULAR for a singular crash or a repeated index, INFEASIBLE for some hi < lo (then NONE).  A bad
         bound, index or flag, a negative eps or a shape beyond basis_bounded_certificate_fits raises LPError with code
         BAD_ARG."""
-        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         kind, index = np.zeros(1, np.int32), np.zeros(1, np.int32)
         farkas, ray, value = np.zeros(m), np.zeros(n), np.zeros(1)
         rc = self.check(self.lib.lp_basis_bounded_certificate(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
@@ -933,7 +910,9 @@ class Context:
         come from: only LPs whose entry is INFEASIBLE or UNBOUNDED get a certificate (and keep the entry as their
         status when it was computed), the others keep their entry and get NONE.  The dict of
         basis_bounded_certificate with a leading batch axis; status, kind, value and index (batch)."""
-        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
         if run_status is not None:
             run_status = np.ascontiguousarray(run_status, dtype=np.int32).reshape(-1)
             if run_status.size != batch:
@@ -953,10 +932,9 @@ class Context:
     # ---- parametric right-hand side and cost of a bounded-variable LP from an optimal basis -------
     def _bounded_parametric(self, fn, width, A, b, c, lo, hi, basis, at_upper, direction, t_max, maximize, eps,
                             max_breaks):
-        _, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, False)
-        direction = _f64(direction).reshape(-1)
-        if direction.size != (n if width == "n" else m):
-            raise ValueError("the direction must have %s entries" % width)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
+        direction = _direction(direction, n if width == "n" else m, "the direction must have %s entries" % width)
         mb = max(int(max_breaks), 0)
         nseg, t, obj, slope, enter, leave, bo, _ = _parametric_out(1, m, mb)
         side, up = np.zeros((1, mb + 1), np.int32), np.zeros(n, np.int32)
@@ -970,10 +948,11 @@ class Context:
 
     def _bounded_parametric_batched(self, fn, width, A, b, c, lo, hi, basis, at_upper, direction, t_max, maximize, eps,
                                     max_breaks, run_status):
-        batch, m, n, Af, b, c, lo, hi, basis, at_upper = self._bounded_basis_in(A, b, c, lo, hi, basis, at_upper, True)
-        direction = _f64(direction).reshape(-1)
-        if direction.size != batch * (n if width == "n" else m):
-            raise ValueError("the direction must have %s entries per LP" % width)
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
+        direction = _direction(direction, batch * (n if width == "n" else m),
+                               "the direction must have %s entries per LP" % width)
         if run_status is not None:
             run_status = np.ascontiguousarray(run_status, dtype=np.int32).reshape(-1)
             if run_status.size != batch:
@@ -1040,14 +1019,9 @@ class Context:
         dict(status, found, x (n_orig), obj, bound, stats (nodes, dual pivots, primal pivots, bound flips, deepest
         level)); x and obj NaN without an incumbent.  A start that is no valid one, a fractional bound on a marked
         column, a bad argument or a shape beyond mip_bounded_fits raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
-        Af, b, c, lo, hi = colmajor(A), _f64(b), _f64(c), _f64(lo), _f64(hi)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
-        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
-        if basis.size != m or at_upper.size != n:
-            raise ValueError("basis must have m and at_upper n entries")
         integer = _mask(integer, n)
         x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5)
         rc = self.check(self.lib.lp_mip_bounded_solve(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
@@ -1064,9 +1038,7 @@ class Context:
         None.  basis=None runs bounded_batched() first and searches from its bases and flags, its statuses passed as
         root_status: an LP whose cold solve is not OPTIMAL keeps that status.  dict(status, found, obj, bound (batch),
         x (batch, n_orig), stats (batch, 5))."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        n_orig = n if n_orig is None else int(n_orig)
+        n_orig = np.shape(A)[2] if n_orig is None else int(n_orig)
         if basis is None:
             if at_upper is not None or root_status is not None:
                 raise ValueError("at_upper and root_status go with basis")
@@ -1075,15 +1047,9 @@ class Context:
             ok = root_status == OPTIMAL   # (an unfinished LP's basis may hold artificials: not read, but checked)
             basis = np.where(ok[:, None], cold["basis"], 0)
             at_upper = np.where(ok[:, None], cold["at_upper"], 0)
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
-        at_upper = np.ascontiguousarray(at_upper, dtype=np.int32).reshape(-1)
-        if b.size != batch * m or c.size != batch * n or lo.size != batch * n or hi.size != batch * n:
-            raise ValueError("b, c, lo, hi must have batch*m, batch*n entries")
-        if basis.size != batch * m or at_upper.size != batch * n:
-            raise ValueError("basis, at_upper must have batch*m, batch*n entries")
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
+        basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
         if root_status is not None:
             root_status = np.ascontiguousarray(root_status, dtype=np.int32).reshape(-1)
             if root_status.size != batch:
@@ -1109,10 +1075,8 @@ class Context:
         index): farkas NaN unless the kind is FARKAS, ray NaN unless it is RAY.  status OPTIMAL means the
         certificate was computed; SINGULAR for a singular crash or a repeated index.  An index out of range or a
         negative eps raises LPError with code BAD_ARG."""
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        m, n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
         kind, index = np.zeros(1, np.int32), np.zeros(1, np.int32)
         farkas, ray, value = np.zeros(m), np.zeros(n), np.zeros(1)
         rc = self.check(self.lib.lp_basis_certificate(self.h, _d(Af), m, n, _d(b), _d(c), _i(basis), int(maximize),
@@ -1124,11 +1088,8 @@ class Context:
     def basis_certificate_batched(self, A, b, c, basis, maximize=True, eps=EPS):
         """lp_basis_certificate_batched: A (batch, m, n), b (batch, m), c (batch, n), basis (batch, m).  The dict
         of basis_certificate with a leading batch axis; status, kind, value and index (batch)."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         kind, index, st = np.zeros(batch, np.int32), np.zeros(batch, np.int32), np.zeros(batch, np.int32)
         farkas, ray, value = np.zeros((batch, m)), np.zeros((batch, n)), np.zeros(batch)
         self.check(self.lib.lp_basis_certificate_batched(self.h, batch, _d(Af), m, n, _d(b), _d(c), _i(basis),
@@ -1143,12 +1104,9 @@ class Context:
     def simplex_solve_batched(self, A, b, c, basis, maximize=True, n_orig=None, eps=EPS,
                               max_iter=MAX_ITER, pivot_rule="dantzig"):
         """A: (batch, m, n); b: (batch, m); c: (batch, n); basis: (batch, m)."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, basis, batched=True)
+        batch, m, n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
         n_orig = n if n_orig is None else n_orig
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
         x = np.zeros((batch, n_orig))
         bo = np.zeros((batch, m), dtype=np.int32)
         obj = np.full(batch, np.nan)
@@ -1167,11 +1125,9 @@ class Context:
                           pivot_rule="dantzig"):
         """lp_simplex_two_phase_batched: A (batch, m, n), b (batch, m), c (batch, n), no basis;
         per LP exactly two_phase().  iters: (batch, 3) = phase I, drive-out, phase II."""
-        A = np.asarray(A, dtype=np.float64)
-        batch, m, n = A.shape
+        p = pack_lp(A, b, c, batched=True)
+        batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
         n_orig = n if n_orig is None else n_orig
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
         x = np.zeros((batch, n_orig))
         bo = np.full((batch, m), -1, dtype=np.int32)
         obj = np.full(batch, np.nan)
@@ -1189,10 +1145,9 @@ class Context:
 
     # ---- enumeration ---------------------------------------------------------------------
     def enum_solve(self, A, b, c, maximize=True, n_orig=None):
-        A = np.asarray(A, dtype=np.float64)
-        m, n = A.shape
+        p = pack_lp(A, b, c)
+        m, n, Af, b, c = p.m, p.n, p.A, p.b, p.c
         n_orig = n if n_orig is None else n_orig
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
         x = np.zeros(n_orig)
         bo = np.zeros(m, dtype=np.int32)
         rank = C.c_uint64(0)
@@ -1212,11 +1167,9 @@ class SimplexProblem:
     """Device-resident tableau (lp_simplex_problem)."""
 
     def __init__(self, ctx, A, b, c, basis, maximize=True, n_orig=None):
-        A = np.asarray(A, dtype=np.float64)
-        self.ctx, self.m, self.n = ctx, A.shape[0], A.shape[1]
-        self.n_orig = self.n if n_orig is None else n_orig
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
-        basis = np.ascontiguousarray(basis, dtype=np.int32)
+        p = pack_lp(A, b, c, basis)
+        self.m, self.n, Af, b, c, basis = p.m, p.n, p.A, p.b, p.c, p.basis
+        self.ctx, self.n_orig = ctx, self.n if n_orig is None else n_orig
         h = _vp()
         ctx.check(ctx.lib.lp_simplex_upload(ctx.h, _d(Af), self.m, self.n, _d(b), _d(c), _i(basis),
                                             int(maximize), self.n_orig, C.byref(h)))
@@ -1290,23 +1243,18 @@ class SimplexProblem:
 
 class BatchedProblem:
     def __init__(self, ctx, A, b, c, basis, maximize=True, n_orig=None, resolve=False):
-        A = np.asarray(A, dtype=np.float64)
-        self.ctx = ctx
-        self.batch, self.m, self.n = A.shape
-        self.n_orig = self.n if n_orig is None else n_orig
-        Af = np.ascontiguousarray(np.transpose(A, (0, 2, 1))).reshape(-1)
-        b, c = _f64(b).reshape(-1), _f64(c).reshape(-1)
-        h = _vp()
         self.two_phase = basis is None   # no starting basis: the two-phase flow
+        p = pack_lp(A, b, c, basis, batched=True)
+        self.batch, self.m, self.n, Af, b, c, basis = p.batch, p.m, p.n, p.A, p.b, p.c, p.basis
+        self.ctx, self.n_orig = ctx, self.n if n_orig is None else n_orig
+        h = _vp()
         if resolve:
-            basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
             ctx.check(ctx.lib.lp_batched_resolve_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
                                                         _i(basis), int(maximize), self.n_orig, C.byref(h)))
         elif self.two_phase:
             ctx.check(ctx.lib.lp_batched_two_phase_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b),
                                                           _d(c), int(maximize), self.n_orig, C.byref(h)))
         else:
-            basis = np.ascontiguousarray(basis, dtype=np.int32).reshape(-1)
             ctx.check(ctx.lib.lp_batched_upload(ctx.h, self.batch, _d(Af), self.m, self.n, _d(b), _d(c),
                                                 _i(basis), int(maximize), self.n_orig, C.byref(h)))
         self.h = h
@@ -1383,9 +1331,7 @@ class BatchedProblem:
     def parametric(self, d, t_max=np.inf, eps=EPS, max_breaks=MAX_BREAKS):
         """lp_batched_parametric after run(): the dict of Context.basis_parametric_batched from each LP's final basis,
         d (batch, m), with the handle's sense; LPs whose run status is not OPTIMAL keep it and get nseg 0."""
-        d = _f64(d).reshape(-1)
-        if d.size != self.batch * self.m:
-            raise ValueError(f"parametric: expected {self.batch * self.m} direction entries, got {d.size}")
+        d = _direction(d, self.batch * self.m, "parametric: expected {size} direction entries, got {got}")
         out = _parametric_out(self.batch, self.m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, st = out
         self.ctx.check(self.ctx.lib.lp_batched_parametric(self.h, _d(d), float(t_max), float(eps), int(max_breaks),
@@ -1397,9 +1343,8 @@ class BatchedProblem:
         """lp_batched_parametric_cost after run(): the dict of Context.basis_parametric_cost_batched from each LP's
         final basis, g (batch, n), with the handle's sense; LPs whose run status is not OPTIMAL keep it and get
         nseg 0."""
-        g = _f64(g).reshape(-1)
-        if g.size != self.batch * self.n:
-            raise ValueError(f"parametric_cost: expected {self.batch * self.n} cost direction entries, got {g.size}")
+        g = _direction(g, self.batch * self.n,
+                       "parametric_cost: expected {size} cost direction entries, got {got}")
         out = _parametric_out(self.batch, self.m, max(int(max_breaks), 0))
         nseg, t, obj, slope, enter, leave, bo, st = out
         self.ctx.check(self.ctx.lib.lp_batched_parametric_cost(self.h, _d(g), float(t_max), float(eps),
@@ -1439,10 +1384,9 @@ class EnumProblem:
     """Device-resident enumeration problem (lp_enum_problem)."""
 
     def __init__(self, ctx, A, b, c, maximize=True):
-        A = np.asarray(A, dtype=np.float64)
-        self.ctx, self.m, self.n = ctx, A.shape[0], A.shape[1]
-        self.maximize = bool(maximize)
-        Af, b, c = colmajor(A), _f64(b), _f64(c)
+        p = pack_lp(A, b, c)
+        self.m, self.n, Af, b, c = p.m, p.n, p.A, p.b, p.c
+        self.ctx, self.maximize = ctx, bool(maximize)
         h = _vp()
         ctx.check(ctx.lib.lp_enum_upload(ctx.h, _d(Af), self.m, self.n, _d(b), _d(c),
                                          int(maximize), C.byref(h)))

@@ -847,19 +847,29 @@ static int parametric_args(lp_context* ctx, const char* fn, double t_max, double
     return LP_OPTIMAL;
 }
 
-// Paths of `batch` LPs whose inputs (d in in.extra) are on the device: LPs whose run status is not LP_OPTIMAL keep it
-// and get nseg 0.
-static int parametric_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
-                                double t_max, double eps, int mb, int* nseg_out, double* t_out, double* obj_out,
-                                double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
+// The statuses with which the per-LP path has written a path: the right-hand side's ends infeasible, the cost's unbounded
+static bool rhs_path_written(int st) { return st == LP_OPTIMAL || st == LP_INFEASIBLE || st == LP_ITER_LIMIT; }
+static bool cost_path_written(int st) { return st == LP_OPTIMAL || st == LP_UNBOUNDED || st == LP_ITER_LIMIT; }
+
+struct ParametricOut {
+    int* nseg;
+    double *t, *obj, *slope;
+    int *enter, *leave, *basis;
+};
+
+// Paths of `batch` LPs whose inputs (the direction in in.extra: d, m per LP, or with `cost` g, n per LP) are on the
+// device: LPs whose run status is not LP_OPTIMAL keep it and get nseg 0.
+static int parametric_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, bool cost,
+                                int maximize, double t_max, double eps, int mb, const ParametricOut& out,
+                                int* status_out) {
+    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1), nd = cost ? n : m;
     lp_device_buffer buf;
     LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B)));
     BasisParametricDev d{};
     d.batch = batch;
     d.m = m;
     d.n = n;
-    (void)lp_basis_parametric_lds_bytes(m, n, &d.pitch);
+    (void)(cost ? lp_basis_parametric_cost_lds_bytes : lp_basis_parametric_lds_bytes)(m, n, &d.pitch);
     d.max_breaks = mb;
     d.eps = eps;
     d.t_max = t_max;
@@ -880,217 +890,144 @@ static int parametric_on_device(lp_context* ctx, int batch, int m, int n, const 
     std::vector<char> done;
     std::vector<int> basis;   // per-LP path: the given bases
     int rc;
-    if (lp_basis_parametric_fits(m, n)) {
-        rc = lp_basis_parametric_launch(ctx, d, maximize);
+    if ((cost ? lp_basis_parametric_cost_fits : lp_basis_parametric_fits)(m, n)) {
+        rc = (cost ? lp_basis_parametric_cost_launch : lp_basis_parametric_launch)(ctx, d, maximize);
     } else {
+        const auto device = cost ? lp_basis_parametric_cost_device : lp_basis_parametric_device;
         rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
-            return lp_basis_parametric_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n,
-                                              in.basis + k * m, in.extra + k * m, maximize, t_max, eps, mb,
-                                              d.nseg + k, d.t + k * (mb + 2), d.obj + k * (mb + 2),
-                                              d.slope + k * (mb + 1), d.enter + k * (mb + 1), d.leave + k * (mb + 1),
-                                              d.basis_out + k * m);
-        }, [](int st) { return st == LP_OPTIMAL || st == LP_INFEASIBLE || st == LP_ITER_LIMIT; }, done, basis);
+            return device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n, in.basis + k * m,
+                          in.extra + k * nd, maximize, t_max, eps, mb, d.nseg + k, d.t + k * (mb + 2),
+                          d.obj + k * (mb + 2), d.slope + k * (mb + 1), d.enter + k * (mb + 1),
+                          d.leave + k * (mb + 1), d.basis_out + k * m);
+        }, cost ? cost_path_written : rhs_path_written, done, basis);
     }
     if (rc == LP_OPTIMAL)
-        rc = lp_download(ctx, "basis parametric", {{t_out, d.t, sizeof(double) * nt},
-                                                   {obj_out, d.obj, sizeof(double) * nt},
-                                                   {slope_out, d.slope, sizeof(double) * ns},
-                                                   {enter_out, d.enter, sizeof(int) * ns},
-                                                   {leave_out, d.leave, sizeof(int) * ns},
-                                                   {basis_out, d.basis_out, sizeof(int) * B * m},
-                                                   {nseg_out, d.nseg, sizeof(int) * B},
-                                                   {status_out, d.status, sizeof(int) * B}});
+        rc = lp_download(ctx, cost ? "basis parametric cost" : "basis parametric",
+                         {{out.t, d.t, sizeof(double) * nt},
+                          {out.obj, d.obj, sizeof(double) * nt},
+                          {out.slope, d.slope, sizeof(double) * ns},
+                          {out.enter, d.enter, sizeof(int) * ns},
+                          {out.leave, d.leave, sizeof(int) * ns},
+                          {out.basis, d.basis_out, sizeof(int) * B * m},
+                          {out.nseg, d.nseg, sizeof(int) * B},
+                          {status_out, d.status, sizeof(int) * B}});
     if (rc != LP_OPTIMAL) return rc;
     if (!basis.empty())
-        parametric_pad(B, m, mb, done, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
+        parametric_pad(B, m, mb, done, basis, out.nseg, out.t, out.obj, out.slope, out.enter, out.leave, out.basis);
     return LP_OPTIMAL;
 }
 
-// Cost paths of `batch` LPs whose inputs (g in in.extra) are on the device: LPs whose run status is not LP_OPTIMAL
-// keep it and get nseg 0.
-static int parametric_cost_on_device(lp_context* ctx, int batch, int m, int n, const BasisInputs& in, int maximize,
-                                     double t_max, double eps, int mb, int* nseg_out, double* t_out, double* obj_out,
-                                     double* slope_out, int* enter_out, int* leave_out, int* basis_out,
-                                     int* status_out) {
-    const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1);
+static bool parametric_out_null(const ParametricOut& o) {
+    return !o.nseg || !o.t || !o.obj || !o.slope || !o.enter || !o.leave || !o.basis;
+}
+
+// The single-LP entry of either path
+static int parametric_one(lp_context* ctx, const char* who, bool cost, const double* A, int m, int n, const double* b,
+                          const double* c, const int* basis, int maximize, const double* dir, double t_max, double eps,
+                          int max_breaks, const ParametricOut& out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !dir || parametric_out_null(out))
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_breaks must be >= 0");
+    parametric_none(0, m, max_breaks, basis, out.nseg, out.t, out.obj, out.slope, out.enter, out.leave, out.basis);
+    int rc = parametric_args(ctx, who, t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
     lp_device_buffer buf;
-    LP_HIP(ctx, hipMalloc(&buf.ptr, sizeof(double) * (2 * nt + ns) + sizeof(int) * (2 * ns + B * m + 2 * B)));
-    BasisParametricCostDev d{};
-    d.batch = batch;
-    d.m = m;
-    d.n = n;
-    (void)lp_basis_parametric_cost_lds_bytes(m, n, &d.pitch);
-    d.max_breaks = mb;
-    d.eps = eps;
-    d.t_max = t_max;
-    d.A = in.A;
-    d.b = in.b;
-    d.c = in.c;
-    d.g = in.extra;
-    d.basis = in.basis;
-    d.run_status = in.run_status;
-    d.t = reinterpret_cast<double*>(buf.ptr);
-    d.obj = d.t + nt;
-    d.slope = d.obj + nt;
-    d.enter = reinterpret_cast<int*>(d.slope + ns);
-    d.leave = d.enter + ns;
-    d.basis_out = d.leave + ns;
-    d.nseg = d.basis_out + B * m;
-    d.status = d.nseg + B;
-    std::vector<char> done;
-    std::vector<int> basis;   // per-LP path: the given bases
-    int rc;
-    if (lp_basis_parametric_cost_fits(m, n)) {
-        rc = lp_basis_parametric_cost_launch(ctx, d, maximize);
-    } else {
-        rc = per_lp(ctx, batch, m, n, in, d.status, run_optimal, basis_in_range, [&](size_t k) {
-            return lp_basis_parametric_cost_device(ctx, in.A + k * m * n, m, n, in.b + k * m, in.c + k * n,
-                                                   in.basis + k * m, in.extra + k * n, maximize, t_max, eps, mb,
-                                                   d.nseg + k, d.t + k * (mb + 2), d.obj + k * (mb + 2),
-                                                   d.slope + k * (mb + 1), d.enter + k * (mb + 1),
-                                                   d.leave + k * (mb + 1), d.basis_out + k * m);
-        }, [](int st) { return st == LP_OPTIMAL || st == LP_UNBOUNDED || st == LP_ITER_LIMIT; }, done, basis);
-    }
+    BasisInputs in;
+    int status = LP_OPTIMAL;
+    rc = upload(ctx, cost ? "basis parametric cost" : "basis parametric", buf, 1, m, n, A, b, c, dir,
+                (size_t)(cost ? n : m), basis, nullptr, in);
     if (rc == LP_OPTIMAL)
-        rc = lp_download(ctx, "basis parametric cost", {{t_out, d.t, sizeof(double) * nt},
-                                                        {obj_out, d.obj, sizeof(double) * nt},
-                                                        {slope_out, d.slope, sizeof(double) * ns},
-                                                        {enter_out, d.enter, sizeof(int) * ns},
-                                                        {leave_out, d.leave, sizeof(int) * ns},
-                                                        {basis_out, d.basis_out, sizeof(int) * B * m},
-                                                        {nseg_out, d.nseg, sizeof(int) * B},
-                                                        {status_out, d.status, sizeof(int) * B}});
-    if (rc != LP_OPTIMAL) return rc;
-    if (!basis.empty())
-        parametric_pad(B, m, mb, done, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-    return LP_OPTIMAL;
+        rc = parametric_on_device(ctx, 1, m, n, in, cost, maximize, t_max, eps, max_breaks, out, &status);
+    if (rc) return rc;
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is not optimal at t = 0");
+    return status;
+}
+
+// The batched entry of either path
+static int parametric_many(lp_context* ctx, const char* who, bool cost, int batch, const double* A, int m, int n,
+                           const double* b, const double* c, const int* basis, int maximize, const double* dir,
+                           double t_max, double eps, int max_breaks, const ParametricOut& out, int* status_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !basis || !dir || parametric_out_null(out) || !status_out)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    int rc = parametric_args(ctx, who, t_max, eps, max_breaks);
+    if (rc) return rc;
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = upload(ctx, cost ? "basis parametric cost" : "basis parametric", buf, batch, m, n, A, b, c, dir,
+                (size_t)(cost ? n : m), basis, nullptr, in);
+    return rc ? rc
+              : parametric_on_device(ctx, batch, m, n, in, cost, maximize, t_max, eps, max_breaks, out, status_out);
+}
+
+// The entry of either path on a batch handle that has run
+static int parametric_handle(lp_batched_problem* p, const char* who, bool cost, const double* dir, double t_max,
+                             double eps, int max_breaks, const ParametricOut& out, int* status_out) {
+    if (!p) return LP_BAD_ARG;
+    lp_context* ctx = p->ctx;
+    if (!dir || parametric_out_null(out) || !status_out) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    int rc = parametric_args(ctx, who, t_max, eps, max_breaks);
+    if (rc) return rc;
+    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the batch has not run");
+    lp_device_buffer buf;
+    BasisInputs in;
+    rc = batch_inputs(p, cost ? "basis parametric cost" : "basis parametric", buf, dir, (size_t)(cost ? p->n : p->m),
+                      in);
+    return rc ? rc
+              : parametric_on_device(ctx, p->batch, p->m, p->n, in, cost, p->maximize, t_max, eps, max_breaks, out,
+                                     status_out);
 }
 
 int lp_basis_parametric(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                         const int* basis, int maximize, const double* d, double t_max, double eps, int max_breaks,
                         int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                         int* leave_out, int* basis_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: bad dimensions");
-    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: max_breaks must be >= 0");
-    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-    int rc = parametric_args(ctx, "lp_basis_parametric", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    lp_device_buffer buf;
-    BasisInputs in;
-    int status = LP_OPTIMAL;
-    rc = upload(ctx, "basis parametric", buf, 1, m, n, A, b, c, d, (size_t)m, basis, nullptr, in);
-    if (rc == LP_OPTIMAL)
-        rc = parametric_on_device(ctx, 1, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out, obj_out,
-                                  slope_out, enter_out, leave_out, basis_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric: the basis is not optimal at t = 0");
-    return status;
+    return parametric_one(ctx, "lp_basis_parametric", false, A, m, n, b, c, basis, maximize, d, t_max, eps, max_breaks,
+                          {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out});
 }
 
 int lp_basis_parametric_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
                                 const double* c, const int* basis, int maximize, const double* d, double t_max,
                                 double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
                                 double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_batched: bad dimensions");
-    int rc = parametric_args(ctx, "lp_basis_parametric_batched", t_max, eps, max_breaks);
-    if (rc) return rc;
-    lp_device_buffer buf;
-    BasisInputs in;
-    rc = upload(ctx, "basis parametric", buf, batch, m, n, A, b, c, d, (size_t)m, basis, nullptr, in);
-    return rc ? rc
-              : parametric_on_device(ctx, batch, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out,
-                                     obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+    return parametric_many(ctx, "lp_basis_parametric_batched", false, batch, A, m, n, b, c, basis, maximize, d, t_max,
+                           eps, max_breaks, {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out},
+                           status_out);
 }
 
 int lp_batched_parametric(lp_batched_problem* p, const double* d, double t_max, double eps, int max_breaks,
                           int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                           int* leave_out, int* basis_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!d || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: null argument");
-    int rc = parametric_args(ctx, "lp_batched_parametric", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric: the batch has not run");
-    lp_device_buffer buf;
-    BasisInputs in;
-    rc = batch_inputs(p, "basis parametric", buf, d, (size_t)p->m, in);
-    return rc ? rc
-              : parametric_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, t_max, eps, max_breaks, nseg_out,
-                                     t_out, obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+    return parametric_handle(p, "lp_batched_parametric", false, d, t_max, eps, max_breaks,
+                             {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out}, status_out);
 }
 
 int lp_basis_parametric_cost(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                              const int* basis, int maximize, const double* g, double t_max, double eps, int max_breaks,
                              int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                              int* leave_out, int* basis_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: bad dimensions");
-    if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: max_breaks must be >= 0");
-    parametric_none(0, m, max_breaks, basis, nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out);
-    int rc = parametric_args(ctx, "lp_basis_parametric_cost", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (basis_in_range(basis, m, n)) LP_FAIL(ctx, LP_BAD_ARG, "basis index out of range");
-    lp_device_buffer buf;
-    BasisInputs in;
-    int status = LP_OPTIMAL;
-    rc = upload(ctx, "basis parametric cost", buf, 1, m, n, A, b, c, g, (size_t)n, basis, nullptr, in);
-    if (rc == LP_OPTIMAL)
-        rc = parametric_cost_on_device(ctx, 1, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out, obj_out,
-                                       slope_out, enter_out, leave_out, basis_out, &status);
-    if (rc) return rc;
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost: the basis is not optimal at t = 0");
-    return status;
+    return parametric_one(ctx, "lp_basis_parametric_cost", true, A, m, n, b, c, basis, maximize, g, t_max, eps,
+                          max_breaks, {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out});
 }
 
 int lp_basis_parametric_cost_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
                                      const double* c, const int* basis, int maximize, const double* g, double t_max,
                                      double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
                                      double* slope_out, int* enter_out, int* leave_out, int* basis_out, int* status_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !basis || !g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out ||
-        !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: null argument");
-    if (batch <= 0 || m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_parametric_cost_batched: bad dimensions");
-    int rc = parametric_args(ctx, "lp_basis_parametric_cost_batched", t_max, eps, max_breaks);
-    if (rc) return rc;
-    lp_device_buffer buf;
-    BasisInputs in;
-    rc = upload(ctx, "basis parametric cost", buf, batch, m, n, A, b, c, g, (size_t)n, basis, nullptr, in);
-    return rc ? rc
-              : parametric_cost_on_device(ctx, batch, m, n, in, maximize, t_max, eps, max_breaks, nseg_out, t_out,
-                                          obj_out, slope_out, enter_out, leave_out, basis_out, status_out);
+    return parametric_many(ctx, "lp_basis_parametric_cost_batched", true, batch, A, m, n, b, c, basis, maximize, g,
+                           t_max, eps, max_breaks,
+                           {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out}, status_out);
 }
 
 int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_max, double eps, int max_breaks,
                                int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                                int* leave_out, int* basis_out, int* status_out) {
-    if (!p) return LP_BAD_ARG;
-    lp_context* ctx = p->ctx;
-    if (!g || !nseg_out || !t_out || !obj_out || !slope_out || !enter_out || !leave_out || !basis_out || !status_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: null argument");
-    int rc = parametric_args(ctx, "lp_batched_parametric_cost", t_max, eps, max_breaks);
-    if (rc) return rc;
-    if (!p->ran) LP_FAIL(ctx, LP_BAD_ARG, "lp_batched_parametric_cost: the batch has not run");
-    lp_device_buffer buf;
-    BasisInputs in;
-    rc = batch_inputs(p, "basis parametric cost", buf, g, (size_t)p->n, in);
-    return rc ? rc
-              : parametric_cost_on_device(ctx, p->batch, p->m, p->n, in, p->maximize, t_max, eps, max_breaks,
-                                          nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out,
-                                          status_out);
+    return parametric_handle(p, "lp_batched_parametric_cost", true, g, t_max, eps, max_breaks,
+                             {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, basis_out}, status_out);
 }
 
 // ===========================================================================

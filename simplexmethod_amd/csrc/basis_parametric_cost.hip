@@ -39,7 +39,7 @@ __host__ __device__ inline int parametric_cost_status(int code) {
 }
 
 template <int NT, bool MX>
-__global__ __launch_bounds__(NT) void k_batched_parametric_cost(BasisParametricCostDev d) {
+__global__ __launch_bounds__(NT) void k_batched_parametric_cost(BasisParametricDev d) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int m = d.m, n = d.n, W = n + 1, pitch = d.pitch;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(NT) void k_batched_parametric_cost(BasisParametricC
     const double* A = d.A + (size_t)lp * m * n;
     const double* b = d.b + (size_t)lp * m;
     const double* c = d.c + (size_t)lp * n;
-    const double* g = d.g + (size_t)lp * n;
+    const double* g = d.dir + (size_t)lp * n;
     const int* N = d.basis + (size_t)lp * m;
     const double eps = d.eps;
     const int MB = d.max_breaks;
@@ -454,7 +454,7 @@ size_t lp_basis_parametric_cost_lds_bytes(int m, int n, int* pitch_out) {
     return (bytes + 15) & ~(size_t)15;
 }
 
-int lp_basis_parametric_cost_launch(lp_context* ctx, const BasisParametricCostDev& d, int maximize) {
+int lp_basis_parametric_cost_launch(lp_context* ctx, const BasisParametricDev& d, int maximize) {
     if (!lp_basis_parametric_cost_fits(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "basis parametric cost: the shape does not fit one CU's LDS");
     if (d.batch <= 0) return LP_OPTIMAL;

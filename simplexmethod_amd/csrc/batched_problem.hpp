@@ -174,16 +174,17 @@ int lp_basis_certificate_device(lp_context* ctx, const double* dA, int m, int n,
 
 // Parametric right-hand-side paths from given optimal bases, one LP per workgroup (basis_parametric.hip): the
 // re-solve's crash on [A | b | d], then one dual-simplex pivot per breakpoint of z*(t) = opt { c.x : A x = b + t d }.
+// The parametric cost (below) takes the same struct.
 struct BasisParametricDev {
     int batch, m, n;
-    int pitch;              // row pitch (doubles) of the LDS tableau: lp_basis_parametric_lds_bytes
+    int pitch;              // row pitch (doubles) of the LDS tableau: lp_basis_parametric[_cost]_lds_bytes
     int max_breaks;
-    int max_iter;           // 0 (batched_lds_loop.hpp's primal loop is compiled in but never called)
+    int max_iter;           // 0 (batched_lds_loop.hpp's primal loop is compiled in but never called; cost: ignored)
     double eps, t_max;
     const double* A;        // batch x (m*n), each column-major
     const double* b;        // batch x m
     const double* c;        // batch x n
-    const double* dir;      // batch x m: the direction d
+    const double* dir;      // batch x m: the direction d (cost: batch x n, the cost direction g)
     const int* basis;       // batch x m (by position)
     const int* run_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it and gets nseg 0
     int* nseg;              // batch
@@ -211,30 +212,11 @@ int lp_basis_parametric_device(lp_context* ctx, const double* dA, int m, int n, 
 
 // Parametric cost paths from given optimal bases, one LP per workgroup (basis_parametric_cost.hip): the re-solve's
 // crash on [A | b; c | 0; g | 0], then one primal pivot per breakpoint of z*(t) = opt { (c + t g).x : A x = b }.
-struct BasisParametricCostDev {
-    int batch, m, n;
-    int pitch;              // row pitch (doubles) of the LDS tableau: lp_basis_parametric_cost_lds_bytes
-    int max_breaks;
-    double eps, t_max;
-    const double* A;        // batch x (m*n), each column-major
-    const double* b;        // batch x m
-    const double* c;        // batch x n
-    const double* g;        // batch x n: the cost direction
-    const int* basis;       // batch x m (by position)
-    const int* run_status;  // batch, or nullptr: an LP whose entry is not LP_OPTIMAL keeps it and gets nseg 0
-    int* nseg;              // batch
-    double* t;              // batch x (max_breaks+2)
-    double* obj;            // batch x (max_breaks+2)
-    double* slope;          // batch x (max_breaks+1)
-    int* enter;             // batch x (max_breaks+1)
-    int* leave;             // batch x (max_breaks+1)
-    int* basis_out;         // batch x m: the final basis (the given one without a path)
-    int* status;            // batch
-};
+// It takes a BasisParametricDev whose dir is g.
 
 // basis_parametric_cost.hip
 size_t lp_basis_parametric_cost_lds_bytes(int m, int n, int* pitch_out);
-int lp_basis_parametric_cost_launch(lp_context* ctx, const BasisParametricCostDev& d, int maximize);   // fitting shapes
+int lp_basis_parametric_cost_launch(lp_context* ctx, const BasisParametricDev& d, int maximize);   // fitting shapes
 // One LP of any shape on the device (the basis in range, eps >= 0, t_max >= 0, max_breaks >= 0): the crash on
 // [A | b; g | 0] and on [A | b; c | 0] by the single-LP launch pair, then one selector + rank-1 update pair over m+2
 // rows per breakpoint under the polling loop; every pointer is a device pointer.  Returns the path's status

@@ -136,6 +136,65 @@ int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, double e
     return p->h_state->status;
 }
 
+// ---- the two-phase flow shared by lp_simplex_two_phase_ex and lp_simplex_bounded_large
+
+using ProblemOwner = std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)>;
+
+// make_b_nonneg (:61-68) and createAuxiliaryProblem (:70-95) on [A | b]: rows with b_i < -eps change sign, an identity
+// of artificials with cost 1 follows A, and they are the starting basis.  A1 (m x (n+m), column-major) and c1 (n+m)
+// come zeroed; b1 may be b itself (lp_simplex_bounded_large's shifted right-hand side).
+void auxiliary_problem(const double* A, int m, int n, const double* b, double eps, double* A1, double* b1, double* c1,
+                       int* N) {
+    std::vector<char> flip((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        flip[(size_t)i] = b[i] < -eps;
+        b1[i] = flip[(size_t)i] ? -b[i] : b[i];
+        A1[(size_t)(n + i) * m + i] = 1.0;
+        c1[n + i] = 1.0;
+        N[i] = n + i;
+    }
+    for (int j = 0; j < n; ++j) {   // (column by column: both matrices are column-major)
+        const double* src = A + (size_t)j * m;
+        double* dst = A1 + (size_t)j * m;
+        for (int i = 0; i < m; ++i) dst[i] = flip[(size_t)i] ? -src[i] : src[i];
+    }
+}
+
+// Phase I's verdict (:347-353): the artificials' values, summed in artificial-index order, against eps
+int phase1_verdict(lp_context* ctx, const std::string& prefix, const double* xa, int m, int n, double eps) {
+    double sum = 0.0;
+    for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
+    if (!(sum > eps)) return LP_OPTIMAL;
+    ctx->last_error = prefix + ": the problem has no feasible solution (phase I optimum > eps)";
+    return LP_INFEASIBLE;
+}
+
+// The positions of the phase-I basis N that still hold an artificial
+std::vector<int> artificial_positions(const int* N, int m, int n) {
+    std::vector<int> positions;
+    for (int pos = 0; pos < m; ++pos)
+        if (N[pos] >= n) positions.push_back(pos);
+    return positions;
+}
+
+// replaceArtificialColumns (:331-381): every artificial still basic (at level 0) leaves for the first non-basic
+// original column with |T[pos][cand]| > eps, chosen on the device; the positions are known from the phase-I basis, so
+// all pivots are queued behind one another.  No bound enters it.
+int drive_out_artificials(lp_simplex_problem* p, const std::string& prefix, const int* N, int m, int n, double eps,
+                          int* pivots) {
+    const std::vector<int> positions = artificial_positions(N, m, n);
+    if (positions.empty()) return LP_OPTIMAL;
+    const int rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, pivots);
+    if (rc == LP_SINGULAR)   // :372-380: linearly dependent constraints
+        p->ctx->last_error = prefix + ": an artificial variable cannot leave the basis (linearly dependent constraints)";
+    return rc;
+}
+
+// After a positive status: the basis reached, as the one-LP-per-workgroup kernels report it
+int download_basis(lp_simplex_problem* p, int* N) {
+    return lp_simplex_download(p, nullptr, N, nullptr, nullptr, nullptr, 0, nullptr);
+}
+
 int run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
     lp_context* ctx = p->ctx;
     int rc = lp_lookahead_prepare(p);
@@ -710,25 +769,13 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
         fprintf(stderr, "[two_phase] %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
         t_prev = t;
     };
-    // make_b_nonneg (:61-68) and createAuxiliaryProblem (:70-95)
-    std::vector<char> flip((size_t)m);
-    for (int i = 0; i < m; ++i) {
-        flip[i] = b[i] < -eps;
-        b1[i] = flip[i] ? -b[i] : b[i];
-        A1[(size_t)(n + i) * m + i] = 1.0;
-    }
-    for (int j = 0; j < n; ++j) {   // (column by column: both matrices are column-major)
-        const double* src = A + (size_t)j * m;
-        double* dst = A1.data() + (size_t)j * m;
-        for (int i = 0; i < m; ++i) dst[i] = flip[i] ? -src[i] : src[i];
-    }
-    for (int j = n; j < na; ++j) c1[j] = 1.0;
-    for (int t = 0; t < m; ++t) N[t] = n + t;
+    auxiliary_problem(A, m, n, b, eps, A1.data(), b1.data(), c1.data(), N.data());
     stage("auxiliary problem (host)");
     // ---- phase I: minimise the sum of the artificials
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
     if (rc) return rc;
+    ProblemOwner owner(p, lp_simplex_free);
     p->pivot_rule = pivot_rule;   // phase I and phase II; the drive-out has its own rule
     stage("upload");
     lp_simplex_stats st;
@@ -737,27 +784,8 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
     stage("phase I run");
     if (rc == LP_OPTIMAL) rc = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
     stage("phase I download");
-    if (rc == LP_OPTIMAL) {
-        double sum = 0.0;  // :347-350
-        for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
-        if (sum > eps) {  // :352-353
-            rc = LP_INFEASIBLE;
-            ctx->last_error = "two-phase: the problem has no feasible solution (phase I optimum > eps)";
-        }
-    }
-    if (rc == LP_OPTIMAL) {
-        // replaceArtificialColumns (:331-381): every artificial still basic (at level 0) leaves for
-        // the first non-basic original column with |T[pos][cand]| > eps, chosen on the device; the
-        // positions are known from the phase-I basis, so all pivots are queued behind one another
-        std::vector<int> positions;
-        for (int pos = 0; pos < m; ++pos)
-            if (N[pos] >= n) positions.push_back(pos);
-        if (!positions.empty()) {
-            rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, &it[1]);
-            if (rc == LP_SINGULAR)   // :372-380: linearly dependent constraints
-                ctx->last_error = "two-phase: an artificial variable cannot leave the basis (linearly dependent constraints)";
-        }
-    }
+    if (rc == LP_OPTIMAL) rc = phase1_verdict(ctx, "two-phase", xa.data(), m, n, eps);
+    if (rc == LP_OPTIMAL) rc = drive_out_artificials(p, "two-phase", N.data(), m, n, eps, &it[1]);
     // ---- phase II (:383-404) continues on the phase-I tableau: original costs priced out over the
     // current basis, artificial columns barred — no re-inversion of the basis from [A' | b']
     stage("drive-out");
@@ -770,12 +798,12 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
         if (rc == LP_OPTIMAL)
             rc = lp_simplex_download(p, x_out, N.data(), obj_out, nullptr, nullptr, 0, nullptr);
         else if (rc > 0)
-            (void)lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
-    } else if (rc > 0) {   // (phase I's iteration limit too: the basis reached, as the batched kernel reports it)
-        (void)lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+            (void)download_basis(p, N.data());
+    } else if (rc > 0) {   // (phase I's iteration limit too)
+        (void)download_basis(p, N.data());
     }
     stage("phase II download");
-    lp_simplex_free(p);
+    owner.reset();
     stage("free");
     if (basis_out) std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
     if (iters_out) std::memcpy(iters_out, it, sizeof(it));
@@ -819,24 +847,12 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
         const double* src = A + (size_t)j * m;
         for (int i = 0; i < m; ++i) b1[(size_t)i] = std::fma(-src[i], lo[j], b1[(size_t)i]);
     }
-    std::vector<char> flip((size_t)m);
-    for (int i = 0; i < m; ++i) {
-        flip[(size_t)i] = b1[(size_t)i] < -eps;
-        if (flip[(size_t)i]) b1[(size_t)i] = -b1[(size_t)i];
-        A1[(size_t)(n + i) * m + i] = 1.0;
-    }
-    for (int j = 0; j < n; ++j) {
-        const double* src = A + (size_t)j * m;
-        double* dst = A1.data() + (size_t)j * m;
-        for (int i = 0; i < m; ++i) dst[i] = flip[(size_t)i] ? -src[i] : src[i];
-    }
-    for (int j = n; j < na; ++j) c1[(size_t)j] = 1.0;
-    for (int t = 0; t < m; ++t) N[(size_t)t] = n + t;
+    auxiliary_problem(A, m, n, b1.data(), eps, A1.data(), b1.data(), c1.data(), N.data());
 
     lp_simplex_problem* p = nullptr;
     int rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
     if (rc) return rc;
-    std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)> owner(p, lp_simplex_free);
+    ProblemOwner owner(p, lp_simplex_free);
     rc = lp_bounded_large_prepare(p);
     if (rc) return rc;
     // the bound state beside the tableau
@@ -861,24 +877,8 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
     it[0] = iters - flips1;
     it[3] = flips1;
     if (rc == LP_OPTIMAL) rc = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
-    if (rc == LP_OPTIMAL) {
-        double sum = 0.0;   // the artificials' values in artificial-index order
-        for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
-        if (sum > eps) {
-            rc = LP_INFEASIBLE;
-            ctx->last_error = std::string(who) + ": the problem has no feasible solution (phase I optimum > eps)";
-        }
-    }
-    if (rc == LP_OPTIMAL) {   // the drive-out of lp_simplex_two_phase_ex: no bound enters it
-        std::vector<int> positions;
-        for (int pos = 0; pos < m; ++pos)
-            if (N[(size_t)pos] >= n) positions.push_back(pos);
-        if (!positions.empty()) {
-            rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, &it[1]);
-            if (rc == LP_SINGULAR)
-                ctx->last_error = std::string(who) + ": an artificial variable cannot leave the basis (linearly dependent constraints)";
-        }
-    }
+    if (rc == LP_OPTIMAL) rc = phase1_verdict(ctx, who, xa.data(), m, n, eps);
+    if (rc == LP_OPTIMAL) rc = drive_out_artificials(p, who, N.data(), m, n, eps, &it[1]);
     if (rc >= 0) {
         const int rf = download_flags();
         if (rf) rc = rf;
@@ -894,16 +894,13 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
         if (rc >= 0) {
             it[2] = iters - (flips - flips1);
             it[3] = flips;
-            int rd;
-            if (rc == LP_OPTIMAL)
-                rd = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
-            else
-                rd = lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+            int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
+                                      : download_basis(p, N.data());
             if (rd == LP_OPTIMAL) rd = download_flags();
             if (rd) rc = rd;
         }
-    } else if (rc > 0) {   // the basis reached, as the one-LP-per-workgroup kernel reports it
-        const int rd = lp_simplex_download(p, nullptr, N.data(), nullptr, nullptr, nullptr, 0, nullptr);
+    } else if (rc > 0) {
+        const int rd = download_basis(p, N.data());
         if (rd) rc = rd;
     }
     (void)hipStreamSynchronize(s);
