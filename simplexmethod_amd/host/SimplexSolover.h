@@ -49,18 +49,13 @@ public:
     lpla::VectorXd solve() { return solve_ex().x; }
 
     Result solve_ex(bool throw_on_failure = true) {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();      // :409-414
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
+        const View p = view();                                           // :409-414
         const std::vector<int>& basis = _problem.GetBasisIndices();
-        const int n_orig = _problem.GetOriginalVariablesCount();
-        const int m = (int)A.rows(), n = (int)A.cols();
         lp_context* ctx = lpgpu::context(_device);
         Result r;
-        r.x = lpla::VectorXd::Zero(n_orig);
-        r.basis.assign((size_t)m, -1);
-        r.status = lp_simplex_solve_ex(ctx, A.data(), m, n, b.data(), c.data(), basis.data(),
-                                       _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
+        r.x = lpla::VectorXd::Zero(p.no);
+        r.basis.assign((size_t)p.m, -1);
+        r.status = lp_simplex_solve_ex(ctx, p.A, p.m, p.n, p.b, p.c, basis.data(), p.maximize, p.no, EPS, MAX_ITER,
                                        r.x.data(), r.basis.data(), &r.objective, &r.iterations,
                                        static_cast<int>(_rule));
         if (throw_on_failure) lpgpu::throw_for_status(r.status, ctx);
@@ -76,20 +71,14 @@ public:
     lpla::VectorXd twoPhaseSimplex() { return twoPhaseSimplex_ex().x; }
 
     Result twoPhaseSimplex_ex(bool throw_on_failure = true, int phase_iterations[3] = nullptr) {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int n_orig = _problem.GetOriginalVariablesCount();
-        const int m = (int)A.rows(), n = (int)A.cols();
+        const View p = view();
         lp_context* ctx = lpgpu::context(_device);
         Result r;
-        r.x = lpla::VectorXd::Zero(n_orig);
-        r.basis.assign((size_t)m, -1);
+        r.x = lpla::VectorXd::Zero(p.no);
+        r.basis.assign((size_t)p.m, -1);
         int it[3] = {0, 0, 0};
-        r.status = lp_simplex_two_phase_ex(ctx, A.data(), m, n, b.data(), c.data(),
-                                           _problem.IsMaximization() ? 1 : 0, n_orig, EPS, MAX_ITER,
-                                           r.x.data(), r.basis.data(), &r.objective, it,
-                                           static_cast<int>(_rule));
+        r.status = lp_simplex_two_phase_ex(ctx, p.A, p.m, p.n, p.b, p.c, p.maximize, p.no, EPS, MAX_ITER, r.x.data(),
+                                           r.basis.data(), &r.objective, it, static_cast<int>(_rule));
         r.iterations = it[0] + it[1] + it[2];
         if (phase_iterations)
             for (int k = 0; k < 3; ++k) phase_iterations[k] = it[k];
@@ -109,26 +98,21 @@ public:
     };
 
     Duals duals(const Result& r) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        const double nan = std::numeric_limits<double>::quiet_NaN();
+        const View p = view();
         Duals out;
-        out.y = lpla::VectorXd::Zero(m);
-        out.d = lpla::VectorXd::Zero(n);
+        out.y = lpla::VectorXd::Zero(p.m);
+        out.d = lpla::VectorXd::Zero(p.n);
         out.status = r.status;
         if (r.status == LP_OPTIMAL) {
-            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::duals: basis size != rows(A)");
+            if ((int)r.basis.size() != p.m) throw std::invalid_argument("Solver::duals: basis size != rows(A)");
             lp_context* ctx = lpgpu::context(_device);
-            out.status = lp_basis_duals(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(), out.y.data(),
-                                        out.d.data(), &out.objective);
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+            out.status = checked(lp_basis_duals(ctx, p.A, p.m, p.n, p.b, p.c, r.basis.data(), out.y.data(),
+                                                out.d.data(), &out.objective), ctx);
         }
         if (out.status != LP_OPTIMAL) {
-            for (int i = 0; i < m; ++i) out.y[i] = nan;
-            for (int j = 0; j < n; ++j) out.d[j] = nan;
-            out.objective = nan;
+            out.y = nans(p.m);
+            out.d = nans(p.n);
+            out.objective = kNaN;
         }
         return out;
     }
@@ -146,49 +130,18 @@ public:
     };
 
     Ranging ranging(const Result& r) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        std::vector<double> rhs(2 * (size_t)m, std::numeric_limits<double>::quiet_NaN()),
-            cost(2 * (size_t)n, std::numeric_limits<double>::quiet_NaN());
-        std::vector<int> rv(2 * (size_t)m, -1), cv(2 * (size_t)n, -1);
+        const View p = view();
+        RangingEnds ends(p.m, p.n);
         Ranging out;
         out.status = r.status;
         if (r.status == LP_OPTIMAL) {
-            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::ranging: basis size != rows(A)");
+            if ((int)r.basis.size() != p.m) throw std::invalid_argument("Solver::ranging: basis size != rows(A)");
             lp_context* ctx = lpgpu::context(_device);
-            out.status = lp_basis_ranging(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
-                                          _problem.IsMaximization() ? 1 : 0, EPS, rhs.data(), rv.data(), cost.data(),
-                                          cv.data());
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+            out.status = checked(lp_basis_ranging(ctx, p.A, p.m, p.n, p.b, p.c, r.basis.data(), p.maximize, EPS,
+                                                  ends.rhs.data(), ends.rv.data(), ends.cost.data(), ends.cv.data()),
+                                 ctx);
         }
-        out.b_lo = lpla::VectorXd::Zero(m);
-        out.b_hi = lpla::VectorXd::Zero(m);
-        out.c_lo = lpla::VectorXd::Zero(n);
-        out.c_hi = lpla::VectorXd::Zero(n);
-        out.b_leave_lo.assign((size_t)m, -1);
-        out.b_leave_hi.assign((size_t)m, -1);
-        out.c_enter_lo.assign((size_t)n, -1);
-        out.c_enter_hi.assign((size_t)n, -1);
-        const bool ok = out.status == LP_OPTIMAL;
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int i = 0; i < m; ++i) {
-            out.b_lo[i] = ok ? rhs[2 * (size_t)i] : nan;
-            out.b_hi[i] = ok ? rhs[2 * (size_t)i + 1] : nan;
-            if (ok) {
-                out.b_leave_lo[(size_t)i] = rv[2 * (size_t)i];
-                out.b_leave_hi[(size_t)i] = rv[2 * (size_t)i + 1];
-            }
-        }
-        for (int j = 0; j < n; ++j) {
-            out.c_lo[j] = ok ? cost[2 * (size_t)j] : nan;
-            out.c_hi[j] = ok ? cost[2 * (size_t)j + 1] : nan;
-            if (ok) {
-                out.c_enter_lo[(size_t)j] = cv[2 * (size_t)j];
-                out.c_enter_hi[(size_t)j] = cv[2 * (size_t)j + 1];
-            }
-        }
+        ends.unpack(out);
         return out;
     }
 
@@ -205,38 +158,7 @@ public:
     };
 
     Parametric parametricRhs(const Result& r, const lpla::VectorXd& d, double tMax) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        Parametric out;
-        out.status = r.status;
-        out.basis = r.basis;
-        int nseg = 0;
-        std::vector<double> t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1);
-        std::vector<int> enter(MAX_BREAKS + 1), leave(MAX_BREAKS + 1);
-        if (r.status == LP_OPTIMAL) {
-            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::parametricRhs: basis size != rows(A)");
-            if ((int)d.size() != m) throw std::invalid_argument("Solver::parametricRhs: d size != rows(A)");
-            lp_context* ctx = lpgpu::context(_device);
-            out.basis.assign((size_t)m, -1);
-            out.status = lp_basis_parametric(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
-                                             _problem.IsMaximization() ? 1 : 0, d.data(), tMax, EPS, MAX_BREAKS,
-                                             &nseg, t.data(), obj.data(), slope.data(), enter.data(), leave.data(),
-                                             out.basis.data());
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
-        }
-        out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.slope = lpla::VectorXd::Zero(nseg);
-        for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
-            out.t[k] = t[(size_t)k];
-            out.obj[k] = obj[(size_t)k];
-        }
-        for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
-        out.enter.assign(enter.begin(), enter.begin() + nseg);
-        out.leave.assign(leave.begin(), leave.begin() + nseg);
-        return out;
+        return parametric(false, r, d, tMax);
     }
 
     // The optimal value along c + t g for t in [0, tMax] (lp_basis_parametric_cost) from a result's final basis, with
@@ -246,38 +168,7 @@ public:
     // than MAX_BREAKS breakpoints), LP_SINGULAR; a result that is not LP_OPTIMAL keeps its status and gets no
     // segments.
     Parametric parametricCost(const Result& r, const lpla::VectorXd& g, double tMax) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        Parametric out;
-        out.status = r.status;
-        out.basis = r.basis;
-        int nseg = 0;
-        std::vector<double> t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1);
-        std::vector<int> enter(MAX_BREAKS + 1), leave(MAX_BREAKS + 1);
-        if (r.status == LP_OPTIMAL) {
-            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::parametricCost: basis size != rows(A)");
-            if ((int)g.size() != n) throw std::invalid_argument("Solver::parametricCost: g size != cols(A)");
-            lp_context* ctx = lpgpu::context(_device);
-            out.basis.assign((size_t)m, -1);
-            out.status = lp_basis_parametric_cost(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
-                                                  _problem.IsMaximization() ? 1 : 0, g.data(), tMax, EPS, MAX_BREAKS,
-                                                  &nseg, t.data(), obj.data(), slope.data(), enter.data(),
-                                                  leave.data(), out.basis.data());
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
-        }
-        out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.slope = lpla::VectorXd::Zero(nseg);
-        for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
-            out.t[k] = t[(size_t)k];
-            out.obj[k] = obj[(size_t)k];
-        }
-        for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
-        out.enter.assign(enter.begin(), enter.begin() + nseg);
-        out.leave.assign(leave.begin(), leave.begin() + nseg);
-        return out;
+        return parametric(true, r, g, tMax);
     }
 
     // Depth-first branch-and-bound (lp_mip_solve) with EPS and the problem's sense: the columns j with integer[j]
@@ -307,25 +198,17 @@ public:
 
     IntegerResult branchAndBound(const std::vector<bool>& integer, const Result& r, int maxDepth = 32,
                                  int maxNodes = 100000) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
-        IntegerResult out;
-        out.status = r.status;
-        out.x = lpla::VectorXd::Zero(no);
-        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        const View p = view();
+        IntegerResult out = blankIntegerResult(r.status, p.no);
         if (r.status != LP_OPTIMAL) return out;
-        if ((int)integer.size() != n) throw std::invalid_argument("Solver::branchAndBound: mask size != cols(A)");
-        if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::branchAndBound: basis size != rows(A)");
-        std::vector<int> mask((size_t)n);
-        for (int j = 0; j < n; ++j) mask[(size_t)j] = integer[(size_t)j] ? 1 : 0;
+        if ((int)integer.size() != p.n) throw std::invalid_argument("Solver::branchAndBound: mask size != cols(A)");
+        if ((int)r.basis.size() != p.m) throw std::invalid_argument("Solver::branchAndBound: basis size != rows(A)");
+        const std::vector<int> mask(integer.begin(), integer.end());
         lp_context* ctx = lpgpu::context(_device);
         int found = 0, stats[4] = {0, 0, 0, 0};
-        out.status = lp_mip_solve(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
-                                  _problem.IsMaximization() ? 1 : 0, no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth,
-                                  maxNodes, MAX_ITER, out.x.data(), &out.objective, &out.bound, &found, stats);
-        if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        out.status = checked(lp_mip_solve(ctx, p.A, p.m, p.n, p.b, p.c, r.basis.data(), p.maximize, p.no, mask.data(),
+                                          EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER, out.x.data(),
+                                          &out.objective, &out.bound, &found, stats), ctx);
         out.found = found != 0;
         out.nodes = stats[0];
         return out;
@@ -401,31 +284,24 @@ public:
 
     BoundedDuals boundedDuals(const std::vector<double>& lo, const std::vector<double>& hi,
                               const BoundedResult& from) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedDuals: lo / hi size != cols(A)");
-        const double nan = std::numeric_limits<double>::quiet_NaN();
+        const View p = view();
+        requireBounds("Solver::boundedDuals", p, lo, hi);
         BoundedDuals out;
-        out.x = lpla::VectorXd::Zero(n);
-        out.y = lpla::VectorXd::Zero(m);
-        out.d = lpla::VectorXd::Zero(n);
+        out.x = lpla::VectorXd::Zero(p.n);
+        out.y = lpla::VectorXd::Zero(p.m);
+        out.d = lpla::VectorXd::Zero(p.n);
         out.status = from.status;
         if (from.status == LP_OPTIMAL) {
-            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-                throw std::invalid_argument("Solver::boundedDuals: the result's basis / atUpper size != rows(A) / cols(A)");
+            requireStart("Solver::boundedDuals", "result", p, from);
             lp_context* ctx = lpgpu::context(_device);
-            out.status = lp_basis_bounded_duals(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                from.basis.data(), from.atUpper.data(), out.x.data(), out.y.data(),
-                                                out.d.data(), &out.objective);
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+            out.status = checked(lp_basis_bounded_duals(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                        from.basis.data(), from.atUpper.data(), out.x.data(),
+                                                        out.y.data(), out.d.data(), &out.objective), ctx);
         }
         if (out.status != LP_OPTIMAL) {
-            for (int j = 0; j < n; ++j) out.x[j] = out.d[j] = nan;
-            for (int i = 0; i < m; ++i) out.y[i] = nan;
-            out.objective = nan;
+            out.x = out.d = nans(p.n);
+            out.y = nans(p.m);
+            out.objective = kNaN;
         }
         return out;
     }
@@ -440,56 +316,22 @@ public:
 
     BoundedRanging boundedRanging(const std::vector<double>& lo, const std::vector<double>& hi,
                                   const BoundedResult& from) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedRanging: lo / hi size != cols(A)");
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        std::vector<double> rhs(2 * (size_t)m, nan), cost(2 * (size_t)n, nan);
-        std::vector<int> rv(2 * (size_t)m, -1), rs(2 * (size_t)m, -1), cv(2 * (size_t)n, -1);
+        const View p = view();
+        requireBounds("Solver::boundedRanging", p, lo, hi);
+        RangingEnds ends(p.m, p.n);
+        std::vector<int> rs(2 * (size_t)p.m, -1);
         BoundedRanging out;
         out.status = from.status;
         if (from.status == LP_OPTIMAL) {
-            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-                throw std::invalid_argument("Solver::boundedRanging: the result's basis / atUpper size != rows(A) / cols(A)");
+            requireStart("Solver::boundedRanging", "result", p, from);
             lp_context* ctx = lpgpu::context(_device);
-            out.status = lp_basis_bounded_ranging(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                  from.basis.data(), from.atUpper.data(),
-                                                  _problem.IsMaximization() ? 1 : 0, EPS, rhs.data(), rv.data(),
-                                                  rs.data(), cost.data(), cv.data());
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+            out.status = checked(lp_basis_bounded_ranging(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                          from.basis.data(), from.atUpper.data(), p.maximize, EPS,
+                                                          ends.rhs.data(), ends.rv.data(), rs.data(), ends.cost.data(),
+                                                          ends.cv.data()), ctx);
         }
-        const bool ok = out.status == LP_OPTIMAL;
-        out.b_lo = lpla::VectorXd::Zero(m);
-        out.b_hi = lpla::VectorXd::Zero(m);
-        out.c_lo = lpla::VectorXd::Zero(n);
-        out.c_hi = lpla::VectorXd::Zero(n);
-        out.b_leave_lo.assign((size_t)m, -1);
-        out.b_leave_hi.assign((size_t)m, -1);
-        out.b_side_lo.assign((size_t)m, -1);
-        out.b_side_hi.assign((size_t)m, -1);
-        out.c_enter_lo.assign((size_t)n, -1);
-        out.c_enter_hi.assign((size_t)n, -1);
-        for (int i = 0; i < m; ++i) {
-            out.b_lo[i] = ok ? rhs[2 * (size_t)i] : nan;
-            out.b_hi[i] = ok ? rhs[2 * (size_t)i + 1] : nan;
-            if (ok) {
-                out.b_leave_lo[(size_t)i] = rv[2 * (size_t)i];
-                out.b_leave_hi[(size_t)i] = rv[2 * (size_t)i + 1];
-                out.b_side_lo[(size_t)i] = rs[2 * (size_t)i];
-                out.b_side_hi[(size_t)i] = rs[2 * (size_t)i + 1];
-            }
-        }
-        for (int j = 0; j < n; ++j) {
-            out.c_lo[j] = ok ? cost[2 * (size_t)j] : nan;
-            out.c_hi[j] = ok ? cost[2 * (size_t)j + 1] : nan;
-            if (ok) {
-                out.c_enter_lo[(size_t)j] = cv[2 * (size_t)j];
-                out.c_enter_hi[(size_t)j] = cv[2 * (size_t)j + 1];
-            }
-        }
+        ends.unpack(out);
+        unpackPairs(out.status == LP_OPTIMAL, rs, -1, out.b_side_lo, out.b_side_hi);
         return out;
     }
 
@@ -509,30 +351,20 @@ public:
     IntegerResult boundedBranchAndBound(const std::vector<bool>& integer, const std::vector<double>& lo,
                                         const std::vector<double>& hi, const BoundedResult& from, int maxDepth = 64,
                                         int maxNodes = 100000) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
-        IntegerResult out;
-        out.status = from.status;
-        out.x = lpla::VectorXd::Zero(no);
-        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
+        const View p = view();
+        IntegerResult out = blankIntegerResult(from.status, p.no);
         if (from.status != LP_OPTIMAL) return out;
-        if ((int)integer.size() != n) throw std::invalid_argument("Solver::boundedBranchAndBound: mask size != cols(A)");
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedBranchAndBound: lo / hi size != cols(A)");
-        if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-            throw std::invalid_argument(
-                "Solver::boundedBranchAndBound: the start's basis / atUpper size != rows(A) / cols(A)");
-        std::vector<int> mask((size_t)n);
-        for (int j = 0; j < n; ++j) mask[(size_t)j] = integer[(size_t)j] ? 1 : 0;
+        if ((int)integer.size() != p.n)
+            throw std::invalid_argument("Solver::boundedBranchAndBound: mask size != cols(A)");
+        requireBounds("Solver::boundedBranchAndBound", p, lo, hi);
+        requireStart("Solver::boundedBranchAndBound", "start", p, from);
+        const std::vector<int> mask(integer.begin(), integer.end());
         lp_context* ctx = lpgpu::context(_device);
         int found = 0, stats[5] = {0, 0, 0, 0, 0};
-        out.status = lp_mip_bounded_solve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                          from.basis.data(), from.atUpper.data(), _problem.IsMaximization() ? 1 : 0,
-                                          no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER,
-                                          out.x.data(), &out.objective, &out.bound, &found, stats);
-        if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        out.status = checked(lp_mip_bounded_solve(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                  from.basis.data(), from.atUpper.data(), p.maximize, p.no,
+                                                  mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER,
+                                                  out.x.data(), &out.objective, &out.bound, &found, stats), ctx);
         out.found = found != 0;
         out.nodes = stats[0];
         return out;
@@ -554,25 +386,14 @@ public:
     };
 
     Certificate certificate(const Result& r) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        Certificate out;
-        out.farkas = lpla::VectorXd::Zero(m);
-        out.ray = lpla::VectorXd::Zero(n);
-        for (int i = 0; i < m; ++i) out.farkas[i] = nan;
-        for (int j = 0; j < n; ++j) out.ray[j] = nan;
-        out.status = r.status;
-        if (r.status == LP_INFEASIBLE || r.status == LP_UNBOUNDED) {
-            if ((int)r.basis.size() != m) throw std::invalid_argument("Solver::certificate: basis size != rows(A)");
+        const View p = view();
+        Certificate out = blankCertificate(p, r.status);
+        if (hasCertificate(r.status)) {
+            if ((int)r.basis.size() != p.m) throw std::invalid_argument("Solver::certificate: basis size != rows(A)");
             lp_context* ctx = lpgpu::context(_device);
-            const int st = lp_basis_certificate(ctx, A.data(), m, n, b.data(), c.data(), r.basis.data(),
-                                                _problem.IsMaximization() ? 1 : 0, EPS, &out.kind, out.farkas.data(),
-                                                out.ray.data(), &out.value, &out.index);
-            if (st < 0 || st == LP_BAD_ARG) lpgpu::throw_for_status(st, ctx);
-            if (st != LP_OPTIMAL) out.status = st;
+            mergeStatus(out, lp_basis_certificate(ctx, p.A, p.m, p.n, p.b, p.c, r.basis.data(), p.maximize, EPS,
+                                                  &out.kind, out.farkas.data(), out.ray.data(), &out.value,
+                                                  &out.index), ctx);
         }
         return out;
     }
@@ -588,30 +409,16 @@ public:
     // its status and gets NONE.  Exceptions as boundedDuals.
     Certificate boundedCertificate(const std::vector<double>& lo, const std::vector<double>& hi,
                                    const BoundedResult& from, double eps = EPS) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedCertificate: lo / hi size != cols(A)");
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        Certificate out;
-        out.farkas = lpla::VectorXd::Zero(m);
-        out.ray = lpla::VectorXd::Zero(n);
-        for (int i = 0; i < m; ++i) out.farkas[i] = nan;
-        for (int j = 0; j < n; ++j) out.ray[j] = nan;
-        out.status = from.status;
-        if (from.status == LP_INFEASIBLE || from.status == LP_UNBOUNDED) {
-            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-                throw std::invalid_argument(
-                    "Solver::boundedCertificate: the result's basis / atUpper size != rows(A) / cols(A)");
+        const View p = view();
+        requireBounds("Solver::boundedCertificate", p, lo, hi);
+        Certificate out = blankCertificate(p, from.status);
+        if (hasCertificate(from.status)) {
+            requireStart("Solver::boundedCertificate", "result", p, from);
             lp_context* ctx = lpgpu::context(_device);
-            const int st = lp_basis_bounded_certificate(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                        from.basis.data(), from.atUpper.data(),
-                                                        _problem.IsMaximization() ? 1 : 0, eps, &out.kind,
-                                                        out.farkas.data(), out.ray.data(), &out.value, &out.index);
-            if (st < 0 || st == LP_BAD_ARG) lpgpu::throw_for_status(st, ctx);
-            if (st != LP_OPTIMAL) out.status = st;
+            mergeStatus(out, lp_basis_bounded_certificate(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                          from.basis.data(), from.atUpper.data(), p.maximize, eps,
+                                                          &out.kind, out.farkas.data(), out.ray.data(), &out.value,
+                                                          &out.index), ctx);
         }
         return out;
     }
@@ -641,48 +448,161 @@ public:
     }
 
 private:
+    // The problem as the ABI takes it
+    struct View {
+        const double *A, *b, *c;
+        int m, n, no, maximize;
+    };
+    View view() const {
+        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
+        return {A.data(), _problem.GetRightHandSide().data(), _problem.GetObjectiveCoefficients().data(),
+                (int)A.rows(), (int)A.cols(), _problem.GetOriginalVariablesCount(), _problem.IsMaximization() ? 1 : 0};
+    }
+
+    static constexpr double kNaN = std::numeric_limits<double>::quiet_NaN();
+
+    // A status the analyses and searches hand back as it is; a runtime failure or a refused argument throws
+    static int checked(int st, lp_context* ctx) {
+        if (st < 0 || st == LP_BAD_ARG) lpgpu::throw_for_status(st, ctx);
+        return st;
+    }
+
+    static lpla::VectorXd nans(int size) {
+        lpla::VectorXd v = lpla::VectorXd::Zero(size);
+        for (int i = 0; i < size; ++i) v[i] = kNaN;
+        return v;
+    }
+
+    static void requireBounds(const char* who, const View& p, const std::vector<double>& lo,
+                              const std::vector<double>& hi) {
+        if ((int)lo.size() != p.n || (int)hi.size() != p.n)
+            throw std::invalid_argument(std::string(who) + ": lo / hi size != cols(A)");
+    }
+
+    // whose: "start" (a solve or search goes on from it) or "result" (it is analysed)
+    static void requireStart(const char* who, const char* whose, const View& p, const BoundedResult& from) {
+        if ((int)from.basis.size() != p.m || (int)from.atUpper.size() != p.n)
+            throw std::invalid_argument(std::string(who) + ": the " + whose +
+                                        "'s basis / atUpper size != rows(A) / cols(A)");
+    }
+
+    // The (lo, hi) pairs an ABI ranging call wrote, one per row or column, as two vectors; `fill` in both unless ok
+    template <class Vec, class T>
+    static void unpackPairs(bool ok, const std::vector<T>& pairs, T fill, Vec& lo, Vec& hi) {
+        const size_t count = pairs.size() / 2;
+        lo = hi = Vec((long)count);
+        for (size_t i = 0; i < count; ++i) {
+            lo[(long)i] = ok ? pairs[2 * i] : fill;
+            hi[(long)i] = ok ? pairs[2 * i + 1] : fill;
+        }
+    }
+
+    // What lp_basis_ranging and lp_basis_bounded_ranging fill, and the Ranging it becomes under out.status
+    struct RangingEnds {
+        std::vector<double> rhs, cost;
+        std::vector<int> rv, cv;
+        RangingEnds(int m, int n)
+            : rhs(2 * (size_t)m, kNaN), cost(2 * (size_t)n, kNaN), rv(2 * (size_t)m, -1), cv(2 * (size_t)n, -1) {}
+        void unpack(Ranging& out) const {
+            const bool ok = out.status == LP_OPTIMAL;
+            unpackPairs(ok, rhs, kNaN, out.b_lo, out.b_hi);
+            unpackPairs(ok, rv, -1, out.b_leave_lo, out.b_leave_hi);
+            unpackPairs(ok, cost, kNaN, out.c_lo, out.c_hi);
+            unpackPairs(ok, cv, -1, out.c_enter_lo, out.c_enter_hi);
+        }
+    };
+
+    // What the four parametric ABI calls fill at MAX_BREAKS, and the Parametric its first nseg segments become
+    struct PathBuffers {
+        int nseg = 0;
+        std::vector<double> t, obj, slope;
+        std::vector<int> enter, leave;
+        PathBuffers()
+            : t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1), enter(MAX_BREAKS + 1),
+              leave(MAX_BREAKS + 1) {}
+        void unpack(Parametric& out) const {
+            out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+            out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
+            out.slope = lpla::VectorXd::Zero(nseg);
+            for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
+                out.t[k] = t[(size_t)k];
+                out.obj[k] = obj[(size_t)k];
+            }
+            for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
+            out.enter.assign(enter.begin(), enter.begin() + nseg);
+            out.leave.assign(leave.begin(), leave.begin() + nseg);
+        }
+    };
+
+    static IntegerResult blankIntegerResult(int status, int no) {
+        IntegerResult out;
+        out.status = status;
+        out.x = nans(no);
+        return out;
+    }
+
+    // The certificate methods: NaN vectors and the result's status, which stands unless the call reports a failure
+    static Certificate blankCertificate(const View& p, int status) {
+        Certificate out;
+        out.farkas = nans(p.m);
+        out.ray = nans(p.n);
+        out.status = status;
+        return out;
+    }
+    static bool hasCertificate(int status) { return status == LP_INFEASIBLE || status == LP_UNBOUNDED; }
+    static void mergeStatus(Certificate& out, int st, lp_context* ctx) {
+        if (checked(st, ctx) != LP_OPTIMAL) out.status = st;
+    }
+
+    // parametricRhs (dir = d, rows(A) entries) or parametricCost (dir = g, cols(A) entries)
+    Parametric parametric(bool cost, const Result& r, const lpla::VectorXd& dir, double tMax) const {
+        const View p = view();
+        const std::string who = cost ? "Solver::parametricCost" : "Solver::parametricRhs";
+        Parametric out;
+        out.status = r.status;
+        out.basis = r.basis;
+        PathBuffers path;
+        if (r.status == LP_OPTIMAL) {
+            if ((int)r.basis.size() != p.m) throw std::invalid_argument(who + ": basis size != rows(A)");
+            if ((int)dir.size() != (cost ? p.n : p.m))
+                throw std::invalid_argument(who + (cost ? ": g size != cols(A)" : ": d size != rows(A)"));
+            lp_context* ctx = lpgpu::context(_device);
+            out.basis.assign((size_t)p.m, -1);
+            out.status = checked((cost ? lp_basis_parametric_cost : lp_basis_parametric)(
+                                     ctx, p.A, p.m, p.n, p.b, p.c, r.basis.data(), p.maximize, dir.data(), tMax, EPS,
+                                     MAX_BREAKS, &path.nseg, path.t.data(), path.obj.data(), path.slope.data(),
+                                     path.enter.data(), path.leave.data(), out.basis.data()), ctx);
+        }
+        path.unpack(out);
+        return out;
+    }
+
     BoundedParametric boundedParametric(bool cost, const std::vector<double>& lo, const std::vector<double>& hi,
                                         const BoundedResult& from, const lpla::VectorXd& dir, double tMax) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument("Solver::boundedParametric: lo / hi size != cols(A)");
+        const View p = view();
+        requireBounds("Solver::boundedParametric", p, lo, hi);
         BoundedParametric out;
         out.status = from.status;
         out.basis = from.basis;
         out.atUpper = from.atUpper;
-        int nseg = 0;
-        std::vector<double> t(MAX_BREAKS + 2), obj(MAX_BREAKS + 2), slope(MAX_BREAKS + 1);
-        std::vector<int> enter(MAX_BREAKS + 1), leave(MAX_BREAKS + 1), side(MAX_BREAKS + 1);
+        PathBuffers path;
+        std::vector<int> side(MAX_BREAKS + 1);
         if (from.status == LP_OPTIMAL) {
-            if ((int)from.basis.size() != m || (int)from.atUpper.size() != n)
-                throw std::invalid_argument(
-                    "Solver::boundedParametric: the result's basis / atUpper size != rows(A) / cols(A)");
-            if ((int)dir.size() != (cost ? n : m))
+            requireStart("Solver::boundedParametric", "result", p, from);
+            if ((int)dir.size() != (cost ? p.n : p.m))
                 throw std::invalid_argument(cost ? "Solver::boundedParametricCost: g size != cols(A)"
                                                  : "Solver::boundedParametricRhs: d size != rows(A)");
             lp_context* ctx = lpgpu::context(_device);
-            out.basis.assign((size_t)m, -1);
-            out.atUpper.assign((size_t)n, 0);
-            out.status = (cost ? lp_basis_bounded_parametric_cost : lp_basis_bounded_parametric)(
-                ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), from.basis.data(), from.atUpper.data(),
-                _problem.IsMaximization() ? 1 : 0, dir.data(), tMax, EPS, MAX_BREAKS, &nseg, t.data(), obj.data(),
-                slope.data(), enter.data(), leave.data(), side.data(), out.basis.data(), out.atUpper.data());
-            if (out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+            out.basis.assign((size_t)p.m, -1);
+            out.atUpper.assign((size_t)p.n, 0);
+            out.status = checked((cost ? lp_basis_bounded_parametric_cost : lp_basis_bounded_parametric)(
+                                     ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                     from.atUpper.data(), p.maximize, dir.data(), tMax, EPS, MAX_BREAKS, &path.nseg,
+                                     path.t.data(), path.obj.data(), path.slope.data(), path.enter.data(),
+                                     path.leave.data(), side.data(), out.basis.data(), out.atUpper.data()), ctx);
         }
-        out.t = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.obj = lpla::VectorXd::Zero(nseg ? nseg + 1 : 0);
-        out.slope = lpla::VectorXd::Zero(nseg);
-        for (int k = 0; k < nseg + (nseg ? 1 : 0); ++k) {
-            out.t[k] = t[(size_t)k];
-            out.obj[k] = obj[(size_t)k];
-        }
-        for (int k = 0; k < nseg; ++k) out.slope[k] = slope[(size_t)k];
-        out.enter.assign(enter.begin(), enter.begin() + nseg);
-        out.leave.assign(leave.begin(), leave.begin() + nseg);
-        out.side.assign(side.begin(), side.begin() + nseg);
+        path.unpack(out);
+        out.side.assign(side.begin(), side.begin() + path.nseg);
         return out;
     }
 
@@ -691,44 +611,38 @@ private:
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
                              const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
                              bool large = false) const {
-        const lpla::MatrixXd& A = _problem.GetConstraintsMatrix();
-        const lpla::VectorXd& b = _problem.GetRightHandSide();
-        const lpla::VectorXd& c = _problem.GetObjectiveCoefficients();
-        const int m = (int)A.rows(), n = (int)A.cols(), no = _problem.GetOriginalVariablesCount();
-        if ((int)lo.size() != n || (int)hi.size() != n)
-            throw std::invalid_argument(std::string(who) + ": lo / hi size != cols(A)");
-        if (from && ((int)from->basis.size() != m || (int)from->atUpper.size() != n))
-            throw std::invalid_argument(std::string(who) + ": the start's basis / atUpper size != rows(A) / cols(A)");
+        const View p = view();
+        requireBounds(who, p, lo, hi);
+        if (from) requireStart(who, "start", p, *from);
         BoundedResult out;
-        out.x = lpla::VectorXd::Zero(no);
-        for (int j = 0; j < no; ++j) out.x[j] = std::numeric_limits<double>::quiet_NaN();
-        out.basis.assign((size_t)m, -1);
-        out.atUpper.assign((size_t)n, 0);
+        out.x = nans(p.no);
+        out.basis.assign((size_t)p.m, -1);
+        out.atUpper.assign((size_t)p.n, 0);
         lp_context* ctx = lpgpu::context(_device);
-        const int mx = _problem.IsMaximization() ? 1 : 0;
         if (large)
-            out.status = lp_simplex_bounded_large(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no,
+            out.status = lp_simplex_bounded_large(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), p.maximize, p.no,
                                                   EPS, MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                                   &out.objective, out.iterations);
         else if (!from && !rule)
-            out.status = lp_simplex_bounded(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no, EPS,
+            out.status = lp_simplex_bounded(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), p.maximize, p.no, EPS,
                                             MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                             &out.objective, out.iterations);
         else if (!from)
-            out.status = lp_simplex_bounded_ex(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(), mx, no, EPS,
-                                               MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
+            out.status = lp_simplex_bounded_ex(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), p.maximize, p.no,
+                                               EPS, MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                                &out.objective, out.iterations, (int)*rule);
         else if (!rule)
-            out.status = lp_simplex_bounded_resolve(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                    from->basis.data(), from->atUpper.data(), mx, no, EPS, MAX_ITER,
-                                                    out.x.data(), out.basis.data(), out.atUpper.data(), &out.objective,
-                                                    out.iterations);
+            out.status = lp_simplex_bounded_resolve(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                    from->basis.data(), from->atUpper.data(), p.maximize, p.no, EPS,
+                                                    MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
+                                                    &out.objective, out.iterations);
         else
-            out.status = lp_simplex_bounded_resolve_ex(ctx, A.data(), m, n, b.data(), c.data(), lo.data(), hi.data(),
-                                                       from->basis.data(), from->atUpper.data(), mx, no, EPS, MAX_ITER,
-                                                       out.x.data(), out.basis.data(), out.atUpper.data(),
+            out.status = lp_simplex_bounded_resolve_ex(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                       from->basis.data(), from->atUpper.data(), p.maximize, p.no, EPS,
+                                                       MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                                        &out.objective, out.iterations, (int)*rule);
-        if (throw_on_failure || out.status < 0 || out.status == LP_BAD_ARG) lpgpu::throw_for_status(out.status, ctx);
+        if (throw_on_failure) lpgpu::throw_for_status(out.status, ctx);
+        checked(out.status, ctx);
         return out;
     }
 

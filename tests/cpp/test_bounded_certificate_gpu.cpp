@@ -3,15 +3,12 @@
 // tests/ref/bounded_certificate_ref.c's bit for bit (the library named by LP_BOUNDED_CERTIFICATE_REF, loaded at run
 // time); a result that is optimal keeps its status with NONE, a repeated basis index is singular, crossed bounds are
 // infeasible without a vector, and a bad flag, index, eps or size throws std::invalid_argument.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
@@ -20,67 +17,25 @@ using lpla::VectorXd;
 
 static const double INF = std::numeric_limits<double>::infinity();
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
 enum Kind { FEASIBLE, INFEASIBLE, UNBOUNDED };
 
-// [A0 | I] x = b with A0 > 0, k structural columns boxed in several ways, costs of both signs.  INFEASIBLE: column 1
-// fixed far above what the rows allow.  UNBOUNDED: column 0 (in [0, inf)) negated with an improving cost and every
-// slack in [0, inf), so the ray moves column 0 and the basic variables with it.
-static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, Kind kind, MatrixXd* Aout, VectorXd* bout,
-                               VectorXd* cout, std::vector<double>* lo, std::vector<double>* hi) {
-    uint64_t s = seed * 7919 + 29;
-    const int n = k + m;
-    MatrixXd A = MatrixXd::Zero(m, n);
-    VectorXd b(m), c = VectorXd::Zero(n);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = 0.05 + u01(s);
-        A(i, k + i) = 1.0;
-        b[i] = 0.5 * k * (1.0 + u01(s));
-    }
-    lo->assign((size_t)n, 0.0);
-    hi->assign((size_t)n, INF);
-    for (int j = 0; j < k; ++j) {
-        c[j] = u01(s) - 0.3;
-        switch (j % 4) {
-            case 1: (*hi)[(size_t)j] = 0.2 + 2.0 * u01(s); break;
-            case 2: (*lo)[(size_t)j] = (*hi)[(size_t)j] = u01(s); break;
-            case 3: (*lo)[(size_t)j] = -u01(s); (*hi)[(size_t)j] = 1.0 + u01(s); break;
-            default: break;
-        }
-    }
+// fixtures.h's boxed problem with A0 >= 0.05, changed after it is drawn.  INFEASIBLE: column 1 fixed far above what the
+// rows allow.  UNBOUNDED: column 0 (in [0, inf)) negated with an improving cost and every slack in [0, inf), so the
+// ray moves column 0 and the basic variables with it.
+static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, Kind kind, MatrixXd* A, VectorXd* b,
+                               VectorXd* c, std::vector<double>* lo, std::vector<double>* hi) {
+    ::boxed_problem(seed, m, k, maximize, A, b, c, lo, hi, /*a_offset=*/0.05);
     if (kind == INFEASIBLE) (*lo)[1] = (*hi)[1] = 1000.0;
     if (kind == UNBOUNDED) {
-        for (int i = 0; i < m; ++i) A(i, 0) = -A(i, 0);
-        c[0] = maximize ? 1.0 : -1.0;
+        for (int i = 0; i < m; ++i) (*A)(i, 0) = -(*A)(i, 0);
+        (*c)[0] = maximize ? 1.0 : -1.0;
     }
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;
-    *Aout = A;
-    *bout = b;
-    *cout = c;
-    Canonical can(A, b, c, basis, /*minimize=*/!maximize);
-    can.SetOriginalVariablesCount(n);
-    return can;
+    return last_columns_basic(*A, *b, *c, maximize);
 }
 
 typedef int (*RefBoundedCertificate)(const double*, int, int, const double*, const double*, const double*,
                                      const double*, const int*, const int*, int, double, int*, double*, double*,
                                      double*, int*);
-
-static bool same_bits(double a, double b) {
-    if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && std::isnan(b);
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y;
-}
 
 // the mirror's certificate for `from` against the reference at the same basis and flags; returns the kind
 static int compare(RefBoundedCertificate ref, const Solver& s, const MatrixXd& A, const VectorXd& b, const VectorXd& c,
@@ -103,14 +58,8 @@ static int compare(RefBoundedCertificate ref, const Solver& s, const MatrixXd& A
 }
 
 TEST(BoundedCertificate_MatchesTheRef) {
-    const char* path = std::getenv("LP_BOUNDED_CERTIFICATE_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefBoundedCertificate ref = reinterpret_cast<RefBoundedCertificate>(dlsym(h, "ref_bounded_certificate"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_BOUNDED_CERTIFICATE_REF");
+    RefBoundedCertificate ref = lib.symbol<RefBoundedCertificate>("ref_bounded_certificate");
     int phase1 = 0, rays = 0, dual = 0;
     for (uint64_t seed = 0; ref && seed < 12; ++seed) {
         const int m = 3 + (int)(seed % 5), k = 5 + (int)(seed % 7);
@@ -149,7 +98,6 @@ TEST(BoundedCertificate_MatchesTheRef) {
         }
     }
     CHECK(phase1 == 12 && rays == 12 && dual >= 8);
-    dlclose(h);
 }
 
 TEST(BoundedCertificate_StatusesAndExceptions) {

@@ -1,6 +1,6 @@
 // GPU tests of Solver::boundedSimplexLarge: on a 160 x 320 boxed LP (beyond lp_simplex_bounded_fits) the result equals,
 // bit for bit, what tests/ref/bounded_ref.c recorded in tests/golden/bounded_large_case.json (the file named by
-// LP_BOUNDED_LARGE_GOLDEN; tests/golden/make_bounded_large_golden.py restates the generator below); an infeasible and
+// LP_BOUNDED_LARGE_GOLDEN; tests/golden/make_bounded_large_golden.py restates large_problem below); an infeasible and
 // an unbounded LP throw unless asked not to, and bad bounds throw std::invalid_argument.
 #include <cmath>
 #include <cstdint>
@@ -11,6 +11,7 @@
 #include <sstream>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
@@ -19,42 +20,10 @@ using lpla::VectorXd;
 
 static const double INF = std::numeric_limits<double>::infinity();
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// [A0 | I] x = b with A0 > 0, k structural columns boxed in several ways, costs of both signs
-static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, std::vector<double>* lo,
+// fixtures.h's boxed problem with b_i in 0.125 k [1, 2), as tests/golden/make_bounded_large_golden.py restates it
+static Canonical large_problem(uint64_t seed, int m, int k, bool maximize, std::vector<double>* lo,
                                std::vector<double>* hi) {
-    uint64_t s = seed * 7919 + 29;
-    const int n = k + m;
-    MatrixXd A = MatrixXd::Zero(m, n);
-    VectorXd b(m), c = VectorXd::Zero(n);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = 1.0;
-        b[i] = 0.125 * k * (1.0 + u01(s));
-    }
-    lo->assign((size_t)n, 0.0);
-    hi->assign((size_t)n, INF);
-    for (int j = 0; j < k; ++j) {
-        c[j] = u01(s) - 0.3;
-        switch (j % 4) {
-            case 1: (*hi)[(size_t)j] = 0.2 + 2.0 * u01(s); break;
-            case 2: (*lo)[(size_t)j] = (*hi)[(size_t)j] = u01(s); break;
-            case 3: (*lo)[(size_t)j] = -u01(s); (*hi)[(size_t)j] = 1.0 + u01(s); break;
-            default: break;
-        }
-    }
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;
-    Canonical can(A, b, c, basis, /*minimize=*/!maximize);
-    can.SetOriginalVariablesCount(n);
-    return can;
+    return boxed_problem(seed, m, k, maximize, nullptr, nullptr, nullptr, lo, hi, /*a_offset=*/0.0, /*b_scale=*/0.125);
 }
 
 // The value of "key" inside the JSON object text `s`: a number, or an array of numbers.
@@ -81,13 +50,6 @@ static std::vector<double> numbers(const std::string& s, const char* key) {
     return out;
 }
 
-static bool same_bits(double a, double b) {
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y || (a == 0.0 && b == 0.0);
-}
-
 TEST(BoundedSimplexLarge_MatchesTheGolden) {
     const char* path = std::getenv("LP_BOUNDED_LARGE_GOLDEN");
     CHECK(path != nullptr);
@@ -106,14 +68,15 @@ TEST(BoundedSimplexLarge_MatchesTheGolden) {
     if ((int)x.size() != n || (int)basis.size() != m || (int)up.size() != n || iters.size() != 4) return;
     CHECK(iters[0] > 0 && iters[2] > 0 && iters[3] > 0);
     std::vector<double> lo, hi;
-    Solver s(boxed_problem((uint64_t)seed, m, k, maximize, &lo, &hi));
+    Solver s(large_problem((uint64_t)seed, m, k, maximize, &lo, &hi));
     const Solver::BoundedResult r = s.boundedSimplexLarge(lo, hi);
     std::printf("  status %d, iterations %d + %d + %d, %d flips\n", r.status, r.iterations[0], r.iterations[1],
                 r.iterations[2], r.iterations[3]);
     CHECK(r.status == (int)numbers(g, "status")[0] && r.status == LP_OPTIMAL);
-    CHECK(same_bits(r.objective, numbers(g, "obj")[0]));
+    CHECK(same_bits_or_zeros(r.objective, numbers(g, "obj")[0]));
     CHECK((int)r.x.size() == n && (int)r.basis.size() == m && (int)r.atUpper.size() == n);
-    for (int j = 0; j < n; ++j) CHECK(same_bits(r.x[j], x[(size_t)j]) && r.atUpper[(size_t)j] == (int)up[(size_t)j]);
+    for (int j = 0; j < n; ++j)
+        CHECK(same_bits_or_zeros(r.x[j], x[(size_t)j]) && r.atUpper[(size_t)j] == (int)up[(size_t)j]);
     for (int t = 0; t < m; ++t) CHECK(r.basis[(size_t)t] == (int)basis[(size_t)t]);
     for (int q = 0; q < 4; ++q) CHECK(r.iterations[q] == (int)iters[(size_t)q]);
     // the LDS entry still refuses this shape
@@ -123,7 +86,7 @@ TEST(BoundedSimplexLarge_MatchesTheGolden) {
 TEST(BoundedSimplexLarge_ExceptionMapping) {
     const int m = 160, k = 160, n = m + k;
     std::vector<double> lo, hi;
-    Canonical p = boxed_problem(3, m, k, true, &lo, &hi);
+    Canonical p = large_problem(3, m, k, true, &lo, &hi);
     Solver s(p);
     // infeasible: hi < lo on one column (no iteration), and a column fixed far above what the rows allow (phase I)
     std::vector<double> crossed = hi;

@@ -4,15 +4,12 @@
 // lp_basis_bounded_parametric_cost_batched on a batch of three LPs with a run status; a result that is not optimal
 // keeps its status without segments, a repeated basis index is singular, crossed bounds are infeasible without
 // segments, and a bad flag, index, size or a start that is not optimal throws std::invalid_argument.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
@@ -22,16 +19,9 @@ using lpla::VectorXd;
 static const double INF = std::numeric_limits<double>::infinity();
 static const int MB = Solver::MAX_BREAKS;
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // [A0 | I] x = b with A0 > 0, k structural columns boxed in several ways (free above, boxed, fixed, a negative lower
-// bound), costs of both signs; d (m) and g (n) are seeded directions of mixed signs.
+// bound), costs of both signs; d (m) and g (n) are seeded directions of mixed signs.  Not fixtures.h's boxed_problem:
+// d is drawn row by row between the draws of A and b, so the stream differs from the first row on.
 static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, MatrixXd* Aout, VectorXd* bout,
                                VectorXd* cout, std::vector<double>* lo, std::vector<double>* hi, VectorXd* d,
                                VectorXd* g) {
@@ -73,14 +63,6 @@ typedef int (*RefBoundedParametric)(const double*, int, int, const double*, cons
                                     const int*, const int*, int, const double*, double, double, int, int*, double*,
                                     double*, double*, int*, int*, int*, int*, int*);
 
-static bool same_bits(double a, double b) {
-    if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && std::isnan(b);
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y;
-}
-
 // One reference path in the padded layout
 struct RefPath {
     int status = -1, nseg = -7;
@@ -118,23 +100,10 @@ static int compare(const Solver::BoundedParametric& g, const RefPath& w) {
     return upper;
 }
 
-static RefBoundedParametric load_ref(const char* name, void** handle) {
-    const char* path = std::getenv("LP_BOUNDED_PARAMETRIC_REF");
-    CHECK(path != nullptr);
-    if (!path) return nullptr;
-    *handle = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(*handle != nullptr);
-    if (!*handle) return nullptr;
-    RefBoundedParametric ref = reinterpret_cast<RefBoundedParametric>(dlsym(*handle, name));
-    CHECK(ref != nullptr);
-    return ref;
-}
-
 TEST(BoundedParametric_SolverMatchesTheRef) {
-    void *h1 = nullptr, *h2 = nullptr;
-    RefBoundedParametric rhs = load_ref("ref_bounded_parametric", &h1);
-    RefBoundedParametric cost = load_ref("ref_bounded_parametric_cost", &h2);
-    if (!rhs || !cost) return;
+    const RefLib lib("LP_BOUNDED_PARAMETRIC_REF");
+    RefBoundedParametric rhs = lib.symbol<RefBoundedParametric>("ref_bounded_parametric");
+    RefBoundedParametric cost = lib.symbol<RefBoundedParametric>("ref_bounded_parametric_cost");
     int paths = 0, breaks = 0, upper = 0;
     for (uint64_t seed = 0; seed < 12; ++seed) {
         const int m = seed % 2 ? 9 : 4, k = seed % 2 ? 14 : 7;   // two shapes
@@ -156,15 +125,12 @@ TEST(BoundedParametric_SolverMatchesTheRef) {
         }
     }
     CHECK(paths >= 40 && breaks >= 60 && upper >= 5);
-    dlclose(h1);
-    dlclose(h2);
 }
 
 TEST(BoundedParametric_CAbiBatchMatchesTheRef) {
-    void *h1 = nullptr, *h2 = nullptr;
-    RefBoundedParametric refs[2] = {load_ref("ref_bounded_parametric", &h1),
-                                    load_ref("ref_bounded_parametric_cost", &h2)};
-    if (!refs[0] || !refs[1]) return;
+    const RefLib lib("LP_BOUNDED_PARAMETRIC_REF");
+    RefBoundedParametric refs[2] = {lib.symbol<RefBoundedParametric>("ref_bounded_parametric"),
+                                    lib.symbol<RefBoundedParametric>("ref_bounded_parametric_cost")};
     lp_context* ctx = lpgpu::context(0);
     for (int shape = 0; shape < 2; ++shape) {
         const int m = shape ? 9 : 4, k = shape ? 14 : 7, n = k + m, B = 3;
@@ -230,8 +196,6 @@ TEST(BoundedParametric_CAbiBatchMatchesTheRef) {
         CHECK(lp_basis_bounded_parametric_fits(m, n) == 1 && lp_basis_bounded_parametric_cost_fits(m, n) == 1);
     }
     CHECK(lp_basis_bounded_parametric_fits(200, 400) == 0 && lp_basis_bounded_parametric_cost_fits(200, 400) == 0);
-    dlclose(h1);
-    dlclose(h2);
 }
 
 TEST(BoundedParametric_StatusesAndExceptions) {

@@ -2,78 +2,23 @@
 // column was tightened, and the result equals tests/ref/bounded_resolve_ref.c's bit for bit (the library named by
 // LP_BOUNDED_RESOLVE_REF, loaded at run time); fed back unchanged it is optimal again; crossed bounds throw unless
 // asked not to, and a bad start throws std::invalid_argument.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
 
-static const double INF = std::numeric_limits<double>::infinity();
-
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// [A0 | I] x = b with A0 > 0, k structural columns boxed in several ways, costs of both signs
-static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, MatrixXd* Aout, VectorXd* bout,
-                               VectorXd* cout, std::vector<double>* lo, std::vector<double>* hi) {
-    uint64_t s = seed * 7919 + 29;
-    const int n = k + m;
-    MatrixXd A = MatrixXd::Zero(m, n);
-    VectorXd b(m), c = VectorXd::Zero(n);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = 1.0;
-        b[i] = 0.5 * k * (1.0 + u01(s));
-    }
-    lo->assign((size_t)n, 0.0);
-    hi->assign((size_t)n, INF);
-    for (int j = 0; j < k; ++j) {
-        c[j] = u01(s) - 0.3;
-        switch (j % 4) {
-            case 1: (*hi)[(size_t)j] = 0.2 + 2.0 * u01(s); break;
-            case 2: (*lo)[(size_t)j] = (*hi)[(size_t)j] = u01(s); break;
-            case 3: (*lo)[(size_t)j] = -u01(s); (*hi)[(size_t)j] = 1.0 + u01(s); break;
-            default: break;
-        }
-    }
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;
-    *Aout = A;
-    *bout = b;
-    *cout = c;
-    Canonical can(A, b, c, basis, /*minimize=*/!maximize);
-    can.SetOriginalVariablesCount(n);
-    return can;
-}
-
 typedef int (*RefBoundedResolve)(const double*, int, int, const double*, const double*, const double*, const double*,
                                  const int*, const int*, int, int, double, int, double*, int*, int*, double*, int*);
 
-static bool same_value(double a, double b) { return (std::isnan(a) && std::isnan(b)) || a == b; }
-
 TEST(BoundedResolve_MatchesTheRef) {
-    const char* path = std::getenv("LP_BOUNDED_RESOLVE_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefBoundedResolve ref = reinterpret_cast<RefBoundedResolve>(dlsym(h, "ref_bounded_resolve"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_BOUNDED_RESOLVE_REF");
+    RefBoundedResolve ref = lib.symbol<RefBoundedResolve>("ref_bounded_resolve");
     int warm = 0, dual = 0;
     for (uint64_t seed = 0; ref && seed < 24; ++seed) {
         const int m = 3 + (int)(seed % 5), k = 5 + (int)(seed % 7), n = k + m;
@@ -114,7 +59,6 @@ TEST(BoundedResolve_MatchesTheRef) {
     }
     CHECK(warm > 12);
     CHECK(dual > 6);
-    dlclose(h);
 }
 
 TEST(BoundedResolve_FailuresAndBadStarts) {

@@ -2,15 +2,12 @@
 // tests/ref/bounded_sens_ref.c's bit for bit (the library named by LP_BOUNDED_SENS_REF, loaded at run time), the dual
 // objective is the primal one, a result that is not optimal keeps its status with NaN, a repeated basis index is
 // singular, and a bad flag or index throws std::invalid_argument.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
@@ -19,70 +16,15 @@ using lpla::VectorXd;
 
 static const double INF = std::numeric_limits<double>::infinity();
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// [A0 | I] x = b with A0 > 0, k structural columns boxed in several ways, costs of both signs
-static Canonical boxed_problem(uint64_t seed, int m, int k, bool maximize, MatrixXd* Aout, VectorXd* bout,
-                               VectorXd* cout, std::vector<double>* lo, std::vector<double>* hi) {
-    uint64_t s = seed * 7919 + 29;
-    const int n = k + m;
-    MatrixXd A = MatrixXd::Zero(m, n);
-    VectorXd b(m), c = VectorXd::Zero(n);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = 1.0;
-        b[i] = 0.5 * k * (1.0 + u01(s));
-    }
-    lo->assign((size_t)n, 0.0);
-    hi->assign((size_t)n, INF);
-    for (int j = 0; j < k; ++j) {
-        c[j] = u01(s) - 0.3;
-        switch (j % 4) {
-            case 1: (*hi)[(size_t)j] = 0.2 + 2.0 * u01(s); break;
-            case 2: (*lo)[(size_t)j] = (*hi)[(size_t)j] = u01(s); break;
-            case 3: (*lo)[(size_t)j] = -u01(s); (*hi)[(size_t)j] = 1.0 + u01(s); break;
-            default: break;
-        }
-    }
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;
-    *Aout = A;
-    *bout = b;
-    *cout = c;
-    Canonical can(A, b, c, basis, /*minimize=*/!maximize);
-    can.SetOriginalVariablesCount(n);
-    return can;
-}
-
 typedef int (*RefBoundedDuals)(const double*, int, int, const double*, const double*, const double*, const double*,
                                const int*, const int*, double*, double*, double*, double*);
 typedef int (*RefBoundedRanging)(const double*, int, int, const double*, const double*, const double*, const double*,
                                  const int*, const int*, int, double, double*, int*, int*, double*, int*);
 
-static bool same_bits(double a, double b) {
-    if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && std::isnan(b);
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y;
-}
-
 TEST(BoundedSens_MatchesTheRef) {
-    const char* path = std::getenv("LP_BOUNDED_SENS_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefBoundedDuals ref_d = reinterpret_cast<RefBoundedDuals>(dlsym(h, "ref_bounded_duals"));
-    RefBoundedRanging ref_r = reinterpret_cast<RefBoundedRanging>(dlsym(h, "ref_bounded_ranging"));
-    CHECK(ref_d != nullptr && ref_r != nullptr);
+    const RefLib lib("LP_BOUNDED_SENS_REF");
+    RefBoundedDuals ref_d = lib.symbol<RefBoundedDuals>("ref_bounded_duals");
+    RefBoundedRanging ref_r = lib.symbol<RefBoundedRanging>("ref_bounded_ranging");
     int checked = 0, at_upper = 0;
     for (uint64_t seed = 0; ref_d && ref_r && seed < 16; ++seed) {
         const int m = 3 + (int)(seed % 5), k = 5 + (int)(seed % 7), n = k + m;
@@ -126,7 +68,6 @@ TEST(BoundedSens_MatchesTheRef) {
         }
     }
     CHECK(checked >= 12 && at_upper >= 4);
-    dlclose(h);
 }
 
 TEST(BoundedSens_StatusesAndExceptions) {

@@ -2,27 +2,16 @@
 // (phase-I bases with artificials) or unbounded in phase II, the certificate at the final basis equals
 // tests/ref/certificate_ref.c's bit for bit (the library named by LP_CERTIFICATE_REF, loaded at run time), and its
 // vectors prove the verdict.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
-
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
 
 // min c.x over [A0 | -I] x = b, x >= 0 (k originals, m surplus columns), c > 0 on the originals.  kind 0: feasible;
 // kind 1: row r made non-negative (its surplus a slack) with b_r < 0: infeasible; kind 2: columns 0 and 1 ride the
@@ -58,26 +47,12 @@ static Canonical problem(uint64_t seed, int m, int k, int kind, MatrixXd* Aout, 
     return can;
 }
 
-static bool same_bits(double a, double b) {
-    if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && std::isnan(b);
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y;
-}
-
 typedef int (*RefCertificate)(const double*, int, int, const double*, const double*, const int*, int, double, int*,
                               double*, double*, double*, int*);
 
 TEST(Certificate_MatchesTheRefAndProves) {
-    const char* path = std::getenv("LP_CERTIFICATE_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefCertificate ref = reinterpret_cast<RefCertificate>(dlsym(h, "ref_certificate"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_CERTIFICATE_REF");
+    RefCertificate ref = lib.symbol<RefCertificate>("ref_certificate");
     int seen[3] = {0, 0, 0};
     for (uint64_t seed = 0; ref && seed < 24; ++seed) {
         const int m = 3 + (int)(seed % 9), k = 4 + (int)(seed % 13), n = k + m, kind = (int)(seed % 3);
@@ -131,7 +106,6 @@ TEST(Certificate_MatchesTheRefAndProves) {
         ++seen[kind];
     }
     CHECK(seen[0] == 8 && seen[1] == 8 && seen[2] == 8);
-    dlclose(h);
 }
 
 int main(int argc, char** argv) { return run_all(argc > 1 ? argv[1] : nullptr); }

@@ -5,37 +5,12 @@
 #include <cstdint>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
-
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// min c.x, A0 x >= b, x >= 0 as [A0 | -I]: k originals, m surplus columns; c > 0 on the originals
-static Canonical min_problem(uint64_t seed, int m, int k) {
-    uint64_t s = seed * 7919 + 17;
-    MatrixXd A = MatrixXd::Zero(m, k + m);
-    VectorXd b(m), c = VectorXd::Zero(k + m);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = -1.0;
-        b[i] = 1.0 + u01(s);
-    }
-    for (int j = 0; j < k; ++j) c[j] = 0.1 + u01(s);
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;   // (ignored by the two-phase flow)
-    Canonical can(A, b, c, basis, /*minimize=*/true);
-    can.SetOriginalVariablesCount(k + m);
-    return can;
-}
 
 TEST(Duals_MatchTheSolvedDual) {
     int checked = 0;

@@ -1,9 +1,13 @@
 // CPU-only tests of the host problem classes; the cases and expected values are the
 // reference's own (tests/test_canonical.cpp, test_symmetrical.cpp, test_parser.cpp,
-// test_transformations.cpp, test_common.cpp) restated without gtest/Eigen.
+// test_transformations.cpp, test_common.cpp) restated without gtest/Eigen.  The Solver_* cases at the end pin what
+// class Solver does before it reaches the device: its size checks and the results it hands through.
+#include <limits>
+
 #include "check.h"
 #include "Canonical.h"
 #include "Common.h"
+#include "SimplexSolover.h"
 #include "Symmetrical.h"
 #include "SymmetricalParser.h"
 
@@ -260,6 +264,221 @@ TEST(Canonical_Conversions) {                    // Canonical.cpp:199-364
     CHECK(d->GetObjectiveCoefficients() == vec({5, 6, -5, -6, 0, 0, 0, 0}));
     CHECK(d->GetRightHandSide() == vec({7, 8, 0, 0}));
     CHECK(d->GetBasisIndices()[0] == 4 && d->GetBasisIndices()[3] == 7);
+}
+
+// ---- class Solver without a device: every size check throws before the context is made, and an analysis of a result
+// that is not optimal (for the certificates: neither infeasible nor unbounded) hands that result through.  No case
+// here may reach lpgpu::context(): on a host without a GPU that throws std::runtime_error and the case fails.
+#define CHECK_WHAT(expr, text) do { std::string w_ = "(nothing thrown)"; \
+    try { expr; } catch (const std::invalid_argument& e) { w_ = e.what(); } \
+    catch (const std::exception& e) { w_ = std::string("(not std::invalid_argument) ") + e.what(); } \
+    if (w_ != (text)) throw std::runtime_error(std::string(__FILE__) + ":" + std::to_string(__LINE__) + ": " #expr \
+                                               " threw \"" + w_ + "\""); } while (0)
+
+static const int SM = 3, SN = 6, SNO = 4;   // rows, columns and original variables of the problem below
+static Canonical solver_problem() {
+    Canonical can(mat(SM, SN, {1, 2, 3, 1, 0, 0, 2, 1, 1, 0, 1, 0, 1, 1, 2, 0, 0, 1}), vec({4, 5, 6}),
+                  vec({3, 2, 1, 0, 0, 0}), {3, 4, 5}, /*minimize=*/false);
+    can.SetOriginalVariablesCount(SNO);
+    return can;
+}
+static bool all_nan(const VectorXd& v, long size) {
+    if (v.size() != size) return false;
+    for (long i = 0; i < size; ++i)
+        if (!std::isnan(v[i])) return false;
+    return true;
+}
+static bool all_minus_one(const std::vector<int>& v, size_t size) { return v == std::vector<int>(size, -1); }
+
+struct SolverArgs {   // right-sized and wrong-sized arguments
+    Solver s{solver_problem()};
+    Solver::Result r, shortBasis;
+    Solver::BoundedResult from, fromShortBasis, fromShortFlags;
+    std::vector<double> lo = std::vector<double>(SN, 0.0), hi = std::vector<double>(SN, 9.0),
+                        few = std::vector<double>(SN - 1, 0.0);
+    std::vector<bool> mask = std::vector<bool>(SN, true), shortMask = std::vector<bool>(SN - 1, true);
+    VectorXd d = VectorXd::Zero(SM), g = VectorXd::Zero(SN);
+    explicit SolverArgs(int status) {
+        r.status = shortBasis.status = from.status = fromShortBasis.status = fromShortFlags.status = status;
+        r.basis = from.basis = fromShortFlags.basis = {3, 4, 5};
+        shortBasis.basis = fromShortBasis.basis = {3, 4};
+        from.atUpper = fromShortBasis.atUpper = {0, 1, 0, 0, 0, 0};
+        fromShortFlags.atUpper = {0, 1, 0, 0, 0};
+    }
+};
+
+TEST(Solver_SizeChecksOfTheBasisAnalyses) {
+    SolverArgs a(LP_OPTIMAL);
+    const Solver& s = a.s;
+    CHECK_WHAT(s.duals(a.shortBasis), "Solver::duals: basis size != rows(A)");
+    CHECK_WHAT(s.ranging(a.shortBasis), "Solver::ranging: basis size != rows(A)");
+    CHECK_WHAT(s.parametricRhs(a.shortBasis, a.d, 1.0), "Solver::parametricRhs: basis size != rows(A)");
+    CHECK_WHAT(s.parametricRhs(a.r, a.g, 1.0), "Solver::parametricRhs: d size != rows(A)");
+    // the basis first
+    CHECK_WHAT(s.parametricRhs(a.shortBasis, a.g, 1.0),
+               "Solver::parametricRhs: basis size != rows(A)");
+    CHECK_WHAT(s.parametricCost(a.shortBasis, a.g, 1.0), "Solver::parametricCost: basis size != rows(A)");
+    CHECK_WHAT(s.parametricCost(a.r, a.d, 1.0), "Solver::parametricCost: g size != cols(A)");
+    CHECK_WHAT(s.parametricCost(a.shortBasis, a.d, 1.0), "Solver::parametricCost: basis size != rows(A)");
+    CHECK_WHAT(s.branchAndBound(a.shortMask), "Solver::branchAndBound: mask size != cols(A)");
+    CHECK_WHAT(s.branchAndBound(a.shortMask, a.r), "Solver::branchAndBound: mask size != cols(A)");
+    CHECK_WHAT(s.branchAndBound(a.mask, a.shortBasis), "Solver::branchAndBound: basis size != rows(A)");
+    // the mask first
+    CHECK_WHAT(s.branchAndBound(a.shortMask, a.shortBasis),
+               "Solver::branchAndBound: mask size != cols(A)");
+    for (int status : {LP_INFEASIBLE, LP_UNBOUNDED}) {
+        a.shortBasis.status = status;
+        CHECK_WHAT(s.certificate(a.shortBasis), "Solver::certificate: basis size != rows(A)");
+    }
+}
+
+TEST(Solver_SizeChecksOfTheBoundedSolves) {
+    SolverArgs a(LP_OPTIMAL);
+    const Solver& s = a.s;
+    typedef Solver::PivotRule Rule;
+    for (bool thr : {true, false}) {   // wrong sizes throw whatever throw_on_failure says
+        CHECK_WHAT(s.boundedSimplex(a.few, a.hi, thr), "Solver::boundedSimplex: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedSimplex(a.lo, a.few, thr), "Solver::boundedSimplex: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedSimplex(a.few, a.hi, Rule::Bland, thr), "Solver::boundedSimplex: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedSimplex(a.lo, a.few, Rule::Devex, thr), "Solver::boundedSimplex: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedSimplexLarge(a.few, a.hi, thr), "Solver::boundedSimplexLarge: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedSimplexLarge(a.lo, a.few, thr), "Solver::boundedSimplexLarge: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedResolve(a.few, a.hi, a.from, thr), "Solver::boundedResolve: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedResolve(a.lo, a.few, a.from, Rule::Bland, thr),
+                   "Solver::boundedResolve: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedResolve(a.lo, a.hi, a.fromShortBasis, thr),
+                   "Solver::boundedResolve: the start's basis / atUpper size != rows(A) / cols(A)");
+        CHECK_WHAT(s.boundedResolve(a.lo, a.hi, a.fromShortFlags, Rule::Devex, thr),
+                   "Solver::boundedResolve: the start's basis / atUpper size != rows(A) / cols(A)");
+        // lo / hi first
+        CHECK_WHAT(s.boundedResolve(a.few, a.hi, a.fromShortBasis, thr),
+                   "Solver::boundedResolve: lo / hi size != cols(A)");
+    }
+    CHECK_WHAT(s.boundedBranchAndBound(a.shortMask, a.lo, a.hi, a.from),
+               "Solver::boundedBranchAndBound: mask size != cols(A)");
+    CHECK_WHAT(s.boundedBranchAndBound(a.mask, a.few, a.hi, a.from),
+               "Solver::boundedBranchAndBound: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedBranchAndBound(a.mask, a.lo, a.few, a.from),
+               "Solver::boundedBranchAndBound: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedBranchAndBound(a.mask, a.lo, a.hi, a.fromShortBasis),
+               "Solver::boundedBranchAndBound: the start's basis / atUpper size != rows(A) / cols(A)");
+    CHECK_WHAT(s.boundedBranchAndBound(a.mask, a.lo, a.hi, a.fromShortFlags),
+               "Solver::boundedBranchAndBound: the start's basis / atUpper size != rows(A) / cols(A)");
+    // the mask first, then lo / hi, then the start
+    CHECK_WHAT(s.boundedBranchAndBound(a.shortMask, a.few, a.hi, a.fromShortBasis),
+               "Solver::boundedBranchAndBound: mask size != cols(A)");
+    CHECK_WHAT(s.boundedBranchAndBound(a.mask, a.few, a.hi, a.fromShortBasis),
+               "Solver::boundedBranchAndBound: lo / hi size != cols(A)");
+    // the form without a start solves the relaxation first, whose size check it is
+    CHECK_WHAT(s.boundedBranchAndBound(a.shortMask, a.few, a.hi), "Solver::boundedSimplex: lo / hi size != cols(A)");
+}
+
+TEST(Solver_SizeChecksOfTheBoundedAnalyses) {
+    SolverArgs a(LP_OPTIMAL);
+    const Solver& s = a.s;
+    const char* result = ": the result's basis / atUpper size != rows(A) / cols(A)";
+    CHECK_WHAT(s.boundedDuals(a.few, a.hi, a.from), "Solver::boundedDuals: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedDuals(a.lo, a.few, a.from), "Solver::boundedDuals: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedDuals(a.lo, a.hi, a.fromShortBasis), std::string("Solver::boundedDuals") + result);
+    CHECK_WHAT(s.boundedDuals(a.lo, a.hi, a.fromShortFlags), std::string("Solver::boundedDuals") + result);
+    // lo / hi first
+    CHECK_WHAT(s.boundedDuals(a.few, a.hi, a.fromShortBasis),
+               "Solver::boundedDuals: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedRanging(a.few, a.hi, a.from), "Solver::boundedRanging: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedRanging(a.lo, a.few, a.from), "Solver::boundedRanging: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedRanging(a.lo, a.hi, a.fromShortBasis), std::string("Solver::boundedRanging") + result);
+    CHECK_WHAT(s.boundedRanging(a.lo, a.hi, a.fromShortFlags), std::string("Solver::boundedRanging") + result);
+    CHECK_WHAT(s.boundedRanging(a.few, a.hi, a.fromShortFlags), "Solver::boundedRanging: lo / hi size != cols(A)");
+    // both parametric paths name Solver::boundedParametric for lo / hi and the result, and themselves for the direction
+    CHECK_WHAT(s.boundedParametricRhs(a.few, a.hi, a.from, a.d, 1.0),
+               "Solver::boundedParametric: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedParametricCost(a.lo, a.few, a.from, a.g, 1.0),
+               "Solver::boundedParametric: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedParametricRhs(a.lo, a.hi, a.fromShortBasis, a.d, 1.0),
+               std::string("Solver::boundedParametric") + result);
+    CHECK_WHAT(s.boundedParametricCost(a.lo, a.hi, a.fromShortFlags, a.g, 1.0),
+               std::string("Solver::boundedParametric") + result);
+    CHECK_WHAT(s.boundedParametricRhs(a.lo, a.hi, a.from, a.g, 1.0), "Solver::boundedParametricRhs: d size != rows(A)");
+    CHECK_WHAT(s.boundedParametricCost(a.lo, a.hi, a.from, a.d, 1.0),
+               "Solver::boundedParametricCost: g size != cols(A)");
+    // lo / hi first, then the result, then the direction
+    CHECK_WHAT(s.boundedParametricRhs(a.few, a.hi, a.fromShortBasis, a.g, 1.0),
+               "Solver::boundedParametric: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedParametricCost(a.lo, a.hi, a.fromShortBasis, a.d, 1.0),
+               std::string("Solver::boundedParametric") + result);
+    for (int status : {LP_INFEASIBLE, LP_UNBOUNDED}) {
+        a.from.status = a.fromShortBasis.status = a.fromShortFlags.status = status;
+        CHECK_WHAT(s.boundedCertificate(a.few, a.hi, a.from), "Solver::boundedCertificate: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedCertificate(a.lo, a.few, a.from), "Solver::boundedCertificate: lo / hi size != cols(A)");
+        CHECK_WHAT(s.boundedCertificate(a.lo, a.hi, a.fromShortBasis),
+                   std::string("Solver::boundedCertificate") + result);
+        CHECK_WHAT(s.boundedCertificate(a.lo, a.hi, a.fromShortFlags),
+                   std::string("Solver::boundedCertificate") + result);
+        CHECK_WHAT(s.boundedCertificate(a.few, a.hi, a.fromShortBasis),
+                   "Solver::boundedCertificate: lo / hi size != cols(A)");
+    }
+    // lo / hi are checked whatever the result's status, the result's own sizes only when it is analysed
+    a.from.status = a.fromShortBasis.status = LP_ITER_LIMIT;
+    CHECK_WHAT(s.boundedDuals(a.few, a.hi, a.from), "Solver::boundedDuals: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedRanging(a.few, a.hi, a.from), "Solver::boundedRanging: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedCertificate(a.few, a.hi, a.from), "Solver::boundedCertificate: lo / hi size != cols(A)");
+    CHECK_WHAT(s.boundedParametricRhs(a.few, a.hi, a.from, a.d, 1.0),
+               "Solver::boundedParametric: lo / hi size != cols(A)");
+    CHECK(s.boundedDuals(a.lo, a.hi, a.fromShortBasis).status == LP_ITER_LIMIT);
+    CHECK(s.boundedRanging(a.lo, a.hi, a.fromShortBasis).status == LP_ITER_LIMIT);
+    CHECK(s.boundedCertificate(a.lo, a.hi, a.fromShortBasis).status == LP_ITER_LIMIT);
+    CHECK(s.boundedParametricCost(a.lo, a.hi, a.fromShortBasis, a.d, 1.0).basis == a.fromShortBasis.basis);
+}
+
+TEST(Solver_ResultsThatAreNotOptimalPassThrough) {
+    SolverArgs a(LP_UNBOUNDED);
+    const Solver& s = a.s;
+    const Solver::Duals du = s.duals(a.r);
+    CHECK(du.status == LP_UNBOUNDED && all_nan(du.y, SM) && all_nan(du.d, SN) && std::isnan(du.objective));
+    const Solver::Ranging rg = s.ranging(a.r);
+    CHECK(rg.status == LP_UNBOUNDED && all_nan(rg.b_lo, SM) && all_nan(rg.b_hi, SM));
+    CHECK(all_nan(rg.c_lo, SN) && all_nan(rg.c_hi, SN));
+    CHECK(all_minus_one(rg.b_leave_lo, SM) && all_minus_one(rg.b_leave_hi, SM));
+    CHECK(all_minus_one(rg.c_enter_lo, SN) && all_minus_one(rg.c_enter_hi, SN));
+    for (int cost = 0; cost < 2; ++cost) {
+        // sizes are not looked at: the short basis comes back as it is
+        const Solver::Parametric p =
+            cost ? s.parametricCost(a.shortBasis, a.d, 1.0) : s.parametricRhs(a.shortBasis, a.g, 1.0);
+        CHECK(p.status == LP_UNBOUNDED && p.t.size() == 0 && p.obj.size() == 0 && p.slope.size() == 0);
+        CHECK(p.enter.empty() && p.leave.empty() && p.basis == a.shortBasis.basis);
+    }
+    for (int bounded = 0; bounded < 2; ++bounded) {
+        const Solver::IntegerResult ir = bounded ? s.boundedBranchAndBound(a.shortMask, a.few, a.hi, a.fromShortBasis)
+                                                 : s.branchAndBound(a.shortMask, a.shortBasis);
+        CHECK(ir.status == LP_UNBOUNDED && !ir.found && all_nan(ir.x, SNO) && ir.nodes == 0);
+        CHECK(std::isnan(ir.objective) && std::isnan(ir.bound));
+    }
+    const Solver::BoundedDuals bd = s.boundedDuals(a.lo, a.hi, a.from);
+    CHECK(bd.status == LP_UNBOUNDED && all_nan(bd.x, SN) && all_nan(bd.y, SM) && all_nan(bd.d, SN));
+    CHECK(std::isnan(bd.objective));
+    const Solver::BoundedRanging br = s.boundedRanging(a.lo, a.hi, a.from);
+    CHECK(br.status == LP_UNBOUNDED && all_nan(br.b_lo, SM) && all_nan(br.b_hi, SM));
+    CHECK(all_nan(br.c_lo, SN) && all_nan(br.c_hi, SN));
+    CHECK(all_minus_one(br.b_leave_lo, SM) && all_minus_one(br.b_leave_hi, SM));
+    CHECK(all_minus_one(br.b_side_lo, SM) && all_minus_one(br.b_side_hi, SM));
+    CHECK(all_minus_one(br.c_enter_lo, SN) && all_minus_one(br.c_enter_hi, SN));
+    for (int cost = 0; cost < 2; ++cost) {
+        const Solver::BoundedParametric p = cost ? s.boundedParametricCost(a.lo, a.hi, a.from, a.g, 1.0)
+                                                 : s.boundedParametricRhs(a.lo, a.hi, a.from, a.d, 1.0);
+        CHECK(p.status == LP_UNBOUNDED && p.t.size() == 0 && p.obj.size() == 0 && p.slope.size() == 0);
+        CHECK(p.enter.empty() && p.leave.empty() && p.side.empty());
+        CHECK(p.basis == a.from.basis && p.atUpper == a.from.atUpper);
+    }
+    // the certificates hand through what is neither infeasible nor unbounded
+    for (int status : {LP_OPTIMAL, LP_ITER_LIMIT, LP_SINGULAR}) {
+        a.shortBasis.status = a.fromShortBasis.status = status;
+        for (int bounded = 0; bounded < 2; ++bounded) {
+            const Solver::Certificate c =
+                bounded ? s.boundedCertificate(a.lo, a.hi, a.fromShortBasis) : s.certificate(a.shortBasis);
+            CHECK(c.status == status && c.kind == LP_CERT_NONE && all_nan(c.farkas, SM) && all_nan(c.ray, SN));
+            CHECK(std::isnan(c.value) && c.index == -1);
+        }
+    }
 }
 
 int main(int argc, char** argv) { return run_all(argc > 1 ? argv[1] : nullptr); }

@@ -2,30 +2,20 @@
 // boundedSimplex result equals tests/ref/mip_bounded_ref.c's bit for bit (the library named by LP_MIP_BOUNDED_REF,
 // loaded at run time), the form without a start solves the relaxation itself and gives the same result, and the
 // refusals throw.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// min c.x, A0 x >= b as [A0 | -I] with k originals in integer boxes [0 or 1, 3 .. 6] and m surplus columns in [0, inf)
+// min c.x, A0 x >= b as [A0 | -I] with k originals in integer boxes [0 or 1, 3 .. 6] and m surplus columns in [0, inf).
+// Not fixtures.h's min_problem (b_spread 3): the boxes are drawn from the same stream after the costs.
 static Canonical min_problem(uint64_t seed, int m, int k, MatrixXd* Aout, VectorXd* bout, VectorXd* cout,
                              std::vector<double>* lo, std::vector<double>* hi) {
     uint64_t s = seed * 7919 + 17;
@@ -57,8 +47,6 @@ typedef int (*RefMipBounded)(const double*, int, int, const double*, const doubl
                              const int*, const int*, int, int, const int*, double, double, double, int, int, int,
                              double*, double*, double*, int*, int*);
 
-static bool same_value(double a, double b) { return (std::isnan(a) && std::isnan(b)) || a == b; }
-
 static void check_against(RefMipBounded ref, const MatrixXd& A, const VectorXd& b, const VectorXd& c,
                           const std::vector<double>& lo, const std::vector<double>& hi,
                           const Solver::BoundedResult& from, const std::vector<bool>& integer, int max_depth,
@@ -82,14 +70,8 @@ static void check_against(RefMipBounded ref, const MatrixXd& A, const VectorXd& 
 }
 
 TEST(BoundedBranchAndBound_MatchesTheRef) {
-    const char* path = std::getenv("LP_MIP_BOUNDED_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefMipBounded ref = reinterpret_cast<RefMipBounded>(dlsym(h, "ref_mip_bounded"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_MIP_BOUNDED_REF");
+    RefMipBounded ref = lib.symbol<RefMipBounded>("ref_mip_bounded");
     int branched = 0, optimal = 0;
     for (uint64_t seed = 0; ref && seed < 16; ++seed) {
         const int m = 3 + (int)(seed % 4), k = 4 + (int)(seed % 5), n = k + m;
@@ -122,7 +104,6 @@ TEST(BoundedBranchAndBound_MatchesTheRef) {
     }
     CHECK(branched > 0);
     CHECK(optimal > 0);
-    dlclose(h);
 }
 
 TEST(BoundedBranchAndBound_NotOptimalAndRefusals) {

@@ -1,53 +1,19 @@
 // GPU tests of Solver::branchAndBound: after twoPhaseSimplex_ex() on MIN canonical problems the search from the final
 // basis equals tests/ref/mip_ref.c's bit for bit (the library named by LP_MIP_REF, loaded at run time), and the form
 // that starts from the problem's own basis agrees with the reference from that basis.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// min c.x, A0 x >= b, x >= 0 as [A0 | -I]: k originals, m surplus columns; c > 0 on the originals
-static Canonical min_problem(uint64_t seed, int m, int k, MatrixXd* Aout, VectorXd* bout, VectorXd* cout) {
-    uint64_t s = seed * 7919 + 17;
-    MatrixXd A = MatrixXd::Zero(m, k + m);
-    VectorXd b(m), c = VectorXd::Zero(k + m);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = -1.0;
-        b[i] = 1.0 + 3.0 * u01(s);
-    }
-    for (int j = 0; j < k; ++j) c[j] = 0.1 + u01(s);
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;   // dual feasible for min with c >= 0
-    *Aout = A;
-    *bout = b;
-    *cout = c;
-    Canonical can(A, b, c, basis, /*minimize=*/true);
-    can.SetOriginalVariablesCount(k + m);
-    return can;
-}
-
 typedef int (*RefMip)(const double*, int, int, const double*, const double*, const int*, int, int, const int*, double,
                       double, double, int, int, int, double*, double*, double*, int*, int*);
-
-static bool same_value(double a, double b) { return (std::isnan(a) && std::isnan(b)) || a == b; }
 
 static void check_against(RefMip ref, const MatrixXd& A, const VectorXd& b, const VectorXd& c,
                           const std::vector<int>& basis, const std::vector<bool>& integer,
@@ -71,20 +37,14 @@ static void check_against(RefMip ref, const MatrixXd& A, const VectorXd& b, cons
 }
 
 TEST(BranchAndBound_MatchesTheRef) {
-    const char* path = std::getenv("LP_MIP_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefMip ref = reinterpret_cast<RefMip>(dlsym(h, "ref_mip"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_MIP_REF");
+    RefMip ref = lib.symbol<RefMip>("ref_mip");
     int branched = 0, optimal = 0;
     for (uint64_t seed = 0; ref && seed < 16; ++seed) {
         const int m = 3 + (int)(seed % 4), k = 4 + (int)(seed % 5), n = k + m;
         MatrixXd A;
         VectorXd b, c;
-        Canonical primal = min_problem(500 + seed, m, k, &A, &b, &c);
+        Canonical primal = min_problem(500 + seed, m, k, &A, &b, &c, /*b_spread=*/3.0);
         Solver s(primal);
         std::vector<bool> integer((size_t)n, false);
         for (int j = 0; j < k; ++j) integer[(size_t)j] = seed % 3 != 1 || j % 2 == 0;   // some mixed masks
@@ -103,13 +63,12 @@ TEST(BranchAndBound_MatchesTheRef) {
     }
     CHECK(branched > 0);
     CHECK(optimal > 0);
-    dlclose(h);
 }
 
 TEST(BranchAndBound_NotOptimalAndBadMask) {
     MatrixXd A;
     VectorXd b, c;
-    Canonical primal = min_problem(3, 4, 5, &A, &b, &c);
+    Canonical primal = min_problem(3, 4, 5, &A, &b, &c, /*b_spread=*/3.0);
     Solver s(primal);
     Solver::Result r = s.twoPhaseSimplex_ex();
     std::vector<bool> integer(9, true);

@@ -1,60 +1,20 @@
 // GPU tests of Solver::parametricCost: after twoPhaseSimplex_ex() on MIN canonical problems the parametric cost path
 // from the final basis equals tests/ref/parametric_cost_ref.c's bit for bit (the library named by
 // LP_PARAMETRIC_COST_REF, loaded at run time), and the path is concave.
-#include <dlfcn.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 
 #include "check.h"
+#include "fixtures.h"
 #include "Canonical.h"
 #include "SimplexSolover.h"
 
 using lpla::MatrixXd;
 using lpla::VectorXd;
 
-static double u01(uint64_t& s) {   // splitmix64
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// min c.x, A0 x >= b, x >= 0 as [A0 | -I]: k originals, m surplus columns; c > 0 on the originals
-static Canonical min_problem(uint64_t seed, int m, int k, MatrixXd* Aout, VectorXd* bout, VectorXd* cout) {
-    uint64_t s = seed * 7919 + 17;
-    MatrixXd A = MatrixXd::Zero(m, k + m);
-    VectorXd b(m), c = VectorXd::Zero(k + m);
-    for (int i = 0; i < m; ++i) {
-        for (int j = 0; j < k; ++j) A(i, j) = u01(s);
-        A(i, k + i) = -1.0;
-        b[i] = 1.0 + u01(s);
-    }
-    for (int j = 0; j < k; ++j) c[j] = 0.1 + u01(s);
-    std::vector<int> basis((size_t)m);
-    for (int i = 0; i < m; ++i) basis[(size_t)i] = k + i;   // (ignored by the two-phase flow)
-    *Aout = A;
-    *bout = b;
-    *cout = c;
-    Canonical can(A, b, c, basis, /*minimize=*/true);
-    can.SetOriginalVariablesCount(k + m);
-    return can;
-}
-
 typedef int (*RefParametricCost)(const double*, int, int, const double*, const double*, const int*, int,
                                  const double*, double, double, int, int*, double*, double*, double*, int*, int*,
                                  int*);
-
-static bool same_bits(double a, double b) {
-    if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && std::isnan(b);
-    uint64_t x, y;
-    std::memcpy(&x, &a, 8);
-    std::memcpy(&y, &b, 8);
-    return x == y;
-}
 
 // a seeded cost direction with mixed signs, scaled by |c| (0.5 where c_j = 0); positive = true takes |g|
 static VectorXd direction(uint64_t seed, const VectorXd& c, bool positive) {
@@ -68,14 +28,8 @@ static VectorXd direction(uint64_t seed, const VectorXd& c, bool positive) {
 }
 
 TEST(ParametricCost_MatchesTheRef) {
-    const char* path = std::getenv("LP_PARAMETRIC_COST_REF");
-    CHECK(path != nullptr);
-    if (!path) return;
-    void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    CHECK(h != nullptr);
-    if (!h) return;
-    RefParametricCost ref = reinterpret_cast<RefParametricCost>(dlsym(h, "ref_parametric_cost"));
-    CHECK(ref != nullptr);
+    const RefLib lib("LP_PARAMETRIC_COST_REF");
+    RefParametricCost ref = lib.symbol<RefParametricCost>("ref_parametric_cost");
     int multi = 0, unbounded = 0;
     for (uint64_t seed = 0; ref && seed < 24; ++seed) {
         const int m = 3 + (int)(seed % 9), k = 4 + (int)(seed % 13), n = k + m;
@@ -109,7 +63,6 @@ TEST(ParametricCost_MatchesTheRef) {
     }
     CHECK(multi > 0);
     CHECK(unbounded > 0);
-    dlclose(h);
 }
 
 TEST(ParametricCost_NotOptimalHasNoSegments) {
