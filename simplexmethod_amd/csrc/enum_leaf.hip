@@ -21,12 +21,12 @@
 // in-LDS pivot and its lanes take 5 columns each (items of table 1).  k_enum_leaves<1> finishes
 // what is left of each child (items of table 0).
 //
-// k_enum_thin (the tails).  A depth m-6 node with fewer than 8 selectable columns holds at most
-// C(7,6) = 7 subsets: as a work item it would cost a pivot and a wave pass for a handful of
-// lanes, and such nodes are two thirds of their level.  Their subsets are exactly the ones that
-// lie inside the LAST 8 columns of a depth m-7 node — at most C(8,7) = 8 per record — and the
-// thin kernel takes them straight from the records in HBM: 8 lanes per record, 7 columns per
-// lane, every lane reading its own record (no LDS staging, nothing wave-uniform).
+// k_enum_thin (the tails).  A depth m-6 node with fewer than THIN_TAIL = 9 selectable columns holds at
+// most C(8,6) = 28 subsets: as a work item it would cost a pivot and a wave pass for a handful of
+// lanes, and such nodes are most of their level.  Their subsets are exactly the ones that lie
+// inside the LAST 9 columns of a depth m-7 node — at most C(9,7) = 36 per record — and the tail
+// kernel takes them from the records: 7 columns per lane, the lanes of a wave packed densely over
+// the subsets of consecutive records, whose last columns are staged in LDS with permuted rows.
 //
 //   phase 1  the KD rows not used by the prefix x the KD chosen columns (+ rhs) sit in
 //            registers; KD-2 Gauss-Jordan steps with partial pivoting among the unused rows
@@ -53,7 +53,10 @@ constexpr int kGrandMin = LP_GRAND_MIN;         // a depth m-5 node with >= 10 s
 #endif
 constexpr int kGreatMin = LP_GREAT_MIN;         // k_enum_leaves<3>: a sub-group (child, j2, j3) that leaves >= 9 selectable
                                       // columns (>= 126 subsets) gets a third in-LDS pivot, 4 columns per lane
-constexpr int THIN_TAIL = 8;          // the thin kernel takes the subsets inside the last 8 columns
+// The tail kernel (k_enum_thin) takes the subsets inside a record's last THIN_TAIL columns; children with fewer
+// selectable columns leave the item tables.  C(32,16) pass with 8 / 9 / 10 columns: 12.80 / 12.67 / 14.64 ms; the
+// other shapes and the shards in lp_enum_launch_leaves.
+constexpr int THIN_TAIL = 9;
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
                                       // same row of different columns hit different banks
 
@@ -1090,73 +1093,249 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
     if (tid < 3 && s_cnt[tid]) atomicAdd(&d.result->counts[tid], s_cnt[tid]);
 }
 
-// The tails: 8 lanes per depth m-7 record, lane j takes the j-th 7-subset (lexicographic) of the
-// record's last min(R, 8) selectable columns — C(8,7) = 8, C(7,7) = 1 — reading the record where
-// it lies in HBM (column stride PG).
-template <bool EXACT>
-__global__ __launch_bounds__(LEAF_THREADS) void k_enum_thin(EnumDev d, PrefixDev pd,
+// The tails: for every depth m-7 record, the 7-subsets inside its last T' = min(R, T) selectable columns (T = THIN_TAIL) —
+// the last C(T',7) subsets of the record in rank order, in the lexicographic order of those T' columns (s_comb).
+// Lanes are packed densely: a wave takes a batch of 64 consecutive records, one lane reads each record's metadata
+// (the next batch's is in flight meanwhile), the records that have subsets inside [begin, end) are compacted into the
+// wave's LDS list with the prefix sums of their subset counts, and passes of 64 consecutive subsets run over that
+// list — a record with one subset costs one lane, not eight.  The columns a pass needs (last T' columns + rhs: one
+// contiguous run of 128-byte columns per record) are loaded coalesced one pass ahead, and written to the wave's LDS
+// slots with the rows permuted by the record's used_mask (the 7 unused rows first, ascending; as the child pivot's
+// write in k_enum_leaves), so that the lanes run leaf_verdict<PERM>: rows of steps 0 and 1 chosen before loading, no
+// rotation selects, phase 2 from LDS.  A pass ends after 64 subsets or kTailSlots records, whichever comes first.
+// (Row offsets of the other five rows: leaf_verdict's computed branch, ~25 integer instructions per subset of
+// ~900; a 49-entry table of 64-bit words would save ~15 of them for two more LDS reads.)
+// Registers: seven columns per lane are 49 + 7 doubles of matrix and 30 of stored pivot rows; with the staged columns
+// the kernel needs 254 VGPRs (2 waves per SIMD).  Held to the leaf kernels' 168 it spills 127-364 registers, and the
+// scratch reloads, which share the loads' in-order counter, serialise every pass: C(32,16) 23-35 ms against 13.
+// kTailSlots: passes made of one-subset records fill only that many lanes; 4 slots instead of 8 cost 8 % of the pass
+// at 8 columns (15.5 against 14.4 ms with the kernel beside the leaf kernels), 16 would not fit the registers.
+constexpr int kTailSlots = 8;                               // records staged per pass and wave
+// doubles per staged record of T + 1 columns: odd, so that lanes reading the same row and column of different records
+// hit different banks
+constexpr int tail_slot(int T) { return ((T + 1) * TS) | 1; }
+constexpr int tail_iter(int T) { return (T + 1 + 3) / 4; }  // columns per 16-lane group and staged record (4 groups per wave)
+__host__ __device__ constexpr int tail_count(int tp) { return tp == 7 ? 1 : tp == 8 ? 8 : 36; }     // C(tp, 7), tp <= 9
+__host__ __device__ constexpr int tail_comb_off(int tp) { return tp == 7 ? 0 : tp == 8 ? 1 : 9; }   // sum of the counts below tp
+constexpr int tail_comb(int T) { return tail_comb_off(T) + tail_count(T); }   // 7-subsets of 7 .. T columns
+// s_waitcnt vmcnt(0) in the gfx9 encoding of the instruction's immediate: vmcnt = bits 3:0 and 15:14 (all zero),
+// expcnt = bits 6:4 (7: not waited for), lgkmcnt = bits 11:8 (15: not waited for)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "k_enum_thin: kWaitVm0 is the gfx9 encoding of s_waitcnt"
+#endif
+constexpr int kWaitVm0 = 0x0F70;
+struct alignas(16) TailRec {
+    unsigned long long rank0;   // rank of the record's first tail subset
+    unsigned used;              // rows used by the prefix
+    unsigned src;               // lane that holds the record's metadata (= record index inside the batch) | T' << 8
+};
+
+template <bool EXACT, int T>
+__global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void k_enum_thin(EnumDev d, PrefixDev pd,
                                                              const double* __restrict__ roots,
                                                              int root_level, int root_cap,
                                                              unsigned long long begin,
                                                              unsigned long long end) {
-    constexpr int KD = 7;
+    static_assert(T == 8 || T == 9, "k_enum_thin: subset table, counts and LDS slots are written for 8 and 9 columns");
+    constexpr int KD = 7, kTailSlot = tail_slot(T), kTailIter = tail_iter(T), kTailComb = tail_comb(T);
+    __shared__ __attribute__((aligned(16))) double s_slot[LEAF_WAVES][kTailSlots * kTailSlot];
+    __shared__ TailRec s_rec[LEAF_WAVES][64];   // the batch's records that have tail subsets in range, compacted
+    __shared__ int s_pre[LEAF_WAVES][65];       // exclusive prefix sums of their subset counts (+ the total)
+    __shared__ unsigned int s_comb[kTailComb];  // 7-subsets of T' columns in lexicographic order, 4 bits per index
+    __shared__ unsigned int s_b7[NMX + KD + 2]; // C(r, 7)
     __shared__ unsigned long long s_cnt[3];
     const int m = d.m, n = d.n, D = m - KD;
     const int nrec = min(pd.level_counts[root_level], root_cap);
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef LP_LEAF_WAVELOG
     const unsigned long long wl_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     if (tid < 3) s_cnt[tid] = 0ULL;
+    if (tid < NMX + KD + 2) s_b7[tid] = (unsigned int)d.binom[tid * kBinomK + KD];
+    if (tid < kTailComb) {
+        const int tp = tid < tail_comb_off(8) ? 7 : tid < tail_comb_off(9) ? 8 : 9;
+        unsigned long long j = (unsigned long long)(tid - tail_comb_off(tp));
+        unsigned pk = 0;
+        int x = 0;
+        for (int t = 0; t < KD; ++t) {
+            for (; x < tp; ++x) {   // subsets whose t-th column is x: C(tp - 1 - x, 6 - t)
+                const unsigned long long cx = binom(d, tp - 1 - x, KD - 1 - t);
+                if (j < cx) break;
+                j -= cx;
+            }
+            pk |= (unsigned)x << (4 * t);
+            ++x;
+        }
+        s_comb[tid] = pk;
+    }
     __syncthreads();
-    // grid-stride over (record, tail subset) pairs: the grid is sized to the chip, and the three
-    // counters leave a block with three atomics in total (one block per 32 records would put
-    // 190 k atomics on three words for C(32,16): 0.7 ms at ~11 ns each)
     unsigned int cnt[3] = {0u, 0u, 0u};
     unsigned int viol = 0;
-    for (long long gid = (long long)blockIdx.x * LEAF_THREADS + tid; gid < (long long)nrec * 8;
-         gid += (long long)gridDim.x * LEAF_THREADS) {
-    const int rec = (int)(gid >> 3), j = (int)(gid & 7);
-    int verdict = -1;
-    unsigned long long rank = 0ULL;
-    if (rec < nrec) {
-        const double* Q = roots + (size_t)rec * rec_doubles(n, D);
-        const NodeMeta* pm = reinterpret_cast<const NodeMeta*>(Q + (size_t)PG * (n - D + 1));
-        const int last = pm->last_col;
-        const int R = n - 1 - last;
-        const int R8 = R < THIN_TAIL ? R : THIN_TAIL;
-        // the 7-subsets of 8 columns in lexicographic order: the j-th leaves out column 7 - j
-        const int ntail = (R8 == THIN_TAIL) ? THIN_TAIL : 1;
-        if (last != kHole && R >= KD && j < ntail) {
-            // L - ntail + j: the tail subsets are the last ones of the node
-            rank = pm->rank_base + (binom(d, R, KD) - (unsigned long long)ntail + (unsigned long long)j);
-            if (rank >= begin && rank < end) {
-                int c[KD];
+    double* const slots = s_slot[wave];
+    TailRec* const recs = s_rec[wave];
+    int* const pre = s_pre[wave];
+    const int nbatch = (nrec + 63) >> 6;
+    const int nw = (int)gridDim.x * LEAF_WAVES;
+    const size_t recd = rec_doubles(n, D);
+    const int row = lane & (PG - 1), cg = lane >> 4;   // staging: lane = (row, one of 4 columns)
+    const unsigned all = (1u << m) - 1u, below = (1u << row) - 1u;
+    // one lane per record of a batch; the metadata of the wave's next batch is loaded a batch ahead
+    int lastN = kHole;
+    unsigned usedN = 0;
+    unsigned long long rbN = 0ULL;
+    double minN = 0.0, maxN = 0.0;
+    auto meta = [&](int batch) {
+        const int rec = batch * 64 + lane;
+        lastN = kHole;
+        if (batch < nbatch && rec < nrec) {
+            const NodeMeta* pm = reinterpret_cast<const NodeMeta*>(roots + (size_t)rec * recd + (size_t)PG * (n - D + 1));
+            lastN = pm->last_col;
+            usedN = pm->used_mask;
+            rbN = pm->rank_base;
+            minN = pm->minp;
+            maxN = pm->maxp;
+        }
+    };
+    double stage[kTailSlots * kTailIter] = {};   // a pass's columns in flight
+    int batch = (int)blockIdx.x * LEAF_WAVES + wave;
+    meta(batch);
+    for (; batch < nbatch; batch += nw) {
+        const int last = lastN;
+        const unsigned used = usedN;
+        const unsigned long long rb = rbN;
+        const double minp_l = minN, maxp_l = maxN;
+        meta(batch + nw);
+        const int recbase = batch * 64;
+        // ---- the batch's work list: records with tail subsets in range, prefix sums of their counts
+        const int R = n - 1 - last, Tp = R < T ? R : T;
+        int c7 = 0;
+        unsigned long long rank0 = 0ULL;
+        if (last != kHole && R >= KD) {
+            c7 = tail_count(Tp);
+            rank0 = rb + (unsigned long long)(s_b7[R] - (unsigned int)c7);   // the tail subsets are the record's last ones
+            if (overlap(rank0, (unsigned long long)c7, begin, end) == 0ULL) c7 = 0;
+        }
+        const unsigned long long nz = __ballot(c7 > 0);
+        const int nk = __popcll(nz);
+        if (nk == 0) continue;
+        const int k = __popcll(nz & ((1ULL << lane) - 1ULL));
+        int incl = c7;   // inclusive wave scan
 #pragma unroll
-                for (int t = 0; t < KD; ++t) c[t] = (R - R8) + t + ((R8 == THIN_TAIL && t >= 7 - j) ? 1 : 0);
-                const unsigned umask = pm->used_mask;
-                int U[KD];
-                unsigned free_rows = ~umask & (m >= 32 ? ~0u : ((1u << m) - 1u));
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
+        if (c7 > 0) {
+            pre[k] = incl - c7;
+            TailRec tr;
+            tr.rank0 = rank0;
+            tr.used = used;
+            tr.src = (unsigned)lane | ((unsigned)Tp << 8);
+            recs[k] = tr;
+        }
+        if (lane == 63) pre[nk] = incl;
+        const int total = __shfl(incl, 63, 64);
+        // a pass: subsets [w0, wend) of the list, inside records k0 .. k0 + nslot - 1 (slot = record - k0)
+        auto plan = [&](int k0, int w0, int& nslot, int& wend) {
+            const int k1 = min(k0 + kTailSlots, nk);
+            wend = __builtin_amdgcn_readfirstlane(min(w0 + 64, pre[k1]));
+            const bool starts = lane < k1 - k0 && pre[min(k0 + lane, nk)] < wend;
+            nslot = __popcll(__ballot(starts));
+        };
+        // Staging: the 16-lane group cg of a wave takes columns cg, cg + 4, cg + 8 of every slot (lane = row), so a
+        // slot costs one address and kTailIter loads / LDS writes at immediate offsets.  The slot's record is
+        // wave-uniform: its fields go through scalar registers.
+        auto issue = [&](int k0, int nslot) {   // loads of a pass's columns (no use of the data here)
 #pragma unroll
-                for (int r = 0; r < KD; ++r) {
-                    U[r] = free_rows ? __builtin_ctz(free_rows) : 0;
-                    free_rows &= free_rows - 1u;
+            for (int s = 0; s < kTailSlots; ++s) {
+                if (s < nslot) {
+                    const unsigned srcw = __builtin_amdgcn_readfirstlane(recs[k0 + s].src);
+                    const int tp = (int)(srcw >> 8);
+                    // column cc of the slot = the record's column n - tp + cc (cc = tp: the rhs)
+                    const double* p = roots + (size_t)(recbase + (int)(srcw & 0xFFu)) * recd + (size_t)(n - tp - D) * PG + lane;
+                    // (a column past the rhs is replaced by the group's first one and never written to LDS: the load
+                    // itself stays unconditional, so that no select waits for its data here)
+#pragma unroll
+                    for (int i = 0; i < kTailIter; ++i) stage[s * kTailIter + i] = p[(cg + 4 * i <= tp) ? 4 * i * PG : 0];
                 }
-                const double* tab = Q + (size_t)(last + 1 - D) * PG;   // column q = column last+1+q
-                verdict = leaf_verdict<KD, PG, false, false, !EXACT>(tab, c, R, U, umask, pm->minp, pm->maxp, m, nullptr, &viol);
             }
+        };
+        auto commit = [&](int k0, int nslot) {  // registers -> LDS slots, rows permuted: unused rows first
+#pragma unroll
+            for (int s = 0; s < kTailSlots; ++s) {
+                if (s < nslot) {
+                    const int tp = (int)(__builtin_amdgcn_readfirstlane(recs[k0 + s].src) >> 8);
+                    const unsigned usedw = __builtin_amdgcn_readfirstlane(recs[k0 + s].used) & all;
+                    const unsigned freem = ~usedw & all;
+                    const int pos = (row >= m) ? row
+                                    : ((freem >> row) & 1u) ? __builtin_popcount(freem & below)
+                                                            : __builtin_popcount(freem) + __builtin_popcount(usedw & below);
+                    double* q = slots + s * kTailSlot + cg * TS + pos;
+#pragma unroll
+                    for (int i = 0; i < kTailIter; ++i)
+                        if (cg + 4 * i <= tp) q[4 * i * TS] = stage[s * kTailIter + i];
+                }
+            }
+        };
+        int k0 = 0, w0 = 0, nslot, wend;
+        plan(k0, w0, nslot, wend);
+        issue(k0, nslot);
+        for (;;) {
+            commit(k0, nslot);
+            // Every staged load has landed by now (the slots just written were the last ones issued), and the
+            // explicit wait tells the compiler so: without it the generated code guards the reuse of each staging
+            // register in the next pass's loads with a wait of its own — the counter is in order, so slot s + 1's
+            // loads then wait for slot s's, one HBM round trip per staged record.
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_waitcnt(kWaitVm0);
+            // (The next batch's metadata loads are older than this pass's staged loads, which the commit above has
+            // waited for already: the counter is in order, so this wait costs them nothing.)
+            // the next pass: its first record is the one this pass ends in, unless that one is finished
+            const int kn = k0 + nslot - (pre[k0 + nslot] == wend ? 0 : 1);
+            const bool more = wend < total;
+            int nslotN = 0, wendN = 0;
+            if (more) {
+                plan(kn, wend, nslotN, wendN);
+                issue(kn, nslotN);
+            }
+            // ---- one subset per lane
+            const int w = w0 + lane;
+            int s = 0;
+            for (int q = 1; q < nslot; ++q) s += (pre[k0 + q] <= w) ? 1 : 0;
+            const TailRec tr = recs[k0 + s];
+            const int src = (int)(tr.src & 0xFFu), tp = (int)(tr.src >> 8);
+            const double minp0 = __shfl(minp_l, src, 64), maxp0 = __shfl(maxp_l, src, 64);
+            const int j = w - pre[k0 + s];
+            int verdict = -1;
+            unsigned long long rank = 0ULL;
+            if (w < wend) {
+                rank = tr.rank0 + (unsigned long long)j;
+                if (rank >= begin && rank < end) {
+                    const unsigned pk = s_comb[tail_comb_off(tp) + j];
+                    int c[KD];
+#pragma unroll
+                    for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (4 * t)) & 15u);
+                    const int U[KD] = {0, 1, 2, 3, 4, 5, 6};   // unused by leaf_verdict<PERM>
+                    verdict = leaf_verdict<KD, TS, true, false, !EXACT, false>(slots + s * kTailSlot, c, tp, U, 0u, minp0, maxp0, m,
+                                                                               nullptr, &viol);
+                }
+            }
+            if (verdict == 0) {
+                const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
+                if (at < pd.list_cap) {
+                    pd.list[at] = rank;
+                    pd.list_rec[at] = recbase + src;
+                }
+            }
+            cnt[0] += verdict == 0;
+            cnt[1] += verdict == 1;
+            cnt[2] += verdict == 2;
+            if (!more) break;
+            k0 = kn;
+            w0 = wend;
+            nslot = nslotN;
+            wend = wendN;
         }
-    }
-    if (verdict == 0) {
-        const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
-        if (at < pd.list_cap) {
-            pd.list[at] = rank;
-            pd.list_rec[at] = rec;
-        }
-    }
-    cnt[0] += verdict == 0;
-    cnt[1] += verdict == 1;
-    cnt[2] += verdict == 2;
     }
 #ifdef LP_LEAF_WAVELOG
     wavelog_put(7, wl_t0, wl_t0, 0, 0);
@@ -1577,8 +1756,8 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
     const unsigned long long b = begin, e = end;
     if (fused) {
         // The three leaf kernels are independent of each other (own item table / work cursor, results
-        // through atomics), and the thin kernel does not even need the item tables: they run on three
-        // streams, so that the thin kernel runs beside the leaf kernels and every kernel's tail (persistent
+        // through atomics), and the tail kernel does not even need the item tables: they run on three
+        // streams, so that the tail kernel runs beside the item builder and every leaf kernel's tail (persistent
         // waves running out of items) is filled by the next kernel's blocks.  The library's stream
         // waits for the other two before anything that follows (list evaluation, result copy).
         if (!ctx->aux_stream[0]) {
@@ -1589,27 +1768,46 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         const int lanes = bound < 300000 ? kItemLanesNarrow : kItemLanesWide;
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[0], s));          // the level records are complete
         LP_HIP(ctx, hipStreamWaitEvent(sT, ctx->aux_event[0], 0));
-        // The thin kernel is latency-bound (8 lanes per record, gathers from HBM: half of its VALU slots idle) and
-        // nothing waits for it: a small grid of it (ONE workgroup per CU, grid-stride) is queued BEHIND the item
-        // builder, which is on the leaf kernels' critical path, and runs beside the leaf kernels.  (Launched first
-        // with 12 workgroups per CU it held the chip while the item builder ran: 14.72 -> 14.50 ms on the whole
-        // range, 2.26 -> 2.21 ms on the slowest 8-way shard.  Round 4, with the leaf kernels' new dealing: 1 / 2 / 3 / 4
-        // workgroups per CU 13.16 / 13.26 / 13.89 / 13.67 ms, slowest shard 1.92 / 1.95 / 2.01 / 1.99 ms — its waves
-        // hold slots that table 0's kernel, which ends the pass, would use better; scripts/time_enum_variant.py.)
-        const int thin_per_cu = 1;
-        const unsigned grid_thin = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>((uint64_t)bound * 8, LEAF_THREADS), (uint64_t)ctx->num_cus * thin_per_cu);
-        auto launch_thin = [&]() {
-            if (exact)
-                hipLaunchKernelGGL(k_enum_thin<true>, grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
-            else
-                hipLaunchKernelGGL(k_enum_thin<false>, grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
-        };
+        // The tail kernel needs the level records only, not the item tables: it is launched on its own stream BESIDE
+        // the item builder and, on a whole range, is over when the leaf kernels start, which then have every workgroup
+        // slot of the chip to themselves.  Its waves hold 254 registers (seven columns per lane), so a CU has room for
+        // two of its workgroups: that is the grid.  Nothing depends on it ending first: workgroups of it that are
+        // still resident when the leaf kernels' blocks arrive keep their slots until they are done, which costs time
+        // only.  Its predecessor (8 lanes per record gathering from HBM) ran behind the item builder, one workgroup per
+        // CU beside the leaf kernels, and held a slot of every CU for 9.0 of their 10.9 ms; launched first with 12
+        // workgroups per CU it had held the chip while the item builder ran (14.72 -> 14.50 ms, slowest 8-way shard
+        // 2.26 -> 2.21 ms), and its grid of 1 / 2 / 3 / 4 per CU gave 13.16 / 13.26 / 13.89 / 13.67 ms, slowest shard
+        // 1.92 / 1.95 / 2.01 / 1.99 ms.
+        // Measured on one MI355X against that predecessor (profiles/enum_tail.json):
+        //   bench step, C(32,16), 7 runs each, alternating: 13.36 -> 13.01 ms (-2.6 %; the predecessor's runs within 0.10 ms)
+        //   kernel time of a pass (scripts/ab_enum.py), predecessor 13.03 ms:
+        //     beside the item builder, 2 workgroups per CU: THIN_TAIL = 8 / 9 / 10  12.80 / 12.67 / 14.64 ms
+        //     THIN_TAIL = 9, 1 / 2 / 4 workgroups per CU: 14.04 / 12.83 / 12.73 ms against 13.18 (8 columns: 14.59 /
+        //       12.80 / 12.81) — one per CU is still running when the leaf kernels' blocks arrive and ends the pass;
+        //       four are two resident and two waiting, inside the noise of two
+        //     alone between the item builder and the leaf kernels, 2 per CU:    12.94 / 12.92 / 13.93 ms
+        //       (the tail kernel by itself 0.89 ms at 8 columns, 3.86 ms at 10; the leaf phase behind it 9.84 ms
+        //       against 10.91 ms with the old kernel beside it; the item builder beside the tail kernel takes
+        //       1.03 ms instead of 0.26 ms, and both end together)
+        //     behind the item builder, beside the leaf kernels as its predecessor, 8 columns, 1 / 2 per CU: 14.36 /
+        //       13.38 ms, 10 columns 18.2 / 14.5 ms — a workgroup of 254-register waves and 45 KB of LDS finds no room
+        //       on a CU that holds three leaf workgroups, and most of the grid ran after table 0's kernel had ended.
+        //   small passes (wall, best / mean; predecessor first): C(28,14) 1.131 / 1.147 -> 1.136 / 1.154 ms (bench leg:
+        //     kernel 1.129 -> 1.110 and 1.120 -> 1.127 ms in two sessions); slowest of the 8 cost-balanced shards of C(32,16) 1.938 / 1.962 -> 2.004 /
+        //     2.032 ms: a shard PAYS 3 % — its item builder is over in 0.05 ms and the tail kernel's blocks are still
+        //     there when the leaf kernels start.  Alone behind the item builder: 1.989 / 2.002 ms, C(28,14) 1.161 ms.
+        //     Eight columns on ranges of fewer than 300,000 records (a build with both widths): shards 1.935 / 2.029 ms,
+        //     but C(28,14) 1.178 / 1.200 ms and its bench leg 1.110 -> 1.148 ms; so one width for every range.
+        const int thin_per_cu = 2;
+        const unsigned grid_thin = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>((uint64_t)bound, 64 * LEAF_WAVES), (uint64_t)ctx->num_cus * thin_per_cu);
+        if (exact)
+            hipLaunchKernelGGL((k_enum_thin<true, THIN_TAIL>), grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
+        else
+            hipLaunchKernelGGL((k_enum_thin<false, THIN_TAIL>), grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
         hipLaunchKernelGGL(k_enum_make_items<true>, lp_ceil_div(bound * lanes, 1024), 1024, 0, s, p->dev, pd,
                            roots, level, bound, THIN_TAIL, lanes, b, e);
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[1], s));          // both item tables are built
         LP_HIP(ctx, hipStreamWaitEvent(s1, ctx->aux_event[1], 0));
-        LP_HIP(ctx, hipStreamWaitEvent(sT, ctx->aux_event[1], 0));
-        launch_thin();
         // both leaf kernels with resident-sized grids (3 workgroups per CU).  (2 for table 1's kernel gives the best
         // single passes — C(28,14) 1.17 against 1.19 ms, C(32,16) 13.2 against 13.3 — but half of the passes then take
         // 14.0-14.1 ms: the average is worse.)
