@@ -595,10 +595,22 @@ int lp_simplex_bounded_fits(int m, int n);
  *     hi_j < lo_j is LP_INFEASIBLE without an iteration (zero counters, basis n + t, no flag).
  *   - max_iter bounds the pivots plus flips of each phase; iters_out[4] = phase-I pivots, drive-out pivots, phase-II
  *     pivots, bound flips.
- *   - Dantzig's rule only.  Out of scope on this path: Bland's rule and Devex pricing, a re-solve from a basis, and
- *     the analyses (duals, ranging, certificates, parametrics, branch and bound); those stay at
- *     lp_simplex_bounded_fits shapes.  lp_simplex_bounded itself is unchanged and still refuses larger shapes.   */
+ *   - Dantzig's rule only.  Out of scope on this path: Bland's rule and Devex pricing, and the analyses (duals,
+ *     ranging, certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The
+ *     re-solve from a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is
+ *     unchanged and still refuses larger shapes.                                                                 */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
+/* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
+ * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
+ * bound, fixing a column or moving b or c costs the m crash pivots that install the basis on the (m+1) x (n+1) tableau
+ * (no artificial columns) plus the dual or primal pivots from there, instead of the whole two-phase solve.  The primal
+ * loop is lp_simplex_bounded_large's phase II; the dual loop is one bounded dual selector and one rank-1 update launch
+ * per pivot.  Arguments, outputs, statuses, refusals and iters_out[3] (dual pivots, primal pivots, bound flips) are
+ * lp_simplex_bounded_resolve's with one difference: there is no lp_simplex_bounded_fits limit (the limits are device
+ * memory for the tableau, and m <= 9960 for the selectors' LDS).  At a shape that also fits LDS every output equals
+ * lp_simplex_bounded_resolve's.  Dantzig's rule only, one LP per call; lp_simplex_bounded_resolve itself is unchanged
+ * and still refuses larger shapes.  Every pointer is required.                                                     */
+int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 
 /* ---- Bounded variables: the re-solve from a basis -------------------------------------------------------------
  * The LP of lp_simplex_bounded re-solved from basis_in (m, by position, every index in [0, n)) and at_upper_in (n,

@@ -148,6 +148,8 @@ SIGNATURES = {
     "lp_simplex_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_simplex_bounded_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                            C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
+    "lp_simplex_bounded_resolve_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int,
+                                             C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
     "lp_simplex_bounded_resolve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int,
                                              C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip]),
     "lp_simplex_bounded_resolve_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -774,6 +776,24 @@ class Context:
         rc = self.check(self.lib.lp_simplex_bounded_large(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
                                                           int(maximize), n_orig, float(eps), int(max_iter), _d(x),
                                                           _i(bo), _i(up), _d(obj), _i(it)))
+        return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
+
+    def bounded_resolve_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
+                              max_iter=MAX_ITER):
+        """lp_simplex_bounded_resolve_large: the re-solve of bounded_resolve() on the tableau in HBM, at any shape
+        bounded_large() runs (no bounded_fits limit); Dantzig's rule.  Returns the dict of bounded_resolve(), equal to
+        it where both run; refusals as there."""
+        p = pack_lp(A, b, c, basis, lo, hi, at_upper)
+        m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
+        n_orig = n if n_orig is None else int(n_orig)
+        x = np.full(n_orig, np.nan)
+        bo = np.full(m, -1, dtype=np.int32)
+        up = np.zeros(n, dtype=np.int32)
+        obj = np.full(1, np.nan)
+        it = np.zeros(3, dtype=np.int32)
+        rc = self.check(self.lib.lp_simplex_bounded_resolve_large(
+            self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
+            float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it)))
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_fits(self, m, n):

@@ -1,5 +1,6 @@
 // simplex_bounded_launch.hip — the bounded-variable simplex on the HBM tableau of simplex_launch.hip
-// (lp_simplex_bounded_large): one select + one rank-1-update launch per iteration, at any shape the launch pair runs.
+// (lp_simplex_bounded_large, and lp_simplex_bounded_resolve_large's classification and dual loop): one select + one
+// rank-1-update launch per iteration, at any shape the launch pair runs.
 //
 // The definition is tests/ref/bounded_ref.c, which is stated on a condensed slot tableau.  Here the tableau is the full
 // one of SimplexDev: (m+1) x ld row-major, one column per variable (the m artificials are columns n_lp .. n_lp+m-1 of
@@ -12,7 +13,8 @@
 // simplex_launch.hip are what they were):
 //   U[d.n]   hi - lo per variable, +inf for the artificials;
 //   up[d.n]  1 = the tableau holds U_j - x'_j in place of x'_j (what at_upper_out reports);
-//   flips    bound flips since the start of the solve (both phases).
+//   flips    bound flips since the start of the solve (both phases);
+//   q[ld]    scratch of the dual selector: the quotients of its ratio test.
 // SimplexState::iters counts the pivots plus flips of the running phase, which is what max_iter bounds.
 //
 // A bound flip is done inside the selector (two strided columns, O(m)) and leaves pivot_valid = 0, so the
@@ -20,6 +22,14 @@
 // k_simplex_update; when the leaving variable leaves at its upper bound (a_r < -eps) the staged pivot row is the
 // complemented one (negated over the columns, xB_r = U - xB_r, the leaving variable's own entry +1 again), and since
 // the update writes row r from the staged copy alone, row r of the tableau itself need not be touched first.
+//
+// The re-solve from a basis (tests/ref/bounded_resolve_ref.c) has no artificial columns: d.n = n_lp, the basis is
+// installed by lp_simplex_upload's crash.  k_simplex_classify_bounded picks its loop; the dual loop is
+// k_simplex_select_dual_bounded + k_simplex_update per pivot.  There the complement happens BEFORE the ratio test (a
+// basic variable above its upper bound is held as U - x, which is below 0, and leaves at that bound), and again only
+// the staged pivot row carries it.
+//
+// Plain C++ and vector stores only: no inline assembly and no scalar-memory writes in this file.
 #include "device_select.hpp"
 #include "lp_internal.hpp"
 #include "simplex_problem.hpp"
@@ -152,6 +162,130 @@ __global__ __launch_bounds__(1024) void k_simplex_select_bounded(SimplexDev d, B
     }
 }
 
+// ---------------------------------------------------------------------------
+// The bounded DUAL selector (step 6 of bounded_resolve_ref.c).  Both scans run on all 1024 threads through
+// lpdev::block_chain_select, which replays the reference's sequential EPS-hysteresis chain exactly.
+//   leaving:  v_t = xB_t if xB_t < -eps, else U_N(t) - xB_t if that is < -eps and U is finite, else ineligible;
+//             r = the chain (min) over v_t in position order; none: optimal.  xB is read once, one row per thread,
+//             into LDS; v_t goes to LDS too (the chain's near-tie replay reads it there);
+//   complement: r violated above: row r is taken negated over the n columns with xB_r = U - xB_r, and up[N(r)]
+//             toggles, whether or not an entering column is found;
+//   entering: e = the chain (min) over d_j / a_j (max) or -d_j / a_j (min) of the non-basic j with a_j < -eps, a_j
+//             the entry of the (complemented) row r, in index order; the quotients go to bd.q.  None: infeasible;
+//   staging:  lcol, prow, basis, nonbasic, iters, enter, leave, pivot_valid as k_simplex_select_dual; prow is the
+//             complemented row with the leaving variable's own entry +1 again.
+// LDS: v[m+2] (then the entering column u[m+1]), xB[m], the chain scratch, 2 ints.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_simplex_select_dual_bounded(SimplexDev d, BoundedLargeDev bd) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_v = s_dyn;                     // m + 2: v_t, afterwards column e
+    double* s_x = s_dyn + (d.m + 2);         // m (+ 2 of padding): xB
+    lpdev::BlockChainScratch* sc = reinterpret_cast<lpdev::BlockChainScratch*>(s_dyn + 2 * (d.m + 2));
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // leaving position
+    double best;
+    auto violation = [&](int t) {
+        const double xb = d.T[(size_t)t * ld + n], u = bd.U[d.basis[t]];
+        s_x[t] = xb;
+        return (xb < -eps) ? xb : (u < INFINITY && u - xb < -eps) ? u - xb : INFINITY;
+    };
+    const int r = lpdev::block_chain_select<false, true>(m, eps, best, violation, s_v, sc);
+    if (r < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // (every thread reads basis[r] and nonbasic[] before the barriers below; thread 0 writes them after the last)
+    const int old = d.basis[r];
+    const bool comp = !(s_x[r] < -eps);   // violated above: the complement of N(r) is what is below 0
+    const double uold = bd.U[old];
+    // entering column
+    const double* trow = d.T + (size_t)r * ld;
+    const double* drow = d.T + (size_t)m * ld;
+    const bool maxi = d.maximize != 0;
+    auto quotient = [&](int j) {
+        const double t = trow[j], a = comp ? -t : t;
+        if (!(d.nonbasic[j] != 0 && a < -eps)) return (double)INFINITY;
+        return maxi ? drow[j] / a : -drow[j] / a;
+    };
+    const int e = lpdev::block_chain_select<false, true>(n, eps, best, quotient, bd.q, sc);
+    if (e < 0) {   // row r sums non-negative terms to a negative right-hand side
+        if (tid == 0) {
+            if (comp) bd.up[old] ^= 1;
+            st->status = LP_INFEASIBLE;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // stage the pivot on (r, e); column e of the complemented row r changes sign with it
+    for (int i = tid; i <= m; i += blockDim.x) s_v[i] = d.T[(size_t)i * ld + e];
+    __syncthreads();
+    const double ur = comp ? -s_v[r] : s_v[r];
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_v[i] / ur;
+    for (int j = tid; j < ld; j += blockDim.x) {
+        double v = trow[j];
+        if (comp) v = (j < n) ? -v : (j == n) ? uold - v : v;
+        if (j == old) v = 1.0;   // the leaving variable's own column: the unit column again (a no-op without comp)
+        d.prow[j] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (comp) bd.up[old] ^= 1;
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+// Which loop lp_simplex_bounded_resolve_large runs: the bounded form of k_simplex_classify.  st->pad0 = bit 0 some
+// basis position violated (xB_t < -eps, or U_N(t) finite and U_N(t) - xB_t < -eps), bit 1 dual infeasible (some
+// non-basic d_j > eps for max, d_j < -eps for min).  One workgroup.
+__global__ __launch_bounds__(1024) void k_simplex_classify_bounded(SimplexDev d, BoundedLargeDev bd, double eps) {
+    const int tid = threadIdx.x, m = d.m, n = d.n, ld = d.ld;
+    int pinf = 0, dinf = 0;
+    for (int t = tid; t < m; t += blockDim.x) {
+        const double xb = d.T[(size_t)t * ld + n], u = bd.U[d.basis[t]];
+        if (xb < -eps || (u < INFINITY && u - xb < -eps)) pinf = 1;
+    }
+    const double* drow = d.T + (size_t)m * ld;
+    for (int j = tid; j < n; j += blockDim.x)
+        if (d.nonbasic[j] && (d.maximize ? (drow[j] > eps) : (drow[j] < -eps))) dinf = 1;
+    pinf = __syncthreads_or(pinf);
+    dinf = __syncthreads_or(dinf);
+    if (tid == 0) d.state->pad0 = (pinf ? 1 : 0) | (dinf ? 2 : 0);
+}
+
+size_t select_dual_bounded_lds_bytes(const lp_simplex_problem* p) {
+    return sizeof(double) * 2 * (size_t)(p->dev.m + 2) + sizeof(lpdev::BlockChainScratch);
+}
+
 size_t select_bounded_lds_bytes(const lp_simplex_problem* p) {
     return sizeof(double) * (2 * (size_t)(p->dev.m + 2) + 2) + 16;
 }
@@ -169,6 +303,34 @@ int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int
     const size_t shm = select_bounded_lds_bytes(p);
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(k_simplex_select_bounded, 1, 1024, shm, p->ctx->stream, p->dev, bd);
+        lp_simplex_launch_update(p);
+    }
+    return 2 * batch;
+}
+
+int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags) {
+    lp_context* ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_simplex_classify_bounded, 1, 1024, 0, s, p->dev, bd, eps);
+    LP_HIP(ctx, hipMemcpyAsync(p->h_state, p->dev.state, sizeof(SimplexState), hipMemcpyDeviceToHost, s));
+    LP_HIP(ctx, hipStreamSynchronize(s));
+    LP_HIP(ctx, hipGetLastError());
+    *flags = p->h_state->pad0;
+    return LP_OPTIMAL;
+}
+
+int lp_bounded_dual_prepare(lp_simplex_problem* p) {
+    const size_t shm = select_dual_bounded_lds_bytes(p);
+    if (shm > 156 * 1024)
+        LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_large: m too large for the dual selector's LDS");
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_dual_bounded), shm));
+    return LP_OPTIMAL;
+}
+
+int lp_bounded_dual_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch) {
+    const size_t shm = select_dual_bounded_lds_bytes(p);
+    for (int k = 0; k < batch; ++k) {
+        hipLaunchKernelGGL(k_simplex_select_dual_bounded, 1, 1024, shm, p->ctx->stream, p->dev, bd);
         lp_simplex_launch_update(p);
     }
     return 2 * batch;

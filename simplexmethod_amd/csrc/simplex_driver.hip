@@ -120,11 +120,14 @@ int run_dual(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* 
 
 // One phase of lp_simplex_bounded_large: the bounded selector + rank-1 update pair per iteration, polled as
 // run_launch.  *iters = the pivots plus flips of the phase, *flips = the flips since the start of the solve.
+// dual: the bounded dual selector in its place (lp_simplex_bounded_resolve_large), polled as run_dual.
 int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int max_iter, int* iters,
-                      int* flips) {
+                      int* flips, bool dual = false) {
     lp_context* ctx = p->ctx;
     int launches = lp_launch_begin(p, eps, max_iter);
-    int rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return lp_bounded_large_queue(p, bd, batch); });
+    int rc = poll_batches(p, 16, 256, &launches, [&](int batch) {
+        return dual ? lp_bounded_dual_queue(p, bd, batch) : lp_bounded_large_queue(p, bd, batch);
+    });
     if (rc) return rc;
     rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
     if (rc) return rc;
@@ -193,6 +196,75 @@ int drive_out_artificials(lp_simplex_problem* p, const std::string& prefix, cons
 // After a positive status: the basis reached, as the one-LP-per-workgroup kernels report it
 int download_basis(lp_simplex_problem* p, int* N) {
     return lp_simplex_download(p, nullptr, N, nullptr, nullptr, nullptr, 0, nullptr);
+}
+
+// ---- the pieces lp_simplex_bounded_large and lp_simplex_bounded_resolve_large share
+
+// lo finite, hi not NaN
+int check_bounds(lp_context* ctx, const char* who, const double* lo, const double* hi, int n) {
+    for (int j = 0; j < n; ++j) {
+        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
+        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
+    }
+    return LP_OPTIMAL;
+}
+
+// Any hi_j < lo_j: LP_INFEASIBLE with nothing launched
+int check_crossed(lp_context* ctx, const char* who, const double* lo, const double* hi, int n) {
+    for (int j = 0; j < n; ++j)
+        if (hi[j] < lo[j]) LP_FAIL(ctx, LP_INFEASIBLE, std::string(who) + ": some hi_j < lo_j");
+    return LP_OPTIMAL;
+}
+
+// The shift chain: b1_i <- fma(-A_ij, w_j, b1_i) over the columns with take(j), per row in ascending j (column by
+// column: A is column-major)
+template <class Take>
+void shift_rhs(const double* A, int m, int n, const double* w, Take take, double* b1) {
+    for (int j = 0; j < n; ++j) {
+        if (!take(j)) continue;
+        const double* src = A + (size_t)j * m;
+        for (int i = 0; i < m; ++i) b1[i] = std::fma(-src[i], w[j], b1[i]);
+    }
+}
+
+// The bound state beside the tableau of p: U (cols entries), the flags (up null: none set), the flip counter and the
+// dual selector's scratch.  buf must be freed before the problem (hipFree waits for the queued kernels).
+int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLargeDev& bd, const double* U,
+                        const int* up, int cols) {
+    lp_context* ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
+        bd.U = cv.take<double>(sizeof(double) * (size_t)cols);
+        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
+        bd.up = cv.take<int>(sizeof(int) * (size_t)cols);
+        bd.flips = cv.take<int>(sizeof(int));
+    }));
+    LP_HIP(ctx, hipMemcpyAsync(bd.U, U, sizeof(double) * (size_t)cols, hipMemcpyHostToDevice, s));
+    if (up)
+        LP_HIP(ctx, hipMemcpyAsync(bd.up, up, sizeof(int) * (size_t)cols, hipMemcpyHostToDevice, s));
+    else
+        LP_HIP(ctx, hipMemsetAsync(bd.up, 0, sizeof(int) * (size_t)cols, s));
+    LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
+    return LP_OPTIMAL;
+}
+
+// Step 9 of bounded_ref.c: for LP_OPTIMAL un-complement and un-shift v (n values, overwritten), the objective in index
+// order, x_out (n_orig) and *obj_out; the basis and the flags for every status.
+void bounded_large_outputs(int rc, int m, int n, int n_orig, const double* c, const double* lo, const double* U,
+                           const int* up, const int* N, double* v, double* x_out, int* basis_out, int* at_upper_out,
+                           double* obj_out) {
+    if (rc == LP_OPTIMAL) {
+        for (int j = 0; j < n; ++j) {
+            const double w = up[j] ? U[j] - v[j] : v[j];
+            v[j] = lo[j] == 0.0 ? w : lo[j] + w;
+        }
+        double z = 0.0;
+        for (int j = 0; j < n; ++j) z += c[j] * v[j];
+        for (int j = 0; j < n_orig; ++j) x_out[j] = v[j];
+        *obj_out = z;
+    }
+    std::memcpy(basis_out, N, sizeof(int) * (size_t)m);
+    for (int j = 0; j < n; ++j) at_upper_out[j] = up[j];
 }
 
 int run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
@@ -823,17 +895,15 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
     if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
-    for (int j = 0; j < n; ++j) {
-        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
-        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
-    }
+    int rc = check_bounds(ctx, who, lo, hi, n);
+    if (rc) return rc;
     const int na = n + m;
     int it[4] = {0, 0, 0, 0};
     for (int t = 0; t < m; ++t) basis_out[t] = n + t;
     for (int j = 0; j < n; ++j) at_upper_out[j] = 0;
     std::memcpy(iters_out, it, sizeof(it));
-    for (int j = 0; j < n; ++j)
-        if (hi[j] < lo[j]) LP_FAIL(ctx, LP_INFEASIBLE, std::string(who) + ": some hi_j < lo_j");
+    rc = check_crossed(ctx, who, lo, hi, n);
+    if (rc) return rc;
 
     // shift x = lo + x' (b' accumulated in ascending j, lo_j == 0 skipped), U = hi - lo, then make_b_nonneg and
     // createAuxiliaryProblem on [A | b'] as lp_simplex_two_phase_ex
@@ -842,32 +912,21 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
     for (int j = 0; j < n; ++j) U[(size_t)j] = hi[j] - lo[j];
     for (int k = n; k < na; ++k) U[(size_t)k] = INFINITY;
     for (int i = 0; i < m; ++i) b1[(size_t)i] = b[i];
-    for (int j = 0; j < n; ++j) {   // (column by column: A is column-major; per row the order is ascending j)
-        if (lo[j] == 0.0) continue;
-        const double* src = A + (size_t)j * m;
-        for (int i = 0; i < m; ++i) b1[(size_t)i] = std::fma(-src[i], lo[j], b1[(size_t)i]);
-    }
+    shift_rhs(A, m, n, lo, [&](int j) { return lo[j] != 0.0; }, b1.data());
     auxiliary_problem(A, m, n, b1.data(), eps, A1.data(), b1.data(), c1.data(), N.data());
 
     lp_simplex_problem* p = nullptr;
-    int rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
+    rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
     if (rc) return rc;
     ProblemOwner owner(p, lp_simplex_free);
     rc = lp_bounded_large_prepare(p);
     if (rc) return rc;
-    // the bound state beside the tableau
+    // the bound state beside the tableau (buf is freed before the problem on every return path)
     hipStream_t s = ctx->stream;
     lp_device_buffer buf;
     BoundedLargeDev bd{};
-    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
-        bd.U = cv.take<double>(sizeof(double) * (size_t)na);
-        bd.up = cv.take<int>(sizeof(int) * (size_t)na);
-        bd.flips = cv.take<int>(sizeof(int));
-    }));
-    LP_HIP(ctx, hipMemcpyAsync(bd.U, U.data(), sizeof(double) * (size_t)na, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemsetAsync(bd.up, 0, sizeof(int) * (size_t)na, s));
-    LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
-    // (buf is freed before the problem on every return path; hipFree waits for the queued kernels)
+    rc = bounded_large_state(p, buf, bd, U.data(), nullptr, na);
+    if (rc) return rc;
     auto download_flags = [&]() { return lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}}); };
 
     // ---- phase I: minimise the sum of the artificials
@@ -905,19 +964,94 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
     }
     (void)hipStreamSynchronize(s);
     if (rc < 0) return rc;
-    if (rc == LP_OPTIMAL) {   // step 9 of the reference: un-complement, un-shift, then the objective in index order
-        for (int j = 0; j < n; ++j) {
-            const double v = xa[(size_t)j];
-            const double w = up[(size_t)j] ? U[(size_t)j] - v : v;
-            xa[(size_t)j] = lo[j] == 0.0 ? w : lo[j] + w;
-        }
-        double z = 0.0;
-        for (int j = 0; j < n; ++j) z += c[j] * xa[(size_t)j];
-        for (int j = 0; j < n_orig; ++j) x_out[j] = xa[(size_t)j];
-        *obj_out = z;
+    bounded_large_outputs(rc, m, n, n_orig, c, lo, U.data(), up.data(), N.data(), xa.data(), x_out, basis_out,
+                          at_upper_out, obj_out);
+    std::memcpy(iters_out, it, sizeof(it));
+    return rc;
+}
+
+// The re-solve of a bounded LP from a basis and flags on the HBM tableau (tests/ref/bounded_resolve_ref.c is the
+// definition): the checks and the set-up arithmetic (shift, the flagged columns held complemented) run here on the
+// host in the reference's order, lp_simplex_upload installs the basis on the (m+1) x (n+1) tableau (no artificial
+// columns), a classification launch picks the loop, and every pivot and flip runs on the GPU: the primal loop is
+// lp_simplex_bounded_large's phase II, the dual loop the selector k_simplex_select_dual_bounded.
+int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                     const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                                     int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
+                                     int* at_upper_out, double* obj_out, int* iters_out) {
+    const char* who = "lp_simplex_bounded_resolve_large";
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi || !basis_in ||
+        !at_upper_in)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    int rc = check_bounds(ctx, who, lo, hi, n);
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j) {
+        if (at_upper_in[j] != 0 && at_upper_in[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
+        if (at_upper_in[j] && hi[j] == INFINITY)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
     }
+    for (int t = 0; t < m; ++t)
+        if (basis_in[t] < 0 || basis_in[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
+    int it[3] = {0, 0, 0};
+    std::vector<int> N(basis_in, basis_in + m), up(at_upper_in, at_upper_in + n);   // (the outputs may be the inputs)
     std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
-    for (int j = 0; j < n; ++j) at_upper_out[j] = up[(size_t)j];
+    std::memcpy(at_upper_out, up.data(), sizeof(int) * (size_t)n);
+    std::memcpy(iters_out, it, sizeof(it));
+    rc = check_crossed(ctx, who, lo, hi, n);
+    if (rc) return rc;
+
+    // steps 2 and 3 of the reference: shift x = lo + x', U = hi - lo, the chain goes on over the flagged columns with
+    // U_j; those columns and their costs change sign
+    std::vector<double> A1(A, A + (size_t)m * n), b1(b, b + m), c1(c, c + n), xa((size_t)n), U((size_t)n);
+    for (int j = 0; j < n; ++j) U[(size_t)j] = hi[j] - lo[j];
+    shift_rhs(A, m, n, lo, [&](int j) { return lo[j] != 0.0; }, b1.data());
+    shift_rhs(A, m, n, U.data(), [&](int j) { return up[(size_t)j] != 0; }, b1.data());
+    for (int j = 0; j < n; ++j) {
+        if (!up[(size_t)j]) continue;
+        double* col = A1.data() + (size_t)j * m;
+        for (int i = 0; i < m; ++i) col[i] = -col[i];
+        c1[(size_t)j] = -c1[(size_t)j];
+    }
+    // step 4: the basis install (n_orig = n: the download below returns every column's value)
+    lp_simplex_problem* p = nullptr;
+    rc = lp_simplex_upload(ctx, A1.data(), m, n, b1.data(), c1.data(), N.data(), maximize, n, &p);
+    if (rc) return rc;
+    ProblemOwner owner(p, lp_simplex_free);
+    if (p->init_status != LP_OPTIMAL)   // LP_SINGULAR: the given basis and flags stay in the outputs
+        LP_FAIL(ctx, p->init_status, std::string(who) + ": the basis matrix is singular");
+    rc = lp_bounded_large_prepare(p);
+    if (rc) return rc;
+    lp_device_buffer buf;   // (freed before the problem on every return path)
+    BoundedLargeDev bd{};
+    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n);
+    if (rc) return rc;
+    // step 5: which loop
+    int flags = 0, iters = 0, flips = 0;
+    rc = lp_bounded_large_classify(p, bd, eps, &flags);
+    if (rc) return rc;
+    if (!(flags & 1)) {   // every basic variable within its bounds: the bounded primal loop
+        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips);
+        if (rc < 0) return rc;
+        it[1] = iters - flips;
+        it[2] = flips;
+    } else if (!(flags & 2)) {   // step 6: the bounded dual loop
+        rc = lp_bounded_dual_prepare(p);
+        if (rc) return rc;
+        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips, true);
+        if (rc < 0) return rc;
+        it[0] = iters;
+    } else {
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
+    }
+    int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
+                              : download_basis(p, N.data());
+    if (rd == LP_OPTIMAL) rd = lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}});
+    if (rd) return rd;
+    bounded_large_outputs(rc, m, n, n_orig, c, lo, U.data(), up.data(), N.data(), xa.data(), x_out, basis_out,
+                          at_upper_out, obj_out);
     std::memcpy(iters_out, it, sizeof(it));
     return rc;
 }

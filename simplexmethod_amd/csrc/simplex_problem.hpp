@@ -135,9 +135,15 @@ struct BoundedLargeDev {
     double* U;    // dev.n: hi - lo, +inf for the artificials
     int* up;      // dev.n: 1 = the column is held complemented
     int* flips;   // bound flips since the start of the solve
+    double* q;    // dev.ld: the quotients of the dual selector's ratio test
 };
 int lp_bounded_large_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, opted in
 int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
+// The re-solve (lp_simplex_bounded_resolve_large).  classify: *flags = bit 0 some basis position outside its bounds,
+// bit 1 dual infeasible (one host sync); the dual path then queues the bounded dual selector + rank-1 update.
+int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags);
+int lp_bounded_dual_prepare(lp_simplex_problem* p);
+int lp_bounded_dual_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
 
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS

@@ -262,6 +262,15 @@ public:
         return boundedRun("Solver::boundedResolve", lo, hi, &from, nullptr, throw_on_failure);
     }
 
+    // The re-solve at any shape boundedSimplexLarge runs (lp_simplex_bounded_resolve_large), normally from its
+    // result: the basis is installed on the tableau in device memory, then the bounded primal or dual loop runs there,
+    // Dantzig's rule; no lp_simplex_bounded_fits limit.  Result and exceptions as boundedResolve(lo, hi, from), and
+    // equal to it where both run.
+    BoundedResult boundedResolveLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                      const BoundedResult& from, bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, nullptr, throw_on_failure, true);
+    }
+
     // The same under a pivot rule (lp_simplex_bounded_resolve_ex): the rule governs the primal loop only; the dual
     // simplex is the same under every rule.
     BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
@@ -607,7 +616,7 @@ private:
     }
 
     // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form;
-    // large (from and rule null): boundedSimplexLarge
+    // large (rule null): boundedSimplexLarge, or with from boundedResolveLarge
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
                              const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
                              bool large = false) const {
@@ -619,7 +628,12 @@ private:
         out.basis.assign((size_t)p.m, -1);
         out.atUpper.assign((size_t)p.n, 0);
         lp_context* ctx = lpgpu::context(_device);
-        if (large)
+        if (large && from)
+            out.status = lp_simplex_bounded_resolve_large(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                          from->basis.data(), from->atUpper.data(), p.maximize, p.no,
+                                                          EPS, MAX_ITER, out.x.data(), out.basis.data(),
+                                                          out.atUpper.data(), &out.objective, out.iterations);
+        else if (large)
             out.status = lp_simplex_bounded_large(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), p.maximize, p.no,
                                                   EPS, MAX_ITER, out.x.data(), out.basis.data(), out.atUpper.data(),
                                                   &out.objective, out.iterations);
