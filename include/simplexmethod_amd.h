@@ -595,10 +595,11 @@ int lp_simplex_bounded_fits(int m, int n);
  *     hi_j < lo_j is LP_INFEASIBLE without an iteration (zero counters, basis n + t, no flag).
  *   - max_iter bounds the pivots plus flips of each phase; iters_out[4] = phase-I pivots, drive-out pivots, phase-II
  *     pivots, bound flips.
- *   - Dantzig's rule only.  Out of scope on this path: Bland's rule and Devex pricing, and the analyses (duals,
- *     ranging, certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The
- *     re-solve from a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is
- *     unchanged and still refuses larger shapes.                                                                 */
+ *   - Dantzig's rule; Bland's rule and Devex pricing at these shapes are lp_simplex_bounded_large_ex (with the _ex
+ *     block below; m <= 9968 under LP_PIVOT_DEVEX).  Out of scope on this path: the analyses (duals, ranging,
+ *     certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The re-solve from
+ *     a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and
+ *     still refuses larger shapes.                                                                               */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 /* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
  * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
@@ -608,8 +609,9 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
  * per pivot.  Arguments, outputs, statuses, refusals and iters_out[3] (dual pivots, primal pivots, bound flips) are
  * lp_simplex_bounded_resolve's with one difference: there is no lp_simplex_bounded_fits limit (the limits are device
  * memory for the tableau, and m <= 9960 for the selectors' LDS).  At a shape that also fits LDS every output equals
- * lp_simplex_bounded_resolve's.  Dantzig's rule only, one LP per call; lp_simplex_bounded_resolve itself is unchanged
- * and still refuses larger shapes.  Every pointer is required.                                                     */
+ * lp_simplex_bounded_resolve's.  Dantzig's rule (Bland's and Devex in the primal loop:
+ * lp_simplex_bounded_resolve_large_ex, with the _ex block below), one LP per call; lp_simplex_bounded_resolve itself
+ * is unchanged and still refuses larger shapes.  Every pointer is required.                                        */
 int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 
 /* ---- Bounded variables: the re-solve from a basis -------------------------------------------------------------
@@ -660,6 +662,20 @@ int lp_simplex_bounded_ex(lp_context* ctx, const double* A, int m, int n, const 
 int lp_simplex_bounded_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule);
 int lp_simplex_bounded_resolve_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule);
 int lp_simplex_bounded_resolve_batched_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule);
+/* The same beyond one workgroup's LDS: lp_simplex_bounded_large and lp_simplex_bounded_resolve_large under a pivot
+ * rule, one selector per rule on the tableau in HBM, each followed by the same rank-1 update launch.
+ * LP_PIVOT_DANTZIG launches what the entry without _ex launches and equals it bit for bit; the entries without _ex
+ * are these with LP_PIVOT_DANTZIG.  Any other value than the three rules is LP_BAD_ARG before anything else is looked
+ * at, and no output is written.  The definitions are tests/ref/bounded_rules_ref.c and bounded_resolve_rules_ref.c, and
+ * every output equals them bit for bit; at a shape where lp_simplex_bounded_rule_fits holds it also equals
+ * lp_simplex_bounded_ex's / lp_simplex_bounded_resolve_ex's.  Devex keeps one weight per tableau column (the phase-I
+ * artificials included) in device memory, all 1.0 when each primal loop starts.  There is no
+ * lp_simplex_bounded_rule_fits limit; the limits are device memory for the tableau and the selector's LDS:
+ * m <= 9980 under LP_PIVOT_DANTZIG and LP_PIVOT_BLAND, m <= 9968 under LP_PIVOT_DEVEX (its pricing keeps sixteen wave
+ * results more), and m <= 9960 in the re-solve's dual branch under every rule.  Bland's rule is the one entry that
+ * terminates on a cycling boxed LP at these shapes; it is slow everywhere else.                                       */
+int lp_simplex_bounded_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule);
+int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule);
 /* Host call, no context.  1: the shape runs under pivot_rule: lp_simplex_bounded_fits(m, n) for LP_PIVOT_DANTZIG and
  * LP_PIVOT_BLAND; under LP_PIVOT_DEVEX the LDS carve with n more doubles, the weights, must still fit 160 KiB.  0
  * otherwise, and for an unknown rule.                                                                                */

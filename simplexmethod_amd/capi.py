@@ -165,6 +165,10 @@ SIGNATURES = {
                                                         _ip, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
                                                         _ip, _ip, C.c_int]),
     "lp_simplex_bounded_rule_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "lp_simplex_bounded_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+                                              C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
+    "lp_simplex_bounded_resolve_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                      C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
     "lp_mip_bounded_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int, _ip,
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                        _ip, _ip]),
@@ -762,9 +766,12 @@ class Context:
                            _i(it), _i(st))
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
-    def bounded_large(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER):
+    def bounded_large(self, A, b, c, lo, hi, maximize=False, n_orig=None, eps=EPS, max_iter=MAX_ITER,
+                      pivot_rule=None):
         """lp_simplex_bounded_large: the LP of bounded() on the tableau in HBM, at any shape two_phase() runs (no
-        bounded_fits limit); Dantzig's rule.  Returns the dict of bounded(), equal to it where both run."""
+        bounded_fits limit).  pivot_rule as in bounded() (None: the entry without a rule, which is Dantzig's; else
+        lp_simplex_bounded_large_ex, no bounded_rule_fits limit either).  Returns the dict of bounded(), equal to it
+        under the same rule where both run."""
         p = pack_lp(A, b, c, lo=lo, hi=hi)
         m, n, Af, b, c, lo, hi = p.m, p.n, p.A, p.b, p.c, p.lo, p.hi
         n_orig = n if n_orig is None else int(n_orig)
@@ -773,16 +780,17 @@ class Context:
         up = np.zeros(n, dtype=np.int32)
         obj = np.full(1, np.nan)
         it = np.zeros(4, dtype=np.int32)
-        rc = self.check(self.lib.lp_simplex_bounded_large(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
-                                                          int(maximize), n_orig, float(eps), int(max_iter), _d(x),
-                                                          _i(bo), _i(up), _d(obj), _i(it)))
+        rc = self._bounded_call("lp_simplex_bounded_large", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c), _d(lo),
+                                _d(hi), int(maximize), n_orig, float(eps), int(max_iter), _d(x), _i(bo), _i(up),
+                                _d(obj), _i(it))
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                              max_iter=MAX_ITER):
+                              max_iter=MAX_ITER, pivot_rule=None):
         """lp_simplex_bounded_resolve_large: the re-solve of bounded_resolve() on the tableau in HBM, at any shape
-        bounded_large() runs (no bounded_fits limit); Dantzig's rule.  Returns the dict of bounded_resolve(), equal to
-        it where both run; refusals as there."""
+        bounded_large() runs (no bounded_fits limit).  pivot_rule as in bounded_resolve() (None: the entry without a
+        rule; else lp_simplex_bounded_resolve_large_ex): it governs the primal loop only.  Returns the dict of
+        bounded_resolve(), equal to it under the same rule where both run; refusals as there."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
@@ -791,9 +799,9 @@ class Context:
         up = np.zeros(n, dtype=np.int32)
         obj = np.full(1, np.nan)
         it = np.zeros(3, dtype=np.int32)
-        rc = self.check(self.lib.lp_simplex_bounded_resolve_large(
-            self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
-            float(eps), int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it)))
+        rc = self._bounded_call("lp_simplex_bounded_resolve_large", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c),
+                                _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps),
+                                int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it))
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_fits(self, m, n):

@@ -14,7 +14,8 @@
 //   U[d.n]   hi - lo per variable, +inf for the artificials;
 //   up[d.n]  1 = the tableau holds U_j - x'_j in place of x'_j (what at_upper_out reports);
 //   flips    bound flips since the start of the solve (both phases);
-//   q[ld]    scratch of the dual selector: the quotients of its ratio test.
+//   q[ld]    scratch of the dual selector: the quotients of its ratio test;
+//   w[d.n]   the Devex weights (LP_PIVOT_DEVEX only; the other selectors never touch them).
 // SimplexState::iters counts the pivots plus flips of the running phase, which is what max_iter bounds.
 //
 // A bound flip is done inside the selector (two strided columns, O(m)) and leaves pivot_valid = 0, so the
@@ -163,6 +164,294 @@ __global__ __launch_bounds__(1024) void k_simplex_select_bounded(SimplexDev d, B
 }
 
 // ---------------------------------------------------------------------------
+// The bounded selector under a pivot rule (tests/ref/bounded_rules_ref.c is the definition; lp_simplex_bounded_large_ex
+// and the primal branch of lp_simplex_bounded_resolve_large_ex).  Launch shape, staging contract and the
+// flip-in-selector design are k_simplex_select_bounded's: a flip leaves pivot_valid = 0, a pivot whose leaving variable
+// leaves at its upper bound is staged complemented, and up, flips and iters are kept the same way.  Every loop is
+// strided over the 1024 threads (m may exceed them, n may exceed one pricing step).
+//
+// BLAND (k_simplex_select_bounded_bland)
+//   entering: the smallest non-basic j with d_j beyond eps, the first-hit scan of k_simplex_select_bland (in phase II
+//             the artificial columns carry no non-basic flag);
+//   rows:     v_t = xB/a for a > eps, (xB - U)/a for a < -eps with U of basis[t] finite, NaN otherwise (neither the
+//             minimum nor the tie test takes a NaN);
+//   step:     theta* = min(min_t v_t, U_e), an exact minimum without eps hysteresis; not below +inf: LP_UNBOUNDED;
+//   blocking: the rows with v_t <= theta* + eps keyed by basis[t], and the entering variable keyed by e when
+//             U_e <= theta* + eps.  The keys are distinct variable indices, so the smallest key is one candidate:
+//             e means the bound flip, a row the pivot (complemented first when a_r < -eps).
+//
+// DEVEX (k_simplex_select_bounded_devex)
+//   weights:  bd.w, one per tableau column (d.n of them, the artificial columns included), all exactly 1.0 when a
+//             primal loop starts (the host resets them on the stream); the drive-out never touches them;
+//   entering: the arg-max of (d_j * d_j) / w_j over the eligible non-basic columns by the whole workgroup, exact ties
+//             to the smallest j, a NaN score never taken: the pricing of k_simplex_select_devex;
+//   ratio test, flip decision and complement: k_simplex_select_bounded's.  A flip leaves every weight alone;
+//   update:   inside the loop that stages prow, from the STAGED row (after the complement, if any), the old
+//             u_r (after the complement) and the old w_e: w_j = fmax(w_j, (t * t) * w_e), t = prow_j / u_r, for
+//             every j < d.n other than e and the leaving variable v = basis[r]; then w_v = fmax(w_e / (u_r * u_r), 1.0).
+//             No multiply feeds an add in the score or the weights, so nothing there can be fused.
+//   The reference keeps a weight per slot of its condensed tableau, and the slot of the entering variable passes to
+//   the leaving one: on the full tableau that is the weight of the leaving variable's column, w_v.  A basic column
+//   j != v holds +0 or -0 in row r; the complement turns that into -0 or +0, still a zero, so t * t = 0 and fmax
+//   keeps w_j (and drops the NaN of 0 * inf).  Column v itself holds +1 in row r (-1 before the staging puts the unit
+//   entry back in a complemented row) and is skipped.  No weight of a basic column is ever read: a column's weight
+//   is rewritten when it leaves the basis, before it can be priced.
+// LDS: k_simplex_select_bounded's; Devex adds the sixteen wave results (16 doubles + 16 ints).
+// ---------------------------------------------------------------------------
+template <int RULE>
+__device__ __forceinline__ void select_bounded_rule(const SimplexDev& d, const BoundedLargeDev& bd) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_u = s_dyn;
+    double* s_ratio = s_dyn + (d.m + 2);
+    double& s_theta = s_dyn[2 * (d.m + 2)];
+    int* s_int = reinterpret_cast<int*>(s_dyn + 2 * (d.m + 2) + 2);
+    int& s_enter = s_int[0];
+    int& s_leave = s_int[1];   // Bland: -2 = the entering variable blocks first (bound flip)
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {   // pivots plus flips of this phase
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    const double* drow = d.T + (size_t)m * ld;
+    if (RULE == LP_PIVOT_BLAND) {
+        if (tid < 64) {
+            constexpr int K = 16;
+            int e = INT_MAX;
+            for (int base = 0; base < n && e == INT_MAX; base += 64 * K) {
+                int first = INT_MAX;
+#pragma unroll
+                for (int k = K - 1; k >= 0; --k) {   // (descending: the lane keeps its smallest hit)
+                    const int j = base + k * 64 + tid;
+                    if (j < n && d.nonbasic[j]) {
+                        const double v = drow[j];
+                        if (d.maximize ? (v > eps) : (v < -eps)) first = j;
+                    }
+                }
+                e = lpdev::wave_min_i32(first);
+            }
+            if (tid == 0) s_enter = e == INT_MAX ? -1 : e;
+        }
+    } else {
+        double* s_score = s_dyn + 2 * (d.m + 2) + 4;
+        int* s_col = reinterpret_cast<int*>(s_score + 16);
+        double best = -1.0;
+        int col = INT_MAX;
+        constexpr int K = 4;   // columns per thread and step: their loads are in flight together
+        for (int j0 = tid; j0 < n; j0 += K * (int)blockDim.x) {
+            double v[K], wj[K];
+            bool nb[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int j = j0 + k * (int)blockDim.x;
+                nb[k] = j < n && d.nonbasic[j] != 0;
+                v[k] = j < n ? drow[j] : 0.0;
+                wj[k] = j < n ? bd.w[j] : 1.0;
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const double s = (v[k] * v[k]) / wj[k];
+                if (nb[k] && (d.maximize ? (v[k] > eps) : (v[k] < -eps)) && s > best) {
+                    best = s;  // j ascending per thread: strict > keeps the smallest index
+                    col = j0 + k * (int)blockDim.x;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double ob = __shfl_xor(best, off, 64);
+            const int oc = __shfl_xor(col, off, 64);
+            if (ob > best || (ob == best && oc < col)) {
+                best = ob;
+                col = oc;
+            }
+        }
+        if ((tid & 63) == 0) {
+            s_score[tid >> 6] = best;
+            s_col[tid >> 6] = col;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
+                if (s_score[q] > best || (s_score[q] == best && s_col[q] < col)) {
+                    best = s_score[q];
+                    col = s_col[q];
+                }
+            s_enter = col == INT_MAX ? -1 : col;
+        }
+    }
+    __syncthreads();
+    const int e = s_enter;
+    if (e < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // column e and the row values; a row that is no candidate holds NaN (Bland) or +inf (the chain of Devex)
+    const double none = RULE == LP_PIVOT_BLAND ? NAN : INFINITY;
+    for (int i = tid; i <= m; i += blockDim.x) {
+        const double a = d.T[(size_t)i * ld + e];
+        s_u[i] = a;
+        if (i < m) {
+            const double xb = d.T[(size_t)i * ld + n], u = bd.U[d.basis[i]];
+            s_ratio[i] = (a > eps) ? xb / a : (a < -eps && u < INFINITY) ? (xb - u) / a : none;
+        }
+    }
+    __syncthreads();
+    const double ue = bd.U[e];
+    if (tid < 64) {
+        if (RULE == LP_PIVOT_BLAND) {
+            double lmin = ue;
+            for (int i = tid; i < m; i += 64) {
+                const double v = s_ratio[i];
+                if (v < lmin) lmin = v;
+            }
+            const double theta = lpdev::wave_ext_f64<false>(lmin);
+            const double thr = theta + eps;
+            int key = INT_MAX, pos = -1;
+            if (tid == 0 && ue <= thr) {
+                key = e;
+                pos = -2;
+            }
+            for (int i = tid; i < m; i += 64)
+                if (s_ratio[i] <= thr && d.basis[i] < key) {
+                    key = d.basis[i];
+                    pos = i;
+                }
+            const int kmin = lpdev::wave_min_i32(key);
+            int r = -1;
+            if (kmin != INT_MAX) r = __builtin_amdgcn_readlane(pos, (int)__builtin_ctzll(__ballot(key == kmin)));
+            if (tid == 0) {
+                s_leave = r;
+                s_theta = theta;
+            }
+        } else {
+            double theta;
+            auto load = [&](int i, bool& ok) {
+                ok = true;  // ineligible rows hold +inf, which the < scan never takes
+                return s_ratio[i];
+            };
+            const int r = lpdev::wave_chain_select<false>(m, eps, theta, load);
+            if (tid == 0) {
+                s_leave = r;
+                s_theta = theta;
+            }
+        }
+    }
+    __syncthreads();
+    const int r = s_leave;
+    bool flip;
+    if (RULE == LP_PIVOT_BLAND) {
+        if (!(s_theta < INFINITY) || r == -1) {   // (a finite theta* has a candidate at it: r == -1 cannot happen)
+            if (tid == 0) {
+                st->status = LP_UNBOUNDED;
+                st->pivot_valid = 0;
+            }
+            return;
+        }
+        flip = r == -2;
+    } else {
+        if (r < 0 && !(ue < INFINITY)) {
+            if (tid == 0) {
+                st->status = LP_UNBOUNDED;
+                st->pivot_valid = 0;
+            }
+            return;
+        }
+        flip = r < 0 || ue <= s_theta;
+    }
+    if (flip) {   // bound flip: e goes to its other bound, the basis (and every weight) stays
+        for (int i = tid; i <= m; i += blockDim.x) {
+            const size_t row = (size_t)i * ld;
+            d.T[row + n] = fma(-ue, s_u[i], d.T[row + n]);
+            d.T[row + e] = -s_u[i];
+        }
+        if (tid == 0) {
+            bd.up[e] ^= 1;
+            *bd.flips += 1;
+            st->iters += 1;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // pivot on row r; a_r < -eps: the leaving variable leaves at its upper bound and is complemented first
+    const int old = d.basis[r];   // (every thread reads it, and Devex's old w_e, before the barrier below; thread 0
+    const bool comp = s_u[r] < -eps;   //  writes basis[r] and w_old after it, and the loop writes neither weight)
+    const double ur = comp ? -s_u[r] : s_u[r];
+    const double we = RULE == LP_PIVOT_DEVEX ? bd.w[e] : 1.0;
+    for (int i = tid; i <= m; i += blockDim.x)
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_u[i] / ur;
+    const double* trow = d.T + (size_t)r * ld;
+    const double uold = bd.U[old];
+    auto staged = [&](int j, double v) {
+        if (comp) v = (j < n) ? -v : (j == n) ? uold - v : v;
+        return (j == old) ? 1.0 : v;   // the leaving variable's own column: the unit column again
+    };
+    if (RULE == LP_PIVOT_DEVEX) {
+        for (int j0 = tid; j0 < ld; j0 += 4 * (int)blockDim.x) {   // (four columns per step, as in the pricing)
+            double a[4], wj[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = j0 + k * (int)blockDim.x;
+                a[k] = j < ld ? trow[j] : 0.0;
+                wj[k] = j < n ? bd.w[j] : 1.0;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = j0 + k * (int)blockDim.x;
+                if (j >= ld) continue;
+                const double v = staged(j, a[k]);
+                d.prow[j] = v;
+                if (j < n && j != e && j != old) {
+                    const double t = v / ur;
+                    bd.w[j] = fmax(wj[k], (t * t) * we);
+                }
+            }
+        }
+    } else {
+        for (int j = tid; j < ld; j += blockDim.x) d.prow[j] = staged(j, trow[j]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (RULE == LP_PIVOT_DEVEX) bd.w[old] = fmax(we / (ur * ur), 1.0);
+        if (comp) bd.up[old] ^= 1;
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        st->iters += 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_simplex_select_bounded_bland(SimplexDev d, BoundedLargeDev bd) {
+    select_bounded_rule<LP_PIVOT_BLAND>(d, bd);
+}
+
+__global__ __launch_bounds__(1024) void k_simplex_select_bounded_devex(SimplexDev d, BoundedLargeDev bd) {
+    select_bounded_rule<LP_PIVOT_DEVEX>(d, bd);
+}
+
+// All d.n Devex weights back to exactly 1.0: queued at the start of every primal loop under LP_PIVOT_DEVEX
+__global__ __launch_bounds__(256) void k_bounded_reset_weights(double* w, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) w[j] = 1.0;
+}
+
+// ---------------------------------------------------------------------------
 // The bounded DUAL selector (step 6 of bounded_resolve_ref.c).  Both scans run on all 1024 threads through
 // lpdev::block_chain_select, which replays the reference's sequential EPS-hysteresis chain exactly.
 //   leaving:  v_t = xB_t if xB_t < -eps, else U_N(t) - xB_t if that is < -eps and U is finite, else ineligible;
@@ -286,23 +575,37 @@ size_t select_dual_bounded_lds_bytes(const lp_simplex_problem* p) {
     return sizeof(double) * 2 * (size_t)(p->dev.m + 2) + sizeof(lpdev::BlockChainScratch);
 }
 
-size_t select_bounded_lds_bytes(const lp_simplex_problem* p) {
-    return sizeof(double) * (2 * (size_t)(p->dev.m + 2) + 2) + 16;
+// (Devex: the sixteen wave results of the pricing, 16 doubles + 16 ints, behind the two ints)
+size_t select_bounded_lds_bytes(const lp_simplex_problem* p, int rule) {
+    return sizeof(double) * (2 * (size_t)(p->dev.m + 2) + 2) + 16 + (rule == LP_PIVOT_DEVEX ? 16 * 8 + 16 * 4 : 0);
+}
+
+using BoundedSelector = void (*)(SimplexDev, BoundedLargeDev);
+BoundedSelector bounded_selector(int rule) {
+    return rule == LP_PIVOT_BLAND   ? k_simplex_select_bounded_bland
+           : rule == LP_PIVOT_DEVEX ? k_simplex_select_bounded_devex
+                                    : k_simplex_select_bounded;
 }
 
 }  // namespace
 
-int lp_bounded_large_prepare(lp_simplex_problem* p) {
-    const size_t shm = select_bounded_lds_bytes(p);
+int lp_bounded_large_prepare(lp_simplex_problem* p, int rule) {
+    const size_t shm = select_bounded_lds_bytes(p, rule);
     if (shm > 156 * 1024) LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_large: m too large for the selector's LDS");
-    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_bounded), shm));
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(bounded_selector(rule)), shm));
     return LP_OPTIMAL;
 }
 
-int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch) {
-    const size_t shm = select_bounded_lds_bytes(p);
+void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd) {
+    const int n = p->dev.n;
+    hipLaunchKernelGGL(k_bounded_reset_weights, (n + 255) / 256, 256, 0, p->ctx->stream, bd.w, n);
+}
+
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule) {
+    const size_t shm = select_bounded_lds_bytes(p, rule);
+    const BoundedSelector select = bounded_selector(rule);
     for (int k = 0; k < batch; ++k) {
-        hipLaunchKernelGGL(k_simplex_select_bounded, 1, 1024, shm, p->ctx->stream, p->dev, bd);
+        hipLaunchKernelGGL(select, 1, 1024, shm, p->ctx->stream, p->dev, bd);
         lp_simplex_launch_update(p);
     }
     return 2 * batch;

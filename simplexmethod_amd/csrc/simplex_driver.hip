@@ -120,13 +120,18 @@ int run_dual(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* 
 
 // One phase of lp_simplex_bounded_large: the bounded selector + rank-1 update pair per iteration, polled as
 // run_launch.  *iters = the pivots plus flips of the phase, *flips = the flips since the start of the solve.
-// dual: the bounded dual selector in its place (lp_simplex_bounded_resolve_large), polled as run_dual.
-int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int max_iter, int* iters,
+// rule: the primal selector (under LP_PIVOT_DEVEX the weights are reset on the stream first).  dual: the bounded dual
+// selector in its place (lp_simplex_bounded_resolve_large; no rule reaches it), polled as run_dual.
+int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule, double eps, int max_iter, int* iters,
                       int* flips, bool dual = false) {
     lp_context* ctx = p->ctx;
     int launches = lp_launch_begin(p, eps, max_iter);
+    if (!dual && rule == LP_PIVOT_DEVEX) {
+        lp_bounded_large_reset_weights(p, bd);
+        ++launches;
+    }
     int rc = poll_batches(p, 16, 256, &launches, [&](int batch) {
-        return dual ? lp_bounded_dual_queue(p, bd, batch) : lp_bounded_large_queue(p, bd, batch);
+        return dual ? lp_bounded_dual_queue(p, bd, batch) : lp_bounded_large_queue(p, bd, batch, rule);
     });
     if (rc) return rc;
     rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
@@ -227,15 +232,17 @@ void shift_rhs(const double* A, int m, int n, const double* w, Take take, double
     }
 }
 
-// The bound state beside the tableau of p: U (cols entries), the flags (up null: none set), the flip counter and the
-// dual selector's scratch.  buf must be freed before the problem (hipFree waits for the queued kernels).
+// The bound state beside the tableau of p: U (cols entries), the flags (up null: none set), the flip counter, the
+// dual selector's scratch and, under LP_PIVOT_DEVEX, the weights (run_bounded_phase sets them).  buf must be freed
+// before the problem (hipFree waits for the queued kernels).
 int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLargeDev& bd, const double* U,
-                        const int* up, int cols) {
+                        const int* up, int cols, int rule) {
     lp_context* ctx = p->ctx;
     hipStream_t s = ctx->stream;
     LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
         bd.U = cv.take<double>(sizeof(double) * (size_t)cols);
         bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
+        bd.w = rule == LP_PIVOT_DEVEX ? cv.take<double>(sizeof(double) * (size_t)cols) : nullptr;
         bd.up = cv.take<int>(sizeof(int) * (size_t)cols);
         bd.flips = cv.take<int>(sizeof(int));
     }));
@@ -889,8 +896,19 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                              const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
                              double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
+    return lp_simplex_bounded_large_ex(ctx, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out,
+                                       at_upper_out, obj_out, iters_out, LP_PIVOT_DANTZIG);
+}
+
+// The same under a pivot rule (tests/ref/bounded_rules_ref.c): the rule picks the selector of both phases' loops; the
+// drive-out, the phase-II costs and the outputs do not depend on it.
+int lp_simplex_bounded_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
+                                double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out,
+                                int pivot_rule) {
     const char* who = "lp_simplex_bounded_large";
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown pivot rule");
     if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi)
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
@@ -919,19 +937,19 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
     rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
     if (rc) return rc;
     ProblemOwner owner(p, lp_simplex_free);
-    rc = lp_bounded_large_prepare(p);
+    rc = lp_bounded_large_prepare(p, pivot_rule);
     if (rc) return rc;
     // the bound state beside the tableau (buf is freed before the problem on every return path)
     hipStream_t s = ctx->stream;
     lp_device_buffer buf;
     BoundedLargeDev bd{};
-    rc = bounded_large_state(p, buf, bd, U.data(), nullptr, na);
+    rc = bounded_large_state(p, buf, bd, U.data(), nullptr, na, pivot_rule);
     if (rc) return rc;
     auto download_flags = [&]() { return lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}}); };
 
     // ---- phase I: minimise the sum of the artificials
     int iters = 0, flips1 = 0, flips = 0;
-    rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips1);
+    rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips1);
     if (rc < 0) return rc;
     it[0] = iters - flips1;
     it[3] = flips1;
@@ -949,7 +967,7 @@ int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, con
         rc = lp_simplex_phase2_costs(p, c2.data(), n, maximize, n);   // (n_orig = n: the download below returns every v_j)
     }
     if (rc == LP_OPTIMAL) {
-        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips);
+        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips);
         if (rc >= 0) {
             it[2] = iters - (flips - flips1);
             it[3] = flips;
@@ -979,8 +997,21 @@ int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, in
                                      const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
                                      int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
                                      int* at_upper_out, double* obj_out, int* iters_out) {
+    return lp_simplex_bounded_resolve_large_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps,
+                                               max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
+                                               LP_PIVOT_DANTZIG);
+}
+
+// The same under a pivot rule (tests/ref/bounded_resolve_rules_ref.c): the rule governs the primal loop only; the
+// crash, the classification and the dual loop are the same under every rule.
+int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                                        const double* c, const double* lo, const double* hi, const int* basis_in,
+                                        const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
+                                        double* x_out, int* basis_out, int* at_upper_out, double* obj_out,
+                                        int* iters_out, int pivot_rule) {
     const char* who = "lp_simplex_bounded_resolve_large";
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown pivot rule");
     if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi || !basis_in ||
         !at_upper_in)
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
@@ -1022,25 +1053,25 @@ int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, in
     ProblemOwner owner(p, lp_simplex_free);
     if (p->init_status != LP_OPTIMAL)   // LP_SINGULAR: the given basis and flags stay in the outputs
         LP_FAIL(ctx, p->init_status, std::string(who) + ": the basis matrix is singular");
-    rc = lp_bounded_large_prepare(p);
+    rc = lp_bounded_large_prepare(p, pivot_rule);
     if (rc) return rc;
     lp_device_buffer buf;   // (freed before the problem on every return path)
     BoundedLargeDev bd{};
-    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n);
+    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n, pivot_rule);
     if (rc) return rc;
     // step 5: which loop
     int flags = 0, iters = 0, flips = 0;
     rc = lp_bounded_large_classify(p, bd, eps, &flags);
     if (rc) return rc;
     if (!(flags & 1)) {   // every basic variable within its bounds: the bounded primal loop
-        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips);
+        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips);
         if (rc < 0) return rc;
         it[1] = iters - flips;
         it[2] = flips;
     } else if (!(flags & 2)) {   // step 6: the bounded dual loop
         rc = lp_bounded_dual_prepare(p);
         if (rc) return rc;
-        rc = run_bounded_phase(p, bd, eps, max_iter, &iters, &flips, true);
+        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips, true);
         if (rc < 0) return rc;
         it[0] = iters;
     } else {

@@ -136,9 +136,12 @@ struct BoundedLargeDev {
     int* up;      // dev.n: 1 = the column is held complemented
     int* flips;   // bound flips since the start of the solve
     double* q;    // dev.ld: the quotients of the dual selector's ratio test
+    double* w;    // dev.n: the Devex weights (LP_PIVOT_DEVEX), 1.0 when a primal loop starts
 };
-int lp_bounded_large_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, opted in
-int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
+// rule: LP_PIVOT_DANTZIG (k_simplex_select_bounded), LP_PIVOT_BLAND or LP_PIVOT_DEVEX, checked by the caller
+int lp_bounded_large_prepare(lp_simplex_problem* p, int rule);   // that selector's LDS: checked, opted in
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule);
+void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd);   // queued, all 1.0
 // The re-solve (lp_simplex_bounded_resolve_large).  classify: *flags = bit 0 some basis position outside its bounds,
 // bit 1 dual infeasible (one host sync); the dual path then queues the bounded dual selector + rank-1 update.
 int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags);

@@ -252,6 +252,14 @@ public:
         return boundedRun("Solver::boundedSimplexLarge", lo, hi, nullptr, nullptr, throw_on_failure, true);
     }
 
+    // The same under a pivot rule (lp_simplex_bounded_large_ex), in phase I and phase II, with no
+    // lp_simplex_bounded_rule_fits limit: PivotRule::Bland cannot cycle, PivotRule::Devex keeps its weights in device
+    // memory, PivotRule::Dantzig is the form above bit for bit.  Equal to boundedSimplex(lo, hi, rule) where both run.
+    BoundedResult boundedSimplexLarge(const std::vector<double>& lo, const std::vector<double>& hi, PivotRule rule,
+                                      bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedSimplexLarge", lo, hi, nullptr, &rule, throw_on_failure, true);
+    }
+
     // The same problem under the bounds lo, hi re-solved from the basis and flags of an earlier result
     // (lp_simplex_bounded_resolve): the bounded primal loop if `from` is still primal feasible, the bounded dual
     // simplex if it is only dual feasible, which it stays under any change of the bounds.  iterations = dual pivots,
@@ -269,6 +277,13 @@ public:
     BoundedResult boundedResolveLarge(const std::vector<double>& lo, const std::vector<double>& hi,
                                       const BoundedResult& from, bool throw_on_failure = true) const {
         return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, nullptr, throw_on_failure, true);
+    }
+
+    // The same under a pivot rule (lp_simplex_bounded_resolve_large_ex): the rule governs the primal loop only.  Equal
+    // to boundedResolve(lo, hi, from, rule) where both run.
+    BoundedResult boundedResolveLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                      const BoundedResult& from, PivotRule rule, bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, &rule, throw_on_failure, true);
     }
 
     // The same under a pivot rule (lp_simplex_bounded_resolve_ex): the rule governs the primal loop only; the dual
@@ -616,7 +631,7 @@ private:
     }
 
     // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form;
-    // large (rule null): boundedSimplexLarge, or with from boundedResolveLarge
+    // large: boundedSimplexLarge, or with from boundedResolveLarge, the same way
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
                              const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
                              bool large = false) const {
@@ -628,7 +643,17 @@ private:
         out.basis.assign((size_t)p.m, -1);
         out.atUpper.assign((size_t)p.n, 0);
         lp_context* ctx = lpgpu::context(_device);
-        if (large && from)
+        if (large && from && rule)
+            out.status = lp_simplex_bounded_resolve_large_ex(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
+                                                             from->basis.data(), from->atUpper.data(), p.maximize,
+                                                             p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
+                                                             out.atUpper.data(), &out.objective, out.iterations,
+                                                             (int)*rule);
+        else if (large && rule)
+            out.status = lp_simplex_bounded_large_ex(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), p.maximize,
+                                                     p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
+                                                     out.atUpper.data(), &out.objective, out.iterations, (int)*rule);
+        else if (large && from)
             out.status = lp_simplex_bounded_resolve_large(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
                                                           from->basis.data(), from->atUpper.data(), p.maximize, p.no,
                                                           EPS, MAX_ITER, out.x.data(), out.basis.data(),
