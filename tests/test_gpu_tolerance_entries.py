@@ -10,8 +10,9 @@ final tableau and the vertex pin them."""
 import numpy as np
 import pytest
 
+from oracle import pyoracle as o
 from simplexmethod_amd import capi
-from tests import bounded_ref, lpcases, mip_bounded_ref, parametric_cost_ref, parametric_ref
+from tests import bland_ref, bounded_ref, lpcases, mip_bounded_ref, parametric_cost_ref, parametric_ref
 from tests import bounded_resolve_ref as W
 from tests import devex_ref as D
 from tests import tolentries as E
@@ -72,44 +73,89 @@ def test_devex_single_lp_launch_and_auto(ctx, case):
             _assert_same(_run_devex(ctx, A[k], b[k], c[k], basis[k], eps, algo), r, (E.NAMES[k], eps, algo))
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_devex_batched(ctx, case):
-    m, n, eps = case
-    A, b, c, basis = E.mixed(m, n)
-    assert ctx.batched_devex_fits(m, n)
-    g = ctx.simplex_solve_batched(A, b, c, basis, True, n - m, eps=eps, pivot_rule="devex")
+def _batch_key(batch, m, n, k):
+    """The memo key of LP k of batch(m, n); E.mixed keeps the key it always had (shared with the single-LP test)."""
+    return (m, n, k) if batch is E.mixed else (batch.__name__, m, n, k)
+
+
+def _rule_ref(rule, batch, m, n, k, A, b, c, basis, eps):
+    """The reference of the plain simplex from a basis under `rule`, once per (rule, LP, eps bits)."""
+    if rule == "devex":
+        return _devex_ref(_batch_key(batch, m, n, k), A, b, c, basis, eps)
+    if rule == "bland":
+        return _ref(("bland",) + _batch_key(batch, m, n, k), eps,
+                    lambda: bland_ref.simplex_tableau(A, b, c, basis, True, n - m, rule=bland_ref.BLAND, eps=eps))
+    return _ref(("dantzig",) + _batch_key(batch, m, n, k), eps,
+                lambda: o.simplex_tableau(A, b, c, basis, True, n - m, eps=eps))
+
+
+def check_batched(ctx, m, n, eps, batch=E.mixed, names=E.NAMES, rule="devex"):
+    """simplex_solve_batched and the batched_problem handle on batch(m, n) under `rule`, on the one-LP-per-workgroup
+    kernel, against the rule's reference: status, iters, basis, x, obj per LP."""
+    A, b, c, basis = batch(m, n)
+    if rule == "devex":
+        assert ctx.batched_devex_fits(m, n)
+    g = ctx.simplex_solve_batched(A, b, c, basis, True, n - m, eps=eps, pivot_rule=rule)
     p = ctx.batched_problem(A, b, c, basis, True, n - m)
     try:
         assert p.path() == 1
-        p.set_pivot_rule("devex")
+        p.set_pivot_rule(rule)
         p.run(eps=eps)
         h = p.download()
     finally:
         p.free()
-    for k in range(BATCH):
-        r = _devex_ref((m, n, k), A[k], b[k], c[k], basis[k], eps)
+    for k in range(len(A)):
+        r = _rule_ref(rule, batch, m, n, k, A[k], b[k], c[k], basis[k], eps)
         for out in (g, h):
-            assert out["iters"][k] == r["iters"], (E.NAMES[k], eps)
-            _assert_lp(out, k, r, (E.NAMES[k], eps))
+            assert out["iters"][k] == r["iters"], (names[k], eps)
+            _assert_lp(out, k, r, (names[k], eps))
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_devex_batched(ctx, case):
+    m, n, eps = case
+    check_batched(ctx, m, n, eps)
+
+
+TWO_PHASE_REF = {   # the references of the two-phase tests of each rule
+    "dantzig": lambda A, b, c, no, eps: o.two_phase(A, b, c, True, no, eps=eps),
+    "bland": lambda A, b, c, no, eps: bland_ref.two_phase(A, b, c, True, no, rule=bland_ref.BLAND, eps=eps),
+    "devex": lambda A, b, c, no, eps: D.two_phase(A, b, c, True, no, eps=eps),
+}
+
+
+def check_two_phase(ctx, m, n, eps, batch=E.mixed, names=E.NAMES, rule="devex", single=True):
+    """two_phase_batched on two_phase_form(batch(m, n)) under `rule` against the rule's reference; single: the
+    single-LP entry too.  With single=False the handle form says that the batch ran one LP per workgroup."""
+    A, b, c, _ = batch(m, n)
+    A, b, c = E.two_phase_form(A, b, c)
+    if rule == "devex":
+        assert ctx.batched_devex_fits(m, n, True)
+    if not single:
+        p = ctx.batched_two_phase_problem(A, b, c, True, n - m)
+        try:
+            assert p.path() == 1
+        finally:
+            p.free()
+    gb = ctx.two_phase_batched(A, b, c, True, n - m, eps=eps, pivot_rule=rule)
+    for k in range(len(A)):
+        what = (names[k], eps, rule)
+        r = _ref((rule + "2",) + _batch_key(batch, m, n, k), eps,
+                 lambda: TWO_PHASE_REF[rule](A[k], b[k], c[k], n - m, eps))
+        if single:
+            g = ctx.two_phase(A[k], b[k], c[k], True, n - m, eps=eps, pivot_rule=rule)
+            assert g["status"] == r["status"] and g["iters"] == r["iters"], what
+            assert np.array_equal(g["basis"], r["basis"]), what
+            if r["status"] == OPTIMAL:
+                assert _same_bits(g["x"], r["x"]) and _same_bits(g["obj"], r["obj"]), what
+        assert gb["iters"][k].tolist() == list(r["iters"]), what
+        _assert_lp(gb, k, r, what)
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_devex_two_phase_and_batched(ctx, case):
     m, n, eps = case
-    A, b, c, _ = E.mixed(m, n)
-    A, b, c = E.two_phase_form(A, b, c)
-    assert ctx.batched_devex_fits(m, n, True)
-    gb = ctx.two_phase_batched(A, b, c, True, n - m, eps=eps, pivot_rule="devex")
-    for k in range(BATCH):
-        what = (E.NAMES[k], eps)
-        r = _ref(("devex2", m, n, k), eps, lambda: D.two_phase(A[k], b[k], c[k], True, n - m, eps=eps))
-        g = ctx.two_phase(A[k], b[k], c[k], True, n - m, eps=eps, pivot_rule="devex")
-        assert g["status"] == r["status"] and g["iters"] == r["iters"], what
-        assert np.array_equal(g["basis"], r["basis"]), what
-        if r["status"] == OPTIMAL:
-            assert _same_bits(g["x"], r["x"]) and _same_bits(g["obj"], r["obj"]), what
-        assert gb["iters"][k].tolist() == r["iters"], what
-        _assert_lp(gb, k, r, what)
+    check_two_phase(ctx, m, n, eps)
 
 
 def test_devex_scaled_costs(ctx):
@@ -140,23 +186,31 @@ def _assert_bounded(g, r, what):
     assert _same_bits(g["x"], r["x"]) and _same_bits(g["obj"], r["obj"]), what
 
 
-@pytest.mark.parametrize("kind", W.PERTURBATIONS)
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_bounded_resolve_and_batched(ctx, case, kind):
-    m, n, eps = case
+def check_bounded_resolve(ctx, m, n, eps, kind, batch=E.mixed, names=E.NAMES, single=None):
+    """bounded_resolve_batched on the warm starts of batch(m, n) perturbed by `kind`, and the single-LP entry on the
+    kept LPs at the positions `single` (None: all of them), against bounded_resolve_ref."""
     assert ctx.bounded_fits(m, n)
-    keep, warm = E.resolve_batch(m, n, eps, kind)
-    refs = E.resolve_ref(m, n, eps, kind)
-    assert len(keep) >= BATCH - 2
+    keep, warm = E.resolve_batch(m, n, eps, kind, batch)
+    refs = E.resolve_ref(m, n, eps, kind, batch)
+    assert len(keep) >= len(names) - 2
     gb = ctx.bounded_resolve_batched(*warm, True, n - m, eps=eps)
     for j, (k, r) in enumerate(zip(keep, refs)):
-        what = (E.NAMES[k], eps, kind)
+        what = (names[k], eps, kind)
         _assert_bounded({key: v[j] for key, v in gb.items()}, r, what)
+        if single is not None and j not in [s % len(keep) for s in single]:
+            continue
         one = [w[j] for w in warm]
         if r["status"] == BAD_ARG:   # no valid start: a status in a batch, an error for one LP
             _bad_arg(lambda: ctx.bounded_resolve(*one, True, n - m, eps=eps))
         else:
             _assert_bounded(ctx.bounded_resolve(*one, True, n - m, eps=eps), r, what)
+
+
+@pytest.mark.parametrize("kind", W.PERTURBATIONS)
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_bounded_resolve_and_batched(ctx, case, kind):
+    m, n, eps = case
+    check_bounded_resolve(ctx, m, n, eps, kind)
 
 
 # ---- C: bounded MIP ---------------------------------------------------------------------------------------------------
@@ -166,15 +220,15 @@ def _assert_mip(g, r, what):
     assert _same_bits(g["x"], r["x"]) and _same_bits(g["obj"], r["obj"]) and _same_bits(g["bound"], r["bound"]), what
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_mip_bounded_batched_and_single(ctx, case):
-    m, n, eps = case
+def check_mip_bounded(ctx, m, n, eps, seed):
+    """mip_bounded_solve_batched on boxed_mip_ties(m, n, seed) under MIP_LIMITS, and the single-LP entry on the first
+    and the last LP with an OPTIMAL root, against mip_bounded_ref."""
     no = n - m
     assert ctx.mip_bounded_fits(m, n, E.MIP_LIMITS["max_depth"])
-    A, b, c, lo, hi, mask = E.boxed_mip_ties(m, n, E.MIP_SEED[(m, n)])
-    refs = E.mip_ref(m, n, eps)
+    A, b, c, lo, hi, mask = E.boxed_mip_ties(m, n, seed)
+    refs = E.mip_ref(m, n, eps, seed)
     ok = np.array([root["status"] == OPTIMAL for root, _ in refs])
-    assert ok.sum() >= BATCH - 3
+    assert ok.sum() >= len(refs) - 3
     root_status = np.array([root["status"] for root, _ in refs], np.int32)
     basis = np.stack([root["basis"] if o_ else np.zeros(m, np.int32) for o_, (root, _) in zip(ok, refs)])
     up = np.stack([root["at_upper"] if o_ else np.zeros(n, np.int32) for o_, (root, _) in zip(ok, refs)])
@@ -194,6 +248,12 @@ def test_mip_bounded_batched_and_single(ctx, case):
             _bad_arg(lambda: ctx.mip_bounded_solve(*args, eps=eps, **E.MIP_LIMITS))
         else:
             _assert_mip(ctx.mip_bounded_solve(*args, eps=eps, **E.MIP_LIMITS), r, (k, eps))
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_mip_bounded_batched_and_single(ctx, case):
+    m, n, eps = case
+    check_mip_bounded(ctx, m, n, eps, E.MIP_SEED[(m, n)])
 
 
 # ---- D: parametric right-hand side and cost ---------------------------------------------------------------------------
@@ -221,21 +281,20 @@ def _lp_of(out, k):
     return {key: v[k] for key, v in out.items()}
 
 
-@pytest.mark.parametrize("which", ["rhs", "cost"])
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_parametric_three_calling_forms(ctx, case, which):
-    m, n, eps = case
+def check_parametric(ctx, m, n, eps, which, seed, batch=E.mixed, names=E.NAMES, single=True):
+    """The parametric RHS or cost path on batch(m, n, seed) at the oracle's final bases: the batched entry, the handle
+    form after a batched run at the same eps (one LP per workgroup) and, with single, the single-LP entry."""
     P = _PARAMETRIC[which]
     trim = P["mod"].trim
     assert getattr(ctx, P["fits"])(m, n)
-    A, b, c, basis, d, g_, status = E.parametric_inputs(m, n, eps)
+    A, b, c, basis, d, g_, status = E.parametric_inputs(m, n, eps, seed, batch)
     direction = d if which == "rhs" else g_
-    ref = E.parametric_refs(m, n, eps, which)
+    ref = E.parametric_refs(m, n, eps, which, seed, batch=batch)
     kw = dict(eps=eps, max_breaks=E.MAX_BREAKS)
     # the batched entry
     gb = getattr(ctx, P["batched"])(A, b, c, basis, direction, np.inf, True, **kw)
     # the handle after a batched run at the same eps
-    slack = np.tile(np.arange(n - m, n, dtype=np.int32), (BATCH, 1))
+    slack = np.tile(np.arange(n - m, n, dtype=np.int32), (len(A), 1))
     p = ctx.batched_problem(A, b, c, slack, True, n - m)
     try:
         assert p.path() == 1
@@ -245,21 +304,30 @@ def test_parametric_three_calling_forms(ctx, case, which):
     finally:
         p.free()
     assert np.array_equal(run["status"], status) and np.array_equal(run["basis"], basis)
-    href = E.parametric_refs(m, n, eps, which, handle=True)
-    for k in range(BATCH):
-        what = (E.NAMES[k], eps, which)
+    href = E.parametric_refs(m, n, eps, which, seed, handle=True, batch=batch)
+    for k in range(len(A)):
+        what = (names[k], eps, which)
         r = _lp_of(ref, k)
         assert gb["nseg"][k] == r["nseg"] or r["status"] in REFUSED, what
         _assert_path(trim(_lp_of(gb, k)), trim(r), what)
         rh = _lp_of(href, k)
         assert gh["nseg"][k] == rh["nseg"] or rh["status"] in REFUSED, what
         _assert_path(trim(_lp_of(gh, k)), trim(rh), what)
+        if not single:
+            continue
         # the single-LP entry
         call = lambda: getattr(ctx, P["single"])(A[k], b[k], c[k], basis[k], direction[k], np.inf, True, **kw)  # noqa: E731
         if r["status"] == BAD_ARG:
             _bad_arg(call)
         else:
             _assert_path(call(), trim(r), what)
+
+
+@pytest.mark.parametrize("which", ["rhs", "cost"])
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_parametric_three_calling_forms(ctx, case, which):
+    m, n, eps = case
+    check_parametric(ctx, m, n, eps, which, E.PARAMETRIC_SEED[(m, n)])
 
 
 # ---- E: the domain of eps ---------------------------------------------------------------------------------------------

@@ -2,9 +2,11 @@
 last bits of a ratio or a reduced cost, or whose operands leave the range in which the kernels' fast reciprocals hold.
 
 Every family is seeded and cheap.  Interesting rows and columns are placed across the kernels' boundaries: partner
-offsets of 1, 63, 64, 65 (same and neighbouring 64-row waves, the batched kernel's rows l and l + 64), 255, 256 (the
-near-tie replay's 256-row tiles, the chip-resident kernel's slices) and 511, 512 (its 8 / 16 slices), clipped to m;
-column partners straddle the 16- and 32-column workgroups of the chip-resident kernel.
+offsets of 1, 63, 64, 65 (same and neighbouring 64-row waves), 255, 256 (the near-tie replay's 256-row tiles, the
+chip-resident kernel's slices) and 511, 512 (its 8 / 16 slices), clipped to m - 1; column partners straddle the 16- and
+32-column workgroups of the chip-resident kernel.  An offset reaches what it is meant for only where m > off: at
+m <= 64 the offsets 64 and 65 are clipped to 63 and no pair reaches the batched kernels' rows l and l + 64 (the second
+ratio register of wave 0).  tests/rowcases.py places the families there, at shapes of m > 64.
 
 All LPs are in slack form [A_orig | I] with the slack basis and maximise (capi.gen_lp), so that the first pricing
 sees d = c and the first ratio test the column A[:, e] against xB = b."""

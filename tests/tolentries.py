@@ -87,9 +87,9 @@ def scaled_cost_case(fam, seed, idx, k, m=64, n=160):
 
 
 # ---- the start of a composite entry ---------------------------------------------------------------------------------
-def bounded_lps(m, n):
-    """The seven LPs with the box recipe: (A, b, c, lo, hi), stacked."""
-    A, b, c, _ = mixed(m, n)
+def bounded_lps(m, n, batch=mixed):
+    """The LPs of batch(m, n) with the box recipe: (A, b, c, lo, hi), stacked."""
+    A, b, c, _ = batch(m, n)
     lo, hi = boxes(c.shape, m)
     return A, b, c, lo, hi
 
@@ -101,33 +101,34 @@ def start_eps(eps):
     return EPS_DEFAULT if eps == np.inf else eps
 
 
-def same_eps_start(kind, m, n, eps, seed=MIXED_SEED):
-    """The cold reference solves of a batch at `eps`, once per (kind, shape, eps bits):
-      "oracle"   mixed(m, n, seed) from the slack basis by the oracle: a list of its result dicts;
-      "bounded"  bounded_lps(m, n) by bounded_ref.bounded at start_eps(eps) with the full vertex (n_orig = n)."""
+def same_eps_start(kind, m, n, eps, seed=MIXED_SEED, batch=mixed):
+    """The cold reference solves of a batch at `eps`, once per (kind, batch maker, shape, eps bits):
+      "oracle"   batch(m, n, seed) from the slack basis by the oracle: a list of its result dicts;
+      "bounded"  bounded_lps(m, n, batch) by bounded_ref.bounded at start_eps(eps) with the full vertex (n_orig = n).
+    batch: the maker of the LPs, mixed or another of its signature (tests/rowcases.py)."""
     def make():
         if kind == "oracle":
-            A, b, c, basis = mixed(m, n, seed)
+            A, b, c, basis = batch(m, n, seed)
             return [o.simplex_tableau(A[k], b[k], c[k], basis[k], True, n - m, eps=eps) for k in range(len(A))]
         if kind == "bounded":
-            A, b, c, lo, hi = bounded_lps(m, n)
+            A, b, c, lo, hi = bounded_lps(m, n, batch)
             return [bounded_ref.bounded(A[k], b[k], c[k], lo[k], hi[k], True, n, eps=start_eps(eps))
                     for k in range(len(A))]
         raise ValueError(kind)
-    return _memo(("start", kind, m, n, seed, eps_key(eps)), make)
+    return _memo(("start", kind, batch.__name__, m, n, seed, eps_key(eps)), make)
 
 
 # ---- bounded re-solve -----------------------------------------------------------------------------------------------
 PERTURB_SEED = {"bound": 3, "rhs": 3, "cost": 5}   # (cost: seeds 0..4 give no bound flip at some shape and eps)
 
 
-def resolve_batch(m, n, eps, kind):
+def resolve_batch(m, n, eps, kind, batch=mixed):
     """The warm starts of the LPs whose cold solve at start_eps(eps) is OPTIMAL, perturbed by
     bounded_resolve_ref.perturb(PERTURB_SEED[kind], kind): (kept indices, (A, b', c', lo', hi', basis, at_upper)
     stacked)."""
     def make():
-        A, b, c, lo, hi = bounded_lps(m, n)
-        cold = same_eps_start("bounded", m, n, eps)
+        A, b, c, lo, hi = bounded_lps(m, n, batch)
+        cold = same_eps_start("bounded", m, n, eps, batch=batch)
         keep = [k for k, r in enumerate(cold) if r["status"] == OPTIMAL]
         rows = []
         for k in keep:
@@ -135,15 +136,15 @@ def resolve_batch(m, n, eps, kind):
             b2, c2, lo2, hi2 = W.perturb(PERTURB_SEED[kind], kind, b[k], c[k], lo[k], hi[k], r["basis"], r["x"])
             rows.append((A[k], b2, c2, lo2, hi2, r["basis"], r["at_upper"]))
         return keep, tuple(np.stack(v) for v in zip(*rows))
-    return _memo(("resolve", m, n, eps_key(eps), kind), make)
+    return _memo(("resolve", batch.__name__, m, n, eps_key(eps), kind), make)
 
 
-def resolve_ref(m, n, eps, kind):
+def resolve_ref(m, n, eps, kind, batch=mixed):
     """bounded_resolve_ref.resolve on every LP of resolve_batch at `eps` (sense max, n_orig = n - m)."""
     def make():
-        _, warm = resolve_batch(m, n, eps, kind)
+        _, warm = resolve_batch(m, n, eps, kind, batch)
         return [W.resolve(*(w[k] for w in warm), True, n - m, eps=eps) for k in range(len(warm[0]))]
-    return _memo(("resolve_ref", m, n, eps_key(eps), kind), make)
+    return _memo(("resolve_ref", batch.__name__, m, n, eps_key(eps), kind), make)
 
 
 # ---- bounded MIP ----------------------------------------------------------------------------------------------------
@@ -194,32 +195,32 @@ def mip_ref(m, n, eps, seed=None):
 MAX_BREAKS = 64
 
 
-def parametric_inputs(m, n, eps, seed=None):
-    """mixed(m, n, seed) at the oracle's final bases at `eps`: (A, b, c, basis, d, g, run_status) with
+def parametric_inputs(m, n, eps, seed=None, batch=mixed):
+    """batch(m, n, seed) at the oracle's final bases at `eps`: (A, b, c, basis, d, g, run_status) with
     d = parametric_ref.direction(1, b), g = parametric_cost_ref.direction(1, c) per LP."""
     seed = PARAMETRIC_SEED[(m, n)] if seed is None else seed
 
     def make():
-        A, b, c, _ = mixed(m, n, seed)
-        cold = same_eps_start("oracle", m, n, eps, seed)
+        A, b, c, _ = batch(m, n, seed)
+        cold = same_eps_start("oracle", m, n, eps, seed, batch)
         basis = np.stack([np.asarray(r["basis"], np.int32) for r in cold])
         status = np.array([r["status"] for r in cold], np.int32)
         d = np.stack([parametric_ref.direction(1, bk) for bk in b])
         g = np.stack([parametric_cost_ref.direction(1, ck) for ck in c])
         return A, b, c, basis, d, g, status
-    return _memo(("parametric", m, n, seed, eps_key(eps)), make)
+    return _memo(("parametric", batch.__name__, m, n, seed, eps_key(eps)), make)
 
 
-def parametric_refs(m, n, eps, which, seed=None, handle=False):
+def parametric_refs(m, n, eps, which, seed=None, handle=False, batch=mixed):
     """parametric_ref.parametric_batched ("rhs") or parametric_cost_ref.parametric_cost_batched ("cost") on
     parametric_inputs.  handle: the form after a batched run, in which an LP whose cold solve is not OPTIMAL keeps that
     status; otherwise every basis is given to the reference as it is."""
     seed = PARAMETRIC_SEED[(m, n)] if seed is None else seed
 
     def make():
-        A, b, c, basis, d, g, status = parametric_inputs(m, n, eps, seed)
+        A, b, c, basis, d, g, status = parametric_inputs(m, n, eps, seed, batch)
         rs = status if handle else None
         if which == "rhs":
             return parametric_ref.parametric_batched(A, b, c, basis, d, np.inf, True, eps, MAX_BREAKS, rs)
         return parametric_cost_ref.parametric_cost_batched(A, b, c, basis, g, np.inf, True, eps, MAX_BREAKS, rs)
-    return _memo(("parametric_ref", which, m, n, seed, eps_key(eps), handle), make)
+    return _memo(("parametric_ref", which, batch.__name__, m, n, seed, eps_key(eps), handle), make)
