@@ -49,11 +49,12 @@ def _twin_scale(a, bp, start):
     return None
 
 
-def near_tie_rows(seed, m, n, off):
+def near_tie_rows(seed, m, n, off, pair=None):
     """ulp near-tie rows at the first ratio test.  Row p gets the smallest ratio by a margin; row q = p + off (behind
     it) becomes its twin fl(s * row_p), b_q = fl(s * b_p) with the scale s chosen so that q's true quotient is a few
     ulp SMALLER than p's.  The reference chain takes q at eps = 0 and p at eps >= 1e-15; a ranking by approximate
-    quotients may keep p.  The other rows are paired the same way at random offsets (more near-ties later on)."""
+    quotients may keep p.  The other rows are paired the same way at random offsets (more near-ties later on).
+    pair = (p, q) fixes the two rows (off is then part of the seed alone)."""
     A, b, c, basis = capi.gen_lp(seed, m, n)
     no = n - m
     rng = _rng(1, seed, m, n, off)
@@ -63,7 +64,7 @@ def near_tie_rows(seed, m, n, off):
     bmin = 0.5 * float((b / A[:, e]).min())
     for t in range(256):   # (another pair, or b_p an ulp lower, until a scale of SCALES qualifies)
         if t % 8 == 0:
-            p, q = _clip_pair(rng, m, off)
+            p, q = _clip_pair(rng, m, off) if pair is None else pair
             b0 = b[p]
             b[p] = bmin * A[p, e]
         s = _twin_scale(A[p, e], b[p], start)
@@ -97,16 +98,17 @@ def first_pivot_pairs(seed, count, m=64, n=96):
     return np.stack(A), np.stack(b), np.stack(c), np.stack(basis)
 
 
-def near_tie_cols(seed, m, n, off):
+def near_tie_cols(seed, m, n, off, cols=None):
     """ulp near-tie columns: column e2 = e + off is column e with every entry and the cost moved one ulp up
     (nextafter); e has the largest cost, so at the first pricing d_e2 exceeds d_e by one ulp: the chain takes e2 at
-    eps = 0 and e at eps >= 1e-15.  The pair straddles the kernels' column workgroups for the larger offsets."""
+    eps = 0 and e at eps >= 1e-15.  The pair straddles the kernels' column workgroups for the larger offsets.
+    cols = (e, e2) fixes the two columns (off is then part of the seed alone)."""
     A, b, c, basis = capi.gen_lp(seed, m, n)
     no = n - m
     rng = _rng(2, seed, m, n, off)
     off = min(off, no - 1)
     e = int(rng.integers(0, no - off))
-    e2 = e + off
+    e, e2 = (e, e + off) if cols is None else cols
     _force_entering(A, c, no, e)
     A[:, e2] = np.nextafter(A[:, e], np.inf)
     c[e2] = np.nextafter(c[e], np.inf)
@@ -136,16 +138,17 @@ def exact_ties(seed, m, n):
     return A, b, c, np.arange(no, n, dtype=np.int32)
 
 
-def tiny_entry(seed, m, n, u, off):
+def tiny_entry(seed, m, n, u, off, pair=None):
     """A degenerate row q = p + off (b_q = 0) whose entry in the first entering column is u (TINY).  Row p holds the
     smallest positive ratio.  At eps = 0 row q is eligible with ratio 0 and leaves first (a pivot on u); at eps > u it
-    is not.  Pivoting on a subnormal u fills the tableau with inf and NaN: the paths must agree on where."""
+    is not.  Pivoting on a subnormal u fills the tableau with inf and NaN: the paths must agree on where.
+    pair = (p, q) fixes the two rows (off is then part of the seed alone)."""
     A, b, c, basis = capi.gen_lp(seed, m, n)
     no = n - m
     rng = _rng(4, seed, m, n, off)
     e = int(rng.integers(0, no))
     _force_entering(A, c, no, e)
-    p, q = _clip_pair(rng, m, off)
+    p, q = _clip_pair(rng, m, off) if pair is None else pair
     b[p] = 0.5 * float((b / A[:, e]).min()) * A[p, e]
     A[q, e] = u
     b[q] = 0.0
