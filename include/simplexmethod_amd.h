@@ -596,10 +596,11 @@ int lp_simplex_bounded_fits(int m, int n);
  *   - max_iter bounds the pivots plus flips of each phase; iters_out[4] = phase-I pivots, drive-out pivots, phase-II
  *     pivots, bound flips.
  *   - Dantzig's rule; Bland's rule and Devex pricing at these shapes are lp_simplex_bounded_large_ex (with the _ex
- *     block below; m <= 9968 under LP_PIVOT_DEVEX).  Out of scope on this path: the analyses (duals, ranging,
- *     certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The re-solve from
- *     a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and
- *     still refuses larger shapes.                                                                               */
+ *     block below; m <= 9968 under LP_PIVOT_DEVEX).  The dual solution and ranging at these shapes are
+ *     lp_basis_bounded_duals_large and lp_basis_bounded_ranging_large below.  Out of scope on this path: the other
+ *     analyses (certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The
+ *     re-solve from a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is
+ *     unchanged and still refuses larger shapes.                                                                 */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 /* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
  * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
@@ -749,6 +750,20 @@ int lp_basis_bounded_ranging_batched(lp_context* ctx, int batch, const double* A
 /* 1: lp_simplex_bounded_fits(m, n) and the analysis kernel's LDS carve (lp_basis_ranging_fits' plus the held values
  * and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.                   */
 int lp_basis_bounded_fits(int m, int n);
+/* The same two analyses beyond one workgroup's LDS, one LP per call (the definition is still
+ * tests/ref/bounded_sens_ref.c, and every output equals it bit for bit, NaN and signed zeros included): what
+ * lp_simplex_bounded_large returns can be analysed where it was solved.  The column codes, the held values and b' are
+ * small kernels (b' one chain per row); lp_basis_ranging's single-LP path does the rest: the crash on [B | I | b']
+ * ([B | b'] for the duals) by one selector and one rank-1 update launch per basis position on a tableau in HBM,
+ * lp_basis_duals' path for y, d and b.y, B^-1 A as tiled chains, then one reduction kernel per range with the bounded
+ * candidates.  Arguments, outputs, statuses and refusals are lp_basis_bounded_duals' and lp_basis_bounded_ranging's
+ * with one difference: there is no lp_basis_bounded_fits limit.  The limit is device memory: two (m+1) x (2m+1)
+ * tableaus ((m+1) x (m+1) for the duals) and, for ranging, the m x n matrix B^-1 A beside the inputs; the crash itself
+ * takes any m.  At a shape where lp_basis_bounded_fits holds every output equals the entry's without _large.  With
+ * lo = 0, hi = +inf and no flag the results are lp_basis_duals' and lp_basis_ranging's.  There is no batched form;
+ * lp_basis_bounded_duals and lp_basis_bounded_ranging themselves are unchanged and still refuse larger shapes.       */
+int lp_basis_bounded_duals_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, double* x_out, double* y_out, double* d_out, double* w_out);
+int lp_basis_bounded_ranging_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out, double* cost_out, int* cost_var_out);
 
 /* ---- Bounded variables: Farkas and unbounded-ray certificates at a basis ----------------------------------------
  * Evidence for an LP_INFEASIBLE or LP_UNBOUNDED verdict of lp_simplex_bounded, lp_simplex_bounded_resolve or

@@ -184,6 +184,10 @@ SIGNATURES = {
     "lp_basis_bounded_ranging_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                    C.c_int, C.c_double, _dp, _ip, _ip, _dp, _ip, _ip]),
     "lp_basis_bounded_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_duals_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp,
+                                               _dp]),
+    "lp_basis_bounded_ranging_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                 C.c_double, _dp, _ip, _ip, _dp, _ip]),
     "lp_basis_bounded_certificate": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
                                                C.c_double, _ip, _dp, _dp, _dp, _ip]),
     "lp_basis_bounded_certificate_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
@@ -862,11 +866,19 @@ class Context:
         columns (c.x at an optimum), in the original variables.  dict(status, x, y, d, w); NaN unless status is
         OPTIMAL (SINGULAR: a crash failed; INFEASIBLE: some hi < lo).  A bad bound, index or flag or a shape beyond
         basis_bounded_fits raises LPError with code BAD_ARG."""
+        return self._bounded_duals(self.lib.lp_basis_bounded_duals, A, b, c, lo, hi, basis, at_upper)
+
+    def bounded_duals_large(self, A, b, c, lo, hi, basis, at_upper):
+        """lp_basis_bounded_duals_large: bounded_duals() on the tableau in HBM, at any shape bounded_large() runs (no
+        basis_bounded_fits limit).  Returns the dict of bounded_duals(), equal to it where both run; refusals as there."""
+        return self._bounded_duals(self.lib.lp_basis_bounded_duals_large, A, b, c, lo, hi, basis, at_upper)
+
+    def _bounded_duals(self, entry, A, b, c, lo, hi, basis, at_upper):
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         x, y, d, w = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(1)
-        rc = self.check(self.lib.lp_basis_bounded_duals(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
-                                                        _i(at_upper), _d(x), _d(y), _d(d), _d(w)))
+        rc = self.check(entry(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), _d(x),
+                              _d(y), _d(d), _d(w)))
         return dict(status=rc, x=x, y=y, d=d, w=float(w[0]))
 
     def bounded_duals_batched(self, A, b, c, lo, hi, basis, at_upper):
@@ -885,13 +897,21 @@ class Context:
         """lp_basis_bounded_ranging: how far each b_i and c_j can move before `basis` and `at_upper` stop being
         feasible / optimal for the LP of bounded().  The dict of basis_ranging plus b_side (m, 2): the bound the
         leaving variable leaves at (0 lower, 1 upper, -1 for an infinite end); NaN and -1 unless status is OPTIMAL."""
+        return self._bounded_ranging(self.lib.lp_basis_bounded_ranging, A, b, c, lo, hi, basis, at_upper, maximize, eps)
+
+    def bounded_ranging_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
+        """lp_basis_bounded_ranging_large: bounded_ranging() on the tableau in HBM, at any shape bounded_large() runs
+        (no basis_bounded_fits limit).  Returns the dict of bounded_ranging(), equal to it where both run."""
+        return self._bounded_ranging(self.lib.lp_basis_bounded_ranging_large, A, b, c, lo, hi, basis, at_upper,
+                                     maximize, eps)
+
+    def _bounded_ranging(self, entry, A, b, c, lo, hi, basis, at_upper, maximize, eps):
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         rhs, cost = np.zeros(2 * m), np.zeros(2 * n)
         rv, rs, cv = np.zeros(2 * m, np.int32), np.zeros(2 * m, np.int32), np.zeros(2 * n, np.int32)
-        rc = self.check(self.lib.lp_basis_bounded_ranging(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
-                                                          _i(at_upper), int(maximize), float(eps), _d(rhs), _i(rv),
-                                                          _i(rs), _d(cost), _i(cv)))
+        rc = self.check(entry(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
+                              int(maximize), float(eps), _d(rhs), _i(rv), _i(rs), _d(cost), _i(cv)))
         return dict(_ranging_dict(rc, rhs, rv, cost, cv), b_side=rs.reshape(-1, 2))
 
     def bounded_ranging_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):

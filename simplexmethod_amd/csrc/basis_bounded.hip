@@ -16,13 +16,18 @@
 //
 // k_batched_bounded_sens<NT, RANGING>: one LP per workgroup, state in LDS, the structure of k_batched_ranging plus v
 // (n) and the basic columns' L, H (2m).  RANGING = false is the duals entry: its second crash is [B | b'] without the
-// identity block (tableau_pivot treats every column on its own, so xB has the same bits).  There is no path beyond
-// lp_basis_bounded_fits, as in the bounded family.
+// identity block (tableau_pivot treats every column on its own, so xB has the same bits).
+//
+// Shapes beyond lp_basis_bounded_fits (lp_basis_bounded_device, one LP): the column codes, the held values and b' by
+// small kernels; k_bsens_gather builds [B | I | b'; 0] ([B | b'; 0] for the duals) and the single-LP launch pair
+// (lp_simplex_crash) pivots it; y, d and b.y by lp_basis_duals_device; then x and w, or k_binv_times_a
+// (basis_ranging.hip) and the two reduction kernels.
 #include <cfloat>
 
 #include "basis_crash.hpp"
 #include "batched_problem.hpp"
 #include "lp_internal.hpp"
+#include "simplex_problem.hpp"
 
 namespace {
 
@@ -336,6 +341,190 @@ int bounded_sens_launch(lp_context* ctx, const BasisBoundedDev& d) {
     return lp_launch_per_lp(ctx, k_batched_bounded_sens<NT, RANGING>, NT, lp_basis_bounded_lds_bytes(d.m, d.n), d);
 }
 
+// ---- the single-LP path beyond lp_basis_bounded_fits
+
+// code[j] by the flag alone (k_bsens_basic overwrites the basic columns'); any hi_j < lo_j raises *crossed
+__global__ __launch_bounds__(256) void k_bsens_codes(int n, const double* lo, const double* hi, const int* up,
+                                                     int* code, int* crossed) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    code[j] = up[j] ? kUpper : kLower;
+    if (hi[j] < lo[j]) *crossed = 1;
+}
+
+__global__ __launch_bounds__(256) void k_bsens_basic(const int* basis, int m, const double* lo, const double* hi,
+                                                     int* code, double* L, double* H) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const int q = basis[t];
+    code[q] = kBasic;
+    L[t] = lo[q];
+    H[t] = hi[q];
+}
+
+// the held values: 0.0 for basic columns
+__global__ __launch_bounds__(256) void k_bsens_held(int n, const double* lo, const double* hi, const int* code,
+                                                    double* v) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) v[j] = code[j] == kBasic ? 0.0 : code[j] == kUpper ? hi[j] : lo[j];
+}
+
+// b'[i] = b[i] - sum_j A[i][j] v_j: one chain per row (one thread), j ascending over v_j != 0.0; consecutive threads
+// read consecutive i of column j, and v_j is the same for the whole block
+__global__ __launch_bounds__(64) void k_bsens_bprime(const double* A, int m, int n, const double* b, const double* v,
+                                                     double* bp) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    double acc = b[i];
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        const double vj = v[j];
+        if (vj != 0.0) acc = fma(-A[(size_t)j * m + i], vj, acc);
+    }
+    bp[i] = acc;
+}
+
+// T (m+1 rows, pitch ld) = [B | I | b'; 0] when s.n = 2m, [B | b'; 0] when s.n = m; the crash bookkeeping's
+// basis = 0..m-1
+__global__ __launch_bounds__(256) void k_bsens_gather(SimplexDev s, const double* A, const double* bp,
+                                                      const int* basis) {
+    const int i = blockIdx.x;   // tableau row, 0..m
+    const int m = s.m;
+    double* row = s.T + (size_t)i * s.ld;
+    if (i == m) {
+        for (int j = threadIdx.x; j < s.ld; j += blockDim.x) row[j] = 0.0;
+        return;
+    }
+    for (int j = threadIdx.x; j < s.ld; j += blockDim.x)
+        row[j] = j < m ? A[(size_t)basis[j] * m + i] : j == s.n ? bp[i] : j < s.n ? (j - m == i ? 1.0 : 0.0) : 0.0;
+    if (threadIdx.x == 0) s.basis[i] = i;
+}
+
+// x = v on the non-basic columns, xB (the crashed tableau's right-hand column, rows in position order) on the basis
+__global__ __launch_bounds__(256) void k_bsens_x(SimplexDev s, int n, const int* basis, const int* code,
+                                                 const double* v, double* x) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n && code[j] != kBasic) x[j] = v[j];
+    if (j < s.m) x[basis[j]] = s.T[(size_t)j * s.ld + s.n];
+}
+
+// w: b.y (already in *w) continued over j ascending with v_j != 0.0 as fma(d_j, v_j, s).  One block: the chunks of d
+// and v are staged by all threads, thread 0 runs the chain.
+__global__ __launch_bounds__(256) void k_bsens_w(int n, const double* dd, const double* v, double* w) {
+    __shared__ double sd[256];
+    __shared__ double sv[256];
+    const int tid = threadIdx.x;
+    double s = tid == 0 ? *w : 0.0;
+    for (int j0 = 0; j0 < n; j0 += 256) {
+        const int j = j0 + tid;
+        sd[tid] = j < n ? dd[j] : 0.0;
+        sv[tid] = j < n ? v[j] : 0.0;
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < 256; ++k)
+                if (sv[k] != 0.0) s = fma(sd[k], sv[k], s);
+        __syncthreads();
+    }
+    if (tid == 0) *w = s;
+}
+
+// RHS ranges: 64 rows i per block (lanes), four interleaved subsets of t (threadIdx.y), ascending in each.  The key
+// of position t's candidate is 2t + side, as in k_batched_bounded_sens: within a subset and across the subsets the
+// smallest key of a tie is the first position.
+__global__ __launch_bounds__(256) void k_bsens_rhs_ranging(SimplexDev s, const double* b, const int* basis,
+                                                           const double* Lv, const double* Hv, double eps,
+                                                           double* rhs, int* rhs_var, int* rhs_side) {
+    __shared__ double sv[2][4][64];
+    __shared__ int sk[2][4][64];
+    const int m = s.m, ld = s.ld;
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int i = blockIdx.x * 64 + tx;
+    double dl = 0.0, dh = 0.0;
+    int kl = -1, kh = -1;
+    if (i < m)
+        for (int t = ty; t < m; t += 4) {
+            const double* Tr = s.T + (size_t)t * ld;
+            const double beta = Tr[m + i], xb = Tr[2 * m], L = Lv[t], H = Hv[t];
+            const double nL = (L == 0.0) ? -xb : L - xb, nH = H - xb;
+            if (beta > eps) {
+                take<true>(nL / beta, 2 * t, dl, kl);
+                if (H < INFINITY) take<false>(nH / beta, 2 * t + 1, dh, kh);
+            } else if (beta < -eps) {
+                take<false>(nL / beta, 2 * t, dh, kh);
+                if (H < INFINITY) take<true>(nH / beta, 2 * t + 1, dl, kl);
+            }
+        }
+    sv[0][ty][tx] = dl;
+    sk[0][ty][tx] = kl;
+    sv[1][ty][tx] = dh;
+    sk[1][ty][tx] = kh;
+    __syncthreads();
+    if (ty != 0 || i >= m) return;
+    for (int y = 1; y < 4; ++y) {
+        take<true>(sv[0][y][tx], sk[0][y][tx], dl, kl);
+        take<false>(sv[1][y][tx], sk[1][y][tx], dh, kh);
+    }
+    rhs[2 * i] = kl < 0 ? -INFINITY : b[i] + dl;
+    rhs[2 * i + 1] = kh < 0 ? INFINITY : b[i] + dh;
+    rhs_var[2 * i] = kl < 0 ? -1 : basis[kl >> 1];
+    rhs_var[2 * i + 1] = kh < 0 ? -1 : basis[kh >> 1];
+    rhs_side[2 * i] = kl < 0 ? -1 : (kl & 1);
+    rhs_side[2 * i + 1] = kh < 0 ? -1 : (kh & 1);
+}
+
+// cost ranges: blocks 0..m-1 reduce row t of alpha over the non-basic columns (the lower end a max, the upper end a
+// min; the column's sense picks the end); the blocks after them write the non-basic columns' ends
+__global__ __launch_bounds__(256) void k_bsens_cost_ranging(const double* alpha, int m, int n, const double* c,
+                                                            const double* dd, const int* basis, const int* code,
+                                                            int maximize, double eps, double* cost, int* cost_var) {
+    __shared__ double sv[2][4];
+    __shared__ int sk[2][4];
+    const bool mx = maximize != 0;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if ((int)blockIdx.x >= m) {
+        const int j = (blockIdx.x - m) * 256 + tid;
+        if (j >= n || code[j] == kBasic) return;
+        const bool mxj = mx != (code[j] == kUpper);
+        const double e = c[j] - dd[j];
+        cost[2 * j] = mxj ? -INFINITY : e;
+        cost[2 * j + 1] = mxj ? e : INFINITY;
+        cost_var[2 * j] = mxj ? -1 : j;
+        cost_var[2 * j + 1] = mxj ? j : -1;
+        return;
+    }
+    const int t = blockIdx.x;
+    const double* ar = alpha + (size_t)t * n;
+    double dl = 0.0, dh = 0.0;
+    int kl = -1, kh = -1;
+    for (int j = tid; j < n; j += 256) {
+        if (code[j] == kBasic) continue;
+        const double s = ar[j];
+        if (!(s > eps) && !(s < -eps)) continue;
+        const bool mxj = mx != (code[j] == kUpper);
+        if ((s > eps) == mxj) take<true>(dd[j] / s, j, dl, kl);
+        else take<false>(dd[j] / s, j, dh, kh);
+    }
+    wave_take<true>(dl, kl);
+    wave_take<false>(dh, kh);
+    if (lane == 0) {
+        sv[0][wave] = dl;
+        sk[0][wave] = kl;
+        sv[1][wave] = dh;
+        sk[1][wave] = kh;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < 4; ++w) {
+        take<true>(sv[0][w], sk[0][w], dl, kl);
+        take<false>(sv[1][w], sk[1][w], dh, kh);
+    }
+    const int col = basis[t];
+    cost[2 * col] = kl < 0 ? -INFINITY : c[col] + dl;
+    cost[2 * col + 1] = kh < 0 ? INFINITY : c[col] + dh;
+    cost_var[2 * col] = kl;
+    cost_var[2 * col + 1] = kh;
+}
+
 }  // namespace
 
 size_t lp_basis_bounded_lds_bytes(int m, int n) {
@@ -355,4 +544,83 @@ int lp_basis_bounded_launch(lp_context* ctx, const BasisBoundedDev& d, bool rang
     if (bsens_threads(d.m) == 256)
         return ranging ? bounded_sens_launch<256, true>(ctx, d) : bounded_sens_launch<256, false>(ctx, d);
     return ranging ? bounded_sens_launch<512, true>(ctx, d) : bounded_sens_launch<512, false>(ctx, d);
+}
+
+// One LP of any shape on the device (d.batch = 1; the bounds, basis and flags checked by the caller, eps >= 0): every
+// launch on the context's stream, one sync beyond the two crashes' own.  Returns LP_OPTIMAL (the duals outputs, or
+// with `ranging` the ranging outputs, written), LP_INFEASIBLE or LP_SINGULAR (outputs untouched); d.status is not
+// written.
+int lp_basis_bounded_device(lp_context* ctx, const BasisBoundedDev& d, bool ranging) {
+    hipStream_t s = ctx->stream;
+    const int m = d.m, n = d.n;
+    const int cols = ranging ? 2 * m : m;   // the right-hand-side column of [B | I | b'] or [B | b']
+    const int ld = (int)lp_ceil_div<size_t>((size_t)cols + 1, 8) * 8;
+    lp_simplex_problem q;
+    q.ctx = ctx;
+    q.tableau_bytes = sizeof(double) * (size_t)(m + 1) * ld;
+    SimplexDev& sd = q.dev;
+    sd.m = m;
+    sd.n = cols;
+    sd.ld = ld;
+    // one allocation: T, the pristine copy the crash permutes through, lcol, prow, state, basis, rowpos, rowused;
+    // v, b', L, H, the codes and the crossed-bound word; for ranging alpha, y, d and b.y as well
+    double *v, *bp, *L, *H, *alpha = nullptr, *dy = d.y, *dd = d.d, *dw = d.w;
+    int *code, *crossed;
+    auto pieces = [&](lp_carver& cv) {
+        sd.T = cv.take<double>(q.tableau_bytes);
+        q.dT0 = cv.take<double>(q.tableau_bytes);
+        sd.lcol = cv.take<double>(sizeof(double) * ((size_t)m + 1));
+        sd.prow = cv.take<double>(sizeof(double) * (size_t)ld);
+        sd.state = cv.take<SimplexState>(sizeof(SimplexState));
+        sd.basis = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowpos = cv.take<int>(sizeof(int) * (size_t)m);
+        sd.rowused = cv.take<unsigned char>((size_t)m);
+        v = cv.take<double>(sizeof(double) * (size_t)n);
+        bp = cv.take<double>(sizeof(double) * (size_t)m);
+        L = cv.take<double>(sizeof(double) * (size_t)m);
+        H = cv.take<double>(sizeof(double) * (size_t)m);
+        code = cv.take<int>(sizeof(int) * (size_t)n);
+        crossed = cv.take<int>(sizeof(int));
+        if (!ranging) return;
+        alpha = cv.take<double>(sizeof(double) * (size_t)m * n);
+        dy = cv.take<double>(sizeof(double) * (size_t)m);
+        dd = cv.take<double>(sizeof(double) * (size_t)n);
+        dw = cv.take<double>(sizeof(double));
+    };
+    char* arena = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&arena, pieces));
+    int rc = LP_OPTIMAL, hcrossed = 0;
+    hipError_t e = hipMemsetAsync(crossed, 0, sizeof(int), s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_bsens_codes, lp_ceil_div(n, 256), 256, 0, s, n, d.lo, d.hi, d.at_upper, code, crossed);
+        hipLaunchKernelGGL(k_bsens_basic, lp_ceil_div(m, 256), 256, 0, s, d.basis, m, d.lo, d.hi, code, L, H);
+        hipLaunchKernelGGL(k_bsens_held, lp_ceil_div(n, 256), 256, 0, s, n, d.lo, d.hi, code, v);
+        hipLaunchKernelGGL(k_bsens_bprime, lp_ceil_div(m, 64), 64, 0, s, d.A, m, n, d.b, v, bp);
+        hipLaunchKernelGGL(k_bsens_gather, m + 1, 256, 0, s, sd, d.A, bp, d.basis);
+        e = hipMemcpyAsync(&hcrossed, crossed, sizeof(int), hipMemcpyDeviceToHost, s);   // read after the crash's sync
+    }
+    if (e != hipSuccess) rc = -(int)e;
+    if (rc == LP_OPTIMAL) rc = lp_simplex_crash(&q);   // m launch pairs, the verdict, rows into position order; one host sync
+    if (rc >= 0 && hcrossed) rc = LP_INFEASIBLE;        // the reference checks the bounds before it pivots
+    if (rc == LP_OPTIMAL) rc = lp_basis_duals_device(ctx, d.A, m, n, d.b, d.c, d.basis, dy, dd, dw);
+    if (rc == LP_OPTIMAL) {
+        if (ranging) {
+            lp_binv_times_a_launch(ctx, sd, d.A, n, alpha);
+            hipLaunchKernelGGL(k_bsens_rhs_ranging, lp_ceil_div(m, 64), dim3(64, 4), 0, s, sd, d.b, d.basis, L, H,
+                               d.eps, d.rhs, d.rhs_var, d.rhs_side);
+            hipLaunchKernelGGL(k_bsens_cost_ranging, m + lp_ceil_div(n, 256), 256, 0, s, alpha, m, n, d.c, dd, d.basis,
+                               code, d.maximize, d.eps, d.cost, d.cost_var);
+        } else {
+            hipLaunchKernelGGL(k_bsens_x, lp_ceil_div(n, 256), 256, 0, s, sd, n, d.basis, code, v, d.x);
+            hipLaunchKernelGGL(k_bsens_w, 1, 256, 0, s, n, dd, v, dw);
+        }
+        e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("bounded basis analysis: ") + hipGetErrorString(e);
+            rc = -(int)e;
+        }
+    }
+    (void)hipFree(arena);
+    return rc;
 }

@@ -7,7 +7,9 @@
 // shape fits it and otherwise runs its single-LP device path one LP after another (per_lp).
 // The analyses of a bounded-variable LP at a basis and flags (basis_bounded.hip, basis_bounded_certificate.hip,
 // basis_bounded_parametric.hip) have two entry points each (one LP, a batch from the host) and no per-LP path:
-// bounded_sens, bounded_certificate and bounded_parametric upload, launch and download in one call.
+// bounded_sens, bounded_certificate and bounded_parametric upload, launch and download in one call.  The duals and
+// ranging of one bounded LP beyond the kernel's fit (lp_basis_bounded_duals_large, lp_basis_bounded_ranging_large) go
+// through bounded_sens as well, with lp_basis_bounded_device in place of the launch.
 #include <cmath>
 #include <functional>
 
@@ -348,7 +350,8 @@ int lp_batched_ranging(lp_batched_problem* p, double eps, double* rhs_out, int* 
 
 // ===========================================================================
 // The dual solution and ranging of a bounded-variable LP at a given basis and flags (basis_bounded.hip): one LP per
-// workgroup for lp_basis_bounded_fits shapes only; as in the bounded family there is no handle and no per-LP path
+// workgroup for lp_basis_bounded_fits shapes; as in the bounded family there is no handle and no per-LP path for a
+// batch.  The _large entries run one LP of any shape on the tableau in HBM.
 // ===========================================================================
 
 int lp_basis_bounded_fits(int m, int n) { return lp_basis_bounded_fits_shape(m, n) ? 1 : 0; }
@@ -412,9 +415,11 @@ struct BoundedRangingOut {
 };
 
 // One allocation for the inputs and the outputs of the batch, one launch of k_batched_bounded_sens, one download:
-// the ranging launch when `ro` is given (maximize and eps are its), else the duals launch into `du`.
+// the ranging launch when `ro` is given (maximize and eps are its), else the duals launch into `du`.  `large` (one LP):
+// lp_basis_bounded_device instead of the launch; it returns the LP's status, and nothing comes down unless that is
+// LP_OPTIMAL.
 static int bounded_sens(lp_context* ctx, const BoundedSensIn& in, const BoundedDualsOut* du, const BoundedRangingOut* ro,
-                        int maximize, double eps, int* status_out) {
+                        int maximize, double eps, int* status_out, bool large = false) {
     const bool ranging = ro != nullptr;
     const int batch = in.batch, m = in.m, n = in.n;
     LP_HIP(ctx, hipSetDevice(ctx->device));
@@ -462,45 +467,61 @@ static int bounded_sens(lp_context* ctx, const BoundedSensIn& in, const BoundedD
         d.rhs_side = d.rhs_var + nr;
         d.cost_var = d.rhs_side + nr;
         d.status = d.cost_var + nc;
-        rc = lp_basis_bounded_launch(ctx, d, true);
+        rc = large ? lp_basis_bounded_device(ctx, d, true) : lp_basis_bounded_launch(ctx, d, true);
         if (rc == LP_OPTIMAL)
             rc = lp_download(ctx, "bounded basis ranging", {{ro->rhs, d.rhs, sizeof(double) * nr},
                                                             {ro->cost, d.cost, sizeof(double) * nc},
                                                             {ro->rhs_var, d.rhs_var, sizeof(int) * nr},
                                                             {ro->rhs_side, d.rhs_side, sizeof(int) * nr},
                                                             {ro->cost_var, d.cost_var, sizeof(int) * nc},
-                                                            {status_out, d.status, sizeof(int) * B}});
+                                                            {status_out, d.status, large ? 0 : sizeof(int) * B}});
     } else {
         d.x = dout;
         d.d = d.x + B * n;
         d.y = d.d + B * n;
         d.w = d.y + B * m;
         d.status = iout;
-        rc = lp_basis_bounded_launch(ctx, d, false);
+        rc = large ? lp_basis_bounded_device(ctx, d, false) : lp_basis_bounded_launch(ctx, d, false);
         if (rc == LP_OPTIMAL)
             rc = lp_download(ctx, "bounded basis duals", {{du->x, d.x, sizeof(double) * B * n},
                                                           {du->d, d.d, sizeof(double) * B * n},
                                                           {du->y, d.y, sizeof(double) * B * m},
                                                           {du->w, d.w, sizeof(double) * B},
-                                                          {status_out, d.status, sizeof(int) * B}});
+                                                          {status_out, d.status, large ? 0 : sizeof(int) * B}});
     }
     return rc;
+}
+
+// lp_basis_bounded_duals (`who`), or with `large` lp_basis_bounded_duals_large: the same checks without the fit
+static int bounded_duals_one(lp_context* ctx, const char* who, bool large, const double* A, int m, int n,
+                             const double* b, const double* c, const double* lo, const double* hi, const int* basis,
+                             const int* at_upper, double* x_out, double* y_out, double* d_out, double* w_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !x_out || !y_out || !d_out || !w_out)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    bounded_duals_nan(0, m, n, x_out, y_out, d_out, w_out);
+    int rc = large ? bounded_basis_values(ctx, who, 1, m, n, lo, hi, basis, at_upper, false)
+                   : bounded_basis_args(ctx, who, 1, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    const BoundedDualsOut out{x_out, y_out, d_out, w_out};
+    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, &out, nullptr, 0, 0.0, &status, large);
+    return rc ? rc : status;
 }
 
 int lp_basis_bounded_duals(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                            const double* lo, const double* hi, const int* basis, const int* at_upper, double* x_out,
                            double* y_out, double* d_out, double* w_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !x_out || !y_out || !d_out || !w_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_duals: bad dimensions");
-    bounded_duals_nan(0, m, n, x_out, y_out, d_out, w_out);
-    int rc = bounded_basis_args(ctx, "lp_basis_bounded_duals", 1, m, n, lo, hi, basis, at_upper);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    const BoundedDualsOut out{x_out, y_out, d_out, w_out};
-    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, &out, nullptr, 0, 0.0, &status);
-    return rc ? rc : status;
+    return bounded_duals_one(ctx, "lp_basis_bounded_duals", false, A, m, n, b, c, lo, hi, basis, at_upper, x_out,
+                             y_out, d_out, w_out);
+}
+
+int lp_basis_bounded_duals_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                 const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                 double* x_out, double* y_out, double* d_out, double* w_out) {
+    return bounded_duals_one(ctx, "lp_basis_bounded_duals_large", true, A, m, n, b, c, lo, hi, basis, at_upper, x_out,
+                             y_out, d_out, w_out);
 }
 
 int lp_basis_bounded_duals_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
@@ -517,23 +538,41 @@ int lp_basis_bounded_duals_batched(lp_context* ctx, int batch, const double* A, 
     return bounded_sens(ctx, {batch, m, n, A, b, c, lo, hi, basis, at_upper}, &out, nullptr, 0, 0.0, status_out);
 }
 
+// lp_basis_bounded_ranging (`who`), or with `large` lp_basis_bounded_ranging_large: the same checks without the fit
+static int bounded_ranging_one(lp_context* ctx, const char* who, bool large, const double* A, int m, int n,
+                               const double* b, const double* c, const double* lo, const double* hi, const int* basis,
+                               const int* at_upper, int maximize, double eps, double* rhs_out, int* rhs_var_out,
+                               int* rhs_side_out, double* cost_out, int* cost_var_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !rhs_out || !rhs_var_out || !rhs_side_out ||
+        !cost_out || !cost_var_out)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    bounded_ranging_nan(0, m, n, rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    int rc = large ? bounded_basis_values(ctx, who, 1, m, n, lo, hi, basis, at_upper, false)
+                   : bounded_basis_args(ctx, who, 1, m, n, lo, hi, basis, at_upper);
+    if (rc) return rc;
+    int status = LP_OPTIMAL;
+    const BoundedRangingOut out{rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out};
+    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, &out, maximize, eps, &status, large);
+    return rc ? rc : status;
+}
+
 int lp_basis_bounded_ranging(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                              const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize,
                              double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out, double* cost_out,
                              int* cost_var_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !rhs_out || !rhs_var_out || !rhs_side_out ||
-        !cost_out || !cost_var_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: bad dimensions");
-    bounded_ranging_nan(0, m, n, rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out);
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_ranging: eps must be >= 0");
-    int rc = bounded_basis_args(ctx, "lp_basis_bounded_ranging", 1, m, n, lo, hi, basis, at_upper);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    const BoundedRangingOut out{rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out};
-    rc = bounded_sens(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, &out, maximize, eps, &status);
-    return rc ? rc : status;
+    return bounded_ranging_one(ctx, "lp_basis_bounded_ranging", false, A, m, n, b, c, lo, hi, basis, at_upper,
+                               maximize, eps, rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out);
+}
+
+int lp_basis_bounded_ranging_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                   const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                   int maximize, double eps, double* rhs_out, int* rhs_var_out, int* rhs_side_out,
+                                   double* cost_out, int* cost_var_out) {
+    return bounded_ranging_one(ctx, "lp_basis_bounded_ranging_large", true, A, m, n, b, c, lo, hi, basis, at_upper,
+                               maximize, eps, rhs_out, rhs_var_out, rhs_side_out, cost_out, cost_var_out);
 }
 
 int lp_basis_bounded_ranging_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,

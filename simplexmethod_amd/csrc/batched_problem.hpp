@@ -361,6 +361,11 @@ struct BasisBoundedDev {
 size_t lp_basis_bounded_lds_bytes(int m, int n);
 bool lp_basis_bounded_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
 int lp_basis_bounded_launch(lp_context* ctx, const BasisBoundedDev& d, bool ranging);   // fitting shapes, else LP_BAD_ARG
+// One LP of any shape on the device (d.batch = 1; bounds, basis and flags checked by the caller, eps >= 0): the crash
+// on [B | I | b'] ([B | b'] for the duals) by the single-LP launch pair, y and d by lp_basis_duals_device, then x and
+// w, or B^-1 A and the reductions.  Returns LP_OPTIMAL / LP_INFEASIBLE / LP_SINGULAR (outputs untouched unless
+// LP_OPTIMAL); d.status is not written.
+int lp_basis_bounded_device(lp_context* ctx, const BasisBoundedDev& d, bool ranging);
 
 // Farkas and unbounded-ray certificates of bounded-variable LPs at given bases and at-upper flags, one LP per
 // workgroup (basis_bounded_certificate.hip; the definition is tests/ref/bounded_certificate_ref.c): the ranging crash

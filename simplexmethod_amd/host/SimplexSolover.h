@@ -308,26 +308,15 @@ public:
 
     BoundedDuals boundedDuals(const std::vector<double>& lo, const std::vector<double>& hi,
                               const BoundedResult& from) const {
-        const View p = view();
-        requireBounds("Solver::boundedDuals", p, lo, hi);
-        BoundedDuals out;
-        out.x = lpla::VectorXd::Zero(p.n);
-        out.y = lpla::VectorXd::Zero(p.m);
-        out.d = lpla::VectorXd::Zero(p.n);
-        out.status = from.status;
-        if (from.status == LP_OPTIMAL) {
-            requireStart("Solver::boundedDuals", "result", p, from);
-            lp_context* ctx = lpgpu::context(_device);
-            out.status = checked(lp_basis_bounded_duals(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
-                                                        from.basis.data(), from.atUpper.data(), out.x.data(),
-                                                        out.y.data(), out.d.data(), &out.objective), ctx);
-        }
-        if (out.status != LP_OPTIMAL) {
-            out.x = out.d = nans(p.n);
-            out.y = nans(p.m);
-            out.objective = kNaN;
-        }
-        return out;
+        return boundedDualsRun("Solver::boundedDuals", lo, hi, from, false);
+    }
+
+    // The same at any shape boundedSimplexLarge runs (lp_basis_bounded_duals_large), normally at its result: the
+    // analysis on a tableau in device memory, no lp_basis_bounded_fits limit.  Result and exceptions as
+    // boundedDuals(lo, hi, from) minus the fit, and equal to it where both run.
+    BoundedDuals boundedDualsLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                   const BoundedResult& from) const {
+        return boundedDualsRun("Solver::boundedDualsLarge", lo, hi, from, true);
     }
 
     // RHS and cost ranging of the bounded problem at a result's basis and flags (lp_basis_bounded_ranging) with EPS and
@@ -340,23 +329,14 @@ public:
 
     BoundedRanging boundedRanging(const std::vector<double>& lo, const std::vector<double>& hi,
                                   const BoundedResult& from) const {
-        const View p = view();
-        requireBounds("Solver::boundedRanging", p, lo, hi);
-        RangingEnds ends(p.m, p.n);
-        std::vector<int> rs(2 * (size_t)p.m, -1);
-        BoundedRanging out;
-        out.status = from.status;
-        if (from.status == LP_OPTIMAL) {
-            requireStart("Solver::boundedRanging", "result", p, from);
-            lp_context* ctx = lpgpu::context(_device);
-            out.status = checked(lp_basis_bounded_ranging(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
-                                                          from.basis.data(), from.atUpper.data(), p.maximize, EPS,
-                                                          ends.rhs.data(), ends.rv.data(), rs.data(), ends.cost.data(),
-                                                          ends.cv.data()), ctx);
-        }
-        ends.unpack(out);
-        unpackPairs(out.status == LP_OPTIMAL, rs, -1, out.b_side_lo, out.b_side_hi);
-        return out;
+        return boundedRangingRun("Solver::boundedRanging", lo, hi, from, false);
+    }
+
+    // The same at any shape boundedSimplexLarge runs (lp_basis_bounded_ranging_large); result and exceptions as
+    // boundedRanging(lo, hi, from) minus the fit, and equal to it where both run.
+    BoundedRanging boundedRangingLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                       const BoundedResult& from) const {
+        return boundedRangingRun("Solver::boundedRangingLarge", lo, hi, from, true);
     }
 
     // Depth-first branch-and-bound over the bounds (lp_mip_bounded_solve) with EPS, INT_TOL, MIP_GAP, MAX_ITER and the
@@ -627,6 +607,54 @@ private:
         }
         path.unpack(out);
         out.side.assign(side.begin(), side.begin() + path.nseg);
+        return out;
+    }
+
+    // boundedDuals, or with large boundedDualsLarge
+    BoundedDuals boundedDualsRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
+                                 const BoundedResult& from, bool large) const {
+        const View p = view();
+        requireBounds(who, p, lo, hi);
+        BoundedDuals out;
+        out.x = lpla::VectorXd::Zero(p.n);
+        out.y = lpla::VectorXd::Zero(p.m);
+        out.d = lpla::VectorXd::Zero(p.n);
+        out.status = from.status;
+        if (from.status == LP_OPTIMAL) {
+            requireStart(who, "result", p, from);
+            lp_context* ctx = lpgpu::context(_device);
+            const auto entry = large ? lp_basis_bounded_duals_large : lp_basis_bounded_duals;
+            out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                       from.atUpper.data(), out.x.data(), out.y.data(), out.d.data(), &out.objective),
+                                 ctx);
+        }
+        if (out.status != LP_OPTIMAL) {
+            out.x = out.d = nans(p.n);
+            out.y = nans(p.m);
+            out.objective = kNaN;
+        }
+        return out;
+    }
+
+    // boundedRanging, or with large boundedRangingLarge
+    BoundedRanging boundedRangingRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
+                                     const BoundedResult& from, bool large) const {
+        const View p = view();
+        requireBounds(who, p, lo, hi);
+        RangingEnds ends(p.m, p.n);
+        std::vector<int> rs(2 * (size_t)p.m, -1);
+        BoundedRanging out;
+        out.status = from.status;
+        if (from.status == LP_OPTIMAL) {
+            requireStart(who, "result", p, from);
+            lp_context* ctx = lpgpu::context(_device);
+            const auto entry = large ? lp_basis_bounded_ranging_large : lp_basis_bounded_ranging;
+            out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                       from.atUpper.data(), p.maximize, EPS, ends.rhs.data(), ends.rv.data(), rs.data(),
+                                       ends.cost.data(), ends.cv.data()), ctx);
+        }
+        ends.unpack(out);
+        unpackPairs(out.status == LP_OPTIMAL, rs, -1, out.b_side_lo, out.b_side_hi);
         return out;
     }
 
