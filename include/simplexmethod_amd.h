@@ -597,10 +597,11 @@ int lp_simplex_bounded_fits(int m, int n);
  *     pivots, bound flips.
  *   - Dantzig's rule; Bland's rule and Devex pricing at these shapes are lp_simplex_bounded_large_ex (with the _ex
  *     block below; m <= 9968 under LP_PIVOT_DEVEX).  The dual solution and ranging at these shapes are
- *     lp_basis_bounded_duals_large and lp_basis_bounded_ranging_large below.  Out of scope on this path: the other
- *     analyses (certificates, parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The
- *     re-solve from a basis at these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is
- *     unchanged and still refuses larger shapes.                                                                 */
+ *     lp_basis_bounded_duals_large and lp_basis_bounded_ranging_large below, and the evidence for an LP_INFEASIBLE or
+ *     LP_UNBOUNDED verdict is lp_basis_bounded_certificate_large.  Out of scope on this path: the other analyses
+ *     (parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The re-solve from a basis at
+ *     these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and still
+ *     refuses larger shapes.                                                                                      */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 /* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
  * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
@@ -812,6 +813,21 @@ int lp_basis_bounded_certificate_batched(lp_context* ctx, int batch, const doubl
 /* 1: lp_simplex_bounded_fits(m, n) and the certificate kernel's LDS carve (lp_basis_certificate_fits' plus b', the held
  * values and the basic columns' bounds) fits one CU's 160 KB (64 x 192 does); 0 otherwise.  A host call.            */
 int lp_basis_bounded_certificate_fits(int m, int n);
+/* The same certificate beyond one workgroup's LDS, one LP per call (the definition is still
+ * tests/ref/bounded_certificate_ref.c, steps 1-6 above, and every output equals it bit for bit, NaN and signed zeros
+ * included): a verdict of lp_simplex_bounded_large or lp_simplex_bounded_resolve_large can be backed by evidence where
+ * it was reached.  The column codes, the held values, b' and b0 are lp_basis_bounded_duals_large's small kernels (b0 is
+ * the b' chain with lo held); lp_basis_certificate's single-LP path does the rest: the crash on [B | I | b'] with the
+ * artificial columns s_i e_i explicit, by one selector and one rank-1 update launch per basis position on a tableau in
+ * HBM, B^-1 A as tiled chains, then three kernels that choose the case and reduce under the box's rules (the first
+ * position and the first column are decided by index, every chain is one thread's).  Arguments, outputs, statuses and
+ * refusals are lp_basis_bounded_certificate's with one difference: there is no lp_basis_bounded_certificate_fits limit.
+ * The limit is device memory: two (m+1) x (2m+1) tableaus and the m x n matrix B^-1 A beside the inputs.  At a shape
+ * where lp_basis_bounded_certificate_fits holds every output equals lp_basis_bounded_certificate's; with lo = 0,
+ * hi = +inf and no flag every output equals lp_basis_certificate's.  Crossed bounds are LP_INFEASIBLE before a repeated
+ * index or a singular basis is LP_SINGULAR, as the definition orders them.  There is no batched form;
+ * lp_basis_bounded_certificate, its _batched form and _fits are unchanged and still refuse larger shapes.            */
+int lp_basis_bounded_certificate_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, double eps, int* kind_out, double* farkas_out, double* ray_out, double* value_out, int* index_out);
 
 /* ---- Parametric right-hand side and parametric cost of a bounded-variable LP (the definition is
  * tests/ref/bounded_parametric_ref.c, numbered steps in its header) ----

@@ -193,6 +193,8 @@ SIGNATURES = {
     "lp_basis_bounded_certificate_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
                                                        _ip, _ip, C.c_int, C.c_double, _ip, _dp, _dp, _dp, _ip, _ip]),
     "lp_basis_bounded_certificate_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_certificate_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                     C.c_double, _ip, _dp, _dp, _dp, _ip]),
     "lp_basis_bounded_parametric": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, _dp,
                                               C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _ip,
                                               _ip]),
@@ -942,13 +944,23 @@ class Context:
         computed; SINGULAR for a singular crash or a repeated index, INFEASIBLE for some hi < lo (then NONE).  A bad
         bound, index or flag, a negative eps or a shape beyond basis_bounded_certificate_fits raises LPError with code
         BAD_ARG."""
+        return self._basis_bounded_certificate(self.lib.lp_basis_bounded_certificate, A, b, c, lo, hi, basis, at_upper,
+                                               maximize, eps)
+
+    def basis_bounded_certificate_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS):
+        """lp_basis_bounded_certificate_large: basis_bounded_certificate() on the tableau in HBM, at any shape
+        bounded_large() and bounded_resolve_large() run (no basis_bounded_certificate_fits limit).  Returns the dict of
+        basis_bounded_certificate(), equal to it where both run; refusals as there."""
+        return self._basis_bounded_certificate(self.lib.lp_basis_bounded_certificate_large, A, b, c, lo, hi, basis,
+                                               at_upper, maximize, eps)
+
+    def _basis_bounded_certificate(self, entry, A, b, c, lo, hi, basis, at_upper, maximize, eps):
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         kind, index = np.zeros(1, np.int32), np.zeros(1, np.int32)
         farkas, ray, value = np.zeros(m), np.zeros(n), np.zeros(1)
-        rc = self.check(self.lib.lp_basis_bounded_certificate(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi),
-                                                              _i(basis), _i(at_upper), int(maximize), float(eps),
-                                                              _i(kind), _d(farkas), _d(ray), _d(value), _i(index)))
+        rc = self.check(entry(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
+                              int(maximize), float(eps), _i(kind), _d(farkas), _d(ray), _d(value), _i(index)))
         return dict(status=rc, kind=int(kind[0]), farkas=farkas, ray=ray, value=float(value[0]), index=int(index[0]))
 
     def basis_bounded_certificate_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, eps=EPS,

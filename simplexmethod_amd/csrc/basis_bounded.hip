@@ -24,6 +24,7 @@
 // (basis_ranging.hip) and the two reduction kernels.
 #include <cfloat>
 
+#include "basis_bounded_kernels.hpp"
 #include "basis_crash.hpp"
 #include "batched_problem.hpp"
 #include "lp_internal.hpp"
@@ -42,8 +43,6 @@ __host__ __device__ inline size_t bsens_scratch(int m) {
     const size_t tile = (size_t)kCW * (kTR + 1), eta = 2 * (size_t)m + 1;
     return tile > eta ? tile : eta;
 }
-
-enum { kLower = 0, kBasic = 1, kUpper = 2 };   // what code[j] says of column j
 
 template <int NT, bool RANGING>
 __global__ __launch_bounds__(NT) void k_batched_bounded_sens(BasisBoundedDev d) {
@@ -343,14 +342,7 @@ int bounded_sens_launch(lp_context* ctx, const BasisBoundedDev& d) {
 
 // ---- the single-LP path beyond lp_basis_bounded_fits
 
-// code[j] by the flag alone (k_bsens_basic overwrites the basic columns'); any hi_j < lo_j raises *crossed
-__global__ __launch_bounds__(256) void k_bsens_codes(int n, const double* lo, const double* hi, const int* up,
-                                                     int* code, int* crossed) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    code[j] = up[j] ? kUpper : kLower;
-    if (hi[j] < lo[j]) *crossed = 1;
-}
+// (k_bsens_codes, k_bsens_held and k_bsens_bprime: basis_bounded_kernels.hpp)
 
 __global__ __launch_bounds__(256) void k_bsens_basic(const int* basis, int m, const double* lo, const double* hi,
                                                      int* code, double* L, double* H) {
@@ -360,28 +352,6 @@ __global__ __launch_bounds__(256) void k_bsens_basic(const int* basis, int m, co
     code[q] = kBasic;
     L[t] = lo[q];
     H[t] = hi[q];
-}
-
-// the held values: 0.0 for basic columns
-__global__ __launch_bounds__(256) void k_bsens_held(int n, const double* lo, const double* hi, const int* code,
-                                                    double* v) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) v[j] = code[j] == kBasic ? 0.0 : code[j] == kUpper ? hi[j] : lo[j];
-}
-
-// b'[i] = b[i] - sum_j A[i][j] v_j: one chain per row (one thread), j ascending over v_j != 0.0; consecutive threads
-// read consecutive i of column j, and v_j is the same for the whole block
-__global__ __launch_bounds__(64) void k_bsens_bprime(const double* A, int m, int n, const double* b, const double* v,
-                                                     double* bp) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    double acc = b[i];
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) {
-        const double vj = v[j];
-        if (vj != 0.0) acc = fma(-A[(size_t)j * m + i], vj, acc);
-    }
-    bp[i] = acc;
 }
 
 // T (m+1 rows, pitch ld) = [B | I | b'; 0] when s.n = 2m, [B | b'; 0] when s.n = m; the crash bookkeeping's

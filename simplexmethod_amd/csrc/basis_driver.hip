@@ -9,7 +9,8 @@
 // basis_bounded_parametric.hip) have two entry points each (one LP, a batch from the host) and no per-LP path:
 // bounded_sens, bounded_certificate and bounded_parametric upload, launch and download in one call.  The duals and
 // ranging of one bounded LP beyond the kernel's fit (lp_basis_bounded_duals_large, lp_basis_bounded_ranging_large) go
-// through bounded_sens as well, with lp_basis_bounded_device in place of the launch.
+// through bounded_sens as well, with lp_basis_bounded_device in place of the launch, and its certificate
+// (lp_basis_bounded_certificate_large) through bounded_certificate with lp_basis_bounded_certificate_device.
 #include <cmath>
 #include <functional>
 
@@ -718,7 +719,8 @@ int lp_batched_certificates(lp_batched_problem* p, double eps, int* kind_out, do
 
 // ===========================================================================
 // Farkas and unbounded-ray certificates of a bounded-variable LP at a given basis and flags
-// (basis_bounded_certificate.hip): one LP per workgroup for lp_basis_bounded_certificate_fits shapes only
+// (basis_bounded_certificate.hip): one LP per workgroup for lp_basis_bounded_certificate_fits shapes;
+// lp_basis_bounded_certificate_large runs one LP of any shape on the tableau in HBM
 // ===========================================================================
 
 int lp_basis_bounded_certificate_fits(int m, int n) { return lp_basis_bounded_certificate_fits_shape(m, n) ? 1 : 0; }
@@ -730,9 +732,11 @@ struct BoundedCertificateOut {
 };
 
 // One allocation for the inputs and the outputs of the batch, uploads queued on the context's stream, one launch of
-// k_batched_bounded_certificate, one download.  run_status may be nullptr.
+// k_batched_bounded_certificate, one download.  run_status may be nullptr.  `large` (one LP, no run_status):
+// lp_basis_bounded_certificate_device instead of the launch; it returns the LP's status, and nothing comes down unless
+// that is LP_OPTIMAL.
 static int bounded_certificate(lp_context* ctx, const BoundedSensIn& in, const int* run_status, int maximize, double eps,
-                               const BoundedCertificateOut& out, int* status_out) {
+                               const BoundedCertificateOut& out, int* status_out, bool large = false) {
     const int batch = in.batch, m = in.m, n = in.n;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nf = B * m, nr = B * n;
@@ -780,34 +784,59 @@ static int bounded_certificate(lp_context* ctx, const BoundedSensIn& in, const i
     d.kind = iout;
     d.index = d.kind + B;
     d.status = d.index + B;
-    int rc = lp_basis_bounded_certificate_launch(ctx, d);
+    int rc = large ? lp_basis_bounded_certificate_device(ctx, d) : lp_basis_bounded_certificate_launch(ctx, d);
     if (rc == LP_OPTIMAL)
         rc = lp_download(ctx, "bounded basis certificate", {{out.farkas, d.farkas, sizeof(double) * nf},
                                                             {out.ray, d.ray, sizeof(double) * nr},
                                                             {out.value, d.value, sizeof(double) * B},
                                                             {out.kind, d.kind, sizeof(int) * B},
                                                             {out.index, d.index, sizeof(int) * B},
-                                                            {status_out, d.status, sizeof(int) * B}});
+                                                            {status_out, d.status, large ? 0 : sizeof(int) * B}});
     return rc;
+}
+
+// lp_basis_bounded_certificate (`who`), or with `large` lp_basis_bounded_certificate_large: the same checks without
+// the fit.  The kernel looks for a repeated index itself; the single-LP device path leaves that to the host, which
+// answers as the definition orders it: crossed bounds (LP_INFEASIBLE) before a repeat (LP_SINGULAR).
+static int bounded_certificate_one(lp_context* ctx, const char* who, bool large, const double* A, int m, int n,
+                                   const double* b, const double* c, const double* lo, const double* hi,
+                                   const int* basis, const int* at_upper, int maximize, double eps, int* kind_out,
+                                   double* farkas_out, double* ray_out, double* value_out, int* index_out) {
+    if (!ctx) return LP_BAD_ARG;
+    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !kind_out || !farkas_out || !ray_out || !value_out ||
+        !index_out)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    int rc = large ? bounded_basis_values(ctx, who, 1, m, n, lo, hi, basis, at_upper, true)
+                   : bounded_basis_args(ctx, who, 1, m, n, lo, hi, basis, at_upper, true);
+    if (rc) return rc;
+    if (large && certificate_basis_check(basis, m, n) == LP_SINGULAR) {
+        for (int j = 0; j < n; ++j)
+            if (hi[j] < lo[j]) return LP_INFEASIBLE;
+        return LP_SINGULAR;
+    }
+    int status = LP_OPTIMAL;
+    rc = bounded_certificate(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, maximize, eps,
+                             {kind_out, farkas_out, ray_out, value_out, index_out}, &status, large);
+    return rc ? rc : status;
 }
 
 int lp_basis_bounded_certificate(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                                  const double* lo, const double* hi, const int* basis, const int* at_upper,
                                  int maximize, double eps, int* kind_out, double* farkas_out, double* ray_out,
                                  double* value_out, int* index_out) {
-    if (!ctx) return LP_BAD_ARG;
-    if (!A || !b || !c || !lo || !hi || !basis || !at_upper || !kind_out || !farkas_out || !ray_out || !value_out ||
-        !index_out)
-        LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: null argument");
-    if (m <= 0 || n < m) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: bad dimensions");
-    certificate_none(0, m, n, kind_out, farkas_out, ray_out, value_out, index_out);
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_basis_bounded_certificate: eps must be >= 0");
-    int rc = bounded_basis_args(ctx, "lp_basis_bounded_certificate", 1, m, n, lo, hi, basis, at_upper, true);
-    if (rc) return rc;
-    int status = LP_OPTIMAL;
-    rc = bounded_certificate(ctx, {1, m, n, A, b, c, lo, hi, basis, at_upper}, nullptr, maximize, eps,
-                             {kind_out, farkas_out, ray_out, value_out, index_out}, &status);
-    return rc ? rc : status;
+    return bounded_certificate_one(ctx, "lp_basis_bounded_certificate", false, A, m, n, b, c, lo, hi, basis, at_upper,
+                                   maximize, eps, kind_out, farkas_out, ray_out, value_out, index_out);
+}
+
+int lp_basis_bounded_certificate_large(lp_context* ctx, const double* A, int m, int n, const double* b,
+                                       const double* c, const double* lo, const double* hi, const int* basis,
+                                       const int* at_upper, int maximize, double eps, int* kind_out,
+                                       double* farkas_out, double* ray_out, double* value_out, int* index_out) {
+    return bounded_certificate_one(ctx, "lp_basis_bounded_certificate_large", true, A, m, n, b, c, lo, hi, basis,
+                                   at_upper, maximize, eps, kind_out, farkas_out, ray_out, value_out, index_out);
 }
 
 int lp_basis_bounded_certificate_batched(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,

@@ -395,6 +395,11 @@ struct BasisBoundedCertificateDev {
 size_t lp_basis_bounded_certificate_lds_bytes(int m, int n);
 bool lp_basis_bounded_certificate_fits_shape(int m, int n);   // lp_bounded_fits_shape and the kernel's LDS <= 160 KiB
 int lp_basis_bounded_certificate_launch(lp_context* ctx, const BasisBoundedCertificateDev& d);   // fitting shapes
+// One LP of any shape on the device (d.batch = 1; bounds, flags, eps and the basis' range and repeats checked by the
+// caller): the column codes, the held values, b' and b0 by small kernels, the crash on [B | I | b'] with the artificial
+// columns explicit by the single-LP launch pair, B^-1 A, then the case and its reductions.  Returns LP_OPTIMAL /
+// LP_INFEASIBLE / LP_SINGULAR (outputs untouched unless LP_OPTIMAL); d.run_status is not read, d.status not written.
+int lp_basis_bounded_certificate_device(lp_context* ctx, const BasisBoundedCertificateDev& d);
 
 // Parametric right-hand-side and parametric cost paths of bounded-variable LPs from given optimal bases and at-upper
 // flags, one LP per workgroup (basis_bounded_parametric.hip; the definition is tests/ref/bounded_parametric_ref.c): the

@@ -413,18 +413,14 @@ public:
     // its status and gets NONE.  Exceptions as boundedDuals.
     Certificate boundedCertificate(const std::vector<double>& lo, const std::vector<double>& hi,
                                    const BoundedResult& from, double eps = EPS) const {
-        const View p = view();
-        requireBounds("Solver::boundedCertificate", p, lo, hi);
-        Certificate out = blankCertificate(p, from.status);
-        if (hasCertificate(from.status)) {
-            requireStart("Solver::boundedCertificate", "result", p, from);
-            lp_context* ctx = lpgpu::context(_device);
-            mergeStatus(out, lp_basis_bounded_certificate(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
-                                                          from.basis.data(), from.atUpper.data(), p.maximize, eps,
-                                                          &out.kind, out.farkas.data(), out.ray.data(), &out.value,
-                                                          &out.index), ctx);
-        }
-        return out;
+        return boundedCertificateRun("Solver::boundedCertificate", lo, hi, from, eps, false);
+    }
+
+    // The same at any shape boundedSimplexLarge and boundedResolveLarge run (lp_basis_bounded_certificate_large):
+    // result and exceptions as boundedCertificate(lo, hi, from, eps) minus the fit, and equal to it where both run.
+    Certificate boundedCertificateLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                        const BoundedResult& from, double eps = EPS) const {
+        return boundedCertificateRun("Solver::boundedCertificateLarge", lo, hi, from, eps, true);
     }
 
     // The optimal value of the bounded problem along b + t d (boundedParametricRhs, lp_basis_bounded_parametric) or
@@ -632,6 +628,23 @@ private:
             out.x = out.d = nans(p.n);
             out.y = nans(p.m);
             out.objective = kNaN;
+        }
+        return out;
+    }
+
+    // boundedCertificate, or with large boundedCertificateLarge
+    Certificate boundedCertificateRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
+                                      const BoundedResult& from, double eps, bool large) const {
+        const View p = view();
+        requireBounds(who, p, lo, hi);
+        Certificate out = blankCertificate(p, from.status);
+        if (hasCertificate(from.status)) {
+            requireStart(who, "result", p, from);
+            lp_context* ctx = lpgpu::context(_device);
+            const auto entry = large ? lp_basis_bounded_certificate_large : lp_basis_bounded_certificate;
+            mergeStatus(out, entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                   from.atUpper.data(), p.maximize, eps, &out.kind, out.farkas.data(), out.ray.data(),
+                                   &out.value, &out.index), ctx);
         }
         return out;
     }
