@@ -12,3 +12,5 @@ for _ in range(5):
     rc, z, counts, st = p.range(0, p.total)
     best = min(best, st.kernel_ms)
 print(os.environ.get("LP_LIB_PATH", "default"), "kernel_ms %.3f" % best, "z", z, "counts", list(counts))
+p.free()
+ctx.close()

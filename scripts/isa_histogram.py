@@ -11,7 +11,7 @@ with tempfile.TemporaryDirectory() as tmp:
                     "-I", os.path.join(ROOT, "simplexmethod_amd", "csrc"), "-S", "--cuda-device-only", "-o", out,
                     os.path.join(ROOT, "simplexmethod_amd", "csrc", "enum_leaf.hip")], check=True, stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")
-name = "_ZN12_GLOBAL__N_113k_enum_leavesILi%sELb0EEEv7EnumDev9PrefixDevPKdyy:" % K
+name = "_ZN12_GLOBAL__N_113k_enum_leavesILi%sELb0EEEv7EnumDev9PrefixDevPKdiyy:" % K
 start = [i for i, l in enumerate(lines) if l.startswith(name)][0]
 end = [i for i, l in enumerate(lines) if i > start and l.strip().startswith(".amdhsa_kernel")][0]
 body = lines[start:end]

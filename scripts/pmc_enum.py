@@ -7,3 +7,5 @@ A, b, c, _ = capi.gen_lp(0, 16, 32)
 p = ctx.enum_problem(A, b, c, True)
 p.range(0, p.total)
 p.range(0, p.total)
+p.free()
+ctx.close()

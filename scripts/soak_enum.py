@@ -72,6 +72,7 @@ def main():
         p.free()
         trials += 1
         kinds[(m > 16, nm > 16)] = kinds.get((m > 16, nm > 16), 0) + 1
+    ctx.close()
     print("ok:", trials, "problems;", "(m > 16, n - m > 16) ->", kinds)
     return 0
 

@@ -34,3 +34,5 @@ A, b, c, _ = capi.gen_lp(0, 14, 28)
 p = ctx.enum_problem(A, b, c, True)
 best, mean, r = timed(p, 0, p.total, 12)
 print("   C(28,14) full pass best %.3f mean %.3f ms wall, z=%r counts=%s" % (best, mean, r[1], r[2]), flush=True)
+p.free()
+ctx.close()   # (exiting with a live problem or context can abort inside the HIP runtime's teardown)

@@ -39,6 +39,10 @@ static EnumKnobs read_knobs() {
     if (const char* e = getenv("LP_ENUM_LEVEL_BUDGET_KB")) k.level_budget = (size_t)strtoull(e, nullptr, 10) << 10;
     if (const char* e = getenv("LP_ENUM_EXACT_DIV")) k.exact_div = atoi(e) != 0;
     if (const char* e = getenv("LP_ENUM_NARROW_MULT")) k.narrow_mult = atoi(e);
+    if (const char* e = getenv("LP_ENUM_CHUNK")) {
+        const int v = atoi(e);
+        if (v >= 1024 && v <= 16384 && (v & (v - 1)) == 0) k.chunk1 = v;
+    }
     return k;
 }
 

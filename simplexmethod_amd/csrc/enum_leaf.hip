@@ -57,6 +57,9 @@ constexpr int kGreatMin = LP_GREAT_MIN;         // k_enum_leaves<3>: a sub-group
 // selectable columns leave the item tables.  C(32,16) pass with 8 / 9 / 10 columns: 12.80 / 12.67 / 14.64 ms; the
 // other shapes and the shards in lp_enum_launch_leaves.
 constexpr int THIN_TAIL = 9;
+#ifndef LP_LEAF_CUT_ROUNDS   // diagnostic builds: 0 = the shared pivots copy six rounds of columns whatever the width
+#define LP_LEAF_CUT_ROUNDS 1
+#endif
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
                                       // same row of different columns hit different banks
 
@@ -407,6 +410,13 @@ __device__ __forceinline__ void wavelog_put(int kernel, unsigned long long t0, u
 #endif
 
 constexpr int kChunk = 1024;  // subsets per work item (16 wave passes)
+// Table 1 (k_enum_leaves<3>) on a range of at least kChunkWideMinRecords depth m-7 records: items of kChunkWide subsets.
+// Every item of a large group repeats the child pivot and the j2 pivot.  C(32,16) pass with 1024 / 2048 / 4096 (wall,
+// means of 3 x 12 on one MI355X, profiles/enum_leaf_steps.json): 12.69 / 12.59 / 12.62 ms.  A small range keeps 1024:
+// forced to 2048 / 4096, C(28,14) takes 1.160 / 1.184 ms against 1.137 and the slowest 8-way shard of C(32,16) 1.980 /
+// 2.081 ms against 1.955 (the last items of the table decide when such a pass ends) — the threshold is the one of
+// kItemLanesNarrow, between those two ranges (116 k and 250 k records) and a whole C(32,16) (2.0 M).
+constexpr int kChunkWide = 2048, kChunkWideMinRecords = 300000;
 // lanes of k_enum_make_items that share one record: 4 on wide levels, 8 on the narrow ones of a small
 // rank range (there the kernel's run time is the length of one lane's loop)
 constexpr int kItemLanesWide = 4, kItemLanesNarrow = 8;
@@ -429,9 +439,10 @@ template <bool FUSED>
 __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev pd,
                                                          const double* __restrict__ roots,
                                                          int root_level, int root_cap, int min_child_R,
-                                                         int kItemLanes, unsigned long long begin,
+                                                         int kItemLanes, int chunk1, unsigned long long begin,
                                                          unsigned long long end) {
     constexpr int KD = 6;
+    const unsigned long long kChunk1 = (unsigned long long)chunk1;   // width of a table-1 item (kChunk or a multiple)
     // C(r, 5) and C(r, 6) for r <= NMX + KD + 1, from LDS (the loops below are chains of dependent
     // lookups; out of L2 they were half of this kernel's time)
     __shared__ unsigned int s_b5[NMX + KD + 2], s_b6[NMX + KD + 2];
@@ -451,13 +462,13 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
         unsigned long long pack_n = 0;
         for (int j2 = 0; R - 1 - j2 >= kGrandMin; ++j2) {
             const unsigned long long cnt2 = s_b5[R - 1 - j2];
-            if (cnt2 >= (unsigned long long)kChunk) {
+            if (cnt2 >= kChunk1) {
                 n1 += pack_ng ? 1 : 0;
                 pack_ng = 0;
                 pack_n = 0;
-                n1 += (int)((cnt2 + kChunk - 1) / kChunk);
+                n1 += (int)((cnt2 + kChunk1 - 1) / kChunk1);
             } else {
-                if (pack_n + cnt2 > (unsigned long long)kChunk) {
+                if (pack_n + cnt2 > kChunk1) {
                     n1 += pack_ng ? 1 : 0;
                     pack_ng = 0;
                     pack_n = 0;
@@ -485,9 +496,9 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
         rb0 = pm->rank_base;
     }
     // chunks of [lo0, hi0) (subset indices relative to `base`) whose rank interval meets [begin, end)
-    auto chunks = [&](unsigned long long base, unsigned long long lo0, unsigned long long hi0, auto&& f) {
-        for (unsigned long long lo = lo0; lo < hi0; lo += kChunk)
-            if (overlap(base + lo, (hi0 - lo < kChunk) ? hi0 - lo : (unsigned long long)kChunk, begin, end)) f((int)lo);
+    auto chunks = [&](unsigned long long base, unsigned long long lo0, unsigned long long hi0, unsigned long long ck, auto&& f) {
+        for (unsigned long long lo = lo0; lo < hi0; lo += ck)
+            if (overlap(base + lo, (hi0 - lo < ck) ? hi0 - lo : ck, begin, end)) f((int)lo);
     };
     // one child a (R selectable columns, L subsets from rank rb) of this lane's share
     auto child = [&](int a, int R, unsigned long long L, unsigned long long rb, int lim, auto&& emit) {
@@ -503,12 +514,12 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
         };
         for (int j2 = 0; R - 1 - j2 >= kGrandMin; ++j2) {
             const unsigned long long cnt2 = s_b5[R - 1 - j2];
-            if (cnt2 >= (unsigned long long)kChunk) {
+            if (cnt2 >= kChunk1) {
                 flush();
-                chunks(rb + off2, 0, cnt2,
+                chunks(rb + off2, 0, cnt2, kChunk1,
                        [&](int lo) { emit(1, a | (j2 << 8) | (1 << 16), lo, (int)(rb + off2 - rb0)); });
             } else {
-                if (pack_n + cnt2 > (unsigned long long)kChunk) flush();
+                if (pack_n + cnt2 > kChunk1) flush();
                 if (pack_ng == 0) {
                     pack_j2 = j2;
                     pack_off = off2;
@@ -559,7 +570,7 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
                 rb += L;
             }
         } else {
-            chunks(rb0, 0, s_b6[n - 1 - last], [&](int lo) { emit(0, last, lo, 0); });
+            chunks(rb0, 0, s_b6[n - 1 - last], (unsigned long long)kChunk, [&](int lo) { emit(0, last, lo, 0); });
         }
     };
     int nch[2] = {0, 0};
@@ -620,9 +631,11 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
 // MODE 0 (m = 6): the root record is the depth m-6 node.
 template <int MODE, bool EXACT>
 __global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
-void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, unsigned long long begin,
+void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, int chunk1, unsigned long long begin,
                    unsigned long long end) {
     constexpr bool FUSED = MODE != 0;
+    // subsets per work item: table 1's width is the host's choice (lp_enum_launch_leaves), the one its items were cut at
+    const unsigned int width = MODE >= 2 ? (unsigned int)chunk1 : (unsigned int)kChunk;
     constexpr int KD = 6;
     constexpr int MAXCOLS = NMX + KD + 1 + (FUSED ? 1 : 0);  // columns of a record (+ rhs)
     constexpr int CHILDCOLS = NMX + KD + 1;                  // columns of a depth m-6 tableau (+ rhs)
@@ -797,7 +810,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
         const unsigned* comb = pd.comb6 + s_off[MODE >= 2 ? 0 : R];
         unsigned long long rb = pm.rank_base + (unsigned long long)(FUSED ? roff : 0);
         const unsigned int leaf_lo = (unsigned int)chunk;
-        const unsigned int leaf_hi = (leaf_lo + kChunk < L) ? leaf_lo + kChunk : L;
+        const unsigned int leaf_hi = (leaf_lo + width < L) ? leaf_lo + width : L;
         double minp0 = pm.minp, maxp0 = pm.maxp;
         unsigned umask = __builtin_amdgcn_readfirstlane(pm.used_mask);
         bool sing0 = false;   // MODE 1: the first child of a paired item turned out singular
@@ -818,7 +831,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
                 if (MODE >= 2) {
                     span = 0;
                     for (int gi = 0; gi < ngroups; ++gi) span += s_binom[(R - 1 - j2_first - gi) * (KD + 1) + KD - 1];
-                    if (ngroups == 1) span = min(span - leaf_lo, (unsigned int)kChunk);
+                    if (ngroups == 1) span = min(span - leaf_lo, width);
                 }
                 if (lane == 0) cntS += (unsigned int)overlap(rb + leaf_lo, span, begin, end);
                 if (MODE == 1 && ((child >> 16) & 1))
@@ -842,9 +855,23 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
                             : ((freem >> r) & 1u) ? __builtin_popcount(freem & below)
                                                   : __builtin_popcount(freem) + __builtin_popcount(umask & all & below);
             double* ctab = s_child[wave];
+            // The rounds end at the tableau's own width (a wave-uniform branch; six rounds whatever the width cost a
+            // 10-column child three rounds of address arithmetic for nothing).  MODE 1: the subsets of a table-0 item
+            // are the child's tail, whose first remaining column leaves fewer than kGrandMin selectable ones — they
+            // reach only the last kGrandMin columns and the rhs, so only those are written (at their own positions).
+            // MODE 2 / 3: the item's groups pivot on columns j2_first .. and read the ones behind them.
+            // (C(32,16): SQ_INSTS_VALU of table 1's kernel 2.520 -> 2.513 G per pass, none in table 0's, whose rounds
+            // beyond the width were skipped by an execz branch already; with the row maximum and the item width the
+            // bench step 12.98 -> 12.75 ms and the slowest 8-way shard 2.07 -> 1.96 ms: profiles/enum_leaf_steps.json)
+            const int Ru = __builtin_amdgcn_readfirstlane(R);
+            const int jlo = !LP_LEAF_CUT_ROUNDS ? 0
+                            : MODE == 1         ? max(Ru - kGrandMin, 0)
+                            : MODE >= 2         ? __builtin_amdgcn_readfirstlane(j2_first)
+                                                : 0;
 #pragma unroll
             for (int q = 0; q < (CHILDCOLS + 3) / 4; ++q) {
-                const int j = g + 4 * q;            // child column j = column child+1+j (j = R: rhs)
+                if (LP_LEAF_CUT_ROUNDS && jlo + 4 * q > Ru) break;
+                const int j = jlo + g + 4 * q;      // child column j = column child+1+j (j = R: rhs)
                 if (j <= R && !sing0) {
                     const double* pc = tab + (child_col + 1 + j - D) * TS;
                     ctab[j * TS + pos] = fma(lx, pc[p], isp ? -0.0 : pc[r]);
@@ -865,7 +892,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
             const int R2 = R - 1 - j2;                 // selectable columns of the depth m-5 node
             const unsigned int L2 = s_binom[R2 * (KD + 1) + K5];
             const unsigned int lo2 = leaf_lo;          // (0 unless the item is a chunk of one large group)
-            const unsigned int hi2 = (lo2 + kChunk < L2) ? lo2 + kChunk : L2;
+            const unsigned int hi2 = (lo2 + width < L2) ? lo2 + width : L2;
             const unsigned long long rb2 = rb;
             rb += L2;                                  // next group of a packed item
             if (overlap(rb2 + lo2, hi2 - lo2, begin, end) == 0ULL) continue;
@@ -885,8 +912,10 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
             // rows of the grandchild: the 5 unused ones at 0..4, the new pivot row at 5, the rest stay
             const int pos = (r < p2) ? r : (r == p2) ? K5 : (r < KD) ? r - 1 : r;
             double* gtab = s_grand[wave];
+            const int R2u = __builtin_amdgcn_readfirstlane(R2);
 #pragma unroll
             for (int q = 0; q < (NMX + KD + 3) / 4; ++q) {
+                if (LP_LEAF_CUT_ROUNDS && 4 * q > R2u) break;
                 const int j = g + 4 * q;        // grandchild column j = child column j2+1+j (j = R2: rhs)
                 if (j <= R2) {
                     const double* pc = tab + (j2 + 1 + j) * TS;
@@ -923,8 +952,10 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
                     const double lx3 = isp3 ? inv3 : -(w3 * inv3);
                     // rows: the 4 unused ones at 0..3, the new pivot row at 4, the rest stay
                     const int pos3 = (r < p3) ? r : (r == p3) ? K4 : (r < K5) ? r - 1 : r;
+                    const int R3u = __builtin_amdgcn_readfirstlane(R3);
 #pragma unroll
                     for (int q = 0; q < (NMX + KD + 2) / 4; ++q) {
+                        if (LP_LEAF_CUT_ROUNDS && 4 * q > R3u) break;
                         const int j = g + 4 * q;        // column j = grandchild column j3+1+j (j = R3: rhs)
                         if (j <= R3) {
                             const double* pc = gtab + (j3 + 1 + j) * TS;
@@ -1019,9 +1050,11 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, un
                     int wv = wave;   // (opaque copy: the slice address is recomputed here, not kept live — and spilled — across items)
                     asm volatile("" : "+v"(wv));
                     double* ctab1 = s_child2[wv];
+                    const int R1u = __builtin_amdgcn_readfirstlane(R1), jlo1 = LP_LEAF_CUT_ROUNDS ? max(R1u - kGrandMin, 0) : 0;   // (as the first child's)
 #pragma unroll
                     for (int q = 0; q < (CHILDCOLS + 3) / 4; ++q) {
-                        const int j = g + 4 * q;        // column j of the second child = record column child_col+2+j
+                        if (LP_LEAF_CUT_ROUNDS && jlo1 + 4 * q > R1u) break;
+                        const int j = jlo1 + g + 4 * q;   // column j of the second child = record column child_col+2+j
                         if (j <= R1) {
                             const double* pc = par + (child_col + 2 + j - D) * TS;
                             ctab1[j * TS + pos] = fma(lx, pc[p], isp ? -0.0 : pc[r]);
@@ -1766,6 +1799,8 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         }
         hipStream_t s = ctx->stream, sT = ctx->aux_stream[0], s1 = ctx->aux_stream[1];
         const int lanes = bound < 300000 ? kItemLanesNarrow : kItemLanesWide;
+        // width of a table-1 item (kChunkWide above; LP_ENUM_CHUNK pins it for tests and measurements)
+        const int chunk1 = p->knobs.chunk1 ? p->knobs.chunk1 : bound < kChunkWideMinRecords ? kChunk : kChunkWide;
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[0], s));          // the level records are complete
         LP_HIP(ctx, hipStreamWaitEvent(sT, ctx->aux_event[0], 0));
         // The tail kernel needs the level records only, not the item tables: it is launched on its own stream BESIDE
@@ -1805,7 +1840,7 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         else
             hipLaunchKernelGGL((k_enum_thin<false, THIN_TAIL>), grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
         hipLaunchKernelGGL(k_enum_make_items<true>, lp_ceil_div(bound * lanes, 1024), 1024, 0, s, p->dev, pd,
-                           roots, level, bound, THIN_TAIL, lanes, b, e);
+                           roots, level, bound, THIN_TAIL, lanes, chunk1, b, e);
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[1], s));          // both item tables are built
         LP_HIP(ctx, hipStreamWaitEvent(s1, ctx->aux_event[1], 0));
         // both leaf kernels with resident-sized grids (3 workgroups per CU).  (2 for table 1's kernel gives the best
@@ -1816,11 +1851,11 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
 #define LP_LEAF_LEVELS 3
 #endif
         if (exact) {
-            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, true>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, b, e);
-            hipLaunchKernelGGL((k_enum_leaves<1, true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, true>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<1, true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
         } else {
-            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, false>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, b, e);
-            hipLaunchKernelGGL((k_enum_leaves<1, false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, false>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<1, false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
         }
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[0], sT));
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[2], s1));
@@ -1828,11 +1863,11 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         LP_HIP(ctx, hipStreamWaitEvent(s, ctx->aux_event[2], 0));
     } else {
         hipLaunchKernelGGL(k_enum_make_items<false>, lp_ceil_div(bound, 1024), 1024, 0, ctx->stream, p->dev, pd,
-                           roots, level, bound, 0, 1, b, e);
+                           roots, level, bound, 0, 1, kChunk, b, e);
         if (exact)
-            hipLaunchKernelGGL((k_enum_leaves<0, true>), grid6, LEAF_THREADS, 0, ctx->stream, p->dev, pd, roots, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<0, true>), grid6, LEAF_THREADS, 0, ctx->stream, p->dev, pd, roots, kChunk, b, e);
         else
-            hipLaunchKernelGGL((k_enum_leaves<0, false>), grid6, LEAF_THREADS, 0, ctx->stream, p->dev, pd, roots, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<0, false>), grid6, LEAF_THREADS, 0, ctx->stream, p->dev, pd, roots, kChunk, b, e);
     }
     return LP_OPTIMAL;
 }

@@ -92,6 +92,7 @@ struct EnumKnobs {
     size_t level_budget = SIZE_MAX;  // LP_ENUM_LEVEL_BUDGET_KB in bytes (SIZE_MAX: by device memory)
     bool exact_div = false;          // LP_ENUM_EXACT_DIV=1: plain divisions from the first pass on
     int narrow_mult = -1;            // LP_ENUM_NARROW_MULT (-1: by record width)
+    int chunk1 = 0;                  // LP_ENUM_CHUNK: subsets per table-1 leaf item, a power of two from 1024 to 16384 (0: by range)
 };
 
 // The feasible list a successful shared-prefix pass left on the device (prefix.list / scores, or in the

@@ -52,17 +52,21 @@ __device__ __forceinline__ unsigned long long overlap(unsigned long long rb, uns
     return hi > lo ? hi - lo : 0ULL;
 }
 
-// max over the 16 lanes of a group (DPP row operations), result in every lane of the group
+// max over the 16 lanes of a group (DPP row operations), result in every lane of the group.
+// Three instructions per step: two v_mov_b32_dpp into fresh registers (every lane of these four
+// permutations has a source lane, so no `old` value is carried in: update_dpp(x, x, ...) cost a
+// v_mov per word first) and v_max_f64 itself.  Its callers pass |w| or -1.0, never a signalling
+// NaN, which the compiler cannot see and would quiet with a v_max_f64 v, v, v per step; a quiet
+// NaN is dropped by the instruction exactly as fmax drops it.  C(32,16) pass: SQ_INSTS_VALU of
+// the leaf kernels 2.520 -> 2.489 G (table 1) and 2.183 -> 2.170 G (table 0),
+// profiles/enum_leaf_steps.json.
 __device__ __forceinline__ double row_max_f64(double v) {
-    double o;
-#define LP_RSTEP(CTRL)                                                                   \
-    {                                                                                    \
-        const long long b = __double_as_longlong(v);                                     \
-        int lo = (int)(b & 0xFFFFFFFFLL), hi = (int)(b >> 32);                           \
-        lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);                 \
-        hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);                 \
-        o = __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);              \
-        v = fmax(v, o);                                                                  \
+#define LP_RSTEP(CTRL)                                                                      \
+    {                                                                                       \
+        const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);  \
+        const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);  \
+        const double o = __hiloint2double(hi, lo);                                          \
+        asm("v_max_f64 %0, %1, %2" : "=v"(v) : "v"(v), "v"(o));                             \
     }
     LP_RSTEP(0xB1)   // quad_perm [1,0,3,2]
     LP_RSTEP(0x4E)   // quad_perm [2,3,0,1]
