@@ -598,10 +598,11 @@ int lp_simplex_bounded_fits(int m, int n);
  *   - Dantzig's rule; Bland's rule and Devex pricing at these shapes are lp_simplex_bounded_large_ex (with the _ex
  *     block below; m <= 9968 under LP_PIVOT_DEVEX).  The dual solution and ranging at these shapes are
  *     lp_basis_bounded_duals_large and lp_basis_bounded_ranging_large below, and the evidence for an LP_INFEASIBLE or
- *     LP_UNBOUNDED verdict is lp_basis_bounded_certificate_large.  Out of scope on this path: the other analyses
- *     (parametrics, branch and bound); those stay at lp_simplex_bounded_fits shapes.  The re-solve from a basis at
- *     these shapes is lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and still
- *     refuses larger shapes.                                                                                      */
+ *     LP_UNBOUNDED verdict is lp_basis_bounded_certificate_large; the parametric paths along b + t d and c + t g are
+ *     lp_basis_bounded_parametric_large and lp_basis_bounded_parametric_cost_large.  Out of scope on this path:
+ *     branch and bound, which stays at lp_simplex_bounded_fits shapes.  The re-solve from a basis at these shapes is
+ *     lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and still refuses larger
+ *     shapes.                                                                                                     */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 /* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
  * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
@@ -877,6 +878,28 @@ int lp_basis_bounded_parametric_cost_batched(lp_context* ctx, int batch, const d
  * otherwise.  Host calls, no context.                                                                              */
 int lp_basis_bounded_parametric_fits(int m, int n);
 int lp_basis_bounded_parametric_cost_fits(int m, int n);
+/* The same two paths beyond one workgroup's LDS, one LP per call (the definition is still
+ * tests/ref/bounded_parametric_ref.c, steps 1-5, R1-R3 and C1-C3, and every output equals it bit for bit on every
+ * status, NaN fills, signed zeros, side_out and at_upper_out included): after lp_simplex_bounded_large or
+ * lp_simplex_bounded_resolve_large the whole of z*(t) along b + t d or c + t g costs one crash and one selector +
+ * rank-1 update launch pair per breakpoint on the tableau in HBM, instead of one re-solve (and its m crash pivots)
+ * per guessed t.  The tableau is the bounded re-solve's (shifted variables, flagged columns complemented, b' its
+ * chain).  RHS path: [A' | d | b'], d barred from entering, so the update carries both right-hand columns and a row
+ * blocked above is staged complemented without touching the tableau.  Cost path: two cost rows and ONE crash, the g'
+ * row carried through each crash step by the step's own update.  Per breakpoint the selector's last wave runs the
+ * obj and slope chains while the other fifteen reduce tau, choose the entering column or the leaving row (or flip the
+ * bound in place) and stage the pivot.  Arguments, outputs, statuses and refusals are lp_basis_bounded_parametric's
+ * and lp_basis_bounded_parametric_cost's with one difference: there is no _fits limit.  The limits are device
+ * memory (two tableaus of (m+1) x (n+2), or (m+2) and (m+1) rows of n+1) and the selectors' dynamic LDS, 24 m + 416
+ * bytes (RHS) or 40 m + 448 bytes (cost) against 156 KiB: m <= 6638 and m <= 3982, else LP_BAD_ARG with a message
+ * and nothing launched.  Crossed bounds are LP_INFEASIBLE (nseg 0) after every LP_BAD_ARG and before a repeated index
+ * or a singular basis is LP_SINGULAR, as the definition orders them.  At a shape where the _fits call holds every
+ * output equals the LDS entry's; with lo = 0, hi = +inf and no flag every output shared with lp_basis_parametric /
+ * lp_basis_parametric_cost equals theirs, side_out is 0 wherever leave_out >= 0 and at_upper_out is 0.  There is no
+ * batched form; the LDS entries, their _batched forms and the _fits calls are unchanged and still refuse larger
+ * shapes.                                                                                                          */
+int lp_basis_bounded_parametric_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, const double* d, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out);
+int lp_basis_bounded_parametric_cost_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis, const int* at_upper, int maximize, const double* g, double t_max, double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out, int* leave_out, int* side_out, int* basis_out, int* at_upper_out);
 
 /* =========================================================================
  * Enumeration — EnumerationSolver (src/EnumerationSolver.h:3-10 is a stub; spec

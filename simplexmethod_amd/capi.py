@@ -209,6 +209,12 @@ SIGNATURES = {
                                                            C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip]),
     "lp_basis_bounded_parametric_fits": (C.c_int, [C.c_int, C.c_int]),
     "lp_basis_bounded_parametric_cost_fits": (C.c_int, [C.c_int, C.c_int]),
+    "lp_basis_bounded_parametric_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                    _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip,
+                                                    _ip, _ip, _ip]),
+    "lp_basis_bounded_parametric_cost_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                         C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, _dp,
+                                                         _dp, _ip, _ip, _ip, _ip, _ip]),
     "lp_binom": (C.c_uint64, [C.c_int, C.c_int]),
     "lp_enum_shard_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _u64p, _u64p]),
     "lp_enum_solve": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -1061,6 +1067,22 @@ class Context:
         """lp_basis_bounded_parametric_cost_batched: as bounded_parametric_batched with g (batch, n)."""
         return self._bounded_parametric_batched(self.lib.lp_basis_bounded_parametric_cost_batched, "n", A, b, c, lo,
                                                 hi, basis, at_upper, g, t_max, maximize, eps, max_breaks, run_status)
+
+    def bounded_parametric_large(self, A, b, c, lo, hi, basis, at_upper, d, t_max=np.inf, maximize=True, eps=EPS,
+                                 max_breaks=MAX_BREAKS):
+        """lp_basis_bounded_parametric_large: bounded_parametric() on the tableau in HBM, at any shape bounded_large()
+        and bounded_resolve_large() run (one selector + one update launch per breakpoint).  Same arguments, dict and
+        statuses; no bounded_parametric_fits limit (m <= 6638 for the selector's LDS)."""
+        return self._bounded_parametric(self.lib.lp_basis_bounded_parametric_large, "m", A, b, c, lo, hi, basis,
+                                        at_upper, d, t_max, maximize, eps, max_breaks)
+
+    def bounded_parametric_cost_large(self, A, b, c, lo, hi, basis, at_upper, g, t_max=np.inf, maximize=True, eps=EPS,
+                                      max_breaks=MAX_BREAKS):
+        """lp_basis_bounded_parametric_cost_large: bounded_parametric_cost() on the tableau in HBM, at any shape
+        bounded_large() and bounded_resolve_large() run.  Same arguments, dict and statuses; no
+        bounded_parametric_cost_fits limit (m <= 3982 for the selector's LDS)."""
+        return self._bounded_parametric(self.lib.lp_basis_bounded_parametric_cost_large, "n", A, b, c, lo, hi, basis,
+                                        at_upper, g, t_max, maximize, eps, max_breaks)
 
     def bounded_parametric_fits(self, m, n):
         """lp_basis_bounded_parametric_fits: True if an m x n bounded LP runs the RHS path's kernel."""

@@ -1101,7 +1101,8 @@ int lp_batched_parametric_cost(lp_batched_problem* p, const double* g, double t_
 // ===========================================================================
 // Parametric right-hand side and parametric cost of a bounded-variable LP from an optimal basis and its at-upper flags
 // (basis_bounded_parametric.hip): one LP per workgroup for lp_basis_bounded_parametric_fits / _cost_fits shapes only;
-// as in the bounded family there is no handle and no per-LP path
+// as in the bounded family there is no handle and no per-LP path.  The _large entries run one LP of any shape on the
+// tableau in HBM (basis_bounded_parametric_large.hip)
 // ===========================================================================
 
 int lp_basis_bounded_parametric_fits(int m, int n) { return lp_basis_bounded_parametric_fits_shape(m, n, false) ? 1 : 0; }
@@ -1140,10 +1141,12 @@ static int bounded_parametric_args(lp_context* ctx, const char* who, const Bound
 
 // One allocation for the inputs and the outputs of the batch, uploads queued on the context's stream, one launch of
 // k_batched_bounded_parametric or k_batched_bounded_parametric_cost, one download.  `dir` is d (m per LP) or g (n per
-// LP); run_status may be nullptr.
+// LP); run_status may be nullptr.  `large` (one LP, no run_status, `out` already holding bounded_parametric_none's
+// fill): lp_basis_bounded_parametric_device instead of the launch; it returns the LP's status into *status_out, and
+// only the path it wrote comes down.
 static int bounded_parametric(lp_context* ctx, const BoundedSensIn& in, const double* dir, bool cost,
                               const int* run_status, int maximize, double t_max, double eps, int mb,
-                              const BoundedParametricOut& out, int* status_out) {
+                              const BoundedParametricOut& out, int* status_out, bool large = false) {
     const int batch = in.batch, m = in.m, n = in.n;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)batch, nt = B * (mb + 2), ns = B * (mb + 1), nd = B * (cost ? n : m);
@@ -1200,6 +1203,23 @@ static int bounded_parametric(lp_context* ctx, const BoundedSensIn& in, const do
     d.at_upper_out = d.basis_out + B * m;
     d.nseg = d.at_upper_out + B * n;
     d.status = d.nseg + B;
+    if (large) {
+        int nseg = 0;
+        const int st = lp_basis_bounded_parametric_device(ctx, d, cost, &nseg);
+        if (st < 0) return st;
+        *status_out = st;
+        if (nseg <= 0) return LP_OPTIMAL;
+        const size_t np = (size_t)nseg;
+        return lp_download(ctx, "bounded basis parametric", {{out.t, d.t, sizeof(double) * (np + 1)},
+                                                             {out.obj, d.obj, sizeof(double) * (np + 1)},
+                                                             {out.slope, d.slope, sizeof(double) * np},
+                                                             {out.enter, d.enter, sizeof(int) * np},
+                                                             {out.leave, d.leave, sizeof(int) * np},
+                                                             {out.side, d.side, sizeof(int) * np},
+                                                             {out.basis, d.basis_out, sizeof(int) * (size_t)m},
+                                                             {out.at_upper, d.at_upper_out, sizeof(int) * (size_t)n},
+                                                             {out.nseg, d.nseg, sizeof(int)}});
+    }
     int rc = lp_basis_bounded_parametric_launch(ctx, d, cost);
     if (rc == LP_OPTIMAL)
         rc = lp_download(ctx, "bounded basis parametric", {{out.t, d.t, sizeof(double) * nt},
@@ -1215,8 +1235,10 @@ static int bounded_parametric(lp_context* ctx, const BoundedSensIn& in, const do
     return rc;
 }
 
-// The single-LP entry of either path
-static int bounded_parametric_one(lp_context* ctx, const char* who, bool cost, const double* A, int m, int n,
+// The single-LP entry of either path (`who`), or with `large` its _large form: the same checks in the same order
+// without the fit (the selectors' LDS bounds m instead), and crossed bounds answered here as the definition orders
+// them, after every LP_BAD_ARG and before the crash can say LP_SINGULAR
+static int bounded_parametric_one(lp_context* ctx, const char* who, bool large, bool cost, const double* A, int m, int n,
                                   const double* b, const double* c, const double* lo, const double* hi,
                                   const int* basis, const int* at_upper, int maximize, const double* dir, double t_max,
                                   double eps, int max_breaks, const BoundedParametricOut& out) {
@@ -1228,10 +1250,21 @@ static int bounded_parametric_one(lp_context* ctx, const char* who, bool cost, c
     if (max_breaks < 0) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": max_breaks must be >= 0");
     bounded_parametric_none(0, m, n, max_breaks, basis, at_upper, out);
     const BoundedSensIn in{1, m, n, A, b, c, lo, hi, basis, at_upper};
-    int rc = bounded_parametric_args(ctx, who, in, cost, t_max, eps, max_breaks);
-    if (rc) return rc;
+    int rc;
+    if (large) {
+        rc = parametric_args(ctx, who, t_max, eps, max_breaks);
+        if (rc == LP_OPTIMAL) rc = bounded_basis_values(ctx, who, 1, m, n, lo, hi, basis, at_upper, false);
+        if (rc) return rc;
+        if (lp_basis_bounded_parametric_large_lds_bytes(m, cost) > 156 * 1024)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": m too large for the selector's LDS");
+        for (int j = 0; j < n; ++j)
+            if (hi[j] < lo[j]) return LP_INFEASIBLE;
+    } else {
+        rc = bounded_parametric_args(ctx, who, in, cost, t_max, eps, max_breaks);
+        if (rc) return rc;
+    }
     int status = LP_OPTIMAL;
-    rc = bounded_parametric(ctx, in, dir, cost, nullptr, maximize, t_max, eps, max_breaks, out, &status);
+    rc = bounded_parametric(ctx, in, dir, cost, nullptr, maximize, t_max, eps, max_breaks, out, &status, large);
     if (rc) return rc;
     if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is not optimal at t = 0");
     return status;
@@ -1259,7 +1292,7 @@ int lp_basis_bounded_parametric(lp_context* ctx, const double* A, int m, int n, 
                                 int maximize, const double* d, double t_max, double eps, int max_breaks,
                                 int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                                 int* leave_out, int* side_out, int* basis_out, int* at_upper_out) {
-    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric", false, A, m, n, b, c, lo, hi, basis, at_upper,
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric", false, false, A, m, n, b, c, lo, hi, basis, at_upper,
                                   maximize, d, t_max, eps, max_breaks,
                                   {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
                                    at_upper_out});
@@ -1282,8 +1315,31 @@ int lp_basis_bounded_parametric_cost(lp_context* ctx, const double* A, int m, in
                                      int maximize, const double* g, double t_max, double eps, int max_breaks,
                                      int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
                                      int* leave_out, int* side_out, int* basis_out, int* at_upper_out) {
-    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric_cost", true, A, m, n, b, c, lo, hi, basis,
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric_cost", false, true, A, m, n, b, c, lo, hi, basis,
                                   at_upper, maximize, g, t_max, eps, max_breaks,
+                                  {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                   at_upper_out});
+}
+
+int lp_basis_bounded_parametric_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                      const double* lo, const double* hi, const int* basis, const int* at_upper,
+                                      int maximize, const double* d, double t_max, double eps, int max_breaks,
+                                      int* nseg_out, double* t_out, double* obj_out, double* slope_out, int* enter_out,
+                                      int* leave_out, int* side_out, int* basis_out, int* at_upper_out) {
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric_large", true, false, A, m, n, b, c, lo, hi, basis,
+                                  at_upper, maximize, d, t_max, eps, max_breaks,
+                                  {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
+                                   at_upper_out});
+}
+
+int lp_basis_bounded_parametric_cost_large(lp_context* ctx, const double* A, int m, int n, const double* b,
+                                           const double* c, const double* lo, const double* hi, const int* basis,
+                                           const int* at_upper, int maximize, const double* g, double t_max,
+                                           double eps, int max_breaks, int* nseg_out, double* t_out, double* obj_out,
+                                           double* slope_out, int* enter_out, int* leave_out, int* side_out,
+                                           int* basis_out, int* at_upper_out) {
+    return bounded_parametric_one(ctx, "lp_basis_bounded_parametric_cost_large", true, true, A, m, n, b, c, lo, hi,
+                                  basis, at_upper, maximize, g, t_max, eps, max_breaks,
                                   {nseg_out, t_out, obj_out, slope_out, enter_out, leave_out, side_out, basis_out,
                                    at_upper_out});
 }

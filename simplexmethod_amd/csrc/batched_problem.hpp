@@ -435,6 +435,14 @@ struct BasisBoundedParametricDev {
 size_t lp_basis_bounded_parametric_lds_bytes(int m, int n, bool cost);
 bool lp_basis_bounded_parametric_fits_shape(int m, int n, bool cost);   // lp_bounded_fits_shape and the carve <= 160 KiB
 int lp_basis_bounded_parametric_launch(lp_context* ctx, const BasisBoundedParametricDev& d, bool cost);   // fitting shapes
+// basis_bounded_parametric_large.hip: one LP of any shape on the tableau in HBM (d.batch = 1; the arguments, bounds,
+// flags, basis range and crossed bounds checked by the caller; d.run_status is not read, d.status not written).  The
+// selectors' dynamic LDS for m rows must not exceed 156 KiB (LP_BAD_ARG with a message, nothing launched).  Returns the
+// path's status; *nseg_host > 0 says that a path was written: then d.t, d.obj [0, nseg], d.slope, d.enter, d.leave,
+// d.side [0, nseg), d.basis_out and d.at_upper_out hold it and everything else is untouched.  LP_SINGULAR and
+// LP_BAD_ARG (the start is not optimal) write nothing.
+size_t lp_basis_bounded_parametric_large_lds_bytes(int m, bool cost);
+int lp_basis_bounded_parametric_device(lp_context* ctx, const BasisBoundedParametricDev& d, bool cost, int* nseg_host);
 
 // A batch handle of the C ABI (batched_driver.hip: upload, run, download); the analyses of basis_driver.hip read its
 // inputs and final bases after a run.  The kind says which kernel a resident handle launches and which single-LP

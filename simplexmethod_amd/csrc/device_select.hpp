@@ -301,6 +301,8 @@ __device__ __forceinline__ int block_select_stage2(const double* vals, int len, 
 // ineligible entries as the sentinel; NaNs are replaced by the sentinel here (the chain never takes either).
 // STORE: the entries are also written to vals[j] (global or LDS scratch of >= len doubles); otherwise vals
 // already holds them.  Result as wave_chain_select's: the chain's last accepted index (or -1) and value.
+// nthreads (a multiple of 64): the callers are threads 0 .. nthreads-1 of a workgroup whose other waves have left the
+// kernel (a barrier waits for the waves still running only); 0 = the whole workgroup.
 //   pass 1  thread t scans entries t, t + T, ...: its extreme and the first index holding it; waves and then the
 //           workgroup combine (M, jM = first index of the overall extreme).
 //   pass 2  "M beats every entry in front of jM by more than eps" — then the sequential chain must end on
@@ -315,8 +317,9 @@ struct BlockChainScratch {   // LDS
 
 template <bool WANT_MAX, bool STORE, typename Produce>
 __device__ __forceinline__ int block_chain_select(int len, double eps, double& best, Produce produce, double* vals,
-                                                  BlockChainScratch* sc) {
-    const int tid = threadIdx.x, T = (int)blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
+                                                  BlockChainScratch* sc, int nthreads = 0) {
+    const int tid = threadIdx.x, T = nthreads ? nthreads : (int)blockDim.x, lane = tid & 63, wave = tid >> 6,
+              nwaves = T >> 6;
     const double sentinel = WANT_MAX ? -INFINITY : INFINITY;
     double lv = sentinel;
     int lj = INT_MAX;

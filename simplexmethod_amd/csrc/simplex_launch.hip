@@ -901,7 +901,7 @@ int lp_simplex_price_out_identity(lp_simplex_problem* p) {
     return LP_OPTIMAL;
 }
 
-int lp_simplex_crash(lp_simplex_problem* p) {
+int lp_simplex_crash(lp_simplex_problem* p, lp_simplex_problem* wide, const std::function<void()>& staged) {
     lp_context* ctx = p->ctx;
     const SimplexDev& d = p->dev;
     hipStream_t s = ctx->stream;
@@ -909,7 +909,8 @@ int lp_simplex_crash(lp_simplex_problem* p) {
     LP_HIP(ctx, hipMemsetAsync(d.rowused, 0, (size_t)d.m, s));
     for (int t = 0; t < d.m; ++t) {
         hipLaunchKernelGGL(k_crash_select, 1, 1024, 0, s, d, t);
-        lp_simplex_launch_update(p);
+        if (staged) staged();
+        lp_simplex_launch_update(wide ? wide : p);
     }
     hipLaunchKernelGGL(k_crash_finish, 1, 1, 0, s, d);
     // permute rows into basis-position order (through the pristine buffer)

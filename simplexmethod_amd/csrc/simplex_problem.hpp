@@ -113,7 +113,12 @@ int lp_launch_prepare(lp_simplex_problem* p);   // the selector's LDS: checked, 
 int lp_launch_begin(lp_simplex_problem* p, double eps, int max_iter);
 int lp_launch_queue(lp_simplex_problem* p, int batch);
 void lp_simplex_launch_update(lp_simplex_problem* p);
-int lp_simplex_crash(lp_simplex_problem* p);
+// The crash of p's basis: m selector + update pairs, the verdict, the rows into position order; one host sync.  A
+// tableau with rows behind the cost row (a second cost row) passes `wide`, the same problem seen with those rows
+// counted in dev.m, and `staged`, which queues what fills their eta entries behind each step's selector: the step's
+// update then runs on `wide` and carries them with the pivot's own arithmetic.  They stay where they are afterwards.
+int lp_simplex_crash(lp_simplex_problem* p, lp_simplex_problem* wide = nullptr,
+                     const std::function<void()>& staged = {});
 int lp_simplex_price_out_identity(lp_simplex_problem* p);  // unit-vector basis with non-zero costs
 int lp_simplex_force(lp_simplex_problem* p, int row, int col);  // host-chosen pivot on the current tableau
 int lp_simplex_driveout(lp_simplex_problem* p, const int* positions, int count, int n_limit, double eps, int* applied);

@@ -447,6 +447,20 @@ public:
         return boundedParametric(true, lo, hi, from, g, tMax);
     }
 
+    // The same at any shape boundedSimplexLarge and boundedResolveLarge run (lp_basis_bounded_parametric_large,
+    // lp_basis_bounded_parametric_cost_large): result and exceptions as boundedParametricRhs / boundedParametricCost
+    // minus the fit (the selector's LDS bounds the rows instead: 6638 and 3982), and equal to them where both run.
+    BoundedParametric boundedParametricRhsLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                                const BoundedResult& from, const lpla::VectorXd& d, double tMax) const {
+        return boundedParametric(false, lo, hi, from, d, tMax, true);
+    }
+
+    BoundedParametric boundedParametricCostLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                                 const BoundedResult& from, const lpla::VectorXd& g,
+                                                 double tMax) const {
+        return boundedParametric(true, lo, hi, from, g, tMax, true);
+    }
+
 private:
     // The problem as the ABI takes it
     struct View {
@@ -578,7 +592,8 @@ private:
     }
 
     BoundedParametric boundedParametric(bool cost, const std::vector<double>& lo, const std::vector<double>& hi,
-                                        const BoundedResult& from, const lpla::VectorXd& dir, double tMax) const {
+                                        const BoundedResult& from, const lpla::VectorXd& dir, double tMax,
+                                        bool large = false) const {
         const View p = view();
         requireBounds("Solver::boundedParametric", p, lo, hi);
         BoundedParametric out;
@@ -595,11 +610,12 @@ private:
             lp_context* ctx = lpgpu::context(_device);
             out.basis.assign((size_t)p.m, -1);
             out.atUpper.assign((size_t)p.n, 0);
-            out.status = checked((cost ? lp_basis_bounded_parametric_cost : lp_basis_bounded_parametric)(
-                                     ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
-                                     from.atUpper.data(), p.maximize, dir.data(), tMax, EPS, MAX_BREAKS, &path.nseg,
-                                     path.t.data(), path.obj.data(), path.slope.data(), path.enter.data(),
-                                     path.leave.data(), side.data(), out.basis.data(), out.atUpper.data()), ctx);
+            const auto entry = large ? (cost ? lp_basis_bounded_parametric_cost_large : lp_basis_bounded_parametric_large)
+                                     : (cost ? lp_basis_bounded_parametric_cost : lp_basis_bounded_parametric);
+            out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                       from.atUpper.data(), p.maximize, dir.data(), tMax, EPS, MAX_BREAKS, &path.nseg,
+                                       path.t.data(), path.obj.data(), path.slope.data(), path.enter.data(),
+                                       path.leave.data(), side.data(), out.basis.data(), out.atUpper.data()), ctx);
         }
         path.unpack(out);
         out.side.assign(side.begin(), side.begin() + path.nseg);
