@@ -316,7 +316,9 @@ template <int G>
 __global__ __launch_bounds__(256) void k_enum_eval_list(EnumDev d, const unsigned long long* list,
                                                         unsigned long long count,
                                                         const unsigned long long* count_ptr,
-                                                        unsigned long long cap, double* scores) {
+                                                        unsigned long long cap, double* scores,
+                                                        const int* __restrict__ list_rec) {
+    // list_rec != null: only the entries without a record (list_rec[e] < 0); k_enum_eval_records scores the others
     // count_ptr != null: the list was filled by kernels queued just before this one and its length
     // still lives on the device (an over-full list is reported by the host afterwards)
     if (count_ptr) count = *count_ptr < cap ? *count_ptr : cap;
@@ -330,6 +332,7 @@ __global__ __launch_bounds__(256) void k_enum_eval_list(EnumDev d, const unsigne
     unsigned long long e = (unsigned long long)blockIdx.x * (blockDim.x / G) + (threadIdx.x / G);
     double best = -INFINITY;
     for (; e < count; e += groups) {
+        if (list_rec && list_rec[e] >= 0) continue;
         int S[G];
         unrank_subset<G>(d, list[e], S);
         SubsetSolve<G> s;
@@ -507,20 +510,26 @@ int lp_enum_direct_vertex(lp_enum_problem* p, uint64_t rank, double* xB, int* su
 // Queues, behind the kernels that fill the feasible list, its evaluation and the tie rule against
 // the list's own best score (tolerance tol) — no host round trip: the caller synchronises once and
 // finds best_key and first_rank in the result block.
-int lp_enum_queue_list_tail(lp_enum_problem* p, double tol, const double* records) {
+int lp_enum_queue_list_tail(lp_enum_problem* p, double tol, const double* records, bool no_record) {
     lp_context* ctx = p->ctx;
     const EnumDev& d = p->dev;
     const PrefixDev& pd = p->prefix;
     const size_t shm = enum_smem_bytes(d);
     const unsigned grid = (unsigned)ctx->num_cus * 2;
-    if (records)
+    if (records) {
         lp_enum_queue_record_eval(p, records);
-    else if (d.m <= 16)
+        if (no_record)   // (16-row records only; the two kernels write disjoint scores and share best_key's atomicMax)
+            hipLaunchKernelGGL((k_enum_eval_list<16>), grid, 256, shm, ctx->stream, d, pd.list, 0ULL,
+                               (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores,
+                               (const int*)pd.list_rec);
+    } else if (d.m <= 16)
         hipLaunchKernelGGL((k_enum_eval_list<16>), grid, 256, shm, ctx->stream, d, pd.list, 0ULL,
-                           (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores);
+                           (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores,
+                           (const int*)nullptr);
     else
         hipLaunchKernelGGL((k_enum_eval_list<32>), grid, 256, shm, ctx->stream, d, pd.list, 0ULL,
-                           (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores);
+                           (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores,
+                           (const int*)nullptr);
     hipLaunchKernelGGL(k_enum_list_first, (unsigned)ctx->num_cus * 4, 256, 0, ctx->stream, d, pd.list, 0ULL,
                        (const unsigned long long*)pd.list_count, (unsigned long long)pd.list_cap, pd.scores, 0.0, tol,
                        0ULL, 1);

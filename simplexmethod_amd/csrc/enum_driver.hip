@@ -16,6 +16,9 @@ using lptree::PG;
 // kEnumNoRoom: no memory for the level buffers, or a level outgrew its buffer (the device's overflow flag):
 // the direct kernel enumerates the range
 constexpr int kEnumNoRoom = 1000;
+#ifndef LP_PARENT_TAILS_BESIDE   // measurement builds: 0 = k_enum_parent_tails behind the last level instead of beside it
+#define LP_PARENT_TAILS_BESIDE 1
+#endif
 // kEnumListOverflow: the feasible list was too small; *h_list_count holds the number of feasible subsets
 // of the range, the caller grows the list, goes dense or splits the range
 constexpr int kEnumListOverflow = 1001;
@@ -43,6 +46,7 @@ static EnumKnobs read_knobs() {
         const int v = atoi(e);
         if (v >= 1024 && v <= 16384 && (v & (v - 1)) == 0) k.chunk1 = v;
     }
+    if (const char* e = getenv("LP_ENUM_PARENT_TAILS")) k.parent_tails = atoi(e) != 0 ? 1 : 0;
     return k;
 }
 
@@ -262,13 +266,14 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
             p->prefix_buf_bytes[k] = got;
         }
     }
+    uint64_t nodes_d0 = 0;   // depth-D0 nodes of the range
     {
         // the range's own node counts (exact) against what the buffers hold
         // (a kept buffer may be larger than this problem's budget share: the budget decides, so that the
         // behaviour does not depend on what ran before)
         const uint64_t have0 = std::min<uint64_t>(p->prefix_buf_bytes[0] / rec_bytes, cap_budget0);
         const uint64_t have1 = std::min<uint64_t>(p->prefix_buf_bytes[1] / rec_prev_bytes, cap_budget1);
-        const uint64_t want0 = host_level_nodes(n, m, begin, end, D0);
+        const uint64_t want0 = nodes_d0 = host_level_nodes(n, m, begin, end, D0);
         const uint64_t want1 = D0 >= 1 ? host_level_nodes(n, m, begin, end, D0 - 1) : 1;
         if (want0 > have0 || want1 > have1 || want0 > 0x7FFFFFFFULL) {
             p->split_hint = std::max<uint64_t>(want0 / std::max<uint64_t>(have0, 1), want1 / std::max<uint64_t>(have1, 1)) + 1;
@@ -282,6 +287,9 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
     // bits set = NaN, which fails its `>=` test (the buffer comes from a pool: old scores, level records)
     if (dense) LP_HIP(ctx, hipMemsetAsync(pd.dense_scores, 0xFF, sizeof(double) * (end - begin), s));
     int launches = 0;
+    // the narrow depth m-7 nodes (at most THIN_TAIL selectable columns) are finished from their parents' records
+    // (enum_leaf.hip: k_enum_parent_tails) where the tuned leaf kernels run: the last level does not store them
+    const bool parent_tails = lp_enum_parent_tails(p, shape, fused, dense, D0, nodes_d0);
     int cur = (D0 % 2 == 0) ? 0 : 1;  // buffer of level 0, so that level D0 is buffer 0
     // All levels and the leaf kernel are queued without a host round trip: every level's record
     // count stays on the device (level_counts[t]); grids are sized for the exact number of the
@@ -305,16 +313,31 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
         const uint64_t waves = bound * (uint64_t)(n - m + 1);
         const int narrow_mult = p->knobs.narrow_mult >= 0 ? p->knobs.narrow_mult : (pg == 16 ? 16 : 128);
         const bool narrow = waves <= (uint64_t)ctx->num_cus * (uint64_t)narrow_mult;
+        const bool last_level = t == D0 - 1;
+        const int stop = (parent_tails && last_level) ? lp_enum_parent_tails_stop(n) : n;
+        if (parent_tails && last_level && LP_PARENT_TAILS_BESIDE) {   // beside the last level (measured: lp_enum_launch_parent_tails)
+            const int rc = lp_enum_launch_parent_tails(p, p->prefix_buf[cur], (int)std::min<uint64_t>(bound, (uint64_t)caps[t]), t, begin, end);
+            if (rc) return rc;
+            ++launches;
+        }
         lp_enum_launch_level(p, shape, t, narrow, bound, p->prefix_buf[cur], t == 0 ? 1 : caps[t], p->prefix_buf[nxt],
-                             cap, begin, end);
+                             cap, stop, begin, end);
         ++launches;
+        if (parent_tails && last_level && !LP_PARENT_TAILS_BESIDE) {   // behind the last level
+            const int rc = lp_enum_launch_parent_tails(p, p->prefix_buf[cur], (int)std::min<uint64_t>(bound, (uint64_t)caps[t]), t, begin, end);
+            if (rc) return rc;
+            ++launches;
+        }
         cur = nxt;
     }
-    const uint64_t root_bound = std::min<uint64_t>(host_level_nodes(n, m, begin, end, D0), 0x7FFFFFFFULL);
+    const uint64_t root_bound = std::min<uint64_t>(nodes_d0, 0x7FFFFFFFULL);
     {
         const int rc = lp_enum_launch_leaves(p, p->prefix_buf[cur], (int)std::min<uint64_t>(root_bound, (uint64_t)caps[D0]),
-                                             D0, fused, shape, dense, begin, end);
-        if (rc) return rc;
+                                             D0, fused, shape, dense, parent_tails, begin, end);
+        if (rc) {   // (no memory for an item table: nothing joined k_enum_parent_tails' stream)
+            if (parent_tails) (void)hipStreamSynchronize(ctx->aux_stream[2]);
+            return rc;
+        }
     }
     ++launches;
     // objectives of the (few) feasible subsets by the direct solver, and the tie rule against this
@@ -323,7 +346,7 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
     if (dense)
         lp_enum_queue_dense_tail(p, kSpecTol, begin, end);
     else
-        lp_enum_queue_list_tail(p, kSpecTol, fused ? p->prefix_buf[cur] : nullptr);
+        lp_enum_queue_list_tail(p, kSpecTol, fused ? p->prefix_buf[cur] : nullptr, parent_tails);
     LP_HIP(ctx, hipEventRecord(p->ev1, s));
     // result, list count, overflow flag and level counts: one block, one copy (enum_problem.hpp: EnumPassBlock)
     LP_HIP(ctx, hipMemcpyAsync(p->h_pass, p->d_pass, sizeof(EnumPassBlock), hipMemcpyDeviceToHost, s));

@@ -28,6 +28,10 @@
 // kernel takes them from the records: 7 columns per lane, the lanes of a wave packed densely over
 // the subsets of consecutive records, whose last columns are staged in LDS with permuted rows.
 //
+// k_enum_parent_tails (wide ranges).  The depth m-7 nodes with at most THIN_TAIL selectable columns — 1, 8 or 36
+// subsets each, three quarters of the level — are not stored at all there: this kernel pivots them from the
+// depth m-8 records, a 16-lane group per node, and finishes their subsets with the tail kernel's routine.
+//
 //   phase 1  the KD rows not used by the prefix x the KD chosen columns (+ rhs) sit in
 //            registers; KD-2 Gauss-Jordan steps with partial pivoting among the unused rows
 //            (pivot row = select chain), then the 2x2 block -> x_a, x_b.
@@ -1386,6 +1390,301 @@ __global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(2)
     if (tid < 3 && s_cnt[tid]) atomicAdd(&d.result->counts[tid], s_cnt[tid]);
 }
 
+// The NARROW depth m-7 nodes finished from their PARENTS' records.  A depth m-7 node with at most T = THIN_TAIL
+// selectable columns (last chosen column a >= n-1-T) holds 1, 8 or 36 subsets and no leaf item: as a stored record
+// it is (R+1)*128 + 64 bytes written by the last level, read once by k_enum_thin and once by the item builder, and
+// such records are three quarters of the level of C(32,16) for 2.7 % of its subsets.  Here they are never stored: the
+// last level stops at column n-1-T (k_enum_expand_staged: stop), and this kernel takes the depth m-8 records, which
+// stay intact in the other level buffer.  k_enum_thin's structure: a wave takes batches of 64 parents, one lane reads
+// each parent's metadata (the next batch's in flight); the narrow children (parent, a), a = max(last+1, n-1-T) ..
+// n-8, whose rank interval meets [begin, end) are compacted into the wave's LDS list (up to three per lane: they are
+// the LAST C(n-a, 8) subsets of the parent, 36 | 8 | 1) with the prefix sums of their subset counts, and passes of 64
+// consecutive subsets run over at most kTailSlots children.  One 16-lane group per child (lane = row, four children
+// at a time, two rounds per pass) loads the parent's columns a .. n-1 and the rhs into registers one pass ahead —
+// eleven loads of 128 bytes per child — and pivots on column a with the level kernel's arithmetic, operand for operand:
+// pick_pivot_row over the rows the parent left unused, plain division, fma(lx, L[c][p], isp ? -0.0 : L[c][row]), the
+// pivot row's entry L[c][p] broadcast inside the group (bcast16).  The result goes to the child's LDS slot with the
+// rows permuted by used | 1 << p, unused rows first, exactly what k_enum_thin stages from a stored record, and the
+// lanes run leaf_verdict<PERM> with the child's min / max |pivot|, which row 0 of the group leaves in LDS.  A child
+// the level kernel would have pruned (no pivot, or min <= eps * m * max) has max = -1 there: its lanes inside
+// [begin, end) count as singular — together the overlap the level kernel adds for a hole.
+// Feasible subsets are listed with record -1 (there is no depth m-7 record: k_enum_eval_records leaves them to
+// k_enum_eval_list, which scores them from scratch, same bits).
+// A child is loaded by itself; loading a parent once for its three children would save the 8- and 1-subset children's
+// loads (half of this kernel's 0.3 GB, out of L2 mostly) for a second kind of slot.
+// (A first form staged the raw columns in the slot, lane = (row, one of four columns) as k_enum_thin, and all four
+// groups pivoted every slot in place: ~100 instructions per child and 14 spilled registers, 1.56 ms by itself for
+// the 16.2 M subsets of C(32,16) against this form's time in lp_enum_launch_parent_tails.)
+struct alignas(16) ParentTailRec {
+    unsigned long long rank0;   // rank of the child's first subset
+    unsigned used;              // rows used by the parent's prefix
+    unsigned src;               // lane that holds the parent's metadata (= parent index inside the batch) | T' << 8
+};
+
+template <bool EXACT, int T>
+__global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void k_enum_parent_tails(EnumDev d, PrefixDev pd,
+                                                             const double* __restrict__ parents,
+                                                             int parent_level, int parent_cap,
+                                                             unsigned long long begin,
+                                                             unsigned long long end) {
+    static_assert(T == 9, "k_enum_parent_tails: three children per parent, 36 | 8 | 1 subsets");
+    constexpr int KD = 7, kSlot = tail_slot(T), kCols = T + 2, kRounds = kTailSlots / 4, kTailComb = tail_comb(T), kKids = T - KD + 1;
+    static_assert(kTailSlots % 4 == 0, "four children per round");
+    __shared__ __attribute__((aligned(16))) double s_slot[LEAF_WAVES][kTailSlots * kSlot];
+    __shared__ ParentTailRec s_rec[LEAF_WAVES][64 * kKids];   // the batch's narrow children in range, compacted
+    __shared__ int s_pre[LEAF_WAVES][64 * kKids + 1];         // exclusive prefix sums of their subset counts (+ the total)
+    __shared__ double s_mm[LEAF_WAVES][kTailSlots][2];        // min / max |pivot| of the staged children (max = -1: pruned)
+    __shared__ double s_par[LEAF_WAVES][64][2];               // ... of the batch's parents (by lane)
+    __shared__ unsigned int s_comb[kTailComb];  // 7-subsets of T' columns in lexicographic order, 4 bits per index
+    __shared__ unsigned int s_b8[NMX + KD + 3]; // C(r, 8)
+    __shared__ unsigned long long s_cnt[3];
+    const int m = d.m, n = d.n, P = m - KD - 1;   // depth of the parents
+    const int nrec = min(pd.level_counts[parent_level], parent_cap);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 3) s_cnt[tid] = 0ULL;
+    if (tid < NMX + KD + 3) s_b8[tid] = (unsigned int)d.binom[tid * kBinomK + KD + 1];
+    if (tid < kTailComb) {
+        const int tp = tid < tail_comb_off(8) ? 7 : tid < tail_comb_off(9) ? 8 : 9;
+        unsigned long long j = (unsigned long long)(tid - tail_comb_off(tp));
+        unsigned pk = 0;
+        int x = 0;
+        for (int t = 0; t < KD; ++t) {
+            for (; x < tp; ++x) {   // subsets whose t-th column is x: C(tp - 1 - x, 6 - t)
+                const unsigned long long cx = binom(d, tp - 1 - x, KD - 1 - t);
+                if (j < cx) break;
+                j -= cx;
+            }
+            pk |= (unsigned)x << (4 * t);
+            ++x;
+        }
+        s_comb[tid] = pk;
+    }
+    __syncthreads();
+    unsigned int cnt[3] = {0u, 0u, 0u};
+    unsigned int viol = 0;
+    double* const slots = s_slot[wave];
+    ParentTailRec* const recs = s_rec[wave];
+    int* const pre = s_pre[wave];
+    const int nbatch = (nrec + 63) >> 6;
+    const int nw = (int)gridDim.x * LEAF_WAVES;
+    const size_t recd = rec_doubles(n, P);
+    const int row = lane & (PG - 1), cg = lane >> 4, gbase = lane & ~(PG - 1);   // pivots: lane = (row, one of 4 children)
+    const unsigned all = (1u << m) - 1u, below = (1u << row) - 1u;
+    const double epsm = DBL_EPSILON * (double)m;
+    int lastN = kHole;
+    unsigned usedN = 0;
+    unsigned long long rbN = 0ULL;
+    double minN = 0.0, maxN = 0.0;
+    auto meta = [&](int batch) {
+        const int rec = batch * 64 + lane;
+        lastN = kHole;
+        if (batch < nbatch && rec < nrec) {
+            const NodeMeta* pm = reinterpret_cast<const NodeMeta*>(parents + (size_t)rec * recd + (size_t)PG * (n - P + 1));
+            lastN = pm->last_col;
+            usedN = pm->used_mask;
+            rbN = pm->rank_base;
+            minN = pm->minp;
+            maxN = pm->maxp;
+        }
+    };
+    double stage[kRounds * kCols] = {};   // a pass's columns in flight: kCols per child, this group's child of each round
+    int batch = (int)blockIdx.x * LEAF_WAVES + wave;
+    meta(batch);
+    for (; batch < nbatch; batch += nw) {
+        const int last = lastN;
+        const unsigned used = usedN;
+        const unsigned long long rb = rbN;
+        s_par[wave][lane][0] = minN;
+        s_par[wave][lane][1] = maxN;
+        meta(batch + nw);
+        const int recbase = batch * 64;
+        // ---- the batch's work list: this parent's narrow children in range (ascending a = rank order)
+        const int Rp = n - 1 - last;   // the parent's selectable columns: C(Rp, 8) subsets, the narrow children's last
+        int ne = 0, c7 = 0;
+        unsigned kept = 0;             // bit ci: child a = n - 1 - (T - ci) is kept
+        const unsigned long long endp = rb + (unsigned long long)s_b8[(last != kHole && Rp >= KD + 1) ? Rp : 0];
+        if (last != kHole && Rp >= KD + 1) {
+#pragma unroll
+            for (int ci = 0; ci < kKids; ++ci) {
+                const int tp = T - ci;
+                const unsigned long long rank0 = endp - (unsigned long long)(tail_comb_off(tp) + tail_count(tp));   // C(tp + 1, 8)
+                if (n - 1 - tp > last && overlap(rank0, (unsigned long long)tail_count(tp), begin, end) != 0ULL) {
+                    kept |= 1u << ci;
+                    ++ne;
+                    c7 += tail_count(tp);
+                }
+            }
+        }
+        int inclE = ne, incl = c7;   // inclusive wave scans: entries, subsets
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int oe = __shfl_up(inclE, off, 64), o = __shfl_up(incl, off, 64);
+            if (lane >= off) {
+                inclE += oe;
+                incl += o;
+            }
+        }
+        const int nk = __shfl(inclE, 63, 64);
+        if (nk == 0) continue;
+        {
+            int k = inclE - ne, at = incl - c7;
+#pragma unroll
+            for (int ci = 0; ci < kKids; ++ci) {
+                if ((kept >> ci) & 1u) {
+                    const int tp = T - ci;
+                    pre[k] = at;
+                    ParentTailRec tr;
+                    tr.rank0 = endp - (unsigned long long)(tail_comb_off(tp) + tail_count(tp));
+                    tr.used = used;
+                    tr.src = (unsigned)lane | ((unsigned)tp << 8);
+                    recs[k] = tr;
+                    ++k;
+                    at += tail_count(tp);
+                }
+            }
+        }
+        if (lane == 63) pre[nk] = incl;
+        const int total = __shfl(incl, 63, 64);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // a pass: subsets [w0, wend) of the list, inside children k0 .. k0 + nslot - 1 (slot = child - k0)
+        auto plan = [&](int k0, int w0, int& nslot, int& wend) {
+            const int k1 = min(k0 + kTailSlots, nk);
+            wend = __builtin_amdgcn_readfirstlane(min(w0 + 64, pre[k1]));
+            const bool starts = lane < k1 - k0 && pre[min(k0 + lane, nk)] < wend;
+            nslot = __popcll(__ballot(starts));
+        };
+        // Round h of a pass: group cg takes the child of slot 4 h + cg.  Column cc of a child = the parent's column
+        // a + cc, a = n - 1 - T' (cc = 0: the pivot column, cc = T' + 1: the rhs).
+        auto issue = [&](int k0, int nslot) {   // loads of a pass's columns (no use of the data here)
+#pragma unroll
+            for (int h = 0; h < kRounds; ++h) {
+                if (4 * h < nslot) {   // (wave-uniform; a group without a child repeats the round's first one)
+                    const int sl = 4 * h + cg;
+                    const unsigned srcw = recs[k0 + (sl < nslot ? sl : 4 * h)].src;
+                    const int tp = (int)(srcw >> 8);
+                    const double* p = parents + (size_t)(recbase + (int)(srcw & 0xFFu)) * recd + (size_t)(n - 1 - tp - P) * PG + row;
+                    // (a column past the rhs is replaced by the pivot column and never used: the load stays unconditional)
+#pragma unroll
+                    for (int cc = 0; cc < kCols; ++cc) stage[h * kCols + cc] = p[(cc <= tp + 1) ? cc * PG : 0];
+                }
+            }
+        };
+        auto commit = [&](int k0, int nslot) {  // the child pivots: registers -> LDS slots, rows permuted: unused rows first
+#pragma unroll
+            for (int h = 0; h < kRounds; ++h) {
+                if (4 * h < nslot) {
+                    const int sl = 4 * h + cg;
+                    const bool active = sl < nslot;   // whole groups are active or not
+                    const ParentTailRec tr = recs[k0 + (active ? sl : 4 * h)];
+                    const int tp = (int)(tr.src >> 8), src = (int)(tr.src & 0xFFu);
+                    const bool prow_used = (row >= m) || ((tr.used >> row) & 1u);
+                    const double w = stage[h * kCols];   // the pivot column a
+                    double big;
+                    const int p = pick_pivot_row(w, prow_used, gbase, big);
+                    const double pmin = s_par[wave][src][0], pmax = s_par[wave][src][1];
+                    const double minp = fmin(pmin, big), maxp = fmax(pmax, big);
+                    const bool pruned = !(big > 0.0) || minp <= epsm * maxp;
+                    const int addr = (gbase + p) << 2;
+                    const double piv = bcast16(w, addr);
+                    const double inv = 1.0 / piv;
+                    const bool isp = (row == p);
+                    const double lx = isp ? inv : -(w * inv);
+                    const unsigned usedc = (tr.used | (1u << p)) & all, freem = ~usedc & all;
+                    const int pos = (row >= m) ? row
+                                    : ((freem >> row) & 1u) ? __builtin_popcount(freem & below)
+                                                            : __builtin_popcount(freem) + __builtin_popcount(usedc & below);
+                    double* q = slots + sl * kSlot + pos;
+#pragma unroll
+                    for (int cc = 1; cc < kCols; ++cc) {
+                        const double v = stage[h * kCols + cc];
+                        const double pe = bcast16(v, addr);   // the pivot row's entry (every lane of the wave takes part)
+                        if (active && cc <= tp + 1) q[(cc - 1) * TS] = fma(lx, pe, isp ? -0.0 : v);
+                    }
+                    if (active && row == 0) {
+                        s_mm[wave][sl][0] = minp;
+                        s_mm[wave][sl][1] = pruned ? -1.0 : maxp;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        };
+        int k0 = 0, w0 = 0, nslot, wend;
+        plan(k0, w0, nslot, wend);
+        issue(k0, nslot);
+        for (;;) {
+            commit(k0, nslot);
+            // (as in k_enum_thin: every staged load has landed; the explicit wait keeps the next pass's loads from
+            // waiting for each other through the reuse of the staging registers)
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_waitcnt(kWaitVm0);
+            const int kn = k0 + nslot - (pre[k0 + nslot] == wend ? 0 : 1);
+            const bool more = wend < total;
+            int nslotN = 0, wendN = 0;
+            if (more) {
+                plan(kn, wend, nslotN, wendN);
+                issue(kn, nslotN);
+            }
+            // ---- one subset per lane
+            const int w = w0 + lane;
+            int s = 0;
+            for (int q = 1; q < nslot; ++q) s += (pre[k0 + q] <= w) ? 1 : 0;
+            const ParentTailRec tr = recs[k0 + s];
+            const int tp = (int)(tr.src >> 8);
+            const double minp0 = s_mm[wave][s][0], maxp0 = s_mm[wave][s][1];
+            const int j = w - pre[k0 + s];
+            int verdict = -1;
+            unsigned long long rank = 0ULL;
+            if (w < wend) {
+                rank = tr.rank0 + (unsigned long long)j;
+                if (rank >= begin && rank < end) {
+                    if (maxp0 < 0.0) {
+                        verdict = 2;   // below a child the level kernel prunes
+                    } else {
+                        const unsigned pk = s_comb[tail_comb_off(tp) + j];
+                        int c[KD];
+#pragma unroll
+                        for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (4 * t)) & 15u);
+                        const int U[KD] = {0, 1, 2, 3, 4, 5, 6};   // unused by leaf_verdict<PERM>
+                        verdict = leaf_verdict<KD, TS, true, false, !EXACT, false>(slots + s * kSlot, c, tp, U, 0u, minp0, maxp0,
+                                                                                   m, nullptr, &viol);
+                    }
+                }
+            }
+            if (verdict == 0) {
+                const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
+                if (at < pd.list_cap) {
+                    pd.list[at] = rank;
+                    pd.list_rec[at] = -1;
+                }
+            }
+            cnt[0] += verdict == 0;
+            cnt[1] += verdict == 1;
+            cnt[2] += verdict == 2;
+            if (!more) break;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();   // (the slots are rewritten by the next pass)
+            k0 = kn;
+            w0 = wend;
+            nslot = nslotN;
+            wend = wendN;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();   // (the list is rewritten by the next batch)
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        unsigned int c = cnt[v];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        if ((tid & 63) == 0 && c) atomicAdd(&s_cnt[v], (unsigned long long)c);
+    }
+    if (!EXACT && viol) atomicOr(&d.result->range_flag, 1ULL);
+    __syncthreads();
+    if (tid < 3 && s_cnt[tid]) atomicAdd(&d.result->counts[tid], s_cnt[tid]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The general leaf kernel: ANY record height (PGT = 16 or 32 rows) and any number of selectable
 // columns.  The three kernels above are tuned for m <= 16, n - m <= 16 (subset tables, LDS slices
@@ -1669,7 +1968,9 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_enum_eval_records(EnumDev d, P
     for (unsigned long long e = (unsigned long long)blockIdx.x * LEAF_THREADS + tid; e < count;
          e += (unsigned long long)gridDim.x * LEAF_THREADS) {
         const unsigned long long rank = pd.list[e];
-        const double* Q = roots + (size_t)pd.list_rec[e] * rec_doubles_g<PGT>(n, D, d.rs);
+        const int rec = pd.list_rec[e];
+        if (rec < 0) continue;   // found under a narrow node that has no record (k_enum_parent_tails): k_enum_eval_list's
+        const double* Q = roots + (size_t)rec * rec_doubles_g<PGT>(n, D, d.rs);
         const int RS = rec_rs<PGT>(d.rs);
         const NodeMetaT<PGT>* pm = reinterpret_cast<const NodeMetaT<PGT>*>(Q + (size_t)RS * (n - D + 1));
         const int last = pm->last_col;
@@ -1719,6 +2020,16 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_enum_eval_records(EnumDev d, P
 
 }  // namespace
 
+// Ranges of fewer depth m-7 records than this keep every record (measured in lp_enum_launch_leaves: an 8-way shard of
+// C(32,16), 250 k records, and C(28,14), 116 k, pay for k_enum_parent_tails; the whole C(32,16), 2.04 M, gains) —
+// the threshold of kItemLanesNarrow and kChunkWide.  LP_ENUM_PARENT_TAILS=0 / 1 decides for every range.
+constexpr uint64_t kParentTailsMinRecords = 300000;
+bool lp_enum_parent_tails(const lp_enum_problem* p, int shape, bool fused, bool dense, int level, uint64_t records) {
+    if (shape != 1 || !fused || dense || level < 1 || p->knobs.parent_tails == 0) return false;
+    return p->knobs.parent_tails == 1 || records >= kParentTailsMinRecords;
+}
+int lp_enum_parent_tails_stop(int n) { return n - 1 - THIN_TAIL; }
+
 void lp_enum_queue_record_eval(lp_enum_problem* p, const double* roots) {
     lp_context* ctx = p->ctx;
     if (p->dev.m > PG)
@@ -1729,12 +2040,63 @@ void lp_enum_queue_record_eval(lp_enum_problem* p, const double* roots) {
                            p->prefix, roots, p->prefix.scores);
 }
 
+static int leaf_streams(lp_context* ctx) {
+    if (!ctx->aux_stream[0]) {
+        for (hipStream_t& a : ctx->aux_stream) LP_HIP(ctx, hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
+        for (hipEvent_t& ev : ctx->aux_event) LP_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    return LP_OPTIMAL;
+}
+
+// The narrow depth m-7 nodes of the pass from the depth m-8 records (`parents`, count in level_counts[level], at most
+// `bound`): queued on a stream of its own behind whatever the library's stream holds at this point, so that it runs
+// beside what is queued there next, and neither the tail kernel nor the leaf kernels wait for it.  aux_event[3]
+// marks its end: lp_enum_launch_leaves makes the library's stream wait for it at the end of the pass.
+#ifndef LP_PARENT_TAILS_PER_CU
+#define LP_PARENT_TAILS_PER_CU 2
+#endif
+int lp_enum_launch_parent_tails(lp_enum_problem* p, const double* parents, int bound, int level, uint64_t begin,
+                                uint64_t end) {
+    lp_context* ctx = p->ctx;
+    int rc = leaf_streams(ctx);
+    if (rc) return rc;
+    hipStream_t sT = ctx->aux_stream[2];
+    LP_HIP(ctx, hipEventRecord(ctx->aux_event[3], ctx->stream));   // the parents' level is complete
+    LP_HIP(ctx, hipStreamWaitEvent(sT, ctx->aux_event[3], 0));
+    // 254-register waves as the tail kernel's: a CU has room for two workgroups, of this kernel or of that one.
+    // Measured on one MI355X against the parent's library, alternating (profiles/enum_parent_tails.json), C(32,16):
+    //   bound, before the kernel existed (last level without the narrow children, their 16.2 M subsets simply missing):
+    //     pass 12.69 -> 10.88 ms wall; last level 1.21 -> 0.47 ms, item builder 1.71 -> 0.77 ms, tail kernel 1.79 -> 0.76 ms
+    //     (they run side by side), last level's end to the first leaf block 1.72 -> 0.79 ms
+    //   this kernel, pass wall (means of 12, three rounds), parent 12.70 ms:
+    //     beside the last level, 2 / 1 workgroups per CU: 11.83 / 12.08 ms;  behind it: 11.96 / 11.90 ms
+    //     (kernel trace, beside, 2 per CU: 2.05 ms from the last level's start to the item builder's end — it shares
+    //     the CUs' registers with the tail kernel, 1.68 ms instead of 0.76, and the item builder takes 1.56 ms between
+    //     them; the leaf kernels start 2.87 ms into the pass instead of 3.75 ms)
+    //   its first form (raw columns staged in the slot, all four groups pivot every slot; the tail kernel queued behind
+    //   it on one stream, which then started beside the leaf kernels and ended the pass): 13.55 / 13.89 ms beside,
+    //   12.91 / 14.35 ms behind
+    //   small ranges PAY: slowest 8-way shard 1.94 -> 2.17 ms, C(28,14) 1.12 -> 1.18 ms (their item builder is over in
+    //   0.05 ms; this kernel's blocks hold the registers the leaf kernels wait for) — hence kParentTailsMinRecords;
+    //   with it the shards of a 2- / 4- / 8-way cut take 6.62 / 3.59 / 1.96 -> 6.44 / 3.55 / 1.94 ms (slowest, two runs)
+    //   bench step, 7 runs each: 12.693 -> 11.879 ms (-6.4 %; the parent's runs within 0.18 ms)
+    const unsigned grid = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>((uint64_t)std::max(bound, 1), 64 * LEAF_WAVES),
+                                                       (uint64_t)ctx->num_cus * LP_PARENT_TAILS_PER_CU);
+    const unsigned long long b = begin, e = end;
+    if (p->exact_div)
+        hipLaunchKernelGGL((k_enum_parent_tails<true, THIN_TAIL>), grid, LEAF_THREADS, 0, sT, p->dev, p->prefix, parents, level, bound, b, e);
+    else
+        hipLaunchKernelGGL((k_enum_parent_tails<false, THIN_TAIL>), grid, LEAF_THREADS, 0, sT, p->dev, p->prefix, parents, level, bound, b, e);
+    LP_HIP(ctx, hipEventRecord(ctx->aux_event[3], sT));
+    return LP_OPTIMAL;
+}
+
 // Second phase of the shared-prefix pass over the records of the last breadth-first level
 // (`roots`, count in level_counts[level], at most `bound`): depth m-7 records (fused = true: the
 // regular kernel pivots once more itself, the thin kernel takes the small tails) or, for m = 6, the
 // root record.  `bound6` bounds the number of depth m-6 nodes (sizes the item table).
 int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, int level, bool fused,
-                          int shape, bool dense, uint64_t begin, uint64_t end) {
+                          int shape, bool dense, bool parent_tails, uint64_t begin, uint64_t end) {
     lp_context* ctx = p->ctx;
     PrefixDev& pd = p->prefix;
     const int n = p->dev.n, m = p->dev.m;
@@ -1793,10 +2155,8 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         // streams, so that the tail kernel runs beside the item builder and every leaf kernel's tail (persistent
         // waves running out of items) is filled by the next kernel's blocks.  The library's stream
         // waits for the other two before anything that follows (list evaluation, result copy).
-        if (!ctx->aux_stream[0]) {
-            for (hipStream_t& a : ctx->aux_stream) LP_HIP(ctx, hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
-            for (hipEvent_t& ev : ctx->aux_event) LP_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
+        rc = leaf_streams(ctx);
+        if (rc) return rc;
         hipStream_t s = ctx->stream, sT = ctx->aux_stream[0], s1 = ctx->aux_stream[1];
         const int lanes = bound < 300000 ? kItemLanesNarrow : kItemLanesWide;
         // width of a table-1 item (kChunkWide above; LP_ENUM_CHUNK pins it for tests and measurements)
@@ -1833,6 +2193,8 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         //     there when the leaf kernels start.  Alone behind the item builder: 1.989 / 2.002 ms, C(28,14) 1.161 ms.
         //     Eight columns on ranges of fewer than 300,000 records (a build with both widths): shards 1.935 / 2.029 ms,
         //     but C(28,14) 1.178 / 1.200 ms and its bench leg 1.110 -> 1.148 ms; so one width for every range.
+        // (k_enum_parent_tails, which takes the narrow records' work on wide ranges: placements and grids measured in
+        // lp_enum_launch_parent_tails; the tail kernel then handles the stored records, all with >= 10 selectable columns)
         const int thin_per_cu = 2;
         const unsigned grid_thin = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>((uint64_t)bound, 64 * LEAF_WAVES), (uint64_t)ctx->num_cus * thin_per_cu);
         if (exact)
@@ -1861,6 +2223,7 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[2], s1));
         LP_HIP(ctx, hipStreamWaitEvent(s, ctx->aux_event[0], 0));
         LP_HIP(ctx, hipStreamWaitEvent(s, ctx->aux_event[2], 0));
+        if (parent_tails) LP_HIP(ctx, hipStreamWaitEvent(s, ctx->aux_event[3], 0));   // k_enum_parent_tails, on its own stream
     } else {
         hipLaunchKernelGGL(k_enum_make_items<false>, lp_ceil_div(bound, 1024), 1024, 0, ctx->stream, p->dev, pd,
                            roots, level, bound, 0, 1, kChunk, b, e);

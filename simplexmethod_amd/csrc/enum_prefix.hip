@@ -67,7 +67,7 @@ constexpr int kStagedParents = 256; // ... of k_enum_expand_staged (16-row recor
 template <int NMXT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_enum_expand_staged(EnumDev d, PrefixDev pd, int t,
                                                             const double* __restrict__ src, int src_cap,
-                                                            double* __restrict__ dst, int dst_cap, int ppw,
+                                                            double* __restrict__ dst, int dst_cap, int ppw, int stop,
                                                             unsigned long long begin,
                                                             unsigned long long end) {
     constexpr int PGT = 16, RS = 16, GW = 4;
@@ -91,7 +91,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int nsrc = min(pd.level_counts[t], src_cap);  // (an overflowed level is reported by the host)
     const int first = blockIdx.x * 4 * ppw;
     if (first >= nsrc) return;
-    const int lim = n - m + t;  // largest column selectable at depth t
+    // largest column expanded at depth t: the largest selectable one, n - m + t, or stop - 1 (children from column
+    // `stop` on are finished from this level's records by k_enum_parent_tails, enum_leaf.hip: no slot, no store and
+    // no singular count for them here; they are the last ones of their parent, so the others' rank bases stand)
+    const int lim = min(n - m + t, stop - 1);
     __syncthreads();
     const size_t rdP = rec_doubles_g<PGT>(n, t, d.rs), rdC = rec_doubles_g<PGT>(n, t + 1, d.rs);
     {   // phase A: children per parent and ONE slot allocation per block — here over up to 256 parents, a lane each in
@@ -453,7 +456,7 @@ __global__ __launch_bounds__(256) void k_enum_expand_staged32(EnumDev d, PrefixD
 template <int PGT, int NMXT>
 __global__ __launch_bounds__(256) void k_enum_expand_narrow(EnumDev d, PrefixDev pd, int t,
                                                             const double* __restrict__ src, int src_cap,
-                                                            double* __restrict__ dst, int dst_cap,
+                                                            double* __restrict__ dst, int dst_cap, int stop,
                                                             unsigned long long begin,
                                                             unsigned long long end) {
     const int m = d.m, n = d.n, S = n - m + 1;   // S = most children a node can have
@@ -468,7 +471,7 @@ __global__ __launch_bounds__(256) void k_enum_expand_narrow(EnumDev d, PrefixDev
     const double* P = src + (size_t)node * rec_doubles_g<PGT>(n, t, d.rs);
     const Meta pm = *reinterpret_cast<const Meta*>(P + (size_t)RS * (n - t + 1));
     const int a = pm.last_col + 1 + j;
-    if (pm.last_col == kHole || a > n - m + t) return;
+    if (pm.last_col == kHole || a > n - m + t || a >= stop) return;   // (stop: as in k_enum_expand_staged)
     // subsets below the siblings in front of this child: one lane per sibling and a wave sum (a loop of up to
     // n - m dependent little loads from the table in L2 was most of a narrow level's 8-60 us)
     const int a2 = pm.last_col + 1 + lane;
@@ -584,9 +587,10 @@ void lp_enum_launch_root(lp_enum_problem* p, int pg, double* dst) {
 }
 
 // Level t -> t+1 over the rank range [begin, end).  bound: the level's parents inside the range (exact; its holes
-// among them).  Grids are sized for bound; blocks beyond the level's actual count return at once.
+// among them).  Grids are sized for bound; blocks beyond the level's actual count return at once.  stop: the first
+// column whose child is not expanded (n: every child is; honoured by the kernels of 16-row records).
 void lp_enum_launch_level(lp_enum_problem* p, int shape, int t, bool narrow, uint64_t bound, const double* src,
-                          int src_cap, double* dst, int cap, uint64_t begin, uint64_t end) {
+                          int src_cap, double* dst, int cap, int stop, uint64_t begin, uint64_t end) {
     lp_context* ctx = p->ctx;
     hipStream_t s = ctx->stream;
     const EnumDev& d = p->dev;
@@ -595,11 +599,11 @@ void lp_enum_launch_level(lp_enum_problem* p, int shape, int t, bool narrow, uin
     if (narrow) {   // one wave per (parent, child)
         const unsigned grid = (unsigned)lp_ceil_div<uint64_t>(bound * (uint64_t)(d.n - d.m + 1), 4);
         if (shape == 1)
-            hipLaunchKernelGGL((k_enum_expand_narrow<16, 16>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, b, e);
+            hipLaunchKernelGGL((k_enum_expand_narrow<16, 16>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, stop, b, e);
         else if (shape == 2)
-            hipLaunchKernelGGL((k_enum_expand_narrow<16, 57>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, b, e);
+            hipLaunchKernelGGL((k_enum_expand_narrow<16, 57>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, stop, b, e);
         else
-            hipLaunchKernelGGL((k_enum_expand_narrow<32, 32>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, b, e);
+            hipLaunchKernelGGL((k_enum_expand_narrow<32, 32>), grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, d.n, b, e);
     } else if (shape == 3) {
         // 4 * ppw parents per block; ppw = 16 once that still leaves 32 waves per CU
         const int ppw = (int)std::max<uint64_t>(1, std::min<uint64_t>(kExpandParents / 4, bound / ((uint64_t)ctx->num_cus * 32)));
@@ -610,8 +614,8 @@ void lp_enum_launch_level(lp_enum_problem* p, int shape, int t, bool narrow, uin
         const int ppw = (int)std::max<uint64_t>(1, std::min<uint64_t>(kStagedParents / 4, bound / ((uint64_t)ctx->num_cus * 32)));
         const unsigned grid = (unsigned)lp_ceil_div<uint64_t>(bound, 4 * (uint64_t)ppw);
         if (shape == 1)
-            hipLaunchKernelGGL(k_enum_expand_staged<16>, grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, ppw, b, e);
+            hipLaunchKernelGGL(k_enum_expand_staged<16>, grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, ppw, stop, b, e);
         else
-            hipLaunchKernelGGL(k_enum_expand_staged<57>, grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, ppw, b, e);
+            hipLaunchKernelGGL(k_enum_expand_staged<57>, grid, 256, 0, s, d, pd, t, src, src_cap, dst, cap, ppw, stop, b, e);
     }
 }

@@ -93,6 +93,8 @@ struct EnumKnobs {
     bool exact_div = false;          // LP_ENUM_EXACT_DIV=1: plain divisions from the first pass on
     int narrow_mult = -1;            // LP_ENUM_NARROW_MULT (-1: by record width)
     int chunk1 = 0;                  // LP_ENUM_CHUNK: subsets per table-1 leaf item, a power of two from 1024 to 16384 (0: by range)
+    int parent_tails = -1;           // LP_ENUM_PARENT_TAILS: 0 = every depth m-7 node is stored and finished from its own record,
+                                     // 1 = the narrow ones from their parents' on any range (-1: by range size)
 };
 
 // The feasible list a successful shared-prefix pass left on the device (prefix.list / scores, or in the
@@ -180,21 +182,33 @@ int lp_enum_direct_vertex(lp_enum_problem* p, uint64_t rank, double* xB, int* su
 // smallest rank of the list whose score is within tol of score_star (UINT64_MAX if none)
 int lp_enum_list_first(lp_enum_problem* p, const EnumList& list, double score_star, double tol, uint64_t* rank_out);
 // evaluation + tie rule against the list's own best, queued without a host round trip; records !=
-// null: the depth m-7 records of the pass (the entries are evaluated from them, enum_leaf.hip)
-int lp_enum_queue_list_tail(lp_enum_problem* p, double tol, const double* records);
+// null: the depth m-7 records of the pass (the entries are evaluated from them, enum_leaf.hip); no_record: some entries
+// have none (list_rec = -1, k_enum_parent_tails) and are solved from scratch beside them
+int lp_enum_queue_list_tail(lp_enum_problem* p, double tol, const double* records, bool no_record);
 int lp_enum_queue_dense_tail(lp_enum_problem* p, double tol, uint64_t begin, uint64_t end);
 void lp_enum_queue_record_eval(lp_enum_problem* p, const double* records);
 
 // enum_prefix.hip: the root record (pg = 16 or 32 rows; also resets the pass's counters), and level t -> t+1
 // of the breadth-first phase (bound: the level's parents inside [begin, end); narrow: one wave per child)
 void lp_enum_launch_root(lp_enum_problem* p, int pg, double* dst);
+// stop: the first column whose child is not expanded (n: every child is)
 void lp_enum_launch_level(lp_enum_problem* p, int shape, int t, bool narrow, uint64_t bound, const double* src,
-                          int src_cap, double* dst, int cap, uint64_t begin, uint64_t end);
+                          int src_cap, double* dst, int cap, int stop, uint64_t begin, uint64_t end);
 
 // enum_leaf.hip: one lane per subset below the records of the last breadth-first level
 // (shape: enum_driver.hip: prefix_shape — 1 = the tuned kernels, 2 / 3 = the general kernel on 16- / 32-row records)
 // dense: every subset's score goes to prefix.dense_scores[rank - begin] (general kernel), no list
+// parent_tails: lp_enum_launch_parent_tails was queued for this pass (the library's stream joins it at the end)
 int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, int level, bool fused,
-                          int shape, bool dense, uint64_t begin, uint64_t end);
+                          int shape, bool dense, bool parent_tails, uint64_t begin, uint64_t end);
+// enum_leaf.hip: whether this pass finishes its narrow depth m-7 nodes from the depth m-8 records (the tuned leaf
+// kernels only: shape 1, fused, list form, at least one level; records: the depth m-7 nodes of the range), and the
+// first column of such a node (n - 1 - THIN_TAIL)
+bool lp_enum_parent_tails(const lp_enum_problem* p, int shape, bool fused, bool dense, int level, uint64_t records);
+int lp_enum_parent_tails_stop(int n);
+// ... and the kernel that finishes them from the depth m-8 records (`bound` of them at most, level = m-8), on the tail
+// kernel's stream behind what the library's stream holds when it is called
+int lp_enum_launch_parent_tails(lp_enum_problem* p, const double* parents, int bound, int level, uint64_t begin,
+                                uint64_t end);
 // enum_leaf.hip: recip_midrange(x[i]) and 1.0 / x[i] computed on the device (lp_debug_reciprocal)
 int lp_enum_debug_reciprocal(lp_context* ctx, const double* x, int n, double* fast_out, double* plain_out);

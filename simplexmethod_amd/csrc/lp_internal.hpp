@@ -27,10 +27,10 @@ struct lp_context {
     unsigned* dcomb6 = nullptr;
     unsigned* dcomb5 = nullptr;
     unsigned* dcomb4 = nullptr;
-    // two more streams + events (created on first use): the enumeration's independent leaf kernels run
+    // three more streams + events (created on first use): the enumeration's independent leaf kernels run
     // side by side so that one kernel's tail is filled by the next one's head
-    hipStream_t aux_stream[2] = {nullptr, nullptr};
-    hipEvent_t aux_event[3] = {nullptr, nullptr, nullptr};
+    hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t aux_event[4] = {nullptr, nullptr, nullptr, nullptr};
     // freed enumeration problems with every allocation intact (their ~20 device / pinned allocations
     // and events cost more than a C(28,14) solve); lp_enum_upload refills one instead of allocating
     std::vector<void*> enum_shells;
