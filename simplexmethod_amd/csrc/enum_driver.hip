@@ -47,6 +47,7 @@ static EnumKnobs read_knobs() {
         if (v >= 1024 && v <= 16384 && (v & (v - 1)) == 0) k.chunk1 = v;
     }
     if (const char* e = getenv("LP_ENUM_PARENT_TAILS")) k.parent_tails = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("LP_ENUM_LEAF_QUADS")) k.leaf_quads = atoi(e) != 0 ? 1 : 0;
     return k;
 }
 

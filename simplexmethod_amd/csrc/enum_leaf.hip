@@ -21,6 +21,10 @@
 // in-LDS pivot and its lanes take 5 columns each (items of table 1).  k_enum_leaves<1> finishes
 // what is left of each child (items of table 0).
 //
+// k_enum_leaves_quads (table 0 of the fused path; k_enum_leaves<1> stays for m = 6 and behind LP_ENUM_LEAF_QUADS=0).
+// One table entry per child; a wave pivots four children at once, a 16-lane group each, straight from the record's
+// columns in registers, and its passes of 64 subsets run on from one round of children into the next.
+//
 // k_enum_thin (the tails).  A depth m-6 node with fewer than THIN_TAIL = 9 selectable columns holds at
 // most C(8,6) = 28 subsets: as a work item it would cost a pivot and a wave pass for a handful of
 // lanes, and such nodes are most of their level.  Their subsets are exactly the ones that lie
@@ -437,14 +441,15 @@ constexpr int kItemLanesWide = 4, kItemLanesNarrow = 8;
 //     group, rank offset of the group inside the record) — a large group in chunks of kChunk, or
 //     several consecutive small groups packed into one item;
 //   table 0 (k_enum_leaves<1>): the child's remaining subsets — (record, a, first subset of the
-//     chunk inside the child, rank offset of the child inside the record).
+//     chunk inside the child, rank offset of the child inside the record).  `quads` (k_enum_leaves_quads): one
+//     entry per child; else children 2k and 2k+1 of a record share an item.
 // !FUSED (m = 6): the one record is the depth m-6 root itself, table 0 only.
 template <bool FUSED>
 __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev pd,
                                                          const double* __restrict__ roots,
                                                          int root_level, int root_cap, int min_child_R,
-                                                         int kItemLanes, int chunk1, unsigned long long begin,
-                                                         unsigned long long end) {
+                                                         int kItemLanes, int chunk1, int quads,
+                                                         unsigned long long begin, unsigned long long end) {
     constexpr int KD = 6;
     const unsigned long long kChunk1 = (unsigned long long)chunk1;   // width of a table-1 item (kChunk or a multiple)
     // C(r, 5) and C(r, 6) for r <= NMX + KD + 1, from LDS (the loops below are chains of dependent
@@ -539,6 +544,10 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
         // from the one record and fills its passes from both tails), emitted by the even one.
         const bool odd = (a - last - 1) & 1;
         const bool mine = overlap(rb + off2, L - off2, begin, end) != 0ULL;
+        if (quads) {   // one entry per child; a lane's children stay adjacent in the table
+            if (mine) emit(0, a, (int)off2, (int)(rb - rb0));
+            return;
+        }
         bool partner = false;   // does the other child of the pair exist and overlap?
         if (!odd && a + 1 <= lim && n - 2 - a >= min_child_R) {
             const int Rn = R - 1;
@@ -566,7 +575,7 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
                 if (R >= min_child_R && ((a - last - 1) >> 1) % kItemLanes == sub) {
                     if (decltype(count_only)::value && rb >= begin && rb + L <= end) {
                         for (int k = 0; k < s_n1[R]; ++k) emit(1, 0, 0, 0);
-                        if (!((a - last - 1) & 1)) emit(0, 0, 0, 0);
+                        if (quads || !((a - last - 1) & 1)) emit(0, 0, 0, 0);
                     } else {
                         child(a, R, L, rb, lim, emit);
                     }
@@ -1685,6 +1694,302 @@ __global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(2)
     if (tid < 3 && s_cnt[tid]) atomicAdd(&d.result->counts[tid], s_cnt[tid]);
 }
 
+// Table 0 by quarters of a wave (LP_ENUM_LEAF_QUADS): k_enum_leaves<1>'s work with k_enum_parent_tails' front end.
+// A table-0 entry is ONE child (record, child column a, first subset of the tail, rank offset of the child); a wave
+// takes rounds of up to four consecutive entries, from the same or from different records.  Group cg (lanes 16 cg ..
+// 16 cg + 15, lane = row) loads its child's pivot column, its last min(R, kGrandMin) columns and the rhs — at most
+// twelve 128-byte lines, one round ahead, nothing of the record is staged in LDS — and pivots from the registers with
+// k_enum_leaves<1>'s arithmetic, operand for operand: pick_pivot_row over the rows the record left unused, 1.0 / piv,
+// lx = isp ? inv : -(w * inv), fma(lx, pe, isp ? -0.0 : v) with the pivot row's entry pe broadcast inside the group.
+// The child's columns go to the group's LDS slot (column j of the child at slot column j - (R - min(R, kGrandMin)))
+// with the rows permuted, unused rows first.  A child the level kernel would have pruned counts its subsets inside
+// [begin, end) as singular, once, and contributes no lanes.
+// The slots are two halves of four: the rounds of a wave form one stream of subsets, and a pass of 64 consecutive
+// subsets may end in the next round's half, which is committed when fewer than 64 subsets of the current round are
+// left — so every pass but a wave's last is full (k_enum_leaves<1>: a single 84-subset child is two passes at 66 %).
+// Every lane finds its slot by the prefix sums of the round's tails and runs leaf_verdict as k_enum_leaves<1> does.
+// Dealing: k_enum_leaves<1>'s runs (static first deal, fixed runs in LDS taken by compare-and-swap, the siblings'
+// runs at the end, s_dry), a round at a time; a run is kQuadRun entries, two whole rounds.
+constexpr int kQuadCols = kGrandMin + 1;                 // columns of a slot: the child's last kGrandMin and the rhs
+constexpr int kQuadSlot = (kQuadCols * TS) | 1;          // doubles per slot (odd: see tail_slot)
+#ifndef LP_QUAD_RUN   // measurement builds: entries per run (a multiple of four: whole rounds)
+#define LP_QUAD_RUN 8
+#endif
+constexpr int kQuadRun = LP_QUAD_RUN;
+static_assert(kQuadRun >= 4 && kQuadRun % 4 == 0, "a run is a whole number of rounds");
+// What a lane needs of its slot, in one read: subset w of the round (pre <= w < pre + the entry's count) is subset
+// leaf = leaf0 + (w - pre) of the child, so rank, subset-table index and tableau address are w plus a constant.
+struct alignas(8) QuadSlot {
+    unsigned long long rank0;   // rank of subset w = rank0 + w
+    double minp, maxp;          // smallest / largest |pivot| down to the child
+    int comb0;                  // its entry of pd.comb6 = comb0 + w
+    int tab0;                   // the child's column 0 (slots + tab0; the slot holds columns R - min(R, kGrandMin) .. R)
+    int R;                      // selectable columns of the child
+    int rec;                    // depth m-7 record (list_rec)
+};
+
+template <bool EXACT>
+__global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
+void k_enum_leaves_quads(EnumDev d, PrefixDev pd, const double* __restrict__ roots, unsigned long long begin,
+                         unsigned long long end) {
+    constexpr int KD = 6;
+    __shared__ __attribute__((aligned(16))) double s_slot[LEAF_WAVES][8 * kQuadSlot];
+    __shared__ QuadSlot s_q[LEAF_WAVES][8];
+    __shared__ unsigned int s_b6[NMX + KD + 2];   // C(r, 6)
+    __shared__ unsigned long long s_cnt[3];
+    __shared__ unsigned int s_off[32];            // offsets of the per-R subset tables inside pd.comb6
+    __shared__ unsigned int s_rows[36];           // leaf_row_table<6>
+    __shared__ unsigned long long s_run[LEAF_WAVES];
+    __shared__ int s_dry;
+    const int m = d.m, n = d.n, D = m - KD - 1;   // depth of the records
+    const int4* const items = pd.items;
+    const int nitems = min(pd.item_count[0], pd.item_cap);
+    int* const cursor = pd.root_cursor;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = lane & (PG - 1), cg = lane >> 4, gbase = lane & ~(PG - 1);
+    if (tid < NMX + KD + 2) s_b6[tid] = (unsigned int)d.binom[tid * kBinomK + KD];
+    if (tid < 3) s_cnt[tid] = 0ULL;
+    if (tid < 32) s_off[tid] = pd.comb6[tid];
+    leaf_row_table<KD>(s_rows, tid);
+    const int nwaves = (int)gridDim.x * LEAF_WAVES;
+    // the first deal is static, whole rounds where the table is long enough
+    const int share = nitems / (nwaves * 4);
+    const int k0 = share >= kQuadRun ? kQuadRun : share >= 4 ? 4 : max(1, share);
+    const int dyn_base = nwaves * k0;
+    auto pack_run = [](int next, int end_) { return ((unsigned long long)(unsigned)next << 32) | (unsigned)end_; };
+    {
+        const int first = ((int)blockIdx.x * LEAF_WAVES + wave) * k0;
+        if (lane == 0) s_run[wave] = pack_run(min(first, nitems), min(first + k0, nitems));
+        if (tid == 0) s_dry = 0;
+    }
+    __syncthreads();
+    unsigned int cnt[3] = {0u, 0u, 0u};
+    unsigned int viol = 0;
+    // up to four entries of wave w's run: first entry (-1: the run is empty), count in nE
+    auto take = [&](int w, int& nE) {
+        int first = -1, k = 0;
+        if (lane == 0) {
+            unsigned long long cur = __hip_atomic_load(&s_run[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            while ((unsigned)(cur >> 32) < (unsigned)cur) {
+                const unsigned left = (unsigned)cur - (unsigned)(cur >> 32);
+                const unsigned kk = left < 4u ? left : 4u;
+                if (__hip_atomic_compare_exchange_strong(&s_run[w], &cur, cur + ((unsigned long long)kk << 32), __ATOMIC_RELAXED,
+                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                    first = (int)(cur >> 32);
+                    k = (int)kk;
+                    break;
+                }
+            }
+        }
+        nE = __builtin_amdgcn_readfirstlane(k);
+        return __builtin_amdgcn_readfirstlane(first);
+    };
+    bool dry = dyn_base >= nitems, none = false;
+    auto draw = [&](int& nE) {   // the next round: first entry (nitems: nothing left) and its number of entries
+        nE = 0;
+        if (none) return nitems;
+        int first = take(wave, nE);
+        if (first >= 0) return first;
+        if (!dry && __hip_atomic_load(&s_dry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) dry = true;
+        if (!dry) {
+            int v = 0, over = 0;
+            if (lane == 0) {
+                v = atomicAdd(cursor, kQuadRun);
+                // (a list far beyond its capacity: the caller switches to the dense form, the waves stop drawing)
+                over = __hip_atomic_load(pd.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > pd.list_abort;
+            }
+            v = __builtin_amdgcn_readfirstlane(v) + dyn_base;
+            if (__builtin_amdgcn_readfirstlane(over)) v = nitems;
+            if (v < nitems) {
+                nE = min(4, nitems - v);
+                if (lane == 0)
+                    __hip_atomic_store(&s_run[wave], pack_run(v + nE, min(v + kQuadRun, nitems)), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+                return v;
+            }
+            dry = true;
+            if (lane == 0) __hip_atomic_store(&s_dry, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        for (int q = 1; q < LEAF_WAVES; ++q) {
+            first = take((wave + q) & (LEAF_WAVES - 1), nE);
+            if (first >= 0) return first;
+        }
+        none = true;
+        nE = 0;
+        return nitems;
+    };
+    const size_t recd = rec_doubles(n, D);
+    const int rec_cols = n - D + 1;
+    const unsigned all = (1u << m) - 1u, below = (1u << row) - 1u;
+    const double epsm = DBL_EPSILON * (double)m;
+    double* const slots = s_slot[wave];
+    QuadSlot* const sq = s_q[wave];
+    // Three rounds are under way: D, drawn, record and child column of its entries in flight (itD); N, its columns in
+    // flight (stage) or already committed to the half the current round does not use; C, the current round, in half
+    // `half`.  What else a pivot needs — the rest of the entry word and the record's metadata, lines this wave has
+    // loaded a round earlier — is read at the commit: held across the passes it cost the lanes' loop its registers.
+    int2 itD = make_int2(0, 0), itN = make_int2(0, 0);
+    int nD = 0, nN = 0, firstD = 0, firstN = 0;
+    double stage[kQuadCols + 1] = {};
+    auto fetch_words = [&]() {   // round D's entries (a group without an entry repeats the round's last one)
+        int nE;
+        firstD = draw(nE);
+        nD = nE;
+        if (nE > 0) itD = *reinterpret_cast<const int2*>(items + firstD + min(cg, nE - 1));
+    };
+    auto issue = [&]() {   // round D becomes round N: loads of its columns (no use of the data here)
+        itN = itD;
+        nN = nD;
+        firstN = firstD;
+        if (nN == 0) return;
+        const double* Q = roots + (size_t)itN.x * recd;
+        const int a = itN.y & 0xFF, R = n - 1 - a, jlo = max(R - kGrandMin, 0);
+        const double* p = Q + (size_t)(a - D) * PG + row;   // the pivot column; child column j = record column a + 1 + j
+        stage[0] = p[0];
+        // (a column past the rhs is replaced by the pivot column and never used: the load stays unconditional)
+#pragma unroll
+        for (int k = 0; k < kQuadCols; ++k) stage[1 + k] = p[(k <= R - jlo) ? (1 + jlo + k) * PG : 0];
+    };
+    // round N's child pivots: registers -> the four slots of half h, rows permuted: unused rows first.  pre[k]: the
+    // round's subsets inside [begin, end) below children that are not pruned, in front of entry k + 1; returns their total.
+    auto commit = [&](int h, int (&pre)[3]) {
+        const bool active = cg < nN;   // whole groups are active or not
+        const int2 lo_roff = *reinterpret_cast<const int2*>(&items[firstN + min(cg, nN - 1)].z);
+        const NodeMeta* pm = reinterpret_cast<const NodeMeta*>(roots + (size_t)itN.x * recd + (size_t)PG * rec_cols);
+        const unsigned long long rbN = pm->rank_base;
+        const double minN = pm->minp, maxN = pm->maxp;
+        const unsigned usedN = pm->used_mask;   // (the item builder makes no entry for a hole)
+        const int a = itN.y & 0xFF, R = n - 1 - a, jlo = max(R - kGrandMin, 0);
+        const bool prow_used = (row >= m) || ((usedN >> row) & 1u);
+        const double w = stage[0];
+        double big;
+        const int p = pick_pivot_row(w, prow_used, gbase, big);
+        const double minp = fmin(minN, big), maxp = fmax(maxN, big);
+        const bool pruned = !(big > 0.0) || minp <= epsm * maxp;
+        const int addr = (gbase + p) << 2;
+        const double piv = bcast16(w, addr);
+        const double inv = 1.0 / piv;
+        const bool isp = (row == p);
+        const double lx = isp ? inv : -(w * inv);
+        const unsigned usedc = (usedN | (1u << p)) & all, freem = ~usedc & all;
+        const int pos = (row >= m) ? row
+                        : ((freem >> row) & 1u) ? __builtin_popcount(freem & below)
+                                                : __builtin_popcount(freem) + __builtin_popcount(usedc & below);
+        const int sl = 4 * h + cg;
+        double* q = slots + sl * kQuadSlot + pos;
+#pragma unroll
+        for (int k = 0; k < kQuadCols; ++k) {
+            const double v = stage[1 + k];
+            const double pe = bcast16(v, addr);   // the pivot row's entry (every lane of the wave takes part)
+            if (active && k <= R - jlo) q[k * TS] = fma(lx, pe, isp ? -0.0 : v);
+        }
+        // the entry's subsets [lo, L) of the child, clipped to the range
+        const unsigned long long rb = rbN + (unsigned long long)(unsigned)lo_roff.y;
+        const unsigned int L = s_b6[R >= 0 ? R : 0], lo = (unsigned int)lo_roff.x;
+        const unsigned long long r0 = rb + lo;
+        unsigned int ov = (active && R >= KD && lo < L) ? (unsigned int)overlap(r0, L - lo, begin, end) : 0u;
+        const unsigned int skip = begin > r0 ? (unsigned int)(begin - r0) : 0u;
+        if (pruned) {
+            if (row == 0) cnt[2] += ov;   // every subset below this child is singular
+            ov = 0u;
+        }
+        const int c0 = __builtin_amdgcn_readlane((int)ov, 0), c1 = __builtin_amdgcn_readlane((int)ov, 16),
+                  c2 = __builtin_amdgcn_readlane((int)ov, 32), c3 = __builtin_amdgcn_readlane((int)ov, 48);
+        const int pre_e = cg == 0 ? 0 : cg == 1 ? c0 : cg == 2 ? c0 + c1 : c0 + c1 + c2;
+        if (row == 0) {
+            const int d0 = (int)(lo + skip) - pre_e;   // leaf - w
+            QuadSlot s;
+            s.rank0 = rb + (unsigned long long)(long long)d0;
+            s.minp = minp;
+            s.maxp = maxp;
+            s.comb0 = (int)s_off[R] + d0;
+            s.tab0 = sl * kQuadSlot - jlo * TS;
+            s.R = R;
+            s.rec = itN.x;
+            sq[sl] = s;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        pre[0] = c0;
+        pre[1] = c0 + c1;
+        pre[2] = c0 + c1 + c2;
+        return c0 + c1 + c2 + c3;
+    };
+    fetch_words();
+    // (the loop starts as if an empty round N had been committed behind an empty current one: its first two turns
+    // issue and commit the wave's first round through the same code as every other)
+    int half = 0, totC = 0, totN = 0, w0 = 0;
+    int preC[3] = {0, 0, 0}, preN[3] = {0, 0, 0};
+    bool committedN = true;
+    const int U[KD] = {0, 1, 2, 3, 4, 5};        // unused by leaf_verdict<PERM>
+    for (;;) {
+        if (totC - w0 < 64 && nN > 0 && !committedN) {
+            // fewer than 64 subsets of the current round are left: the next pass runs on into round N
+            // (the half it is written to held the round before the current one: no lane reads it any more)
+            totN = commit(half ^ 1, preN);
+            committedN = true;
+        }
+        if (w0 >= totC) {   // the current round is finished: round N takes its place
+            if (!committedN) break;   // (there is none)
+            w0 -= totC;
+            half ^= 1;
+            totC = totN;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) preC[q] = preN[q];
+            totN = 0;
+            committedN = false;
+            issue();
+            fetch_words();
+            continue;
+        }
+        const int avail = totC - w0 + (committedN ? totN : 0);
+        const int len = avail < 64 ? avail : 64;
+        // ---- one subset per lane
+        int verdict = -1;
+        unsigned long long rank = 0ULL;
+        int rec = 0;
+        if (lane < len) {
+            const int w = w0 + lane;
+            const bool inN = w >= totC;
+            const int wl = inN ? w - totC : w;
+            const int s = (wl >= (inN ? preN[0] : preC[0]) ? 1 : 0) + (wl >= (inN ? preN[1] : preC[1]) ? 1 : 0) +
+                          (wl >= (inN ? preN[2] : preC[2]) ? 1 : 0);
+            const QuadSlot e = sq[4 * (inN ? half ^ 1 : half) + s];
+            rank = e.rank0 + (unsigned long long)(unsigned)wl;
+            rec = e.rec;
+            const unsigned pk = pd.comb6[e.comb0 + wl];
+            int c[KD];
+#pragma unroll
+            for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
+            verdict = leaf_verdict<KD, TS, true, false, !EXACT, true>(slots + e.tab0, c, e.R, U, 0u, e.minp, e.maxp, m, nullptr,
+                                                                      &viol, s_rows);
+        }
+        if (verdict == 0) {
+            const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
+            if (at < pd.list_cap) {
+                pd.list[at] = rank;
+                pd.list_rec[at] = rec;
+            }
+        }
+        cnt[0] += verdict == 0;
+        cnt[1] += verdict == 1;
+        cnt[2] += verdict == 2;
+        w0 += len;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();   // (the other half is rewritten once this round is finished)
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        unsigned int c = cnt[v];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        if (lane == 0 && c) atomicAdd(&s_cnt[v], (unsigned long long)c);
+    }
+    if (!EXACT && viol) atomicOr(&d.result->range_flag, 1ULL);
+    __syncthreads();
+    if (tid < 3 && s_cnt[tid]) atomicAdd(&d.result->counts[tid], s_cnt[tid]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The general leaf kernel: ANY record height (PGT = 16 or 32 rows) and any number of selectable
 // columns.  The three kernels above are tuned for m <= 16, n - m <= 16 (subset tables, LDS slices
@@ -2030,6 +2335,14 @@ bool lp_enum_parent_tails(const lp_enum_problem* p, int shape, bool fused, bool 
 }
 int lp_enum_parent_tails_stop(int n) { return n - 1 - THIN_TAIL; }
 
+// Table 0 by k_enum_leaves_quads (one entry per child, four children pivoted per wave at once) or by
+// k_enum_leaves<1> (paired items).  LP_ENUM_LEAF_QUADS=0 / 1 decides for every range; unset, the new kernel runs on
+// every range — no threshold: measured on one MI355X against the parent's library, alternating
+// (profiles/enum_leaf_quads.json), C(32,16) pass 11.86 -> 11.44 ms wall, slowest shard of a 2- / 4- / 8-way cut 6.43 /
+// 3.56 / 1.94 -> 6.16 / 3.40 / 1.87 ms, C(28,14) 1.124 -> 1.122 ms; bench step, 7 runs each: 11.970 -> 11.557 ms
+// (-3.45 %; the parent's runs within 0.07 ms).  SQ_INSTS_VALU of table 0's kernel 2.169 -> 2.015 G per pass.
+static bool leaf_quads(const lp_enum_problem* p) { return p->knobs.leaf_quads != 0; }
+
 void lp_enum_queue_record_eval(lp_enum_problem* p, const double* roots) {
     lp_context* ctx = p->ctx;
     if (p->dev.m > PG)
@@ -2159,6 +2472,7 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         if (rc) return rc;
         hipStream_t s = ctx->stream, sT = ctx->aux_stream[0], s1 = ctx->aux_stream[1];
         const int lanes = bound < 300000 ? kItemLanesNarrow : kItemLanesWide;
+        const bool quads = leaf_quads(p);
         // width of a table-1 item (kChunkWide above; LP_ENUM_CHUNK pins it for tests and measurements)
         const int chunk1 = p->knobs.chunk1 ? p->knobs.chunk1 : bound < kChunkWideMinRecords ? kChunk : kChunkWide;
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[0], s));          // the level records are complete
@@ -2202,7 +2516,7 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         else
             hipLaunchKernelGGL((k_enum_thin<false, THIN_TAIL>), grid_thin, LEAF_THREADS, 0, sT, p->dev, pd, roots, level, bound, b, e);
         hipLaunchKernelGGL(k_enum_make_items<true>, lp_ceil_div(bound * lanes, 1024), 1024, 0, s, p->dev, pd,
-                           roots, level, bound, THIN_TAIL, lanes, chunk1, b, e);
+                           roots, level, bound, THIN_TAIL, lanes, chunk1, quads ? 1 : 0, b, e);
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[1], s));          // both item tables are built
         LP_HIP(ctx, hipStreamWaitEvent(s1, ctx->aux_event[1], 0));
         // both leaf kernels with resident-sized grids (3 workgroups per CU).  (2 for table 1's kernel gives the best
@@ -2214,10 +2528,16 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
 #endif
         if (exact) {
             hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, true>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
-            hipLaunchKernelGGL((k_enum_leaves<1, true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
+            if (quads)
+                hipLaunchKernelGGL((k_enum_leaves_quads<true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
+            else
+                hipLaunchKernelGGL((k_enum_leaves<1, true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
         } else {
             hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, false>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
-            hipLaunchKernelGGL((k_enum_leaves<1, false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
+            if (quads)
+                hipLaunchKernelGGL((k_enum_leaves_quads<false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
+            else
+                hipLaunchKernelGGL((k_enum_leaves<1, false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
         }
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[0], sT));
         LP_HIP(ctx, hipEventRecord(ctx->aux_event[2], s1));
@@ -2226,7 +2546,7 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         if (parent_tails) LP_HIP(ctx, hipStreamWaitEvent(s, ctx->aux_event[3], 0));   // k_enum_parent_tails, on its own stream
     } else {
         hipLaunchKernelGGL(k_enum_make_items<false>, lp_ceil_div(bound, 1024), 1024, 0, ctx->stream, p->dev, pd,
-                           roots, level, bound, 0, 1, kChunk, b, e);
+                           roots, level, bound, 0, 1, kChunk, 0, b, e);
         if (exact)
             hipLaunchKernelGGL((k_enum_leaves<0, true>), grid6, LEAF_THREADS, 0, ctx->stream, p->dev, pd, roots, kChunk, b, e);
         else

@@ -95,6 +95,8 @@ struct EnumKnobs {
     int chunk1 = 0;                  // LP_ENUM_CHUNK: subsets per table-1 leaf item, a power of two from 1024 to 16384 (0: by range)
     int parent_tails = -1;           // LP_ENUM_PARENT_TAILS: 0 = every depth m-7 node is stored and finished from its own record,
                                      // 1 = the narrow ones from their parents' on any range (-1: by range size)
+    int leaf_quads = -1;             // LP_ENUM_LEAF_QUADS: 0 = table 0 by k_enum_leaves<1> with paired items, 1 = by
+                                     // k_enum_leaves_quads, one entry per child (-1: the default, the latter)
 };
 
 // The feasible list a successful shared-prefix pass left on the device (prefix.list / scores, or in the
