@@ -68,6 +68,9 @@ constexpr int THIN_TAIL = 9;
 #ifndef LP_LEAF_CUT_ROUNDS   // diagnostic builds: 0 = the shared pivots copy six rounds of columns whatever the width
 #define LP_LEAF_CUT_ROUNDS 1
 #endif
+#ifndef LP_LEAF_UNROLL_ROWS   // diagnostic builds: 0 = phase 2 of the tuned leaf kernels as a rolled loop over the rows
+#define LP_LEAF_UNROLL_ROWS 1
+#endif
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
                                       // same row of different columns hit different banks
 
@@ -120,6 +123,18 @@ __device__ __forceinline__ double recip_midrange(double x) {
     return fma(fma(-x, r2, 1.0), r2, r2);
 }
 constexpr double kRecipLo = 0x1p-500, kRecipHi = 0x1p500;
+
+// Phase 2 of leaf_verdict on rows I .. END-1 of a tableau of m rows, every row index a constant: row(i, true) while a
+// lane of the wave is still alive.
+template <int I, int END, class Row>
+__device__ __forceinline__ void leaf_rows_unrolled(int m, const bool& alive, Row& row) {
+    if constexpr (I < END) {
+        if (I < m && __any(alive)) {
+            row(I, true);
+            leaf_rows_unrolled<I + 1, END>(m, alive, row);
+        }
+    }
+}
 
 // FAST: every division is recip_midrange(pivot); *redo is set if a pivot of THIS function that is a number other
 // than zero lay outside its range — whatever the verdict: every later pivot, and with it `sing`, then rests on
@@ -325,8 +340,11 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         if constexpr (OBJ) xr[r] = x;
     }
     // ---- phase 2: rows already used by the prefix, one at a time
-    // (a subset survives phase 1 with probability ~2^-8, so the loop below usually ends
-    // after a row or two: it stops as soon as no lane of the wave is still feasible)
+    // (the loop below stops as soon as no lane of the wave is still feasible.  A lane survives phase 1 with
+    // probability ~2^-KD — about one half per component: C(32,16), seed 0, has 8,102 feasible subsets of 601 M,
+    // 2^-16.2 — so with six or seven columns per lane the loop usually ends after a row or two; with the four of
+    // k_enum_leaves<3>'s sub-groups about four lanes of a full pass are still alive here, and it runs for about
+    // three rows — 0.8 ms of a C(32,16) pass as a rolled loop: profiles/enum_leaf_defer.json)
     bool alive = !sing && feas;
     unsigned rows = used & (m >= 32 ? ~0u : ((1u << m) - 1u));
     auto one_row = [&](int i, bool has) {
@@ -361,6 +379,13 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         z = fma(obj->cost[obj->col0 + c[KD - 2]], xa, z);
         z = fma(obj->cost[obj->col0 + c[KD - 1]], xb, z);
         obj->z = z;
+    } else if constexpr (PERM && TAB && LP_LEAF_UNROLL_ROWS) {
+        // (the tuned kernels, tableaus of PG rows: unrolled over the rows the tableau can hold, so that every row is an
+        // LDS read at an immediate offset from the column addresses phase 1 already holds — the rolled loop spends ten
+        // of its ~26 vector instructions per row on addresses: a running pointer per column and an add per read)
+        // (by recursion: the compiler does not unroll a loop that leaves through a wave vote)
+        static_assert(STRIDE == PG + 1, "rows of a tableau in LDS");
+        leaf_rows_unrolled<KD, PG>(m, alive, one_row);
     } else if constexpr (PERM) {
         for (int i = KD; i < m && __any(alive); ++i) one_row(i, true);
     } else {
