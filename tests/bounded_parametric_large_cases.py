@@ -51,8 +51,10 @@ def beyond(path, m, n, seed, maximize, kind="mixed"):
 def tall(path, reverse):
     """More basis positions and more columns than the selectors have threads: a minimisation from the slack basis (in
     order: the crash is skipped; reversed: the crash and the row permutation run), optimal at t = 0 because every
-    structural cost is positive and b lies inside the slacks' boxes.  The first breakpoint is an exact tie across the
-    1024 seam: of two positions (RHS path) or of two columns (cost path)."""
+    structural cost is positive and b lies inside the slacks' boxes.  The first breakpoint is an exact tie of two tau
+    candidates, two positions (RHS path) or two columns (cost path), across the 1024 stride of the gather, which runs
+    on all 1024 threads.  The entering chain and the ratio test behind it run on 960 threads and are replayed in tiles
+    of 1024: their seams are pinned by tests/bounded_parametric_seam_cases.py."""
     m, n = TALL_SHAPE
     rng = np.random.default_rng(TALL_SEED)
     k = n - m
