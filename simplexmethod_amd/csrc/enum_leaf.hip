@@ -71,6 +71,14 @@ constexpr int THIN_TAIL = 9;
 #ifndef LP_LEAF_UNROLL_ROWS   // diagnostic builds: 0 = phase 2 of the tuned leaf kernels as a rolled loop over the rows
 #define LP_LEAF_UNROLL_ROWS 1
 #endif
+#ifndef LP_LEAF_MASKED_ROT   // leaf_verdict's row rotation: 1 = 64-bit moves under the lane mask (one statement per row);
+#define LP_LEAF_MASKED_ROT 1 // diagnostic builds: 0 = the select form
+#endif
+#ifndef LP_LEAF_MASKED_2X2   // the 2x2 block's row choice: 1 = a row swap under the lane mask (nine 64-bit moves);
+#define LP_LEAF_MASKED_2X2 1 // diagnostic builds: 0 = twelve selects
+#endif
+// -DLP_LEAF_NO_ROTATE (diagnostic builds, WRONG RESULTS on purpose): the chosen row is taken to be row t — the pass
+// time without any rotation, the bound on what a cheaper rotation can return.
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
                                       // same row of different columns hit different banks
 
@@ -123,6 +131,120 @@ __device__ __forceinline__ double recip_midrange(double x) {
     return fma(fma(-x, r2, 1.0), r2, r2);
 }
 constexpr double kRecipLo = 0x1p-500, kRecipHi = 0x1p500;
+
+// d[k] = s[k], k < N, in the lanes of `mask`; the other lanes keep d.  One 64-bit move per value under the lane mask
+// instead of two 32-bit selects: the mask is saved, narrowed and restored by scalar instructions, which do not take
+// the vector slot the leaf kernels are bound by.  `mask` is a wave vote taken under the current lane mask, so lanes
+// that are off stay off; an empty mask executes the moves as no-ops (no branch: the routine stays one basic block).
+// One statement, so that nothing can be scheduled between the mask's change and its restoration; the saved mask is
+// an early-clobber scalar pair of the compiler's choosing.  No s_nop stands between the mask's writes and the moves:
+// the ISA's table of required software wait states lists none for a scalar write of the lane mask followed by a
+// vector ALU instruction, and the compiler's own divergent blocks place none behind their s_and_saveexec_b64.
+#define LP_MM_HEAD "s_and_saveexec_b64 %0, %[m]\n\t"
+#define LP_MM_TAIL "s_mov_b64 exec, %0"
+#define LP_MM(k) "v_mov_b64 %[d" #k "], %[s" #k "]\n\t"
+#define LP_MM_D(k) [d##k] "+v"(d[k])
+#define LP_MM_S(k) [s##k] "v"(s[k])
+template <int N>
+__device__ __forceinline__ void masked_moves(unsigned long long mask, double (&d)[N], const double (&s)[N]) {
+    static_assert(N >= 4 && N <= 8, "KD - t + 1 values per row: KD <= 7, t <= KD - 3");
+    unsigned long long sv;
+    if constexpr (N == 4)
+        asm(LP_MM_HEAD LP_MM(0) LP_MM(1) LP_MM(2) LP_MM(3) LP_MM_TAIL
+            : "=&s"(sv), LP_MM_D(0), LP_MM_D(1), LP_MM_D(2), LP_MM_D(3)
+            : [m] "s"(mask), LP_MM_S(0), LP_MM_S(1), LP_MM_S(2), LP_MM_S(3)
+            : "scc");
+    else if constexpr (N == 5)
+        asm(LP_MM_HEAD LP_MM(0) LP_MM(1) LP_MM(2) LP_MM(3) LP_MM(4) LP_MM_TAIL
+            : "=&s"(sv), LP_MM_D(0), LP_MM_D(1), LP_MM_D(2), LP_MM_D(3), LP_MM_D(4)
+            : [m] "s"(mask), LP_MM_S(0), LP_MM_S(1), LP_MM_S(2), LP_MM_S(3), LP_MM_S(4)
+            : "scc");
+    else if constexpr (N == 6)
+        asm(LP_MM_HEAD LP_MM(0) LP_MM(1) LP_MM(2) LP_MM(3) LP_MM(4) LP_MM(5) LP_MM_TAIL
+            : "=&s"(sv), LP_MM_D(0), LP_MM_D(1), LP_MM_D(2), LP_MM_D(3), LP_MM_D(4), LP_MM_D(5)
+            : [m] "s"(mask), LP_MM_S(0), LP_MM_S(1), LP_MM_S(2), LP_MM_S(3), LP_MM_S(4), LP_MM_S(5)
+            : "scc");
+    else if constexpr (N == 7)
+        asm(LP_MM_HEAD LP_MM(0) LP_MM(1) LP_MM(2) LP_MM(3) LP_MM(4) LP_MM(5) LP_MM(6) LP_MM_TAIL
+            : "=&s"(sv), LP_MM_D(0), LP_MM_D(1), LP_MM_D(2), LP_MM_D(3), LP_MM_D(4), LP_MM_D(5), LP_MM_D(6)
+            : [m] "s"(mask), LP_MM_S(0), LP_MM_S(1), LP_MM_S(2), LP_MM_S(3), LP_MM_S(4), LP_MM_S(5), LP_MM_S(6)
+            : "scc");
+    else
+        asm(LP_MM_HEAD LP_MM(0) LP_MM(1) LP_MM(2) LP_MM(3) LP_MM(4) LP_MM(5) LP_MM(6) LP_MM(7) LP_MM_TAIL
+            : "=&s"(sv), LP_MM_D(0), LP_MM_D(1), LP_MM_D(2), LP_MM_D(3), LP_MM_D(4), LP_MM_D(5), LP_MM_D(6), LP_MM_D(7)
+            : [m] "s"(mask), LP_MM_S(0), LP_MM_S(1), LP_MM_S(2), LP_MM_S(3), LP_MM_S(4), LP_MM_S(5), LP_MM_S(6), LP_MM_S(7)
+            : "scc");
+}
+#undef LP_MM_HEAD
+#undef LP_MM_TAIL
+#undef LP_MM
+#undef LP_MM_D
+#undef LP_MM_S
+
+// Rows x1 <-> x2 (three values each) in the lanes of `mask`: three 64-bit moves per value through a scratch register
+// that is defined in those lanes only.
+__device__ __forceinline__ void masked_row_swap(unsigned long long mask, double (&x1)[3], double (&x2)[3]) {
+    unsigned long long sv;
+    double tmp;
+    asm("s_and_saveexec_b64 %0, %[m]\n\t"
+        "v_mov_b64 %[t], %[a0]\n\tv_mov_b64 %[a0], %[b0]\n\tv_mov_b64 %[b0], %[t]\n\t"
+        "v_mov_b64 %[t], %[a1]\n\tv_mov_b64 %[a1], %[b1]\n\tv_mov_b64 %[b1], %[t]\n\t"
+        "v_mov_b64 %[t], %[a2]\n\tv_mov_b64 %[a2], %[b2]\n\tv_mov_b64 %[b2], %[t]\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(sv), [t] "=&v"(tmp), [a0] "+v"(x1[0]), [a1] "+v"(x1[1]), [a2] "+v"(x1[2]), [b0] "+v"(x2[0]),
+          [b1] "+v"(x2[1]), [b2] "+v"(x2[2])
+        : [m] "s"(mask)
+        : "scc");
+}
+
+// leaf_verdict's rotation at step T: row p (T <= p < KD) of [E[:, T..KD-1] | H] moves to position T, rows T..p-1 down
+// by one.  Every move of a row shares one condition — r == p for the chosen row's way into the temporaries, r <= p
+// for the shift, from the highest row down — so a row is KD-T+1 moves under one mask.  Pure moves: the values and the
+// order of the rows are the select form's, bit for bit.
+// The masks come from the pivot search itself: eq[r] is the wave's vote on |E[r][T]| == big (a compare writes it to
+// a scalar pair as it is), row r > T is the chosen one where eq[r] holds and no eq[T..r-1] does, and r <= p where some
+// row holds the maximum and none of T..r-1 does (no row does if the column is all NaN: p = T, nothing moves) — scalar
+// and / or / and-not on the votes in place of the select chain for p and two integer compares per row.
+template <int KD, int T>
+__device__ __forceinline__ void leaf_rotate_masked(double (&E)[KD][KD], double (&H)[KD], double big) {
+    if constexpr (T < KD - 2) {
+        constexpr int N = KD - T + 1;
+        unsigned long long eq[KD], before[KD], any = 0ull;   // before[r]: a row of T..r-1 holds the maximum
+#pragma unroll
+        for (int r = T; r < KD; ++r) {
+            eq[r] = __builtin_amdgcn_ballot_w64(fabs(E[r][T]) == big);
+            before[r] = any;
+            any |= eq[r];
+        }
+        auto get = [&](int r, double (&v)[N]) {
+#pragma unroll
+            for (int k = 0; k < N - 1; ++k) v[k] = E[r][T + k];
+            v[N - 1] = H[r];
+        };
+        auto put = [&](int r, const double (&v)[N]) {
+#pragma unroll
+            for (int k = 0; k < N - 1; ++k) E[r][T + k] = v[k];
+            H[r] = v[N - 1];
+        };
+        double pr[N];
+        get(T, pr);
+#pragma unroll
+        for (int r = T + 1; r < KD; ++r) {
+            double v[N];
+            get(r, v);
+            masked_moves<N>(eq[r] & ~before[r], pr, v);    // r == p
+        }
+#pragma unroll
+        for (int r = KD - 1; r > T; --r) {
+            double d[N], s[N];
+            get(r, d);
+            get(r - 1, s);
+            masked_moves<N>(any & ~before[r], d, s);       // r <= p
+            put(r, d);
+        }
+        put(T, pr);
+    }
+}
 
 // Phase 2 of leaf_verdict on rows I .. END-1 of a tableau of m rows, every row index a constant: row(i, true) while a
 // lane of the wave is still alive.
@@ -269,8 +391,22 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         }
         minp = fmin(minp, big);
         maxp = fmax(maxp, big);
-        // rotate row p to position t (columns t..KD-1 and the rhs)
-        if (!(PERM && t <= 1))
+        // rotate row p to position t (columns t..KD-1 and the rhs).  A select on a double is two v_cndmask_b32, and
+        // every select of a row shares one condition: by default the rows move as 64-bit moves under the lane mask
+        // (leaf_rotate_masked; profiles/enum_leaf_masked_rot.json), the select form stays behind LP_LEAF_MASKED_ROT 0
+#ifdef LP_LEAF_NO_ROTATE
+        const bool rotate = false;
+#else
+        const bool rotate = !(PERM && t <= 1);
+#endif
+        if (rotate && LP_LEAF_MASKED_ROT) {
+            static_assert(KD <= 7, "leaf_rotate_masked: steps 0..4");
+            if (t == 0) leaf_rotate_masked<KD, 0>(E, H, big);
+            else if (t == 1) leaf_rotate_masked<KD, 1>(E, H, big);
+            else if (t == 2) leaf_rotate_masked<KD, 2>(E, H, big);
+            else if (t == 3) leaf_rotate_masked<KD, 3>(E, H, big);
+            else leaf_rotate_masked<KD, 4>(E, H, big);
+        } else if (rotate)
 #pragma unroll
         for (int cc = t; cc <= KD; ++cc) {
             double pr = (cc < KD) ? E[t][cc < KD ? cc : 0] : H[t];
@@ -311,8 +447,14 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
     const double a1 = E[KD - 2][KD - 2], a2 = E[KD - 1][KD - 2], b1 = E[KD - 2][KD - 1],
                  b2 = E[KD - 1][KD - 1], h1 = H[KD - 2], h2 = H[KD - 1];
     const bool second = fabs(a2) > fabs(a1);
+#if LP_LEAF_MASKED_2X2
+    double row1[3] = {a1, b1, h1}, row2[3] = {a2, b2, h2};
+    masked_row_swap(__builtin_amdgcn_ballot_w64(second), row1, row2);
+    const double pa = row1[0], pb = row1[1], ph = row1[2], qa = row2[0], qb = row2[1], qh = row2[2];
+#else
     const double pa = second ? a2 : a1, pb = second ? b2 : b1, ph = second ? h2 : h1;
     const double qa = second ? a1 : a2, qb = second ? b1 : b2, qh = second ? h1 : h2;
+#endif
     const double big1 = fabs(pa);
     const double inv1 = recip(pa);
     const double l = -(qa * inv1);
