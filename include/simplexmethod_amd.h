@@ -599,10 +599,10 @@ int lp_simplex_bounded_fits(int m, int n);
  *     block below; m <= 9968 under LP_PIVOT_DEVEX).  The dual solution and ranging at these shapes are
  *     lp_basis_bounded_duals_large and lp_basis_bounded_ranging_large below, and the evidence for an LP_INFEASIBLE or
  *     LP_UNBOUNDED verdict is lp_basis_bounded_certificate_large; the parametric paths along b + t d and c + t g are
- *     lp_basis_bounded_parametric_large and lp_basis_bounded_parametric_cost_large.  Out of scope on this path:
- *     branch and bound, which stays at lp_simplex_bounded_fits shapes.  The re-solve from a basis at these shapes is
- *     lp_simplex_bounded_resolve_large below.  lp_simplex_bounded itself is unchanged and still refuses larger
- *     shapes.                                                                                                     */
+ *     lp_basis_bounded_parametric_large and lp_basis_bounded_parametric_cost_large.  The re-solve
+ *     from a basis at these shapes is lp_simplex_bounded_resolve_large below, and branch and bound over the bounds is
+ *     lp_mip_bounded_solve_large (with the bounded MIP block).  lp_simplex_bounded itself is unchanged and still
+ *     refuses larger shapes.                                                                                      */
 int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out);
 /* The re-solve of lp_simplex_bounded_resolve (below) on the tableau in HBM (the definition is
  * tests/ref/bounded_resolve_ref.c, and the results equal it bit for bit): after lp_simplex_bounded_large, tightening a
@@ -701,8 +701,8 @@ int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule);
  *     bound_out as lp_mip_solve.  A node LP that ends neither LP_OPTIMAL nor LP_INFEASIBLE stops the search with its
  *     status;
  *   - stats_out[5] = nodes solved, dual pivots, primal pivots, bound flips, deepest level (crash pivots not counted);
- *   - only shapes with lp_mip_bounded_fits(m, n, max_depth) run: the others get LP_BAD_ARG.  There is no per-LP host
- *     path.                                                                                                        */
+ *   - only shapes with lp_mip_bounded_fits(m, n, max_depth) run: the others get LP_BAD_ARG here, and are what
+ *     lp_mip_bounded_solve_large below is for.                                                                     */
 int lp_mip_bounded_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
 /* A batch of problems of one shape and one mask: arrays as lp_simplex_bounded_resolve_batched; outputs x_out
  * batch*n_orig, obj_out / bound_out / found_out / status_out batch, stats_out batch*5.  root_status (batch ints, may
@@ -712,6 +712,20 @@ int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, in
 /* 1: lp_simplex_bounded_fits' carve plus max_depth records of 24 + 4 m + 4 ceil(n / 32) bytes fits one CU's 160 KB and
  * max_depth is in [0, 1024] (64 x 192 at depth 64, 32 x 96 at 256, 16 x 40 at 1024); 0 otherwise.  A host call.      */
 int lp_mip_bounded_fits(int m, int n, int max_depth);
+/* The search of lp_mip_bounded_solve on the tableau in HBM (the definition is still
+ * tests/ref/mip_bounded_ref.c, and every output equals it bit for bit), one problem per call.  The host drives the
+ * depth-first search; A, b and c go up once, and the tableau, the bound state, the incumbent and the records' bases and
+ * flags stay on the device.  A node that ended LP_OPTIMAL is evaluated by one launch (x, z, pruning, the branching
+ * column, the record, the first child's bound change on the live tableau) and one host sync; the first child then runs
+ * lp_simplex_bounded_resolve_large's dual loop where it stands, without a crash; a second child is staged on the device
+ * from the persistent A and pays the m crash pivots that install the recorded basis.  Arguments, outputs, statuses,
+ * refusals and stats_out[5] are lp_mip_bounded_solve's with one difference: there is no lp_mip_bounded_fits limit (the
+ * limits are lp_simplex_bounded_resolve_large's, device memory for the tableau and m <= 9960 for the dual selector's
+ * LDS, plus max_depth records of m + n ints in device memory; max_depth stays in [0, 1024]).  Refusals are checked
+ * before anything is launched and leave the context usable.  At a shape that also fits LDS every output equals
+ * lp_mip_bounded_solve's.  Dantzig's rule; lp_mip_bounded_solve itself is unchanged and still refuses larger shapes.
+ * Every pointer is required.                                                                                        */
+int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
 
 /* ---- Bounded variables: the dual solution and ranging at a basis ------------------------------------------------
  * The LP of lp_simplex_bounded analysed at basis (m, by position, every index in [0, n)) and at_upper (n, 0/1),

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <memory>
 
+#include "batched_problem.hpp"   // lp_mip_check_search, LP_MIP_BOUNDED_MAX_DEPTH
 #include "lp_internal.hpp"
 #include "simplex_problem.hpp"
 
@@ -449,20 +450,20 @@ __global__ __launch_bounds__(256) void k_build_tableau(const double* __restrict_
 }
 }  // namespace
 
-int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const double* b,
-                      const double* c, const int* basis_in, int maximize, int n_orig,
-                      lp_simplex_problem** problem_out) {
-    if (!ctx || !problem_out) return LP_BAD_ARG;
+}  // extern "C"
+
+// The problem record of an m x n tableau with every device buffer behind it (one arena from the context's pool), the
+// pinned state block and the events; nothing is uploaded.  c (n, may be null): the costs lp_simplex_download evaluates.
+int lp_simplex_alloc(lp_context* ctx, int m, int n, const double* c, int maximize, int n_orig,
+                     lp_simplex_problem** problem_out) {
     *problem_out = nullptr;
-    int rc = check_canonical(ctx, A, m, n, b, c, basis_in, n_orig);
-    if (rc) return rc;
     LP_HIP(ctx, hipSetDevice(ctx->device));
     // every error return below frees the half-built problem
     std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)> owner(new lp_simplex_problem(), lp_simplex_free);
     lp_simplex_problem* p = owner.get();
     p->ctx = ctx;
     p->n_orig = n_orig;
-    p->h_c.assign(c, c + n);
+    if (c) p->h_c.assign(c, c + n);
     SimplexDev& d = p->dev;
     d.m = m;
     d.n = n;
@@ -533,19 +534,24 @@ int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const doub
         LP_HIP(ctx, hipEventCreate(&p->ev0));
         LP_HIP(ctx, hipEventCreate(&p->ev1));
     }
-    hipStream_t s = ctx->stream;
-    LP_HIP(ctx, hipMemsetAsync(la.count, 0, sizeof(int), s));
+    LP_HIP(ctx, hipMemsetAsync(la.count, 0, sizeof(int), ctx->stream));
+    *problem_out = owner.release();
+    return LP_OPTIMAL;
+}
 
-    // ---- initial tableau [A | b] with the cost row c underneath, row-major: A goes up as the caller
-    // holds it (column-major) into the staging area and is transposed on the device
-    double* dA = p->dT0;
-    double* db = dA + (size_t)m * n;
-    double* dc = db + m;
+// The tail of an upload: the tableau [A | b] with the cost row c underneath from the column-major A, b and c staged
+// in p->dT0 (A first, then b, then c), the basis, and computeBFS; the post-crash snapshot goes back into p->dT0.
+// identity / zero_costs: lp_slack_identity's verdict on the staged problem.  Sets p->init_status.
+int lp_simplex_install(lp_simplex_problem* p, const int* basis_in, bool identity, bool zero_costs) {
+    lp_context* ctx = p->ctx;
+    const SimplexDev& d = p->dev;
+    const int m = d.m, n = d.n;
+    hipStream_t s = ctx->stream;
+    const double* dA = p->dT0;
+    const double* db = dA + (size_t)m * n;
+    const double* dc = db + m;
     std::vector<unsigned char> nonbasic((size_t)n, 1);
     for (int t = 0; t < m; ++t) nonbasic[(size_t)basis_in[t]] = 0;
-    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_build_tableau, dim3(lp_ceil_div(n, 32), lp_ceil_div(m, 32)), 256, 0, s, dA, db, dc, d.T, m, n,
                        d.ld);
     LP_HIP(ctx, hipMemcpyAsync(d.basis, basis_in, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, s));
@@ -558,21 +564,47 @@ int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const doub
     // computeBFS (SimplexSolover.h:423): nothing to do for the slack identity basis with
     // zero basic costs (Symmetrical::ToCanonical, Symmetrical.cpp:169-188); otherwise m
     // Gauss-Jordan pivots on the device.
-    bool identity, zero_costs;
-    lp_slack_identity(A, m, c, basis_in, &identity, &zero_costs);
     p->init_status = LP_OPTIMAL;
     if (identity && !zero_costs) {
         // unit-vector basis with costs (the artificial basis of a phase-I problem): the crash pivots
         // only touch the reduced-cost row — one pass instead of m rank-1 updates
-        rc = lp_simplex_price_out_identity(p);
+        const int rc = lp_simplex_price_out_identity(p);
         if (rc) return rc;
     } else if (!identity) {
-        rc = lp_simplex_crash(p);
+        const int rc = lp_simplex_crash(p);
         if (rc < 0) return rc;
         p->init_status = rc;
     }
     LP_HIP(ctx, hipMemcpyAsync(p->dT0, d.T, p->tableau_bytes, hipMemcpyDeviceToDevice, s));
     LP_HIP(ctx, hipStreamSynchronize(s));
+    return LP_OPTIMAL;
+}
+
+extern "C" {
+
+int lp_simplex_upload(lp_context* ctx, const double* A, int m, int n, const double* b,
+                      const double* c, const int* basis_in, int maximize, int n_orig,
+                      lp_simplex_problem** problem_out) {
+    if (!ctx || !problem_out) return LP_BAD_ARG;
+    *problem_out = nullptr;
+    int rc = check_canonical(ctx, A, m, n, b, c, basis_in, n_orig);
+    if (rc) return rc;
+    lp_simplex_problem* p = nullptr;
+    rc = lp_simplex_alloc(ctx, m, n, c, maximize, n_orig, &p);
+    if (rc) return rc;
+    ProblemOwner owner(p, lp_simplex_free);   // every error return below frees the half-built problem
+    // A goes up as the caller holds it (column-major) into the staging area and is transposed on the device
+    hipStream_t s = ctx->stream;
+    double* dA = p->dT0;
+    double* db = dA + (size_t)m * n;
+    double* dc = db + m;
+    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    bool identity, zero_costs;
+    lp_slack_identity(A, m, c, basis_in, &identity, &zero_costs);
+    rc = lp_simplex_install(p, basis_in, identity, zero_costs);
+    if (rc) return rc;
     *problem_out = owner.release();
     return LP_OPTIMAL;
 }
@@ -1085,6 +1117,242 @@ int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m,
                           at_upper_out, obj_out);
     std::memcpy(iters_out, it, sizeof(it));
     return rc;
+}
+
+// Depth-first branch-and-bound over the bounds on the HBM tableau (tests/ref/mip_bounded_ref.c is the definition; the
+// kernels are mip_bounded_large.hip's).  The host drives the search and keeps what is O(depth): j, v, z and the sides of
+// the records, the incumbent's objective, the counters.  A, b and c go up once; the tableau, the bound state, the node's
+// lo, the incumbent and the records' bases and flags stay on the device.  A node that ended LP_OPTIMAL costs one launch
+// of the node kernel and one sync; its first child continues on the live tableau with the bounded dual loop (no crash);
+// a second child is staged on the device from the persistent A and installed by lp_simplex_install.
+int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                               const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                               int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
+                               int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
+                               double* bound_out, int* found_out, int* stats_out) {
+    const char* who = "lp_mip_bounded_solve_large";
+    if (!ctx) return LP_BAD_ARG;
+    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !A || !b || !c || !lo || !hi || !basis_in ||
+        !at_upper_in || !integer)
+        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
+    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
+    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
+    int rc = check_bounds(ctx, who, lo, hi, n);
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j) {
+        if (at_upper_in[j] != 0 && at_upper_in[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
+        if (at_upper_in[j] && hi[j] == INFINITY)
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
+    }
+    for (int t = 0; t < m; ++t)
+        if (basis_in[t] < 0 || basis_in[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
+    rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_BOUNDED_MAX_DEPTH, max_nodes);
+    if (rc) return rc;
+    for (int j = 0; j < n_orig; ++j)
+        if (integer[j] && (lo[j] != std::floor(lo[j]) || (std::isfinite(hi[j]) && hi[j] != std::floor(hi[j]))))
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": an integer column has a fractional bound");
+
+    // ---- the problem record, the selectors' LDS (m <= 9960), and everything that lives for the whole call
+    struct Pinned {
+        MipLargeResult* ptr = nullptr;
+        ~Pinned() { (void)hipHostFree(ptr); }
+    } pinned;   // (declared first: freed after the device buffers, whose hipFree waits for the queued kernels)
+    lp_simplex_problem* p = nullptr;
+    rc = lp_simplex_alloc(ctx, m, n, nullptr, maximize, n, &p);
+    if (rc) return rc;
+    ProblemOwner owner(p, lp_simplex_free);
+    rc = lp_bounded_large_prepare(p, LP_PIVOT_DANTZIG);
+    if (rc) return rc;
+    rc = lp_bounded_dual_prepare(p);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const int D = max_depth;
+    lp_device_buffer buf;   // (freed before the problem on every return path)
+    BoundedLargeDev bd{};
+    MipLargeDev md{};
+    double *dA = nullptr, *db = nullptr, *dc = nullptr;
+    int* dmask = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
+        dA = cv.take<double>(sizeof(double) * (size_t)m * n);
+        db = cv.take<double>(sizeof(double) * (size_t)m);
+        dc = cv.take<double>(sizeof(double) * (size_t)n);
+        bd.U = cv.take<double>(sizeof(double) * (size_t)n);
+        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
+        md.lo = cv.take<double>(sizeof(double) * (size_t)n);
+        md.x = cv.take<double>(sizeof(double) * (size_t)n);
+        md.xinc = cv.take<double>(sizeof(double) * (size_t)n_orig);
+        bd.up = cv.take<int>(sizeof(int) * (size_t)n);
+        bd.flips = cv.take<int>(sizeof(int));
+        dmask = cv.take<int>(sizeof(int) * (size_t)n);
+        md.rec_basis = cv.take<int>(sizeof(int) * (size_t)D * m);
+        md.rec_up = cv.take<int>(sizeof(int) * (size_t)D * n);
+    }));
+    LP_HIP(ctx, hipHostMalloc(&pinned.ptr, sizeof(MipLargeResult)));
+    md.A = dA;
+    md.b = db;
+    md.c = dc;
+    md.integer = dmask;
+    md.result = pinned.ptr;
+    md.n_orig = n_orig;
+    md.max_depth = D;
+    md.int_tol = int_tol;
+    md.gap = gap;
+    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(dmask, integer, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+
+    int stats[5] = {0, 0, 0, 0, 0};
+    for (int j = 0; j < n_orig; ++j) x_out[j] = NAN;
+    *obj_out = NAN;
+    *bound_out = NAN;
+    *found_out = 0;
+
+    // step 2 of the reference on the node's bounds, basis and flags: its status, or a negative HIP error
+    std::vector<double> U((size_t)n);
+    auto install = [&](const double* lov, const double* hiv, const int* N, const int* up) -> int {
+        for (int j = 0; j < n; ++j)
+            if (hiv[j] < lov[j]) return LP_INFEASIBLE;
+        for (int j = 0; j < n; ++j) U[(size_t)j] = hiv[j] - lov[j];
+        LP_HIP(ctx, hipMemcpyAsync(md.lo, lov, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        LP_HIP(ctx, hipMemcpyAsync(bd.U, U.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        LP_HIP(ctx, hipMemcpyAsync(bd.up, up, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+        LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
+        lp_mip_large_stage(p, bd, md);
+        // the unit columns in order with zero costs: the m basic columns and their signs, O(m^2) on the host
+        bool identity = true, zero_costs = true;
+        for (int t = 0; t < m && identity; ++t) {
+            const int q = N[t];
+            if (c[q] != 0.0) zero_costs = false;
+            const double* col = A + (size_t)q * m;
+            for (int i = 0; i < m && identity; ++i)
+                if ((up[q] ? -col[i] : col[i]) != ((i == t) ? 1.0 : 0.0)) identity = false;
+        }
+        int r = lp_simplex_install(p, N, identity, zero_costs);
+        if (r) return r;
+        if (p->init_status != LP_OPTIMAL) return p->init_status;   // LP_SINGULAR
+        int flags = 0, iters = 0, flips = 0;
+        r = lp_bounded_large_classify(p, bd, eps, &flags);
+        if (r) return r;
+        if (!(flags & 1)) {
+            r = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips);
+            if (r < 0) return r;
+            stats[2] += iters - flips;
+            stats[3] += flips;
+        } else if (!(flags & 2)) {
+            r = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+            if (r < 0) return r;
+            stats[1] += iters;
+        } else {
+            r = LP_BAD_ARG;   // neither primal nor dual feasible
+        }
+        return r;
+    };
+    auto beats = [&](double z, double zs, double g) { return maximize ? (z > zs + g) : (z < zs - g); };
+
+    struct Record {
+        int j, first_down, second_taken;
+        double v, z;
+    };
+    std::vector<Record> rec((size_t)D);
+    std::vector<double> lov((size_t)n), hiv((size_t)n);
+    std::vector<int> N((size_t)m), up((size_t)n);
+
+    // ---- root
+    int st = install(lo, hi, basis_in, at_upper_in);
+    if (st < 0) return st;
+    stats[0] = 1;
+    int status = st;
+    if (st != LP_OPTIMAL) {
+        if (st == LP_UNBOUNDED || st == LP_ITER_LIMIT) *bound_out = maximize ? INFINITY : -INFINITY;
+    } else {
+        int L = 0, top = -1, found = 0, stop = LP_OPTIMAL, have_ab = 0;
+        double zstar = 0.0, zab = 0.0;
+        for (;;) {
+            bool backtrack = true;
+            if (st == LP_OPTIMAL) {
+                // steps 3 to 5 on the device; a node is counted before it starts, so the dive waits for the budget
+                const int dive = stats[0] < max_nodes;
+                lp_mip_large_node(p, bd, md, L, found, zstar, dive);
+                LP_HIP(ctx, hipStreamSynchronize(s));
+                LP_HIP(ctx, hipGetLastError());
+                const MipLargeResult r = *pinned.ptr;
+                if (r.what == LP_MIPL_INTEGRAL) {
+                    found = 1;
+                    zstar = r.z;
+                } else if (r.what == LP_MIPL_ABANDONED) {
+                    if (!have_ab || beats(r.z, zab, 0.0)) zab = r.z;
+                    have_ab = 1;
+                } else if (r.what == LP_MIPL_BRANCHED || r.what == LP_MIPL_NOT_BASIC) {
+                    rec[(size_t)L] = Record{r.j, (r.v - std::floor(r.v)) <= 0.5, 0, r.v, r.z};
+                    top = L;
+                    if (!dive) { stop = LP_ITER_LIMIT; break; }
+                    if (r.what == LP_MIPL_NOT_BASIC) { stop = LP_BAD_ARG; break; }
+                    ++L;
+                    ++stats[0];
+                    if (L > stats[4]) stats[4] = L;
+                    if (r.un_negative) {
+                        st = LP_INFEASIBLE;   // without a pivot
+                    } else {
+                        int iters = 0, flips = 0;
+                        st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+                        if (st < 0) return st;
+                        stats[1] += iters;
+                    }
+                    backtrack = false;
+                }
+            } else if (st != LP_INFEASIBLE) {
+                stop = st;
+                break;
+            }
+            if (!backtrack) continue;
+            while (top >= 0 && rec[(size_t)top].second_taken) --top;
+            if (top < 0) break;
+            rec[(size_t)top].second_taken = 1;
+            if (stats[0] >= max_nodes) { stop = LP_ITER_LIMIT; break; }
+            // ---- the second child of record `top`: the root's bounds overlaid in level order, the recorded start
+            L = top + 1;
+            std::memcpy(lov.data(), lo, sizeof(double) * (size_t)n);
+            std::memcpy(hiv.data(), hi, sizeof(double) * (size_t)n);
+            for (int l = 0; l < L; ++l) {
+                const Record& R = rec[(size_t)l];
+                const int down = R.second_taken ? !R.first_down : R.first_down;
+                if (down) hiv[(size_t)R.j] = std::floor(R.v);
+                else lov[(size_t)R.j] = std::ceil(R.v);
+            }
+            rc = lp_download(ctx, who, {{N.data(), md.rec_basis + (size_t)top * m, sizeof(int) * (size_t)m},
+                                        {up.data(), md.rec_up + (size_t)top * n, sizeof(int) * (size_t)n}});
+            if (rc) return rc;
+            ++stats[0];
+            if (L > stats[4]) stats[4] = L;
+            st = install(lov.data(), hiv.data(), N.data(), up.data());
+            if (st < 0) return st;
+        }
+        // ---- status and bound (step 8)
+        int have_open = have_ab;
+        double zo = zab;
+        for (int k = 0; k <= top; ++k)
+            if (!rec[(size_t)k].second_taken || (stop != LP_OPTIMAL && k == top)) {
+                if (!have_open || beats(rec[(size_t)k].z, zo, 0.0)) zo = rec[(size_t)k].z;
+                have_open = 1;
+            }
+        if (stop != LP_OPTIMAL) status = stop;
+        else if (found) status = (have_ab && beats(zab, zstar, gap)) ? LP_ITER_LIMIT : LP_OPTIMAL;
+        else status = have_ab ? LP_ITER_LIMIT : LP_INFEASIBLE;
+        if (found) {
+            rc = lp_download(ctx, who, {{x_out, md.xinc, sizeof(double) * (size_t)n_orig}});
+            if (rc) return rc;
+            *found_out = 1;
+            *obj_out = zstar;
+            *bound_out = (have_open && beats(zo, zstar, gap)) ? zo : zstar;
+        } else if (have_open) {
+            *bound_out = zo;
+        }
+    }
+    std::memcpy(stats_out, stats, sizeof(stats));
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
+    if (status == LP_SINGULAR) ctx->last_error = std::string(who) + ": the basis matrix is singular";
+    return status;
 }
 
 // Diagnostic: switches the look-ahead selector's per-phase cycle stamps on (cap_pivots > 0)

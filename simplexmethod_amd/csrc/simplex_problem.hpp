@@ -104,6 +104,14 @@ void lp_slack_identity(const double* A, int m, const double* c, const int* basis
 // Dynamic LDS above the default 48 KiB needs an opt-in.  The limit is an attribute of the kernel, not of a
 // problem, so every run sets it for the size it is about to launch with.
 hipError_t lp_lds_opt_in(const void* kernel, size_t bytes);
+// lp_simplex_upload in its two halves.  alloc: the problem record of an m x n tableau with every device buffer, the
+// pinned state block and the events; nothing is uploaded (c, n values or null: the costs lp_simplex_download
+// evaluates).  install: from the column-major A, then b, then c staged in p->dT0 the tableau, the basis and computeBFS
+// (identity / zero_costs: lp_slack_identity's verdict on what is staged); sets p->init_status and leaves the
+// post-crash snapshot in p->dT0.  lp_mip_bounded_solve_large stages every rebuilt node on the device and installs it.
+int lp_simplex_alloc(lp_context* ctx, int m, int n, const double* c, int maximize, int n_orig,
+                     lp_simplex_problem** problem_out);
+int lp_simplex_install(lp_simplex_problem* p, const int* basis_in, bool identity, bool zero_costs);
 
 // Each path's launch surface.  begin() queues the state-init launches of a run and returns how many it queued;
 // queue(batch) queues `batch` pivots and returns the launches queued (a negative value is a HIP error).
@@ -152,6 +160,38 @@ void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev
 int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags);
 int lp_bounded_dual_prepare(lp_simplex_problem* p);
 int lp_bounded_dual_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
+
+// mip_bounded_large.hip: the device side of lp_mip_bounded_solve_large's search (tests/ref/mip_bounded_ref.c steps 2
+// to 5).  What a solved node was, written by the node kernel into pinned host memory:
+enum { LP_MIPL_PRUNED = 0, LP_MIPL_INTEGRAL = 1, LP_MIPL_ABANDONED = 2, LP_MIPL_BRANCHED = 3, LP_MIPL_NOT_BASIC = 4 };
+struct MipLargeResult {
+    int what;          // LP_MIPL_*
+    int j;             // the branching column (BRANCHED, NOT_BASIC)
+    int un_negative;   // BRANCHED with the dive applied: the first child's new width U' is < 0
+    int pad;
+    double z;          // the node's objective
+    double v;          // x_j of the branching column
+};
+struct MipLargeDev {
+    const double* A;        // m x n column-major, b (m), c (n): uploaded once per call
+    const double* b;
+    const double* c;
+    const int* integer;     // n: the mask
+    double* lo;             // n: the node's lower bounds (a dive up moves one)
+    double* x;              // n: the node's vertex in the caller's variables
+    double* xinc;           // n_orig: the incumbent
+    int* rec_basis;         // max_depth x m: the basis recorded when a level branched
+    int* rec_up;            // max_depth x n: and the flags
+    MipLargeResult* result; // pinned host memory
+    int n_orig, max_depth;
+    double int_tol, gap;
+};
+// Stages [A' | b' | c'] of the node (lo = md.lo, U = bd.U, flags = bd.up) in p->dT0 for lp_simplex_install; queued.
+void lp_mip_large_stage(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md);
+// The node kernel on the LP_OPTIMAL tableau of a node at level L; found / zstar: the incumbent so far; dive: apply
+// the first child's bound change when the node branches.  Queued; md.result is valid after the next stream sync.
+void lp_mip_large_node(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, int L, int found,
+                       double zstar, int dive);
 
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS

@@ -355,23 +355,23 @@ public:
     IntegerResult boundedBranchAndBound(const std::vector<bool>& integer, const std::vector<double>& lo,
                                         const std::vector<double>& hi, const BoundedResult& from, int maxDepth = 64,
                                         int maxNodes = 100000) const {
-        const View p = view();
-        IntegerResult out = blankIntegerResult(from.status, p.no);
-        if (from.status != LP_OPTIMAL) return out;
-        if ((int)integer.size() != p.n)
-            throw std::invalid_argument("Solver::boundedBranchAndBound: mask size != cols(A)");
-        requireBounds("Solver::boundedBranchAndBound", p, lo, hi);
-        requireStart("Solver::boundedBranchAndBound", "start", p, from);
-        const std::vector<int> mask(integer.begin(), integer.end());
-        lp_context* ctx = lpgpu::context(_device);
-        int found = 0, stats[5] = {0, 0, 0, 0, 0};
-        out.status = checked(lp_mip_bounded_solve(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
-                                                  from.basis.data(), from.atUpper.data(), p.maximize, p.no,
-                                                  mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER,
-                                                  out.x.data(), &out.objective, &out.bound, &found, stats), ctx);
-        out.found = found != 0;
-        out.nodes = stats[0];
-        return out;
+        return boundedSearch("Solver::boundedBranchAndBound", integer, lo, hi, from, maxDepth, maxNodes, false);
+    }
+
+    // The same search at any shape boundedSimplexLarge runs (lp_mip_bounded_solve_large): the tableau stays in device
+    // memory from a node to its first child, a second child is rebuilt there; no lp_mip_bounded_fits limit.  The first
+    // form solves the relaxation by boundedSimplexLarge.  Result and exceptions as boundedBranchAndBound minus the fit,
+    // and equal to it where both run.
+    IntegerResult boundedBranchAndBoundLarge(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                             const std::vector<double>& hi, int maxDepth = 64,
+                                             int maxNodes = 100000) const {
+        return boundedBranchAndBoundLarge(integer, lo, hi, boundedSimplexLarge(lo, hi, false), maxDepth, maxNodes);
+    }
+
+    IntegerResult boundedBranchAndBoundLarge(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                             const std::vector<double>& hi, const BoundedResult& from,
+                                             int maxDepth = 64, int maxNodes = 100000) const {
+        return boundedSearch("Solver::boundedBranchAndBoundLarge", integer, lo, hi, from, maxDepth, maxNodes, true);
     }
 
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
@@ -739,6 +739,28 @@ private:
                                                        &out.objective, out.iterations, (int)*rule);
         if (throw_on_failure) lpgpu::throw_for_status(out.status, ctx);
         checked(out.status, ctx);
+        return out;
+    }
+
+    // boundedBranchAndBound, or with large boundedBranchAndBoundLarge, from a result's basis and flags
+    IntegerResult boundedSearch(const char* who, const std::vector<bool>& integer, const std::vector<double>& lo,
+                                const std::vector<double>& hi, const BoundedResult& from, int maxDepth, int maxNodes,
+                                bool large) const {
+        const View p = view();
+        IntegerResult out = blankIntegerResult(from.status, p.no);
+        if (from.status != LP_OPTIMAL) return out;
+        if ((int)integer.size() != p.n) throw std::invalid_argument(std::string(who) + ": mask size != cols(A)");
+        requireBounds(who, p, lo, hi);
+        requireStart(who, "start", p, from);
+        const std::vector<int> mask(integer.begin(), integer.end());
+        lp_context* ctx = lpgpu::context(_device);
+        int found = 0, stats[5] = {0, 0, 0, 0, 0};
+        const auto entry = large ? lp_mip_bounded_solve_large : lp_mip_bounded_solve;
+        out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                   from.atUpper.data(), p.maximize, p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth,
+                                   maxNodes, MAX_ITER, out.x.data(), &out.objective, &out.bound, &found, stats), ctx);
+        out.found = found != 0;
+        out.nodes = stats[0];
         return out;
     }
 
