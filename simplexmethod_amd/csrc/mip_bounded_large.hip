@@ -1,8 +1,8 @@
 // mip_bounded_large.hip — the device side of lp_mip_bounded_solve_large: depth-first branch-and-bound over variable
 // bounds on the HBM tableau of simplex_launch.hip, at any shape lp_simplex_bounded_resolve_large runs.
 //
-// The definition is tests/ref/mip_bounded_ref.c.  The host (simplex_driver.hip) drives the search; the tableau, the
-// bound state (BoundedLargeDev), the node's lower bounds, the incumbent and the record stack stay on the device
+// The definition is tests/ref/mip_bounded_ref.c.  The host (simplex_bounded_driver.hip) drives the search; the tableau,
+// the bound state (BoundedLargeDev), the node's lower bounds, the incumbent and the record stack stay on the device
 // (MipLargeDev).  Two pieces live here:
 //   staging   [A' | b' | c'] of a node from the A, b, c uploaded once per call: flagged columns and their costs
 //             negated, b' the reference's two fma chains per row (the shift over lo_j != 0, then the flagged columns

@@ -601,9 +601,9 @@ void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev
     hipLaunchKernelGGL(k_bounded_reset_weights, (n + 255) / 256, 256, 0, p->ctx->stream, bd.w, n);
 }
 
-int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule) {
-    const size_t shm = select_bounded_lds_bytes(p, rule);
-    const BoundedSelector select = bounded_selector(rule);
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual) {
+    const size_t shm = dual ? select_dual_bounded_lds_bytes(p) : select_bounded_lds_bytes(p, rule);
+    const BoundedSelector select = dual ? k_simplex_select_dual_bounded : bounded_selector(rule);
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(select, 1, 1024, shm, p->ctx->stream, p->dev, bd);
         lp_simplex_launch_update(p);
@@ -628,13 +628,4 @@ int lp_bounded_dual_prepare(lp_simplex_problem* p) {
         LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_large: m too large for the dual selector's LDS");
     LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_dual_bounded), shm));
     return LP_OPTIMAL;
-}
-
-int lp_bounded_dual_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch) {
-    const size_t shm = select_dual_bounded_lds_bytes(p);
-    for (int k = 0; k < batch; ++k) {
-        hipLaunchKernelGGL(k_simplex_select_dual_bounded, 1, 1024, shm, p->ctx->stream, p->dev, bd);
-        lp_simplex_launch_update(p);
-    }
-    return 2 * batch;
 }

@@ -1,13 +1,12 @@
 // simplex_driver.hip — the host side of the single-LP simplex: upload and download, the dispatch among the four
 // algorithms, the batch-and-poll loop three of them share, the epilogue that fills lp_simplex_stats, the two-phase
 // flow and the update micro-benchmarks.  The algorithm files (simplex_launch / _lookahead / _overlap / _resident.hip)
-// hold the kernels and the small launch surface declared in simplex_problem.hpp.
+// hold the kernels and the small launch surface declared in simplex_problem.hpp.  The bounded-variable entries on the
+// same tableau (simplex_bounded_driver.hip) use the upload, the polling loop and the two-phase pieces of this file.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <memory>
 
-#include "batched_problem.hpp"   // lp_mip_check_search, LP_MIP_BOUNDED_MAX_DEPTH
 #include "lp_internal.hpp"
 #include "simplex_problem.hpp"
 
@@ -23,12 +22,15 @@ int check_canonical(lp_context* ctx, const double* A, int m, int n, const double
     return LP_OPTIMAL;
 }
 
-void lp_slack_identity(const double* A, int m, const double* c, const int* basis, bool* identity, bool* zero_costs) {
+void lp_slack_identity(const double* A, int m, const double* c, const int* basis, bool* identity, bool* zero_costs,
+                       const int* at_upper) {
     bool id = true, zero = true;
     for (int t = 0; t < m && id; ++t) {
         if (c[basis[t]] != 0.0) zero = false;
+        const bool negated = at_upper && at_upper[basis[t]];
+        const double* col = A + (size_t)basis[t] * m;
         for (int i = 0; i < m && id; ++i)
-            if (A[(size_t)basis[t] * m + i] != ((i == t) ? 1.0 : 0.0)) id = false;
+            if ((negated ? -col[i] : col[i]) != ((i == t) ? 1.0 : 0.0)) id = false;
     }
     *identity = id;
     *zero_costs = zero;
@@ -92,187 +94,21 @@ int record_run(lp_simplex_problem* p, int algo, int launches, float ms, float up
     return status;
 }
 
-int run_launch(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
-    int rc = lp_launch_prepare(p);
+// A select + rank-1 update launch pair per pivot, polled in batches: prepare(p) opts the selector's LDS in, queue(p,
+// batch) queues the pairs.  The selector of p->pivot_rule, or the pair passed (lp_simplex_resolve_run: the dual one).
+int run_launch(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats,
+               int (*prepare)(lp_simplex_problem*) = lp_launch_prepare,
+               int (*queue)(lp_simplex_problem*, int) = lp_launch_queue) {
+    int rc = prepare(p);
     if (rc) return rc;
     LP_HIP(p->ctx, hipEventRecord(p->ev0, p->ctx->stream));
     int launches = lp_launch_begin(p, eps, max_iter);
-    rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return lp_launch_queue(p, batch); });
+    rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return queue(p, batch); });
     if (rc) return rc;
     float ms = 0.f;
     rc = close_window(p, &ms);
     if (rc) return rc;
     return record_run(p, LP_SIMPLEX_ALGO_LAUNCH, launches, ms, 0.f, 0, stats);
-}
-
-// The dual simplex of a re-solve: the dual selector + rank-1 update pair per pivot, polled as run_launch.
-int run_dual(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
-    int rc = lp_dual_prepare(p);
-    if (rc) return rc;
-    LP_HIP(p->ctx, hipEventRecord(p->ev0, p->ctx->stream));
-    int launches = lp_launch_begin(p, eps, max_iter);
-    rc = poll_batches(p, 16, 256, &launches, [&](int batch) { return lp_dual_queue(p, batch); });
-    if (rc) return rc;
-    float ms = 0.f;
-    rc = close_window(p, &ms);
-    if (rc) return rc;
-    return record_run(p, LP_SIMPLEX_ALGO_LAUNCH, launches, ms, 0.f, 0, stats);
-}
-
-// One phase of lp_simplex_bounded_large: the bounded selector + rank-1 update pair per iteration, polled as
-// run_launch.  *iters = the pivots plus flips of the phase, *flips = the flips since the start of the solve.
-// rule: the primal selector (under LP_PIVOT_DEVEX the weights are reset on the stream first).  dual: the bounded dual
-// selector in its place (lp_simplex_bounded_resolve_large; no rule reaches it), polled as run_dual.
-int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule, double eps, int max_iter, int* iters,
-                      int* flips, bool dual = false) {
-    lp_context* ctx = p->ctx;
-    int launches = lp_launch_begin(p, eps, max_iter);
-    if (!dual && rule == LP_PIVOT_DEVEX) {
-        lp_bounded_large_reset_weights(p, bd);
-        ++launches;
-    }
-    int rc = poll_batches(p, 16, 256, &launches, [&](int batch) {
-        return dual ? lp_bounded_dual_queue(p, bd, batch) : lp_bounded_large_queue(p, bd, batch, rule);
-    });
-    if (rc) return rc;
-    rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
-    if (rc) return rc;
-    LP_HIP(ctx, hipGetLastError());
-    *iters = p->h_state->iters;
-    p->last_status = p->h_state->status;
-    p->last_iters = p->h_state->iters;
-    p->last_algo = LP_SIMPLEX_ALGO_LAUNCH;
-    return p->h_state->status;
-}
-
-// ---- the two-phase flow shared by lp_simplex_two_phase_ex and lp_simplex_bounded_large
-
-using ProblemOwner = std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)>;
-
-// make_b_nonneg (:61-68) and createAuxiliaryProblem (:70-95) on [A | b]: rows with b_i < -eps change sign, an identity
-// of artificials with cost 1 follows A, and they are the starting basis.  A1 (m x (n+m), column-major) and c1 (n+m)
-// come zeroed; b1 may be b itself (lp_simplex_bounded_large's shifted right-hand side).
-void auxiliary_problem(const double* A, int m, int n, const double* b, double eps, double* A1, double* b1, double* c1,
-                       int* N) {
-    std::vector<char> flip((size_t)m);
-    for (int i = 0; i < m; ++i) {
-        flip[(size_t)i] = b[i] < -eps;
-        b1[i] = flip[(size_t)i] ? -b[i] : b[i];
-        A1[(size_t)(n + i) * m + i] = 1.0;
-        c1[n + i] = 1.0;
-        N[i] = n + i;
-    }
-    for (int j = 0; j < n; ++j) {   // (column by column: both matrices are column-major)
-        const double* src = A + (size_t)j * m;
-        double* dst = A1 + (size_t)j * m;
-        for (int i = 0; i < m; ++i) dst[i] = flip[(size_t)i] ? -src[i] : src[i];
-    }
-}
-
-// Phase I's verdict (:347-353): the artificials' values, summed in artificial-index order, against eps
-int phase1_verdict(lp_context* ctx, const std::string& prefix, const double* xa, int m, int n, double eps) {
-    double sum = 0.0;
-    for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
-    if (!(sum > eps)) return LP_OPTIMAL;
-    ctx->last_error = prefix + ": the problem has no feasible solution (phase I optimum > eps)";
-    return LP_INFEASIBLE;
-}
-
-// The positions of the phase-I basis N that still hold an artificial
-std::vector<int> artificial_positions(const int* N, int m, int n) {
-    std::vector<int> positions;
-    for (int pos = 0; pos < m; ++pos)
-        if (N[pos] >= n) positions.push_back(pos);
-    return positions;
-}
-
-// replaceArtificialColumns (:331-381): every artificial still basic (at level 0) leaves for the first non-basic
-// original column with |T[pos][cand]| > eps, chosen on the device; the positions are known from the phase-I basis, so
-// all pivots are queued behind one another.  No bound enters it.
-int drive_out_artificials(lp_simplex_problem* p, const std::string& prefix, const int* N, int m, int n, double eps,
-                          int* pivots) {
-    const std::vector<int> positions = artificial_positions(N, m, n);
-    if (positions.empty()) return LP_OPTIMAL;
-    const int rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, pivots);
-    if (rc == LP_SINGULAR)   // :372-380: linearly dependent constraints
-        p->ctx->last_error = prefix + ": an artificial variable cannot leave the basis (linearly dependent constraints)";
-    return rc;
-}
-
-// After a positive status: the basis reached, as the one-LP-per-workgroup kernels report it
-int download_basis(lp_simplex_problem* p, int* N) {
-    return lp_simplex_download(p, nullptr, N, nullptr, nullptr, nullptr, 0, nullptr);
-}
-
-// ---- the pieces lp_simplex_bounded_large and lp_simplex_bounded_resolve_large share
-
-// lo finite, hi not NaN
-int check_bounds(lp_context* ctx, const char* who, const double* lo, const double* hi, int n) {
-    for (int j = 0; j < n; ++j) {
-        if (!std::isfinite(lo[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": lo must be finite");
-        if (std::isnan(hi[j])) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": hi is NaN");
-    }
-    return LP_OPTIMAL;
-}
-
-// Any hi_j < lo_j: LP_INFEASIBLE with nothing launched
-int check_crossed(lp_context* ctx, const char* who, const double* lo, const double* hi, int n) {
-    for (int j = 0; j < n; ++j)
-        if (hi[j] < lo[j]) LP_FAIL(ctx, LP_INFEASIBLE, std::string(who) + ": some hi_j < lo_j");
-    return LP_OPTIMAL;
-}
-
-// The shift chain: b1_i <- fma(-A_ij, w_j, b1_i) over the columns with take(j), per row in ascending j (column by
-// column: A is column-major)
-template <class Take>
-void shift_rhs(const double* A, int m, int n, const double* w, Take take, double* b1) {
-    for (int j = 0; j < n; ++j) {
-        if (!take(j)) continue;
-        const double* src = A + (size_t)j * m;
-        for (int i = 0; i < m; ++i) b1[i] = std::fma(-src[i], w[j], b1[i]);
-    }
-}
-
-// The bound state beside the tableau of p: U (cols entries), the flags (up null: none set), the flip counter, the
-// dual selector's scratch and, under LP_PIVOT_DEVEX, the weights (run_bounded_phase sets them).  buf must be freed
-// before the problem (hipFree waits for the queued kernels).
-int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLargeDev& bd, const double* U,
-                        const int* up, int cols, int rule) {
-    lp_context* ctx = p->ctx;
-    hipStream_t s = ctx->stream;
-    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
-        bd.U = cv.take<double>(sizeof(double) * (size_t)cols);
-        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
-        bd.w = rule == LP_PIVOT_DEVEX ? cv.take<double>(sizeof(double) * (size_t)cols) : nullptr;
-        bd.up = cv.take<int>(sizeof(int) * (size_t)cols);
-        bd.flips = cv.take<int>(sizeof(int));
-    }));
-    LP_HIP(ctx, hipMemcpyAsync(bd.U, U, sizeof(double) * (size_t)cols, hipMemcpyHostToDevice, s));
-    if (up)
-        LP_HIP(ctx, hipMemcpyAsync(bd.up, up, sizeof(int) * (size_t)cols, hipMemcpyHostToDevice, s));
-    else
-        LP_HIP(ctx, hipMemsetAsync(bd.up, 0, sizeof(int) * (size_t)cols, s));
-    LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
-    return LP_OPTIMAL;
-}
-
-// Step 9 of bounded_ref.c: for LP_OPTIMAL un-complement and un-shift v (n values, overwritten), the objective in index
-// order, x_out (n_orig) and *obj_out; the basis and the flags for every status.
-void bounded_large_outputs(int rc, int m, int n, int n_orig, const double* c, const double* lo, const double* U,
-                           const int* up, const int* N, double* v, double* x_out, int* basis_out, int* at_upper_out,
-                           double* obj_out) {
-    if (rc == LP_OPTIMAL) {
-        for (int j = 0; j < n; ++j) {
-            const double w = up[j] ? U[j] - v[j] : v[j];
-            v[j] = lo[j] == 0.0 ? w : lo[j] + w;
-        }
-        double z = 0.0;
-        for (int j = 0; j < n; ++j) z += c[j] * v[j];
-        for (int j = 0; j < n_orig; ++j) x_out[j] = v[j];
-        *obj_out = z;
-    }
-    std::memcpy(basis_out, N, sizeof(int) * (size_t)m);
-    for (int j = 0; j < n; ++j) at_upper_out[j] = up[j];
 }
 
 int run_lookahead(lp_simplex_problem* p, double eps, int max_iter, lp_simplex_stats* stats) {
@@ -375,12 +211,68 @@ int bench_replay(lp_simplex_problem* p, int iters, float* ms_per_launch, Stage s
     return LP_OPTIMAL;
 }
 
-
 }  // namespace
 
 int lp_poll_pivots(lp_simplex_problem* p, const std::function<int(int)>& queue) {
     int launches = 0;
     return poll_batches(p, 16, 256, &launches, queue);
+}
+
+// ---- the two-phase flow shared by lp_simplex_two_phase_ex and lp_simplex_bounded_large (simplex_bounded_driver.hip)
+
+// make_b_nonneg (:61-68) and createAuxiliaryProblem (:70-95) on [A | b]: rows with b_i < -eps change sign, an identity
+// of artificials with cost 1 follows A, and they are the starting basis.  A1 (m x (n+m), column-major) and c1 (n+m)
+// come zeroed; b1 may be b itself (lp_simplex_bounded_large's shifted right-hand side).
+void auxiliary_problem(const double* A, int m, int n, const double* b, double eps, double* A1, double* b1, double* c1,
+                       int* N) {
+    std::vector<char> flip((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        flip[(size_t)i] = b[i] < -eps;
+        b1[i] = flip[(size_t)i] ? -b[i] : b[i];
+        A1[(size_t)(n + i) * m + i] = 1.0;
+        c1[n + i] = 1.0;
+        N[i] = n + i;
+    }
+    for (int j = 0; j < n; ++j) {   // (column by column: both matrices are column-major)
+        const double* src = A + (size_t)j * m;
+        double* dst = A1 + (size_t)j * m;
+        for (int i = 0; i < m; ++i) dst[i] = flip[(size_t)i] ? -src[i] : src[i];
+    }
+}
+
+// Phase I's verdict (:347-353): the artificials' values, summed in artificial-index order, against eps
+int phase1_verdict(lp_context* ctx, const std::string& prefix, const double* xa, int m, int n, double eps) {
+    double sum = 0.0;
+    for (int i = 0; i < m; ++i) sum += xa[(size_t)n + i];
+    if (!(sum > eps)) return LP_OPTIMAL;
+    ctx->last_error = prefix + ": the problem has no feasible solution (phase I optimum > eps)";
+    return LP_INFEASIBLE;
+}
+
+// The positions of the phase-I basis N that still hold an artificial
+static std::vector<int> artificial_positions(const int* N, int m, int n) {
+    std::vector<int> positions;
+    for (int pos = 0; pos < m; ++pos)
+        if (N[pos] >= n) positions.push_back(pos);
+    return positions;
+}
+
+// replaceArtificialColumns (:331-381): every artificial still basic (at level 0) leaves for the first non-basic
+// original column with |T[pos][cand]| > eps, chosen on the device; the positions are known from the phase-I basis, so
+// all pivots are queued behind one another.  No bound enters it.
+int drive_out_artificials(lp_simplex_problem* p, const std::string& prefix, const int* N, int m, int n, double eps,
+                          int* pivots) {
+    const std::vector<int> positions = artificial_positions(N, m, n);
+    if (positions.empty()) return LP_OPTIMAL;
+    const int rc = lp_simplex_driveout(p, positions.data(), (int)positions.size(), n, eps, pivots);
+    if (rc == LP_SINGULAR)   // :372-380: linearly dependent constraints
+        p->ctx->last_error = prefix + ": an artificial variable cannot leave the basis (linearly dependent constraints)";
+    return rc;
+}
+
+// After a positive status: the basis reached, as the one-LP-per-workgroup kernels report it
+int download_basis(lp_simplex_problem* p, int* N) {
+    return lp_simplex_download(p, nullptr, N, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
 extern "C" {
@@ -637,15 +529,12 @@ int lp_simplex_run(lp_simplex_problem* p, double eps, int max_iter, int algo,
         return p->init_status;
     }
     const bool asked_auto = algo == LP_SIMPLEX_ALGO_AUTO;
-    if (p->pivot_rule == LP_PIVOT_BLAND) {   // Bland's selector exists for the launch pair only
+    const bool bland = p->pivot_rule == LP_PIVOT_BLAND;
+    if (bland || p->pivot_rule == LP_PIVOT_DEVEX) {   // Bland's and the Devex selector exist for the launch pair only
         if (algo == LP_SIMPLEX_ALGO_AUTO) algo = LP_SIMPLEX_ALGO_LAUNCH;
         if (algo == LP_SIMPLEX_ALGO_RESIDENT || algo == LP_SIMPLEX_ALGO_LOOKAHEAD || algo == LP_SIMPLEX_ALGO_OVERLAP)
-            LP_FAIL(ctx, LP_BAD_ARG, "Bland's pivot rule runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
-    }
-    if (p->pivot_rule == LP_PIVOT_DEVEX) {   // so does the Devex selector
-        if (algo == LP_SIMPLEX_ALGO_AUTO) algo = LP_SIMPLEX_ALGO_LAUNCH;
-        if (algo == LP_SIMPLEX_ALGO_RESIDENT || algo == LP_SIMPLEX_ALGO_LOOKAHEAD || algo == LP_SIMPLEX_ALGO_OVERLAP)
-            LP_FAIL(ctx, LP_BAD_ARG, "Devex pricing runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
+            LP_FAIL(ctx, LP_BAD_ARG, bland ? "Bland's pivot rule runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only"
+                                           : "Devex pricing runs on LP_SIMPLEX_ALGO_LAUNCH (or AUTO) only");
     }
     if (algo == LP_SIMPLEX_ALGO_AUTO)
         algo = p->res.G >= 1 ? LP_SIMPLEX_ALGO_RESIDENT
@@ -709,7 +598,7 @@ int lp_simplex_resolve_run(lp_simplex_problem* p, double eps, int max_iter, int*
         return rc;
     }
     if (flags & 2) LP_FAIL(ctx, LP_BAD_ARG, "re-solve: the basis is neither primal nor dual feasible");
-    rc = run_dual(p, eps, max_iter, stats_out);
+    rc = run_launch(p, eps, max_iter, stats_out, lp_dual_prepare, lp_dual_queue);   // the dual selector's pair
     if (stats_out) {
         stats_out->algo_used = LP_SIMPLEX_ALGO_LAUNCH;
         stats_out->fell_back = 0;
@@ -919,440 +808,6 @@ int lp_simplex_two_phase_ex(lp_context* ctx, const double* A, int m, int n, cons
     if (basis_out) std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
     if (iters_out) std::memcpy(iters_out, it, sizeof(it));
     return rc;
-}
-
-// The bounded-variable two-phase simplex on the HBM tableau (tests/ref/bounded_ref.c is the definition): the flow of
-// lp_simplex_two_phase_ex with the selector of simplex_bounded_launch.hip in both phases.  The set-up arithmetic
-// (shift, sign changes, U, the phase-II costs of complemented columns, the outputs) runs here on the host in the
-// reference's order; every pivot and flip runs on the GPU.
-int lp_simplex_bounded_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                             const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
-                             double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out) {
-    return lp_simplex_bounded_large_ex(ctx, A, m, n, b, c, lo, hi, maximize, n_orig, eps, max_iter, x_out, basis_out,
-                                       at_upper_out, obj_out, iters_out, LP_PIVOT_DANTZIG);
-}
-
-// The same under a pivot rule (tests/ref/bounded_rules_ref.c): the rule picks the selector of both phases' loops; the
-// drive-out, the phase-II costs and the outputs do not depend on it.
-int lp_simplex_bounded_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                                const double* lo, const double* hi, int maximize, int n_orig, double eps, int max_iter,
-                                double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out,
-                                int pivot_rule) {
-    const char* who = "lp_simplex_bounded_large";
-    if (!ctx) return LP_BAD_ARG;
-    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown pivot rule");
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi)
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
-    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
-    int rc = check_bounds(ctx, who, lo, hi, n);
-    if (rc) return rc;
-    const int na = n + m;
-    int it[4] = {0, 0, 0, 0};
-    for (int t = 0; t < m; ++t) basis_out[t] = n + t;
-    for (int j = 0; j < n; ++j) at_upper_out[j] = 0;
-    std::memcpy(iters_out, it, sizeof(it));
-    rc = check_crossed(ctx, who, lo, hi, n);
-    if (rc) return rc;
-
-    // shift x = lo + x' (b' accumulated in ascending j, lo_j == 0 skipped), U = hi - lo, then make_b_nonneg and
-    // createAuxiliaryProblem on [A | b'] as lp_simplex_two_phase_ex
-    std::vector<double> A1((size_t)m * na, 0.0), b1((size_t)m), c1((size_t)na, 0.0), xa((size_t)na), U((size_t)na);
-    std::vector<int> N((size_t)m), up((size_t)na, 0);
-    for (int j = 0; j < n; ++j) U[(size_t)j] = hi[j] - lo[j];
-    for (int k = n; k < na; ++k) U[(size_t)k] = INFINITY;
-    for (int i = 0; i < m; ++i) b1[(size_t)i] = b[i];
-    shift_rhs(A, m, n, lo, [&](int j) { return lo[j] != 0.0; }, b1.data());
-    auxiliary_problem(A, m, n, b1.data(), eps, A1.data(), b1.data(), c1.data(), N.data());
-
-    lp_simplex_problem* p = nullptr;
-    rc = lp_simplex_upload(ctx, A1.data(), m, na, b1.data(), c1.data(), N.data(), 0, na, &p);
-    if (rc) return rc;
-    ProblemOwner owner(p, lp_simplex_free);
-    rc = lp_bounded_large_prepare(p, pivot_rule);
-    if (rc) return rc;
-    // the bound state beside the tableau (buf is freed before the problem on every return path)
-    hipStream_t s = ctx->stream;
-    lp_device_buffer buf;
-    BoundedLargeDev bd{};
-    rc = bounded_large_state(p, buf, bd, U.data(), nullptr, na, pivot_rule);
-    if (rc) return rc;
-    auto download_flags = [&]() { return lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}}); };
-
-    // ---- phase I: minimise the sum of the artificials
-    int iters = 0, flips1 = 0, flips = 0;
-    rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips1);
-    if (rc < 0) return rc;
-    it[0] = iters - flips1;
-    it[3] = flips1;
-    if (rc == LP_OPTIMAL) rc = lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr);
-    if (rc == LP_OPTIMAL) rc = phase1_verdict(ctx, who, xa.data(), m, n, eps);
-    if (rc == LP_OPTIMAL) rc = drive_out_artificials(p, who, N.data(), m, n, eps, &it[1]);
-    if (rc >= 0) {
-        const int rf = download_flags();
-        if (rf) rc = rf;
-    }
-    // ---- phase II on the phase-I tableau: a complemented column's cost changes sign
-    if (rc == LP_OPTIMAL) {
-        std::vector<double> c2((size_t)n);
-        for (int j = 0; j < n; ++j) c2[(size_t)j] = up[(size_t)j] ? -c[j] : c[j];
-        rc = lp_simplex_phase2_costs(p, c2.data(), n, maximize, n);   // (n_orig = n: the download below returns every v_j)
-    }
-    if (rc == LP_OPTIMAL) {
-        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips);
-        if (rc >= 0) {
-            it[2] = iters - (flips - flips1);
-            it[3] = flips;
-            int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
-                                      : download_basis(p, N.data());
-            if (rd == LP_OPTIMAL) rd = download_flags();
-            if (rd) rc = rd;
-        }
-    } else if (rc > 0) {
-        const int rd = download_basis(p, N.data());
-        if (rd) rc = rd;
-    }
-    (void)hipStreamSynchronize(s);
-    if (rc < 0) return rc;
-    bounded_large_outputs(rc, m, n, n_orig, c, lo, U.data(), up.data(), N.data(), xa.data(), x_out, basis_out,
-                          at_upper_out, obj_out);
-    std::memcpy(iters_out, it, sizeof(it));
-    return rc;
-}
-
-// The re-solve of a bounded LP from a basis and flags on the HBM tableau (tests/ref/bounded_resolve_ref.c is the
-// definition): the checks and the set-up arithmetic (shift, the flagged columns held complemented) run here on the
-// host in the reference's order, lp_simplex_upload installs the basis on the (m+1) x (n+1) tableau (no artificial
-// columns), a classification launch picks the loop, and every pivot and flip runs on the GPU: the primal loop is
-// lp_simplex_bounded_large's phase II, the dual loop the selector k_simplex_select_dual_bounded.
-int lp_simplex_bounded_resolve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                                     const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
-                                     int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out,
-                                     int* at_upper_out, double* obj_out, int* iters_out) {
-    return lp_simplex_bounded_resolve_large_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, eps,
-                                               max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
-                                               LP_PIVOT_DANTZIG);
-}
-
-// The same under a pivot rule (tests/ref/bounded_resolve_rules_ref.c): the rule governs the primal loop only; the
-// crash, the classification and the dual loop are the same under every rule.
-int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
-                                        const double* c, const double* lo, const double* hi, const int* basis_in,
-                                        const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
-                                        double* x_out, int* basis_out, int* at_upper_out, double* obj_out,
-                                        int* iters_out, int pivot_rule) {
-    const char* who = "lp_simplex_bounded_resolve_large";
-    if (!ctx) return LP_BAD_ARG;
-    if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown pivot rule");
-    if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo || !hi || !basis_in ||
-        !at_upper_in)
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
-    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
-    int rc = check_bounds(ctx, who, lo, hi, n);
-    if (rc) return rc;
-    for (int j = 0; j < n; ++j) {
-        if (at_upper_in[j] != 0 && at_upper_in[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
-        if (at_upper_in[j] && hi[j] == INFINITY)
-            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
-    }
-    for (int t = 0; t < m; ++t)
-        if (basis_in[t] < 0 || basis_in[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
-    int it[3] = {0, 0, 0};
-    std::vector<int> N(basis_in, basis_in + m), up(at_upper_in, at_upper_in + n);   // (the outputs may be the inputs)
-    std::memcpy(basis_out, N.data(), sizeof(int) * (size_t)m);
-    std::memcpy(at_upper_out, up.data(), sizeof(int) * (size_t)n);
-    std::memcpy(iters_out, it, sizeof(it));
-    rc = check_crossed(ctx, who, lo, hi, n);
-    if (rc) return rc;
-
-    // steps 2 and 3 of the reference: shift x = lo + x', U = hi - lo, the chain goes on over the flagged columns with
-    // U_j; those columns and their costs change sign
-    std::vector<double> A1(A, A + (size_t)m * n), b1(b, b + m), c1(c, c + n), xa((size_t)n), U((size_t)n);
-    for (int j = 0; j < n; ++j) U[(size_t)j] = hi[j] - lo[j];
-    shift_rhs(A, m, n, lo, [&](int j) { return lo[j] != 0.0; }, b1.data());
-    shift_rhs(A, m, n, U.data(), [&](int j) { return up[(size_t)j] != 0; }, b1.data());
-    for (int j = 0; j < n; ++j) {
-        if (!up[(size_t)j]) continue;
-        double* col = A1.data() + (size_t)j * m;
-        for (int i = 0; i < m; ++i) col[i] = -col[i];
-        c1[(size_t)j] = -c1[(size_t)j];
-    }
-    // step 4: the basis install (n_orig = n: the download below returns every column's value)
-    lp_simplex_problem* p = nullptr;
-    rc = lp_simplex_upload(ctx, A1.data(), m, n, b1.data(), c1.data(), N.data(), maximize, n, &p);
-    if (rc) return rc;
-    ProblemOwner owner(p, lp_simplex_free);
-    if (p->init_status != LP_OPTIMAL)   // LP_SINGULAR: the given basis and flags stay in the outputs
-        LP_FAIL(ctx, p->init_status, std::string(who) + ": the basis matrix is singular");
-    rc = lp_bounded_large_prepare(p, pivot_rule);
-    if (rc) return rc;
-    lp_device_buffer buf;   // (freed before the problem on every return path)
-    BoundedLargeDev bd{};
-    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n, pivot_rule);
-    if (rc) return rc;
-    // step 5: which loop
-    int flags = 0, iters = 0, flips = 0;
-    rc = lp_bounded_large_classify(p, bd, eps, &flags);
-    if (rc) return rc;
-    if (!(flags & 1)) {   // every basic variable within its bounds: the bounded primal loop
-        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips);
-        if (rc < 0) return rc;
-        it[1] = iters - flips;
-        it[2] = flips;
-    } else if (!(flags & 2)) {   // step 6: the bounded dual loop
-        rc = lp_bounded_dual_prepare(p);
-        if (rc) return rc;
-        rc = run_bounded_phase(p, bd, pivot_rule, eps, max_iter, &iters, &flips, true);
-        if (rc < 0) return rc;
-        it[0] = iters;
-    } else {
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
-    }
-    int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
-                              : download_basis(p, N.data());
-    if (rd == LP_OPTIMAL) rd = lp_download(ctx, who, {{up.data(), bd.up, sizeof(int) * (size_t)n}});
-    if (rd) return rd;
-    bounded_large_outputs(rc, m, n, n_orig, c, lo, U.data(), up.data(), N.data(), xa.data(), x_out, basis_out,
-                          at_upper_out, obj_out);
-    std::memcpy(iters_out, it, sizeof(it));
-    return rc;
-}
-
-// Depth-first branch-and-bound over the bounds on the HBM tableau (tests/ref/mip_bounded_ref.c is the definition; the
-// kernels are mip_bounded_large.hip's).  The host drives the search and keeps what is O(depth): j, v, z and the sides of
-// the records, the incumbent's objective, the counters.  A, b and c go up once; the tableau, the bound state, the node's
-// lo, the incumbent and the records' bases and flags stay on the device.  A node that ended LP_OPTIMAL costs one launch
-// of the node kernel and one sync; its first child continues on the live tableau with the bounded dual loop (no crash);
-// a second child is staged on the device from the persistent A and installed by lp_simplex_install.
-int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
-                               const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
-                               int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
-                               int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
-                               double* bound_out, int* found_out, int* stats_out) {
-    const char* who = "lp_mip_bounded_solve_large";
-    if (!ctx) return LP_BAD_ARG;
-    if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !A || !b || !c || !lo || !hi || !basis_in ||
-        !at_upper_in || !integer)
-        LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
-    if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": eps must be >= 0");
-    if (m <= 0 || n < m || n_orig <= 0 || n_orig > n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": bad dimensions");
-    int rc = check_bounds(ctx, who, lo, hi, n);
-    if (rc) return rc;
-    for (int j = 0; j < n; ++j) {
-        if (at_upper_in[j] != 0 && at_upper_in[j] != 1) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": at_upper must be 0 or 1");
-        if (at_upper_in[j] && hi[j] == INFINITY)
-            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": a column without an upper bound is flagged at_upper");
-    }
-    for (int t = 0; t < m; ++t)
-        if (basis_in[t] < 0 || basis_in[t] >= n) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": basis index out of range");
-    rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_BOUNDED_MAX_DEPTH, max_nodes);
-    if (rc) return rc;
-    for (int j = 0; j < n_orig; ++j)
-        if (integer[j] && (lo[j] != std::floor(lo[j]) || (std::isfinite(hi[j]) && hi[j] != std::floor(hi[j]))))
-            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": an integer column has a fractional bound");
-
-    // ---- the problem record, the selectors' LDS (m <= 9960), and everything that lives for the whole call
-    struct Pinned {
-        MipLargeResult* ptr = nullptr;
-        ~Pinned() { (void)hipHostFree(ptr); }
-    } pinned;   // (declared first: freed after the device buffers, whose hipFree waits for the queued kernels)
-    lp_simplex_problem* p = nullptr;
-    rc = lp_simplex_alloc(ctx, m, n, nullptr, maximize, n, &p);
-    if (rc) return rc;
-    ProblemOwner owner(p, lp_simplex_free);
-    rc = lp_bounded_large_prepare(p, LP_PIVOT_DANTZIG);
-    if (rc) return rc;
-    rc = lp_bounded_dual_prepare(p);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    const int D = max_depth;
-    lp_device_buffer buf;   // (freed before the problem on every return path)
-    BoundedLargeDev bd{};
-    MipLargeDev md{};
-    double *dA = nullptr, *db = nullptr, *dc = nullptr;
-    int* dmask = nullptr;
-    LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
-        dA = cv.take<double>(sizeof(double) * (size_t)m * n);
-        db = cv.take<double>(sizeof(double) * (size_t)m);
-        dc = cv.take<double>(sizeof(double) * (size_t)n);
-        bd.U = cv.take<double>(sizeof(double) * (size_t)n);
-        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
-        md.lo = cv.take<double>(sizeof(double) * (size_t)n);
-        md.x = cv.take<double>(sizeof(double) * (size_t)n);
-        md.xinc = cv.take<double>(sizeof(double) * (size_t)n_orig);
-        bd.up = cv.take<int>(sizeof(int) * (size_t)n);
-        bd.flips = cv.take<int>(sizeof(int));
-        dmask = cv.take<int>(sizeof(int) * (size_t)n);
-        md.rec_basis = cv.take<int>(sizeof(int) * (size_t)D * m);
-        md.rec_up = cv.take<int>(sizeof(int) * (size_t)D * n);
-    }));
-    LP_HIP(ctx, hipHostMalloc(&pinned.ptr, sizeof(MipLargeResult)));
-    md.A = dA;
-    md.b = db;
-    md.c = dc;
-    md.integer = dmask;
-    md.result = pinned.ptr;
-    md.n_orig = n_orig;
-    md.max_depth = D;
-    md.int_tol = int_tol;
-    md.gap = gap;
-    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(dmask, integer, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-
-    int stats[5] = {0, 0, 0, 0, 0};
-    for (int j = 0; j < n_orig; ++j) x_out[j] = NAN;
-    *obj_out = NAN;
-    *bound_out = NAN;
-    *found_out = 0;
-
-    // step 2 of the reference on the node's bounds, basis and flags: its status, or a negative HIP error
-    std::vector<double> U((size_t)n);
-    auto install = [&](const double* lov, const double* hiv, const int* N, const int* up) -> int {
-        for (int j = 0; j < n; ++j)
-            if (hiv[j] < lov[j]) return LP_INFEASIBLE;
-        for (int j = 0; j < n; ++j) U[(size_t)j] = hiv[j] - lov[j];
-        LP_HIP(ctx, hipMemcpyAsync(md.lo, lov, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-        LP_HIP(ctx, hipMemcpyAsync(bd.U, U.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-        LP_HIP(ctx, hipMemcpyAsync(bd.up, up, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-        LP_HIP(ctx, hipMemsetAsync(bd.flips, 0, sizeof(int), s));
-        lp_mip_large_stage(p, bd, md);
-        // the unit columns in order with zero costs: the m basic columns and their signs, O(m^2) on the host
-        bool identity = true, zero_costs = true;
-        for (int t = 0; t < m && identity; ++t) {
-            const int q = N[t];
-            if (c[q] != 0.0) zero_costs = false;
-            const double* col = A + (size_t)q * m;
-            for (int i = 0; i < m && identity; ++i)
-                if ((up[q] ? -col[i] : col[i]) != ((i == t) ? 1.0 : 0.0)) identity = false;
-        }
-        int r = lp_simplex_install(p, N, identity, zero_costs);
-        if (r) return r;
-        if (p->init_status != LP_OPTIMAL) return p->init_status;   // LP_SINGULAR
-        int flags = 0, iters = 0, flips = 0;
-        r = lp_bounded_large_classify(p, bd, eps, &flags);
-        if (r) return r;
-        if (!(flags & 1)) {
-            r = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips);
-            if (r < 0) return r;
-            stats[2] += iters - flips;
-            stats[3] += flips;
-        } else if (!(flags & 2)) {
-            r = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
-            if (r < 0) return r;
-            stats[1] += iters;
-        } else {
-            r = LP_BAD_ARG;   // neither primal nor dual feasible
-        }
-        return r;
-    };
-    auto beats = [&](double z, double zs, double g) { return maximize ? (z > zs + g) : (z < zs - g); };
-
-    struct Record {
-        int j, first_down, second_taken;
-        double v, z;
-    };
-    std::vector<Record> rec((size_t)D);
-    std::vector<double> lov((size_t)n), hiv((size_t)n);
-    std::vector<int> N((size_t)m), up((size_t)n);
-
-    // ---- root
-    int st = install(lo, hi, basis_in, at_upper_in);
-    if (st < 0) return st;
-    stats[0] = 1;
-    int status = st;
-    if (st != LP_OPTIMAL) {
-        if (st == LP_UNBOUNDED || st == LP_ITER_LIMIT) *bound_out = maximize ? INFINITY : -INFINITY;
-    } else {
-        int L = 0, top = -1, found = 0, stop = LP_OPTIMAL, have_ab = 0;
-        double zstar = 0.0, zab = 0.0;
-        for (;;) {
-            bool backtrack = true;
-            if (st == LP_OPTIMAL) {
-                // steps 3 to 5 on the device; a node is counted before it starts, so the dive waits for the budget
-                const int dive = stats[0] < max_nodes;
-                lp_mip_large_node(p, bd, md, L, found, zstar, dive);
-                LP_HIP(ctx, hipStreamSynchronize(s));
-                LP_HIP(ctx, hipGetLastError());
-                const MipLargeResult r = *pinned.ptr;
-                if (r.what == LP_MIPL_INTEGRAL) {
-                    found = 1;
-                    zstar = r.z;
-                } else if (r.what == LP_MIPL_ABANDONED) {
-                    if (!have_ab || beats(r.z, zab, 0.0)) zab = r.z;
-                    have_ab = 1;
-                } else if (r.what == LP_MIPL_BRANCHED || r.what == LP_MIPL_NOT_BASIC) {
-                    rec[(size_t)L] = Record{r.j, (r.v - std::floor(r.v)) <= 0.5, 0, r.v, r.z};
-                    top = L;
-                    if (!dive) { stop = LP_ITER_LIMIT; break; }
-                    if (r.what == LP_MIPL_NOT_BASIC) { stop = LP_BAD_ARG; break; }
-                    ++L;
-                    ++stats[0];
-                    if (L > stats[4]) stats[4] = L;
-                    if (r.un_negative) {
-                        st = LP_INFEASIBLE;   // without a pivot
-                    } else {
-                        int iters = 0, flips = 0;
-                        st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
-                        if (st < 0) return st;
-                        stats[1] += iters;
-                    }
-                    backtrack = false;
-                }
-            } else if (st != LP_INFEASIBLE) {
-                stop = st;
-                break;
-            }
-            if (!backtrack) continue;
-            while (top >= 0 && rec[(size_t)top].second_taken) --top;
-            if (top < 0) break;
-            rec[(size_t)top].second_taken = 1;
-            if (stats[0] >= max_nodes) { stop = LP_ITER_LIMIT; break; }
-            // ---- the second child of record `top`: the root's bounds overlaid in level order, the recorded start
-            L = top + 1;
-            std::memcpy(lov.data(), lo, sizeof(double) * (size_t)n);
-            std::memcpy(hiv.data(), hi, sizeof(double) * (size_t)n);
-            for (int l = 0; l < L; ++l) {
-                const Record& R = rec[(size_t)l];
-                const int down = R.second_taken ? !R.first_down : R.first_down;
-                if (down) hiv[(size_t)R.j] = std::floor(R.v);
-                else lov[(size_t)R.j] = std::ceil(R.v);
-            }
-            rc = lp_download(ctx, who, {{N.data(), md.rec_basis + (size_t)top * m, sizeof(int) * (size_t)m},
-                                        {up.data(), md.rec_up + (size_t)top * n, sizeof(int) * (size_t)n}});
-            if (rc) return rc;
-            ++stats[0];
-            if (L > stats[4]) stats[4] = L;
-            st = install(lov.data(), hiv.data(), N.data(), up.data());
-            if (st < 0) return st;
-        }
-        // ---- status and bound (step 8)
-        int have_open = have_ab;
-        double zo = zab;
-        for (int k = 0; k <= top; ++k)
-            if (!rec[(size_t)k].second_taken || (stop != LP_OPTIMAL && k == top)) {
-                if (!have_open || beats(rec[(size_t)k].z, zo, 0.0)) zo = rec[(size_t)k].z;
-                have_open = 1;
-            }
-        if (stop != LP_OPTIMAL) status = stop;
-        else if (found) status = (have_ab && beats(zab, zstar, gap)) ? LP_ITER_LIMIT : LP_OPTIMAL;
-        else status = have_ab ? LP_ITER_LIMIT : LP_INFEASIBLE;
-        if (found) {
-            rc = lp_download(ctx, who, {{x_out, md.xinc, sizeof(double) * (size_t)n_orig}});
-            if (rc) return rc;
-            *found_out = 1;
-            *obj_out = zstar;
-            *bound_out = (have_open && beats(zo, zstar, gap)) ? zo : zstar;
-        } else if (have_open) {
-            *bound_out = zo;
-        }
-    }
-    std::memcpy(stats_out, stats, sizeof(stats));
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
-    if (status == LP_SINGULAR) ctx->last_error = std::string(who) + ": the basis matrix is singular";
-    return status;
 }
 
 // Diagnostic: switches the look-ahead selector's per-phase cycle stamps on (cap_pivots > 0)

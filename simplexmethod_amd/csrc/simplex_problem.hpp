@@ -2,6 +2,7 @@
 #pragma once
 
 #include <functional>
+#include <memory>
 
 #include "lp_internal.hpp"
 
@@ -99,8 +100,9 @@ struct lp_simplex_problem {
 int check_canonical(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                     const int* basis, int n_orig);
 // Is basis (m positions) the unit-vector basis of the column-major A, and are its costs all zero?  (*zero_costs is
-// only meaningful when *identity holds.)
-void lp_slack_identity(const double* A, int m, const double* c, const int* basis, bool* identity, bool* zero_costs);
+// only meaningful when *identity holds.)  at_upper (per column, may be null): the columns flagged in it count negated.
+void lp_slack_identity(const double* A, int m, const double* c, const int* basis, bool* identity, bool* zero_costs,
+                       const int* at_upper = nullptr);
 // Dynamic LDS above the default 48 KiB needs an opt-in.  The limit is an attribute of the kernel, not of a
 // problem, so every run sets it for the size it is about to launch with.
 hipError_t lp_lds_opt_in(const void* kernel, size_t bytes);
@@ -112,6 +114,18 @@ hipError_t lp_lds_opt_in(const void* kernel, size_t bytes);
 int lp_simplex_alloc(lp_context* ctx, int m, int n, const double* c, int maximize, int n_orig,
                      lp_simplex_problem** problem_out);
 int lp_simplex_install(lp_simplex_problem* p, const int* basis_in, bool identity, bool zero_costs);
+// simplex_driver.hip: what lp_simplex_two_phase_ex shares with lp_simplex_bounded_large (simplex_bounded_driver.hip).
+using ProblemOwner = std::unique_ptr<lp_simplex_problem, void (*)(lp_simplex_problem*)>;   // frees on every return
+// The phase-I problem of [A | b]: rows with b_i < -eps negated, then an identity of artificials, which is the basis N.
+void auxiliary_problem(const double* A, int m, int n, const double* b, double eps, double* A1, double* b1, double* c1,
+                       int* N);
+// Phase I's verdict on its vertex xa: LP_INFEASIBLE under prefix's name when the artificials sum to more than eps.
+int phase1_verdict(lp_context* ctx, const std::string& prefix, const double* xa, int m, int n, double eps);
+// Pivots the artificials still in the phase-I basis N out (*pivots counts them); LP_SINGULAR when one cannot leave.
+int drive_out_artificials(lp_simplex_problem* p, const std::string& prefix, const int* N, int m, int n, double eps,
+                          int* pivots);
+// The basis of p alone, after a run that ended with a positive status.
+int download_basis(lp_simplex_problem* p, int* N);
 
 // Each path's launch surface.  begin() queues the state-init launches of a run and returns how many it queued;
 // queue(batch) queues `batch` pivots and returns the launches queued (a negative value is a HIP error).
@@ -142,8 +156,8 @@ int lp_dual_queue(lp_simplex_problem* p, int batch);
 // queues `batch` pivots and returns the launches queued); returns once the state word has left kRunning.
 int lp_poll_pivots(lp_simplex_problem* p, const std::function<int(int)>& queue);
 
-// simplex_bounded_launch.hip: the bounded-variable selector + the rank-1 update per iteration
-// (lp_simplex_bounded_large).  The bound state lives beside the tableau, one entry per tableau column.
+// simplex_bounded_launch.hip: the bounded-variable selector + the rank-1 update per iteration (the entries and their
+// host side are simplex_bounded_driver.hip's).  The bound state lives beside the tableau, one entry per tableau column.
 struct BoundedLargeDev {
     double* U;    // dev.n: hi - lo, +inf for the artificials
     int* up;      // dev.n: 1 = the column is held complemented
@@ -151,15 +165,15 @@ struct BoundedLargeDev {
     double* q;    // dev.ld: the quotients of the dual selector's ratio test
     double* w;    // dev.n: the Devex weights (LP_PIVOT_DEVEX), 1.0 when a primal loop starts
 };
-// rule: LP_PIVOT_DANTZIG (k_simplex_select_bounded), LP_PIVOT_BLAND or LP_PIVOT_DEVEX, checked by the caller
+// rule: LP_PIVOT_DANTZIG (k_simplex_select_bounded), LP_PIVOT_BLAND or LP_PIVOT_DEVEX, checked by the caller; dual:
+// the bounded dual selector in that selector's place (no rule reaches it; lp_bounded_dual_prepare first)
 int lp_bounded_large_prepare(lp_simplex_problem* p, int rule);   // that selector's LDS: checked, opted in
-int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule);
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual);
 void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd);   // queued, all 1.0
 // The re-solve (lp_simplex_bounded_resolve_large).  classify: *flags = bit 0 some basis position outside its bounds,
 // bit 1 dual infeasible (one host sync); the dual path then queues the bounded dual selector + rank-1 update.
 int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags);
 int lp_bounded_dual_prepare(lp_simplex_problem* p);
-int lp_bounded_dual_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch);
 
 // mip_bounded_large.hip: the device side of lp_mip_bounded_solve_large's search (tests/ref/mip_bounded_ref.c steps 2
 // to 5).  What a solved node was, written by the node kernel into pinned host memory:

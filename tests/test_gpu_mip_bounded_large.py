@@ -181,6 +181,12 @@ def test_refusals(ctx):
               (A, b, c, lo, hi, basis, up, mask, maximize, 0), (A, b, c, lo, hi, basis, up, mask, maximize, n + 1)):
         with pytest.raises(capi.LPError):
             ctx.mip_bounded_solve_large(*a)
+    # crossed bounds at the root are no refusal: LP_INFEASIBLE after one node, nothing found, as the reference
+    crossed = hi.copy()
+    crossed[j] = lo[j] - 1.0
+    rc = Q.ref(("crossed-160",), A, b, c, lo, crossed, basis, up, mask, maximize, no)
+    assert rc["status"] == INFEASIBLE and rc["stats"][0] == 1 and not rc["found"]
+    _same(ctx.mip_bounded_solve_large(A, b, c, lo, crossed, basis, up, mask, maximize, no), rc)
     # NULL pointers and a NULL context through the raw symbol: LP_BAD_ARG, nothing launched
     fn = ctx.lib.lp_mip_bounded_solve_large
     d = np.zeros(16).ctypes.data_as(C.POINTER(C.c_double))
