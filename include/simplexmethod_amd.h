@@ -657,7 +657,8 @@ int lp_simplex_bounded_resolve_batched(lp_context* ctx, int batch, const double*
  *     complement are Dantzig's; a flip leaves the weights alone; before a pivot w_s = max(w_s, (T_rs/u_r)^2 w_e) and
  *     w_se = max(w_e/u_r^2, 1), as in lp_simplex_two_phase_batched_ex.
  * In the re-solve the rule governs the primal branch only: the crash, the classification and the dual branch are
- * unchanged, and their result under any rule is lp_simplex_bounded_resolve's bit for bit.  With lo = 0, hi = +inf and
+ * unchanged, and their result under any rule is lp_simplex_bounded_resolve's bit for bit (the dual branch has a pricing
+ * rule of its own: the _dual_ex entries and LP_DUAL_* below).  With lo = 0, hi = +inf and
  * no flag every output under a rule equals lp_simplex_two_phase_batched_ex's under that rule bit for bit.
  * Shapes: lp_simplex_bounded_rule_fits; a shape that fits plain but not with Devex's weights is LP_BAD_ARG under
  * LP_PIVOT_DEVEX, and nothing is launched.  The branch-and-bound over bounds stays with Dantzig's rule.            */
@@ -683,6 +684,34 @@ int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m,
  * LP_PIVOT_BLAND; under LP_PIVOT_DEVEX the LDS carve with n more doubles, the weights, must still fit 160 KiB.  0
  * otherwise, and for an unknown rule.                                                                                */
 int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule);
+
+/* The pricing rule of the bounded DUAL loop, the loop every warm re-solve from a dual feasible basis ends in (DESIGN.md
+ * §4.5k3; the definition is tests/ref/bounded_resolve_dual_rules_ref.c, which every output equals bit for bit).  The
+ * three entries take the arguments of their _ex entry with dual_rule appended.  pivot_rule governs the primal branch
+ * only and dual_rule the dual branch only; a re-solve runs one of the two.
+ *   - LP_DUAL_DANTZIG: the most violated position leaves (the EPS-hysteresis chain over v_t).  The entry launches
+ *     exactly what its _ex entry launches and equals it bit for bit.
+ *   - LP_DUAL_DEVEX: one fp64 reference weight per basis position, all exactly 1.0 when the dual loop starts.  With
+ *     v_t the violation (xB_t below -eps, else U - xB_t below -eps for a finite U), the violated position of largest
+ *     (v_t * v_t) / w_t leaves; exact ties go to the smallest position, a NaN score never wins, and there is no eps
+ *     hysteresis.  The complement of a position violated above, the entering ratio test and the infeasible verdict
+ *     are unchanged.  Before the pivot on (r, e), with a = T[r][e] after the complement: w_i = max(w_i, (T[i][e]/a)^2 w_r)
+ *     for i != r, then w_r = max(w_r / a^2, 1).  Status and objective are those of LP_DUAL_DANTZIG up to rounding
+ *     wherever that one ends optimal; the optimal basis and the pivot count may differ.
+ * Any other dual_rule is LP_BAD_ARG before anything else is looked at, and no output is written.
+ * Shapes: the two LDS entries need lp_simplex_bounded_dual_rule_fits (else LP_BAD_ARG, nothing launched).  The _large
+ * entry keeps its m weights in device memory and has no such limit; its Devex dual selector keeps sixteen wave results
+ * more in LDS than the plain one: m <= 9957 in the dual branch under LP_DUAL_DEVEX.
+ * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large) and the parametric paths keep
+ * Dantzig's dual rule, and the unbounded lp_simplex_resolve family is not touched.                                    */
+enum { LP_DUAL_DANTZIG = 0, LP_DUAL_DEVEX = 1 };
+int lp_simplex_bounded_resolve_dual_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule);
+int lp_simplex_bounded_resolve_batched_dual_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule);
+int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule);
+/* Host call, no context.  A re-solve runs its primal or its dual loop, never both, so the two weight arrays share one
+ * region: 1 when the LDS carve of lp_simplex_bounded_fits plus max(pivot_rule == LP_PIVOT_DEVEX ? n : 0,
+ * dual_rule == LP_DUAL_DEVEX ? m : 0) doubles fits 160 KiB; 0 otherwise, and for an unknown rule of either kind.      */
+int lp_simplex_bounded_dual_rule_fits(int m, int n, int pivot_rule, int dual_rule);
 
 /* ---- Bounded variables: branch-and-bound over the bounds ------------------------------------------------------
  * The LP of lp_simplex_bounded with the columns j < n_orig of integer[j] = 1 integral (one mask of n entries for the

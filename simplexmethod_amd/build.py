@@ -154,6 +154,7 @@ REFS = {
     "bounded_parametric": ("bounded_resolve", "bounded"),
     "bounded_rules": ("bounded",),
     "bounded_resolve_rules": ("bounded_resolve", "bounded", "bounded_rules"),
+    "bounded_resolve_dual_rules": ("bounded_resolve_rules", "bounded_resolve", "bounded", "bounded_rules"),
 }
 
 
@@ -194,6 +195,7 @@ build_bounded_certificate_ref = functools.partial(build_ref, "bounded_certificat
 build_bounded_parametric_ref = functools.partial(build_ref, "bounded_parametric")
 build_bounded_rules_ref = functools.partial(build_ref, "bounded_rules")
 build_bounded_resolve_rules_ref = functools.partial(build_ref, "bounded_resolve_rules")
+build_bounded_resolve_dual_rules_ref = functools.partial(build_ref, "bounded_resolve_dual_rules")
 
 
 def build_all(force=False, verbose=False):

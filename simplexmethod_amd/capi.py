@@ -18,6 +18,7 @@ SUBSET_FEASIBLE, SUBSET_INFEASIBLE, SUBSET_SINGULAR = range(3)
 SIMPLEX_AUTO, SIMPLEX_LAUNCH, SIMPLEX_LOOKAHEAD, SIMPLEX_RESIDENT, SIMPLEX_OVERLAP = 0, 1, 2, 3, 4
 ENUM_AUTO, ENUM_DIRECT, ENUM_PREFIX = 0, 1, 2
 PIVOT_DANTZIG, PIVOT_BLAND, PIVOT_DEVEX = 0, 1, 2
+DUAL_DANTZIG, DUAL_DEVEX = 0, 1
 CERT_NONE, CERT_FARKAS, CERT_RAY = 0, 1, 2
 U64_MAX = (1 << 64) - 1
 EPS = 1e-9        # Solver::EPS, SimplexSolover.h:13
@@ -165,6 +166,16 @@ SIGNATURES = {
                                                         _ip, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
                                                         _ip, _ip, C.c_int]),
     "lp_simplex_bounded_rule_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve_dual_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                     C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int,
+                                                     C.c_int]),
+    "lp_simplex_bounded_resolve_batched_dual_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                             _ip, _ip, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip,
+                                                             _ip, _dp, _ip, _ip, C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve_large_dual_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                           C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
+                                                           _ip, C.c_int, C.c_int]),
+    "lp_simplex_bounded_dual_rule_fits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "lp_simplex_bounded_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                               C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
     "lp_simplex_bounded_resolve_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
@@ -295,6 +306,17 @@ def pivot_rule_id(rule):
         names = {"dantzig": PIVOT_DANTZIG, "bland": PIVOT_BLAND, "devex": PIVOT_DEVEX}
         if rule.lower() not in names:
             raise ValueError(f"unknown pivot rule {rule!r} (expected 'dantzig', 'bland' or 'devex')")
+        return names[rule.lower()]
+    return int(rule)
+
+
+def dual_rule_id(rule):
+    """"dantzig" | "devex" | DUAL_DANTZIG | DUAL_DEVEX -> the LP_DUAL_* value (other integers pass through: the
+    library refuses them with LP_BAD_ARG)."""
+    if isinstance(rule, str):
+        names = {"dantzig": DUAL_DANTZIG, "devex": DUAL_DEVEX}
+        if rule.lower() not in names:
+            raise ValueError(f"unknown dual rule {rule!r} (expected 'dantzig' or 'devex')")
         return names[rule.lower()]
     return int(rule)
 
@@ -736,8 +758,14 @@ class Context:
         return bool(self.lib.lp_mip_fits(m, n, max_depth))
 
     # ---- bounded-variable simplex -------------------------------------------------------------
-    def _bounded_call(self, name, pivot_rule, *args):
-        """The entry `name` of the bounded family, or with a pivot_rule its _ex form with the rule appended."""
+    dual_rule_id = staticmethod(dual_rule_id)
+
+    def _bounded_call(self, name, pivot_rule, *args, dual_rule=None):
+        """The entry `name` of the bounded family, or with a pivot_rule its _ex form with the rule appended, or (the
+        re-solves) with a dual_rule its _dual_ex form with both appended (no pivot_rule: Dantzig's)."""
+        if dual_rule is not None:
+            rule = PIVOT_DANTZIG if pivot_rule is None else pivot_rule_id(pivot_rule)
+            return self.check(getattr(self.lib, name + "_dual_ex")(*args, rule, dual_rule_id(dual_rule)))
         if pivot_rule is None:
             return self.check(getattr(self.lib, name)(*args))
         return self.check(getattr(self.lib, name + "_ex")(*args, pivot_rule_id(pivot_rule)))
@@ -801,11 +829,13 @@ class Context:
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                              max_iter=MAX_ITER, pivot_rule=None):
+                              max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
         """lp_simplex_bounded_resolve_large: the re-solve of bounded_resolve() on the tableau in HBM, at any shape
         bounded_large() runs (no bounded_fits limit).  pivot_rule as in bounded_resolve() (None: the entry without a
         rule; else lp_simplex_bounded_resolve_large_ex): it governs the primal loop only.  Returns the dict of
-        bounded_resolve(), equal to it under the same rule where both run; refusals as there."""
+        bounded_resolve(), equal to it under the same rules where both run; refusals as there.  dual_rule as in
+        bounded_resolve() (lp_simplex_bounded_resolve_large_dual_ex; the m weights live in device memory, no
+        bounded_dual_rule_fits limit)."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
@@ -816,7 +846,7 @@ class Context:
         it = np.zeros(3, dtype=np.int32)
         rc = self._bounded_call("lp_simplex_bounded_resolve_large", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c),
                                 _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps),
-                                int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it))
+                                int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule)
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_fits(self, m, n):
@@ -828,14 +858,24 @@ class Context:
         and under PIVOT_DEVEX with n more doubles, the weights.  False for an unknown rule."""
         return bool(self.lib.lp_simplex_bounded_rule_fits(m, n, pivot_rule_id(pivot_rule)))
 
+    def bounded_dual_rule_fits(self, m, n, pivot_rule, dual_rule):
+        """lp_simplex_bounded_dual_rule_fits: True if an m x n bounded re-solve fits one CU's LDS under both rules:
+        bounded_fits plus the larger of n doubles (PIVOT_DEVEX) and m doubles (DUAL_DEVEX), one region for the loop
+        that runs.  False for an unknown rule of either kind."""
+        return bool(self.lib.lp_simplex_bounded_dual_rule_fits(m, n, pivot_rule_id(pivot_rule), dual_rule_id(dual_rule)))
+
     def bounded_resolve(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                        max_iter=MAX_ITER, pivot_rule=None):
+                        max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
         """lp_simplex_bounded_resolve: the LP of bounded() re-solved from `basis` (m) and `at_upper` (n, 0/1), normally
         an earlier result's, after a change of lo, hi, b or c: the bounded primal loop if the basis is primal feasible,
         the bounded dual simplex if it is only dual feasible.  dict as bounded() with iters = (dual pivots, primal
         pivots, bound flips).  A basis that is neither, a bad index or flag, a bad bound or a shape beyond bounded_fits
         raises LPError with code BAD_ARG.  pivot_rule as in bounded() (lp_simplex_bounded_resolve_ex): it governs the
-        primal loop only; the dual simplex is the same under every rule."""
+        primal loop only; the dual simplex is the same under every pivot rule.  dual_rule ("dantzig", "devex" or a
+        DUAL_* value; None: the call made without it) goes through lp_simplex_bounded_resolve_dual_ex and governs the
+        leaving choice of the dual simplex only: under "devex" status and objective are Dantzig's up to rounding, the
+        optimal basis and the pivot count may differ.  An unknown dual rule or a shape beyond bounded_dual_rule_fits
+        raises LPError with code BAD_ARG."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
@@ -846,15 +886,15 @@ class Context:
         it = np.zeros(3, dtype=np.int32)
         rc = self._bounded_call("lp_simplex_bounded_resolve", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c), _d(lo),
                                 _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter), _d(x),
-                                _i(bo), _i(up), _d(obj), _i(it))
+                                _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule)
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                                max_iter=MAX_ITER, pivot_rule=None):
+                                max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
         """lp_simplex_bounded_resolve_batched: arrays as bounded_batched(), basis (batch, m), at_upper (batch, n).
         dict as bounded_batched() with iters (batch, 3); per LP exactly bounded_resolve(), except that a basis that
         is no valid start is that LP's status BAD_ARG.  pivot_rule as in bounded_resolve()
-        (lp_simplex_bounded_resolve_batched_ex)."""
+        (lp_simplex_bounded_resolve_batched_ex), dual_rule as there (lp_simplex_bounded_resolve_batched_dual_ex)."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
         batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
         basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
@@ -867,7 +907,7 @@ class Context:
         st = np.zeros(batch, dtype=np.int32)
         self._bounded_call("lp_simplex_bounded_resolve_batched", pivot_rule, self.h, batch, _d(Af), m, n, _d(b), _d(c),
                            _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter),
-                           _d(x), _i(bo), _i(up), _d(obj), _i(it), _i(st))
+                           _d(x), _i(bo), _i(up), _d(obj), _i(it), _i(st), dual_rule=dual_rule)
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     # ---- the dual solution and ranging of a bounded-variable LP at a basis ----------------------

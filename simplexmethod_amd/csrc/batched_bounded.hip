@@ -69,6 +69,14 @@ bool lp_bounded_fits_shape(int m, int n) {
 
 size_t lp_bounded_devex_lds_bytes(int m, int n) { return bounded_carve(m, n, true).bytes; }
 
+// (the region's size alone decides the bytes: n doubles as `weights` or as `dual_weights` carve alike)
+size_t lp_bounded_weights_lds_bytes(int m, int n, int weights) { return bounded_carve(m, n, false, weights).bytes; }
+
+bool lp_bounded_dual_rule_fits_shape(int m, int n, int pivot_rule, int dual_rule) {
+    if (!lp_pivot_rule_known(pivot_rule) || !lp_dual_rule_known(dual_rule) || !lp_bounded_fits_shape(m, n)) return false;
+    return lp_bounded_weights_lds_bytes(m, n, lp_bounded_resolve_weights(m, n, pivot_rule, dual_rule)) <= 160 * 1024;
+}
+
 bool lp_bounded_rule_fits_shape(int m, int n, int pivot_rule) {
     return lp_pivot_rule_known(pivot_rule) && lp_bounded_fits_shape(m, n) &&
            (pivot_rule != LP_PIVOT_DEVEX || lp_bounded_devex_lds_bytes(m, n) <= 160 * 1024);

@@ -9,11 +9,36 @@
 // sign already applied: q = d / a (max) or -d / a (min) over the slots holding a variable < n with a < -eps, in
 // variable order.  pub[0] entering slot, pub[1] leaving position, pub[2] complement first: every wave takes the same
 // branch.
+//
+// Under the macro LP_BOUNDED_DUAL_DEVEX (the _ddevex kernels of batched_bounded_resolve.hip, with the carve's dwts, one
+// double per basis position; tests/ref/bounded_resolve_dual_rules_ref.c states the rule) the loop sets the weights to
+// 1.0 when it starts, and the leaving position is the violated one of largest (v * v) / w, exact ties to the smallest
+// position, without eps.  Between the complement and the pivot every thread updates the weights from column se:
+// w_i = cand if cand = (g * g) * w_r > w_i with g = T[i][se] / a, a = T[r][se] as the complement left it, then
+// w_r = max(w_r / (a * a), 1.0) by the thread that owns r.  a and the old w_r are read ahead of a barrier of their
+// own, so no thread reads w_r after its owner has rewritten it.  Without the macro the code is what it was.
     auto bounded_dual = [&](int& iters) -> int {
         if (d.max_iter <= 0) return LP_ITER_LIMIT;
+#ifdef LP_BOUNDED_DUAL_DEVEX
+        for (int t = tid; t < m; t += NT) dwts[t] = 1.0;
+        __syncthreads();
+#endif
         for (;;) {
             if (wave == 0) {
                 double best;
+#ifdef LP_BOUNDED_DUAL_DEVEX
+                const int r0 = wave_argmax_keyed(m, [&](int t, double& v, int& k, bool& ok) {
+                    const double xb = T[(size_t)t * pitch + n], u = U[basis[t]];
+                    double viol = xb;
+                    ok = true;
+                    if (!(xb < -eps)) {
+                        viol = u - xb;
+                        ok = u < INFINITY && viol < -eps;
+                    }
+                    v = (viol * viol) / dwts[t];
+                    k = t;
+                });
+#else
                 const int r0 = wave_scan_keyed<false>(m, eps, best, [&](int t, double& v, int& k, bool& ok) {
                     const double xb = T[(size_t)t * pitch + n], u = U[basis[t]];
                     k = t;
@@ -25,6 +50,7 @@
                         ok = u < INFINITY && v < -eps;
                     }
                 });
+#endif
                 int se0 = -1, comp = 0;
                 if (r0 >= 0) {
                     const double* rrow = T + (size_t)r0 * pitch;
@@ -56,6 +82,21 @@
                 __syncthreads();
             }
             if (se < 0) return LP_INFEASIBLE;
+#ifdef LP_BOUNDED_DUAL_DEVEX
+            {
+                const double a = T[(size_t)r * pitch + se], wr = dwts[r];
+                __syncthreads();
+                for (int i = tid; i < m; i += NT) {
+                    if (i == r) {
+                        dwts[i] = fmax(wr / (a * a), 1.0);
+                    } else {
+                        const double g = T[(size_t)i * pitch + se] / a;
+                        const double cand = (g * g) * wr;
+                        if (cand > dwts[i]) dwts[i] = cand;
+                    }
+                }
+            }
+#endif
             pivot(r, se);
             ++iters;
             if (iters >= d.max_iter) return LP_ITER_LIMIT;

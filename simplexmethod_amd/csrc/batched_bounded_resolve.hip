@@ -16,7 +16,8 @@
 // flags are read from HBM.  After the crash the lcol buffer holds the row permutation until the rows are in position
 // order.  There is no host fallback: larger shapes get LP_BAD_ARG.
 // The kernel's text is batched_bounded_resolve_body.hpp, shared with its Bland and Devex forms below, in which the
-// rule governs the primal branch only.
+// rule governs the primal branch only, and with the _ddevex forms, in which the dual branch prices by Devex
+// (LP_DUAL_DEVEX) under each of the three primal rules.
 #include <cfloat>
 #include <climits>
 
@@ -51,10 +52,53 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_resolve_devex(BatchedBou
 #undef LP_BOUNDED_DEVEX
 }
 
+// The three kernels above with Devex pricing in the dual branch (LP_DUAL_DEVEX, batched_bounded_dual_loop.hpp): one
+// weight per basis position behind the carve, m doubles, in the region of the primal Devex weights where the kernel
+// has both (n >= m doubles then: lp_bounded_resolve_weights).
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_ddevex(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DUAL_DEVEX
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_DEVEX
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_bland_ddevex(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_BLAND
+#define LP_BOUNDED_DUAL_DEVEX
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_DEVEX
+#undef LP_BOUNDED_BLAND
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_devex_ddevex(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DEVEX
+#define LP_BOUNDED_DUAL_DEVEX
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_DEVEX
+#undef LP_BOUNDED_DEVEX
+}
+
 }  // namespace
 
-int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule) {
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule, int dual_rule) {
     if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: unknown pivot rule");
+    if (!lp_dual_rule_known(dual_rule)) LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: unknown dual rule");
+    if (dual_rule == LP_DUAL_DEVEX) {
+        if (!lp_bounded_dual_rule_fits_shape(d.m, d.n, pivot_rule, dual_rule))
+            LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve, dual Devex: the tableau and the weights do not fit one CU's LDS (lp_simplex_bounded_dual_rule_fits)");
+        const size_t cells = (size_t)(d.m + 1) * (d.n + 1);
+        const size_t lds = lp_bounded_weights_lds_bytes(d.m, d.n, lp_bounded_resolve_weights(d.m, d.n, pivot_rule, dual_rule));
+        if (pivot_rule == LP_PIVOT_DEVEX)
+            return lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_devex_ddevex<256>,
+                                    k_batched_bounded_resolve_devex_ddevex<1024>, lds, d);
+        if (pivot_rule == LP_PIVOT_BLAND)
+            return lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_bland_ddevex<256>,
+                                    k_batched_bounded_resolve_bland_ddevex<1024>, lds, d);
+        return lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_ddevex<256>, k_batched_bounded_resolve_ddevex<1024>,
+                                lds, d);
+    }
     if (!lp_bounded_fits_shape(d.m, d.n))
         LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: the shape does not fit one CU's LDS");
     if (!lp_bounded_rule_fits_shape(d.m, d.n, pivot_rule))

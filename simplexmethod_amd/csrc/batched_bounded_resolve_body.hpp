@@ -1,14 +1,18 @@
 // batched_bounded_resolve_body.hpp — the body of k_batched_bounded_resolve<NT> and of its rule forms
 // (batched_bounded_resolve.hip, which describes the flow and the layout), included INSIDE each of them. As it stands
 // it runs Dantzig's rule; under the macro LP_BOUNDED_BLAND or LP_BOUNDED_DEVEX batched_bounded_loop.hpp's loop runs
-// that rule, and under LP_BOUNDED_DEVEX the carve carries the weights (wts). BLAND = false is for
-// batched_lds_loop.hpp, of which only the pivot is used. Not a standalone header.
+// that rule, and under LP_BOUNDED_DEVEX the carve carries the weights (wts). Under LP_BOUNDED_DUAL_DEVEX
+// batched_bounded_dual_loop.hpp's loop prices by Devex with one weight per basis position (dwts), which share the
+// region of wts: an LP runs one of the two loops. BLAND = false is for batched_lds_loop.hpp, of which only the pivot
+// is used. Not a standalone header.
     constexpr bool BLAND = false;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     char* base = reinterpret_cast<char*>(smem);
     const int m = d.m, n = d.n, W = n + 1;
 #ifdef LP_BOUNDED_DEVEX
     const BoundedCarve K = bounded_carve(m, n, true);
+#elif defined(LP_BOUNDED_DUAL_DEVEX)
+    const BoundedCarve K = bounded_carve(m, n, false, m);
 #else
     const BoundedCarve K = bounded_carve(m, n);
 #endif
@@ -27,6 +31,9 @@
     int* up = reinterpret_cast<int*>(base + K.up);
 #ifdef LP_BOUNDED_DEVEX
     double* wts = reinterpret_cast<double*>(base + K.wts);   // the Devex weights, one per slot
+#endif
+#ifdef LP_BOUNDED_DUAL_DEVEX
+    double* dwts = reinterpret_cast<double*>(base + K.wts);   // the dual Devex weights, one per basis position
 #endif
     int* pub = pubs->v;   // [0] entering slot / crash row, [1] leaving position, [2] action / verdict, [3] block_any
 

@@ -283,6 +283,14 @@ size_t lp_bounded_lds_bytes(int m, int n, int* pitch_out);
 bool lp_bounded_fits_shape(int m, int n);
 size_t lp_bounded_devex_lds_bytes(int m, int n);                    // the carve with the Devex weights behind it
 bool lp_bounded_rule_fits_shape(int m, int n, int pivot_rule);      // a known rule, lp_bounded_fits_shape, Devex: the weights too
+// The re-solve under a dual rule too (LP_DUAL_*): one weight region for the loop that runs, n doubles for the primal
+// Devex, m for the dual Devex, the larger when both are chosen, none otherwise
+inline int lp_bounded_resolve_weights(int m, int n, int pivot_rule, int dual_rule) {
+    const int p = pivot_rule == LP_PIVOT_DEVEX ? n : 0, q = dual_rule == LP_DUAL_DEVEX ? m : 0;
+    return p > q ? p : q;
+}
+size_t lp_bounded_weights_lds_bytes(int m, int n, int weights);     // the carve with `weights` doubles behind it
+bool lp_bounded_dual_rule_fits_shape(int m, int n, int pivot_rule, int dual_rule);   // known rules, and that carve <= 160 KiB
 // fitting shapes (under the rule), else LP_BAD_ARG; LP_PIVOT_DANTZIG launches the kernel there has always been
 int lp_batched_bounded_launch(lp_context* ctx, const BatchedBoundedDev& d, int pivot_rule = LP_PIVOT_DANTZIG);
 
@@ -296,7 +304,8 @@ struct BatchedBoundedResolveDev : BatchedBoundedDev {
 
 // batched_bounded_resolve.hip
 // fitting shapes (under the rule), else LP_BAD_ARG; the rule governs the primal branch only
-int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule = LP_PIVOT_DANTZIG);
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule = LP_PIVOT_DANTZIG,
+                                      int dual_rule = LP_DUAL_DANTZIG);
 
 // Depth-first branch-and-bound over variable bounds, one mixed-integer bounded LP per workgroup
 // (batched_mip_bounded.hip; the definition is tests/ref/mip_bounded_ref.c): the bounded re-solve at the root, then per

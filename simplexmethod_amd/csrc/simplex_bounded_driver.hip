@@ -1,6 +1,6 @@
 // simplex_bounded_driver.hip — the host side of the bounded-variable simplex on the tableau in HBM, for LPs beyond one
-// workgroup's LDS: lp_simplex_bounded_large, lp_simplex_bounded_resolve_large (both also as _ex under a pivot rule) and
-// lp_mip_bounded_solve_large.  The selectors are simplex_bounded_launch.hip's, the search's kernels
+// workgroup's LDS: lp_simplex_bounded_large, lp_simplex_bounded_resolve_large (both also as _ex under a pivot rule, the
+// re-solve as _dual_ex under a dual pricing rule too) and lp_mip_bounded_solve_large.  The selectors are simplex_bounded_launch.hip's, the search's kernels
 // mip_bounded_large.hip's; the problem record, the upload and the two-phase pieces are simplex_driver.hip's.
 #include <cmath>
 
@@ -63,9 +63,10 @@ void shift_rhs(const double* A, int m, int n, const double* w, Take take, double
 
 // The rule's selector (its LDS checked and opted in) and the bound state beside the tableau of p: U (cols entries), the
 // flags (up null: none set), the flip counter, the dual selector's scratch and, under LP_PIVOT_DEVEX, the weights
-// (run_bounded_phase sets them).  buf must be freed before the problem (hipFree waits for the queued kernels).
+// (run_bounded_phase sets them; under LP_DUAL_DEVEX the dual loop's m weights live in the same cols >= m entries).
+// buf must be freed before the problem (hipFree waits for the queued kernels).
 int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLargeDev& bd, const double* U,
-                        const int* up, int cols, int rule) {
+                        const int* up, int cols, int rule, int dual_rule = LP_DUAL_DANTZIG) {
     lp_context* ctx = p->ctx;
     hipStream_t s = ctx->stream;
     const int rc = lp_bounded_large_prepare(p, rule);
@@ -73,7 +74,7 @@ int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLar
     LP_HIP(ctx, lp_carve_malloc(&buf.ptr, [&](lp_carver& cv) {
         bd.U = cv.take<double>(sizeof(double) * (size_t)cols);
         bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
-        bd.w = rule == LP_PIVOT_DEVEX ? cv.take<double>(sizeof(double) * (size_t)cols) : nullptr;
+        bd.w = rule == LP_PIVOT_DEVEX || dual_rule == LP_DUAL_DEVEX ? cv.take<double>(sizeof(double) * (size_t)cols) : nullptr;
         bd.up = cv.take<int>(sizeof(int) * (size_t)cols);
         bd.flips = cv.take<int>(sizeof(int));
     }));
@@ -88,13 +89,15 @@ int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLar
 
 // One loop on the tableau of p: the bounded selector + rank-1 update pair per iteration, polled by lp_poll_pivots.
 // *iters = its pivots plus flips, *flips = the flips since the start of the solve.  rule: the primal selector (Devex:
-// the weights are reset on the stream first).  dual: the dual selector in its place (lp_bounded_dual_prepare has run).
+// the weights are reset on the stream first).  dual: the dual selector of dual_rule in its place (lp_bounded_dual_prepare
+// has run for it; LP_DUAL_DEVEX: its m weights are reset on the stream first).
 int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule, double eps, int max_iter, int* iters,
-                      int* flips, bool dual = false) {
+                      int* flips, bool dual = false, int dual_rule = LP_DUAL_DANTZIG) {
     lp_context* ctx = p->ctx;
     lp_launch_begin(p, eps, max_iter);
     if (!dual && rule == LP_PIVOT_DEVEX) lp_bounded_large_reset_weights(p, bd);
-    int rc = lp_poll_pivots(p, [&](int batch) { return lp_bounded_large_queue(p, bd, batch, rule, dual); });
+    if (dual && dual_rule == LP_DUAL_DEVEX) lp_bounded_large_reset_weights(p, bd, true);
+    int rc = lp_poll_pivots(p, [&](int batch) { return lp_bounded_large_queue(p, bd, batch, rule, dual, dual_rule); });
     if (rc) return rc;
     rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
     if (rc) return rc;
@@ -107,15 +110,16 @@ int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule
 // every basic variable is within its bounds, else the dual loop when the start is dual feasible, else LP_BAD_ARG under
 // who's name.  Returns the loop's status or a negative HIP error; count[0..2] += its dual pivots, primal pivots and
 // flips.  prepare_dual: opt the dual selector's LDS in on the dual branch (the re-solve; the search did it up front).
+// dual_rule: the pricing of the dual loop (the search passes none: Dantzig's).
 int bounded_run_from_start(lp_simplex_problem* p, const BoundedLargeDev& bd, const char* who, int rule, double eps,
-                           int max_iter, bool prepare_dual, int* count) {
+                           int max_iter, bool prepare_dual, int* count, int dual_rule = LP_DUAL_DANTZIG) {
     int flags = 0, iters = 0, flips = 0;
     int rc = lp_bounded_large_classify(p, bd, eps, &flags);
     if (rc) return rc;
     const bool dual = flags & 1;
     if (dual && (flags & 2)) LP_FAIL(p->ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
-    if (dual && prepare_dual && (rc = lp_bounded_dual_prepare(p)) != LP_OPTIMAL) return rc;
-    rc = run_bounded_phase(p, bd, rule, eps, max_iter, &iters, &flips, dual);
+    if (dual && prepare_dual && (rc = lp_bounded_dual_prepare(p, dual_rule)) != LP_OPTIMAL) return rc;
+    rc = run_bounded_phase(p, bd, rule, eps, max_iter, &iters, &flips, dual, dual_rule);
     if (rc < 0) return rc;
     count[dual ? 0 : 1] += dual ? iters : iters - flips;
     if (!dual) count[2] += flips;
@@ -326,9 +330,23 @@ int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m,
                                         const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
                                         double* x_out, int* basis_out, int* at_upper_out, double* obj_out,
                                         int* iters_out, int pivot_rule) {
+    return lp_simplex_bounded_resolve_large_dual_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig,
+                                                    eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
+                                                    pivot_rule, LP_DUAL_DANTZIG);
+}
+
+// The same under a dual pricing rule too (tests/ref/bounded_resolve_dual_rules_ref.c): dual_rule picks the dual loop's
+// selector and nothing else; under LP_DUAL_DANTZIG every launch is lp_simplex_bounded_resolve_large_ex's.
+int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                                             const double* c, const double* lo, const double* hi, const int* basis_in,
+                                             const int* at_upper_in, int maximize, int n_orig, double eps,
+                                             int max_iter, double* x_out, int* basis_out, int* at_upper_out,
+                                             double* obj_out, int* iters_out, int pivot_rule, int dual_rule) {
     const char* who = "lp_simplex_bounded_resolve_large";
     const bool any_null = !x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo ||
                           !hi || !basis_in || !at_upper_in;
+    if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_rule_known(dual_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown dual rule");
     int rc = check_bounded_entry(ctx, who, pivot_rule, any_null, eps, m, n, n_orig, lo, hi);
     if (rc) return rc;
     rc = check_bounded_start(ctx, who, n, m, hi, basis_in, at_upper_in);
@@ -362,10 +380,10 @@ int lp_simplex_bounded_resolve_large_ex(lp_context* ctx, const double* A, int m,
         LP_FAIL(ctx, p->init_status, std::string(who) + ": the basis matrix is singular");
     lp_device_buffer buf;   // (freed before the problem on every return path)
     BoundedLargeDev bd{};
-    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n, pivot_rule);
+    rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n, pivot_rule, dual_rule);
     if (rc) return rc;
     // steps 5 and 6: the loop the start allows (a refusal or a HIP error leaves iters_out at zero)
-    rc = bounded_run_from_start(p, bd, who, pivot_rule, eps, max_iter, true, it);
+    rc = bounded_run_from_start(p, bd, who, pivot_rule, eps, max_iter, true, it, dual_rule);
     if (rc < 0 || rc == LP_BAD_ARG) return rc;
     int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
                               : download_basis(p, N.data());

@@ -15,7 +15,8 @@
 //   up[d.n]  1 = the tableau holds U_j - x'_j in place of x'_j (what at_upper_out reports);
 //   flips    bound flips since the start of the solve (both phases);
 //   q[ld]    scratch of the dual selector: the quotients of its ratio test;
-//   w[d.n]   the Devex weights (LP_PIVOT_DEVEX only; the other selectors never touch them).
+//   w[d.n]   the Devex weights (LP_PIVOT_DEVEX only; the other selectors never touch them).  The dual loop under
+//            LP_DUAL_DEVEX keeps its own in the first m of them, one per basis position (a call runs one of the loops).
 // SimplexState::iters counts the pivots plus flips of the running phase, which is what max_iter bounds.
 //
 // A bound flip is done inside the selector (two strided columns, O(m)) and leaves pivot_valid = 0, so the
@@ -553,6 +554,149 @@ __global__ __launch_bounds__(1024) void k_simplex_select_dual_bounded(SimplexDev
     }
 }
 
+// ---------------------------------------------------------------------------
+// The bounded dual selector under Devex pricing (LP_DUAL_DEVEX; tests/ref/bounded_resolve_dual_rules_ref.c is the
+// definition).  Everything but the leaving choice and the weights is k_simplex_select_dual_bounded's: the complement,
+// the entering chain with its quotients in bd.q, the staging of lcol / prow, the trace.
+//   weights:  bd.w[0 .. m), one per basis position, all exactly 1.0 when the dual loop starts (the host resets them
+//             on the stream);
+//   leaving:  the arg-max of (v_t * v_t) / w_t over the violated positions by the whole workgroup: each thread strides
+//             over its positions (m may exceed the 1024 threads) with a strict >, the waves and then the workgroup
+//             combine on (score, position) with exact ties to the smaller position, as k_simplex_select_bounded_devex
+//             does for its columns.  A NaN score fails every comparison and is never taken.  Every thread combines the
+//             sixteen published wave results itself, so all of them hold the same r without another barrier;
+//   update:   in the loop that stages lcol, from column e in LDS, a = T[r][e] as the complement left it and the old
+//             w_r (read by every thread right after the selection, several barriers ahead of its rewrite):
+//             w_i = cand if cand = (g * g) * w_r > w_i, g = T[i][e] / a, for i != r; w_r = max(w_r / (a * a), 1.0) by
+//             the thread that owns r.  An infeasible exit updates nothing.  No multiply feeds an add.
+// LDS: k_simplex_select_dual_bounded's plus the sixteen wave results (16 doubles + 16 ints):
+// 16 (m + 2) + 208 + 192 bytes <= 156 KiB, m <= 9957.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_simplex_select_dual_bounded_devex(SimplexDev d, BoundedLargeDev bd) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_v = s_dyn;                     // m + 2: column e
+    double* s_x = s_dyn + (d.m + 2);         // m (+ 2 of padding): xB
+    lpdev::BlockChainScratch* sc = reinterpret_cast<lpdev::BlockChainScratch*>(s_dyn + 2 * (d.m + 2));
+    double* s_score = reinterpret_cast<double*>(sc + 1);   // the sixteen wave results of the leaving choice
+    int* s_pos = reinterpret_cast<int*>(s_score + 16);
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // leaving position
+    double best = -1.0;
+    int r = INT_MAX;
+    for (int t = tid; t < m; t += blockDim.x) {
+        const double xb = d.T[(size_t)t * ld + n], u = bd.U[d.basis[t]], wt = bd.w[t];
+        s_x[t] = xb;
+        const double v = (xb < -eps) ? xb : u - xb;
+        const double s = (v * v) / wt;
+        if ((xb < -eps || (u < INFINITY && v < -eps)) && s > best) {
+            best = s;   // t ascending per thread: strict > keeps the smallest position
+            r = t;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int op = __shfl_xor(r, off, 64);
+        if (ob > best || (ob == best && op < r)) {
+            best = ob;
+            r = op;
+        }
+    }
+    if ((tid & 63) == 0) {
+        s_score[tid >> 6] = best;
+        s_pos[tid >> 6] = r;
+    }
+    __syncthreads();
+    best = s_score[0];
+    r = s_pos[0];
+    for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
+        if (s_score[q] > best || (s_score[q] == best && s_pos[q] < r)) {
+            best = s_score[q];
+            r = s_pos[q];
+        }
+    if (r == INT_MAX) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // (every thread reads basis[r], w[r] and nonbasic[] before the barriers below; they are written after the last)
+    const int old = d.basis[r];
+    const double wr = bd.w[r];
+    const bool comp = !(s_x[r] < -eps);   // violated above: the complement of N(r) is what is below 0
+    const double uold = bd.U[old];
+    // entering column
+    const double* trow = d.T + (size_t)r * ld;
+    const double* drow = d.T + (size_t)m * ld;
+    const bool maxi = d.maximize != 0;
+    auto quotient = [&](int j) {
+        const double t = trow[j], a = comp ? -t : t;
+        if (!(d.nonbasic[j] != 0 && a < -eps)) return (double)INFINITY;
+        return maxi ? drow[j] / a : -drow[j] / a;
+    };
+    const int e = lpdev::block_chain_select<false, true>(n, eps, best, quotient, bd.q, sc);
+    if (e < 0) {   // row r sums non-negative terms to a negative right-hand side
+        if (tid == 0) {
+            if (comp) bd.up[old] ^= 1;
+            st->status = LP_INFEASIBLE;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // stage the pivot on (r, e); column e of the complemented row r changes sign with it
+    for (int i = tid; i <= m; i += blockDim.x) s_v[i] = d.T[(size_t)i * ld + e];
+    __syncthreads();
+    const double ur = comp ? -s_v[r] : s_v[r];
+    for (int i = tid; i <= m; i += blockDim.x) {
+        d.lcol[i] = (i == r) ? 1.0 / ur : -s_v[i] / ur;
+        if (i == r) {
+            bd.w[i] = fmax(wr / (ur * ur), 1.0);
+        } else if (i < m) {
+            const double g = s_v[i] / ur;
+            const double cand = (g * g) * wr;
+            if (cand > bd.w[i]) bd.w[i] = cand;
+        }
+    }
+    for (int j = tid; j < ld; j += blockDim.x) {
+        double v = trow[j];
+        if (comp) v = (j < n) ? -v : (j == n) ? uold - v : v;
+        if (j == old) v = 1.0;   // the leaving variable's own column: the unit column again (a no-op without comp)
+        d.prow[j] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (comp) bd.up[old] ^= 1;
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
 // Which loop lp_simplex_bounded_resolve_large runs: the bounded form of k_simplex_classify.  st->pad0 = bit 0 some
 // basis position violated (xB_t < -eps, or U_N(t) finite and U_N(t) - xB_t < -eps), bit 1 dual infeasible (some
 // non-basic d_j > eps for max, d_j < -eps for min).  One workgroup.
@@ -571,8 +715,10 @@ __global__ __launch_bounds__(1024) void k_simplex_classify_bounded(SimplexDev d,
     if (tid == 0) d.state->pad0 = (pinf ? 1 : 0) | (dinf ? 2 : 0);
 }
 
-size_t select_dual_bounded_lds_bytes(const lp_simplex_problem* p) {
-    return sizeof(double) * 2 * (size_t)(p->dev.m + 2) + sizeof(lpdev::BlockChainScratch);
+// (LP_DUAL_DEVEX: the sixteen wave results of the leaving choice, 16 doubles + 16 ints, behind the chain scratch)
+size_t select_dual_bounded_lds_bytes(const lp_simplex_problem* p, int dual_rule = LP_DUAL_DANTZIG) {
+    return sizeof(double) * 2 * (size_t)(p->dev.m + 2) + sizeof(lpdev::BlockChainScratch) +
+           (dual_rule == LP_DUAL_DEVEX ? 16 * 8 + 16 * 4 : 0);
 }
 
 // (Devex: the sixteen wave results of the pricing, 16 doubles + 16 ints, behind the two ints)
@@ -596,14 +742,17 @@ int lp_bounded_large_prepare(lp_simplex_problem* p, int rule) {
     return LP_OPTIMAL;
 }
 
-void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd) {
-    const int n = p->dev.n;
+void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd, bool dual) {
+    const int n = dual ? p->dev.m : p->dev.n;
     hipLaunchKernelGGL(k_bounded_reset_weights, (n + 255) / 256, 256, 0, p->ctx->stream, bd.w, n);
 }
 
-int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual) {
-    const size_t shm = dual ? select_dual_bounded_lds_bytes(p) : select_bounded_lds_bytes(p, rule);
-    const BoundedSelector select = dual ? k_simplex_select_dual_bounded : bounded_selector(rule);
+int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual,
+                           int dual_rule) {
+    const size_t shm = dual ? select_dual_bounded_lds_bytes(p, dual_rule) : select_bounded_lds_bytes(p, rule);
+    const BoundedSelector select = !dual                         ? bounded_selector(rule)
+                                   : dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_devex
+                                                                : k_simplex_select_dual_bounded;
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(select, 1, 1024, shm, p->ctx->stream, p->dev, bd);
         lp_simplex_launch_update(p);
@@ -622,10 +771,11 @@ int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, 
     return LP_OPTIMAL;
 }
 
-int lp_bounded_dual_prepare(lp_simplex_problem* p) {
-    const size_t shm = select_dual_bounded_lds_bytes(p);
+int lp_bounded_dual_prepare(lp_simplex_problem* p, int dual_rule) {
+    const size_t shm = select_dual_bounded_lds_bytes(p, dual_rule);
     if (shm > 156 * 1024)
         LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_large: m too large for the dual selector's LDS");
-    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(k_simplex_select_dual_bounded), shm));
+    const BoundedSelector select = dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_devex : k_simplex_select_dual_bounded;
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(select), shm));
     return LP_OPTIMAL;
 }

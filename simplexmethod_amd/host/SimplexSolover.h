@@ -38,6 +38,10 @@ public:
     // fewer pivots on badly scaled or large problems and runs on a slower-per-pivot path
     // (include/simplexmethod_amd.h).
     enum class PivotRule { Dantzig = LP_PIVOT_DANTZIG, Bland = LP_PIVOT_BLAND, Devex = LP_PIVOT_DEVEX };
+    // The pricing rule of the dual simplex of boundedResolve() and boundedResolveLarge(): the most violated basis
+    // position leaves (Dantzig, the default), or the one of largest violation^2 / reference weight (Devex), which
+    // takes fewer dual pivots on LPs of many rows (include/simplexmethod_amd.h, LP_DUAL_*).
+    enum class DualRule { Dantzig = LP_DUAL_DANTZIG, Devex = LP_DUAL_DEVEX };
 
     explicit Solver(const Canonical& problem, int device = 0) : _problem(problem), _device(device) {}
 
@@ -291,6 +295,24 @@ public:
     BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
                                  const BoundedResult& from, PivotRule rule, bool throw_on_failure = true) const {
         return boundedRun("Solver::boundedResolve", lo, hi, &from, &rule, throw_on_failure);
+    }
+
+    // boundedResolve under a pivot rule and a dual pricing rule (lp_simplex_bounded_resolve_dual_ex): `rule` governs
+    // the primal loop only and `dual` the dual simplex only.  DualRule::Dantzig is the form above bit for bit; under
+    // DualRule::Devex status and objective are its up to rounding, the optimal basis and the pivot count may differ.  A
+    // shape beyond lp_simplex_bounded_dual_rule_fits throws std::invalid_argument.
+    BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
+                                 const BoundedResult& from, PivotRule rule, DualRule dual,
+                                 bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolve", lo, hi, &from, &rule, throw_on_failure, false, &dual);
+    }
+
+    // The same at any shape boundedSimplexLarge runs (lp_simplex_bounded_resolve_large_dual_ex): the dual weights live
+    // in device memory.  Equal to boundedResolve(lo, hi, from, rule, dual) where both run.
+    BoundedResult boundedResolveLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                      const BoundedResult& from, PivotRule rule, DualRule dual,
+                                      bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, &rule, throw_on_failure, true, &dual);
     }
 
     // The dual solution of the bounded problem at a result's basis and flags (lp_basis_bounded_duals), in the original
@@ -688,10 +710,11 @@ private:
     }
 
     // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form;
-    // large: boundedSimplexLarge, or with from boundedResolveLarge, the same way
+    // large: boundedSimplexLarge, or with from boundedResolveLarge, the same way; dual (with from and rule): the
+    // re-solve's _dual_ex form
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
                              const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
-                             bool large = false) const {
+                             bool large = false, const DualRule* dual = nullptr) const {
         const View p = view();
         requireBounds(who, p, lo, hi);
         if (from) requireStart(who, "start", p, *from);
@@ -700,7 +723,12 @@ private:
         out.basis.assign((size_t)p.m, -1);
         out.atUpper.assign((size_t)p.n, 0);
         lp_context* ctx = lpgpu::context(_device);
-        if (large && from && rule)
+        if (from && rule && dual) {
+            const auto entry = large ? lp_simplex_bounded_resolve_large_dual_ex : lp_simplex_bounded_resolve_dual_ex;
+            out.status = entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from->basis.data(),
+                               from->atUpper.data(), p.maximize, p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
+                               out.atUpper.data(), &out.objective, out.iterations, (int)*rule, (int)*dual);
+        } else if (large && from && rule)
             out.status = lp_simplex_bounded_resolve_large_ex(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(),
                                                              from->basis.data(), from->atUpper.data(), p.maximize,
                                                              p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
