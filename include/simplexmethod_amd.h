@@ -702,8 +702,9 @@ int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule);
  * Shapes: the two LDS entries need lp_simplex_bounded_dual_rule_fits (else LP_BAD_ARG, nothing launched).  The _large
  * entry keeps its m weights in device memory and has no such limit; its Devex dual selector keeps sixteen wave results
  * more in LDS than the plain one: m <= 9957 in the dual branch under LP_DUAL_DEVEX.
- * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large) and the parametric paths keep
- * Dantzig's dual rule, and the unbounded lp_simplex_resolve family is not touched.                                    */
+ * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large and _large_ex, whose snapshots
+ * change where a second child starts and not how a node is priced) and the parametric paths keep Dantzig's dual rule,
+ * and the unbounded lp_simplex_resolve family is not touched.                                                         */
 enum { LP_DUAL_DANTZIG = 0, LP_DUAL_DEVEX = 1 };
 int lp_simplex_bounded_resolve_dual_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule);
 int lp_simplex_bounded_resolve_batched_dual_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule);
@@ -752,9 +753,36 @@ int lp_mip_bounded_fits(int m, int n, int max_depth);
  * limits are lp_simplex_bounded_resolve_large's, device memory for the tableau and m <= 9960 for the dual selector's
  * LDS, plus max_depth records of m + n ints in device memory; max_depth stays in [0, 1024]).  Refusals are checked
  * before anything is launched and leave the context usable.  At a shape that also fits LDS every output equals
- * lp_mip_bounded_solve's.  Dantzig's rule; lp_mip_bounded_solve itself is unchanged and still refuses larger shapes.
- * Every pointer is required.                                                                                        */
+ * lp_mip_bounded_solve's.  Dantzig's primal and dual rules at every node; lp_mip_bounded_solve itself is unchanged and
+ * still refuses larger shapes.  Every pointer is required.
+ *
+ * lp_mip_bounded_solve_large_ex: the same search with up to `snapshots` = K tableau snapshots in device memory (DESIGN.md
+ * §4.5l3; the definition is tests/ref/mip_bounded_snapshots_ref.c, and every output equals it bit for bit).  A node that
+ * branches at level L and dives is saved as it stood before the dive's bound change (the tableau, U and the node's lo;
+ * the basis and the flags are the level's record) in slot L mod K, which then belongs to level L; a second child whose
+ * level still owns its slot is restored from it and continues exactly like a first child: the other side's bound change
+ * on the restored tableau (one launch, one sync), then the bounded dual loop, with no staging, no crash and no
+ * classification.  Any other second child is rebuilt as above.  With K >= max_depth every second child is restored; a
+ * smaller ring keeps the K deepest pending levels, the ones depth-first search returns to first.
+ *   - snapshots outside [0, 1024] is LP_BAD_ARG before anything else is looked at, and no output is written; every
+ *     other refusal is lp_mip_bounded_solve_large's;
+ *   - at most min(snapshots, max_depth) slots are allocated, each when the search first writes it (so a call takes at
+ *     most lp_mip_bounded_snapshot_bytes(m, n, min(snapshots, max_depth)) for them); a failed allocation returns the
+ *     negative HIP error, frees what the call took and leaves the context usable;
+ *   - snapshots = 0 launches exactly what lp_mip_bounded_solve_large launches and equals it in every output;
+ *     lp_mip_bounded_solve_large is this entry with 0 snapshots and a five-entry copy-out;
+ *   - stats_out[7] = the five counters, then the second children restored, then the second children rebuilt;
+ *   - with K > 0 the status, found_out and the nodes solved are those of K = 0 on every committed case and the objective
+ *     agrees to rounding, but x_out may differ in its last bits: a restored child continues the parent's pivots where
+ *     a rebuilt one crashes its basis afresh.  Dantzig's rules here too.                                             */
 int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
+int lp_mip_bounded_solve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int snapshots);
+/* Host call, no context.  *bytes_out = the device bytes `snapshots` slots take at m x n: snapshots x 8 x ((m + 1) ld +
+ * 2 n2) with ld = n + 1 rounded up to a multiple of 8 and n2 = n rounded up to a multiple of 2 (the tableau's padded
+ * rows, then U and the node's lo).
+ * A caller sizes `snapshots` against free device memory with it.  LP_BAD_ARG (nothing written) for a NULL bytes_out,
+ * m <= 0, n < m or snapshots outside [0, 1024].                                                                      */
+int lp_mip_bounded_snapshot_bytes(int m, int n, int snapshots, unsigned long long* bytes_out);
 
 /* ---- Bounded variables: the dual solution and ranging at a basis ------------------------------------------------
  * The LP of lp_simplex_bounded analysed at basis (m, by position, every index in [0, n)) and at_upper (n, 0/1),

@@ -149,6 +149,7 @@ REFS = {
     "bounded": (),
     "bounded_resolve": ("bounded",),
     "mip_bounded": ("bounded_resolve", "bounded"),
+    "mip_bounded_snapshots": ("mip_bounded", "bounded_resolve", "bounded"),
     "bounded_sens": ("ranging", "duals"),
     "bounded_certificate": ("certificate", "ranging", "duals"),
     "bounded_parametric": ("bounded_resolve", "bounded"),
@@ -190,6 +191,7 @@ build_mip_ref = functools.partial(build_ref, "mip")
 build_bounded_ref = functools.partial(build_ref, "bounded")
 build_bounded_resolve_ref = functools.partial(build_ref, "bounded_resolve")
 build_mip_bounded_ref = functools.partial(build_ref, "mip_bounded")
+build_mip_bounded_snapshots_ref = functools.partial(build_ref, "mip_bounded_snapshots")
 build_bounded_sens_ref = functools.partial(build_ref, "bounded_sens")
 build_bounded_certificate_ref = functools.partial(build_ref, "bounded_certificate")
 build_bounded_parametric_ref = functools.partial(build_ref, "bounded_parametric")

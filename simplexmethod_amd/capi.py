@@ -190,6 +190,10 @@ SIGNATURES = {
     "lp_mip_bounded_solve_large": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int,
                                              _ip, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
                                              _dp, _dp, _ip, _ip]),
+    "lp_mip_bounded_solve_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                C.c_int, _dp, _dp, _dp, _ip, _ip, C.c_int]),
+    "lp_mip_bounded_snapshot_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, _u64p]),
     "lp_basis_bounded_duals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
     "lp_basis_bounded_duals_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                  _dp, _dp, _dp, _dp, _ip]),
@@ -1191,21 +1195,36 @@ class Context:
 
     def mip_bounded_solve_large(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,
                                 int_tol=INT_TOL, gap=GAP, max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES,
-                                max_iter=MAX_ITER):
+                                max_iter=MAX_ITER, snapshots=None):
         """lp_mip_bounded_solve_large: mip_bounded_solve() on the tableau in HBM, at any shape
         bounded_resolve_large() runs (no mip_bounded_fits limit; m <= 9960).  Arguments, the dict returned and the
-        refusals are mip_bounded_solve()'s, and at a shape that also fits LDS so is every value."""
+        refusals are mip_bounded_solve()'s, and at a shape that also fits LDS so is every value.
+        snapshots = K (an int in [0, 1024]): lp_mip_bounded_solve_large_ex, which keeps up to min(K, max_depth)
+        tableau snapshots on the device (mip_bounded_snapshot_bytes says how large) and starts a second child from its
+        parent's final tableau where its level's snapshot is still there; stats then has seven entries, the last two
+        the second children restored and rebuilt.  K = 0 equals the call without the argument."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
         integer = _mask(integer, n)
-        x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5)
-        rc = self.check(self.lib.lp_mip_bounded_solve_large(
-            self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
-            _i(integer), float(eps), float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter), _d(x),
-            _d(obj), _d(bound), _i(found), _i(stats)))
+        x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5 if snapshots is None else 7)
+        args = (self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
+                _i(integer), float(eps), float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter),
+                _d(x), _d(obj), _d(bound), _i(found), _i(stats))
+        if snapshots is None:
+            rc = self.check(self.lib.lp_mip_bounded_solve_large(*args))
+        else:
+            rc = self.check(self.lib.lp_mip_bounded_solve_large_ex(*args, int(snapshots)))
         return dict(status=rc, found=int(found[0]), x=x[0], obj=float(obj[0]), bound=float(bound[0]),
                     stats=tuple(int(v) for v in stats[0]))
+
+    def mip_bounded_snapshot_bytes(self, m, n, snapshots):
+        """lp_mip_bounded_snapshot_bytes: the device bytes `snapshots` tableau snapshots of an m x n problem take."""
+        out = C.c_uint64(0)
+        rc = self.lib.lp_mip_bounded_snapshot_bytes(int(m), int(n), int(snapshots), C.byref(out))
+        if rc != OPTIMAL:   # (a host call: the context holds no message for it)
+            raise LPError(rc, "lp_mip_bounded_snapshot_bytes: bad dimensions or snapshots outside [0, 1024]")
+        return int(out.value)
 
     def mip_bounded_fits(self, m, n, max_depth=MAX_DEPTH_BOUNDED):
         """lp_mip_bounded_fits: True if an m x n bounded problem searched to max_depth fits one CU's LDS."""

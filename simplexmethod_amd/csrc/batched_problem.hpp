@@ -312,6 +312,7 @@ int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResol
 // node one bound changed on the live tableau (first child) or the re-solve's install from the path's bounds and the
 // recorded basis and flags (second child).  The tableau never grows, so the depth is bounded by the records alone.
 #define LP_MIP_BOUNDED_MAX_DEPTH 1024
+#define LP_MIP_BOUNDED_MAX_SNAPSHOTS 1024   // lp_mip_bounded_solve_large_ex: the tableau snapshots a call may ask for
 struct BatchedMipBoundedDev {
     int batch, m, n, n_orig;
     int maximize;

@@ -12,6 +12,17 @@
 //             variables, z as one serial chain on one lane, the pruning test, the branching column, and then the
 //             incumbent, the abandoned node, or record L and the first child's bound change on the live tableau (one
 //             held value, U_j and lo_j move).  One small result goes to pinned host memory: one host sync per node.
+// lp_mip_bounded_solve_large_ex (tests/ref/mip_bounded_snapshots_ref.c) adds three more:
+//   save      the state of a node that branched, as it was BEFORE the dive's bound change, into a snapshot slot: the
+//             (m+1) x ld tableau as 16-byte moves of 64-bit words, then U and the node's lo.  The node kernel has
+//             already applied the change, so it reports the three values it overwrote and where (MipLargeResult), the
+//             host queues the save once it has seen LP_MIPL_BRANCHED, and the save writes those values into the slot
+//             in place of the live ones: no copy for a node that does not branch, no sync of its own;
+//   restore   the copy back, with the basis and the flags from the level's record (rec_basis, rec_up: the node kernel
+//             recorded them before the change, so a slot does not hold them twice) and the non-basic marks set;
+//   the second child   step 5 with the other side on the restored state, one workgroup: the basic columns' marks
+//             cleared, the position of j found in the basis, the bound change, U' < 0 reported through the pinned
+//             result.  The bounded dual loop follows where the tableau stands: no staging, crash or classification.
 //
 // Plain C++ and vector stores only: no inline assembly and no scalar-memory writes in this file.
 #include <climits>
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(kNodeThreads) void k_mipl_node(SimplexDev d, Bounde
             res->what = LP_MIPL_PRUNED;
             res->j = -1;
             res->un_negative = 0;
+            res->t = -1;
             res->z = z;
             res->v = 0.0;
             __threadfence_system();
@@ -170,6 +182,7 @@ __global__ __launch_bounds__(kNodeThreads) void k_mipl_node(SimplexDev d, Bounde
     res->z = z;
     res->j = jb;
     res->un_negative = 0;
+    res->t = -1;
     res->v = 0.0;
     if (jb < 0) {
         res->what = LP_MIPL_INTEGRAL;
@@ -187,6 +200,11 @@ __global__ __launch_bounds__(kNodeThreads) void k_mipl_node(SimplexDev d, Bounde
             double* xb = d.T + (size_t)t * ld + n;
             const int f = bd.up[jb];
             const double Uj = bd.U[jb], lj = md.lo[jb];
+            // what the change overwrites, for a snapshot of the node as it stood
+            res->t = t;
+            res->xb_before = *xb;
+            res->U_before = Uj;
+            res->lo_before = lj;
             double Un;
             if ((v - floor(v)) <= 0.5) {   // down: hi_j := floor(v)
                 Un = floor(v) - lj;
@@ -200,6 +218,105 @@ __global__ __launch_bounds__(kNodeThreads) void k_mipl_node(SimplexDev d, Bounde
             bd.U[jb] = Un;
             res->un_negative = Un < 0.0;
         }
+    }
+    __threadfence_system();
+}
+
+// ---- snapshots (lp_mip_bounded_solve_large_ex)
+
+constexpr int kCopyThreads = 256;
+constexpr unsigned kCopyBlocks = 2048;   // grid-stride above this: 8 workgroups per CU
+
+typedef unsigned long long u64;
+
+// Saves the node into a slot.  pairs = (m+1) * ld / 2 16-byte words of the tableau (ld is a multiple of 8, both
+// buffers 16-byte aligned); the 64-bit word `patch` of it (the held value of position t) is written as xb, entry j of U
+// and of lo as Uj and lj: the values from before the dive's bound change.  Every index is a size_t: pairs passes 2^31
+// bytes at shapes the entry accepts.
+__global__ __launch_bounds__(kCopyThreads) void k_mipl_save(const ulonglong2* __restrict__ T,
+                                                            ulonglong2* __restrict__ sT, size_t pairs, size_t patch,
+                                                            u64 xb, const u64* __restrict__ U,
+                                                            const u64* __restrict__ lo, u64* __restrict__ sU,
+                                                            u64* __restrict__ slo, int n, int j, u64 Uj, u64 lj) {
+    const size_t first = (size_t)blockIdx.x * kCopyThreads + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kCopyThreads;
+    const size_t ppair = patch >> 1;
+    for (size_t k = first; k < pairs; k += stride) {
+        ulonglong2 w = T[k];
+        if (k == ppair) {
+            if (patch & 1) w.y = xb;
+            else w.x = xb;
+        }
+        sT[k] = w;
+    }
+    for (size_t k = first; k < (size_t)n; k += stride) {
+        const bool own = k == (size_t)j;
+        sU[k] = own ? Uj : U[k];
+        slo[k] = own ? lj : lo[k];
+    }
+}
+
+// Restores a slot into the live state: the tableau, U and the node's lo from the slot, the flags and the basis from
+// the level's record, every column marked non-basic (k_mipl_second_child clears the basic ones' marks).
+__global__ __launch_bounds__(kCopyThreads) void k_mipl_restore(const ulonglong2* __restrict__ sT,
+                                                               ulonglong2* __restrict__ T, size_t pairs,
+                                                               const u64* __restrict__ sU, const u64* __restrict__ slo,
+                                                               u64* __restrict__ U, u64* __restrict__ lo,
+                                                               const int* __restrict__ rec_up, int* __restrict__ up,
+                                                               unsigned char* __restrict__ nonbasic, int n,
+                                                               const int* __restrict__ rec_basis,
+                                                               int* __restrict__ basis, int m) {
+    const size_t first = (size_t)blockIdx.x * kCopyThreads + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * kCopyThreads;
+    for (size_t k = first; k < pairs; k += stride) T[k] = sT[k];
+    for (size_t k = first; k < (size_t)n; k += stride) {
+        U[k] = sU[k];
+        lo[k] = slo[k];
+        up[k] = rec_up[k];
+        nonbasic[k] = 1;
+    }
+    for (size_t k = first; k < (size_t)m; k += stride) basis[k] = rec_basis[k];
+}
+
+// Step 5 with the side `down` for column j of value v on a restored node, one workgroup (m may exceed it: the pass
+// strides).  The result: LP_MIPL_BRANCHED with un_negative, or LP_MIPL_NOT_BASIC when the basis does not hold j.
+__global__ __launch_bounds__(kNodeThreads) void k_mipl_second_child(SimplexDev d, BoundedLargeDev bd, MipLargeDev md,
+                                                                    int j, double v, int down) {
+    __shared__ int s_t;
+    const int tid = threadIdx.x, m = d.m, n = d.n, ld = d.ld;
+    if (tid == 0) s_t = -1;
+    __syncthreads();
+    for (int t = tid; t < m; t += kNodeThreads) {
+        const int q = d.basis[t];
+        d.nonbasic[q] = 0;
+        if (q == j) s_t = t;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    MipLargeResult* res = md.result;
+    const int t = s_t;
+    res->j = j;
+    res->t = t;
+    res->v = v;
+    res->z = 0.0;
+    res->un_negative = 0;
+    res->what = t < 0 ? LP_MIPL_NOT_BASIC : LP_MIPL_BRANCHED;
+    if (t >= 0) {
+        double* xb = d.T + (size_t)t * ld + n;
+        const int f = bd.up[j];
+        const double Uj = bd.U[j], lj = md.lo[j];
+        double Un;
+        if (down) {   // hi_j := floor(v)
+            Un = floor(v) - lj;
+            if (f) *xb = *xb + (Un - Uj);
+        } else {      // lo_j := ceil(v)
+            const double dl = ceil(v) - lj;
+            Un = Uj - dl;
+            md.lo[j] = lj + dl;
+            if (!f) *xb = *xb - dl;
+        }
+        bd.U[j] = Un;
+        res->un_negative = Un < 0.0;
     }
     __threadfence_system();
 }
@@ -222,4 +339,61 @@ void lp_mip_large_stage(lp_simplex_problem* p, const BoundedLargeDev& bd, const 
 void lp_mip_large_node(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, int L, int found,
                        double zstar, int dive) {
     hipLaunchKernelGGL(k_mipl_node, 1, kNodeThreads, 0, p->ctx->stream, p->dev, bd, md, L, found, zstar, dive);
+}
+
+size_t lp_mip_large_slot_bytes(int m, int n) {
+    const size_t ld = ((size_t)n + 1 + 7) / 8 * 8, npad = ((size_t)n + 1) / 2 * 2;
+    return sizeof(double) * (((size_t)m + 1) * ld + 2 * npad);
+}
+
+namespace {
+
+struct SlotView {
+    double *T, *U, *lo;
+};
+
+SlotView slot_view(const lp_simplex_problem* p, char* slot) {
+    const size_t words = ((size_t)p->dev.m + 1) * (size_t)p->dev.ld, npad = ((size_t)p->dev.n + 1) / 2 * 2;
+    double* T = reinterpret_cast<double*>(slot);
+    return SlotView{T, T + words, T + words + npad};
+}
+
+unsigned copy_blocks(size_t pairs) {
+    const size_t want = lp_ceil_div(pairs, (size_t)kCopyThreads);
+    return (unsigned)(want < kCopyBlocks ? want : kCopyBlocks);
+}
+
+u64 bits_of(double v) {
+    u64 w;
+    std::memcpy(&w, &v, sizeof(w));
+    return w;
+}
+
+}  // namespace
+
+void lp_mip_large_save(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, char* slot,
+                       const MipLargeResult& r) {
+    const SimplexDev& d = p->dev;
+    const SlotView sv = slot_view(p, slot);
+    const size_t pairs = ((size_t)d.m + 1) * (size_t)d.ld / 2;
+    const size_t patch = (size_t)r.t * (size_t)d.ld + (size_t)d.n;
+    hipLaunchKernelGGL(k_mipl_save, copy_blocks(pairs), kCopyThreads, 0, p->ctx->stream,
+                       reinterpret_cast<const ulonglong2*>(d.T), reinterpret_cast<ulonglong2*>(sv.T), pairs, patch,
+                       bits_of(r.xb_before), reinterpret_cast<const u64*>(bd.U), reinterpret_cast<const u64*>(md.lo),
+                       reinterpret_cast<u64*>(sv.U), reinterpret_cast<u64*>(sv.lo), d.n, r.j, bits_of(r.U_before),
+                       bits_of(r.lo_before));
+}
+
+void lp_mip_large_second_child(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, char* slot,
+                               int level, int j, double v, int down) {
+    const SimplexDev& d = p->dev;
+    const SlotView sv = slot_view(p, slot);
+    const size_t pairs = ((size_t)d.m + 1) * (size_t)d.ld / 2;
+    hipLaunchKernelGGL(k_mipl_restore, copy_blocks(pairs), kCopyThreads, 0, p->ctx->stream,
+                       reinterpret_cast<const ulonglong2*>(sv.T), reinterpret_cast<ulonglong2*>(d.T), pairs,
+                       reinterpret_cast<const u64*>(sv.U), reinterpret_cast<const u64*>(sv.lo),
+                       reinterpret_cast<u64*>(bd.U), reinterpret_cast<u64*>(md.lo),
+                       (const int*)(md.rec_up + (size_t)level * d.n), bd.up, d.nonbasic, d.n,
+                       (const int*)(md.rec_basis + (size_t)level * d.m), d.basis, d.m);
+    hipLaunchKernelGGL(k_mipl_second_child, 1, kNodeThreads, 0, p->ctx->stream, d, bd, md, j, v, down);
 }

@@ -1,7 +1,9 @@
 // simplex_bounded_driver.hip — the host side of the bounded-variable simplex on the tableau in HBM, for LPs beyond one
 // workgroup's LDS: lp_simplex_bounded_large, lp_simplex_bounded_resolve_large (both also as _ex under a pivot rule, the
-// re-solve as _dual_ex under a dual pricing rule too) and lp_mip_bounded_solve_large.  The selectors are simplex_bounded_launch.hip's, the search's kernels
+// re-solve as _dual_ex under a dual pricing rule too) and lp_mip_bounded_solve_large (as _ex with tableau snapshots for
+// the second children).  The selectors are simplex_bounded_launch.hip's, the search's kernels
 // mip_bounded_large.hip's; the problem record, the upload and the two-phase pieces are simplex_driver.hip's.
+#include <algorithm>
 #include <cmath>
 
 #include "batched_problem.hpp"   // lp_mip_check_search, LP_MIP_BOUNDED_MAX_DEPTH
@@ -147,7 +149,8 @@ void bounded_large_outputs(int rc, int m, int n, int n_orig, const double* c, co
 
 // ---- the pieces of lp_mip_bounded_solve_large.  What lives for one call: the pinned result, the problem record, one
 // device allocation (A, b, c and the mask, the bound state, the node's lo and vertex, the incumbent, the records' bases
-// and flags) and what an install needs of the arguments.
+// and flags), the snapshot slots (one allocation each, made when the search first writes the slot) and what an install
+// needs of the arguments.
 struct MipLargeCall {
     struct Pinned {
         MipLargeResult* ptr = nullptr;
@@ -155,6 +158,8 @@ struct MipLargeCall {
     } pinned;   // (declared first: freed after the device buffers, whose hipFree waits for the queued kernels)
     ProblemOwner owner{nullptr, lp_simplex_free};
     lp_device_buffer buf;   // (freed before the problem on every return path)
+    std::vector<lp_device_buffer> slots;   // the ring of lp_mip_bounded_solve_large_ex (freed before buf)
+    std::vector<int> slot_level;           // the level a slot belongs to, -1: none
     BoundedLargeDev bd{};
     MipLargeDev md{};
     const double *A = nullptr, *c = nullptr;   // the caller's: the identity scan of an install reads them
@@ -211,6 +216,210 @@ int mip_large_verdict(const std::vector<MipRecord>& rec, int top, int stop, int 
     if (stop != LP_OPTIMAL) return stop;
     if (found) return (have_ab && mip_beats(maximize, zab, zstar, gap)) ? LP_ITER_LIMIT : LP_OPTIMAL;
     return have_ab ? LP_ITER_LIMIT : LP_INFEASIBLE;
+}
+
+// Depth-first branch-and-bound over the bounds on the HBM tableau (tests/ref/mip_bounded_ref.c is the definition; the
+// kernels are mip_bounded_large.hip's).  The host drives the search and keeps what is O(depth): j, v, z and the sides of
+// the records, the incumbent's objective, the counters.  A, b and c go up once; the tableau, the bound state, the node's
+// lo, the incumbent and the records' bases and flags stay on the device.  A node that ended LP_OPTIMAL costs one launch
+// of the node kernel and one sync; its first child continues on the live tableau with the bounded dual loop (no crash);
+// a second child is staged on the device from the persistent A and installed by lp_simplex_install.
+// With snapshots = K > 0 (tests/ref/mip_bounded_snapshots_ref.c): a node that branches at level L and dives is saved, as
+// it stood before the dive's bound change, in slot L mod K' (K' = min(K, max_depth): L < max_depth, so the slot and
+// whether it survives are those of L mod K); a second child whose slot still belongs to its level is restored from it
+// and continues like a first child, with one sync for its bound change and none of the rebuild's work.
+// stats_out: nstats entries, 5 (the counters of the reference) or 7 (then the second children restored and rebuilt).
+int mip_large_search(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                     const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig,
+                     const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes,
+                     int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
+                     int nstats, int snapshots) {
+    const char* who = "lp_mip_bounded_solve_large";
+    const bool any_null = !x_out || !obj_out || !bound_out || !found_out || !stats_out || !A || !b || !c || !lo || !hi ||
+                          !basis_in || !at_upper_in || !integer;
+    // step 1: the entry and the start as the re-solve, the search's own arguments, integral bounds on the marked columns
+    int rc = check_bounded_entry(ctx, who, LP_PIVOT_DANTZIG, any_null, eps, m, n, n_orig, lo, hi);
+    if (rc) return rc;
+    rc = check_bounded_start(ctx, who, n, m, hi, basis_in, at_upper_in);
+    if (rc) return rc;
+    rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_BOUNDED_MAX_DEPTH, max_nodes);
+    if (rc) return rc;
+    for (int j = 0; j < n_orig; ++j)
+        if (integer[j] && (lo[j] != std::floor(lo[j]) || (std::isfinite(hi[j]) && hi[j] != std::floor(hi[j]))))
+            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": an integer column has a fractional bound");
+    // ---- the problem record, the selectors' LDS (m <= 9960), the call's allocations and the four uploads (queued)
+    MipLargeCall k;
+    lp_simplex_problem* p = nullptr;
+    rc = lp_simplex_alloc(ctx, m, n, nullptr, maximize, n, &p);
+    if (rc) return rc;
+    k.owner.reset(p);
+    rc = lp_bounded_large_prepare(p, LP_PIVOT_DANTZIG);
+    if (rc) return rc;
+    rc = lp_bounded_dual_prepare(p);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    BoundedLargeDev& bd = k.bd;
+    MipLargeDev& md = k.md;
+    double *dA = nullptr, *db = nullptr, *dc = nullptr;   // (md's own pointers to them are const)
+    int* dmask = nullptr;
+    LP_HIP(ctx, lp_carve_malloc(&k.buf.ptr, [&](lp_carver& cv) {
+        dA = cv.take<double>(sizeof(double) * (size_t)m * n);
+        db = cv.take<double>(sizeof(double) * (size_t)m);
+        dc = cv.take<double>(sizeof(double) * (size_t)n);
+        bd.U = cv.take<double>(sizeof(double) * (size_t)n);
+        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
+        md.lo = cv.take<double>(sizeof(double) * (size_t)n);
+        md.x = cv.take<double>(sizeof(double) * (size_t)n);
+        md.xinc = cv.take<double>(sizeof(double) * (size_t)n_orig);
+        bd.up = cv.take<int>(sizeof(int) * (size_t)n);
+        bd.flips = cv.take<int>(sizeof(int));
+        dmask = cv.take<int>(sizeof(int) * (size_t)n);
+        md.rec_basis = cv.take<int>(sizeof(int) * (size_t)max_depth * m);
+        md.rec_up = cv.take<int>(sizeof(int) * (size_t)max_depth * n);
+    }));
+    LP_HIP(ctx, hipHostMalloc(&k.pinned.ptr, sizeof(MipLargeResult)));
+    md.A = dA; md.b = db; md.c = dc; md.integer = dmask; md.result = k.pinned.ptr;
+    md.n_orig = n_orig; md.max_depth = max_depth; md.int_tol = int_tol; md.gap = gap;
+    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    LP_HIP(ctx, hipMemcpyAsync(dmask, integer, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+    k.A = A; k.c = c; k.eps = eps; k.max_iter = max_iter;
+    const int K = std::min(snapshots, max_depth);
+    const size_t slot_bytes = lp_mip_large_slot_bytes(m, n);
+    k.slots = std::vector<lp_device_buffer>((size_t)K);
+    k.slot_level.assign((size_t)K, -1);
+
+    int stats[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < n_orig; ++j) x_out[j] = NAN;
+    *obj_out = NAN;
+    *bound_out = NAN;
+    *found_out = 0;
+
+    std::vector<MipRecord> rec((size_t)max_depth);
+    std::vector<double> lov((size_t)n), hiv((size_t)n);
+    std::vector<int> N((size_t)m), up((size_t)n);
+
+    // ---- root
+    int st = mip_large_install(k, who, lo, hi, basis_in, at_upper_in, stats);
+    if (st < 0) return st;
+    stats[0] = 1;
+    int status = st;
+    if (st != LP_OPTIMAL) {
+        if (st == LP_UNBOUNDED || st == LP_ITER_LIMIT) *bound_out = maximize ? INFINITY : -INFINITY;
+    } else {
+        int L = 0, top = -1, found = 0, stop = LP_OPTIMAL, have_ab = 0;
+        double zstar = 0.0, zab = 0.0;
+        for (;;) {
+            bool backtrack = true;
+            if (st == LP_OPTIMAL) {
+                // steps 3 to 5 on the device; a node is counted before it starts, so the dive waits for the budget
+                const int dive = stats[0] < max_nodes;
+                lp_mip_large_node(p, bd, md, L, found, zstar, dive);
+                LP_HIP(ctx, hipStreamSynchronize(s));
+                LP_HIP(ctx, hipGetLastError());
+                const MipLargeResult r = *k.pinned.ptr;
+                if (r.what == LP_MIPL_INTEGRAL) {
+                    found = 1;
+                    zstar = r.z;
+                } else if (r.what == LP_MIPL_ABANDONED) {
+                    if (!have_ab || mip_beats(maximize, r.z, zab, 0.0)) zab = r.z;
+                    have_ab = 1;
+                } else if (r.what == LP_MIPL_BRANCHED || r.what == LP_MIPL_NOT_BASIC) {
+                    rec[(size_t)L] = MipRecord{r.j, (r.v - std::floor(r.v)) <= 0.5, 0, r.v, r.z};
+                    top = L;
+                    if (!dive) { stop = LP_ITER_LIMIT; break; }
+                    if (r.what == LP_MIPL_NOT_BASIC) { stop = LP_BAD_ARG; break; }
+                    if (K > 0) {   // step 4': the node as it stood before the bound change, into slot L mod K
+                        lp_device_buffer& slot = k.slots[(size_t)(L % K)];
+                        if (!slot.ptr) {
+                            const hipError_t e = hipMalloc(&slot.ptr, slot_bytes);
+                            if (e != hipSuccess) {
+                                (void)hipGetLastError();
+                                LP_FAIL(ctx, -(int)e, std::string(who) + ": a snapshot slot: " + hipGetErrorString(e));
+                            }
+                        }
+                        k.slot_level[(size_t)(L % K)] = L;
+                        lp_mip_large_save(p, bd, md, slot.ptr, r);
+                    }
+                    ++L;
+                    ++stats[0];
+                    if (L > stats[4]) stats[4] = L;
+                    if (r.un_negative) {
+                        st = LP_INFEASIBLE;   // without a pivot
+                    } else {
+                        int iters = 0, flips = 0;
+                        st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+                        if (st < 0) return st;
+                        stats[1] += iters;
+                    }
+                    backtrack = false;
+                }
+            } else if (st != LP_INFEASIBLE) {
+                stop = st;
+                break;
+            }
+            if (!backtrack) continue;
+            while (top >= 0 && rec[(size_t)top].second_taken) --top;
+            if (top < 0) break;
+            rec[(size_t)top].second_taken = 1;
+            if (stats[0] >= max_nodes) { stop = LP_ITER_LIMIT; break; }
+            L = top + 1;
+            if (K > 0 && k.slot_level[(size_t)(top % K)] == top) {
+                // ---- step 6': the second child from the snapshot of its level, the other side
+                const MipRecord& R = rec[(size_t)top];
+                k.slot_level[(size_t)(top % K)] = -1;
+                ++stats[0];
+                ++stats[5];
+                if (L > stats[4]) stats[4] = L;
+                lp_mip_large_second_child(p, bd, md, k.slots[(size_t)(top % K)].ptr, top, R.j, R.v, !R.first_down);
+                LP_HIP(ctx, hipStreamSynchronize(s));
+                LP_HIP(ctx, hipGetLastError());
+                const MipLargeResult r = *k.pinned.ptr;
+                if (r.what == LP_MIPL_NOT_BASIC) { stop = LP_BAD_ARG; break; }
+                if (r.un_negative) {
+                    st = LP_INFEASIBLE;   // without a pivot
+                } else {
+                    int iters = 0, flips = 0;
+                    st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+                    if (st < 0) return st;
+                    stats[1] += iters;
+                }
+                continue;
+            }
+            // ---- the second child of record `top`: the root's bounds overlaid in level order, the recorded start
+            ++stats[6];
+            std::memcpy(lov.data(), lo, sizeof(double) * (size_t)n);
+            std::memcpy(hiv.data(), hi, sizeof(double) * (size_t)n);
+            for (int l = 0; l < L; ++l) {
+                const MipRecord& R = rec[(size_t)l];
+                const int down = R.second_taken ? !R.first_down : R.first_down;
+                if (down) hiv[(size_t)R.j] = std::floor(R.v);
+                else lov[(size_t)R.j] = std::ceil(R.v);
+            }
+            rc = lp_download(ctx, who, {{N.data(), md.rec_basis + (size_t)top * m, sizeof(int) * (size_t)m},
+                                        {up.data(), md.rec_up + (size_t)top * n, sizeof(int) * (size_t)n}});
+            if (rc) return rc;
+            ++stats[0];
+            if (L > stats[4]) stats[4] = L;
+            st = mip_large_install(k, who, lov.data(), hiv.data(), N.data(), up.data(), stats);
+            if (st < 0) return st;
+        }
+        // ---- status and bound (step 8)
+        double bound = NAN;
+        status = mip_large_verdict(rec, top, stop, found, have_ab, zab, zstar, gap, maximize, &bound);
+        if (found) {
+            rc = lp_download(ctx, who, {{x_out, md.xinc, sizeof(double) * (size_t)n_orig}});
+            if (rc) return rc;
+            *found_out = 1;
+            *obj_out = zstar;
+        }
+        *bound_out = bound;
+    }
+    std::memcpy(stats_out, stats, sizeof(int) * (size_t)nstats);
+    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
+    if (status == LP_SINGULAR) ctx->last_error = std::string(who) + ": the basis matrix is singular";
+    return status;
 }
 
 }  // namespace
@@ -395,164 +604,37 @@ int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, i
     return rc;
 }
 
-// Depth-first branch-and-bound over the bounds on the HBM tableau (tests/ref/mip_bounded_ref.c is the definition; the
-// kernels are mip_bounded_large.hip's).  The host drives the search and keeps what is O(depth): j, v, z and the sides of
-// the records, the incumbent's objective, the counters.  A, b and c go up once; the tableau, the bound state, the node's
-// lo, the incumbent and the records' bases and flags stay on the device.  A node that ended LP_OPTIMAL costs one launch
-// of the node kernel and one sync; its first child continues on the live tableau with the bounded dual loop (no crash);
-// a second child is staged on the device from the persistent A and installed by lp_simplex_install.
+// The search beyond LDS (mip_large_search above): the definition is tests/ref/mip_bounded_ref.c.
 int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                                const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
                                int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
                                int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
                                double* bound_out, int* found_out, int* stats_out) {
-    const char* who = "lp_mip_bounded_solve_large";
-    const bool any_null = !x_out || !obj_out || !bound_out || !found_out || !stats_out || !A || !b || !c || !lo || !hi ||
-                          !basis_in || !at_upper_in || !integer;
-    // step 1: the entry and the start as the re-solve, the search's own arguments, integral bounds on the marked columns
-    int rc = check_bounded_entry(ctx, who, LP_PIVOT_DANTZIG, any_null, eps, m, n, n_orig, lo, hi);
-    if (rc) return rc;
-    rc = check_bounded_start(ctx, who, n, m, hi, basis_in, at_upper_in);
-    if (rc) return rc;
-    rc = lp_mip_check_search(ctx, who, n, n_orig, integer, int_tol, gap, max_depth, LP_MIP_BOUNDED_MAX_DEPTH, max_nodes);
-    if (rc) return rc;
-    for (int j = 0; j < n_orig; ++j)
-        if (integer[j] && (lo[j] != std::floor(lo[j]) || (std::isfinite(hi[j]) && hi[j] != std::floor(hi[j]))))
-            LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": an integer column has a fractional bound");
-    // ---- the problem record, the selectors' LDS (m <= 9960), the call's allocations and the four uploads (queued)
-    MipLargeCall k;
-    lp_simplex_problem* p = nullptr;
-    rc = lp_simplex_alloc(ctx, m, n, nullptr, maximize, n, &p);
-    if (rc) return rc;
-    k.owner.reset(p);
-    rc = lp_bounded_large_prepare(p, LP_PIVOT_DANTZIG);
-    if (rc) return rc;
-    rc = lp_bounded_dual_prepare(p);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    BoundedLargeDev& bd = k.bd;
-    MipLargeDev& md = k.md;
-    double *dA = nullptr, *db = nullptr, *dc = nullptr;   // (md's own pointers to them are const)
-    int* dmask = nullptr;
-    LP_HIP(ctx, lp_carve_malloc(&k.buf.ptr, [&](lp_carver& cv) {
-        dA = cv.take<double>(sizeof(double) * (size_t)m * n);
-        db = cv.take<double>(sizeof(double) * (size_t)m);
-        dc = cv.take<double>(sizeof(double) * (size_t)n);
-        bd.U = cv.take<double>(sizeof(double) * (size_t)n);
-        bd.q = cv.take<double>(sizeof(double) * (size_t)p->dev.ld);
-        md.lo = cv.take<double>(sizeof(double) * (size_t)n);
-        md.x = cv.take<double>(sizeof(double) * (size_t)n);
-        md.xinc = cv.take<double>(sizeof(double) * (size_t)n_orig);
-        bd.up = cv.take<int>(sizeof(int) * (size_t)n);
-        bd.flips = cv.take<int>(sizeof(int));
-        dmask = cv.take<int>(sizeof(int) * (size_t)n);
-        md.rec_basis = cv.take<int>(sizeof(int) * (size_t)max_depth * m);
-        md.rec_up = cv.take<int>(sizeof(int) * (size_t)max_depth * n);
-    }));
-    LP_HIP(ctx, hipHostMalloc(&k.pinned.ptr, sizeof(MipLargeResult)));
-    md.A = dA; md.b = db; md.c = dc; md.integer = dmask; md.result = k.pinned.ptr;
-    md.n_orig = n_orig; md.max_depth = max_depth; md.int_tol = int_tol; md.gap = gap;
-    LP_HIP(ctx, hipMemcpyAsync(dA, A, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    LP_HIP(ctx, hipMemcpyAsync(dmask, integer, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-    k.A = A; k.c = c; k.eps = eps; k.max_iter = max_iter;
+    return mip_large_search(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, integer, eps, int_tol,
+                            gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, 5, 0);
+}
 
-    int stats[5] = {0, 0, 0, 0, 0};
-    for (int j = 0; j < n_orig; ++j) x_out[j] = NAN;
-    *obj_out = NAN;
-    *bound_out = NAN;
-    *found_out = 0;
+// The same with up to `snapshots` tableau snapshots (tests/ref/mip_bounded_snapshots_ref.c): 0 launches what the entry
+// above launches.
+int lp_mip_bounded_solve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                  const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                                  int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
+                                  int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
+                                  double* bound_out, int* found_out, int* stats_out, int snapshots) {
+    if (!ctx) return LP_BAD_ARG;
+    if (snapshots < 0 || snapshots > LP_MIP_BOUNDED_MAX_SNAPSHOTS)
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_large: snapshots outside [0, 1024]");
+    return mip_large_search(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, integer, eps, int_tol,
+                            gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, 7,
+                            snapshots);
+}
 
-    std::vector<MipRecord> rec((size_t)max_depth);
-    std::vector<double> lov((size_t)n), hiv((size_t)n);
-    std::vector<int> N((size_t)m), up((size_t)n);
-
-    // ---- root
-    int st = mip_large_install(k, who, lo, hi, basis_in, at_upper_in, stats);
-    if (st < 0) return st;
-    stats[0] = 1;
-    int status = st;
-    if (st != LP_OPTIMAL) {
-        if (st == LP_UNBOUNDED || st == LP_ITER_LIMIT) *bound_out = maximize ? INFINITY : -INFINITY;
-    } else {
-        int L = 0, top = -1, found = 0, stop = LP_OPTIMAL, have_ab = 0;
-        double zstar = 0.0, zab = 0.0;
-        for (;;) {
-            bool backtrack = true;
-            if (st == LP_OPTIMAL) {
-                // steps 3 to 5 on the device; a node is counted before it starts, so the dive waits for the budget
-                const int dive = stats[0] < max_nodes;
-                lp_mip_large_node(p, bd, md, L, found, zstar, dive);
-                LP_HIP(ctx, hipStreamSynchronize(s));
-                LP_HIP(ctx, hipGetLastError());
-                const MipLargeResult r = *k.pinned.ptr;
-                if (r.what == LP_MIPL_INTEGRAL) {
-                    found = 1;
-                    zstar = r.z;
-                } else if (r.what == LP_MIPL_ABANDONED) {
-                    if (!have_ab || mip_beats(maximize, r.z, zab, 0.0)) zab = r.z;
-                    have_ab = 1;
-                } else if (r.what == LP_MIPL_BRANCHED || r.what == LP_MIPL_NOT_BASIC) {
-                    rec[(size_t)L] = MipRecord{r.j, (r.v - std::floor(r.v)) <= 0.5, 0, r.v, r.z};
-                    top = L;
-                    if (!dive) { stop = LP_ITER_LIMIT; break; }
-                    if (r.what == LP_MIPL_NOT_BASIC) { stop = LP_BAD_ARG; break; }
-                    ++L;
-                    ++stats[0];
-                    if (L > stats[4]) stats[4] = L;
-                    if (r.un_negative) {
-                        st = LP_INFEASIBLE;   // without a pivot
-                    } else {
-                        int iters = 0, flips = 0;
-                        st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
-                        if (st < 0) return st;
-                        stats[1] += iters;
-                    }
-                    backtrack = false;
-                }
-            } else if (st != LP_INFEASIBLE) {
-                stop = st;
-                break;
-            }
-            if (!backtrack) continue;
-            while (top >= 0 && rec[(size_t)top].second_taken) --top;
-            if (top < 0) break;
-            rec[(size_t)top].second_taken = 1;
-            if (stats[0] >= max_nodes) { stop = LP_ITER_LIMIT; break; }
-            // ---- the second child of record `top`: the root's bounds overlaid in level order, the recorded start
-            L = top + 1;
-            std::memcpy(lov.data(), lo, sizeof(double) * (size_t)n);
-            std::memcpy(hiv.data(), hi, sizeof(double) * (size_t)n);
-            for (int l = 0; l < L; ++l) {
-                const MipRecord& R = rec[(size_t)l];
-                const int down = R.second_taken ? !R.first_down : R.first_down;
-                if (down) hiv[(size_t)R.j] = std::floor(R.v);
-                else lov[(size_t)R.j] = std::ceil(R.v);
-            }
-            rc = lp_download(ctx, who, {{N.data(), md.rec_basis + (size_t)top * m, sizeof(int) * (size_t)m},
-                                        {up.data(), md.rec_up + (size_t)top * n, sizeof(int) * (size_t)n}});
-            if (rc) return rc;
-            ++stats[0];
-            if (L > stats[4]) stats[4] = L;
-            st = mip_large_install(k, who, lov.data(), hiv.data(), N.data(), up.data(), stats);
-            if (st < 0) return st;
-        }
-        // ---- status and bound (step 8)
-        double bound = NAN;
-        status = mip_large_verdict(rec, top, stop, found, have_ab, zab, zstar, gap, maximize, &bound);
-        if (found) {
-            rc = lp_download(ctx, who, {{x_out, md.xinc, sizeof(double) * (size_t)n_orig}});
-            if (rc) return rc;
-            *found_out = 1;
-            *obj_out = zstar;
-        }
-        *bound_out = bound;
-    }
-    std::memcpy(stats_out, stats, sizeof(stats));
-    if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
-    if (status == LP_SINGULAR) ctx->last_error = std::string(who) + ": the basis matrix is singular";
-    return status;
+// The device bytes `snapshots` slots take at m x n: each the (m+1) x ld tableau (ld = n + 1 rounded up to 8) and two
+// vectors of n doubles rounded up to 2.  A host call.
+int lp_mip_bounded_snapshot_bytes(int m, int n, int snapshots, unsigned long long* bytes_out) {
+    if (!bytes_out || m <= 0 || n < m || snapshots < 0 || snapshots > LP_MIP_BOUNDED_MAX_SNAPSHOTS) return LP_BAD_ARG;
+    *bytes_out = (unsigned long long)snapshots * (unsigned long long)lp_mip_large_slot_bytes(m, n);
+    return LP_OPTIMAL;
 }
 
 }  // extern "C"

@@ -186,9 +186,11 @@ struct MipLargeResult {
     int what;          // LP_MIPL_*
     int j;             // the branching column (BRANCHED, NOT_BASIC)
     int un_negative;   // BRANCHED with the dive applied: the first child's new width U' is < 0
-    int pad;
+    int t;             // BRANCHED with the dive applied: the basis position of j, else -1
     double z;          // the node's objective
     double v;          // x_j of the branching column
+    double xb_before, U_before, lo_before;   // BRANCHED with the dive applied: xB_t, U_j and lo_j as the bound change
+                                             // found them (what a snapshot of the node holds in their place)
 };
 struct MipLargeDev {
     const double* A;        // m x n column-major, b (m), c (n): uploaded once per call
@@ -210,6 +212,18 @@ void lp_mip_large_stage(lp_simplex_problem* p, const BoundedLargeDev& bd, const 
 // the first child's bound change when the node branches.  Queued; md.result is valid after the next stream sync.
 void lp_mip_large_node(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, int L, int found,
                        double zstar, int dive);
+// Snapshots (lp_mip_bounded_solve_large_ex; tests/ref/mip_bounded_snapshots_ref.c steps 4' and 6').  A slot holds the
+// (m+1) x ld tableau, then U and the node's lo (n doubles each, padded to 16 bytes): slot_bytes of device memory,
+// 16-byte aligned.  The basis and the flags of its level are the record's (rec_basis, rec_up).
+size_t lp_mip_large_slot_bytes(int m, int n);
+// Queued: the live state into `slot` with the three values of r (the node kernel's LP_MIPL_BRANCHED result, dive
+// applied) in place of the live ones, so the slot holds the node as it stood before the dive's bound change.
+void lp_mip_large_save(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, char* slot,
+                       const MipLargeResult& r);
+// Queued: `slot` and the record of `level` back into the live state, then step 5 for column j of value v to the side
+// `down`.  md.result is valid after the next stream sync: LP_MIPL_BRANCHED with un_negative, or LP_MIPL_NOT_BASIC.
+void lp_mip_large_second_child(lp_simplex_problem* p, const BoundedLargeDev& bd, const MipLargeDev& md, char* slot,
+                               int level, int j, double v, int down);
 
 // simplex_lookahead.hip: J pivots per select + rank-J-update launch pair
 int lp_lookahead_pick_j(int m, int n);          // the shape test: 0 = the selector does not fit LDS

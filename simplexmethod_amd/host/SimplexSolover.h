@@ -189,6 +189,7 @@ public:
         double objective = std::numeric_limits<double>::quiet_NaN();
         double bound = std::numeric_limits<double>::quiet_NaN();
         int nodes = 0;
+        int restored = 0, rebuilt = 0;   // boundedBranchAndBoundLarge with snapshots: second children by kind
     };
     static constexpr double INT_TOL = 1e-6;
     static constexpr double MIP_GAP = 1e-9;
@@ -394,6 +395,24 @@ public:
                                              const std::vector<double>& hi, const BoundedResult& from,
                                              int maxDepth = 64, int maxNodes = 100000) const {
         return boundedSearch("Solver::boundedBranchAndBoundLarge", integer, lo, hi, from, maxDepth, maxNodes, true);
+    }
+
+    // The same with up to `snapshots` tableau snapshots in device memory (lp_mip_bounded_solve_large_ex, snapshots in
+    // [0, 1024], else std::invalid_argument): a second child whose level's snapshot is still there starts from its
+    // parent's final tableau like a first child instead of being rebuilt.  restored and rebuilt count the second
+    // children by kind.  Status, found and nodes are those of the forms above; the objective agrees to rounding.
+    IntegerResult boundedBranchAndBoundLarge(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                             const std::vector<double>& hi, int maxDepth, int maxNodes,
+                                             int snapshots) const {
+        return boundedBranchAndBoundLarge(integer, lo, hi, boundedSimplexLarge(lo, hi, false), maxDepth, maxNodes,
+                                          snapshots);
+    }
+
+    IntegerResult boundedBranchAndBoundLarge(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                             const std::vector<double>& hi, const BoundedResult& from, int maxDepth,
+                                             int maxNodes, int snapshots) const {
+        return boundedSearch("Solver::boundedBranchAndBoundLarge", integer, lo, hi, from, maxDepth, maxNodes, true,
+                             snapshots);
     }
 
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
@@ -770,10 +789,11 @@ private:
         return out;
     }
 
-    // boundedBranchAndBound, or with large boundedBranchAndBoundLarge, from a result's basis and flags
+    // boundedBranchAndBound, or with large boundedBranchAndBoundLarge, from a result's basis and flags; snapshots >= 0
+    // (large only): the _ex entry with that many snapshots
     IntegerResult boundedSearch(const char* who, const std::vector<bool>& integer, const std::vector<double>& lo,
                                 const std::vector<double>& hi, const BoundedResult& from, int maxDepth, int maxNodes,
-                                bool large) const {
+                                bool large, int snapshots = -1) const {
         const View p = view();
         IntegerResult out = blankIntegerResult(from.status, p.no);
         if (from.status != LP_OPTIMAL) return out;
@@ -782,13 +802,23 @@ private:
         requireStart(who, "start", p, from);
         const std::vector<int> mask(integer.begin(), integer.end());
         lp_context* ctx = lpgpu::context(_device);
-        int found = 0, stats[5] = {0, 0, 0, 0, 0};
-        const auto entry = large ? lp_mip_bounded_solve_large : lp_mip_bounded_solve;
-        out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
-                                   from.atUpper.data(), p.maximize, p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth,
-                                   maxNodes, MAX_ITER, out.x.data(), &out.objective, &out.bound, &found, stats), ctx);
+        int found = 0, stats[7] = {0, 0, 0, 0, 0, 0, 0};
+        if (large && snapshots >= 0) {
+            out.status = checked(lp_mip_bounded_solve_large_ex(
+                ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(), from.atUpper.data(), p.maximize,
+                p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER, out.x.data(), &out.objective,
+                &out.bound, &found, stats, snapshots), ctx);
+        } else {
+            const auto entry = large ? lp_mip_bounded_solve_large : lp_mip_bounded_solve;
+            out.status = checked(entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(),
+                                       from.atUpper.data(), p.maximize, p.no, mask.data(), EPS, INT_TOL, MIP_GAP,
+                                       maxDepth, maxNodes, MAX_ITER, out.x.data(), &out.objective, &out.bound, &found,
+                                       stats), ctx);
+        }
         out.found = found != 0;
         out.nodes = stats[0];
+        out.restored = stats[5];
+        out.rebuilt = stats[6];
         return out;
     }
 
