@@ -273,6 +273,13 @@ int lp_batched_set_pivot_rule(lp_batched_problem* p, int pivot_rule);
  * else 0.  A batch that runs one LP per workgroup under the other rules and has 0 here returns LP_BAD_ARG
  * from lp_batched_run under Devex; batches that go LP by LP anyway are not concerned.               */
 int lp_batched_devex_fits(int m, int n, int two_phase);
+/* The kernel form a plain m x n batch takes under LP_PIVOT_DANTZIG when it runs one LP per workgroup (host
+ * arithmetic only: no context, no device).  out = {threads, rows_per_thread, aligned, dreg} of the
+ * register-resident kernel: its workgroup size, its row array per updating thread, 1 if the columns are
+ * assigned wave by wave with a wave of its own for xB, 1 if wave 0 keeps the reduced costs in registers; or
+ * threads = 0 (all four zero) for the LDS tableau.  Returns 1 if the condensed tableau fits the
+ * one-LP-per-workgroup path at all (n > m and (m+1) x (n-m+1) doubles within one CU's LDS), else 0 with out zeroed. */
+int lp_batched_form(int m, int n, int out[4]);
 /* BASELINE.json configs[4] "1 -> 8 GPUs": the LPs of a batch are independent, so participant `shard`
  * of `shards` (one process or host thread per GPU) uploads and solves the LPs [*lo, *hi) of the batch
  * and nobody exchanges anything (replicas of the code, no collective; the caller concatenates the

@@ -79,6 +79,7 @@ SIGNATURES = {
                                               _ip, _ip, C.c_int]),
     "lp_batched_set_pivot_rule": (C.c_int, [_vp, C.c_int]),
     "lp_batched_devex_fits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "lp_batched_form": (C.c_int, [C.c_int, C.c_int, _ip]),
     "lp_batched_upload": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, C.c_int,
                                     C.c_int, C.POINTER(_vp)]),
     "lp_batched_run": (C.c_int, [_vp, C.c_double, C.c_int, _fp]),
@@ -407,7 +408,16 @@ def gen_lp(seed, m, n):
     return A, b, c, basis
 
 
-MAX_BREAKS = 64   # default bound on the breakpoints of a parametric path
+def batched_form(m, n):
+    """lp_batched_form: the kernel form a plain m x n batch takes under Dantzig's rule, without a device.
+    (fits, threads, rows_per_thread, aligned, dreg): fits says that the batch can run one LP per workgroup at all;
+    threads = 0 is the LDS tableau, otherwise the register-resident kernel's workgroup size, row array and layout."""
+    out = (C.c_int * 4)()
+    fits = load().lp_batched_form(m, n, out)
+    return (bool(fits), out[0], out[1], bool(out[2]), bool(out[3]))
+
+
+MAX_BREAKS = 64  # default bound on the breakpoints of a parametric path
 INT_TOL = 1e-6    # branch-and-bound defaults: integrality tolerance, pruning gap, depth and node limits
 GAP = 1e-9
 MAX_DEPTH = 32

@@ -153,6 +153,9 @@ __host__ __device__ inline int batched_reg_rpt(int m, int n) {   // rows per upd
     return (m + G - 1) / G;
 }
 
+// The reduced-cost row in wave 0's registers, four entries per lane: the kernel's choice and lp_batched_form's.
+__host__ __device__ inline bool batched_reg_dreg(int nn) { return nn <= 256; }
+
 // (NT = 512 asks for 4 waves per SIMD = two workgroups per CU: two LPs share a CU, and one LP's
 // one-wave scans run under the other's update)
 // DREG: wave 0 keeps the reduced-cost row in registers (12 more VGPRs: not in the 512-thread form,
@@ -225,6 +228,8 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 1) void k_batched_simplex_reg(B
     // read, two branches of the pivot-row scaling) took 3.6-4.3 k cycles for an update the others did in 2.0-2.3 k,
     // and the whole workgroup waited for them at the loop's barrier.
     const int CW = nn / 64;
+    // (lp_batched_form repeats this condition: behind a helper shared with it the kernel's registers were allocated
+    // differently.  Change both together.)
     const bool aligned = (nn % 64) == 0 && G * CW + 1 <= (NT - 64) / 64 && m <= 256;
     int j, g;
     bool upd;
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 1) void k_batched_simplex_reg(B
     // the reduced-cost row and the slots' keys in REGISTERS (entry lane + 64*q), so a pivot's pricing
     // reads no LDS but the pivot row; LDS drow[] then only carries the entering slot's value (the
     // -objective entry of the row is not kept: the objective is evaluated from the vertex on the host).
-    const bool dreg = DREG && nn <= 256;
+    const bool dreg = DREG && batched_reg_dreg(nn);
     double dv[4] = {0.0, 0.0, 0.0, 0.0};
     int kv[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
     if (wave == 0 && dreg) {
@@ -642,6 +647,40 @@ size_t lp_batched_devex_lds_bytes(int m, int n) {
     return (bytes + 15) & ~(size_t)15;
 }
 
+// The form of a plain batch under Dantzig's rule, for lp_batched_launch and lp_batched_form alike: the threads and the
+// row array of the register-resident kernel, or threads 0 for the LDS tableau.
+// Register-resident form, smallest row array that holds the shape.  Shapes with many rows per
+// thread take the 512-thread form first: two workgroups (two LPs) then share a CU and one LP's
+// one-wave scans run under the other's update (128 x 256: 3.24 ms against 3.63 ms for the
+// 1024-thread form and 4.02 ms for the LDS form).
+struct BatchedForm {
+    int threads, rpt;
+};
+static BatchedForm batched_form(int m, int n) {
+    const int rpt = batched_reg_rpt<1024>(m, n), rpt2 = batched_reg_rpt<512>(m, n);
+    if (rpt >= 1 && rpt <= 4) return {1024, 4};
+    if (rpt >= 1 && rpt <= 12) return {1024, 12};
+    if (rpt2 >= 1 && rpt2 <= 44) return {512, 44};
+    if (rpt >= 1 && rpt <= 20) return {1024, 20};
+    return {0, 0};
+}
+
+extern "C" int lp_batched_form(int m, int n, int out[4]) {
+    if (!out) return 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (m <= 0 || n <= m || lp_batched_lds_bytes(m, n, nullptr) > 160 * 1024) return 0;
+    const BatchedForm f = batched_form(m, n);
+    if (f.threads) {
+        const int nn = n - m, G = (f.threads - 64) / (nn + 1), CW = nn / 64;
+        out[0] = f.threads;
+        out[1] = f.rpt;
+        // (k_batched_simplex_reg's `aligned`, repeated: see there.  Change both together.)
+        out[2] = ((nn % 64) == 0 && G * CW + 1 <= (f.threads - 64) / 64 && m <= 256) ? 1 : 0;
+        out[3] = batched_reg_dreg(nn) ? 1 : 0;   // (every instantiation lp_batched_launch makes has DREG)
+    }
+    return 1;
+}
+
 int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule) {
     if (pivot_rule == LP_PIVOT_DEVEX) {   // the LDS form only, with the weights behind its carve
         const size_t shm = lp_batched_devex_lds_bytes(d.m, d.n);
@@ -665,15 +704,11 @@ int lp_batched_launch(lp_context* ctx, const BatchedDev& d, int pivot_rule) {
         LP_FAIL(ctx, LP_BAD_ARG, "LP_BATCHED_STAMPS=reg: the shape does not take the 512-thread register form");
     }
     if (!d.stamps) {
-        // Register-resident form, smallest row array that holds the shape.  Shapes with many rows per
-        // thread take the 512-thread form first: two workgroups (two LPs) then share a CU and one LP's
-        // one-wave scans run under the other's update (128 x 256: 3.24 ms against 3.63 ms for the
-        // 1024-thread form and 4.02 ms for the LDS form).
-        const int rpt = batched_reg_rpt<1024>(d.m, d.n), rpt2 = batched_reg_rpt<512>(d.m, d.n);
-        if (rpt >= 1 && rpt <= 4) return batched_reg_launch<1024, 4, true>(ctx, d);
-        if (rpt >= 1 && rpt <= 12) return batched_reg_launch<1024, 12, true>(ctx, d);
-        if (rpt2 >= 1 && rpt2 <= 44) return batched_reg_launch<512, 44, true>(ctx, d);
-        if (rpt >= 1 && rpt <= 20) return batched_reg_launch<1024, 20, true>(ctx, d);
+        const BatchedForm f = batched_form(d.m, d.n);
+        if (f.threads == 1024 && f.rpt == 4) return batched_reg_launch<1024, 4, true>(ctx, d);
+        if (f.threads == 1024 && f.rpt == 12) return batched_reg_launch<1024, 12, true>(ctx, d);
+        if (f.threads == 512 && f.rpt == 44) return batched_reg_launch<512, 44, true>(ctx, d);
+        if (f.threads == 1024 && f.rpt == 20) return batched_reg_launch<1024, 20, true>(ctx, d);
     }
     const size_t shm = lp_batched_lds_bytes(d.m, d.n, nullptr);
     if (d.stamps) {

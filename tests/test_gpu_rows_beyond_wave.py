@@ -52,8 +52,10 @@ def test_plain_batched(ctx, case, rule):
     """simplex_solve_batched and the batched_problem handle on seam_pairs, beyond_pairs and seam_mixed.  By lp_batched_launch's
     choice all three shapes run the register-resident rows under Dantzig's rule (100 x 150: 1024 threads, 12 rows per
     thread; 130 x 140: 1024 threads, 4 rows; 128 x 256: 512 threads, 44 rows), whose ratio test is
-    wave_ratio_select<2> for m <= 128 and <4> beyond; under Bland's and the Devex rule they run the LDS tableau
-    (wave_bland_ratio; wave_ratio_select<4> at every m <= 256)."""
+    wave_ratio_select<2> for m <= 128 and <4> up to 256; under Bland's and the Devex rule they run the LDS tableau
+    (wave_bland_ratio; wave_ratio_select<4> at every m <= 256).  These are three of the four register forms: the
+    fourth (1024 threads, 20 rows), the layouts and the ratio scan beyond m = 256 of all of them are
+    tests/test_gpu_batched_forms.py's."""
     m, n, eps = case
     G.check_batched(ctx, m, n, eps, R.seam_pairs, _pair_names(m, n), rule)
     G.check_batched(ctx, m, n, eps, R.beyond_pairs, _beyond_names(m, n), rule)
