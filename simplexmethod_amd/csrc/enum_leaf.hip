@@ -77,6 +77,23 @@ constexpr int THIN_TAIL = 9;
 #ifndef LP_LEAF_MASKED_2X2   // the 2x2 block's row choice: 1 = a row swap under the lane mask (nine 64-bit moves);
 #define LP_LEAF_MASKED_2X2 1 // diagnostic builds: 0 = twelve selects
 #endif
+// The head of a pass (profiles/enum_leaf_pass_head.json; each part measured and dropped alone):
+#ifndef LP_LEAF_COMB_AHEAD   // k_enum_leaves<3> / <0>: the subset-table word of the NEXT pass is loaded in front of the current
+#define LP_LEAF_COMB_AHEAD 1 // pass's verdicts, the first pass's in front of the shared pivot's copy rounds; 0 = at the head of its pass
+#endif
+#ifndef LP_LEAF_ASM_MINMAX   // the running min / max |pivot| of leaf_verdict and of table 1's shared pivots as v_min_f64 /
+#define LP_LEAF_ASM_MINMAX 1 // v_max_f64 themselves (no canonicalising v_max_f64 x, x in front of them); 0 = fmin / fmax
+#endif
+#ifndef LP_LEAF_WINDOW_CLAMP // k_enum_leaves<3> / <0>: the leaf loops' bounds are cut to [begin, end) once per loop and no lane
+#define LP_LEAF_WINDOW_CLAMP 1 // tests its rank; table 1 keeps its item's fields, the bounds of its groups and sub-groups and the
+#endif                       // window (as leaf indices of the group) in scalar registers; 0 = 64-bit vector arithmetic per lane
+#ifndef LP_LEAF_SCALAR_BASE  // the subset-table load as scalar base + 32-bit lane offset; 0 = a 64-bit address per lane
+#define LP_LEAF_SCALAR_BASE 1
+#endif
+// -DLP_LEAF_COMB_BOUND (diagnostic builds, WRONG RESULTS on purpose): every pass of k_enum_leaves<3>'s two loops takes the
+// subset-table word its lane loaded in front of the loop.  NOT the bound on LP_LEAF_COMB_AHEAD it was meant to be: the
+// word is then loop-invariant, and the compiler hoists the column addresses and part of the LDS reads out of the loop
+// (SQ_INSTS_VALU of the kernel -14 %); the look-ahead load itself is the measurement of what the load's round trip cost.
 // -DLP_LEAF_NO_ROTATE (diagnostic builds, WRONG RESULTS on purpose): the chosen row is taken to be row t — the pass
 // time without any rotation, the bound on what a cheaper rotation can return.
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
@@ -131,6 +148,78 @@ __device__ __forceinline__ double recip_midrange(double x) {
     return fma(fma(-x, r2, 1.0), r2, r2);
 }
 constexpr double kRecipLo = 0x1p-500, kRecipHi = 0x1p500;
+
+// fmin / fmax of leaf_verdict's running min / max |pivot| as the instruction itself.  fmin / fmax quiet a signalling NaN
+// operand first (v_max_f64 x, x) wherever the compiler cannot prove that none arrives, and it cannot for the loop-
+// invariant minp0 / maxp0 of the caller, for bigs1 (the result of an asm v_max_f64) or for a value that went through the
+// masked moves.  None can: minp0 / maxp0 are results of fmin / fmax over |tableau entries| in the level kernels and the
+// shared pivots (or the root's constants), every `big` is a v_max_f64 result, |an fma result| or the constant -1, and the
+// reciprocals are fma results — arithmetic never produces a signalling NaN.  On quiet NaNs, zeros and numbers the
+// instruction is fmin / fmax bit for bit (it is what they are lowered to).
+__device__ __forceinline__ double leaf_min(double a, double b) {
+#if LP_LEAF_ASM_MINMAX
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fmin(a, b);
+#endif
+}
+__device__ __forceinline__ double leaf_max(double a, double b) {
+#if LP_LEAF_ASM_MINMAX
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fmax(a, b);
+#endif
+}
+
+// The word at table[idx].  LP_LEAF_SCALAR_BASE: `table` is wave-uniform and held in scalar registers by the caller
+// (readfirstlane of its offset), the lane's part is a 32-bit byte offset (the tables are far below 4 GB) — the load
+// then takes the scalar-base form instead of a 64-bit address formed per lane.
+__device__ __forceinline__ unsigned comb_word(const unsigned* table, unsigned idx) {
+#if LP_LEAF_SCALAR_BASE
+    return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(table) + (size_t)(idx * 4u));
+#else
+    return table[idx];
+#endif
+}
+// A wave-uniform value that came out of memory or LDS, moved to scalar registers: what is computed from it is scalar
+// arithmetic, which does not take the vector slot.
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+}
+// The subsets [lo, hi) of a node whose subset 0 has rank rb, cut to the ranks inside [begin, end): hi <= lo if there is
+// none.  Every operand is wave-uniform; the bounds come back in scalar registers (LP_LEAF_WINDOW_CLAMP: once per leaf
+// loop, in place of two 64-bit compares and an add per lane and pass).  k_enum_leaves<0>'s form; table 1 states the
+// window once per group as leaf indices and cuts with 32-bit min / max (k_enum_leaves<3> below).
+__device__ __forceinline__ void clamp_to_window(unsigned long long rb, unsigned& lo, unsigned& hi, unsigned long long begin,
+                                                unsigned long long end) {
+#if LP_LEAF_WINDOW_CLAMP
+    const unsigned long long rbu = uniform64(rb);
+    const unsigned lou = (unsigned)__builtin_amdgcn_readfirstlane((int)lo), hiu = (unsigned)__builtin_amdgcn_readfirstlane((int)hi);
+    const unsigned long long a = rbu + lou, b = rbu + hiu;
+    const unsigned long long a2 = a > begin ? a : begin, b2 = b < end ? b : end;
+    lo = b2 > a2 ? (unsigned)(a2 - rbu) : lou;
+    hi = b2 > a2 ? (unsigned)(b2 - rbu) : lou;
+#endif
+}
+__device__ __forceinline__ unsigned uniform_len(unsigned len) {   // (a binomial out of LDS)
+#if LP_LEAF_WINDOW_CLAMP
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)len);
+#else
+    return len;
+#endif
+}
+__device__ __forceinline__ unsigned uniform_off(unsigned off) {
+#if LP_LEAF_SCALAR_BASE
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)off);
+#else
+    return off;
+#endif
+}
 
 // d[k] = s[k], k < N, in the lanes of `mask`; the other lanes keep d.  One 64-bit move per value under the lane mask
 // instead of two 32-bit selects: the mask is saved, narrowed and restored by scalar instructions, which do not take
@@ -389,8 +478,8 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         if constexpr (!FAST) {
             if (!(big > 0.0)) sing = true;
         }
-        minp = fmin(minp, big);
-        maxp = fmax(maxp, big);
+        minp = leaf_min(minp, big);
+        maxp = leaf_max(maxp, big);
         // rotate row p to position t (columns t..KD-1 and the rhs).  A select on a double is two v_cndmask_b32, and
         // every select of a row shares one condition: by default the rows move as 64-bit moves under the lane mask
         // (leaf_rotate_masked; profiles/enum_leaf_masked_rot.json), the select form stays behind LP_LEAF_MASKED_ROT 0
@@ -465,8 +554,8 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
     const double xb = rq * inv2;
     const double xa = fma(-pb, xb, ph) * inv1;
     if (!(big1 > 0.0) || !(big2 > 0.0)) sing = true;
-    minp = fmin(minp, fmin(big1, big2));
-    maxp = fmax(maxp, fmax(big1, big2));
+    minp = leaf_min(minp, fmin(big1, big2));
+    maxp = leaf_max(maxp, fmax(big1, big2));
     if (minp <= DBL_EPSILON * (double)m * maxp) sing = true;
     if constexpr (FAST) {
         maxinv = fmax(maxinv, fmax(fabs(inv1), fabs(inv2)));
@@ -964,7 +1053,10 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         ++wl_items;
 #endif
         // ---- item B becomes the current item: registers -> LDS slice (odd column stride)
-        const int chunk = chunkB, child = childB, roff = roffB, rec = recB;
+        // (table 1, LP_LEAF_WINDOW_CLAMP: the item's fields in scalar registers — the bounds of its groups and sub-groups
+        // and their cuts to [begin, end) below are then scalar arithmetic)
+        auto field = [](int v) { return (MODE >= 2 && LP_LEAF_WINDOW_CLAMP) ? __builtin_amdgcn_readfirstlane(v) : v; };
+        const int chunk = field(chunkB), child = field(childB), roff = field(roffB), rec = recB;
         const NodeMeta pm = pmB;
         double* tab = s_tab[wave * 2 + buf];
 #pragma unroll
@@ -989,6 +1081,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         // (one L2-resident load; a dependent unranking loop over binomials costs ~2k cycles)
         const unsigned* comb = pd.comb6 + s_off[MODE >= 2 ? 0 : R];
         unsigned long long rb = pm.rank_base + (unsigned long long)(FUSED ? roff : 0);
+        if (MODE >= 2 && LP_LEAF_WINDOW_CLAMP) rb = uniform64(rb);
         const unsigned int leaf_lo = (unsigned int)chunk;
         const unsigned int leaf_hi = (leaf_lo + width < L) ? leaf_lo + width : L;
         double minp0 = pm.minp, maxp0 = pm.maxp;
@@ -1070,20 +1163,40 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             // the unused rows in ascending original order, so "first row of largest |w|" keeps its meaning
             const int j2 = j2_first + gi;
             const int R2 = R - 1 - j2;                 // selectable columns of the depth m-5 node
-            const unsigned int L2 = s_binom[R2 * (KD + 1) + K5];
+            const unsigned int L2 = uniform_len(s_binom[R2 * (KD + 1) + K5]);
             const unsigned int lo2 = leaf_lo;          // (0 unless the item is a chunk of one large group)
             const unsigned int hi2 = (lo2 + width < L2) ? lo2 + width : L2;
             const unsigned long long rb2 = rb;
             rb += L2;                                  // next group of a packed item
-            if (overlap(rb2 + lo2, hi2 - lo2, begin, end) == 0ULL) continue;
+            // LP_LEAF_WINDOW_CLAMP: [begin, end) as leaf indices of this group, [wlo, whi) — saturated at 2^32 - 1, far
+            // beyond a group's C(21, 5) subsets — so that the cuts below are 32-bit scalar min / max
+            [[maybe_unused]] unsigned int wlo = 0u, whi = ~0u;
+            if (LP_LEAF_WINDOW_CLAMP) {
+                const unsigned long long rlo = begin > rb2 ? begin - rb2 : 0ULL, rhi = end > rb2 ? end - rb2 : 0ULL;
+                wlo = rlo < 0xFFFFFFFFULL ? (unsigned int)rlo : ~0u;
+                whi = rhi < 0xFFFFFFFFULL ? (unsigned int)rhi : ~0u;
+            }
+            // leaves [a, b) of the group, a < b, cut to the window (b <= a: none inside), and how many are inside
+            auto cut = [&](unsigned int& a, unsigned int& b) {
+                if (LP_LEAF_WINDOW_CLAMP) {
+                    a = max(a, wlo);
+                    b = min(b, whi);
+                }
+            };
+            auto inside = [&](unsigned int a, unsigned int b) {
+                if (!LP_LEAF_WINDOW_CLAMP) return (unsigned int)overlap(rb2 + a, b - a, begin, end);
+                cut(a, b);
+                return b > a ? b - a : 0u;
+            };
+            if (inside(lo2, hi2) == 0u) continue;
             const int r = lane & (PG - 1), g = lane >> 4;
             const double* pcol = tab + j2 * TS;
             const double w = pcol[r];
             double big;
             const int p2 = __builtin_amdgcn_readfirstlane(pick_pivot_row(w, r >= KD, lane & ~(PG - 1), big));
-            const double minp2 = fmin(minp1, big), maxp2 = fmax(maxp1, big);
+            const double minp2 = leaf_min(minp1, big), maxp2 = leaf_max(maxp1, big);   // (big: a v_max_f64 result)
             if (!(big > 0.0) || minp2 <= DBL_EPSILON * (double)m * maxp2) {
-                if (lane == 0) cntS += (unsigned int)overlap(rb2 + lo2, hi2 - lo2, begin, end);
+                if (lane == 0) cntS += inside(lo2, hi2);
                 continue;
             }
             const double inv = 1.0 / pcol[p2];
@@ -1093,6 +1206,18 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             const int pos = (r < p2) ? r : (r == p2) ? K5 : (r < KD) ? r - 1 : r;
             double* gtab = s_grand[wave];
             const int R2u = __builtin_amdgcn_readfirstlane(R2);
+            const unsigned* comb5 = pd.comb5 + uniform_off(s_off[R2]);
+            // The 5-column loop's bounds, known before the sub-groups run: the sub-groups are the first remaining
+            // columns j3 that leave k = R2-1 .. kGreatMin selectable ones, sum of C(k, 4) = C(R2, 5) - C(kGreatMin, 5)
+            // subsets (if the sub-group loop below ends early, at off3 >= hi2, this is >= hi2 as well: no tail either way).
+            unsigned int tail_lo = lo2;                // MODE 3: the leaves in front of it went to sub-groups
+            if (MODE == 3 && R2 >= kGreatMin) tail_lo = max(lo2, L2 - uniform_len(s_binom[kGreatMin * (KD + 1) + K5]));
+            unsigned int tl = tail_lo, th = hi2;       // ... and cut to [begin, end)
+            cut(tl, th);
+            // The first pass's table word is issued here: the copy rounds and the sub-groups hide its round trip.
+            // (Clamped index: a lane past the loop's end reads the group's last word and never uses it.)
+            [[maybe_unused]] unsigned pk5 = 0u;
+            if (LP_LEAF_COMB_AHEAD) pk5 = comb_word(comb5, min(tl + (unsigned)lane, hi2 - 1u));
 #pragma unroll
             for (int q = 0; q < (NMX + KD + 3) / 4; ++q) {
                 if (LP_LEAF_CUT_ROUNDS && 4 * q > R2u) break;
@@ -1102,29 +1227,26 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                     gtab[j * TS + pos] = fma(lx, pc[p2], isp ? -0.0 : pc[r]);
                 }
             }
-            const unsigned* comb5 = pd.comb5 + s_off[R2];
             const int U5[K5] = {0, 1, 2, 3, 4};        // unused by leaf_verdict<PERM>
-            unsigned int tail_lo = lo2;                // MODE 3: the leaves in front of it went to sub-groups
             if constexpr (MODE == 3) {
                 constexpr int K4 = KD - 2;
                 double* ggtab = s_tab[wave * 2 + buf];  // (the next item's slice: written at the top of the next iteration)
                 unsigned int off3 = 0;                  // first leaf of sub-group j3 inside the group
                 for (int j3 = 0; R2 - 1 - j3 >= kGreatMin && off3 < hi2; ++j3) {
                     const int R3 = R2 - 1 - j3;         // selectable columns of the depth m-4 node
-                    const unsigned int L3 = s_binom[R3 * (KD + 1) + K4];
+                    const unsigned int L3 = uniform_len(s_binom[R3 * (KD + 1) + K4]);
                     const unsigned int a3 = off3 > lo2 ? off3 : lo2, b3 = off3 + L3 < hi2 ? off3 + L3 : hi2;
                     const unsigned int base3 = off3;
                     off3 += L3;
-                    tail_lo = off3 > lo2 ? off3 : lo2;
-                    if (a3 >= b3 || overlap(rb2 + a3, b3 - a3, begin, end) == 0ULL) continue;
+                    if (a3 >= b3 || inside(a3, b3) == 0u) continue;
                     // ---- third pivot, on column j3 of the grandchild tableau (unused rows at positions 0..4, ascending)
                     const double* pcol3 = gtab + j3 * TS;
                     const double w3 = pcol3[r];
                     double big3;
                     const int p3 = __builtin_amdgcn_readfirstlane(pick_pivot_row(w3, r >= K5, lane & ~(PG - 1), big3));
-                    const double minp3 = fmin(minp2, big3), maxp3 = fmax(maxp2, big3);
+                    const double minp3 = leaf_min(minp2, big3), maxp3 = leaf_max(maxp2, big3);
                     if (!(big3 > 0.0) || minp3 <= DBL_EPSILON * (double)m * maxp3) {
-                        if (lane == 0) cntS += (unsigned int)overlap(rb2 + a3, b3 - a3, begin, end);
+                        if (lane == 0) cntS += inside(a3, b3);
                         continue;
                     }
                     const double inv3 = 1.0 / pcol3[p3];
@@ -1133,6 +1255,13 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                     // rows: the 4 unused ones at 0..3, the new pivot row at 4, the rest stay
                     const int pos3 = (r < p3) ? r : (r == p3) ? K4 : (r < K5) ? r - 1 : r;
                     const int R3u = __builtin_amdgcn_readfirstlane(R3);
+                    // the sub-group's table (words relative to the group's leaf 0), its loop bounds cut to
+                    // [begin, end), and the first pass's word, issued in front of the copy rounds
+                    const unsigned* comb4 = pd.comb4 + uniform_off(s_off4[R3]) - uniform_off(base3);
+                    unsigned int a3w = a3, b3w = b3;
+                    cut(a3w, b3w);
+                    [[maybe_unused]] unsigned pk4 = 0u;
+                    if (LP_LEAF_COMB_AHEAD) pk4 = comb_word(comb4, min(a3w + (unsigned)lane, b3 - 1u));
 #pragma unroll
                     for (int q = 0; q < (NMX + KD + 2) / 4; ++q) {
                         if (LP_LEAF_CUT_ROUNDS && 4 * q > R3u) break;
@@ -1142,13 +1271,23 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                             ggtab[j * TS + pos3] = fma(lx3, pc[p3], isp3 ? -0.0 : pc[r]);
                         }
                     }
-                    const unsigned* comb4 = pd.comb4 + s_off4[R3];
                     const int U4[K4] = {0, 1, 2, 3};    // unused by leaf_verdict<PERM>
-                    for (unsigned int leaf = a3 + lane; leaf < b3; leaf += 64) {
+                    for (unsigned int leaf = a3w + lane; leaf < b3w; leaf += 64) {
                         const unsigned long long rank = rb2 + leaf;
+#if !LP_LEAF_WINDOW_CLAMP
                         if (rank < begin || rank >= end) continue;
+#endif
                         int c4[K4];
-                        const unsigned pk = comb4[leaf - base3];
+#if LP_LEAF_COMB_AHEAD
+                        // this pass's word was loaded a pass ago; the next pass's is in flight during the verdicts
+                        // (index clamped to the sub-group's last leaf: no read past its table, no branch)
+                        const unsigned pk = pk4;
+#ifndef LP_LEAF_COMB_BOUND
+                        pk4 = comb_word(comb4, min(leaf + 64u, b3 - 1u));
+#endif
+#else
+                        const unsigned pk = comb_word(comb4, leaf);
+#endif
 #pragma unroll
                         for (int t = 0; t < K4; ++t) c4[t] = (int)((pk >> (5 * t)) & 31u);
                         const int verdict = leaf_verdict<K4, TS, true, false, !EXACT, true>(ggtab, c4, R3, U4, 0u, minp3, maxp3, m, nullptr, &viol, s_rows4);
@@ -1167,11 +1306,20 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                     }
                 }
             }
-            for (unsigned int leaf = tail_lo + lane; leaf < hi2; leaf += 64) {
+            for (unsigned int leaf = tl + lane; leaf < th; leaf += 64) {
                 const unsigned long long rank = rb2 + leaf;
+#if !LP_LEAF_WINDOW_CLAMP
                 if (rank < begin || rank >= end) continue;
+#endif
                 int c[K5];
-                const unsigned pk = comb5[leaf];
+#if LP_LEAF_COMB_AHEAD
+                const unsigned pk = pk5;   // (as the sub-groups' loop: one pass ahead, clamped to the group's last leaf)
+#ifndef LP_LEAF_COMB_BOUND
+                pk5 = comb_word(comb5, min(leaf + 64u, hi2 - 1u));
+#endif
+#else
+                const unsigned pk = comb_word(comb5, leaf);
+#endif
 #pragma unroll
                 for (int t = 0; t < K5; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
                 const int verdict = leaf_verdict<K5, TS, true, false, !EXACT, true>(gtab, c, R2, U5, 0u, minp2, maxp2, m, nullptr, &viol, s_rows);
@@ -1272,11 +1420,24 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             }
         } else {
         const int U[KD] = {0, 1, 2, 3, 4, 5};        // unused by leaf_verdict<PERM>
-        for (unsigned int leaf = leaf_lo + lane; leaf < leaf_hi; leaf += 64) {
+        // (m = 6: bounds cut to [begin, end) and the table word one pass ahead, as k_enum_leaves<3>'s loops)
+        const unsigned* comb0 = pd.comb6 + uniform_off(s_off[R]);
+        unsigned int l0 = leaf_lo, l1 = leaf_hi;
+        clamp_to_window(rb, l0, l1, begin, end);
+        [[maybe_unused]] unsigned pk6 = 0u;
+        if (LP_LEAF_COMB_AHEAD) pk6 = comb_word(comb0, min(l0 + (unsigned)lane, leaf_hi - 1u));
+        for (unsigned int leaf = l0 + lane; leaf < l1; leaf += 64) {
             const unsigned long long rank = rb + leaf;
+#if !LP_LEAF_WINDOW_CLAMP
             if (rank < begin || rank >= end) continue;
+#endif
             int c[KD];
-            const unsigned pk = comb[leaf];
+#if LP_LEAF_COMB_AHEAD
+            const unsigned pk = pk6;
+            pk6 = comb_word(comb0, min(leaf + 64u, leaf_hi - 1u));
+#else
+            const unsigned pk = comb_word(comb0, leaf);
+#endif
 #pragma unroll
             for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
             const int verdict = leaf_verdict<KD, TS, true, false, !EXACT, true>(tab, c, R, U, umask, minp0, maxp0, m, nullptr, &viol, s_rows);
@@ -2124,7 +2285,7 @@ void k_enum_leaves_quads(EnumDev d, PrefixDev pd, const double* __restrict__ roo
             const QuadSlot e = sq[4 * (inN ? half ^ 1 : half) + s];
             rank = e.rank0 + (unsigned long long)(unsigned)wl;
             rec = e.rec;
-            const unsigned pk = pd.comb6[e.comb0 + wl];
+            const unsigned pk = comb_word(pd.comb6, (unsigned)(e.comb0 + wl));   // (the index of a lane's own subset: >= 0)
             int c[KD];
 #pragma unroll
             for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
