@@ -16,9 +16,6 @@ using lptree::PG;
 // kEnumNoRoom: no memory for the level buffers, or a level outgrew its buffer (the device's overflow flag):
 // the direct kernel enumerates the range
 constexpr int kEnumNoRoom = 1000;
-#ifndef LP_PARENT_TAILS_BESIDE   // measurement builds: 0 = k_enum_parent_tails behind the last level instead of beside it
-#define LP_PARENT_TAILS_BESIDE 1
-#endif
 // kEnumListOverflow: the feasible list was too small; *h_list_count holds the number of feasible subsets
 // of the range, the caller grows the list, goes dense or splits the range
 constexpr int kEnumListOverflow = 1001;
@@ -316,7 +313,7 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
         const bool narrow = waves <= (uint64_t)ctx->num_cus * (uint64_t)narrow_mult;
         const bool last_level = t == D0 - 1;
         const int stop = (parent_tails && last_level) ? lp_enum_parent_tails_stop(n) : n;
-        if (parent_tails && last_level && LP_PARENT_TAILS_BESIDE) {   // beside the last level (measured: lp_enum_launch_parent_tails)
+        if (parent_tails && last_level) {   // beside the last level, not behind it (measured: lp_enum_launch_parent_tails)
             const int rc = lp_enum_launch_parent_tails(p, p->prefix_buf[cur], (int)std::min<uint64_t>(bound, (uint64_t)caps[t]), t, begin, end);
             if (rc) return rc;
             ++launches;
@@ -324,11 +321,6 @@ static int prefix_range_once(lp_enum_problem* p, uint64_t begin, uint64_t end, d
         lp_enum_launch_level(p, shape, t, narrow, bound, p->prefix_buf[cur], t == 0 ? 1 : caps[t], p->prefix_buf[nxt],
                              cap, stop, begin, end);
         ++launches;
-        if (parent_tails && last_level && !LP_PARENT_TAILS_BESIDE) {   // behind the last level
-            const int rc = lp_enum_launch_parent_tails(p, p->prefix_buf[cur], (int)std::min<uint64_t>(bound, (uint64_t)caps[t]), t, begin, end);
-            if (rc) return rc;
-            ++launches;
-        }
         cur = nxt;
     }
     const uint64_t root_bound = std::min<uint64_t>(nodes_d0, 0x7FFFFFFFULL);

@@ -16,10 +16,10 @@
 // abundance (the cooperative sweep of enum_prefix.hip shares two more levels but is bound by the
 // latency of its broadcasts, pivot searches and workgroup barriers).
 //
-// k_enum_leaves<2> / <3> (two thirds of the subsets; <3> adds a third shared pivot for the large sub-groups, see MODE 3).  The subsets below a child are grouped by their
+// k_enum_leaves<3> (two thirds of the subsets).  The subsets below a child are grouped by their
 // first remaining column; a group that leaves >= kGrandMin selectable columns gets a second
-// in-LDS pivot and its lanes take 5 columns each (items of table 1).  k_enum_leaves<1> finishes
-// what is left of each child (items of table 0).
+// in-LDS pivot and its lanes take 5 columns each (items of table 1); its large sub-groups get a
+// third one (see MODE 3).  k_enum_leaves<1> finishes what is left of each child (items of table 0).
 //
 // k_enum_leaves_quads (table 0 of the fused path; k_enum_leaves<1> stays for m = 6 and behind LP_ENUM_LEAF_QUADS=0).
 // One table entry per child; a wave pivots four children at once, a 16-lane group each, straight from the record's
@@ -65,37 +65,6 @@ constexpr int kGreatMin = LP_GREAT_MIN;         // k_enum_leaves<3>: a sub-group
 // selectable columns leave the item tables.  C(32,16) pass with 8 / 9 / 10 columns: 12.80 / 12.67 / 14.64 ms; the
 // other shapes and the shards in lp_enum_launch_leaves.
 constexpr int THIN_TAIL = 9;
-#ifndef LP_LEAF_CUT_ROUNDS   // diagnostic builds: 0 = the shared pivots copy six rounds of columns whatever the width
-#define LP_LEAF_CUT_ROUNDS 1
-#endif
-#ifndef LP_LEAF_UNROLL_ROWS   // diagnostic builds: 0 = phase 2 of the tuned leaf kernels as a rolled loop over the rows
-#define LP_LEAF_UNROLL_ROWS 1
-#endif
-#ifndef LP_LEAF_MASKED_ROT   // leaf_verdict's row rotation: 1 = 64-bit moves under the lane mask (one statement per row);
-#define LP_LEAF_MASKED_ROT 1 // diagnostic builds: 0 = the select form
-#endif
-#ifndef LP_LEAF_MASKED_2X2   // the 2x2 block's row choice: 1 = a row swap under the lane mask (nine 64-bit moves);
-#define LP_LEAF_MASKED_2X2 1 // diagnostic builds: 0 = twelve selects
-#endif
-// The head of a pass (profiles/enum_leaf_pass_head.json; each part measured and dropped alone):
-#ifndef LP_LEAF_COMB_AHEAD   // k_enum_leaves<3> / <0>: the subset-table word of the NEXT pass is loaded in front of the current
-#define LP_LEAF_COMB_AHEAD 1 // pass's verdicts, the first pass's in front of the shared pivot's copy rounds; 0 = at the head of its pass
-#endif
-#ifndef LP_LEAF_ASM_MINMAX   // the running min / max |pivot| of leaf_verdict and of table 1's shared pivots as v_min_f64 /
-#define LP_LEAF_ASM_MINMAX 1 // v_max_f64 themselves (no canonicalising v_max_f64 x, x in front of them); 0 = fmin / fmax
-#endif
-#ifndef LP_LEAF_WINDOW_CLAMP // k_enum_leaves<3> / <0>: the leaf loops' bounds are cut to [begin, end) once per loop and no lane
-#define LP_LEAF_WINDOW_CLAMP 1 // tests its rank; table 1 keeps its item's fields, the bounds of its groups and sub-groups and the
-#endif                       // window (as leaf indices of the group) in scalar registers; 0 = 64-bit vector arithmetic per lane
-#ifndef LP_LEAF_SCALAR_BASE  // the subset-table load as scalar base + 32-bit lane offset; 0 = a 64-bit address per lane
-#define LP_LEAF_SCALAR_BASE 1
-#endif
-// -DLP_LEAF_COMB_BOUND (diagnostic builds, WRONG RESULTS on purpose): every pass of k_enum_leaves<3>'s two loops takes the
-// subset-table word its lane loaded in front of the loop.  NOT the bound on LP_LEAF_COMB_AHEAD it was meant to be: the
-// word is then loop-invariant, and the compiler hoists the column addresses and part of the LDS reads out of the loop
-// (SQ_INSTS_VALU of the kernel -14 %); the look-ahead load itself is the measurement of what the load's round trip cost.
-// -DLP_LEAF_NO_ROTATE (diagnostic builds, WRONG RESULTS on purpose): the chosen row is taken to be row t — the pass
-// time without any rotation, the bound on what a cheaper rotation can return.
 constexpr int TS = PG + 1;            // LDS column stride (doubles): odd, so that lanes reading the
                                       // same row of different columns hit different banks
 
@@ -157,33 +126,21 @@ constexpr double kRecipLo = 0x1p-500, kRecipHi = 0x1p500;
 // reciprocals are fma results — arithmetic never produces a signalling NaN.  On quiet NaNs, zeros and numbers the
 // instruction is fmin / fmax bit for bit (it is what they are lowered to).
 __device__ __forceinline__ double leaf_min(double a, double b) {
-#if LP_LEAF_ASM_MINMAX
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return fmin(a, b);
-#endif
 }
 __device__ __forceinline__ double leaf_max(double a, double b) {
-#if LP_LEAF_ASM_MINMAX
     double r;
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return fmax(a, b);
-#endif
 }
 
-// The word at table[idx].  LP_LEAF_SCALAR_BASE: `table` is wave-uniform and held in scalar registers by the caller
+// The word at table[idx]: `table` is wave-uniform and held in scalar registers by the caller
 // (readfirstlane of its offset), the lane's part is a 32-bit byte offset (the tables are far below 4 GB) — the load
 // then takes the scalar-base form instead of a 64-bit address formed per lane.
 __device__ __forceinline__ unsigned comb_word(const unsigned* table, unsigned idx) {
-#if LP_LEAF_SCALAR_BASE
     return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(table) + (size_t)(idx * 4u));
-#else
-    return table[idx];
-#endif
 }
 // A wave-uniform value that came out of memory or LDS, moved to scalar registers: what is computed from it is scalar
 // arithmetic, which does not take the vector slot.
@@ -192,33 +149,23 @@ __device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
            (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
 }
 // The subsets [lo, hi) of a node whose subset 0 has rank rb, cut to the ranks inside [begin, end): hi <= lo if there is
-// none.  Every operand is wave-uniform; the bounds come back in scalar registers (LP_LEAF_WINDOW_CLAMP: once per leaf
+// none.  Every operand is wave-uniform; the bounds come back in scalar registers (once per leaf
 // loop, in place of two 64-bit compares and an add per lane and pass).  k_enum_leaves<0>'s form; table 1 states the
 // window once per group as leaf indices and cuts with 32-bit min / max (k_enum_leaves<3> below).
 __device__ __forceinline__ void clamp_to_window(unsigned long long rb, unsigned& lo, unsigned& hi, unsigned long long begin,
                                                 unsigned long long end) {
-#if LP_LEAF_WINDOW_CLAMP
     const unsigned long long rbu = uniform64(rb);
     const unsigned lou = (unsigned)__builtin_amdgcn_readfirstlane((int)lo), hiu = (unsigned)__builtin_amdgcn_readfirstlane((int)hi);
     const unsigned long long a = rbu + lou, b = rbu + hiu;
     const unsigned long long a2 = a > begin ? a : begin, b2 = b < end ? b : end;
     lo = b2 > a2 ? (unsigned)(a2 - rbu) : lou;
     hi = b2 > a2 ? (unsigned)(b2 - rbu) : lou;
-#endif
 }
 __device__ __forceinline__ unsigned uniform_len(unsigned len) {   // (a binomial out of LDS)
-#if LP_LEAF_WINDOW_CLAMP
     return (unsigned)__builtin_amdgcn_readfirstlane((int)len);
-#else
-    return len;
-#endif
 }
 __device__ __forceinline__ unsigned uniform_off(unsigned off) {
-#if LP_LEAF_SCALAR_BASE
     return (unsigned)__builtin_amdgcn_readfirstlane((int)off);
-#else
-    return off;
-#endif
 }
 
 // d[k] = s[k], k < N, in the lanes of `mask`; the other lanes keep d.  One 64-bit move per value under the lane mask
@@ -462,16 +409,14 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
     bool sing = false;
 #pragma unroll
     for (int t = 0; t < KD - 2; ++t) {
-        // first row of largest |entry| (a NaN entry is never the maximum: fmax drops it)
+        // the largest |entry| (a NaN entry is never the maximum: fmax drops it); its first row p is found from `big`
+        // by leaf_rotate_masked's votes
         double big = -1.0;
-        int p = t;
         if (PERM && t <= 1) {
             big = t == 0 ? big0 : bigs1;   // chosen while loading; the pivot rows already sit at positions 0, 1
         } else {
 #pragma unroll
             for (int r = t; r < KD; ++r) big = fmax(big, fabs(E[r][t]));
-#pragma unroll
-            for (int r = KD - 1; r >= t; --r) p = (fabs(E[r][t]) == big) ? r : p;   // descending: the first wins
         }
         // (FAST: no test here — a zero column leaves big = 0, a NaN column -1, so minp <= 0 and the threshold
         // test behind the 2x2 block says singular: one compare per step less in the leaf kernels' hot loop)
@@ -481,37 +426,16 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         minp = leaf_min(minp, big);
         maxp = leaf_max(maxp, big);
         // rotate row p to position t (columns t..KD-1 and the rhs).  A select on a double is two v_cndmask_b32, and
-        // every select of a row shares one condition: by default the rows move as 64-bit moves under the lane mask
-        // (leaf_rotate_masked; profiles/enum_leaf_masked_rot.json), the select form stays behind LP_LEAF_MASKED_ROT 0
-#ifdef LP_LEAF_NO_ROTATE
-        const bool rotate = false;
-#else
+        // every select of a row shares one condition: the rows move as 64-bit moves under the lane mask
+        // (leaf_rotate_masked; profiles/enum_leaf_masked_rot.json)
         const bool rotate = !(PERM && t <= 1);
-#endif
-        if (rotate && LP_LEAF_MASKED_ROT) {
+        if (rotate) {
             static_assert(KD <= 7, "leaf_rotate_masked: steps 0..4");
             if (t == 0) leaf_rotate_masked<KD, 0>(E, H, big);
             else if (t == 1) leaf_rotate_masked<KD, 1>(E, H, big);
             else if (t == 2) leaf_rotate_masked<KD, 2>(E, H, big);
             else if (t == 3) leaf_rotate_masked<KD, 3>(E, H, big);
             else leaf_rotate_masked<KD, 4>(E, H, big);
-        } else if (rotate)
-#pragma unroll
-        for (int cc = t; cc <= KD; ++cc) {
-            double pr = (cc < KD) ? E[t][cc < KD ? cc : 0] : H[t];
-#pragma unroll
-            for (int r = t + 1; r < KD; ++r) {
-                const double v = (cc < KD) ? E[r][cc < KD ? cc : 0] : H[r];
-                pr = (r == p) ? v : pr;
-            }
-#pragma unroll
-            for (int r = KD - 1; r > t; --r) {
-                if (cc < KD)
-                    E[r][cc < KD ? cc : 0] = (r <= p) ? E[r - 1][cc < KD ? cc : 0] : E[r][cc < KD ? cc : 0];
-                else
-                    H[r] = (r <= p) ? H[r - 1] : H[r];
-            }
-            if (cc < KD) E[t][cc < KD ? cc : 0] = pr; else H[t] = pr;
         }
         // the pivot element, now in its static position (PERM, step 0: its reciprocal is already there)
         const double inv = (PERM && t == 0) ? inv0 : recip(E[t][t]);
@@ -536,14 +460,9 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
     const double a1 = E[KD - 2][KD - 2], a2 = E[KD - 1][KD - 2], b1 = E[KD - 2][KD - 1],
                  b2 = E[KD - 1][KD - 1], h1 = H[KD - 2], h2 = H[KD - 1];
     const bool second = fabs(a2) > fabs(a1);
-#if LP_LEAF_MASKED_2X2
     double row1[3] = {a1, b1, h1}, row2[3] = {a2, b2, h2};
     masked_row_swap(__builtin_amdgcn_ballot_w64(second), row1, row2);
     const double pa = row1[0], pb = row1[1], ph = row1[2], qa = row2[0], qb = row2[1], qh = row2[2];
-#else
-    const double pa = second ? a2 : a1, pb = second ? b2 : b1, ph = second ? h2 : h1;
-    const double qa = second ? a1 : a2, qb = second ? b1 : b2, qh = second ? h1 : h2;
-#endif
     const double big1 = fabs(pa);
     const double inv1 = recip(pa);
     const double l = -(qa * inv1);
@@ -610,7 +529,7 @@ __device__ __forceinline__ int leaf_verdict_impl(const double* tab, const int (&
         z = fma(obj->cost[obj->col0 + c[KD - 2]], xa, z);
         z = fma(obj->cost[obj->col0 + c[KD - 1]], xb, z);
         obj->z = z;
-    } else if constexpr (PERM && TAB && LP_LEAF_UNROLL_ROWS) {
+    } else if constexpr (PERM && TAB) {
         // (the tuned kernels, tableaus of PG rows: unrolled over the rows the tableau can hold, so that every row is an
         // LDS read at an immediate offset from the column addresses phase 1 already holds — the rolled loop spends ten
         // of its ~26 vector instructions per row on addresses: a running pointer per column and an add per read)
@@ -884,46 +803,47 @@ __global__ __launch_bounds__(1024) void k_enum_make_items(EnumDev d, PrefixDev p
 
 // MODE 1: work items of table 0 over the depth m-7 records; the wave pivots on the child column
 //         itself (depth m-6 tableau in LDS), the lanes take the 6 remaining columns.
-// MODE 2: work items of table 1; the wave pivots twice (child, then the group's first column j2:
+// MODE 3: work items of table 1; the wave pivots twice (child, then the group's first column j2:
 //         depth m-5 tableau in LDS) and the lanes take the 5 remaining columns — consecutive
 //         subsets share their first remaining column and with it the whole first elimination
 //         step, which costs a lane a third of its instructions.  A kernel of its own so that the
 //         register allocation of MODE 1's loop is not disturbed (the two loops in one kernel cost
 //         that loop 12 %).
-// MODE 3: MODE 2's items; inside a group the subsets are in lexicographic order again, so those that share their
+//         Inside a group the subsets are in lexicographic order again, so those that share their
 //         first remaining column j3 are consecutive — C(R2 - 1 - j3, 4) of them.  Every such sub-group that leaves
 //         >= kGreatMin selectable columns (half of all subsets of C(32,16)) gets a THIRD in-LDS pivot and its lanes
 //         take 4 columns each (two Gauss-Jordan steps whose rows are chosen before they are loaded, no register
 //         rotation at all, then the 2x2 block: ~200 instructions per subset against ~320 with 5 columns); what is
-//         left of the group is finished with 5 columns as in MODE 2.  The great-grandchild tableau lives in the
+//         left of the group is finished with 5 columns.  The great-grandchild tableau lives in the
 //         half of the record's double buffer that the NEXT item's record will be written to (free until then).
 // MODE 0 (m = 6): the root record is the depth m-6 node.
+// (No MODE 2: it was MODE 3 without the third pivot; tests and profiles name the others by these numbers.)
 template <int MODE, bool EXACT>
 __global__ __launch_bounds__(LEAF_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
 void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, int chunk1, unsigned long long begin,
                    unsigned long long end) {
     constexpr bool FUSED = MODE != 0;
     // subsets per work item: table 1's width is the host's choice (lp_enum_launch_leaves), the one its items were cut at
-    const unsigned int width = MODE >= 2 ? (unsigned int)chunk1 : (unsigned int)kChunk;
+    const unsigned int width = MODE == 3 ? (unsigned int)chunk1 : (unsigned int)kChunk;
     constexpr int KD = 6;
     constexpr int MAXCOLS = NMX + KD + 1 + (FUSED ? 1 : 0);  // columns of a record (+ rhs)
     constexpr int CHILDCOLS = NMX + KD + 1;                  // columns of a depth m-6 tableau (+ rhs)
     __shared__ __attribute__((aligned(16))) double s_tab[LEAF_WAVES * 2][MAXCOLS * TS];  // double-buffered
     __shared__ __attribute__((aligned(16))) double s_child[FUSED ? LEAF_WAVES : 1][FUSED ? CHILDCOLS * TS : 1];
     __shared__ __attribute__((aligned(16))) double s_child2[MODE == 1 ? LEAF_WAVES : 1][MODE == 1 ? CHILDCOLS * TS : 1];
-    __shared__ __attribute__((aligned(16))) double s_grand[MODE >= 2 ? LEAF_WAVES : 1][MODE >= 2 ? (NMX + KD) * TS : 1];
+    __shared__ __attribute__((aligned(16))) double s_grand[MODE == 3 ? LEAF_WAVES : 1][MODE == 3 ? (NMX + KD) * TS : 1];
     __shared__ unsigned int s_binom[(NMX + KD + 2) * (KD + 1)];  // C(r, k), r <= NMX+KD+1, k <= KD
     __shared__ unsigned long long s_cnt[3];
     __shared__ unsigned int s_off[32];  // offsets of the per-R subset tables inside pd.comb6
-    __shared__ unsigned int s_rows[36];  // leaf_row_table of this kernel's lanes (5 columns each in MODE 2 / 3, else 6)
+    __shared__ unsigned int s_rows[36];  // leaf_row_table of this kernel's lanes (5 columns each in MODE 3, else 6)
     __shared__ unsigned int s_off4[MODE == 3 ? 32 : 1], s_rows4[MODE == 3 ? 16 : 1];   // MODE 3: the same for 4 columns
     __shared__ unsigned long long s_run[LEAF_WAVES];   // every wave's run of work items {next, end}: see draw() below
     __shared__ int s_dry;                              // a wave of this workgroup has seen the end of the item table
 
     const int m = d.m, n = d.n, D = m - KD - (FUSED ? 1 : 0);   // depth of the records
-    const int4* const items = MODE >= 2 ? pd.items2 : pd.items;   // built by k_enum_make_items
-    const int nitems = MODE >= 2 ? min(pd.item_count[1], pd.item_cap2) : min(pd.item_count[0], pd.item_cap);
-    int* const cursor = pd.root_cursor + (MODE >= 2 ? 1 : 0);
+    const int4* const items = MODE == 3 ? pd.items2 : pd.items;   // built by k_enum_make_items
+    const int nitems = MODE == 3 ? min(pd.item_count[1], pd.item_cap2) : min(pd.item_count[0], pd.item_cap);
+    int* const cursor = pd.root_cursor + (MODE == 3 ? 1 : 0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef LP_LEAF_WAVELOG
     const unsigned long long wl_t0 = __builtin_amdgcn_s_memrealtime();
@@ -935,8 +855,8 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         s_binom[k] = (unsigned int)d.binom[r * kBinomK + kk];
     }
     if (tid < 3) s_cnt[tid] = 0ULL;
-    if (tid < 32) s_off[tid] = MODE >= 2 ? pd.comb5[tid] : pd.comb6[tid];
-    leaf_row_table<(MODE >= 2 ? 5 : 6)>(s_rows, tid);
+    if (tid < 32) s_off[tid] = MODE == 3 ? pd.comb5[tid] : pd.comb6[tid];
+    leaf_row_table<(MODE == 3 ? 5 : 6)>(s_rows, tid);
     if constexpr (MODE == 3) {
         if (tid < 32) s_off4[tid] = pd.comb4[tid];
         leaf_row_table<4>(s_rows4, tid);
@@ -1053,9 +973,9 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         ++wl_items;
 #endif
         // ---- item B becomes the current item: registers -> LDS slice (odd column stride)
-        // (table 1, LP_LEAF_WINDOW_CLAMP: the item's fields in scalar registers — the bounds of its groups and sub-groups
+        // (table 1: the item's fields in scalar registers — the bounds of its groups and sub-groups
         // and their cuts to [begin, end) below are then scalar arithmetic)
-        auto field = [](int v) { return (MODE >= 2 && LP_LEAF_WINDOW_CLAMP) ? __builtin_amdgcn_readfirstlane(v) : v; };
+        auto field = [](int v) { return MODE == 3 ? __builtin_amdgcn_readfirstlane(v) : v; };
         const int chunk = field(chunkB), child = field(childB), roff = field(roffB), rec = recB;
         const NodeMeta pm = pmB;
         double* tab = s_tab[wave * 2 + buf];
@@ -1070,18 +990,18 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         if (itemB < nitems) fetch(itemB);
         if (pm.last_col == kHole) continue;
         const int child_col = FUSED ? (child & 0xFF) : pm.last_col;   // last chosen column of the depth m-6 node
-        const int j2_first = (child >> 8) & 0xFF;      // MODE 2: first remaining column of the (first) group
-        const int ngroups = child >> 16;               // MODE 2: groups packed into this item
+        const int j2_first = (child >> 8) & 0xFF;      // MODE 3: first remaining column of the (first) group
+        const int ngroups = child >> 16;               // MODE 3: groups packed into this item
         const int last = child_col;
         const int R = n - 1 - last;                    // selectable columns of the depth m-6 node
         if (R < KD) continue;
-        // subsets of this item: [leaf_lo, leaf_hi) inside the node (MODE 0/1) or inside the group (MODE 2)
+        // subsets of this item: [leaf_lo, leaf_hi) inside the node (MODE 0/1) or inside the group (MODE 3)
         const unsigned int L = s_binom[R * (KD + 1) + KD];   // (MODE 0/1)
         // subset table: all 6-subsets of R columns in lexicographic order, 5 bits per index
         // (one L2-resident load; a dependent unranking loop over binomials costs ~2k cycles)
-        const unsigned* comb = pd.comb6 + s_off[MODE >= 2 ? 0 : R];
+        const unsigned* comb = pd.comb6 + s_off[MODE == 3 ? 0 : R];
         unsigned long long rb = pm.rank_base + (unsigned long long)(FUSED ? roff : 0);
-        if (MODE >= 2 && LP_LEAF_WINDOW_CLAMP) rb = uniform64(rb);
+        if (MODE == 3) rb = uniform64(rb);
         const unsigned int leaf_lo = (unsigned int)chunk;
         const unsigned int leaf_hi = (leaf_lo + width < L) ? leaf_lo + width : L;
         double minp0 = pm.minp, maxp0 = pm.maxp;
@@ -1101,7 +1021,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             if (!(big > 0.0) || minp0 <= DBL_EPSILON * (double)m * maxp0) {
                 // every subset below this node is singular
                 unsigned int span = leaf_hi - leaf_lo;
-                if (MODE >= 2) {
+                if (MODE == 3) {
                     span = 0;
                     for (int gi = 0; gi < ngroups; ++gi) span += s_binom[(R - 1 - j2_first - gi) * (KD + 1) + KD - 1];
                     if (ngroups == 1) span = min(span - leaf_lo, width);
@@ -1132,18 +1052,15 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             // 10-column child three rounds of address arithmetic for nothing).  MODE 1: the subsets of a table-0 item
             // are the child's tail, whose first remaining column leaves fewer than kGrandMin selectable ones — they
             // reach only the last kGrandMin columns and the rhs, so only those are written (at their own positions).
-            // MODE 2 / 3: the item's groups pivot on columns j2_first .. and read the ones behind them.
+            // MODE 3: the item's groups pivot on columns j2_first .. and read the ones behind them.
             // (C(32,16): SQ_INSTS_VALU of table 1's kernel 2.520 -> 2.513 G per pass, none in table 0's, whose rounds
             // beyond the width were skipped by an execz branch already; with the row maximum and the item width the
             // bench step 12.98 -> 12.75 ms and the slowest 8-way shard 2.07 -> 1.96 ms: profiles/enum_leaf_steps.json)
             const int Ru = __builtin_amdgcn_readfirstlane(R);
-            const int jlo = !LP_LEAF_CUT_ROUNDS ? 0
-                            : MODE == 1         ? max(Ru - kGrandMin, 0)
-                            : MODE >= 2         ? __builtin_amdgcn_readfirstlane(j2_first)
-                                                : 0;
+            const int jlo = MODE == 1 ? max(Ru - kGrandMin, 0) : MODE == 3 ? __builtin_amdgcn_readfirstlane(j2_first) : 0;
 #pragma unroll
             for (int q = 0; q < (CHILDCOLS + 3) / 4; ++q) {
-                if (LP_LEAF_CUT_ROUNDS && jlo + 4 * q > Ru) break;
+                if (jlo + 4 * q > Ru) break;
                 const int j = jlo + g + 4 * q;      // child column j = column child+1+j (j = R: rhs)
                 if (j <= R && !sing0) {
                     const double* pc = tab + (child_col + 1 + j - D) * TS;
@@ -1155,7 +1072,7 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             tab += (last + 1 - D) * TS;              // column q below = column last+1+q
             // (m = 6: the root record, no row used yet — the identity is the permuted order)
         }
-        if constexpr (MODE >= 2) {
+        if constexpr (MODE == 3) {
             constexpr int K5 = KD - 1;
             const double minp1 = minp0, maxp1 = maxp0;
             for (int gi = 0; gi < ngroups; ++gi) {
@@ -1168,23 +1085,17 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             const unsigned int hi2 = (lo2 + width < L2) ? lo2 + width : L2;
             const unsigned long long rb2 = rb;
             rb += L2;                                  // next group of a packed item
-            // LP_LEAF_WINDOW_CLAMP: [begin, end) as leaf indices of this group, [wlo, whi) — saturated at 2^32 - 1, far
+            // [begin, end) as leaf indices of this group, [wlo, whi) — saturated at 2^32 - 1, far
             // beyond a group's C(21, 5) subsets — so that the cuts below are 32-bit scalar min / max
-            [[maybe_unused]] unsigned int wlo = 0u, whi = ~0u;
-            if (LP_LEAF_WINDOW_CLAMP) {
-                const unsigned long long rlo = begin > rb2 ? begin - rb2 : 0ULL, rhi = end > rb2 ? end - rb2 : 0ULL;
-                wlo = rlo < 0xFFFFFFFFULL ? (unsigned int)rlo : ~0u;
-                whi = rhi < 0xFFFFFFFFULL ? (unsigned int)rhi : ~0u;
-            }
+            const unsigned long long rlo = begin > rb2 ? begin - rb2 : 0ULL, rhi = end > rb2 ? end - rb2 : 0ULL;
+            const unsigned int wlo = rlo < 0xFFFFFFFFULL ? (unsigned int)rlo : ~0u;
+            const unsigned int whi = rhi < 0xFFFFFFFFULL ? (unsigned int)rhi : ~0u;
             // leaves [a, b) of the group, a < b, cut to the window (b <= a: none inside), and how many are inside
             auto cut = [&](unsigned int& a, unsigned int& b) {
-                if (LP_LEAF_WINDOW_CLAMP) {
-                    a = max(a, wlo);
-                    b = min(b, whi);
-                }
+                a = max(a, wlo);
+                b = min(b, whi);
             };
             auto inside = [&](unsigned int a, unsigned int b) {
-                if (!LP_LEAF_WINDOW_CLAMP) return (unsigned int)overlap(rb2 + a, b - a, begin, end);
                 cut(a, b);
                 return b > a ? b - a : 0u;
             };
@@ -1210,17 +1121,16 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
             // The 5-column loop's bounds, known before the sub-groups run: the sub-groups are the first remaining
             // columns j3 that leave k = R2-1 .. kGreatMin selectable ones, sum of C(k, 4) = C(R2, 5) - C(kGreatMin, 5)
             // subsets (if the sub-group loop below ends early, at off3 >= hi2, this is >= hi2 as well: no tail either way).
-            unsigned int tail_lo = lo2;                // MODE 3: the leaves in front of it went to sub-groups
-            if (MODE == 3 && R2 >= kGreatMin) tail_lo = max(lo2, L2 - uniform_len(s_binom[kGreatMin * (KD + 1) + K5]));
+            unsigned int tail_lo = lo2;                // the leaves in front of it went to sub-groups
+            if (R2 >= kGreatMin) tail_lo = max(lo2, L2 - uniform_len(s_binom[kGreatMin * (KD + 1) + K5]));
             unsigned int tl = tail_lo, th = hi2;       // ... and cut to [begin, end)
             cut(tl, th);
             // The first pass's table word is issued here: the copy rounds and the sub-groups hide its round trip.
             // (Clamped index: a lane past the loop's end reads the group's last word and never uses it.)
-            [[maybe_unused]] unsigned pk5 = 0u;
-            if (LP_LEAF_COMB_AHEAD) pk5 = comb_word(comb5, min(tl + (unsigned)lane, hi2 - 1u));
+            unsigned pk5 = comb_word(comb5, min(tl + (unsigned)lane, hi2 - 1u));
 #pragma unroll
             for (int q = 0; q < (NMX + KD + 3) / 4; ++q) {
-                if (LP_LEAF_CUT_ROUNDS && 4 * q > R2u) break;
+                if (4 * q > R2u) break;
                 const int j = g + 4 * q;        // grandchild column j = child column j2+1+j (j = R2: rhs)
                 if (j <= R2) {
                     const double* pc = tab + (j2 + 1 + j) * TS;
@@ -1228,98 +1138,77 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                 }
             }
             const int U5[K5] = {0, 1, 2, 3, 4};        // unused by leaf_verdict<PERM>
-            if constexpr (MODE == 3) {
-                constexpr int K4 = KD - 2;
-                double* ggtab = s_tab[wave * 2 + buf];  // (the next item's slice: written at the top of the next iteration)
-                unsigned int off3 = 0;                  // first leaf of sub-group j3 inside the group
-                for (int j3 = 0; R2 - 1 - j3 >= kGreatMin && off3 < hi2; ++j3) {
-                    const int R3 = R2 - 1 - j3;         // selectable columns of the depth m-4 node
-                    const unsigned int L3 = uniform_len(s_binom[R3 * (KD + 1) + K4]);
-                    const unsigned int a3 = off3 > lo2 ? off3 : lo2, b3 = off3 + L3 < hi2 ? off3 + L3 : hi2;
-                    const unsigned int base3 = off3;
-                    off3 += L3;
-                    if (a3 >= b3 || inside(a3, b3) == 0u) continue;
-                    // ---- third pivot, on column j3 of the grandchild tableau (unused rows at positions 0..4, ascending)
-                    const double* pcol3 = gtab + j3 * TS;
-                    const double w3 = pcol3[r];
-                    double big3;
-                    const int p3 = __builtin_amdgcn_readfirstlane(pick_pivot_row(w3, r >= K5, lane & ~(PG - 1), big3));
-                    const double minp3 = leaf_min(minp2, big3), maxp3 = leaf_max(maxp2, big3);
-                    if (!(big3 > 0.0) || minp3 <= DBL_EPSILON * (double)m * maxp3) {
-                        if (lane == 0) cntS += inside(a3, b3);
-                        continue;
-                    }
-                    const double inv3 = 1.0 / pcol3[p3];
-                    const bool isp3 = (r == p3);
-                    const double lx3 = isp3 ? inv3 : -(w3 * inv3);
-                    // rows: the 4 unused ones at 0..3, the new pivot row at 4, the rest stay
-                    const int pos3 = (r < p3) ? r : (r == p3) ? K4 : (r < K5) ? r - 1 : r;
-                    const int R3u = __builtin_amdgcn_readfirstlane(R3);
-                    // the sub-group's table (words relative to the group's leaf 0), its loop bounds cut to
-                    // [begin, end), and the first pass's word, issued in front of the copy rounds
-                    const unsigned* comb4 = pd.comb4 + uniform_off(s_off4[R3]) - uniform_off(base3);
-                    unsigned int a3w = a3, b3w = b3;
-                    cut(a3w, b3w);
-                    [[maybe_unused]] unsigned pk4 = 0u;
-                    if (LP_LEAF_COMB_AHEAD) pk4 = comb_word(comb4, min(a3w + (unsigned)lane, b3 - 1u));
+            constexpr int K4 = KD - 2;
+            double* ggtab = s_tab[wave * 2 + buf];  // (the next item's slice: written at the top of the next iteration)
+            unsigned int off3 = 0;                  // first leaf of sub-group j3 inside the group
+            for (int j3 = 0; R2 - 1 - j3 >= kGreatMin && off3 < hi2; ++j3) {
+                const int R3 = R2 - 1 - j3;         // selectable columns of the depth m-4 node
+                const unsigned int L3 = uniform_len(s_binom[R3 * (KD + 1) + K4]);
+                const unsigned int a3 = off3 > lo2 ? off3 : lo2, b3 = off3 + L3 < hi2 ? off3 + L3 : hi2;
+                const unsigned int base3 = off3;
+                off3 += L3;
+                if (a3 >= b3 || inside(a3, b3) == 0u) continue;
+                // ---- third pivot, on column j3 of the grandchild tableau (unused rows at positions 0..4, ascending)
+                const double* pcol3 = gtab + j3 * TS;
+                const double w3 = pcol3[r];
+                double big3;
+                const int p3 = __builtin_amdgcn_readfirstlane(pick_pivot_row(w3, r >= K5, lane & ~(PG - 1), big3));
+                const double minp3 = leaf_min(minp2, big3), maxp3 = leaf_max(maxp2, big3);
+                if (!(big3 > 0.0) || minp3 <= DBL_EPSILON * (double)m * maxp3) {
+                    if (lane == 0) cntS += inside(a3, b3);
+                    continue;
+                }
+                const double inv3 = 1.0 / pcol3[p3];
+                const bool isp3 = (r == p3);
+                const double lx3 = isp3 ? inv3 : -(w3 * inv3);
+                // rows: the 4 unused ones at 0..3, the new pivot row at 4, the rest stay
+                const int pos3 = (r < p3) ? r : (r == p3) ? K4 : (r < K5) ? r - 1 : r;
+                const int R3u = __builtin_amdgcn_readfirstlane(R3);
+                // the sub-group's table (words relative to the group's leaf 0), its loop bounds cut to
+                // [begin, end), and the first pass's word, issued in front of the copy rounds
+                const unsigned* comb4 = pd.comb4 + uniform_off(s_off4[R3]) - uniform_off(base3);
+                unsigned int a3w = a3, b3w = b3;
+                cut(a3w, b3w);
+                unsigned pk4 = comb_word(comb4, min(a3w + (unsigned)lane, b3 - 1u));
 #pragma unroll
-                    for (int q = 0; q < (NMX + KD + 2) / 4; ++q) {
-                        if (LP_LEAF_CUT_ROUNDS && 4 * q > R3u) break;
-                        const int j = g + 4 * q;        // column j = grandchild column j3+1+j (j = R3: rhs)
-                        if (j <= R3) {
-                            const double* pc = gtab + (j3 + 1 + j) * TS;
-                            ggtab[j * TS + pos3] = fma(lx3, pc[p3], isp3 ? -0.0 : pc[r]);
-                        }
+                for (int q = 0; q < (NMX + KD + 2) / 4; ++q) {
+                    if (4 * q > R3u) break;
+                    const int j = g + 4 * q;        // column j = grandchild column j3+1+j (j = R3: rhs)
+                    if (j <= R3) {
+                        const double* pc = gtab + (j3 + 1 + j) * TS;
+                        ggtab[j * TS + pos3] = fma(lx3, pc[p3], isp3 ? -0.0 : pc[r]);
                     }
-                    const int U4[K4] = {0, 1, 2, 3};    // unused by leaf_verdict<PERM>
-                    for (unsigned int leaf = a3w + lane; leaf < b3w; leaf += 64) {
-                        const unsigned long long rank = rb2 + leaf;
-#if !LP_LEAF_WINDOW_CLAMP
-                        if (rank < begin || rank >= end) continue;
-#endif
-                        int c4[K4];
-#if LP_LEAF_COMB_AHEAD
-                        // this pass's word was loaded a pass ago; the next pass's is in flight during the verdicts
-                        // (index clamped to the sub-group's last leaf: no read past its table, no branch)
-                        const unsigned pk = pk4;
-#ifndef LP_LEAF_COMB_BOUND
-                        pk4 = comb_word(comb4, min(leaf + 64u, b3 - 1u));
-#endif
-#else
-                        const unsigned pk = comb_word(comb4, leaf);
-#endif
+                }
+                const int U4[K4] = {0, 1, 2, 3};    // unused by leaf_verdict<PERM>
+                for (unsigned int leaf = a3w + lane; leaf < b3w; leaf += 64) {
+                    const unsigned long long rank = rb2 + leaf;
+                    int c4[K4];
+                    // this pass's word was loaded a pass ago; the next pass's is in flight during the verdicts
+                    // (index clamped to the sub-group's last leaf: no read past its table, no branch)
+                    const unsigned pk = pk4;
+                    pk4 = comb_word(comb4, min(leaf + 64u, b3 - 1u));
 #pragma unroll
-                        for (int t = 0; t < K4; ++t) c4[t] = (int)((pk >> (5 * t)) & 31u);
-                        const int verdict = leaf_verdict<K4, TS, true, false, !EXACT, true>(ggtab, c4, R3, U4, 0u, minp3, maxp3, m, nullptr, &viol, s_rows4);
-                        if (verdict == 2) {
-                            ++cntS;
-                        } else if (verdict == 1) {
-                            ++cntI;
-                        } else {
-                            ++cntF;
-                            const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
-                            if (at < pd.list_cap) {
-                                pd.list[at] = rank;
-                                pd.list_rec[at] = rec;
-                            }
+                    for (int t = 0; t < K4; ++t) c4[t] = (int)((pk >> (5 * t)) & 31u);
+                    const int verdict = leaf_verdict<K4, TS, true, false, !EXACT, true>(ggtab, c4, R3, U4, 0u, minp3, maxp3, m, nullptr, &viol, s_rows4);
+                    if (verdict == 2) {
+                        ++cntS;
+                    } else if (verdict == 1) {
+                        ++cntI;
+                    } else {
+                        ++cntF;
+                        const unsigned long long at = atomicAdd(pd.list_count, 1ULL);
+                        if (at < pd.list_cap) {
+                            pd.list[at] = rank;
+                            pd.list_rec[at] = rec;
                         }
                     }
                 }
             }
             for (unsigned int leaf = tl + lane; leaf < th; leaf += 64) {
                 const unsigned long long rank = rb2 + leaf;
-#if !LP_LEAF_WINDOW_CLAMP
-                if (rank < begin || rank >= end) continue;
-#endif
                 int c[K5];
-#if LP_LEAF_COMB_AHEAD
                 const unsigned pk = pk5;   // (as the sub-groups' loop: one pass ahead, clamped to the group's last leaf)
-#ifndef LP_LEAF_COMB_BOUND
                 pk5 = comb_word(comb5, min(leaf + 64u, hi2 - 1u));
-#endif
-#else
-                const unsigned pk = comb_word(comb5, leaf);
-#endif
 #pragma unroll
                 for (int t = 0; t < K5; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
                 const int verdict = leaf_verdict<K5, TS, true, false, !EXACT, true>(gtab, c, R2, U5, 0u, minp2, maxp2, m, nullptr, &viol, s_rows);
@@ -1378,10 +1267,10 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
                     int wv = wave;   // (opaque copy: the slice address is recomputed here, not kept live — and spilled — across items)
                     asm volatile("" : "+v"(wv));
                     double* ctab1 = s_child2[wv];
-                    const int R1u = __builtin_amdgcn_readfirstlane(R1), jlo1 = LP_LEAF_CUT_ROUNDS ? max(R1u - kGrandMin, 0) : 0;   // (as the first child's)
+                    const int R1u = __builtin_amdgcn_readfirstlane(R1), jlo1 = max(R1u - kGrandMin, 0);   // (as the first child's)
 #pragma unroll
                     for (int q = 0; q < (CHILDCOLS + 3) / 4; ++q) {
-                        if (LP_LEAF_CUT_ROUNDS && jlo1 + 4 * q > R1u) break;
+                        if (jlo1 + 4 * q > R1u) break;
                         const int j = jlo1 + g + 4 * q;   // column j of the second child = record column child_col+2+j
                         if (j <= R1) {
                             const double* pc = par + (child_col + 2 + j - D) * TS;
@@ -1424,20 +1313,12 @@ void k_enum_leaves(EnumDev d, PrefixDev pd, const double* __restrict__ roots, in
         const unsigned* comb0 = pd.comb6 + uniform_off(s_off[R]);
         unsigned int l0 = leaf_lo, l1 = leaf_hi;
         clamp_to_window(rb, l0, l1, begin, end);
-        [[maybe_unused]] unsigned pk6 = 0u;
-        if (LP_LEAF_COMB_AHEAD) pk6 = comb_word(comb0, min(l0 + (unsigned)lane, leaf_hi - 1u));
+        unsigned pk6 = comb_word(comb0, min(l0 + (unsigned)lane, leaf_hi - 1u));
         for (unsigned int leaf = l0 + lane; leaf < l1; leaf += 64) {
             const unsigned long long rank = rb + leaf;
-#if !LP_LEAF_WINDOW_CLAMP
-            if (rank < begin || rank >= end) continue;
-#endif
             int c[KD];
-#if LP_LEAF_COMB_AHEAD
             const unsigned pk = pk6;
             pk6 = comb_word(comb0, min(leaf + 64u, leaf_hi - 1u));
-#else
-            const unsigned pk = comb_word(comb0, leaf);
-#endif
 #pragma unroll
             for (int t = 0; t < KD; ++t) c[t] = (int)((pk >> (5 * t)) & 31u);
             const int verdict = leaf_verdict<KD, TS, true, false, !EXACT, true>(tab, c, R, U, umask, minp0, maxp0, m, nullptr, &viol, s_rows);
@@ -2657,6 +2538,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_enum_eval_records(EnumDev d, P
 // C(32,16), 250 k records, and C(28,14), 116 k, pay for k_enum_parent_tails; the whole C(32,16), 2.04 M, gains) —
 // the threshold of kItemLanesNarrow and kChunkWide.  LP_ENUM_PARENT_TAILS=0 / 1 decides for every range.
 constexpr uint64_t kParentTailsMinRecords = 300000;
+constexpr int kParentTailsPerCu = 2;   // workgroups of k_enum_parent_tails per CU (2 against 1: lp_enum_launch_parent_tails)
 bool lp_enum_parent_tails(const lp_enum_problem* p, int shape, bool fused, bool dense, int level, uint64_t records) {
     if (shape != 1 || !fused || dense || level < 1 || p->knobs.parent_tails == 0) return false;
     return p->knobs.parent_tails == 1 || records >= kParentTailsMinRecords;
@@ -2693,9 +2575,6 @@ static int leaf_streams(lp_context* ctx) {
 // `bound`): queued on a stream of its own behind whatever the library's stream holds at this point, so that it runs
 // beside what is queued there next, and neither the tail kernel nor the leaf kernels wait for it.  aux_event[3]
 // marks its end: lp_enum_launch_leaves makes the library's stream wait for it at the end of the pass.
-#ifndef LP_PARENT_TAILS_PER_CU
-#define LP_PARENT_TAILS_PER_CU 2
-#endif
 int lp_enum_launch_parent_tails(lp_enum_problem* p, const double* parents, int bound, int level, uint64_t begin,
                                 uint64_t end) {
     lp_context* ctx = p->ctx;
@@ -2722,7 +2601,7 @@ int lp_enum_launch_parent_tails(lp_enum_problem* p, const double* parents, int b
     //   with it the shards of a 2- / 4- / 8-way cut take 6.62 / 3.59 / 1.96 -> 6.44 / 3.55 / 1.94 ms (slowest, two runs)
     //   bench step, 7 runs each: 12.693 -> 11.879 ms (-6.4 %; the parent's runs within 0.18 ms)
     const unsigned grid = (unsigned)std::min<uint64_t>(lp_ceil_div<uint64_t>((uint64_t)std::max(bound, 1), 64 * LEAF_WAVES),
-                                                       (uint64_t)ctx->num_cus * LP_PARENT_TAILS_PER_CU);
+                                                       (uint64_t)ctx->num_cus * kParentTailsPerCu);
     const unsigned long long b = begin, e = end;
     if (p->exact_div)
         hipLaunchKernelGGL((k_enum_parent_tails<true, THIN_TAIL>), grid, LEAF_THREADS, 0, sT, p->dev, p->prefix, parents, level, bound, b, e);
@@ -2851,17 +2730,14 @@ int lp_enum_launch_leaves(lp_enum_problem* p, const double* roots, int bound, in
         // single passes — C(28,14) 1.17 against 1.19 ms, C(32,16) 13.2 against 13.3 — but half of the passes then take
         // 14.0-14.1 ms: the average is worse.)
         const int grid2 = grid6, grid1 = grid6;
-#ifndef LP_LEAF_LEVELS   // diagnostic builds: 2 = table 1's kernel without the third in-LDS pivot
-#define LP_LEAF_LEVELS 3
-#endif
         if (exact) {
-            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, true>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<3, true>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
             if (quads)
                 hipLaunchKernelGGL((k_enum_leaves_quads<true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
             else
                 hipLaunchKernelGGL((k_enum_leaves<1, true>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, kChunk, b, e);
         } else {
-            hipLaunchKernelGGL((k_enum_leaves<LP_LEAF_LEVELS, false>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
+            hipLaunchKernelGGL((k_enum_leaves<3, false>), grid2, LEAF_THREADS, 0, s, p->dev, pd, roots, chunk1, b, e);
             if (quads)
                 hipLaunchKernelGGL((k_enum_leaves_quads<false>), grid1, LEAF_THREADS, 0, s1, p->dev, pd, roots, b, e);
             else

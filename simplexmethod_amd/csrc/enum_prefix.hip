@@ -58,12 +58,10 @@ constexpr int kStagedParents = 256; // ... of k_enum_expand_staged (16-row recor
 // — not the records — were what a parent cost (staging the records alone changed nothing: 1.82 against 1.66 ms
 // for the last level; with the table in LDS 1.04 ms = 3.5 TB/s of the 3.66 GB, the five wide levels of C(32,16)
 // 2.70 -> 1.66 ms).  The child's metadata is assembled word-wise (the byte-wise form was a third of the loop's
-// instructions).
+// instructions).  A hand-counted wait for the prefetch (asm loads, s_waitcnt vmcnt(n) with n a lower bound of the
+// stores issued behind them, instead of the compiler's vmcnt(0)) was tried and dropped: 1.03 against 1.04 ms.
 // ---------------------------------------------------------------------------
 // (4 waves per SIMD: 6 changed nothing, 8 spills and is 70 % slower)
-#ifndef LP_STAGED_COUNTED
-#define LP_STAGED_COUNTED 0
-#endif
 template <int NMXT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_enum_expand_staged(EnumDev d, PrefixDev pd, int t,
                                                             const double* __restrict__ src, int src_cap,
@@ -77,7 +75,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     __shared__ int s_base[kStagedParents];
     __shared__ int s_last[kStagedParents];
     __shared__ int s_wtot[5];
-    __shared__ int s_nst[4];   // per wave: store instructions issued behind the prefetch in flight
     __shared__ __attribute__((aligned(16))) double s_rec[4][MAXC * RS + META];
     // subsets below a child with last column a: C(n-1-a, m-t-1) — one table per level, in LDS (looked up per
     // child by every parent's lane in phase A and again per lane in the expansion: out of L2 these dependent
@@ -149,19 +146,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int idx = u * 64 + lane;
-#if LP_STAGED_COUNTED
-            // (asm: a load the compiler does not track — the wait for it is the counted one at the staging below)
-            if (idx < cnt) asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(pre[u]) : "v"(Q + idx) : "memory");
-#else
             pre[u] = idx < cnt ? Q[idx] : 0.0;
-#endif
         }
     };
-#if LP_STAGED_COUNTED
-#pragma unroll
-    for (int u = 0; u < PER; ++u) pre[u] = 0.0;
-    if (lane == 0) s_nst[wave] = 0;
-#endif
     fetch(0);
     for (int it = 0; it < ppw; ++it) {
         const int local = wave * ppw + it;
@@ -173,22 +160,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             continue;
         }
         const int cnt = (n - last) * RS + META;
-#if LP_STAGED_COUNTED
-        {
-            // The wave's memory counter retires loads and stores in issue order, and the compiler, not knowing how many
-            // stores the previous parent issued behind this parent's loads, would wait for ALL of them (vmcnt(0)): every
-            // parent then pays its predecessor's store acknowledgements, ~2-3 us.  The previous iteration counted the
-            // store instructions it issued at wave level (a lower bound: the column loops' trips and the rhs stores) —
-            // waiting until at most that many operations are outstanding retires exactly the loads and whatever is older.
-            const int nst = __builtin_amdgcn_readfirstlane(s_nst[wave]);
-            if (nst >= 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-            else if (nst >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if (nst >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (nst >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) s_nst[wave] = 0;
-        }
-#endif
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int idx = u * 64 + lane;
@@ -248,12 +219,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             const double inv = 1.0 / piv;
             const bool isp = (gl == p);
             const double lx = isp ? inv : -(w * inv);
-#if LP_STAGED_COUNTED
-            {   // the groups that write a child this round: the first one has the smallest a, i.e. the longest column loop
-                const unsigned long long run = __ballot(1);
-                if (lane == (int)__builtin_ctzll(run)) s_nst[wave] += n - a;   // n - 1 - a columns + the rhs
-            }
-#endif
             double* Cc = C + (size_t)(a - t) * RS + gl;   // column c of the child at (c - t - 1) * RS
             const double* Lc = La + RS;                   // column a + 1 of the parent
 #pragma unroll 2
