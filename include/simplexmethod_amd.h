@@ -721,6 +721,34 @@ int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, i
  * dual_rule == LP_DUAL_DEVEX ? m : 0) doubles fits 160 KiB; 0 otherwise, and for an unknown rule of either kind.      */
 int lp_simplex_bounded_dual_rule_fits(int m, int n, int pivot_rule, int dual_rule);
 
+/* The ratio test of the bounded DUAL loop: how the entering column is chosen once a position r leaves (DESIGN.md
+ * §4.5k4; the definition is tests/ref/bounded_resolve_long_step_ref.c, which every output equals bit for bit).  The
+ * three entries take the arguments of their _dual_ex entry with dual_ratio appended.  dual_ratio governs the entering
+ * step of the dual branch only: the checks, the crash, the classification, the primal branch, the leaving choice under
+ * either dual rule and the complement of a position violated above are unchanged.
+ *   - LP_DUAL_RATIO_TEXTBOOK: the column of smallest d_s / T[r][s] enters, whatever its own box.  The entry launches
+ *     exactly what its _dual_ex entry launches and equals it in every output.
+ *   - LP_DUAL_RATIO_LONG_STEP: the bound-flipping ratio test.  With e the candidate of that same chain: if U_e is
+ *     finite and fma(-U_e, T[r][e], xB_r) < -eps, row r stays violated with e at its other bound, so e is flipped as
+ *     the primal loop flips (xB_i = fma(-U_e, T[i][e], xB_i) for every row and the cost row, column e negated, its
+ *     flag toggled) and the chain runs again on the same row; the first candidate whose flip would cure the violation
+ *     is pivoted on.  A flip is O(m) where the pivot it replaces is O(m n).  No candidate left: LP_INFEASIBLE, with
+ *     the basis and the flags as they stand, flips included.  Under LP_DUAL_DEVEX a flip leaves the weights alone.
+ *     Status and objective are LP_DUAL_RATIO_TEXTBOOK's up to rounding wherever that one ends optimal; the optimal
+ *     basis, the flags and the counts may differ.
+ * max_iter bounds the dual pivots, as before; a dual iteration makes at most n flips.  iters_out[2] counts the dual
+ * loop's flips as well as the primal loop's (a re-solve runs one of the two).
+ * Any other dual_ratio is LP_BAD_ARG before anything else is looked at, and no output is written.
+ * Shapes: the long-step kernels need no LDS beyond their textbook forms: lp_simplex_bounded_dual_rule_fits for the two
+ * LDS entries, and the _large entry's limits on m are those of its _dual_ex entry.
+ * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large and _large_ex) and the parametric
+ * paths keep the textbook ratio test, and the unbounded lp_simplex_resolve family (no boxes, so nothing to flip) is
+ * not touched.                                                                                                      */
+enum { LP_DUAL_RATIO_TEXTBOOK = 0, LP_DUAL_RATIO_LONG_STEP = 1 };
+int lp_simplex_bounded_resolve_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule, int dual_ratio);
+int lp_simplex_bounded_resolve_batched_ratio_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule, int dual_ratio);
+int lp_simplex_bounded_resolve_large_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule, int dual_ratio);
+
 /* ---- Bounded variables: branch-and-bound over the bounds ------------------------------------------------------
  * The LP of lp_simplex_bounded with the columns j < n_orig of integer[j] = 1 integral (one mask of n entries for the
  * whole batch), searched depth first from basis_in and at_upper_in, normally what lp_simplex_bounded returned

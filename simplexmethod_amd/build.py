@@ -156,6 +156,8 @@ REFS = {
     "bounded_rules": ("bounded",),
     "bounded_resolve_rules": ("bounded_resolve", "bounded", "bounded_rules"),
     "bounded_resolve_dual_rules": ("bounded_resolve_rules", "bounded_resolve", "bounded", "bounded_rules"),
+    "bounded_resolve_long_step": ("bounded_resolve_dual_rules", "bounded_resolve_rules", "bounded_resolve", "bounded",
+                                  "bounded_rules"),
 }
 
 
@@ -198,6 +200,7 @@ build_bounded_parametric_ref = functools.partial(build_ref, "bounded_parametric"
 build_bounded_rules_ref = functools.partial(build_ref, "bounded_rules")
 build_bounded_resolve_rules_ref = functools.partial(build_ref, "bounded_resolve_rules")
 build_bounded_resolve_dual_rules_ref = functools.partial(build_ref, "bounded_resolve_dual_rules")
+build_bounded_resolve_long_step_ref = functools.partial(build_ref, "bounded_resolve_long_step")
 
 
 def build_all(force=False, verbose=False):

@@ -19,6 +19,7 @@ SIMPLEX_AUTO, SIMPLEX_LAUNCH, SIMPLEX_LOOKAHEAD, SIMPLEX_RESIDENT, SIMPLEX_OVERL
 ENUM_AUTO, ENUM_DIRECT, ENUM_PREFIX = 0, 1, 2
 PIVOT_DANTZIG, PIVOT_BLAND, PIVOT_DEVEX = 0, 1, 2
 DUAL_DANTZIG, DUAL_DEVEX = 0, 1
+DUAL_RATIO_TEXTBOOK, DUAL_RATIO_LONG_STEP = 0, 1
 CERT_NONE, CERT_FARKAS, CERT_RAY = 0, 1, 2
 U64_MAX = (1 << 64) - 1
 EPS = 1e-9        # Solver::EPS, SimplexSolover.h:13
@@ -177,6 +178,15 @@ SIGNATURES = {
                                                            C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
                                                            _ip, C.c_int, C.c_int]),
     "lp_simplex_bounded_dual_rule_fits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve_ratio_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                      C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int,
+                                                      C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve_batched_ratio_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
+                                                              _ip, _ip, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip,
+                                                              _ip, _dp, _ip, _ip, C.c_int, C.c_int, C.c_int]),
+    "lp_simplex_bounded_resolve_large_ratio_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                            C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _dp,
+                                                            _ip, C.c_int, C.c_int, C.c_int]),
     "lp_simplex_bounded_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                               C.c_double, C.c_int, _dp, _ip, _ip, _dp, _ip, C.c_int]),
     "lp_simplex_bounded_resolve_large_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
@@ -324,6 +334,17 @@ def dual_rule_id(rule):
             raise ValueError(f"unknown dual rule {rule!r} (expected 'dantzig' or 'devex')")
         return names[rule.lower()]
     return int(rule)
+
+
+def dual_ratio_id(ratio):
+    """"textbook" | "long_step" | DUAL_RATIO_TEXTBOOK | DUAL_RATIO_LONG_STEP -> the LP_DUAL_RATIO_* value (other
+    integers pass through: the library refuses them with LP_BAD_ARG)."""
+    if isinstance(ratio, str):
+        names = {"textbook": DUAL_RATIO_TEXTBOOK, "long_step": DUAL_RATIO_LONG_STEP}
+        if ratio.lower() not in names:
+            raise ValueError(f"unknown dual ratio test {ratio!r} (expected 'textbook' or 'long_step')")
+        return names[ratio.lower()]
+    return int(ratio)
 
 
 class LPError(RuntimeError):
@@ -773,10 +794,16 @@ class Context:
 
     # ---- bounded-variable simplex -------------------------------------------------------------
     dual_rule_id = staticmethod(dual_rule_id)
+    dual_ratio_id = staticmethod(dual_ratio_id)
 
-    def _bounded_call(self, name, pivot_rule, *args, dual_rule=None):
+    def _bounded_call(self, name, pivot_rule, *args, dual_rule=None, dual_ratio=None):
         """The entry `name` of the bounded family, or with a pivot_rule its _ex form with the rule appended, or (the
-        re-solves) with a dual_rule its _dual_ex form with both appended (no pivot_rule: Dantzig's)."""
+        re-solves) with a dual_rule its _dual_ex form with both appended (no pivot_rule: Dantzig's), or with a
+        dual_ratio its _ratio_ex form with all three appended (no dual_rule: Dantzig's)."""
+        if dual_ratio is not None:
+            rule = PIVOT_DANTZIG if pivot_rule is None else pivot_rule_id(pivot_rule)
+            dual = DUAL_DANTZIG if dual_rule is None else dual_rule_id(dual_rule)
+            return self.check(getattr(self.lib, name + "_ratio_ex")(*args, rule, dual, dual_ratio_id(dual_ratio)))
         if dual_rule is not None:
             rule = PIVOT_DANTZIG if pivot_rule is None else pivot_rule_id(pivot_rule)
             return self.check(getattr(self.lib, name + "_dual_ex")(*args, rule, dual_rule_id(dual_rule)))
@@ -843,13 +870,13 @@ class Context:
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_large(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                              max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
+                              max_iter=MAX_ITER, pivot_rule=None, dual_rule=None, dual_ratio=None):
         """lp_simplex_bounded_resolve_large: the re-solve of bounded_resolve() on the tableau in HBM, at any shape
         bounded_large() runs (no bounded_fits limit).  pivot_rule as in bounded_resolve() (None: the entry without a
         rule; else lp_simplex_bounded_resolve_large_ex): it governs the primal loop only.  Returns the dict of
         bounded_resolve(), equal to it under the same rules where both run; refusals as there.  dual_rule as in
         bounded_resolve() (lp_simplex_bounded_resolve_large_dual_ex; the m weights live in device memory, no
-        bounded_dual_rule_fits limit)."""
+        bounded_dual_rule_fits limit), dual_ratio as there (lp_simplex_bounded_resolve_large_ratio_ex)."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
@@ -860,7 +887,7 @@ class Context:
         it = np.zeros(3, dtype=np.int32)
         rc = self._bounded_call("lp_simplex_bounded_resolve_large", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c),
                                 _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps),
-                                int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule)
+                                int(max_iter), _d(x), _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule, dual_ratio=dual_ratio)
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_fits(self, m, n):
@@ -879,7 +906,7 @@ class Context:
         return bool(self.lib.lp_simplex_bounded_dual_rule_fits(m, n, pivot_rule_id(pivot_rule), dual_rule_id(dual_rule)))
 
     def bounded_resolve(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                        max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
+                        max_iter=MAX_ITER, pivot_rule=None, dual_rule=None, dual_ratio=None):
         """lp_simplex_bounded_resolve: the LP of bounded() re-solved from `basis` (m) and `at_upper` (n, 0/1), normally
         an earlier result's, after a change of lo, hi, b or c: the bounded primal loop if the basis is primal feasible,
         the bounded dual simplex if it is only dual feasible.  dict as bounded() with iters = (dual pivots, primal
@@ -889,7 +916,11 @@ class Context:
         DUAL_* value; None: the call made without it) goes through lp_simplex_bounded_resolve_dual_ex and governs the
         leaving choice of the dual simplex only: under "devex" status and objective are Dantzig's up to rounding, the
         optimal basis and the pivot count may differ.  An unknown dual rule or a shape beyond bounded_dual_rule_fits
-        raises LPError with code BAD_ARG."""
+        raises LPError with code BAD_ARG.  dual_ratio ("textbook", "long_step" or a DUAL_RATIO_* value; None: the call
+        made without it) goes through lp_simplex_bounded_resolve_ratio_ex and governs the entering step of the dual
+        simplex only: under "long_step" (the bound-flipping ratio test) a candidate whose flip to its other bound leaves
+        the leaving row violated is flipped, not pivoted on, and iters[2] counts those flips; status and objective are
+        the textbook test's up to rounding.  An unknown dual ratio raises LPError with code BAD_ARG."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
@@ -900,15 +931,16 @@ class Context:
         it = np.zeros(3, dtype=np.int32)
         rc = self._bounded_call("lp_simplex_bounded_resolve", pivot_rule, self.h, _d(Af), m, n, _d(b), _d(c), _d(lo),
                                 _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter), _d(x),
-                                _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule)
+                                _i(bo), _i(up), _d(obj), _i(it), dual_rule=dual_rule, dual_ratio=dual_ratio)
         return dict(status=rc, x=x, basis=bo, at_upper=up, obj=float(obj[0]), iters=it.tolist())
 
     def bounded_resolve_batched(self, A, b, c, lo, hi, basis, at_upper, maximize=False, n_orig=None, eps=EPS,
-                                max_iter=MAX_ITER, pivot_rule=None, dual_rule=None):
+                                max_iter=MAX_ITER, pivot_rule=None, dual_rule=None, dual_ratio=None):
         """lp_simplex_bounded_resolve_batched: arrays as bounded_batched(), basis (batch, m), at_upper (batch, n).
         dict as bounded_batched() with iters (batch, 3); per LP exactly bounded_resolve(), except that a basis that
         is no valid start is that LP's status BAD_ARG.  pivot_rule as in bounded_resolve()
-        (lp_simplex_bounded_resolve_batched_ex), dual_rule as there (lp_simplex_bounded_resolve_batched_dual_ex)."""
+        (lp_simplex_bounded_resolve_batched_ex), dual_rule as there (lp_simplex_bounded_resolve_batched_dual_ex),
+        dual_ratio as there (lp_simplex_bounded_resolve_batched_ratio_ex)."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper, batched=True)
         batch, m, n, Af, b, c = p.batch, p.m, p.n, p.A, p.b, p.c
         basis, lo, hi, at_upper = p.basis, p.lo, p.hi, p.at_upper
@@ -921,7 +953,7 @@ class Context:
         st = np.zeros(batch, dtype=np.int32)
         self._bounded_call("lp_simplex_bounded_resolve_batched", pivot_rule, self.h, batch, _d(Af), m, n, _d(b), _d(c),
                            _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig, float(eps), int(max_iter),
-                           _d(x), _i(bo), _i(up), _d(obj), _i(it), _i(st), dual_rule=dual_rule)
+                           _d(x), _i(bo), _i(up), _d(obj), _i(it), _i(st), dual_rule=dual_rule, dual_ratio=dual_ratio)
         return dict(status=st, x=x, basis=bo, at_upper=up, obj=obj, iters=it)
 
     # ---- the dual solution and ranging of a bounded-variable LP at a basis ----------------------

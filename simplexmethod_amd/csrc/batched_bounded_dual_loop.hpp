@@ -17,7 +17,20 @@
 // w_i = cand if cand = (g * g) * w_r > w_i with g = T[i][se] / a, a = T[r][se] as the complement left it, then
 // w_r = max(w_r / (a * a), 1.0) by the thread that owns r.  a and the old w_r are read ahead of a barrier of their
 // own, so no thread reads w_r after its owner has rewritten it.  Without the macro the code is what it was.
+//
+// Under the macro LP_BOUNDED_DUAL_LONG_STEP (the _long kernels of batched_bounded_resolve.hip;
+// tests/ref/bounded_resolve_long_step_ref.c states the rule) the entering step is the bound-flipping ratio test.  Wave 0
+// publishes with its candidate whether it is to be flipped (bit 1 of pub[2]): U_e finite and
+// fma(-U_e, a, xB_r) < -eps on the complemented row r, so that row r stays violated with e at its other bound.  Every
+// thread then does batched_bounded_loop.hpp's flip on column se and the xB column, rows 0 .. m; one barrier; wave 0
+// rescans row r, which holds its complement by then, with the same keyed scan (the flipped slot has a > eps now and
+// nothing else of row r or of the cost row changed, so no mask is needed) and publishes again.  The loop takes
+// `flips` as a second counter; max_iter bounds the pivots alone.  Without the macro the code is what it was.
+#ifdef LP_BOUNDED_DUAL_LONG_STEP
+    auto bounded_dual = [&](int& iters, int& flips) -> int {
+#else
     auto bounded_dual = [&](int& iters) -> int {
+#endif
         if (d.max_iter <= 0) return LP_ITER_LIMIT;
 #ifdef LP_BOUNDED_DUAL_DEVEX
         for (int t = tid; t < m; t += NT) dwts[t] = 1.0;
@@ -63,6 +76,15 @@
                         v = maximize ? drow[s] / a : -drow[s] / a;
                     });
                 }
+#ifdef LP_BOUNDED_DUAL_LONG_STEP
+                if (se0 >= 0) {   // flip se0 first? (row r0 as the complement below will leave it)
+                    const double* rrow = T + (size_t)r0 * pitch;
+                    const double a = comp ? -rrow[se0] : rrow[se0];
+                    const double xbr = comp ? U[basis[r0]] - rrow[n] : rrow[n];
+                    const double ue = U[slotvar[se0]];
+                    if (ue < INFINITY && fma(-ue, a, xbr) < -eps) comp |= 2;
+                }
+#endif
                 if (lane == 0) {
                     pub[0] = se0;
                     pub[1] = r0;
@@ -70,9 +92,17 @@
                 }
             }
             __syncthreads();
+#ifdef LP_BOUNDED_DUAL_LONG_STEP
+            int se = pub[0];
+            const int r = pub[1];
+            int flip = pub[2] & 2;
+            if (r < 0) return LP_OPTIMAL;
+            if (pub[2] & 1) {
+#else
             const int se = pub[0], r = pub[1];
             if (r < 0) return LP_OPTIMAL;
             if (pub[2]) {
+#endif
                 const int k = basis[r];
                 for (int j = tid; j < n; j += NT) T[(size_t)r * pitch + j] = -T[(size_t)r * pitch + j];
                 if (tid == 0) {
@@ -82,6 +112,46 @@
                 __syncthreads();
             }
             if (se < 0) return LP_INFEASIBLE;
+#ifdef LP_BOUNDED_DUAL_LONG_STEP
+            while (flip) {
+                // bound flip (batched_bounded_loop.hpp's): row r stays violated with the candidate at its other bound
+                const int e = slotvar[se];
+                const double ue = U[e];
+                for (int i = tid; i <= m; i += NT) {
+                    double* te = T + (size_t)i * pitch + se;
+                    double* xb = T + (size_t)i * pitch + n;
+                    *xb = fma(-ue, *te, *xb);
+                    *te = -*te;
+                }
+                if (tid == 0) up[e] ^= 1;
+                ++flips;
+                __syncthreads();
+                if (wave == 0) {
+                    double best;
+                    const double* rrow = T + (size_t)r * pitch;
+                    const double* drow = T + (size_t)m * pitch;
+                    const int se0 = wave_scan_keyed<false>(n, eps, best, [&](int s, double& v, int& k, bool& ok) {
+                        const double a = rrow[s];
+                        k = slotvar[s];
+                        ok = k < n && a < -eps;
+                        v = maximize ? drow[s] / a : -drow[s] / a;
+                    });
+                    int again = 0;
+                    if (se0 >= 0) {
+                        const double u2 = U[slotvar[se0]];
+                        again = (u2 < INFINITY && fma(-u2, rrow[se0], rrow[n]) < -eps) ? 2 : 0;
+                    }
+                    if (lane == 0) {
+                        pub[0] = se0;
+                        pub[2] = again;
+                    }
+                }
+                __syncthreads();
+                se = pub[0];
+                flip = pub[2];
+                if (se < 0) return LP_INFEASIBLE;
+            }
+#endif
 #ifdef LP_BOUNDED_DUAL_DEVEX
             {
                 const double a = T[(size_t)r * pitch + se], wr = dwts[r];

@@ -17,7 +17,8 @@
 // order.  There is no host fallback: larger shapes get LP_BAD_ARG.
 // The kernel's text is batched_bounded_resolve_body.hpp, shared with its Bland and Devex forms below, in which the
 // rule governs the primal branch only, and with the _ddevex forms, in which the dual branch prices by Devex
-// (LP_DUAL_DEVEX) under each of the three primal rules.
+// (LP_DUAL_DEVEX) under each of the three primal rules, and with the _long forms of all six, in which the dual branch
+// enters by the bound-flipping ratio test (LP_DUAL_RATIO_LONG_STEP).
 #include <cfloat>
 #include <climits>
 
@@ -80,11 +81,92 @@ __global__ __launch_bounds__(NT) void k_batched_bounded_resolve_devex_ddevex(Bat
 #undef LP_BOUNDED_DEVEX
 }
 
+// The six kernels above with the bound-flipping ratio test in the dual branch (LP_DUAL_RATIO_LONG_STEP,
+// batched_bounded_dual_loop.hpp): the same carve, no LDS more.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_ddevex_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DUAL_DEVEX
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+#undef LP_BOUNDED_DUAL_DEVEX
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_bland_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_BLAND
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+#undef LP_BOUNDED_BLAND
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_bland_ddevex_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_BLAND
+#define LP_BOUNDED_DUAL_DEVEX
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+#undef LP_BOUNDED_DUAL_DEVEX
+#undef LP_BOUNDED_BLAND
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_devex_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DEVEX
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+#undef LP_BOUNDED_DEVEX
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_batched_bounded_resolve_devex_ddevex_long(BatchedBoundedResolveDev d) {
+#define LP_BOUNDED_DEVEX
+#define LP_BOUNDED_DUAL_DEVEX
+#define LP_BOUNDED_DUAL_LONG_STEP
+#include "batched_bounded_resolve_body.hpp"
+#undef LP_BOUNDED_DUAL_LONG_STEP
+#undef LP_BOUNDED_DUAL_DEVEX
+#undef LP_BOUNDED_DEVEX
+}
+
 }  // namespace
 
-int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule, int dual_rule) {
+int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule, int dual_rule,
+                                      int dual_ratio) {
     if (!lp_pivot_rule_known(pivot_rule)) LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: unknown pivot rule");
     if (!lp_dual_rule_known(dual_rule)) LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: unknown dual rule");
+    if (!lp_dual_ratio_known(dual_ratio)) LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve: unknown dual ratio test");
+    if (dual_ratio == LP_DUAL_RATIO_LONG_STEP) {   // the carve of the textbook kernel under the same two rules
+        if (!lp_bounded_dual_rule_fits_shape(d.m, d.n, pivot_rule, dual_rule))
+            LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve, long-step: the tableau and the weights do not fit one CU's LDS (lp_simplex_bounded_dual_rule_fits)");
+        const size_t cells = (size_t)(d.m + 1) * (d.n + 1);
+        const size_t lds = lp_bounded_weights_lds_bytes(d.m, d.n, lp_bounded_resolve_weights(d.m, d.n, pivot_rule, dual_rule));
+        const bool dd = dual_rule == LP_DUAL_DEVEX;
+        if (pivot_rule == LP_PIVOT_DEVEX)
+            return dd ? lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_devex_ddevex_long<256>,
+                                         k_batched_bounded_resolve_devex_ddevex_long<1024>, lds, d)
+                      : lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_devex_long<256>,
+                                         k_batched_bounded_resolve_devex_long<1024>, lds, d);
+        if (pivot_rule == LP_PIVOT_BLAND)
+            return dd ? lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_bland_ddevex_long<256>,
+                                         k_batched_bounded_resolve_bland_ddevex_long<1024>, lds, d)
+                      : lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_bland_long<256>,
+                                         k_batched_bounded_resolve_bland_long<1024>, lds, d);
+        return dd ? lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_ddevex_long<256>,
+                                     k_batched_bounded_resolve_ddevex_long<1024>, lds, d)
+                  : lp_launch_per_lp(ctx, cells, k_batched_bounded_resolve_long<256>, k_batched_bounded_resolve_long<1024>,
+                                     lds, d);
+    }
     if (dual_rule == LP_DUAL_DEVEX) {
         if (!lp_bounded_dual_rule_fits_shape(d.m, d.n, pivot_rule, dual_rule))
             LP_FAIL(ctx, LP_BAD_ARG, "batched bounded re-solve, dual Devex: the tableau and the weights do not fit one CU's LDS (lp_simplex_bounded_dual_rule_fits)");

@@ -3,8 +3,9 @@
 // it runs Dantzig's rule; under the macro LP_BOUNDED_BLAND or LP_BOUNDED_DEVEX batched_bounded_loop.hpp's loop runs
 // that rule, and under LP_BOUNDED_DEVEX the carve carries the weights (wts). Under LP_BOUNDED_DUAL_DEVEX
 // batched_bounded_dual_loop.hpp's loop prices by Devex with one weight per basis position (dwts), which share the
-// region of wts: an LP runs one of the two loops. BLAND = false is for batched_lds_loop.hpp, of which only the pivot
-// is used. Not a standalone header.
+// region of wts: an LP runs one of the two loops. Under LP_BOUNDED_DUAL_LONG_STEP that loop's entering step is the
+// bound-flipping ratio test, whose flips are counted with the primal loop's. BLAND = false is for
+// batched_lds_loop.hpp, of which only the pivot is used. Not a standalone header.
     constexpr bool BLAND = false;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     char* base = reinterpret_cast<char*>(smem);
@@ -121,7 +122,11 @@
         if (!violated)
             status = bounded_simplex(true, maximize, it[1], it[2]);   // artificial slots barred
         else if (dual_feasible)
+#ifdef LP_BOUNDED_DUAL_LONG_STEP
+            status = bounded_dual(it[0], it[2]);
+#else
             status = bounded_dual(it[0]);
+#endif
         else
             status = LP_BAD_ARG;
         __syncthreads();

@@ -604,12 +604,13 @@ static int bounded_upload(lp_context* ctx, lp_device_buffer& buf, int batch, con
 // basis_in and at_upper_in: 3 counters per LP) and downloads; x (n_orig) and obj (over all n columns, as
 // lp_simplex_two_phase_batched) are written for LP_OPTIMAL LPs only.  pivot_rule picks the kernel's rule form (the
 // re-solve: of its primal branch); LP_PIVOT_DANTZIG is the kernel the entries without _ex launch.  dual_rule (the
-// re-solve only) picks the pricing of its dual branch; LP_DUAL_DANTZIG is the kernel the _ex entries launch.
+// re-solve only) picks the pricing of its dual branch; LP_DUAL_DANTZIG is the kernel the _ex entries launch.  dual_ratio
+// (the re-solve only) picks that branch's ratio test; LP_DUAL_RATIO_TEXTBOOK is the kernel the _dual_ex entries launch.
 static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
                          const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
                          int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out,
                          double* obj_out, int* iters_out, int* status_out, int pivot_rule = LP_PIVOT_DANTZIG,
-                         int dual_rule = LP_DUAL_DANTZIG) {
+                         int dual_rule = LP_DUAL_DANTZIG, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK) {
     const size_t B = (size_t)batch, iw = basis_in ? 3 : 4;
     lp_device_buffer buf;
     BoundedInputs in;
@@ -637,7 +638,7 @@ static int bounded_solve(lp_context* ctx, int batch, const double* A, int m, int
     d.basis_in = in.basis_in;
     d.at_upper_in = in.at_upper_in;
     std::vector<double> x(B * n);
-    rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d, pivot_rule, dual_rule) : lp_batched_bounded_launch(ctx, d, pivot_rule);
+    rc = basis_in ? lp_batched_bounded_resolve_launch(ctx, d, pivot_rule, dual_rule, dual_ratio) : lp_batched_bounded_launch(ctx, d, pivot_rule);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded simplex: ") + hipGetErrorString(e));
@@ -744,13 +745,15 @@ static int bounded_rule_args(lp_context* ctx, const char* who, int m, int n, int
 // The eight entries of the family in one: single (batch 1, status_out null: the status is the return value) or
 // batched, cold or from given bases (warm), under pivot_rule.  The entries without _ex pass LP_PIVOT_DANTZIG.  The two
 // _dual_ex entries (warm) pass dual_rule too: an unknown one is refused before anything else is looked at, and Devex
-// needs room for the larger of the two weight arrays (lp_simplex_bounded_dual_rule_fits).
+// needs room for the larger of the two weight arrays (lp_simplex_bounded_dual_rule_fits).  The two _ratio_ex entries
+// (warm) pass dual_ratio as well: an unknown one is refused ahead of even that; the long-step form needs no LDS more.
 static int bounded_entry(lp_context* ctx, const char* who, bool batched, bool warm, int batch, const double* A, int m,
                          int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in,
                          const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
                          int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out,
-                         int pivot_rule, int dual_rule = LP_DUAL_DANTZIG) {
+                         int pivot_rule, int dual_rule = LP_DUAL_DANTZIG, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK) {
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_ratio_known(dual_ratio)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown dual ratio test");
     if (!lp_dual_rule_known(dual_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown dual rule");
     if (!x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || (batched && !status_out))
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": null argument");
@@ -765,7 +768,7 @@ static int bounded_entry(lp_context* ctx, const char* who, bool batched, bool wa
     int status = LP_OPTIMAL;
     rc = bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, warm ? basis_in : nullptr, warm ? at_upper_in : nullptr,
                        maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
-                       batched ? status_out : &status, pivot_rule, dual_rule);
+                       batched ? status_out : &status, pivot_rule, dual_rule, dual_ratio);
     if (rc || batched) return rc;
     if (warm && status == LP_BAD_ARG)
         LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
@@ -860,6 +863,23 @@ int lp_simplex_bounded_resolve_batched_dual_ex(lp_context* ctx, int batch, const
     return bounded_entry(ctx, "lp_simplex_bounded_resolve_batched_dual_ex", true, true, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
                          maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
                          pivot_rule, dual_rule);
+}
+
+int lp_simplex_bounded_resolve_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
+                                        const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out,
+                                        int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule, int dual_ratio) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve_ratio_ex", false, true, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, nullptr,
+                         pivot_rule, dual_rule, dual_ratio);
+}
+
+int lp_simplex_bounded_resolve_batched_ratio_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c,
+                                                const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter,
+                                                double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule,
+                                                int dual_ratio) {
+    return bounded_entry(ctx, "lp_simplex_bounded_resolve_batched_ratio_ex", true, true, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in,
+                         maximize, n_orig, eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out, status_out,
+                         pivot_rule, dual_rule, dual_ratio);
 }
 
 int lp_mip_bounded_fits(int m, int n, int max_depth) { return lp_mip_bounded_fits_shape(m, n, max_depth) ? 1 : 0; }

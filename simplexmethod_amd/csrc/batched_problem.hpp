@@ -303,9 +303,10 @@ struct BatchedBoundedResolveDev : BatchedBoundedDev {
 };
 
 // batched_bounded_resolve.hip
-// fitting shapes (under the rule), else LP_BAD_ARG; the rule governs the primal branch only
+// fitting shapes (under the rule), else LP_BAD_ARG; the rule governs the primal branch only, dual_rule and dual_ratio
+// (LP_DUAL_RATIO_*) the dual branch only
 int lp_batched_bounded_resolve_launch(lp_context* ctx, const BatchedBoundedResolveDev& d, int pivot_rule = LP_PIVOT_DANTZIG,
-                                      int dual_rule = LP_DUAL_DANTZIG);
+                                      int dual_rule = LP_DUAL_DANTZIG, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK);
 
 // Depth-first branch-and-bound over variable bounds, one mixed-integer bounded LP per workgroup
 // (batched_mip_bounded.hip; the definition is tests/ref/mip_bounded_ref.c): the bounded re-solve at the root, then per

@@ -157,6 +157,9 @@ static inline bool lp_pivot_rule_known(int rule) {
 // The dual pricing rules the _dual_ex entries accept.
 static inline bool lp_dual_rule_known(int rule) { return rule == LP_DUAL_DANTZIG || rule == LP_DUAL_DEVEX; }
 
+// The dual ratio tests the _ratio_ex entries accept.
+static inline bool lp_dual_ratio_known(int ratio) { return ratio == LP_DUAL_RATIO_TEXTBOOK || ratio == LP_DUAL_RATIO_LONG_STEP; }
+
 // Host-side combinatorics shared by the enumeration paths (exact u64; 0 = overflow).
 uint64_t lp_host_binom(int n, int k);
 // rank, among the t-subsets of {0 .. n-m+t-1}, of the first t elements of the rank-th m-subset of

@@ -1,6 +1,6 @@
 // simplex_bounded_driver.hip — the host side of the bounded-variable simplex on the tableau in HBM, for LPs beyond one
 // workgroup's LDS: lp_simplex_bounded_large, lp_simplex_bounded_resolve_large (both also as _ex under a pivot rule, the
-// re-solve as _dual_ex under a dual pricing rule too) and lp_mip_bounded_solve_large (as _ex with tableau snapshots for
+// re-solve as _dual_ex under a dual pricing rule and as _ratio_ex under a dual ratio test too) and lp_mip_bounded_solve_large (as _ex with tableau snapshots for
 // the second children).  The selectors are simplex_bounded_launch.hip's, the search's kernels
 // mip_bounded_large.hip's; the problem record, the upload and the two-phase pieces are simplex_driver.hip's.
 #include <algorithm>
@@ -92,14 +92,16 @@ int bounded_large_state(lp_simplex_problem* p, lp_device_buffer& buf, BoundedLar
 // One loop on the tableau of p: the bounded selector + rank-1 update pair per iteration, polled by lp_poll_pivots.
 // *iters = its pivots plus flips, *flips = the flips since the start of the solve.  rule: the primal selector (Devex:
 // the weights are reset on the stream first).  dual: the dual selector of dual_rule in its place (lp_bounded_dual_prepare
-// has run for it; LP_DUAL_DEVEX: its m weights are reset on the stream first).
+// has run for it; LP_DUAL_DEVEX: its m weights are reset on the stream first) under dual_ratio (LP_DUAL_RATIO_LONG_STEP:
+// the dual loop flips too, and *iters stays its pivots alone).
 int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule, double eps, int max_iter, int* iters,
-                      int* flips, bool dual = false, int dual_rule = LP_DUAL_DANTZIG) {
+                      int* flips, bool dual = false, int dual_rule = LP_DUAL_DANTZIG,
+                      int dual_ratio = LP_DUAL_RATIO_TEXTBOOK) {
     lp_context* ctx = p->ctx;
     lp_launch_begin(p, eps, max_iter);
     if (!dual && rule == LP_PIVOT_DEVEX) lp_bounded_large_reset_weights(p, bd);
     if (dual && dual_rule == LP_DUAL_DEVEX) lp_bounded_large_reset_weights(p, bd, true);
-    int rc = lp_poll_pivots(p, [&](int batch) { return lp_bounded_large_queue(p, bd, batch, rule, dual, dual_rule); });
+    int rc = lp_poll_pivots(p, [&](int batch) { return lp_bounded_large_queue(p, bd, batch, rule, dual, dual_rule, dual_ratio); });
     if (rc) return rc;
     rc = lp_download(ctx, "lp_simplex_bounded_large", {{flips, bd.flips, sizeof(int)}});
     if (rc) return rc;
@@ -112,19 +114,23 @@ int run_bounded_phase(lp_simplex_problem* p, const BoundedLargeDev& bd, int rule
 // every basic variable is within its bounds, else the dual loop when the start is dual feasible, else LP_BAD_ARG under
 // who's name.  Returns the loop's status or a negative HIP error; count[0..2] += its dual pivots, primal pivots and
 // flips.  prepare_dual: opt the dual selector's LDS in on the dual branch (the re-solve; the search did it up front).
-// dual_rule: the pricing of the dual loop (the search passes none: Dantzig's).
+// dual_rule: the pricing of the dual loop (the search passes none: Dantzig's).  dual_ratio: its ratio test (the search
+// passes none: the textbook one); under LP_DUAL_RATIO_LONG_STEP the dual loop's flips are counted in count[2] too.
 int bounded_run_from_start(lp_simplex_problem* p, const BoundedLargeDev& bd, const char* who, int rule, double eps,
-                           int max_iter, bool prepare_dual, int* count, int dual_rule = LP_DUAL_DANTZIG) {
+                           int max_iter, bool prepare_dual, int* count, int dual_rule = LP_DUAL_DANTZIG,
+                           int dual_ratio = LP_DUAL_RATIO_TEXTBOOK) {
     int flags = 0, iters = 0, flips = 0;
     int rc = lp_bounded_large_classify(p, bd, eps, &flags);
     if (rc) return rc;
     const bool dual = flags & 1;
     if (dual && (flags & 2)) LP_FAIL(p->ctx, LP_BAD_ARG, std::string(who) + ": the basis is neither primal nor dual feasible");
-    if (dual && prepare_dual && (rc = lp_bounded_dual_prepare(p, dual_rule)) != LP_OPTIMAL) return rc;
-    rc = run_bounded_phase(p, bd, rule, eps, max_iter, &iters, &flips, dual, dual_rule);
+    if (dual && prepare_dual && (rc = lp_bounded_dual_prepare(p, dual_rule, dual_ratio)) != LP_OPTIMAL) return rc;
+    rc = run_bounded_phase(p, bd, rule, eps, max_iter, &iters, &flips, dual, dual_rule, dual_ratio);
     if (rc < 0) return rc;
     count[dual ? 0 : 1] += dual ? iters : iters - flips;
-    if (!dual) count[2] += flips;
+    // (flips counts since the start of the solve, and the search runs textbook dual loops after primal ones on one
+    // bound state: only a loop that flips may add it, or the primal loop's flips would be counted again)
+    if (!dual || dual_ratio == LP_DUAL_RATIO_LONG_STEP) count[2] += flips;
     return rc;
 }
 
@@ -551,10 +557,25 @@ int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, i
                                              const int* at_upper_in, int maximize, int n_orig, double eps,
                                              int max_iter, double* x_out, int* basis_out, int* at_upper_out,
                                              double* obj_out, int* iters_out, int pivot_rule, int dual_rule) {
+    return lp_simplex_bounded_resolve_large_ratio_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig,
+                                                     eps, max_iter, x_out, basis_out, at_upper_out, obj_out, iters_out,
+                                                     pivot_rule, dual_rule, LP_DUAL_RATIO_TEXTBOOK);
+}
+
+// The same with a choice of the dual loop's ratio test too (tests/ref/bounded_resolve_long_step_ref.c): dual_ratio picks
+// the textbook or the bound-flipping form of the dual selector and nothing else; under LP_DUAL_RATIO_TEXTBOOK every
+// launch is lp_simplex_bounded_resolve_large_dual_ex's.  iters_out[2] counts the dual loop's flips too.
+int lp_simplex_bounded_resolve_large_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b,
+                                              const double* c, const double* lo, const double* hi, const int* basis_in,
+                                              const int* at_upper_in, int maximize, int n_orig, double eps,
+                                              int max_iter, double* x_out, int* basis_out, int* at_upper_out,
+                                              double* obj_out, int* iters_out, int pivot_rule, int dual_rule,
+                                              int dual_ratio) {
     const char* who = "lp_simplex_bounded_resolve_large";
     const bool any_null = !x_out || !basis_out || !at_upper_out || !obj_out || !iters_out || !A || !b || !c || !lo ||
                           !hi || !basis_in || !at_upper_in;
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_ratio_known(dual_ratio)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown dual ratio test");
     if (!lp_dual_rule_known(dual_rule)) LP_FAIL(ctx, LP_BAD_ARG, std::string(who) + ": unknown dual rule");
     int rc = check_bounded_entry(ctx, who, pivot_rule, any_null, eps, m, n, n_orig, lo, hi);
     if (rc) return rc;
@@ -592,7 +613,7 @@ int lp_simplex_bounded_resolve_large_dual_ex(lp_context* ctx, const double* A, i
     rc = bounded_large_state(p, buf, bd, U.data(), up.data(), n, pivot_rule, dual_rule);
     if (rc) return rc;
     // steps 5 and 6: the loop the start allows (a refusal or a HIP error leaves iters_out at zero)
-    rc = bounded_run_from_start(p, bd, who, pivot_rule, eps, max_iter, true, it, dual_rule);
+    rc = bounded_run_from_start(p, bd, who, pivot_rule, eps, max_iter, true, it, dual_rule, dual_ratio);
     if (rc < 0 || rc == LP_BAD_ARG) return rc;
     int rd = rc == LP_OPTIMAL ? lp_simplex_download(p, xa.data(), N.data(), nullptr, nullptr, nullptr, 0, nullptr)
                               : download_basis(p, N.data());

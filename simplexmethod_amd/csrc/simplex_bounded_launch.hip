@@ -697,6 +697,209 @@ __global__ __launch_bounds__(1024) void k_simplex_select_dual_bounded_devex(Simp
     }
 }
 
+// ---------------------------------------------------------------------------
+// The two bounded dual selectors with the bound-flipping ratio test (LP_DUAL_RATIO_LONG_STEP;
+// tests/ref/bounded_resolve_long_step_ref.c is the definition).  DEVEX = false: the leaving choice of
+// k_simplex_select_dual_bounded; true: that of k_simplex_select_dual_bounded_devex with its weight update.  The
+// complement, the first entering chain with its quotients in bd.q, the staging and the trace are theirs.
+//   round:    column e goes to LDS (it is staged from there if the round ends in the pivot).  With a the entry of the
+//             complemented row r and xbr its right-hand side, both as this launch has left them, e is flipped when
+//             U_e is finite and fma(-U_e, a, xbr) < -eps: row r stays violated with e at its other bound;
+//   flip:     the primal selector's, by the whole workgroup, rows 0 .. m (strided beyond 1024, the cost row included):
+//             T[i][n] = fma(-U_e, T[i][e], T[i][n]), T[i][e] negated; up[e] toggles and bd.flips counts it.  Row r's
+//             complement is virtual here, so its entry of column e is flipped as the complemented view sees it
+//             (a = -T[r][e]; the stored T[r][e] is negated like every other row's) and its right-hand side lives in
+//             xbr alone, which every thread carries through the same operations and which is staged as prow[n]; the
+//             stored T[r][n] of a complemented row is left as it was, for k_simplex_update writes row r from prow;
+//   rescan:   q[e] = +inf, a barrier, and block_chain_select again over bd.q as it stands: the flipped column has
+//             a > eps now and nothing else of row r or of the cost row has changed, so this is the reference's rescan.
+//             None left: infeasible, with the flips made and the complement's flag kept.
+// st->iters counts the dual pivots only, as max_iter bounds them; a launch makes at most n flips.
+// LDS: that of the selector it extends; no more.
+// ---------------------------------------------------------------------------
+// The two pieces of k_simplex_select_dual_bounded_long that restate the textbook selectors, which themselves stay as
+// they are.  Every thread of the 1024-thread workgroup calls them.
+// The leaving choice of k_simplex_select_dual_bounded_devex: xB goes to s_x, the result is the same in every thread
+// (-1: no position violated).
+__device__ __forceinline__ int dual_devex_leaving(const SimplexDev& d, const BoundedLargeDev& bd, double eps, double* s_x,
+                                                  double* s_score, int* s_pos) {
+    const int tid = threadIdx.x, m = d.m, n = d.n, ld = d.ld;
+    double best = -1.0;
+    int r = INT_MAX;
+    for (int t = tid; t < m; t += blockDim.x) {
+        const double xb = d.T[(size_t)t * ld + n], u = bd.U[d.basis[t]], wt = bd.w[t];
+        s_x[t] = xb;
+        const double v = (xb < -eps) ? xb : u - xb;
+        const double s = (v * v) / wt;
+        if ((xb < -eps || (u < INFINITY && v < -eps)) && s > best) {
+            best = s;   // t ascending per thread: strict > keeps the smallest position
+            r = t;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int op = __shfl_xor(r, off, 64);
+        if (ob > best || (ob == best && op < r)) {
+            best = ob;
+            r = op;
+        }
+    }
+    if ((tid & 63) == 0) {
+        s_score[tid >> 6] = best;
+        s_pos[tid >> 6] = r;
+    }
+    __syncthreads();
+    best = s_score[0];
+    r = s_pos[0];
+    for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
+        if (s_score[q] > best || (s_score[q] == best && s_pos[q] < r)) {
+            best = s_score[q];
+            r = s_pos[q];
+        }
+    return r == INT_MAX ? -1 : r;
+}
+
+// The staging of the pivot on (r, e) for k_simplex_update, as the textbook selectors do it, from column e in s_v:
+// ur is the entry of the (complemented) row r in column e and xbr that row's right-hand side, which goes to prow[n]
+// as carried, not as stored.
+__device__ __forceinline__ void dual_long_stage(const SimplexDev& d, const BoundedLargeDev& bd, int r, int e, int old,
+                                                bool comp, double ur, double xbr, const double* s_v) {
+    SimplexState* st = d.state;
+    const int tid = threadIdx.x, m = d.m, n = d.n, ld = d.ld;
+    const double* trow = d.T + (size_t)r * ld;
+    for (int i = tid; i <= m; i += blockDim.x) d.lcol[i] = (i == r) ? 1.0 / ur : -s_v[i] / ur;
+    for (int j = tid; j < ld; j += blockDim.x) {
+        double v = trow[j];
+        if (comp) v = (j < n) ? -v : v;
+        if (j == n) v = xbr;
+        if (j == old) v = 1.0;   // the leaving variable's own column: the unit column again (a no-op without comp)
+        d.prow[j] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (comp) bd.up[old] ^= 1;
+        d.basis[r] = e;
+        d.nonbasic[e] = 0;
+        d.nonbasic[old] = 1;
+        const int it = st->iters;
+        if (it < d.trace_cap) {
+            d.trace_enter[it] = e;
+            d.trace_leave[it] = r;
+        }
+        st->iters = it + 1;
+        st->enter = e;
+        st->leave = r;
+        st->pivot_valid = 1;
+    }
+}
+
+template <bool DEVEX>
+__global__ __launch_bounds__(1024) void k_simplex_select_dual_bounded_long(SimplexDev d, BoundedLargeDev bd) {
+    SimplexState* st = d.state;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    double* s_v = s_dyn;                     // m + 2: v_t (Dantzig), afterwards column e
+    double* s_x = s_dyn + (d.m + 2);         // m (+ 2 of padding): xB
+    lpdev::BlockChainScratch* sc = reinterpret_cast<lpdev::BlockChainScratch*>(s_dyn + 2 * (d.m + 2));
+    double* s_score = reinterpret_cast<double*>(sc + 1);   // DEVEX: the sixteen wave results of the leaving choice
+    int* s_pos = reinterpret_cast<int*>(s_score + 16);
+
+    const int tid = threadIdx.x;
+    if (st->status != kRunning) {
+        if (tid == 0) st->pivot_valid = 0;
+        return;
+    }
+    const int m = d.m, n = d.n, ld = d.ld;
+    const double eps = st->eps;
+    if (st->iters >= st->max_iter) {
+        if (tid == 0) {
+            st->status = LP_ITER_LIMIT;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // leaving position
+    double best;
+    int r;
+    if constexpr (DEVEX) {
+        r = dual_devex_leaving(d, bd, eps, s_x, s_score, s_pos);
+    } else {
+        auto violation = [&](int t) {
+            const double xb = d.T[(size_t)t * ld + n], u = bd.U[d.basis[t]];
+            s_x[t] = xb;
+            return (xb < -eps) ? xb : (u < INFINITY && u - xb < -eps) ? u - xb : INFINITY;
+        };
+        r = lpdev::block_chain_select<false, true>(m, eps, best, violation, s_v, sc);
+    }
+    if (r < 0) {
+        if (tid == 0) {
+            st->status = LP_OPTIMAL;
+            st->pivot_valid = 0;
+        }
+        return;
+    }
+    // (every thread reads basis[r], w[r] and nonbasic[] before the barriers below; they are written after the last)
+    const int old = d.basis[r];
+    const double wr = DEVEX ? bd.w[r] : 0.0;
+    const bool comp = !(s_x[r] < -eps);   // violated above: the complement of N(r) is what is below 0
+    const double uold = bd.U[old];
+    double xbr = comp ? uold - s_x[r] : s_x[r];   // the complemented row's right-hand side, the same in every thread
+    // entering column
+    const double* trow = d.T + (size_t)r * ld;
+    const double* drow = d.T + (size_t)m * ld;
+    const bool maxi = d.maximize != 0;
+    auto quotient = [&](int j) {
+        const double t = trow[j], a = comp ? -t : t;
+        if (!(d.nonbasic[j] != 0 && a < -eps)) return (double)INFINITY;
+        return maxi ? drow[j] / a : -drow[j] / a;
+    };
+    int e = lpdev::block_chain_select<false, true>(n, eps, best, quotient, bd.q, sc);
+    double ur;
+    for (;;) {
+        if (e < 0) {   // row r sums non-negative terms to a negative right-hand side, at either bound of every column
+            if (tid == 0) {
+                if (comp) bd.up[old] ^= 1;
+                st->status = LP_INFEASIBLE;
+                st->pivot_valid = 0;
+            }
+            return;
+        }
+        // column e; the entry of the complemented row r changes sign with it
+        for (int i = tid; i <= m; i += blockDim.x) s_v[i] = d.T[(size_t)i * ld + e];
+        __syncthreads();
+        ur = comp ? -s_v[r] : s_v[r];
+        const double ue = bd.U[e];
+        if (!(ue < INFINITY && fma(-ue, ur, xbr) < -eps)) break;
+        // bound flip: row r stays violated with e at its other bound
+        for (int i = tid; i <= m; i += blockDim.x) {
+            const size_t row = (size_t)i * ld;
+            if (i != r || !comp) d.T[row + n] = fma(-ue, s_v[i], d.T[row + n]);
+            d.T[row + e] = -s_v[i];
+        }
+        xbr = fma(-ue, ur, xbr);
+        if (tid == 0) {
+            bd.up[e] ^= 1;
+            *bd.flips += 1;
+            bd.q[e] = INFINITY;
+        }
+        __syncthreads();   // q[e], and every read of s_v, ahead of the next round
+        e = lpdev::block_chain_select<false, false>(n, eps, best, [&](int j) { return bd.q[j]; }, bd.q, sc);
+    }
+    // stage the pivot on (r, e); under Devex the weights move with it
+    if constexpr (DEVEX) {
+        for (int i = tid; i < m; i += blockDim.x) {
+            if (i == r) {
+                bd.w[i] = fmax(wr / (ur * ur), 1.0);
+            } else {
+                const double g = s_v[i] / ur;
+                const double cand = (g * g) * wr;
+                if (cand > bd.w[i]) bd.w[i] = cand;
+            }
+        }
+    }
+    dual_long_stage(d, bd, r, e, old, comp, ur, xbr, s_v);
+}
+
 // Which loop lp_simplex_bounded_resolve_large runs: the bounded form of k_simplex_classify.  st->pad0 = bit 0 some
 // basis position violated (xB_t < -eps, or U_N(t) finite and U_N(t) - xB_t < -eps), bit 1 dual infeasible (some
 // non-basic d_j > eps for max, d_j < -eps for min).  One workgroup.
@@ -733,6 +936,13 @@ BoundedSelector bounded_selector(int rule) {
                                     : k_simplex_select_bounded;
 }
 
+// (the long-step forms need the LDS of the selector they extend: select_dual_bounded_lds_bytes by dual_rule)
+BoundedSelector bounded_dual_selector(int dual_rule, int dual_ratio) {
+    if (dual_ratio == LP_DUAL_RATIO_LONG_STEP)
+        return dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_long<true> : k_simplex_select_dual_bounded_long<false>;
+    return dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_devex : k_simplex_select_dual_bounded;
+}
+
 }  // namespace
 
 int lp_bounded_large_prepare(lp_simplex_problem* p, int rule) {
@@ -748,11 +958,9 @@ void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev
 }
 
 int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual,
-                           int dual_rule) {
+                           int dual_rule, int dual_ratio) {
     const size_t shm = dual ? select_dual_bounded_lds_bytes(p, dual_rule) : select_bounded_lds_bytes(p, rule);
-    const BoundedSelector select = !dual                         ? bounded_selector(rule)
-                                   : dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_devex
-                                                                : k_simplex_select_dual_bounded;
+    const BoundedSelector select = dual ? bounded_dual_selector(dual_rule, dual_ratio) : bounded_selector(rule);
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(select, 1, 1024, shm, p->ctx->stream, p->dev, bd);
         lp_simplex_launch_update(p);
@@ -771,11 +979,10 @@ int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, 
     return LP_OPTIMAL;
 }
 
-int lp_bounded_dual_prepare(lp_simplex_problem* p, int dual_rule) {
+int lp_bounded_dual_prepare(lp_simplex_problem* p, int dual_rule, int dual_ratio) {
     const size_t shm = select_dual_bounded_lds_bytes(p, dual_rule);
     if (shm > 156 * 1024)
         LP_FAIL(p->ctx, LP_BAD_ARG, "lp_simplex_bounded_resolve_large: m too large for the dual selector's LDS");
-    const BoundedSelector select = dual_rule == LP_DUAL_DEVEX ? k_simplex_select_dual_bounded_devex : k_simplex_select_dual_bounded;
-    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(select), shm));
+    LP_HIP(p->ctx, lp_lds_opt_in(reinterpret_cast<const void*>(bounded_dual_selector(dual_rule, dual_ratio)), shm));
     return LP_OPTIMAL;
 }

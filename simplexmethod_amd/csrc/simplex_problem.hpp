@@ -168,16 +168,17 @@ struct BoundedLargeDev {
 };
 // rule: LP_PIVOT_DANTZIG (k_simplex_select_bounded), LP_PIVOT_BLAND or LP_PIVOT_DEVEX, checked by the caller; dual:
 // the bounded dual selector in that selector's place (no pivot rule reaches it; lp_bounded_dual_prepare first), under
-// dual_rule: LP_DUAL_DANTZIG (k_simplex_select_dual_bounded) or LP_DUAL_DEVEX, checked by the caller
+// dual_rule: LP_DUAL_DANTZIG (k_simplex_select_dual_bounded) or LP_DUAL_DEVEX, and dual_ratio: LP_DUAL_RATIO_TEXTBOOK
+// (those two selectors) or LP_DUAL_RATIO_LONG_STEP (their bound-flipping forms), both checked by the caller
 int lp_bounded_large_prepare(lp_simplex_problem* p, int rule);   // that selector's LDS: checked, opted in
 int lp_bounded_large_queue(lp_simplex_problem* p, const BoundedLargeDev& bd, int batch, int rule, bool dual,
-                           int dual_rule = LP_DUAL_DANTZIG);
+                           int dual_rule = LP_DUAL_DANTZIG, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK);
 // queued, all 1.0: the dev.n weights of a primal loop, or (dual) the dev.m of a dual loop
 void lp_bounded_large_reset_weights(lp_simplex_problem* p, const BoundedLargeDev& bd, bool dual = false);
 // The re-solve (lp_simplex_bounded_resolve_large).  classify: *flags = bit 0 some basis position outside its bounds,
 // bit 1 dual infeasible (one host sync); the dual path then queues the bounded dual selector + rank-1 update.
 int lp_bounded_large_classify(lp_simplex_problem* p, const BoundedLargeDev& bd, double eps, int* flags);
-int lp_bounded_dual_prepare(lp_simplex_problem* p, int dual_rule = LP_DUAL_DANTZIG);
+int lp_bounded_dual_prepare(lp_simplex_problem* p, int dual_rule = LP_DUAL_DANTZIG, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK);
 
 // mip_bounded_large.hip: the device side of lp_mip_bounded_solve_large's search (tests/ref/mip_bounded_ref.c steps 2
 // to 5).  What a solved node was, written by the node kernel into pinned host memory:

@@ -42,6 +42,11 @@ public:
     // position leaves (Dantzig, the default), or the one of largest violation^2 / reference weight (Devex), which
     // takes fewer dual pivots on LPs of many rows (include/simplexmethod_amd.h, LP_DUAL_*).
     enum class DualRule { Dantzig = LP_DUAL_DANTZIG, Devex = LP_DUAL_DEVEX };
+    // The ratio test of that dual simplex: the column of smallest ratio enters whatever its own box (Textbook, the
+    // default), or a candidate whose flip to its other bound leaves the leaving row violated is flipped, O(m), and the
+    // next one looked at (LongStep, the bound-flipping ratio test), which takes fewer dual pivots on boxed LPs
+    // (include/simplexmethod_amd.h, LP_DUAL_RATIO_*).
+    enum class DualRatio { Textbook = LP_DUAL_RATIO_TEXTBOOK, LongStep = LP_DUAL_RATIO_LONG_STEP };
 
     explicit Solver(const Canonical& problem, int device = 0) : _problem(problem), _device(device) {}
 
@@ -314,6 +319,23 @@ public:
                                       const BoundedResult& from, PivotRule rule, DualRule dual,
                                       bool throw_on_failure = true) const {
         return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, &rule, throw_on_failure, true, &dual);
+    }
+
+    // boundedResolve under a dual ratio test too (lp_simplex_bounded_resolve_ratio_ex): `ratio` governs the entering
+    // step of the dual simplex only.  DualRatio::Textbook is the form above bit for bit; under DualRatio::LongStep
+    // status and objective are its up to rounding, and iterations[2] counts the dual simplex's bound flips.
+    BoundedResult boundedResolve(const std::vector<double>& lo, const std::vector<double>& hi,
+                                 const BoundedResult& from, PivotRule rule, DualRule dual, DualRatio ratio,
+                                 bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolve", lo, hi, &from, &rule, throw_on_failure, false, &dual, &ratio);
+    }
+
+    // The same at any shape boundedSimplexLarge runs (lp_simplex_bounded_resolve_large_ratio_ex).  Equal to
+    // boundedResolve(lo, hi, from, rule, dual, ratio) where both run.
+    BoundedResult boundedResolveLarge(const std::vector<double>& lo, const std::vector<double>& hi,
+                                      const BoundedResult& from, PivotRule rule, DualRule dual, DualRatio ratio,
+                                      bool throw_on_failure = true) const {
+        return boundedRun("Solver::boundedResolveLarge", lo, hi, &from, &rule, throw_on_failure, true, &dual, &ratio);
     }
 
     // The dual solution of the bounded problem at a result's basis and flags (lp_basis_bounded_duals), in the original
@@ -730,10 +752,10 @@ private:
 
     // boundedSimplex (from null) or boundedResolve, through the entry without a rule (rule null) or its _ex form;
     // large: boundedSimplexLarge, or with from boundedResolveLarge, the same way; dual (with from and rule): the
-    // re-solve's _dual_ex form
+    // re-solve's _dual_ex form; ratio (with dual): its _ratio_ex form
     BoundedResult boundedRun(const char* who, const std::vector<double>& lo, const std::vector<double>& hi,
                              const BoundedResult* from, const PivotRule* rule, bool throw_on_failure,
-                             bool large = false, const DualRule* dual = nullptr) const {
+                             bool large = false, const DualRule* dual = nullptr, const DualRatio* ratio = nullptr) const {
         const View p = view();
         requireBounds(who, p, lo, hi);
         if (from) requireStart(who, "start", p, *from);
@@ -742,7 +764,12 @@ private:
         out.basis.assign((size_t)p.m, -1);
         out.atUpper.assign((size_t)p.n, 0);
         lp_context* ctx = lpgpu::context(_device);
-        if (from && rule && dual) {
+        if (from && rule && dual && ratio) {
+            const auto entry = large ? lp_simplex_bounded_resolve_large_ratio_ex : lp_simplex_bounded_resolve_ratio_ex;
+            out.status = entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from->basis.data(),
+                               from->atUpper.data(), p.maximize, p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
+                               out.atUpper.data(), &out.objective, out.iterations, (int)*rule, (int)*dual, (int)*ratio);
+        } else if (from && rule && dual) {
             const auto entry = large ? lp_simplex_bounded_resolve_large_dual_ex : lp_simplex_bounded_resolve_dual_ex;
             out.status = entry(ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from->basis.data(),
                                from->atUpper.data(), p.maximize, p.no, EPS, MAX_ITER, out.x.data(), out.basis.data(),
