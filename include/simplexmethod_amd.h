@@ -709,9 +709,11 @@ int lp_simplex_bounded_rule_fits(int m, int n, int pivot_rule);
  * Shapes: the two LDS entries need lp_simplex_bounded_dual_rule_fits (else LP_BAD_ARG, nothing launched).  The _large
  * entry keeps its m weights in device memory and has no such limit; its Devex dual selector keeps sixteen wave results
  * more in LDS than the plain one: m <= 9957 in the dual branch under LP_DUAL_DEVEX.
- * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large and _large_ex, whose snapshots
- * change where a second child starts and not how a node is priced) and the parametric paths keep Dantzig's dual rule,
- * and the unbounded lp_simplex_resolve family is not touched.                                                         */
+ * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large and _large_ex, and their _ratio_ex
+ * forms below) and the parametric paths keep Dantzig's dual rule, and the unbounded lp_simplex_resolve family is not
+ * touched.  In the search the rule was measured on the host and left out: a node's dual loop is a handful of pivots,
+ * too short for reference weights that restart at 1.0 to matter (32 435 dual pivots against 32 109 over 1800 nodes at
+ * 32 x 96, under 2 % either way at every shape tried).                                              */
 enum { LP_DUAL_DANTZIG = 0, LP_DUAL_DEVEX = 1 };
 int lp_simplex_bounded_resolve_dual_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule);
 int lp_simplex_bounded_resolve_batched_dual_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule);
@@ -741,9 +743,10 @@ int lp_simplex_bounded_dual_rule_fits(int m, int n, int pivot_rule, int dual_rul
  * Any other dual_ratio is LP_BAD_ARG before anything else is looked at, and no output is written.
  * Shapes: the long-step kernels need no LDS beyond their textbook forms: lp_simplex_bounded_dual_rule_fits for the two
  * LDS entries, and the _large entry's limits on m are those of its _dual_ex entry.
- * Not covered: the branch-and-bound entries (lp_mip_bounded_solve, _batched, _large and _large_ex) and the parametric
- * paths keep the textbook ratio test, and the unbounded lp_simplex_resolve family (no boxes, so nothing to flip) is
- * not touched.                                                                                                      */
+ * The branch-and-bound over the bounds takes the same choice through lp_mip_bounded_solve_ratio_ex, _batched_ratio_ex
+ * and _large_ratio_ex (below); its entries without that suffix keep the textbook test, and every one of them keeps
+ * Dantzig's primal and dual pricing.  Not covered: the parametric paths keep the textbook ratio test, and the unbounded
+ * lp_simplex_resolve family (no boxes, so nothing to flip) is not touched.                                          */
 enum { LP_DUAL_RATIO_TEXTBOOK = 0, LP_DUAL_RATIO_LONG_STEP = 1 };
 int lp_simplex_bounded_resolve_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int pivot_rule, int dual_rule, int dual_ratio);
 int lp_simplex_bounded_resolve_batched_ratio_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, double eps, int max_iter, double* x_out, int* basis_out, int* at_upper_out, double* obj_out, int* iters_out, int* status_out, int pivot_rule, int dual_rule, int dual_ratio);
@@ -812,6 +815,28 @@ int lp_mip_bounded_fits(int m, int n, int max_depth);
  *     a rebuilt one crashes its basis afresh.  Dantzig's rules here too.                                             */
 int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out);
 int lp_mip_bounded_solve_large_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int snapshots);
+/* The three searches above with a choice of the ratio test of their dual loops (the definition is
+ * tests/ref/mip_bounded_long_step_ref.c, which every output, the counters included, equals bit for bit).  Each takes
+ * the arguments of lp_mip_bounded_solve, lp_mip_bounded_solve_batched or lp_mip_bounded_solve_large_ex (stats_out[7],
+ * snapshots) with dual_ratio appended.
+ *   - LP_DUAL_RATIO_TEXTBOOK launches exactly what the entry without the suffix launches and equals it in every
+ *     output; those entries are these with LP_DUAL_RATIO_TEXTBOOK.
+ *   - LP_DUAL_RATIO_LONG_STEP: every dual loop of the search, the install's at the root and at a rebuilt second child,
+ *     a first child's on the live tableau and a restored second child's, enters by the bound-flipping ratio test of
+ *     lp_simplex_bounded_resolve_ratio_ex under Dantzig's dual rule.  stats_out[3] counts the dual loops' flips as well
+ *     as the primal loops'.  max_iter bounds a node's dual pivots alone in a dual loop (a dual iteration makes at most
+ *     n flips) and its pivots plus flips in a primal loop, as before.  A node whose dual loop runs out of candidates,
+ *     after flips or without one, is LP_INFEASIBLE and the search goes on.  A level's record, and its snapshot if any,
+ *     are taken before the child's bound change, so a child's flips are in neither.  Node order, branching and pruning
+ *     are unchanged; the nodes solved, the incumbent's last bits and the counters may differ from the textbook
+ *     search's, and the objectives agree within gap plus rounding wherever both end LP_OPTIMAL.
+ *   - Any other dual_ratio is LP_BAD_ARG before anything else is looked at, and no output is written.
+ * Shapes: the long-step kernel needs no LDS beyond the textbook one, so lp_mip_bounded_fits is the limit of both LDS
+ * entries; the _large entry's limits are lp_mip_bounded_solve_large_ex's.  Pricing stays Dantzig's, primal and dual
+ * (see LP_DUAL_DEVEX above for the measured reason).                                                                */
+int lp_mip_bounded_solve_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int dual_ratio);
+int lp_mip_bounded_solve_batched_ratio_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, const int* root_status, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int* status_out, int dual_ratio);
+int lp_mip_bounded_solve_large_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out, int snapshots, int dual_ratio);
 /* Host call, no context.  *bytes_out = the device bytes `snapshots` slots take at m x n: snapshots x 8 x ((m + 1) ld +
  * 2 n2) with ld = n + 1 rounded up to a multiple of 8 and n2 = n rounded up to a multiple of 2 (the tableau's padded
  * rows, then U and the node's lo).

@@ -158,6 +158,9 @@ REFS = {
     "bounded_resolve_dual_rules": ("bounded_resolve_rules", "bounded_resolve", "bounded", "bounded_rules"),
     "bounded_resolve_long_step": ("bounded_resolve_dual_rules", "bounded_resolve_rules", "bounded_resolve", "bounded",
                                   "bounded_rules"),
+    "mip_bounded_long_step": ("mip_bounded_snapshots", "mip_bounded", "bounded_resolve_long_step",
+                              "bounded_resolve_dual_rules", "bounded_resolve_rules", "bounded_resolve", "bounded",
+                              "bounded_rules"),
 }
 
 
@@ -201,6 +204,7 @@ build_bounded_rules_ref = functools.partial(build_ref, "bounded_rules")
 build_bounded_resolve_rules_ref = functools.partial(build_ref, "bounded_resolve_rules")
 build_bounded_resolve_dual_rules_ref = functools.partial(build_ref, "bounded_resolve_dual_rules")
 build_bounded_resolve_long_step_ref = functools.partial(build_ref, "bounded_resolve_long_step")
+build_mip_bounded_long_step_ref = functools.partial(build_ref, "mip_bounded_long_step")
 
 
 def build_all(force=False, verbose=False):

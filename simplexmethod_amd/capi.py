@@ -205,6 +205,16 @@ SIGNATURES = {
                                                 C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                                 C.c_int, _dp, _dp, _dp, _ip, _ip, C.c_int]),
     "lp_mip_bounded_snapshot_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, _u64p]),
+    "lp_mip_bounded_solve_ratio_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                C.c_int, _dp, _dp, _dp, _ip, _ip, C.c_int]),
+    "lp_mip_bounded_solve_batched_ratio_ex": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip,
+                                                        _ip, _ip, C.c_int, C.c_int, _ip, C.c_double, C.c_double,
+                                                        C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip,
+                                                        _ip, C.c_int]),
+    "lp_mip_bounded_solve_large_ratio_ex": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int,
+                                                      C.c_int, _ip, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                      C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int]),
     "lp_basis_bounded_duals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
     "lp_basis_bounded_duals_batched": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                  _dp, _dp, _dp, _dp, _ip]),
@@ -1184,31 +1194,39 @@ class Context:
     # ---- branch-and-bound over the bounds of a bounded-variable LP -----------------------------
     def mip_bounded_solve(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,
                           int_tol=INT_TOL, gap=GAP, max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES,
-                          max_iter=MAX_ITER):
+                          max_iter=MAX_ITER, dual_ratio=None):
         """lp_mip_bounded_solve: opt c.x, A x = b, lo <= x <= hi, x_j integral where integer[j] (n entries, 0/1,
         j < n_orig), searched by changing bounds from `basis` (m) and `at_upper` (n), normally bounded()'s result.
         dict(status, found, x (n_orig), obj, bound, stats (nodes, dual pivots, primal pivots, bound flips, deepest
         level)); x and obj NaN without an incumbent.  A start that is no valid one, a fractional bound on a marked
-        column, a bad argument or a shape beyond mip_bounded_fits raises LPError with code BAD_ARG."""
+        column, a bad argument or a shape beyond mip_bounded_fits raises LPError with code BAD_ARG.
+        dual_ratio ("textbook", "long_step" or a DUAL_RATIO_* value; None: the call made without it) goes through
+        lp_mip_bounded_solve_ratio_ex and picks the ratio test of every dual loop of the search; under "long_step"
+        stats[3] counts the dual loops' flips too."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
         integer = _mask(integer, n)
         x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5)
-        rc = self.check(self.lib.lp_mip_bounded_solve(self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis),
-                                                      _i(at_upper), int(maximize), n_orig, _i(integer), float(eps),
-                                                      float(int_tol), float(gap), int(max_depth), int(max_nodes),
-                                                      int(max_iter), _d(x), _d(obj), _d(bound), _i(found), _i(stats)))
+        args = (self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
+                _i(integer), float(eps), float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter),
+                _d(x), _d(obj), _d(bound), _i(found), _i(stats))
+        if dual_ratio is None:
+            rc = self.check(self.lib.lp_mip_bounded_solve(*args))
+        else:
+            rc = self.check(self.lib.lp_mip_bounded_solve_ratio_ex(*args, dual_ratio_id(dual_ratio)))
         return dict(status=rc, found=int(found[0]), x=x[0], obj=float(obj[0]), bound=float(bound[0]),
                     stats=tuple(int(v) for v in stats[0]))
 
     def mip_bounded_solve_batched(self, A, b, c, lo, hi, integer, basis=None, at_upper=None, root_status=None,
                                   maximize=True, n_orig=None, eps=EPS, int_tol=INT_TOL, gap=GAP,
-                                  max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES, max_iter=MAX_ITER):
+                                  max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES, max_iter=MAX_ITER,
+                                  dual_ratio=None):
         """lp_mip_bounded_solve_batched: arrays as bounded_resolve_batched(), one mask (n); root_status (batch) or
         None.  basis=None runs bounded_batched() first and searches from its bases and flags, its statuses passed as
         root_status: an LP whose cold solve is not OPTIMAL keeps that status.  dict(status, found, obj, bound (batch),
-        x (batch, n_orig), stats (batch, 5))."""
+        x (batch, n_orig), stats (batch, 5)).  dual_ratio as mip_bounded_solve() (lp_mip_bounded_solve_batched_ratio_ex);
+        the cold solve of the basis=None chain has no dual loop and is the same under every value."""
         n_orig = np.shape(A)[2] if n_orig is None else int(n_orig)
         if basis is None:
             if at_upper is not None or root_status is not None:
@@ -1228,37 +1246,46 @@ class Context:
         integer = _mask(integer, n)
         out = _mip_out(batch, n_orig, 5)
         x, obj, bound, found, stats, st = out
-        self.check(self.lib.lp_mip_bounded_solve_batched(
-            self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
-            _i(root_status), int(maximize), n_orig, _i(integer), float(eps),
-            float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter), _d(x), _d(obj), _d(bound),
-            _i(found), _i(stats), _i(st)))
+        args = (self.h, batch, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper),
+                _i(root_status), int(maximize), n_orig, _i(integer), float(eps),
+                float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter), _d(x), _d(obj), _d(bound),
+                _i(found), _i(stats), _i(st))
+        if dual_ratio is None:
+            self.check(self.lib.lp_mip_bounded_solve_batched(*args))
+        else:
+            self.check(self.lib.lp_mip_bounded_solve_batched_ratio_ex(*args, dual_ratio_id(dual_ratio)))
         return _mip_dict(out)
 
     def mip_bounded_solve_large(self, A, b, c, lo, hi, basis, at_upper, integer, maximize=True, n_orig=None, eps=EPS,
                                 int_tol=INT_TOL, gap=GAP, max_depth=MAX_DEPTH_BOUNDED, max_nodes=MAX_NODES,
-                                max_iter=MAX_ITER, snapshots=None):
+                                max_iter=MAX_ITER, snapshots=None, dual_ratio=None):
         """lp_mip_bounded_solve_large: mip_bounded_solve() on the tableau in HBM, at any shape
         bounded_resolve_large() runs (no mip_bounded_fits limit; m <= 9960).  Arguments, the dict returned and the
         refusals are mip_bounded_solve()'s, and at a shape that also fits LDS so is every value.
         snapshots = K (an int in [0, 1024]): lp_mip_bounded_solve_large_ex, which keeps up to min(K, max_depth)
         tableau snapshots on the device (mip_bounded_snapshot_bytes says how large) and starts a second child from its
         parent's final tableau where its level's snapshot is still there; stats then has seven entries, the last two
-        the second children restored and rebuilt.  K = 0 equals the call without the argument."""
+        the second children restored and rebuilt.  K = 0 equals the call without the argument.
+        dual_ratio as mip_bounded_solve(): lp_mip_bounded_solve_large_ratio_ex (with snapshots=None: no snapshots, and
+        the five counters are returned)."""
         p = pack_lp(A, b, c, basis, lo, hi, at_upper)
         m, n, Af, b, c, basis, lo, hi, at_upper = p.m, p.n, p.A, p.b, p.c, p.basis, p.lo, p.hi, p.at_upper
         n_orig = n if n_orig is None else int(n_orig)
         integer = _mask(integer, n)
-        x, obj, bound, found, stats, _ = _mip_out(1, n_orig, 5 if snapshots is None else 7)
+        nstats = 5 if snapshots is None else 7
+        x, obj, bound, found, stats, _ = _mip_out(1, n_orig, nstats if dual_ratio is None else 7)
         args = (self.h, _d(Af), m, n, _d(b), _d(c), _d(lo), _d(hi), _i(basis), _i(at_upper), int(maximize), n_orig,
                 _i(integer), float(eps), float(int_tol), float(gap), int(max_depth), int(max_nodes), int(max_iter),
                 _d(x), _d(obj), _d(bound), _i(found), _i(stats))
-        if snapshots is None:
+        if dual_ratio is not None:
+            rc = self.check(self.lib.lp_mip_bounded_solve_large_ratio_ex(*args, int(snapshots or 0),
+                                                                         dual_ratio_id(dual_ratio)))
+        elif snapshots is None:
             rc = self.check(self.lib.lp_mip_bounded_solve_large(*args))
         else:
             rc = self.check(self.lib.lp_mip_bounded_solve_large_ex(*args, int(snapshots)))
         return dict(status=rc, found=int(found[0]), x=x[0], obj=float(obj[0]), bound=float(bound[0]),
-                    stats=tuple(int(v) for v in stats[0]))
+                    stats=tuple(int(v) for v in stats[0][:nstats]))
 
     def mip_bounded_snapshot_bytes(self, m, n, snapshots):
         """lp_mip_bounded_snapshot_bytes: the device bytes `snapshots` tableau snapshots of an m x n problem take."""

@@ -674,14 +674,14 @@ static int mip_bounded_args(lp_context* ctx, const char* who, int batch, const d
     return LP_OPTIMAL;
 }
 
-// Uploads `batch` problems with their starts, the mask and root_status (may be null), runs k_batched_mip_bounded and
-// downloads.
+// Uploads `batch` problems with their starts, the mask and root_status (may be null), runs k_batched_mip_bounded (its
+// _long form under LP_DUAL_RATIO_LONG_STEP) and downloads.
 static int mip_bounded_solve(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
                              const double* c, const double* lo, const double* hi, const int* basis_in,
                              const int* at_upper_in, const int* root_status, int maximize, int n_orig,
                              const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes,
                              int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out,
-                             int* stats_out, int* status_out) {
+                             int* stats_out, int* status_out, int dual_ratio) {
     const size_t B = (size_t)batch;
     lp_device_buffer buf;
     BoundedInputs in;
@@ -721,7 +721,7 @@ static int mip_bounded_solve(lp_context* ctx, int batch, const double* A, int m,
     if (e == hipSuccess && root_status)
         e = hipMemcpyAsync(droot, root_status, sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded MIP upload: ") + hipGetErrorString(e));
-    rc = lp_batched_mip_bounded_launch(ctx, d);
+    rc = lp_batched_mip_bounded_launch(ctx, d, dual_ratio);
     if (rc) return rc;
     e = hipGetLastError();
     if (e != hipSuccess) LP_FAIL(ctx, -(int)e, std::string("batched bounded MIP: ") + hipGetErrorString(e));
@@ -884,12 +884,25 @@ int lp_simplex_bounded_resolve_batched_ratio_ex(lp_context* ctx, int batch, cons
 
 int lp_mip_bounded_fits(int m, int n, int max_depth) { return lp_mip_bounded_fits_shape(m, n, max_depth) ? 1 : 0; }
 
+// The search over the bounds in LDS.  The entries without a suffix are the _ratio_ex ones under LP_DUAL_RATIO_TEXTBOOK;
+// an unknown dual_ratio is refused before anything else is looked at.
 int lp_mip_bounded_solve(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
                          const double* lo, const double* hi, const int* basis_in, const int* at_upper_in, int maximize,
                          int n_orig, const int* integer, double eps, double int_tol, double gap, int max_depth,
                          int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out,
                          int* found_out, int* stats_out) {
+    return lp_mip_bounded_solve_ratio_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, integer,
+                                         eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out,
+                                         found_out, stats_out, LP_DUAL_RATIO_TEXTBOOK);
+}
+
+int lp_mip_bounded_solve_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                  const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                                  int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
+                                  int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
+                                  double* bound_out, int* found_out, int* stats_out, int dual_ratio) {
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_ratio_known(dual_ratio)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: unknown dual ratio test");
     if (!x_out || !obj_out || !bound_out || !found_out || !stats_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: eps must be >= 0");
@@ -899,7 +912,7 @@ int lp_mip_bounded_solve(lp_context* ctx, const double* A, int m, int n, const d
     int status = LP_OPTIMAL;
     rc = mip_bounded_solve(ctx, 1, A, m, n, b, c, lo, hi, basis_in, at_upper_in, nullptr, maximize, n_orig, integer, eps,
                            int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out,
-                           &status);
+                           &status, dual_ratio);
     if (rc) return rc;
     if (status == LP_BAD_ARG) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve: the basis is neither primal nor dual feasible");
     return status;
@@ -911,7 +924,22 @@ int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, in
                                  const int* integer, double eps, double int_tol, double gap, int max_depth,
                                  int max_nodes, int max_iter, double* x_out, double* obj_out, double* bound_out,
                                  int* found_out, int* stats_out, int* status_out) {
+    return lp_mip_bounded_solve_batched_ratio_ex(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, root_status,
+                                                 maximize, n_orig, integer, eps, int_tol, gap, max_depth, max_nodes,
+                                                 max_iter, x_out, obj_out, bound_out, found_out, stats_out, status_out,
+                                                 LP_DUAL_RATIO_TEXTBOOK);
+}
+
+int lp_mip_bounded_solve_batched_ratio_ex(lp_context* ctx, int batch, const double* A, int m, int n, const double* b,
+                                          const double* c, const double* lo, const double* hi, const int* basis_in,
+                                          const int* at_upper_in, const int* root_status, int maximize, int n_orig,
+                                          const int* integer, double eps, double int_tol, double gap, int max_depth,
+                                          int max_nodes, int max_iter, double* x_out, double* obj_out,
+                                          double* bound_out, int* found_out, int* stats_out, int* status_out,
+                                          int dual_ratio) {
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_ratio_known(dual_ratio))
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_batched: unknown dual ratio test");
     if (!x_out || !obj_out || !bound_out || !found_out || !stats_out || !status_out)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_batched: null argument");
     if (!(eps >= 0.0)) LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_batched: eps must be >= 0");
@@ -921,7 +949,7 @@ int lp_mip_bounded_solve_batched(lp_context* ctx, int batch, const double* A, in
     if (rc) return rc;
     return mip_bounded_solve(ctx, batch, A, m, n, b, c, lo, hi, basis_in, at_upper_in, root_status, maximize, n_orig,
                              integer, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out,
-                             found_out, stats_out, status_out);
+                             found_out, stats_out, status_out, dual_ratio);
 }
 
 }  // extern "C"

@@ -340,7 +340,9 @@ struct BatchedMipBoundedDev {
 // batched_mip_bounded.hip
 size_t lp_mip_bounded_lds_bytes(int m, int n, int max_depth);
 bool lp_mip_bounded_fits_shape(int m, int n, int max_depth);
-int lp_batched_mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d);   // fitting shapes, else LP_BAD_ARG
+// fitting shapes, else LP_BAD_ARG; dual_ratio (LP_DUAL_RATIO_*) picks the ratio test of every dual loop of the search:
+// LP_DUAL_RATIO_LONG_STEP launches k_batched_mip_bounded_long (tests/ref/mip_bounded_long_step_ref.c), the same LDS
+int lp_batched_mip_bounded_launch(lp_context* ctx, const BatchedMipBoundedDev& d, int dual_ratio = LP_DUAL_RATIO_TEXTBOOK);
 
 // The dual solution and RHS / cost ranging of bounded-variable LPs at given bases and at-upper flags, one LP per
 // workgroup (basis_bounded.hip; the definition is tests/ref/bounded_sens_ref.c).  The duals launch writes x, y, d, w;

@@ -171,6 +171,7 @@ struct MipLargeCall {
     const double *A = nullptr, *c = nullptr;   // the caller's: the identity scan of an install reads them
     double eps = 0.0;
     int max_iter = 0;
+    int dual_ratio = LP_DUAL_RATIO_TEXTBOOK;   // the ratio test of every dual loop of the search
 };
 
 // Step 2 of the reference on a node's bounds, basis and flags: its status or a negative HIP error, stats[1..3] counted.
@@ -195,7 +196,8 @@ int mip_large_install(MipLargeCall& k, const char* who, const double* lov, const
     const int r = lp_simplex_install(p, N, identity, zero_costs);
     if (r) return r;
     if (p->init_status != LP_OPTIMAL) return p->init_status;   // LP_SINGULAR
-    return bounded_run_from_start(p, k.bd, who, LP_PIVOT_DANTZIG, k.eps, k.max_iter, false, stats + 1);
+    return bounded_run_from_start(p, k.bd, who, LP_PIVOT_DANTZIG, k.eps, k.max_iter, false, stats + 1, LP_DUAL_DANTZIG,
+                                  k.dual_ratio);
 }
 
 // One branching: the column, its value, the node's objective, which child went first, whether the second was taken
@@ -205,6 +207,24 @@ struct MipRecord {
 };
 
 bool mip_beats(int maximize, double z, double zs, double g) { return maximize ? (z > zs + g) : (z < zs - g); }
+
+// The dual loop of a first child or of a restored second child, where the tableau stands: its status or a negative HIP
+// error, stats[1] += its pivots.  Under LP_DUAL_RATIO_LONG_STEP the loop flips too: bd.flips counts since the last
+// install's memset (bounded_run_from_start relies on that for the install's own loop), so it is zeroed on the stream
+// ahead of the loop and stats[3] += this loop's flips alone, whatever ran since that install.  The textbook loop
+// queues what it always queued.
+int mip_large_child_loop(MipLargeCall& k, int* stats) {
+    lp_simplex_problem* p = k.owner.get();
+    const bool flipping = k.dual_ratio == LP_DUAL_RATIO_LONG_STEP;
+    if (flipping) LP_HIP(p->ctx, hipMemsetAsync(k.bd.flips, 0, sizeof(int), p->ctx->stream));
+    int iters = 0, flips = 0;
+    const int st = run_bounded_phase(p, k.bd, LP_PIVOT_DANTZIG, k.eps, k.max_iter, &iters, &flips, true, LP_DUAL_DANTZIG,
+                                     k.dual_ratio);
+    if (st < 0) return st;
+    stats[1] += iters;
+    if (flipping) stats[3] += flips;
+    return st;
+}
 
 // Step 8 of the reference: the status and, where one is defined (*bound is left alone otherwise), the bound.  Open are
 // the abandoned nodes (have_ab, zab), the records whose second child was not taken and, after a stop, the one on top.
@@ -235,11 +255,15 @@ int mip_large_verdict(const std::vector<MipRecord>& rec, int top, int stop, int 
 // whether it survives are those of L mod K); a second child whose slot still belongs to its level is restored from it
 // and continues like a first child, with one sync for its bound change and none of the rebuild's work.
 // stats_out: nstats entries, 5 (the counters of the reference) or 7 (then the second children restored and rebuilt).
+// dual_ratio (tests/ref/mip_bounded_long_step_ref.c): the ratio test of every dual loop, the install's, a first
+// child's and a restored second child's; under LP_DUAL_RATIO_LONG_STEP stats[3] counts their flips too.  A snapshot is
+// queued before the child's loop and the flags of a restored node come from the level's record, which the node kernel
+// wrote before the bound change, so the flips of a child's loop are in neither.
 int mip_large_search(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c, const double* lo,
                      const double* hi, const int* basis_in, const int* at_upper_in, int maximize, int n_orig,
                      const int* integer, double eps, double int_tol, double gap, int max_depth, int max_nodes,
                      int max_iter, double* x_out, double* obj_out, double* bound_out, int* found_out, int* stats_out,
-                     int nstats, int snapshots) {
+                     int nstats, int snapshots, int dual_ratio) {
     const char* who = "lp_mip_bounded_solve_large";
     const bool any_null = !x_out || !obj_out || !bound_out || !found_out || !stats_out || !A || !b || !c || !lo || !hi ||
                           !basis_in || !at_upper_in || !integer;
@@ -261,7 +285,7 @@ int mip_large_search(lp_context* ctx, const double* A, int m, int n, const doubl
     k.owner.reset(p);
     rc = lp_bounded_large_prepare(p, LP_PIVOT_DANTZIG);
     if (rc) return rc;
-    rc = lp_bounded_dual_prepare(p);
+    rc = lp_bounded_dual_prepare(p, LP_DUAL_DANTZIG, dual_ratio);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     BoundedLargeDev& bd = k.bd;
@@ -290,7 +314,7 @@ int mip_large_search(lp_context* ctx, const double* A, int m, int n, const doubl
     LP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
     LP_HIP(ctx, hipMemcpyAsync(dc, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     LP_HIP(ctx, hipMemcpyAsync(dmask, integer, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-    k.A = A; k.c = c; k.eps = eps; k.max_iter = max_iter;
+    k.A = A; k.c = c; k.eps = eps; k.max_iter = max_iter; k.dual_ratio = dual_ratio;
     const int K = std::min(snapshots, max_depth);
     const size_t slot_bytes = lp_mip_large_slot_bytes(m, n);
     k.slots = std::vector<lp_device_buffer>((size_t)K);
@@ -354,10 +378,8 @@ int mip_large_search(lp_context* ctx, const double* A, int m, int n, const doubl
                     if (r.un_negative) {
                         st = LP_INFEASIBLE;   // without a pivot
                     } else {
-                        int iters = 0, flips = 0;
-                        st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+                        st = mip_large_child_loop(k, stats);
                         if (st < 0) return st;
-                        stats[1] += iters;
                     }
                     backtrack = false;
                 }
@@ -386,10 +408,8 @@ int mip_large_search(lp_context* ctx, const double* A, int m, int n, const doubl
                 if (r.un_negative) {
                     st = LP_INFEASIBLE;   // without a pivot
                 } else {
-                    int iters = 0, flips = 0;
-                    st = run_bounded_phase(p, bd, LP_PIVOT_DANTZIG, eps, max_iter, &iters, &flips, true);
+                    st = mip_large_child_loop(k, stats);
                     if (st < 0) return st;
-                    stats[1] += iters;
                 }
                 continue;
             }
@@ -632,7 +652,8 @@ int lp_mip_bounded_solve_large(lp_context* ctx, const double* A, int m, int n, c
                                int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
                                double* bound_out, int* found_out, int* stats_out) {
     return mip_large_search(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, integer, eps, int_tol,
-                            gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, 5, 0);
+                            gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, 5, 0,
+                            LP_DUAL_RATIO_TEXTBOOK);
 }
 
 // The same with up to `snapshots` tableau snapshots (tests/ref/mip_bounded_snapshots_ref.c): 0 launches what the entry
@@ -642,12 +663,28 @@ int lp_mip_bounded_solve_large_ex(lp_context* ctx, const double* A, int m, int n
                                   int maximize, int n_orig, const int* integer, double eps, double int_tol, double gap,
                                   int max_depth, int max_nodes, int max_iter, double* x_out, double* obj_out,
                                   double* bound_out, int* found_out, int* stats_out, int snapshots) {
+    return lp_mip_bounded_solve_large_ratio_ex(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig,
+                                               integer, eps, int_tol, gap, max_depth, max_nodes, max_iter, x_out, obj_out,
+                                               bound_out, found_out, stats_out, snapshots, LP_DUAL_RATIO_TEXTBOOK);
+}
+
+// The same with a choice of the ratio test of the search's dual loops (tests/ref/mip_bounded_long_step_ref.c): an
+// unknown dual_ratio is refused before anything else is looked at; LP_DUAL_RATIO_TEXTBOOK launches what the entry above
+// launches, LP_DUAL_RATIO_LONG_STEP the selector k_simplex_select_dual_bounded_long in every dual loop.
+int lp_mip_bounded_solve_large_ratio_ex(lp_context* ctx, const double* A, int m, int n, const double* b, const double* c,
+                                        const double* lo, const double* hi, const int* basis_in, const int* at_upper_in,
+                                        int maximize, int n_orig, const int* integer, double eps, double int_tol,
+                                        double gap, int max_depth, int max_nodes, int max_iter, double* x_out,
+                                        double* obj_out, double* bound_out, int* found_out, int* stats_out,
+                                        int snapshots, int dual_ratio) {
     if (!ctx) return LP_BAD_ARG;
+    if (!lp_dual_ratio_known(dual_ratio))
+        LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_large: unknown dual ratio test");
     if (snapshots < 0 || snapshots > LP_MIP_BOUNDED_MAX_SNAPSHOTS)
         LP_FAIL(ctx, LP_BAD_ARG, "lp_mip_bounded_solve_large: snapshots outside [0, 1024]");
     return mip_large_search(ctx, A, m, n, b, c, lo, hi, basis_in, at_upper_in, maximize, n_orig, integer, eps, int_tol,
                             gap, max_depth, max_nodes, max_iter, x_out, obj_out, bound_out, found_out, stats_out, 7,
-                            snapshots);
+                            snapshots, dual_ratio);
 }
 
 // The device bytes `snapshots` slots take at m x n: each the (m+1) x ld tableau (ld = n + 1 rounded up to 8) and two

@@ -437,6 +437,25 @@ public:
                              snapshots);
     }
 
+    // The searches above under a dual ratio test (lp_mip_bounded_solve_ratio_ex, lp_mip_bounded_solve_large_ratio_ex):
+    // `ratio` governs the entering step of every dual simplex run of the search, the root's, a first child's and a
+    // second child's, rebuilt or restored.  DualRatio::Textbook is the form without it in every value; under
+    // DualRatio::LongStep node order, branching and pruning are unchanged and the objective agrees within MIP_GAP plus
+    // rounding wherever both searches finish.  Pricing stays Dantzig's.
+    IntegerResult boundedBranchAndBound(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                        const std::vector<double>& hi, const BoundedResult& from, int maxDepth,
+                                        int maxNodes, DualRatio ratio) const {
+        return boundedSearch("Solver::boundedBranchAndBound", integer, lo, hi, from, maxDepth, maxNodes, false, -1,
+                             &ratio);
+    }
+
+    IntegerResult boundedBranchAndBoundLarge(const std::vector<bool>& integer, const std::vector<double>& lo,
+                                             const std::vector<double>& hi, const BoundedResult& from, int maxDepth,
+                                             int maxNodes, int snapshots, DualRatio ratio) const {
+        return boundedSearch("Solver::boundedBranchAndBoundLarge", integer, lo, hi, from, maxDepth, maxNodes, true,
+                             snapshots, &ratio);
+    }
+
     // Evidence for a result that is not optimal (lp_basis_certificate) at its final basis, with EPS and the problem's
     // sense.  A basis index n+i is row i's artificial, so the phase-I basis of an infeasible twoPhaseSimplex_ex(false)
     // result passes as it is.  kind LP_CERT_FARKAS: A^T farkas >= -EPS and b.farkas = value < 0 (no x >= 0 solves
@@ -817,10 +836,11 @@ private:
     }
 
     // boundedBranchAndBound, or with large boundedBranchAndBoundLarge, from a result's basis and flags; snapshots >= 0
-    // (large only): the _ex entry with that many snapshots
+    // (large only): the _ex entry with that many snapshots; ratio: the _ratio_ex entries (large: snapshots as given, a
+    // negative count refused by the entry)
     IntegerResult boundedSearch(const char* who, const std::vector<bool>& integer, const std::vector<double>& lo,
                                 const std::vector<double>& hi, const BoundedResult& from, int maxDepth, int maxNodes,
-                                bool large, int snapshots = -1) const {
+                                bool large, int snapshots = -1, const DualRatio* ratio = nullptr) const {
         const View p = view();
         IntegerResult out = blankIntegerResult(from.status, p.no);
         if (from.status != LP_OPTIMAL) return out;
@@ -830,7 +850,17 @@ private:
         const std::vector<int> mask(integer.begin(), integer.end());
         lp_context* ctx = lpgpu::context(_device);
         int found = 0, stats[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (large && snapshots >= 0) {
+        if (ratio && large) {
+            out.status = checked(lp_mip_bounded_solve_large_ratio_ex(
+                ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(), from.atUpper.data(), p.maximize,
+                p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER, out.x.data(), &out.objective,
+                &out.bound, &found, stats, snapshots, (int)*ratio), ctx);
+        } else if (ratio) {
+            out.status = checked(lp_mip_bounded_solve_ratio_ex(
+                ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(), from.atUpper.data(), p.maximize,
+                p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER, out.x.data(), &out.objective,
+                &out.bound, &found, stats, (int)*ratio), ctx);
+        } else if (large && snapshots >= 0) {
             out.status = checked(lp_mip_bounded_solve_large_ex(
                 ctx, p.A, p.m, p.n, p.b, p.c, lo.data(), hi.data(), from.basis.data(), from.atUpper.data(), p.maximize,
                 p.no, mask.data(), EPS, INT_TOL, MIP_GAP, maxDepth, maxNodes, MAX_ITER, out.x.data(), &out.objective,
